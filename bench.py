@@ -25,8 +25,9 @@ be 720 GB) -- with pairs = stored pairs, the roofline on the stored-pair bytes, 
 baseline on the same block structure at 50 kb.
 
 Order of the measurements: convergence legs, read sweep, --settle-ms of untimed iterations
-(the chip's clocks need load to settle), W warm-up steps, the K timed
-steps (`value`, `ms_per_step`, `roofline`), then --reps more K-step blocks for the spread.
+(the chip's clocks need load to settle), W warm-up steps from X0, the K
+timed steps (`value`, `ms_per_step`, `roofline`; --dump-outputs DIR writes what they computed),
+then --reps more K-step blocks for the spread.
 
 Prints ONE JSON line on rank 0.  `roofline` prices the dominant kernel
 (stress_grad_kernel) by its ALGORITHMIC bytes -- 4 B (one fp32 wish distance)
@@ -101,7 +102,15 @@ def parse():
                          "back (one sync + D2H, ~30 us) every this many steps, as fit(tol=..., "
                          "check_every=...) does; at N=50k a step is 0.8 ms, so checking every "
                          "step costs less than stopping up to k-1 steps late")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed block computed -- the coordinates after its last "
+                         "step (structure.npy) and the stress of each of its steps (stress.npy), "
+                         "float64 -- to DIR, at most 64 MB in all (a seeded sample of rows "
+                         "beyond that).  The timed block starts from the same seeded inputs on "
+                         "every run, so two builds can be compared output for output")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.bins is None:
         a.bins = 50000 if a.workload == "dense" else 309568
     if a.cpu_bins is None:
@@ -146,6 +155,29 @@ def self_launch(a):
 def random_walk(n, seed=0):
     x = numpy.cumsum(numpy.random.default_rng(seed).standard_normal((n, 3)), axis=0)
     return x - x.mean(axis=0)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write each array as <directory>/<name>.npy in float64.  If together they exceed
+    `limit`, every array keeps the same share of its rows, a sorted sample drawn with a
+    fixed seed, so that two runs of the same arguments write the same rows.  Returns
+    {name: shape written}."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: numpy.asarray(v, dtype=numpy.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    header = 128 * len(arrays)                     # .npy header per file
+    written = {}
+    for name, v in arrays.items():
+        if total + header > limit and v.shape[0] > 1:
+            keep = max(1, v.shape[0] * (limit - header) // total)
+            rows = numpy.random.default_rng(0).choice(v.shape[0], keep, replace=False)
+            v = v[numpy.sort(rows)]
+        numpy.save(os.path.join(directory, name + ".npy"), numpy.ascontiguousarray(v))
+        written[name] = list(v.shape)
+    return written
 
 
 def host_cores():
@@ -521,6 +553,9 @@ def main():
     for _ in range(n_settle if a.settle_ms > 0 else 0):
         steps(blk)                           # untimed; speed does not depend on the state
         eng.sync()                           # (tools/state_probe.py), clocks do on the load
+    # how many settle blocks ran depends on the clock: start the warm-up and the timed block
+    # from X0 again, so that what they compute depends on the arguments alone (--dump-outputs)
+    eng.set_coords(x0)
     steps(a.warmup)
     fence()
     # HIP events on a sample of the steps of the timed region: three records cost ~10 us of
@@ -536,6 +571,11 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     tim = eng.timing()
+    outputs = None
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path receives (StructureSolver's structure_ / stress_):
+        # the coordinates after the last timed step, the stress of each timed step
+        outputs = {"structure": eng.get_coords(), "stress": eng.stress_history()[-a.steps:]}
     # For the record: what two HIP events recorded back to back cost on this stream.  Every
     # event-timed interval of a sampled step contains a part of that (rocprofv3's dispatch
     # durations of the same kernels come out 2-4 us shorter), which is why kernel_ms +
@@ -683,6 +723,9 @@ def main():
             out["cpu_baseline"] = (cpu_baseline(a.cpu_bins, a.cpu_iters) if tiles is None else
                                    cpu_baseline_genome(a.cpu_bins, max(1, a.band_bins * a.cpu_bins // n),
                                                        a.cpu_iters))
+        if outputs is not None:
+            out["dump_outputs"] = {"dir": a.dump_outputs,
+                                   "arrays": dump_outputs(a.dump_outputs, outputs)}
         print(json.dumps(out))
     if use_dist:
         dist.barrier()

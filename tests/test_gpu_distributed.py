@@ -238,22 +238,30 @@ def test_config4_size_two_ranks_over_the_peer_exchange():
     assert h1[-1] < h1[0]
 
 
+@pytest.fixture(autouse=True)
+def _no_rank_process_outlives_its_test():
+    yield
+    from tests import _ranks
+    _ranks.close_all()
+
+
+def _set_wish(eng, wish):
+    eng.set_wish_dense(wish() if callable(wish) else wish, "wish", 3.0)
+
+
+def _peer_ranks(world, n, dtype, tiles=None):
+    """`world` ranks, a process each (tests/_ranks.py), their receive arenas connected
+    through IPC handles as a job of several processes connects them."""
+    from tests import _ranks
+    return _ranks.peer_ranks(world, n, dtype, tiles)
+
+
 def _peer_engines(world, n, dtype, wish, x0, mu=0.0):
-    """`world` ranks inside this process, one HipEngine (own stream) each, their
-    receive arenas connected directly (same-process shortcut of peer_connect)."""
-    import ctypes
-    from blueberry_amd import _lib
-    from blueberry_amd.solver import HipEngine
-    lib = _lib.load()
-    engs = [HipEngine(n, dtype, rank=r, world=world) for r in range(world)]
-    blobs = []
+    """_peer_ranks with the wish matrix, X0 and momentum set.  `wish`: the matrix, or a
+    function that makes it (called in every rank's process: nothing large is sent)."""
+    engs = _peer_ranks(world, n, dtype)
     for e in engs:
-        buf = ctypes.create_string_buffer(_lib.BB_PEER_HANDLE_BYTES)
-        _lib.check(lib.bb_solver_peer_export(e._h, buf), "export")
-        blobs.append(buf.raw)
-    for e in engs:
-        _lib.check(lib.bb_solver_peer_connect(e._h, b"".join(blobs)), "connect")
-        e.set_wish_dense(wish, "wish", 3.0)
+        e.run(_set_wish, wish)
         e.set_coords(x0)
         e.set_momentum(mu)
     return engs
@@ -263,7 +271,8 @@ def _peer_engines(world, n, dtype, wish, x0, mu=0.0):
 @pytest.mark.parametrize("dtype,tol,world", [("float32", 1e-5, 2), ("float64", 1e-12, 2),
                                              ("float32", 1e-5, 3)])
 def test_peer_exchange_in_one_process(dtype, tol, world, form, monkeypatch):
-    """Ranks on separate streams of one process: every iteration of every rank is
+    """Ranks on one GPU, a process each (tests/_ranks.py says why not one process): every
+    iteration of every rank is
     enqueued up front, the kernels meet through the arenas' flags.  Both forms of the
     exchange (include/blueberry_hip.h): reduce + push + wait + sum + update in one launch,
     workgroup by workgroup, and the two launches with one flag per rank."""
@@ -320,8 +329,8 @@ def test_peer_exchange_forms_agree_bit_for_bit_over_a_long_run(monkeypatch):
         monkeypatch.setenv("BB_PEER_FUSED", "1" if form == "one launch" else "0")
         engs = _peer_engines(world, n, "float32", w, x0, mu=0.3)
         assert engs[0].peer_form() == form
-        # in turns and in small pieces: the ranks of ONE process share its host thread, and a
-        # rank whose launch queue is full would block the thread that feeds the ranks it waits for
+        # in turns and in small pieces: ONE host thread feeds the ranks, and a rank whose
+        # launch queue is full would block the thread that feeds the ranks it waits for
         for chunk in (1, 99) + (100,) * 5:
             for e in engs:
                 e.iterate_peer(chunk, 1.0 / (2 * n))
@@ -471,10 +480,6 @@ def test_peer_exchange_contributor_mask_changes_no_bit(form, monkeypatch):
     monkeypatch.setenv("BB_PEER_FUSED", "1" if form == "one launch" else "0")
     from blueberry_amd.solver import tiles_from_blocks
     from tests import _oracle
-    import ctypes
-    from blueberry_amd import _lib
-    from blueberry_amd.solver import HipEngine
-    lib = _lib.load()
     world, k = 3, 5
     for n, tiles in ((2600, None), (3100, tiles_from_blocks(3100, [0, 1500, 2300, 3100], 100, "float32")[0])):
         xs = _oracle.random_walk(n)
@@ -483,14 +488,8 @@ def test_peer_exchange_contributor_mask_changes_no_bit(form, monkeypatch):
         out = {}
         for setting in ("1", "0"):
             monkeypatch.setenv("BB_PEER_MASK", setting)
-            engs = [HipEngine(n, "float32", rank=r, world=world, tiles=tiles) for r in range(world)]
-            blobs = []
+            engs = _peer_ranks(world, n, "float32", tiles)
             for e in engs:
-                buf = ctypes.create_string_buffer(_lib.BB_PEER_HANDLE_BYTES)
-                _lib.check(lib.bb_solver_peer_export(e._h, buf), "export")
-                blobs.append(buf.raw)
-            for e in engs:
-                _lib.check(lib.bb_solver_peer_connect(e._h, b"".join(blobs)), "connect")
                 e.set_wish_from_coords(xs)
                 e.set_coords(x0)
                 e.set_momentum(0.3)
@@ -508,28 +507,24 @@ def test_peer_exchange_contributor_mask_changes_no_bit(form, monkeypatch):
 
 
 def test_eight_ranks_over_the_peer_exchange_in_one_process():
-    """World size 8 -- what the scaling run uses -- rehearsed on one GPU: eight ranks of ONE
-    process (more than the six processes a box allows on its GPU), arenas connected directly,
-    random call sequences of tools/peer_sequence_fuzz.py (iterate_peer, the spectral start,
-    per-bin steps, the two-call path) against the one-rank model; ranks bit-identical after
-    every call.  Needs more hardware queues than the HIP runtime's default of four (streams
-    that share a queue deadlock when one waits for the other), hence a process of its own
-    with GPU_MAX_HW_QUEUES set; the one-launch form keeps to a size whose waiting workgroups
-    of all eight ranks fit one chip (the tool says why)."""
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="32", BB_FUZZ_WORLDS="8,5", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    """World size 8 -- what the scaling run uses -- rehearsed on one GPU: eight ranks (two
+    to a process, tests/_ranks.py), random call sequences of tools/peer_sequence_fuzz.py
+    (iterate_peer, the spectral start, per-bin steps, the two-call path) against the one-rank
+    model; ranks bit-identical after every call.  The one-launch form keeps to a size whose
+    waiting workgroups of all eight ranks fit one chip (the tool says why)."""
+    env = dict(os.environ, BB_FUZZ_WORLDS="8,5", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "peer_sequence_fuzz.py"), "12", "7"],
-                       capture_output=True, text=True, timeout=600, env=env)
+                       capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0 and "FAILURES: 0" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
     assert "world=8" in r.stdout or "world=5" in r.stdout
 
 
 def test_world_size_eight_at_full_sizes_on_one_gpu():
-    """The scaling run's world size at BASELINE's sizes: eight ranks of one process, each with
-    its 1/8 share of the units of the headline map (N = 50,000 dense fp32) and of config 5
+    """The scaling run's world size at BASELINE's sizes: eight ranks (two to a process), each
+    with its 1/8 share of the units of the headline map (N = 50,000 dense fp32) and of config 5
     (N = 309,568 block-sparse), iterate over the peer exchange and end where ONE rank ends
-    (1e-5; measured 6e-8), bit-identical among themselves (tools/world8_rehearsal.py; a
-    process of its own for the hardware queues)."""
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="32", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    (1e-5; measured 6e-8), bit-identical among themselves (tools/world8_rehearsal.py)."""
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "world8_rehearsal.py")],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0 and "world-8 rehearsal ok" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
@@ -590,6 +585,14 @@ class _CountingLib(object):
         return fn
 
 
+def _count_moving_calls(eng):
+    eng._lib = _CountingLib(eng._lib)
+
+
+def _moving_calls(eng):
+    return eng._lib.counts
+
+
 @pytest.mark.parametrize("form", ["one launch", "two launches"])
 @pytest.mark.parametrize("dtype,tol,world", [("float64", 1e-12, 2), ("float32", 1e-5, 3)])
 def test_block_steps_on_several_ranks(dtype, tol, world, form, monkeypatch):
@@ -618,7 +621,7 @@ def test_block_steps_on_several_ranks(dtype, tol, world, form, monkeypatch):
     assert all(e.peer_form() == form for e in engs)
     for e in engs:
         e.set_block_steps(scale)
-    for _ in range(k):                                # ranks of one process: step by step
+    for _ in range(k):                                # ranks fed by one thread: step by step
         for e in engs:
             e.iterate_peer(1, lr)
     Xs = [e.get_coords() for e in engs]
@@ -647,7 +650,7 @@ def test_block_steps_on_several_ranks(dtype, tol, world, form, monkeypatch):
 @pytest.mark.parametrize("form", ["one launch", "two launches"])
 @pytest.mark.parametrize("dtype,tol,world", [("float64", 1e-12, 2), ("float32", 1e-5, 3)])
 def test_multi_rank_spectral_start_stays_on_the_device(dtype, tol, world, form, monkeypatch):
-    """init='spectral' on several ranks.  `world` ranks of this process, their
+    """init='spectral' on several ranks.  `world` ranks, a process each, their
     arenas connected, each driven by a thread of its own (the start synchronises at its end;
     the ranks' kernels meet in the exchange): the per-rank products of the block power
     iteration are summed through the peer exchange ON THE DEVICE -- no (N, 3) array crosses
@@ -678,7 +681,7 @@ def test_multi_rank_spectral_start_stays_on_the_device(dtype, tol, world, form, 
     engs = _peer_engines(world, n, dtype, w, v0)
     assert all(e.peer_form() == form for e in engs)
     for e in engs:
-        e._lib = _CountingLib(e._lib)
+        e.run(_count_moving_calls)
     errs = []
 
     def run(e):
@@ -695,7 +698,8 @@ def test_multi_rank_spectral_start_stays_on_the_device(dtype, tol, world, form, 
     assert not errs, errs
     for e in engs:
         assert e.peer_status() == 0
-        assert e._lib.counts == {}, e._lib.counts   # nothing of size N moved during the start
+        moved = e.run(_moving_calls)
+        assert moved == {}, moved                     # nothing of size N moved during the start
     Xs = [e.get_coords() for e in engs]
     for X in Xs:
         assert numpy.abs(X - X1).max() < tol * numpy.abs(X1).max()

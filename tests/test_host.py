@@ -486,6 +486,29 @@ def test_bench_self_launch_relays_rank0_line(tmp_path):
     assert r.returncode != 0                                       # a rank's failure is relayed
 
 
+def test_bench_dump_outputs_fit_the_limit_and_sample_the_same_rows(tmp_path):
+    """bench.py --dump-outputs: float64 .npy files, at most the limit in all; beyond it a
+    sample of rows that is the same on every run."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    X = numpy.random.default_rng(5).standard_normal((1000, 3)).astype(numpy.float32)
+    h = numpy.linspace(2.0, 1.0, 40)
+    small = bench.dump_outputs(str(tmp_path / "all"), {"structure": X, "stress": h})
+    assert small == {"structure": [1000, 3], "stress": [40]}
+    got = numpy.load(str(tmp_path / "all" / "structure.npy"))
+    assert got.dtype == numpy.float64 and numpy.array_equal(got, X.astype(numpy.float64))
+    limit = 8192
+    for d in ("a", "b"):
+        w = bench.dump_outputs(str(tmp_path / d), {"structure": X, "stress": h}, limit=limit)
+        assert 0 < w["structure"][0] < 1000 and w["structure"][1] == 3
+        assert sum(os.path.getsize(str(tmp_path / d / f)) for f in os.listdir(str(tmp_path / d))) <= limit
+    a, b = (numpy.load(str(tmp_path / d / "structure.npy")) for d in ("a", "b"))
+    assert numpy.array_equal(a, b)
+    rows = [int(numpy.nonzero((X.astype(numpy.float64) == r).all(1))[0][0]) for r in a]
+    assert rows == sorted(set(rows))             # distinct rows of X, in their order
+
+
 def test_n_iter_beyond_the_device_history_is_refused_up_front():
     import blueberry_amd as bb
     with pytest.raises(ValueError, match="2\\*\\*20"):

@@ -1,13 +1,11 @@
-"""World size 8 at BASELINE's full sizes on ONE GPU: eight ranks of this process (one solver,
-one stream each; arenas connected directly), each holding its 1/8 share of the units, iterate
+"""World size 8 at BASELINE's full sizes on ONE GPU: eight ranks (one solver each, two to a
+process: tests/_ranks.py), each holding its 1/8 share of the units, iterate
 over the peer exchange (two-launch form: the form ranks that share a GPU use) -- the headline
 map (N = 50,000 dense fp32) and config 5 (N = 309,568 block-sparse) -- and must end where ONE
 rank ends (1e-5), bit-identical among themselves.  What this cannot show is time: eight
-ranks on one chip take turns.  Start with GPU_MAX_HW_QUEUES >= 16 (tools/peer_sequence_fuzz.py
-says why).
+ranks on one chip take turns.
 
-    GPU_MAX_HW_QUEUES=32 python tools/world8_rehearsal.py [dense|genome10kb ...]"""
-import ctypes
+    python tools/world8_rehearsal.py [dense|genome10kb ...]"""
 import os
 import sys
 import time
@@ -17,10 +15,9 @@ import numpy
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 os.environ.setdefault("BB_PEER_FUSED", "0")
 os.environ.setdefault("BB_PEER_TIMEOUT_MS", "60000")
-from blueberry_amd import _lib                                            # noqa: E402
-from blueberry_amd.solver import HipEngine, max_degree, tiles_from_blocks  # noqa: E402
+from blueberry_amd.solver import max_degree, tiles_from_blocks            # noqa: E402
 from blueberry_amd.utils import genome_boundaries                          # noqa: E402
-from tests import _oracle                                                  # noqa: E402
+from tests import _oracle, _ranks                                          # noqa: E402
 
 WORLD, K = 8, 4
 
@@ -35,7 +32,7 @@ def run(workload):
         lr = 1.0 / (2 * max_degree(n, tiles, "float32"))
     xs = _oracle.random_walk(n)
     x0 = _oracle.noisy_init(xs)
-    one = HipEngine(n, "float32", tiles=tiles)
+    one, = _ranks.start(1, n, "float32", tiles)     # a process that ends before the 8 start
     one.set_wish_from_coords(xs)
     one.set_coords(x0)
     one.set_momentum(0.3)
@@ -43,17 +40,11 @@ def run(workload):
     X1, h1 = one.get_coords(), one.stress_history()
     n_units = one.layout()["n_units"]
     one.close()
-    lib = _lib.load()
-    engs = [HipEngine(n, "float32", rank=r, world=WORLD, tiles=tiles) for r in range(WORLD)]
+    engs = _ranks.start(WORLD, n, "float32", tiles)
     shares = [e.layout()["u_end"] - e.layout()["u_begin"] for e in engs]
     assert sum(shares) == n_units and max(shares) - min(shares) <= 1, shares
-    blobs = []
+    _ranks.connect(engs)
     for e in engs:
-        buf = ctypes.create_string_buffer(_lib.BB_PEER_HANDLE_BYTES)
-        _lib.check(lib.bb_solver_peer_export(e._h, buf), "export")
-        blobs.append(buf.raw)
-    for e in engs:
-        _lib.check(lib.bb_solver_peer_connect(e._h, b"".join(blobs)), "connect")
         e.set_wish_from_coords(xs)
         e.set_coords(x0)
         e.set_momentum(0.3)
