@@ -137,8 +137,7 @@ __device__ __forceinline__ void nt_store(double *p, double v) { *p = v; }
 #else
 __device__ __forceinline__ void nt_store(double *p, double v) { __builtin_nontemporal_store(v, p); }
 #endif
-// kNT = tile edge (128: one 1024-thread workgroup per CU; 64: 512 threads, up to four per CU)
-template <int kNT>
+constexpr int kNT = 128;   // tile edge: one 1024-thread workgroup per CU
 __global__ __launch_bounds__(kNT * 8) void normalize128_kernel(double *m, int64_t d, int64_t n_bins,
                                                                const double *__restrict__ kr,
                                                                const double *__restrict__ krexp,
@@ -327,80 +326,9 @@ __global__ __launch_bounds__(256) void gather_kernel(const double *__restrict__ 
 }
 
 // ---- eigenvector (datatypes.pyx:216-235): Lanczos on the resident matrix -----------
-// y = M x.  One wave takes kSymvRows consecutive rows (a workgroup 4 waves), so x is
-// loaded once per kSymvRows row loads, and reads them as 16-byte elements: a row starts on
-// a 16-byte boundary or 8 bytes past one (odd d: every other row), so each row gets its
-// own one-element head and its pairs are {x[2c+o], x[2c+o+1]} with o = 0 or 1.  kSymvUnroll
-// wave loads of 1 KiB per row in flight; fixed summation order; HBM-bound, 8 B per element.
-constexpr int kSymvRows = 4, kSymvUnroll = 4;
-__global__ __launch_bounds__(256) void symv_kernel(const double *__restrict__ m, int64_t d,
-                                                   const double *__restrict__ x,
-                                                   double *__restrict__ y) {
-    typedef double d2 __attribute__((ext_vector_type(2)));
-    const int lane = threadIdx.x & 63;
-    const int64_t row0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * kSymvRows;
-    if (row0 >= d) return;
-    const d2 *p2[kSymvRows];
-    int off[kSymvRows];
-    double acc[kSymvRows];
-#pragma unroll
-    for (int r = 0; r < kSymvRows; ++r) {
-        const int64_t row = row0 + r < d ? row0 + r : d - 1;      // a ragged last group re-reads row d-1
-        const double *p = m + row * d;
-        off[r] = (int)((row * d) & 1);
-        p2[r] = reinterpret_cast<const d2 *>(p + off[r]);
-        acc[r] = (off[r] && lane == 0) ? p[0] * x[0] : 0.0;        // the head element
-    }
-    const int64_t n2 = (d - 1) / 2;      // pairs every row has after its head, whatever its o
-    int64_t c = lane;
-    for (; c + 64 * (kSymvUnroll - 1) < n2; c += 64 * kSymvUnroll) {
-        d2 a[kSymvRows][kSymvUnroll];
-        double x0[kSymvUnroll], x1[kSymvUnroll], x2[kSymvUnroll];
-#pragma unroll
-        for (int q = 0; q < kSymvUnroll; ++q) {
-#pragma unroll
-            for (int r = 0; r < kSymvRows; ++r)
-                a[r][q] = __builtin_nontemporal_load(p2[r] + c + 64 * q);
-            const int64_t e = 2 * (c + 64 * q);
-            x0[q] = x[e]; x1[q] = x[e + 1]; x2[q] = x[e + 2];      // e + 2 <= 2 n2 <= d - 1
-        }
-#pragma unroll
-        for (int q = 0; q < kSymvUnroll; ++q)
-#pragma unroll
-            for (int r = 0; r < kSymvRows; ++r) {
-                acc[r] = fma(a[r][q].x, off[r] ? x1[q] : x0[q], acc[r]);
-                acc[r] = fma(a[r][q].y, off[r] ? x2[q] : x1[q], acc[r]);
-            }
-    }
-    for (; c < n2; c += 64) {
-        const int64_t e = 2 * c;
-#pragma unroll
-        for (int r = 0; r < kSymvRows; ++r) {
-            const d2 v = p2[r][c];
-            acc[r] = fma(v.x, x[e + off[r]], acc[r]);
-            acc[r] = fma(v.y, x[e + off[r] + 1], acc[r]);
-        }
-    }
-    // what is left of a row behind its n2 pairs: elements off + 2 n2 .. d - 1 (at most 2)
-    if (lane == 0) {
-#pragma unroll
-        for (int r = 0; r < kSymvRows; ++r) {
-            const int64_t row = row0 + r < d ? row0 + r : d - 1;
-            for (int64_t e = off[r] + 2 * n2; e < d; ++e) acc[r] = fma(m[row * d + e], x[e], acc[r]);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < kSymvRows; ++r) {
-        double v = acc[r];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-        if (lane == 0 && row0 + r < d) y[row0 + r] = v;
-    }
-}
-
-// ---- the same product from the UPPER triangle alone (round 3) ------------------------
-// symv_kernel reads both triangles of a symmetric matrix: 8 B per element where 8 B per
-// PAIR would do (4.25 TB/s, 53 % of peak, on its own accounting).  Here element (i, j),
+// y = M x from the UPPER triangle alone (round 3).  Reading both triangles of a symmetric
+// matrix costs 8 B per element where 8 B per PAIR will do (round 2's kernel did that: 4.25
+// TB/s, 53 % of peak, on its own accounting).  Here element (i, j),
 // j >= i, is read once and serves both ends, y_i += m_ij x_j and y_j += m_ij x_i -- the
 // pattern of the solver's sweep (kOpMatvec2).  The matrix is taken to be symmetric, as the
 // reference's eigsh call takes it (datatypes.pyx:234) and as every ContactMap is built.
@@ -1120,30 +1048,20 @@ int bb_cm_normalize(bb_cm *cm, int64_t n_bins, const double *KRnorm, const doubl
         if (e == hipSuccess)
             e = hipMemcpyAsync(ke.p, KRexpected, (size_t)n_bins * sizeof(double), hipMemcpyHostToDevice, st);
     }
-    const char *env = getenv("BB_CM_NORMALIZE_TILE");
-    const int tile = env ? atoi(env) : 128;
-    const bool big = tile != 32 && d >= 256;              // small maps: more, smaller tiles
-    if (e == hipSuccess && big) {
-        const int nt_edge = tile == 64 ? 64 : 128;
-        const int lds = nt_edge * (nt_edge + 1) * 8;
-        const uint64_t nt = (uint64_t)((d + nt_edge - 1) / nt_edge), pairs = nt * (nt + 1) / 2;
-        static bool attr_done[2] = {false, false};
-        const void *fn = nt_edge == 64 ? (const void *)normalize128_kernel<64>
-                                       : (const void *)normalize128_kernel<128>;
-        if (!attr_done[nt_edge == 64]) {
-            e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            attr_done[nt_edge == 64] = e == hipSuccess;
+    if (e == hipSuccess && d >= 256) {                    // small maps: more, smaller tiles
+        const int lds = kNT * (kNT + 1) * 8;
+        const uint64_t nt = (uint64_t)((d + kNT - 1) / kNT), pairs = nt * (nt + 1) / 2;
+        static bool attr_done = false;
+        if (!attr_done) {
+            e = hipFuncSetAttribute((const void *)normalize128_kernel,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            attr_done = e == hipSuccess;
         }
         int cus = 256;
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cm->device);
-        const char *envw = getenv("BB_CM_NORMALIZE_WGS");
-        const uint64_t per_cu = envw ? (uint64_t)atoi(envw) : (nt_edge == 64 ? 4 : 1);
-        const unsigned grid = (unsigned)std::min<uint64_t>(pairs, (uint64_t)cus * per_cu);
-        if (e == hipSuccess && nt_edge == 64)
-            e = bb::launch(normalize128_kernel<64>, dim3(grid), dim3(512), (size_t)lds, st, cm->m, d, n_bins,
-                           (const double *)kr.p, (const double *)ke.p, (unsigned)pairs);
-        else if (e == hipSuccess)
-            e = bb::launch(normalize128_kernel<128>, dim3(grid), dim3(1024), (size_t)lds, st, cm->m, d,
+        const unsigned grid = (unsigned)std::min<uint64_t>(pairs, (uint64_t)cus);
+        if (e == hipSuccess)
+            e = bb::launch(normalize128_kernel, dim3(grid), dim3(kNT * 8), (size_t)lds, st, cm->m, d,
                            n_bins, (const double *)kr.p, (const double *)ke.p, (unsigned)pairs);
     } else if (e == hipSuccess) {
         const uint64_t nt = (uint64_t)((d + kT - 1) / kT);
@@ -1240,12 +1158,7 @@ int bb_cm_symv(bb_cm *cm, const double *x, double *y) {
     if (e == hipSuccess) e = dy.alloc((size_t)d * 8);
     if (e != hipSuccess) return bb::fail(BB_ERR_NOMEM, std::string("bb_cm_symv: ") + hipGetErrorString(e));
     e = hipMemcpyAsync(dx.p, x, (size_t)d * 8, hipMemcpyHostToDevice, cm->stream);
-    const char *env = getenv("BB_CM_SYMV_FULL");          // 1: read both triangles (round 2)
-    if (e == hipSuccess && env && atoi(env) != 0)
-        e = bb::launch(symv_kernel, dim3((unsigned)((d + 4 * kSymvRows - 1) / (4 * kSymvRows))), dim3(256), 0, cm->stream,
-                       (const double *)cm->m, d, (const double *)dx.p, (double *)dy.p);
-    else if (e == hipSuccess)
-        e = symv_enqueue(cm, (const double *)dx.p, (double *)dy.p);
+    if (e == hipSuccess) e = symv_enqueue(cm, (const double *)dx.p, (double *)dy.p);
     if (e == hipSuccess) e = hipStreamSynchronize(cm->stream);
     if (e == hipSuccess) e = hipMemcpy(y, dy.p, (size_t)d * 8, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return bb::fail(BB_ERR_HIP, std::string("bb_cm_symv: ") + hipGetErrorString(e));
@@ -1303,19 +1216,13 @@ int bb_cm_eigenvector(bb_cm *cm, double *vec, double *eigenvalue, double tol, in
     if (e == hipSuccess) e = sc.alloc((size_t)(2 * m + 1 + (m + 1) * kDotSegs) * 8);
     double *d_alpha = (double *)sc.p, *d_beta = d_alpha + m, *d_inv = d_beta + m, *d_part = d_inv + 1;
     const bool two_stage = d >= 4096;
-    const char *env_full = getenv("BB_CM_SYMV_FULL");
-    const bool full = env_full && atoi(env_full) != 0;
     bool done = false;
     while (e == hipSuccess && !done) {
         const int steps = (int)std::min<int64_t>(m, std::max<int64_t>(1, max_matvecs - used));
         e = hipMemsetAsync(sc.p, 0, (size_t)(2 * m + 1) * 8, st);
         for (int k = 0; k < steps && e == hipSuccess; ++k) {
             // w = M v_k
-            if (full)
-                e = bb::launch(symv_kernel, dim3((unsigned)((d + 4 * kSymvRows - 1) / (4 * kSymvRows))), b256, 0, st,
-                               (const double *)cm->m, d, (const double *)(dV + (int64_t)k * d), dw);
-            else
-                e = symv_enqueue(cm, (const double *)(dV + (int64_t)k * d), dw);
+            e = symv_enqueue(cm, (const double *)(dV + (int64_t)k * d), dw);
             ++used;
             // coefficients against the whole basis (alpha_k is the last one), subtract, and
             // once more for the rounding the first pass leaves (classical Gram-Schmidt x 2)
@@ -1449,7 +1356,7 @@ int bb_cm_correlation(bb_cm *cm, double *tflops) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const double fact_inv = 1.0 / (double)(d - 1);   // numpy: true_divide(1, N - ddof); d = 1 -> inf
     // a whole row in the registers of one workgroup where it fits (d <= 32,768); else two passes
-    const int ch = d >= 2048 && d <= 32768 && !getenv("BB_CM_CENTER_OLD") ? (int)((d + 1023) / 1024) : 0;
+    const int ch = d >= 2048 && d <= 32768 ? (int)((d + 1023) / 1024) : 0;
     if (ch == 0) {
         e = hipMemsetAsync(xc.p, 0, (size_t)dp * ldx * 8, st);
         if (e == hipSuccess)

@@ -61,23 +61,19 @@ struct bb_solver {
     int *d_map_ptr = nullptr, *d_map_idx = nullptr;
     double *d_map_scalar = nullptr;      // per-map stress of bb_solver_stress_maps
     std::vector<int64_t> map_begin;      // first bin of every map, + n_bins
-    int64_t *d_blk_ptr = nullptr, *d_blk_chunk = nullptr;    // final stage: one list per block
-    int64_t *d_s1_ptr = nullptr, *d_s1_chunk = nullptr;      // stage 1: slices of long lists
-    int64_t n_slices = 0, part2_off = 0;
     int64_t *d_red_lists = nullptr;   // reduce_sliced_kernel: one padded chunk list per block
-    int red_stride = 0, red_slices = 0;   // entries per block (multiple of 16 * slices); 4 or 8 slices, 0 = old reduce
+    int red_stride = 0, red_slices = 0;   // entries per block (multiple of 16 * slices); 4 or 8 slices
     double *d_stress_hist = nullptr, *d_stress_scalar = nullptr;
     double *d_f64_tmp = nullptr;  // (n_pad,3) staging for coordinate I/O
     void *d_mv_in = nullptr;      // (n_pad,3) right-hand sides of bb_solver_matvec_sq, kept
     int64_t rowpart_elems = 0, colpart_elems = 0;
     int n_waves = 0, n_slots = 0;
     int wpb = 4;                   // waves per workgroup of the sweep: 4, or 8 (paired, see kernel)
-    int wg_map = 0;                // block index -> run of chunks (stress_grad_kernel): 0 identity
     int dense_u0 = -1;             // dense tile list: this rank's first global unit (the kernel then
                                    // computes a wave's first descriptor), else -1
-    int defer_cap_units = 0;       // fp32: units of row sums a wave can park in LDS (0 = none)
-    int64_t defer_lds_bytes = 0;   // dynamic LDS per workgroup for that, 0 = per-unit stores
-    unsigned defer_attr_done = 0;  // kernel variants whose dynamic-LDS ceiling was raised
+    int defer_cap_units = 0;       // fp32 / fp64 wide: units of row sums a wave can park in LDS
+    int64_t defer_lds_bytes = 0;   // dynamic LDS per workgroup of the sweep
+    unsigned defer_attr_done = 0;  // sweep instantiations whose dynamic-LDS ceiling was raised
     int64_t hist_cap = 0, hist_n = 0;
     bool have_wish = false, have_coords = false, grad_pending = false;
     // exchange_sum(): while set, the reduce / exchange kernels leave the plain sum over the
@@ -203,33 +199,15 @@ int build_indices(bb_solver *s) {
     }
     nw = bb::round_up(nw, s->wpb);
     s->n_waves = (int)nw;
-    {
-        // BB_WG_MAP: 0 identity, m > 0 multiplicative permutation (made coprime with the
-        // workgroup count), -1 one contiguous eighth of the chunks per XCD
-        const char *e = getenv("BB_WG_MAP");
-        const int64_t nwg = nw / s->wpb;
-        int m = e ? atoi(e) : 0;
-        if (m < 0 && nwg % 8 != 0) m = 0;
-        if (m > 0) {
-            auto gcd = [](int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; };
-            while (gcd(m, nwg) != 1) ++m;
-            m = (int)(m % nwg);
-            if (nwg * (int64_t)m >= ((int64_t)1 << 32)) m = 0;
-        }
-        s->wg_map = m;
-    }
 
     if (s->n_local >= ((int64_t)1 << 31))
         return bb::fail(BB_ERR_INVALID, "bb_solver_create: more than 2^31 units on one rank");
-    {
-        // Matrix loads are non-temporal (measured: +2.5 % on the kernel, +9 % on a pure read
-        // sweep at N=50k) unless this rank's units fit the 256-MB Infinity Cache: then they
-        // are read again from it on the next iteration, and plain loads keep them there
-        // (N=8,000 / 10,000: kernel -8 %, step -3.5 / -6 %; equal at N=12,000 = 288 MB;
-        // non-temporal 3-4 % better at N=17,700; profiles/archive/r02_nt_ab.txt).  BB_NT=0|1 overrides.
-        const char *e = getenv("BB_NT");
-        s->nontemporal = e ? atoi(e) != 0 : s->n_local * bb::kUnitBytes > ((int64_t)240 << 20);
-    }
+    // Matrix loads are non-temporal (measured: +2.5 % on the kernel, +9 % on a pure read
+    // sweep at N=50k) unless this rank's units fit the 256-MB Infinity Cache: then they
+    // are read again from it on the next iteration, and plain loads keep them there
+    // (N=8,000 / 10,000: kernel -8 %, step -3.5 / -6 %; equal at N=12,000 = 288 MB;
+    // non-temporal 3-4 % better at N=17,700; profiles/archive/r02_nt_ab.txt).
+    s->nontemporal = s->n_local * bb::kUnitBytes > ((int64_t)240 << 20);
     // wave w owns the contiguous chunk [w*q + min(w, r), +q (+1 if w < r)), q = n_local / nw,
     // r = n_local % nw: the kernels compute it the same way (no table to load)
     s->chunk_q = (int)(s->n_local / nw);
@@ -242,53 +220,46 @@ int build_indices(bb_solver *s) {
         chunk_max = std::max<int64_t>(chunk_max, wave_range[w].y - wave_range[w].x);
     }
     {
-        // fp32: a wave parks the row sums of (the last cap units of) its chunk in LDS
-        // until it has finished reading (stress_grad_kernel, DEFER); cap is what the
-        // workgroups sharing a CU can hold.  BB_DEFER_ROWS=0 turns it off.
-        const char *e = getenv("BB_DEFER_ROWS");
+        // fp32 / fp64 wide: a wave parks the row sums of (the last cap units of) its chunk
+        // in LDS until it has finished reading (stress_grad_kernel, DEFER); cap is what the
+        // workgroups sharing a CU can hold, 0 only on a rank without units.
         const int64_t wgs_per_cu = std::max<int64_t>(1, (nw / s->wpb + cus - 1) / cus);
         const int64_t budget = 156 * 1024 / wgs_per_cu;               // of the CU's 160 KiB
         const int64_t cap = std::min<int64_t>(chunk_max, (budget / s->wpb - 16 - 8) / 48);
-        const bool on = !(e && atoi(e) == 0);
-        if ((s->dtype == BB_F32 || s->wide) && on && cap > 0) s->defer_cap_units = (int)cap;
+        if ((s->dtype == BB_F32 || s->wide) && cap > 0) s->defer_cap_units = (int)cap;
         // a wave's LDS region: the parked row sums while it sweeps, its last column partial
         // (3 * vw elements) at the end; + the 8 progress words of a paired workgroup
         const int64_t col_words = 3 * vw * bb::elem_size(s->dtype) / 4;
         s->lds_wave_floats = (int)std::max<int64_t>((int64_t)s->defer_cap_units * 12 + 4, col_words);
-        s->defer_lds_bytes = (int64_t)s->wpb * s->lds_wave_floats * 4 + 32 +
-                             (abl::kUnitTrace ? (int64_t)s->wpb * abl::kUnitTraceSlots * 8 : 0);
+        s->defer_lds_bytes = (int64_t)s->wpb * s->lds_wave_floats * 4 + 32;
     }
     // Column-partial slots.  A wave's strips but the last get private slots (it writes them
     // itself, mid-sweep: rare); the strip a wave ENDS in shares one slot with the other
     // waves of its workgroup that end in the same strip (summed in LDS by the sweep's
-    // epilogue).  BB_WG_COLSUM=0 gives every wave its own last slot too (for A/B).
+    // epilogue).
     std::vector<int32_t> &slot_strip = s->slot_strip;
     slot_strip.clear();
     s->wave_last_strip.assign((size_t)nw, -1);
     std::vector<int2> wave_slots(nw);
-    {
-        const char *e = getenv("BB_WG_COLSUM");
-        const bool share = !(e && atoi(e) == 0);
-        for (int64_t w = 0; w < nw; ++w) {
-            wave_slots[w] = make_int2((int)slot_strip.size(), -1);
-            if (wave_range[w].x >= wave_range[w].y) continue;           // no units
-            int cur = -1;
-            std::vector<int> strips;
-            for (int64_t ul = wave_range[w].x; ul < wave_range[w].y; ++ul) {
-                const int J = s->udesc[ul].y / (int)vw;
-                if (J != cur) { strips.push_back(J); cur = J; }
-            }
-            for (size_t q = 0; q + 1 < strips.size(); ++q) slot_strip.push_back(strips[q]);
-            const int Jlast = strips.back();
-            s->wave_last_strip[(size_t)w] = Jlast;
-            const bool same_wg = w % s->wpb != 0;
-            if (share && same_wg && wave_slots[w - 1].y >= 0 &&
-                slot_strip[(size_t)wave_slots[w - 1].y] == Jlast) {
-                wave_slots[w].y = wave_slots[w - 1].y;
-            } else {
-                wave_slots[w].y = (int)slot_strip.size();
-                slot_strip.push_back(Jlast);
-            }
+    for (int64_t w = 0; w < nw; ++w) {
+        wave_slots[w] = make_int2((int)slot_strip.size(), -1);
+        if (wave_range[w].x >= wave_range[w].y) continue;           // no units
+        int cur = -1;
+        std::vector<int> strips;
+        for (int64_t ul = wave_range[w].x; ul < wave_range[w].y; ++ul) {
+            const int J = s->udesc[ul].y / (int)vw;
+            if (J != cur) { strips.push_back(J); cur = J; }
+        }
+        for (size_t q = 0; q + 1 < strips.size(); ++q) slot_strip.push_back(strips[q]);
+        const int Jlast = strips.back();
+        s->wave_last_strip[(size_t)w] = Jlast;
+        const bool same_wg = w % s->wpb != 0;
+        if (same_wg && wave_slots[w - 1].y >= 0 &&
+            slot_strip[(size_t)wave_slots[w - 1].y] == Jlast) {
+            wave_slots[w].y = wave_slots[w - 1].y;
+        } else {
+            wave_slots[w].y = (int)slot_strip.size();
+            slot_strip.push_back(Jlast);
         }
     }
     s->n_slots = (int)slot_strip.size();
@@ -308,61 +279,24 @@ int build_indices(bb_solver *s) {
     for (int sl = 0; sl < s->n_slots; ++sl)
         blk_chunk[fill[slot_strip[sl]]++] = s->rowpart_elems + (int64_t)sl * ch;
 
-    // Reduce: a block's list can hold hundreds of chunks (one per strip of its tile row, one
-    // per wave that crossed its strip).  One element per thread and kReduceSlice loads in
-    // flight make a list of L chunks cost about L / kReduceSlice memory round trips, so while
-    // the longest list has at most 128 chunks (N <= ~35k on one rank, every 1/8 share of
-    // N=50k) ONE launch sums every list whole; beyond that lists are cut into slices that a
-    // first launch sums in parallel into `part2`, which the final stage then combines.
-    // Measured (profiles/archive/r02_reduce_ab.txt): one launch saves 1-1.6 us per iteration at
-    // N=17,700 / 24,926, nothing at 50k, and loses 1-2 us at 61,914 -- the reduce is bound by
-    // the 20-56 MB of partials the sweep has just written, not by its launches.
-    // BB_REDUCE_SINGLE_MAX overrides.
-    constexpr int64_t kSlice = kReduceSlice;
-    int64_t single_max = 128;
-    if (const char *e = getenv("BB_REDUCE_SINGLE_MAX")) single_max = atoll(e);
+    // Reduce (reduce_sliced_kernel): every block's whole list in one table of fixed stride,
+    // padded with the offset of a chunk of zeros that sits behind the column partials; 4
+    // slices per workgroup while no list is longer than 64 chunks, else 8
     int64_t longest = 0;
     for (int64_t b = 0; b < nb; ++b) longest = std::max(longest, blk_ptr[b + 1] - blk_ptr[b]);
-    const int64_t slice_from = longest <= single_max ? longest : kSlice;   // lists longer than this are sliced
-    std::vector<int64_t> s1_ptr(1, 0), s1_chunk, fin_ptr(nb + 1, 0), fin_chunk;
-    s->part2_off = s->rowpart_elems + s->colpart_elems;
-    for (int64_t b = 0; b < nb; ++b) {
-        const int64_t k0 = blk_ptr[b], k1 = blk_ptr[b + 1];
-        if (k1 - k0 <= slice_from) {
-            for (int64_t k = k0; k < k1; ++k) fin_chunk.push_back(blk_chunk[k]);
-        } else {
-            for (int64_t k = k0; k < k1; k += kSlice) {
-                const int64_t ke = std::min(k + kSlice, k1);
-                fin_chunk.push_back(s->part2_off + (int64_t)(s1_ptr.size() - 1) * ch);
-                for (int64_t q = k; q < ke; ++q) s1_chunk.push_back(blk_chunk[q]);
-                s1_ptr.push_back((int64_t)s1_chunk.size());
-            }
-        }
-        fin_ptr[b + 1] = (int64_t)fin_chunk.size();
-    }
-    s->n_slices = (int64_t)s1_ptr.size() - 1;
-    if (s1_chunk.empty()) s1_chunk.push_back(0);
-    if (fin_chunk.empty()) fin_chunk.push_back(0);
-    // reduce_sliced_kernel (the default; BB_REDUCE_OLD=1 keeps the two-stage reduce above):
-    // every block's whole list in one table of fixed stride, padded with the offset of a
-    // chunk of zeros that sits behind the stage-1 partials
-    const int64_t zero_off = s->part2_off + s->n_slices * ch;
+    const int64_t zero_off = s->rowpart_elems + s->colpart_elems;
     const int64_t part_total = zero_off + ch;
     std::vector<int64_t> red_lists;
     {
-        const char *e = getenv("BB_REDUCE_OLD");
-        s->red_slices = (e && atoi(e) != 0) ? 0 : (longest <= 64 ? 4 : 8);
+        s->red_slices = longest <= 64 ? 4 : 8;
         if (const char *f = getenv("BB_REDUCE_SLICES")) s->red_slices = atoi(f) == 4 ? 4 : 8;
-        if (s->red_slices > 0) {
-            const int64_t quantum = 16 * s->red_slices;
-            s->red_stride = (int)bb::round_up(std::max<int64_t>(longest, 1), quantum);
-            red_lists.assign((size_t)(nb * s->red_stride), zero_off);
-            for (int64_t b = 0; b < nb; ++b)
-                for (int64_t k = blk_ptr[b]; k < blk_ptr[b + 1]; ++k)
-                    red_lists[(size_t)(b * s->red_stride + (k - blk_ptr[b]))] = blk_chunk[k];
-        }
+        const int64_t quantum = 16 * s->red_slices;
+        s->red_stride = (int)bb::round_up(std::max<int64_t>(longest, 1), quantum);
+        red_lists.assign((size_t)(nb * s->red_stride), zero_off);
+        for (int64_t b = 0; b < nb; ++b)
+            for (int64_t k = blk_ptr[b]; k < blk_ptr[b + 1]; ++k)
+                red_lists[(size_t)(b * s->red_stride + (k - blk_ptr[b]))] = blk_chunk[k];
     }
-    if (red_lists.empty()) red_lists.push_back(0);
 
     const int64_t es = bb::elem_size(s->dtype);
     s->hist_cap = kHistCap;
@@ -371,10 +305,8 @@ int build_indices(bb_solver *s) {
         s->full_ld = bb::round_up(s->L.n_bins, s->dtype == BB_F32 ? RowTrip<float>::COLS
                                                                   : RowTrip<double>::COLS);
         // waves per row: enough of them that a small map still covers the chip with
-        // about 16 waves per CU (N=963: 4 per row); BB_ROW_OWNER_WPR overrides
-        const char *ew = getenv("BB_ROW_OWNER_WPR");
-        int wpr = ew ? atoi(ew) : (s->L.n_bins <= 1024 ? 4 : (s->L.n_bins <= 2048 ? 2 : 1));
-        s->ro_wpr = wpr >= 4 ? 4 : (wpr >= 2 ? 2 : 1);
+        // about 16 waves per CU (N=963: 4 per row)
+        s->ro_wpr = s->L.n_bins <= 1024 ? 4 : (s->L.n_bins <= 2048 ? 2 : 1);
         const int rows_per_wg = 4 / s->ro_wpr;
         s->ro_blocks = (int)((s->L.n_bins + rows_per_wg - 1) / rows_per_wg);
     }
@@ -392,13 +324,8 @@ int build_indices(bb_solver *s) {
         add((char **)&s->d_part, part_total * es);
         add(&s->d_udesc, (int64_t)s->udesc.size());
         add(&s->d_wave_slots, nw);
-        // nw partials (+ 8 stamps per wave, + one stamp per unit: diagnostic builds)
-        add(&s->d_stresspart, nw * (9 + (abl::kUnitTrace ? abl::kUnitTraceSlots : 0)));
+        add(&s->d_stresspart, nw);
         add(&s->d_stress_slot, std::max<int64_t>(s->n_slots, 1));
-        add(&s->d_blk_ptr, nb + 1);
-        add(&s->d_blk_chunk, (int64_t)fin_chunk.size());
-        add(&s->d_s1_ptr, (int64_t)s1_ptr.size());
-        add(&s->d_s1_chunk, (int64_t)s1_chunk.size());
         add(&s->d_red_lists, (int64_t)red_lists.size());
         add(&s->d_stress_hist, kHistCap);
         add(&s->d_stress_scalar, 1);
@@ -425,14 +352,6 @@ int build_indices(bb_solver *s) {
                                 hipMemcpyHostToDevice, st));
     BB_HIP_CHECK(hipMemcpyAsync(s->d_wave_slots, wave_slots.data(), nw * sizeof(int2),
                                 hipMemcpyHostToDevice, st));
-    BB_HIP_CHECK(hipMemcpyAsync(s->d_blk_ptr, fin_ptr.data(), (nb + 1) * sizeof(int64_t),
-                                hipMemcpyHostToDevice, st));
-    BB_HIP_CHECK(hipMemcpyAsync(s->d_blk_chunk, fin_chunk.data(),
-                                fin_chunk.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    BB_HIP_CHECK(hipMemcpyAsync(s->d_s1_ptr, s1_ptr.data(), s1_ptr.size() * sizeof(int64_t),
-                                hipMemcpyHostToDevice, st));
-    BB_HIP_CHECK(hipMemcpyAsync(s->d_s1_chunk, s1_chunk.data(),
-                                s1_chunk.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
     BB_HIP_CHECK(hipMemcpyAsync(s->d_red_lists, red_lists.data(),
                                 red_lists.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
     // rows of boundary tiles owned by another rank are never written: keep them 0
@@ -465,46 +384,39 @@ int launch_grad_t(bb_solver *s, int op, const void *x_in) {
                  (s->u_begin - s->t_first * s->L.units_per_tile) * (3 * s->L.rows_per_unit);
     T *colpart = (T *)s->d_part + s->rowpart_elems;
     const dim3 grid(s->n_waves / s->wpb), block(64 * s->wpb);
-    // fp32 with the whole chunk of row sums parked in LDS (s->defer_lds_bytes > 0), or the
-    // per-unit store.  The dynamic-LDS ceiling of a kernel is raised once per instantiation.
-#define BB_LAUNCH3(NTV, OPV, DEF, LDS, WPBV)                                                    \
+    // The dynamic-LDS ceiling of a kernel (row-sum parking and the column partials) is raised
+    // once per instantiation: one bit per (WPB, NT, OP).
+#define BB_LAUNCH(NTV, OPV, WPBV)                                                               \
     do {                                                                                        \
-        auto kern = stress_grad_kernel<T, W, NTV, OPV, DEF, WPBV>;                              \
+        auto kern = stress_grad_kernel<T, W, NTV, OPV, WPBV>;                                   \
         constexpr unsigned bit =                                                                \
             1u << ((WPBV == 8 ? 4 : 0) + (NTV ? 2 : 0) + (OPV == kOpMatvec2 ? 1 : 0));          \
-        if ((LDS) > 0 && !(s->defer_attr_done & bit)) {                                        \
+        if (s->defer_lds_bytes > 0 && !(s->defer_attr_done & bit)) {                            \
             BB_HIP_CHECK(hipFuncSetAttribute((const void *)kern,                                \
                                              hipFuncAttributeMaxDynamicSharedMemorySize,        \
-                                             (int)(LDS)));                                      \
+                                             (int)s->defer_lds_bytes));                         \
             s->defer_attr_done |= bit;                                                          \
         }                                                                                       \
-        BB_HIP_CHECK(bb::launch(kern, grid, block, (size_t)(LDS), s->stream, units, X,          \
-                                s->d_udesc, s->chunk_q, s->chunk_r, s->d_wave_slots, rowpart,   \
+        BB_HIP_CHECK(bb::launch(kern, grid, block, (size_t)s->defer_lds_bytes, s->stream, units, \
+                                X, s->d_udesc, s->chunk_q, s->chunk_r, s->d_wave_slots, rowpart, \
                                 colpart, s->d_stresspart, s->defer_cap_units,                   \
-                                s->lds_wave_floats, s->wg_map, s->dense_u0, s->d_stress_slot)); \
+                                s->lds_wave_floats, s->dense_u0, s->d_stress_slot));            \
     } while (0)
-#define BB_LAUNCH2(NTV, OPV, DEF, LDS)                                                          \
+    // 8 waves per workgroup only for the 512-wide layouts (fp32, fp64 wide)
+#define BB_LAUNCH_WPB(NTV, OPV)                                                                 \
     do {                                                                                        \
         if ((sizeof(T) == 4 || W) && s->wpb == 8)                                               \
-            BB_LAUNCH3(NTV, OPV, DEF, LDS, ((sizeof(T) == 4 || W) ? 8 : 4));                    \
+            BB_LAUNCH(NTV, OPV, ((sizeof(T) == 4 || W) ? 8 : 4));                               \
         else                                                                                    \
-            BB_LAUNCH3(NTV, OPV, DEF, LDS, 4);                                                  \
-    } while (0)
-#define BB_LAUNCH(NTV, OPV)                                                                     \
-    do {                                                                                        \
-        if ((sizeof(T) == 4 || W) && s->defer_cap_units > 0)                                    \
-            BB_LAUNCH2(NTV, OPV, (sizeof(T) == 4 || W), s->defer_lds_bytes);                    \
-        else                                                                                    \
-            BB_LAUNCH2(NTV, OPV, false, s->defer_lds_bytes);                                    \
+            BB_LAUNCH(NTV, OPV, 4);                                                             \
     } while (0)
     if (op == kOpMatvec2) {
-        if (s->nontemporal) BB_LAUNCH(true, kOpMatvec2); else BB_LAUNCH(false, kOpMatvec2);
+        if (s->nontemporal) BB_LAUNCH_WPB(true, kOpMatvec2); else BB_LAUNCH_WPB(false, kOpMatvec2);
     } else {
-        if (s->nontemporal) BB_LAUNCH(true, kOpStress); else BB_LAUNCH(false, kOpStress);
+        if (s->nontemporal) BB_LAUNCH_WPB(true, kOpStress); else BB_LAUNCH_WPB(false, kOpStress);
     }
 #undef BB_LAUNCH
-#undef BB_LAUNCH2
-#undef BB_LAUNCH3
+#undef BB_LAUNCH_WPB
     return BB_OK;
 }
 
@@ -550,7 +462,6 @@ void fill_reduce_params(bb_solver *s, ReduceParams<T> &p, int mode, double lr, d
     p.mu = s->sum_target ? T(0) : (T)s->momentum;
     p.scale = (T)scale;
     p.exch = (T *)s->d_exch;
-    p.part_out = (T *)s->d_part + s->part2_off;
     p.stress_out = stress_out;
     p.n_pad = s->L.n_pad;
     p.n_waves = s->n_waves;
@@ -566,8 +477,6 @@ void fill_reduce_params(bb_solver *s, ReduceParams<T> &p, int mode, double lr, d
         p.seq = s->peer_seq;
         p.n_peers = s->world;
     }
-    p.blk_ptr = nullptr;
-    p.blk_chunk = nullptr;
     p.mode = mode;
     p.stress_slot = s->d_stress_slot;
     p.n_slots = s->n_slots;
@@ -585,31 +494,15 @@ int launch_reduce_t(bb_solver *s, int mode, double lr, double *stress_out, doubl
     ReduceParams<T> p;
     fill_reduce_params<T>(s, p, mode, lr, stress_out, scale);
     const unsigned segs = 3 * Lay<T, W>::VW / kRedWG;   // workgroups per block of 3*vw elements
-    if (s->red_slices > 0) {
-        // one launch: every list whole, 128 elements x 4 or 8 slices per workgroup
-        const dim3 grid = mode == kReduceStressOnly ? dim3((unsigned)s->n_maps, 1)
-                                                    : dim3((unsigned)s->L.n_blocks, segs);
-        if (s->red_slices == 4)
-            BB_HIP_CHECK(bb::launch(reduce_sliced_kernel<T, W, 4>, grid, dim3(128 * 4), 0, s->stream,
-                                    p, (const int64_t *)s->d_red_lists, s->red_stride));
-        else
-            BB_HIP_CHECK(bb::launch(reduce_sliced_kernel<T, W, 8>, grid, dim3(128 * 8), 0, s->stream,
-                                    p, (const int64_t *)s->d_red_lists, s->red_stride));
-        return BB_OK;
-    }
-    if (mode != kReduceStressOnly && s->n_slices > 0) {
-        p.blk_ptr = s->d_s1_ptr;
-        p.blk_chunk = s->d_s1_chunk;
-        p.mode = kReducePartial;
-        BB_HIP_CHECK(bb::launch(reduce_kernel<T, W>, dim3((unsigned)s->n_slices, segs), dim3(kRedWG),
-                                0, s->stream, p));
-    }
-    p.blk_ptr = s->d_blk_ptr;
-    p.blk_chunk = s->d_blk_chunk;
-    p.mode = mode;
+    // one launch: every list whole, 128 elements x 4 or 8 slices per workgroup
     const dim3 grid = mode == kReduceStressOnly ? dim3((unsigned)s->n_maps, 1)
                                                 : dim3((unsigned)s->L.n_blocks, segs);
-    BB_HIP_CHECK(bb::launch(reduce_kernel<T, W>, grid, dim3(kRedWG), 0, s->stream, p));
+    if (s->red_slices == 4)
+        BB_HIP_CHECK(bb::launch(reduce_sliced_kernel<T, W, 4>, grid, dim3(128 * 4), 0, s->stream,
+                                p, (const int64_t *)s->d_red_lists, s->red_stride));
+    else
+        BB_HIP_CHECK(bb::launch(reduce_sliced_kernel<T, W, 8>, grid, dim3(128 * 8), 0, s->stream,
+                                p, (const int64_t *)s->d_red_lists, s->red_stride));
     return BB_OK;
 }
 
@@ -1794,7 +1687,7 @@ int exchange_sum(bb_solver *s) {
         s->peer_seq++;
         s->sum_target = s->d_exch;
         int rc;
-        if (s->peer_fused && s->red_slices > 0) {
+        if (s->peer_fused) {
             rc = launch_exchange(s, -1.0, s->d_stress_scalar, kScalePlainSum);
         } else {
             rc = launch_reduce(s, kReducePeer, 0.0, nullptr, kScalePlainSum);
@@ -1946,7 +1839,7 @@ int bb_solver_peer_connect(bb_solver *s, const void *handles) {
     }
     BB_TRY(dev_alloc(&s->d_peer_state, 1));
     // the top counter + one per block on a line of its own (reduce_sliced_kernel's two-level
-    // check-in), also good for reduce_kernel, which uses the top one only
+    // check-in)
     const int64_t n_counters = 32 * (s->L.n_blocks + 1);
     BB_TRY(dev_alloc(&s->d_peer_counter, n_counters));
     BB_HIP_CHECK(hipMemset(s->d_peer_state, 0, sizeof(PeerState)));
@@ -1979,7 +1872,6 @@ int bb_solver_peer_connect(bb_solver *s, const void *handles) {
         const char *env = getenv("BB_PEER_FUSED");
         s->peer_fused = env ? atoi(env) != 0 : most_on_one_gpu == 1;
         s->peer_ranks_on_gpu = most_on_one_gpu;
-        if (s->red_slices <= 0) s->peer_fused = false;
     }
     s->peer_connected = true;
     BB_HIP_CHECK(hipDeviceSynchronize());
@@ -2011,7 +1903,7 @@ int bb_solver_peer_set_form(bb_solver *s, int one_launch) {
 int bb_solver_peer_form(bb_solver *s, int *one_launch) {
     BB_REQUIRE(s != nullptr && one_launch != nullptr, "bb_solver_peer_form: NULL argument");
     if (!s->peer_connected) return bb::fail(BB_ERR_STATE, "bb_solver_peer_form: not connected");
-    *one_launch = (s->peer_fused && s->red_slices > 0) ? 1 : 0;
+    *one_launch = s->peer_fused ? 1 : 0;
     return BB_OK;
 }
 
@@ -2025,7 +1917,7 @@ int bb_solver_peer_status(bb_solver *s, int *status) {
     BB_HIP_CHECK(hipMemcpy(&st, s->d_peer_state, sizeof(st), hipMemcpyDeviceToHost));
     if (status) *status = st.status;
     if (st.status != 0) {
-        const bool one = s->peer_fused && s->red_slices > 0;
+        const bool one = s->peer_fused;
         return bb::fail(BB_ERR_STATE,
                         std::string("peer exchange: a rank did not deliver its partial within the "
                                     "time limit (BB_PEER_TIMEOUT_MS), or reported its own failure; ") +
@@ -2056,7 +1948,7 @@ int bb_solver_iterate_peer(bb_solver *s, int64_t iters, double lr) {
         BB_TRY(launch_grad(s));
         if (ev) BB_HIP_CHECK(hipEventRecord(ev[1], s->stream));
         s->peer_seq++;
-        if (s->peer_fused && s->red_slices > 0) {
+        if (s->peer_fused) {
             // one launch: reduce, push, wait, sum, update (reduce_exchange_kernel)
             BB_TRY(launch_exchange(s, lr, s->d_stress_hist + s->hist_n));
             if (ev) BB_HIP_CHECK(hipEventRecord(ev[2], s->stream));
@@ -2341,98 +2233,6 @@ int bb_solver_measure_stream_read(bb_solver *s, int launches, double *ms_avg) {
     *ms_avg = ms / launches;
     return BB_OK;
 }
-
-#if defined(BB_WAVE_TRACE) || defined(BB_UNIT_TRACE)
-// Diagnostic build only: `times` sweep launches back to back with nothing in between
-// (is a launch's slow first unit a cold instruction cache?).
-BB_API int bb_solver_debug_grad_repeat(bb_solver *s, int times) {
-    BB_TRY(check_ready(s, "bb_solver_debug_grad_repeat"));
-    BB_TRY(bb::enter_device(s->device));
-    for (int k = 0; k < times; ++k) BB_TRY(launch_grad(s));
-    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-    return BB_OK;
-}
-// Diagnostic build only (-DBB_OVERLAP_PROBE rides on the trace builds): an UPPER BOUND of what
-// overlapping the reduce of iteration k with sweep k + 1 could save (lever (a)).
-// The two run as a software pipeline on two streams -- sweep k waits for reduce k - 1 (one
-// iteration stale: the coordinates it reads are not the ones the solver would use, timing
-// only), reduce k waits for sweep k -- so every iteration has the two cross-queue
-// dependencies the real thing would have and NONE of its in-kernel hand-off.  If this is not
-// faster than the plain loop, nothing built on it can be.
-BB_API int bb_solver_debug_overlap_bound(bb_solver *s, int iters, double lr, double *us_plain,
-                                         double *us_pipelined) {
-    BB_TRY(check_ready(s, "bb_solver_debug_overlap_bound"));
-    BB_REQUIRE(us_plain != nullptr && us_pipelined != nullptr && iters >= 2 && iters <= 100000,
-               "bb_solver_debug_overlap_bound: bad argument");
-    BB_REQUIRE(s->world == 1 && !s->row_owner, "bb_solver_debug_overlap_bound: one rank, sweep path");
-    BB_TRY(bb::enter_device(s->device));
-    hipStream_t main_st = s->stream, side = nullptr;
-    BB_HIP_CHECK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-    hipEvent_t e_sweep[2], e_red[2];
-    for (int q = 0; q < 2; ++q) {
-        BB_HIP_CHECK(hipEventCreateWithFlags(&e_sweep[q], hipEventDisableTiming));
-        BB_HIP_CHECK(hipEventCreateWithFlags(&e_red[q], hipEventDisableTiming));
-    }
-    auto now = []() { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e6 + t.tv_nsec * 1e-3; };
-    int rc = BB_OK;
-    for (int phase = 0; phase < 2 && rc == BB_OK; ++phase) {
-        for (int pass = 0; pass < 2 && rc == BB_OK; ++pass) {        // pass 0 warms up
-            const int n = pass == 0 ? std::max(20, iters / 4) : iters;
-            const double t0 = now();
-            for (int k = 0; k < n && rc == BB_OK; ++k) {
-                if (phase == 0) {
-                    rc = launch_grad(s);
-                    if (rc == BB_OK) rc = launch_reduce(s, kReduceApply, lr, s->d_stress_scalar);
-                } else {
-                    if (k > 0) (void)hipStreamWaitEvent(main_st, e_red[(k - 1) & 1], 0);
-                    rc = launch_grad(s);
-                    (void)hipEventRecord(e_sweep[k & 1], main_st);
-                    (void)hipStreamWaitEvent(side, e_sweep[k & 1], 0);
-                    s->stream = side;
-                    if (rc == BB_OK) rc = launch_reduce(s, kReduceApply, lr, s->d_stress_scalar);
-                    s->stream = main_st;
-                    (void)hipEventRecord(e_red[k & 1], side);
-                }
-            }
-            (void)hipStreamSynchronize(side);
-            (void)hipStreamSynchronize(main_st);
-            if (pass == 1) *(phase == 0 ? us_plain : us_pipelined) = (now() - t0) / n;
-        }
-    }
-    for (int q = 0; q < 2; ++q) { hipEventDestroy(e_sweep[q]); hipEventDestroy(e_red[q]); }
-    hipStreamDestroy(side);
-    return rc;
-}
-// Diagnostic build only: the stamps of the last stress_grad_kernel launch,
-// 8 x uint64 per wave {start, first unit done, last unit consumed, end, xcc<<32 | hw_id,
-// first load landed, window landed, coordinates landed}.
-BB_API int bb_solver_debug_wave_trace(bb_solver *s, unsigned long long *out, int64_t cap,
-                                      int64_t *n_waves) {
-    BB_REQUIRE(s != nullptr && n_waves != nullptr, "bb_solver_debug_wave_trace: NULL argument");
-    BB_TRY(bb::enter_device(s->device));
-    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-    *n_waves = s->n_waves;
-    if (out && cap >= 8 * (int64_t)s->n_waves)
-        BB_HIP_CHECK(hipMemcpy(out, s->d_stresspart + s->n_waves, (size_t)s->n_waves * 64,
-                               hipMemcpyDeviceToHost));
-    return BB_OK;
-}
-// -DBB_UNIT_TRACE: kUnitTraceSlots stamps per wave of the last sweep launch: slot k = the top
-// of the wave's unit k (10-ns ticks), slot n_units = the end of its last unit, 0 = unused.
-BB_API int bb_solver_debug_unit_trace(bb_solver *s, unsigned long long *out, int64_t cap,
-                                      int64_t *n_waves, int64_t *slots) {
-    BB_REQUIRE(s != nullptr && n_waves != nullptr && slots != nullptr,
-               "bb_solver_debug_unit_trace: NULL argument");
-    BB_TRY(bb::enter_device(s->device));
-    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-    *n_waves = s->n_waves;
-    *slots = abl::kUnitTrace ? abl::kUnitTraceSlots : 0;
-    if (out && abl::kUnitTrace && cap >= *slots * (int64_t)s->n_waves)
-        BB_HIP_CHECK(hipMemcpy(out, s->d_stresspart + (int64_t)s->n_waves * 9,
-                               (size_t)s->n_waves * abl::kUnitTraceSlots * 8, hipMemcpyDeviceToHost));
-    return BB_OK;
-}
-#endif
 
 int bb_solver_iteration_path(const bb_solver *s, int *row_owner, int *waves_per_row) {
     BB_REQUIRE(s != nullptr, "bb_solver_iteration_path: solver is NULL");

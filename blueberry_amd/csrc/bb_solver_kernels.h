@@ -24,7 +24,6 @@
 
 #include <type_traits>
 
-#include "bb_ablate.h"
 #include "blueberry_hip.h"
 
 namespace {
@@ -71,9 +70,7 @@ struct Lay;
 template <bool W>
 struct Lay<float, W> {
     static constexpr int LPR = 2, VW = 512, RPU = 4;
-    static constexpr int MIN_WG = abl::kDppRowSum ? 4 : 2;   // __launch_bounds__: <= 128 VGPRs (the
-                                                // -DBB_MFMA_ROWSUM experiment keeps 12 selectors and
-                                                // an accumulator more: <= 256)
+    static constexpr int MIN_WG = 4;            // __launch_bounds__: <= 128 VGPRs
     static constexpr bool SCALAR_XROW = true;   // 12 row coordinates through the scalar cache
 };
 template <>
@@ -88,7 +85,7 @@ struct Lay<double, false> {
     // <= 256 VGPRs.  This shape only ever runs one workgroup of 4 waves per CU (at most 4096
     // bins: fewer than 65k units, waves_per_cu() = 4), so a cap of 128 registers bought no
     // occupancy and, from round 3 on, cost a 20-byte scratch spill in the stress sweep
-    // (tests/test_host.py::test_no_product_kernel_spills guards against the next one).
+    // (tests/test_host.py::test_product_kernels_do_not_spill guards against the next one).
     static constexpr int MIN_WG = 2;
     static constexpr bool SCALAR_XROW = false;  // 24 doubles x 2 would not fit the SGPR file:
                                                 // one per-lane load + v_readlane instead
@@ -229,11 +226,12 @@ __device__ __forceinline__ double weight01_f64(double delta) {
     return __builtin_fmin(__builtin_fmax(delta * 0x1p1000, 0.0), 1.0);
 }
 
-// Pair math for one matrix row of a unit: VPL pairs per lane.
+// Pair math for one matrix row of a unit: VPL pairs per lane (fp64; fp32 has pair_step2).
 template <typename T, int C, int OP>
 __device__ __forceinline__ void pair_step(const typename Traits<T>::Vec &drow, T xi, T yi, T zi,
                                           const T (&xj)[Traits<T>::VPL][3],
                                           T (&gc)[Traits<T>::VPL][3], T &gx, T &gy, T &gz, T &s) {
+    static_assert(sizeof(T) == 8, "fp32 pairs go through pair_step2");
     const T delta = elem<C>(drow);
     if constexpr (OP == kOpMatvec2) {
         const T a = delta * delta;
@@ -243,36 +241,19 @@ __device__ __forceinline__ void pair_step(const typename Traits<T>::Vec &drow, T
     }
     const T dx = xi - xj[C][0], dy = yi - xj[C][1], dz = zi - xj[C][2];
     const T d2 = fma(dx, dx, fma(dy, dy, fma(dz, dz, Traits<T>::eps2())));  // SPEC 2.2
-    if constexpr (sizeof(T) == 8 && !abl::kF64Libm) {
-        // fp64 has no packed forms and its pair math alone is worth the HBM time of a
-        // unit, so every instruction counts: 25 + v_rsq per pair
-        T rinv, dist;
-        rsqrt_sqrt_f64(d2, rinv, dist);
-        // (dist - delta) or 0 in ONE instruction: w is 1, or 0 exactly where delta is 0, so
-        // dist * w - delta is dist - delta (the product is exact) or 0 - 0
-        const T res = fma(dist, weight01_f64(delta), -delta);
-        s = fma(res, res, s);
-        const T coef = res * rinv;  // (d - delta) / d ; the factor 2 is applied in the reduce
-        gx = fma(coef, dx, gx); gy = fma(coef, dy, gy); gz = fma(coef, dz, gz);
-        gc[C][0] = fma(-coef, dx, gc[C][0]);
-        gc[C][1] = fma(-coef, dy, gc[C][1]);
-        gc[C][2] = fma(-coef, dz, gc[C][2]);
-        return;
-    }
+    // fp64 has no packed forms and its pair math alone is worth the HBM time of a
+    // unit, so every instruction counts: 25 + v_rsq per pair
     T rinv, dist;
-    if constexpr (sizeof(T) == 4) {
-        rinv = __builtin_amdgcn_rsqf(d2);
-        dist = d2 * rinv;
-    } else {
-        dist = sqrt(d2);            // timing experiment (BB_ABL_F64_LIBM): ~55 fp64 ops
-        rinv = 1.0 / dist;
-    }
-    const T res = delta > T(0) ? dist - delta : T(0);
+    rsqrt_sqrt_f64(d2, rinv, dist);
+    // (dist - delta) or 0 in ONE instruction: w is 1, or 0 exactly where delta is 0, so
+    // dist * w - delta is dist - delta (the product is exact) or 0 - 0
+    const T res = fma(dist, weight01_f64(delta), -delta);
     s = fma(res, res, s);
     const T coef = res * rinv;  // (d - delta) / d ; the factor 2 is applied in the reduce
-    const T fx = coef * dx, fy = coef * dy, fz = coef * dz;
-    gx += fx; gy += fy; gz += fz;
-    gc[C][0] -= fx; gc[C][1] -= fy; gc[C][2] -= fz;
+    gx = fma(coef, dx, gx); gy = fma(coef, dy, gy); gz = fma(coef, dz, gz);
+    gc[C][0] = fma(-coef, dx, gc[C][0]);
+    gc[C][1] = fma(-coef, dy, gc[C][1]);
+    gc[C][2] = fma(-coef, dz, gc[C][2]);
 }
 
 // Matrix rows are read exactly once per launch: NT = true marks the loads
@@ -299,33 +280,15 @@ __device__ __forceinline__ double2 stream_load(const double2 *p) {
 }
 
 // Where a wave's rolling window is refilled from: the k-th wave-load (1 KiB) of the NEXT
-// unit.  WinPtr (product): plain pointers.  WinBuf (-DBB_BUFFER_WINDOW, A/B only): buffer
-// loads through a descriptor that covers exactly the wave's chunk, so that the refills of
-// a wave's last unit fall out of range and cost no traffic -- measured 1.5-2.5 us SLOWER per
-// launch at N=12,000-17,700 (the scheduler clusters the refills differently:
-// profiles/r03_window_ab.txt); the pointer form gets the same saving by pointing all lanes
-// of those last refills at one line (see window_of in the kernel).
+// unit, through plain pointers.  (Buffer loads through a descriptor of the wave's chunk, so
+// that the refills of its last unit fall out of range, measured 1.5-2.5 us slower per launch:
+// profiles/r03_window_ab.txt.  The pointer form gets the same saving by pointing all lanes of
+// those last refills at one line: see window_of in the kernel.)
 template <typename Vec>
 struct WinPtr {
     const Vec *p;
     template <bool NT>
     __device__ __forceinline__ Vec load(int k) const { return stream_load<NT>(p + k * 64); }
-};
-template <typename Vec>
-struct WinBuf {
-    __amdgpu_buffer_rsrc_t rsrc;
-    unsigned off;      // byte offset of this lane's 16 bytes of wave-load 0 of the unit
-    template <bool NT>
-    __device__ __forceinline__ Vec load(int k) const {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + (unsigned)k * 1024u, 0,
-                                                              NT ? 2 : 0);   // aux bit 1 = nt
-        if constexpr (sizeof(Vec) == sizeof(float4) && std::is_same<Vec, float4>::value)
-            return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z),
-                               __uint_as_float(v.w));
-        else
-            return make_double2(__hiloint2double((int)v.y, (int)v.x),
-                                __hiloint2double((int)v.w, (int)v.z));
-    }
 };
 
 // One unit, generic (fp64) form: RPU matrix rows of LPR wave-loads each.  Load k of
@@ -394,18 +357,6 @@ __device__ __forceinline__ double swap_sum32(double t) {
     return __hiloint2double((int)b[0], (int)a[0]) + __hiloint2double((int)b[1], (int)a[1]);
 }
 
-__device__ __forceinline__ float swap_sum16(float t) {
-    const unsigned b = __float_as_uint(t);
-    const auto a = __builtin_amdgcn_permlane16_swap(b, b, false, false);
-    return __uint_as_float(a[0]) + __uint_as_float(a[1]);
-}
-__device__ __forceinline__ float swap_sum32(float t) {
-    const unsigned b = __float_as_uint(t);
-    const auto a = __builtin_amdgcn_permlane32_swap(b, b, false, false);
-    return __uint_as_float(a[0]) + __uint_as_float(a[1]);
-}
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
 // The three sums of a matrix row (x, y, z components) over the 64 lanes in 10 VALU
 // instructions instead of 18 (round 3; the sweep is issue-bound at the clock the chip runs it
 // at, see the kernel's comment).  gfx950's lane swaps exchange half of one register with the
@@ -435,7 +386,7 @@ __device__ __forceinline__ int swap_rowsum_slot(int lane) {
     return 3 * r + (lane < 16 ? 0 : (lane < 32 ? 2 : 1));
 }
 
-template <bool NT, int OP, bool DEFER, typename XR, typename WIN>
+template <bool NT, int OP, typename XR, typename WIN>
 __device__ __forceinline__ void process_unit_f64w(double2 (&d)[8], const XR &xrow,
                                                   const WIN &next,
                                                   const double (&xj)[4][2][3], double (&gc)[4][2][3],
@@ -467,7 +418,7 @@ __device__ __forceinline__ void process_unit_f64w(double2 (&d)[8], const XR &xro
     t = swap_sum16(t);
     t = swap_sum32(t);                   // every lane with lane % 16 == v: the unit's sum v
     // lanes 48..53 keep one sum each; parked in LDS or stored, exactly one of the two lands
-    if constexpr (DEFER) *reinterpret_cast<double *>(row_lds + stage_idx) = t;
+    *reinterpret_cast<double *>(row_lds + stage_idx) = t;
     const u32x2 bits = {(unsigned)__double2loint(t), (unsigned)__double2hiint(t)};
     __builtin_amdgcn_raw_buffer_store_b64(bits, row_rsrc, row_voff, 0, 0);
     stress += s;
@@ -515,14 +466,10 @@ __device__ __forceinline__ void pair_step2(f32x2 delta, f32x2 xi, f32x2 yi, f32x
     const f32x2 dx = xi - st.x[K][H][0], dy = yi - st.x[K][H][1], dz = zi - st.x[K][H][2];
     const f32x2 d2 = dx * dx + (dy * dy + (dz * dz + eps2));  // SPEC 2.2: |d|^2 + eps^2
     f32x2 rinv;
-    if constexpr (abl::kNoRsq) {
-        rinv = d2 * eps2;
-    } else {
-        rinv.x = __builtin_amdgcn_rsqf(d2.x);
-        rinv.y = __builtin_amdgcn_rsqf(d2.y);
-    }
+    rinv.x = __builtin_amdgcn_rsqf(d2.x);
+    rinv.y = __builtin_amdgcn_rsqf(d2.y);
     f32x2 res = d2 * rinv - delta;
-    if constexpr (!abl::kNoMask) res *= weight01(delta);  // (dist - delta) or 0
+    res *= weight01(delta);  // (dist - delta) or 0
     s2 += res * res;
     const f32x2 coef = res * rinv;
     if constexpr (FIRST) {
@@ -530,40 +477,30 @@ __device__ __forceinline__ void pair_step2(f32x2 delta, f32x2 xi, f32x2 yi, f32x
     } else {
         rx += coef * dx; ry += coef * dy; rz += coef * dz;
     }
-    if constexpr (!abl::kNoCol) {
-        st.g[K][H][0] -= coef * dx;
-        st.g[K][H][1] -= coef * dy;
-        st.g[K][H][2] -= coef * dz;
-    }
+    st.g[K][H][0] -= coef * dx;
+    st.g[K][H][1] -= coef * dy;
+    st.g[K][H][2] -= coef * dz;
 }
 
 // d[] holds the unit's 8 wave-loads in row order: d[2*r + k] = row r, load k.
-// Row sums: a fixed-tree 64-lane DPP reduction per matrix row (wave_sum_hi3).  Round 3 tried
-// them through the matrix pipe, as the fp64 unit does (-DBB_MFMA_ROWSUM: v_mfma_f32_16x16x4_f32
-// with a 0/1 selector per sum, the unit's 12 sums side by side in one accumulator, 3 adds and two
-// lane swaps at the end): 72 DPP adds fewer per unit, but 164 VGPRs, a different clustering of
-// the refills and the wait for the accumulator at the end of every unit -- 2.7-6 % slower at
-// every size (profiles/r03_mfma_rowsum_ab.txt).  Why it looked promising: at two waves per SIMD
-// the chip runs this kernel at 1.75-1.83 GHz (power) and the SIMD's VALU is then busy most of a
-// unit's time (418 VALU instructions per unit and wave, 32 of them quarter-rate v_rsq_f32);
-// tools/unit_trace.py prints each XCD's clock.
-template <bool NT, int OP, bool DEFER, bool REFILL = true, typename WIN>
+// Row sums: row_sum3_swap per matrix row (10 VALU instructions against 18 for the 64-lane DPP
+// tree: profiles/r03_swap_rowsum_ab.txt).  Through the matrix pipe, as the fp64 unit does, they
+// measured 2.7-6 % slower at every size (164 VGPRs, the wait for the accumulator at the end of
+// every unit: profiles/r03_mfma_rowsum_ab.txt).  At two waves per SIMD the chip runs this kernel
+// at 1.75-1.83 GHz (power) and the SIMD's VALU is then busy most of a unit's time (418 VALU
+// instructions per unit and wave, 32 of them quarter-rate v_rsq_f32).
+template <bool NT, int OP, typename WIN>
 __device__ __forceinline__ void process_unit_f32(float4 (&d)[8], const float (&xrow)[12],
                                                  const WIN &next, StripF32 &st,
                                                  double &stress, __amdgpu_buffer_rsrc_t row_rsrc,
-                                                 unsigned row_voff, int stage_idx,
-                                                 const float (&sel)[12]) {
+                                                 unsigned row_voff, int stage_idx) {
     extern __shared__ __attribute__((aligned(16))) float row_lds[];
     f32x2 s2 = {0.f, 0.f};
-    // The 12 row sums of the unit are collected into lanes 48..59 of one register
-    // (after the reduction every lane >= 48 holds the wave total) and leave with
-    // ONE 48-byte store per unit: a 12-byte store per row costs as much VMEM issue
-    // as a 1-KiB load and measured 5.6 % of the kernel.
-    const int slot = (int)(threadIdx.x & 63) - 48;  // value index this lane keeps, if 0..11
-    const int comp = slot - 3 * (slot / 3);     // 0,1,2 = x,y,z
+    // The 12 row sums of the unit are collected into lanes 0..3, 16..19 and 32..35 of one
+    // register and leave with ONE 48-byte store per unit: a 12-byte store per row costs as
+    // much VMEM issue as a 1-KiB load and measured 5.6 % of the kernel.
     float keep = 0.f;
-    f32x4v acc = {0.f, 0.f, 0.f, 0.f};
-    // (row_sum3_swap) the matrix row of the unit whose sum this lane keeps, or -1
+    // the matrix row of the unit whose sum this lane keeps, or -1
     const int swap_role = (((threadIdx.x & 15) < 4) && ((threadIdx.x & 63) < 48)) ? (int)(threadIdx.x & 15) : -1;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -572,55 +509,23 @@ __device__ __forceinline__ void process_unit_f32(float4 (&d)[8], const float (&x
         f32x2 rx, ry, rz, qx, qy, qz;  // row-side sums of load 0 / load 1
         pair_step2<0, 0, true, OP>(f32x2{d[2 * r].x, d[2 * r].y}, xi, yi, zi, st, rx, ry, rz, s2);
         pair_step2<0, 1, false, OP>(f32x2{d[2 * r].z, d[2 * r].w}, xi, yi, zi, st, rx, ry, rz, s2);
-        if constexpr (REFILL) d[2 * r] = next.template load<NT>(2 * r);
+        d[2 * r] = next.template load<NT>(2 * r);
         // (no sched_barrier here: letting the scheduler mix the rows of a unit measured
         // 1 % faster at N=50k and 6 % faster at 1/8 size; it stays within 125 VGPRs)
         pair_step2<1, 0, true, OP>(f32x2{d[2 * r + 1].x, d[2 * r + 1].y}, xi, yi, zi, st, qx, qy, qz, s2);
         pair_step2<1, 1, false, OP>(f32x2{d[2 * r + 1].z, d[2 * r + 1].w}, xi, yi, zi, st, qx, qy, qz, s2);
-        if constexpr (REFILL) d[2 * r + 1] = next.template load<NT>(2 * r + 1);
+        d[2 * r + 1] = next.template load<NT>(2 * r + 1);
         rx += qx; ry += qy; rz += qz;
-        float gx = rx.x + rx.y, gy = ry.x + ry.y, gz = rz.x + rz.y;
-        if constexpr (abl::kSwapRowSum) {
-            const float w = row_sum3_swap(gx, gy, gz);
-            keep = (swap_role == r) ? w : keep;
-        } else if constexpr (abl::kDppRowSum) {
-            if constexpr (!abl::kNoDpp) wave_sum_hi3(gx, gy, gz);
-            const float mine = comp == 0 ? gx : (comp == 1 ? gy : gz);
-            keep = (slot >= 3 * r && slot < 3 * r + 3) ? mine : keep;
-        } else {
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(gx, sel[3 * r + 0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(gy, sel[3 * r + 1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(gz, sel[3 * r + 2], acc, 0, 0, 0);
-        }
+        const float gx = rx.x + rx.y, gy = ry.x + ry.y, gz = rz.x + rz.y;
+        const float w = row_sum3_swap(gx, gy, gz);
+        keep = (swap_role == r) ? w : keep;
     }
-    if constexpr (!abl::kDppRowSum && !abl::kSwapRowSum) {
-        // lane (g = lane / 16, j = lane % 16) holds rows 4g..4g+3 of column j: add them, then
-        // the four lane groups (gfx950 lane swaps: VALU, no LDS); every lane with
-        // lane % 16 == v then holds the unit's sum v -- lanes 48..59 keep theirs
-        float t = (acc.x + acc.y) + (acc.z + acc.w);
-        t = swap_sum16(t);
-        keep = swap_sum32(t);
-    }
-    if constexpr (abl::kNoStore) {
-        asm volatile("" ::"v"(keep));
-    } else {
-        // DEFER: both are issued for every unit and exactly one of them lands -- the LDS
-        // slot is a dummy word while the unit is stored directly, the store's lanes are
-        // all out of range (free) while the unit is parked (see the kernel)
-        if constexpr (DEFER) row_lds[stage_idx] = keep;
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(keep), row_rsrc, row_voff, 0, 0);
-    }
+    // both are issued for every unit and exactly one of them lands -- the LDS slot is a
+    // dummy word while the unit is stored directly, the store's lanes are all out of
+    // range (free) while the unit is parked (see the kernel's DEFER)
+    row_lds[stage_idx] = keep;
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(keep), row_rsrc, row_voff, 0, 0);
     stress += (double)(s2.x + s2.y);
-    if constexpr (abl::kSchedRefill > 0) {
-        // experiment (-DBB_SCHED_REFILL=n): ask the scheduler for a refill after every n VALU
-        // instructions, i.e. right behind the half row it replaces, instead of where it
-        // puts them by itself (two in the middle of the unit, six at its end)
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            __builtin_amdgcn_sched_group_barrier(0x002, abl::kSchedRefill, 0);   // VALU
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                   // one VMEM read
-        }
-    }
 }
 
 __device__ __forceinline__ void load_strip_f32(StripF32 &st, const float *__restrict__ X, int j0,
@@ -711,25 +616,6 @@ __device__ __forceinline__ void store_strip(const T (&gc)[(Lay<T, W>::LPR)][Trai
     }
 }
 
-// Diagnostic build only (-DBB_WAVE_TRACE): time stamp k (0..7) of wave w, 10-ns ticks of the
-// constant-rate clock, into a region of its own behind the per-wave stress partials
-// (nothing reads it but bb_solver_debug_wave_trace).  Folds away in the product build.
-__device__ __forceinline__ void wave_stamp(double *stresspart, int n_waves, int w, int k) {
-    if constexpr (abl::kWaveTrace || abl::kUnitTrace) {
-        if ((threadIdx.x & 63) == 0) {
-            unsigned long long *t = reinterpret_cast<unsigned long long *>(stresspart + n_waves);
-            unsigned long long v = (unsigned long long)wall_clock64();
-            if (k == 4) {     // where the wave ran: XCC id | HW_ID
-                unsigned xcc, hw;
-                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-                v = ((unsigned long long)xcc << 32) | hw;
-            }
-            t[(long long)w * 8 + k] = v;
-        }
-    }
-}
-
 // One wave = one contiguous chunk of units; 4 independent waves per workgroup.
 // No LDS, no barriers, no atomics: results are bitwise reproducible.
 //
@@ -747,7 +633,7 @@ __device__ __forceinline__ void wave_stamp(double *stresspart, int n_waves, int 
 //   stresspart one double per wave: the stress of the strip the wave ENDS in
 //   stress_slot one double per private column slot: the stress of a strip the wave left
 //
-// DEFER (fp32 only): the row sums do not leave the wave unit by unit.  Writing 48
+// DEFER (fp32 and fp64 wide): the row sums do not leave the wave unit by unit.  Writing 48
 // bytes to a fresh line per 8 KiB read costs 7.5 % of the kernel at N=50k, and not in
 // issue: a store whose lanes are all out of range is free, so is one that keeps
 // hitting the same line, and grouping 16 units into 768-byte bursts changes nothing
@@ -757,44 +643,38 @@ __device__ __forceinline__ void wave_stamp(double *stresspart, int n_waves, int 
 // row sums fits in LDS (cap_units * 48 B per wave: N=50k on one GPU, every multi-GPU
 // share), they are parked there and written out as one contiguous burst when the
 // wave has finished reading: -5.8 % kernel time at N=50k.  A longer chunk parks its
-// LAST cap_units units and stores the ones before them directly.
+// LAST cap_units units and stores the ones before them directly.  A property of the
+// layout, not a launch choice: a rank without units (cap_units = 0) parks nothing.
 //
 // WPB = waves per workgroup.  4: one wave per SIMD and workgroup.  8 (used when a CU
 // holds 8 waves): the two waves that share a SIMD -- wave k and k + 4 -- sit in ONE
 // workgroup and keep each other's pace.  Left alone, the SIMD's issue arbitration favours
 // the older of two co-resident waves on every conflict, and with static, equal chunks
-// that adds up: per-wave time stamps (tools/wave_trace.py) have the favoured partner
+// that adds up: per-wave time stamps have the favoured partner
 // finish its chunk 15-25 % before the other, which then runs the tail alone with half the
 // bytes in flight.  Each wave posts the number of units it has done in LDS and reads its
 // partner's; whoever is behind raises its priority (s_setprio) for the next unit.  The
 // results do not depend on any of it: chunks, slots and summation order stay static.
-template <typename T, bool W, bool NT, int OP, bool DEFER, int WPB>
+template <typename T, bool W, bool NT, int OP, int WPB>
 __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_kernel(
     const T *__restrict__ units, const T *__restrict__ X, const int2 *__restrict__ udesc,
     int chunk_q, int chunk_r, const int2 *__restrict__ wave_slots, T *__restrict__ rowpart,
     T *__restrict__ colpart, double *__restrict__ stresspart, int cap_units, int lds_wave_floats,
-    int wg_map, int dense_u0, double *__restrict__ stress_slot) {
+    int dense_u0, double *__restrict__ stress_slot) {
     using Vec = typename Traits<T>::Vec;
     constexpr int VPL = Traits<T>::VPL;
     constexpr int VW = Lay<T, W>::VW;
+    constexpr bool DEFER = sizeof(T) == 4 || W;
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave in workgroup
-    // Which run of WPB chunks this workgroup sweeps: a bijection of the block index (the
-    // host checks it is one).  0: the identity.  m > 0: (b * m) mod n.  -1: block b -- on XCD
-    // b mod 8 under round-robin placement -- takes chunk (b mod 8) * n / 8 + b / 8, i.e.
-    // every XCD sweeps one contiguous eighth of the units.  Speed only: every chunk is swept
-    // exactly once whatever the placement.
-    const int wg = wg_map == 0 ? (int)blockIdx.x
-                 : wg_map > 0 ? (int)(((unsigned)blockIdx.x * (unsigned)wg_map) % gridDim.x)
-                              : (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3));
+    // workgroup b sweeps the b-th run of WPB chunks (permuting that map by XCD changed
+    // nothing: docs/EXPERIMENTS.md)
+    const int wg = (int)blockIdx.x;
     const int w = wg * WPB + wib;
     // wave w owns units [w*q + min(w, r), +q (+1 if w < r)): arithmetic, not a table --
     // one dependent memory round trip less before the wave's first matrix load
     const int ua = w * chunk_q + (w < chunk_r ? w : chunk_r);
     const int ub = ua + chunk_q + (w < chunk_r ? 1 : 0);
-    const int n_waves_all = gridDim.x * WPB;
-    wave_stamp(stresspart, n_waves_all, w, 0);      // (diagnostic build only)
-    wave_stamp(stresspart, n_waves_all, w, 4);
     double stress = 0.0;
     // the shared column slots of this workgroup's waves (epilogue), read NOW: behind the
     // fences further down the compiler no longer takes them through the scalar cache, and a
@@ -815,9 +695,6 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
     double sel[6];
 #pragma unroll
     for (int v = 0; v < 6; ++v) sel[v] = (lane & 15) == v ? 1.0 : 0.0;
-    float sel32[12];   // the same for the 12 row sums of an fp32 unit (process_unit_f32)
-#pragma unroll
-    for (int v = 0; v < 12; ++v) sel32[v] = (lane & 15) == v ? 1.f : 0.f;
 
     if (ua < ub) {
         int slot = wave_slots[w].x;
@@ -878,8 +755,7 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
             T v;
             __device__ __forceinline__ T get(int q) const { return lane_value(v, q); }
         };
-        using XRow = typename std::conditional<Lay<T, W>::SCALAR_XROW && !abl::kXrowVector, XRowS,
-                                               XRowV>::type;
+        using XRow = typename std::conditional<Lay<T, W>::SCALAR_XROW, XRowS, XRowV>::type;
         auto xrow_load = [&](int i0) __attribute__((always_inline)) {
             XRow x;
             if constexpr (std::is_same<XRow, XRowS>::value) {
@@ -892,34 +768,20 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
             return x;
         };
         XRow xr = xrow_load(dc.x);
-        using Win = typename std::conditional<abl::kGlobalWindow, WinPtr<Vec>, WinBuf<Vec>>::type;
-        // the wave's chunk as a buffer: (ub - ua) units of 8 KiB (< 4 GiB: the host checks)
-        const __amdgpu_buffer_rsrc_t win_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<T *>(units) + (int64_t)ua * (8192 / (int)sizeof(T)), 0,
-            (int)((unsigned)(ub - ua) * 8192u), 0x00020000);
+        using Win = WinPtr<Vec>;
         auto window_of = [&](int u_next) __attribute__((always_inline)) {
-            if constexpr (abl::kGlobalWindow) {
-                // The refills of the wave's LAST unit are never consumed.  They stay in the
-                // loop (a branch around them would cost every unit its exact wait counts),
-                // but all lanes ask for the same 16 bytes of the chunk's last unit: 8 lines
-                // instead of 8 KiB per wave and launch (1.3-2.7 % of the bytes of a 1/8 share
-                // of N=50k), back at once, so the epilogue gets the window's registers early.
-                const bool real = u_next < ub;
-                return Win{unit_ptr<T>(units, real ? u_next : ub - 1, real ? lane : 0)};
-            } else {
-                return Win{win_rsrc, (unsigned)(u_next - ua) * 8192u + (unsigned)lane * 16u};
-            }
+            // The refills of the wave's LAST unit are never consumed.  They stay in the
+            // loop (a branch around them would cost every unit its exact wait counts),
+            // but all lanes ask for the same 16 bytes of the chunk's last unit: 8 lines
+            // instead of 8 KiB per wave and launch (1.3-2.7 % of the bytes of a 1/8 share
+            // of N=50k), back at once, so the epilogue gets the window's registers early.
+            const bool real = u_next < ub;
+            return Win{unit_ptr<T>(units, real ? u_next : ub - 1, real ? lane : 0)};
         };
         {
             const Win first = window_of(ua);
 #pragma unroll
             for (int r = 0; r < 8; ++r) d[r] = first.template load<NT>(r);
-        }
-        if constexpr (abl::kWaveTrace) {     // diagnostic build: when does the first data land?
-            asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-            wave_stamp(stresspart, n_waves_all, w, 5);           // first 1 KiB of the window
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            wave_stamp(stresspart, n_waves_all, w, 6);           // all 8 KiB of it
         }
         // this wave's row partials: 3*RPU elements per unit of its group's chunk
         constexpr unsigned kRowBytes = 3 * Lay<T, W>::RPU * sizeof(T);
@@ -927,32 +789,15 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
             rowpart + (int64_t)ua * (3 * Lay<T, W>::RPU), 0, (int)((unsigned)(ub - ua) * kRowBytes),
             0x00020000);
 
-        // `first`: the peeled first unit of a strip (a timing experiment may treat it apart)
-        // -DBB_UNIT_TRACE: the time at the top of unit k goes to LDS slot k of the wave one
-        // unit later (by then it has certainly arrived: no wait of its own), branch-free
-        unsigned long long t_prev = 0;
-        unsigned long long *ut_lds = reinterpret_cast<unsigned long long *>(
-            row_lds + WPB * lds_wave_floats + 8 + 2 * abl::kUnitTraceSlots * wib);
-        auto unit_stamp = [&](int k) __attribute__((always_inline)) {
-            if constexpr (abl::kUnitTrace) {
-                const unsigned long long t_now = (unsigned long long)wall_clock64();
-                const int sl = (lane == 0 && k >= 1 && k <= abl::kUnitTraceSlots - 2)
-                                   ? k - 1 : abl::kUnitTraceSlots - 1;   // last slot: dummy
-                ut_lds[sl] = t_prev;
-                t_prev = t_now;
-            }
-        };
         // fp32: which of a unit's 12 row sums this lane holds -- lanes 0..3 / 16..19 / 32..35
-        // after the lane swaps (row_sum3_swap), lanes 48..59 after the DPP tree -- and what
-        // follows from it for the unit's store offset and parking slot
-        const int f32_sl12 = abl::kSwapRowSum ? swap_rowsum_slot(lane)
-                                              : (lane >= 48 && lane < 60 ? lane - 48 : -1);
+        // after the lane swaps (row_sum3_swap) -- and what follows from it for the unit's
+        // store offset and parking slot
+        const int f32_sl12 = swap_rowsum_slot(lane);
         const unsigned f32_voff_lane = f32_sl12 >= 0 ? (unsigned)f32_sl12 * 4u : 0x40000000u;
         const int f32_lds_dummy = stage0 + cap_units * 12 + (lane & 3);
         const int f32_lds_real = f32_sl12 >= 0 ? stage0 + f32_sl12 : f32_lds_dummy;
         const int f32_m12 = f32_sl12 >= 0 ? 12 : 0;
-        auto unit_step = [&](int u, auto first) __attribute__((always_inline)) {
-            unit_stamp(u - ua);
+        auto unit_step = [&](int u) __attribute__((always_inline)) {
             if constexpr (WPB == 8) {
                 // pace keeping (see the kernel's comment): the partner's count was read
                 // one unit ago, so nothing here waits on LDS
@@ -972,7 +817,7 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
             unsigned row_voff;
             int stage_slot = 0;
             if constexpr (sizeof(T) == 4) {
-                // fp32: lanes 48..59 hold one of the unit's 12 sums each.  Units before
+                // fp32: 12 lanes hold one of the unit's 12 sums each.  Units before
                 // park_from are stored directly; the later ones are parked in LDS slot
                 // (k - park_from) and their store is dropped (every lane out of range).
                 // per-lane parts are loop constants (f32_voff_lane, f32_lds_real / _dummy,
@@ -981,15 +826,15 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
                 // of range (dropped) unless the lane holds a sum AND the unit is not parked:
                 // 0x40000000 from either side puts the offset beyond any chunk.
                 const int k = u - ua;
-                const bool parked = DEFER && k >= park_from;
+                const bool parked = k >= park_from;
                 row_voff = f32_voff_lane + (parked ? 0x40000000u : (unsigned)k * kRowBytes);
                 stage_slot = (parked ? f32_lds_real : f32_lds_dummy) +
                              (parked ? k - park_from : 0) * f32_m12;
-            } else if constexpr (W && !abl::kF64Generic) {
+            } else if constexpr (W) {
                 // fp64, 2 x 512 units: lanes 48..53 hold one of the unit's 6 sums each
                 // (parking as in fp32; an LDS slot is 4 bytes, a sum takes two)
                 const int k = u - ua;
-                const bool parked = DEFER && k >= park_from;
+                const bool parked = k >= park_from;
                 const bool mine = lane >= 48 && lane < 54;
                 row_voff = (mine && !parked) ? (unsigned)k * kRowBytes + (unsigned)(lane - 48) * 8u
                                              : kDropOffset;
@@ -999,15 +844,15 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
                 row_voff = lane == 63 ? (unsigned)(u - ua) * kRowBytes : kDropOffset;
             }
             if constexpr (sizeof(T) == 4) {
-                float xs12[12];             // scalar registers in the product build
+                float xs12[12];             // scalar registers
 #pragma unroll
                 for (int q = 0; q < 12; ++q) xs12[q] = xr.get(q);
-                process_unit_f32<NT, OP, DEFER, !(decltype(first)::value && abl::kNoRefillFirst)>(
-                    d, xs12, window_of(u + 1), st, stress, row_rsrc, row_voff, stage_slot, sel32);
+                process_unit_f32<NT, OP>(d, xs12, window_of(u + 1), st, stress, row_rsrc, row_voff,
+                                         stage_slot);
             }
-            else if constexpr (W && !abl::kF64Generic)
-                process_unit_f64w<NT, OP, DEFER>(d, xr, window_of(u + 1), st.xj, st.gc,
-                                                 sel, stress, row_rsrc, row_voff, stage_slot);
+            else if constexpr (W)
+                process_unit_f64w<NT, OP>(d, xr, window_of(u + 1), st.xj, st.gc, sel, stress,
+                                          row_rsrc, row_voff, stage_slot);
             else
                 process_unit<T, W, NT, OP>(d, xr, window_of(u + 1), st.xj, st.gc, stress,
                                        row_rsrc, row_voff);
@@ -1016,65 +861,23 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
             dn = dnn;
         };
         // Outer loop: one trip per column strip the wave's sweep crosses (rare).
-        // Inner loop: the units of that strip, with NO branch in the body.  Its
-        // first unit is peeled, so the inner loop is only ever entered from a
-        // state with the loop body's own pattern of outstanding loads and
-        // stores: hipcc's s_waitcnt counts are static and are merged over every
-        // entry of a loop header, and a prologue- or strip-change-shaped entry
-        // drains most of the 8-row prefetch window on every iteration.
-        if constexpr (abl::kUnitTrace) {
-            // slots 5 / 7 of the wave: shader clock (s_memtime) and 100-MHz clock when its
-            // loop begins (stored now: nothing is carried through the loop); slot 6 at its end
-            if (lane == 0) {
-                unsigned long long *t8 = reinterpret_cast<unsigned long long *>(stresspart + n_waves_all);
-                t8[(long long)w * 8 + 5] = (unsigned long long)__builtin_amdgcn_s_memtime();
-                t8[(long long)w * 8 + 7] = (unsigned long long)wall_clock64();
-            }
-        }
+        // Inner loop: the units of that strip, with NO branch in the body.
         int u = ua;
         for (;;) {
             const int curj = dc.y;
             strip_load(curj);
-            if constexpr (abl::kWarmup > 0) {
-                if (u == ua) {
-                    typedef float f2 __attribute__((ext_vector_type(2)));
-                    f2 a0 = {1.f, 1.f}, a1 = a0, a2 = a0, a3 = a0;
-                    const f2 m = {0.999f, 1.001f};
-                    for (int i = 0; i < abl::kWarmup; ++i)
-                        asm volatile("v_pk_fma_f32 %0, %0, %4, %4\n\tv_pk_fma_f32 %1, %1, %4, %4\n\t"
-                                     "v_pk_fma_f32 %2, %2, %4, %4\n\tv_pk_fma_f32 %3, %3, %4, %4"
-                                     : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3)
-                                     : "v"(m));
-                    asm volatile("" ::"v"(a0), "v"(a1), "v"(a2), "v"(a3));
-                }
-            }
-            if constexpr (abl::kWaveTrace) {
-                if (u == ua) {
-                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                    wave_stamp(stresspart, n_waves_all, w, 7);   // column + row coordinates here
-                }
-            }
-            if constexpr (abl::kPeelFirstUnit || abl::kWaveTrace) {   // (the trace stamps unit 1)
-                unit_step(u, std::true_type{});
-                if (u == ua) wave_stamp(stresspart, n_waves_all, w, 1);   // first unit done
+            // ONE copy of the unit body, entered with nothing in flight: hipcc's s_waitcnt
+            // counts are static and merged over every entry of a loop header, and a
+            // prologue- or strip-change-shaped entry would drain most of the 8-row prefetch
+            // window on every iteration.  The strip's coordinates have to be here anyway,
+            // and they were asked for after the window, so the wait counts inside the loop
+            // are those of the back edge alone.  Same speed as peeling the first unit at
+            // every size (profiles/archive/r02_peel_ab.txt), a third less code.
+            __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+            do {
+                unit_step(u);
                 ++u;
-                while (u < ub && dc.y == curj) {
-                    unit_step(u, std::false_type{});
-                    ++u;
-                }
-            } else {
-                // ONE copy of the unit body.  The loop is entered with nothing in flight:
-                // the strip's coordinates have to be here anyway, and they were asked
-                // for after the window -- so the compiler's wait counts inside the loop
-                // are those of the back edge alone, which is what round 1 peeled the first
-                // iteration for.  Same speed as the peeled form at every size
-                // (profiles/archive/r02_peel_ab.txt), a third less code.
-                __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-                do {
-                    unit_step(u, std::false_type{});
-                    ++u;
-                } while (u < ub && dc.y == curj);
-            }
+            } while (u < ub && dc.y == curj);
             if (u >= ub) break;      // the wave's last strip: its column partial goes out below
             strip_store(slot);
             // the stress of the strip left behind goes with its slot (rare: once per strip a
@@ -1091,22 +894,6 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
             // done: the partner stops yielding
             __hip_atomic_store(progress + wib, 0x7fffffff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             __builtin_amdgcn_s_setprio(0);
-        }
-        wave_stamp(stresspart, n_waves_all, w, 2);                    // last unit consumed
-        if constexpr (abl::kUnitTrace) {
-            if (lane == 0) {
-                unsigned long long *t8 = reinterpret_cast<unsigned long long *>(stresspart + n_waves_all);
-                t8[(long long)w * 8 + 6] = (unsigned long long)__builtin_amdgcn_s_memtime();
-            }
-            // slot k = top of unit k, slot n = end of the last unit; out to HBM behind the stamps
-            unit_stamp(ub - ua);
-            unit_stamp(ub - ua + 1);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            unsigned long long *out = reinterpret_cast<unsigned long long *>(stresspart + n_waves_all * 9) +
-                                      (long long)w * abl::kUnitTraceSlots;
-            for (int q = lane; q < abl::kUnitTraceSlots - 1; q += 64)
-                out[q] = q <= ub - ua && q <= abl::kUnitTraceSlots - 3 ? ut_lds[q] : 0ull;
         }
         if constexpr (DEFER) {
             // the chunk's row sums, 48 bytes per unit in either precision (12 floats or
@@ -1140,7 +927,7 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
     // workgroup are added here, in wave order (fixed), and leave as one slot -- an eighth
     // of the bytes for the sweep to write and for the reduce to read back.  wave_slots[].y
     // names the shared slot; waves of one workgroup that end in the same strip carry the
-    // same number (the host deals them, and with BB_WG_COLSUM=0 deals every wave its own).
+    // same number (the host deals them).
     // The barrier orders LDS only: __syncthreads() is also a release of the wave's global
     // stores, and waiting here for the acknowledgement of the row-sum burst (s_waitcnt vmcnt
     // in front of s_barrier) kept every wave 1-2 us at the end of every launch.
@@ -1174,22 +961,15 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
     // of the launch: six __shfl_down steps of a double are twelve ds_bpermute)
     stress = wave_sum_hi(stress);
     if (lane == 63) stresspart[w] = stress;
-    wave_stamp(stresspart, n_waves_all, w, 3);                        // partials issued
 }
 
 // --------------------------------------------------------------------------
 // reduce (+ update) kernel: one workgroup per vw-bin block
 // --------------------------------------------------------------------------
-#ifndef BB_REDUCE_BATCH
-#define BB_REDUCE_BATCH 16
-#endif
-constexpr int kReduceSlice = BB_REDUCE_BATCH;  // chunks per stage-1 slice = chunks loaded per round trip
-
 enum ReduceMode {
     kReduceApply = 0,      // X -= lr * 2 * sum
     kReduceExchange = 1,   // exch = 2 * sum (+ stress hi/lo)
     kReduceStressOnly = 2, // stress only
-    kReducePartial = 3,    // stage 1: raw sum of one slice of a block's chunk list
     kReducePeer = 4        // 2 * sum (+ stress hi/lo) stored into this rank's slot on every peer
 };
 
@@ -1219,16 +999,13 @@ constexpr unsigned long long kPeerPoison = ~0ull;
 
 template <typename T>
 struct ReduceParams {
-    const T *__restrict__ part;              // rowpart | colpart
-    const int64_t *__restrict__ blk_ptr;     // n_blocks + 1
-    const int64_t *__restrict__ blk_chunk;   // element offsets into part
+    const T *__restrict__ part;              // rowpart | colpart | a chunk of zeros
     const double *__restrict__ stresspart;
     T *__restrict__ X;                       // apply mode
     T *__restrict__ V;                       // apply mode: velocity (heavy-ball momentum)
     T mu;                                    // momentum coefficient, 0 = plain gradient step
     T scale;                                 // 2 for the gradient (SPEC 2.3), 1 for a matvec
     T *__restrict__ exch;                    // exchange mode: [3*n_pad | hi | lo]
-    T *__restrict__ part_out;                // partial mode: CH elements per workgroup
     const PeerTable<T> *__restrict__ peer;   // peer mode: destinations, in device memory
     unsigned *__restrict__ peer_counter;     // peer mode: workgroups done (last one raises flags)
     const PeerState *peer_state;             // peer mode: a failed rank pushes nothing
@@ -1276,124 +1053,19 @@ __device__ __forceinline__ double stress_share(const ReduceParams<T> &p, int m, 
     return s;
 }
 
-constexpr int kRedWG = 128;  // threads per reduce workgroup = elements it sums
-// Grid: x = the block (or stage-1 slice) of the list, y = which kRedWG of the block's
-// 3*vw elements.  One element per thread: a thread's whole slice -- up to kBatch chunks
-// -- is in flight before its first add, so a launch costs about one memory round trip,
-// and a problem of B blocks puts B * (3*vw/128) workgroups on the chip instead of B
-// (N=17,700: 35 blocks used 35 CUs and 18 us for the two stages).
-template <typename T, bool W>
-__global__ __launch_bounds__(kRedWG) void reduce_kernel(ReduceParams<T> p) {
-    constexpr int CH = 3 * Lay<T, W>::VW;
-    static_assert(CH % kRedWG == 0, "3*vw is a multiple of the workgroup size");
-    const int tid = threadIdx.x;
-    const int b = blockIdx.x;
-    const int e = (int)blockIdx.y * kRedWG + tid;      // element of the block, < CH
-    __shared__ __attribute__((aligned(16))) T push_stage[kRedWG];   // peer mode only
-    // peer mode: once this rank's exchange has failed it stops delivering (the status
-    // word is only ever written by peer_receive_kernel, i.e. between reduce launches: uniform)
-    const bool peer_live =
-        p.mode != kReducePeer ||
-        __hip_atomic_load(&p.peer_state->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
-    if (p.mode != kReduceStressOnly) {
-        const int64_t k0 = p.blk_ptr[b], k1 = p.blk_ptr[b + 1];
-        T acc = T(0);
-        // Chunks are summed in list order (deterministic).
-        constexpr int kBatch = kReduceSlice;
-        for (int64_t k = k0; k < k1; k += kBatch) {
-            T v[kBatch];
-#pragma unroll
-            for (int q = 0; q < kBatch; ++q) {
-                const bool on = k + q < k1;
-                v[q] = on ? p.part[p.blk_chunk[on ? k + q : k0] + e] : T(0);
-            }
-#pragma unroll
-            for (int q = 0; q < kBatch; ++q) acc += v[q];
-        }
-        const int64_t o = (int64_t)b * CH + e;
-        if (p.mode == kReducePartial) {
-            p.part_out[o] = acc;
-        } else {
-            const T g = p.bin_scale ? p.bin_scale[o / 3] * (p.scale * acc) : p.scale * acc;
-            if (p.mode == kReduceApply) {
-                // SPEC 2.4: V <- mu V - lr g ; X <- X + V   (mu = 0: X -= lr g)
-                const T v = p.mu * p.V[o] - p.lr * g;
-                p.V[o] = v;
-                p.X[o] += v;
-            } else if (p.mode == kReducePeer) {
-                push_stage[tid] = g;
-            } else {
-                p.exch[o] = g;
-            }
-        }
-        if (p.mode == kReducePeer && peer_live) {
-            // the workgroup's values go out as 16-byte stores, one wave instruction per
-            // peer: what crosses xGMI is 512-byte (fp32) / 1-KiB (fp64) bursts
-            typedef T vec_t __attribute__((ext_vector_type(16 / sizeof(T))));
-            constexpr int NV = kRedWG * (int)sizeof(T) / 16;
-            __syncthreads();
-            if (tid < NV && (p.peer_mask == nullptr || (p.peer_mask[b] >> p.rank & 1u))) {
-                const vec_t val = ((const vec_t *)push_stage)[tid];
-                for (int q = 0; q < p.n_peers; ++q)
-                    ((vec_t *)(p.peer->dst[q] + (int64_t)b * CH + (int64_t)blockIdx.y * kRedWG))[tid] = val;
-            }
-        }
-    }
-    if (p.mode == kReducePartial) return;
-    if (b < (p.n_maps > 1 ? p.n_maps : 1) && blockIdx.y == 0) {
-        __shared__ double sh[kRedWG];
-        sh[tid] = stress_share(p, b, tid, kRedWG);
-        __syncthreads();
-        for (int off = kRedWG / 2; off > 0; off >>= 1) {
-            if (tid < off) sh[tid] += sh[tid + off];
-            __syncthreads();
-        }
-        if (tid == 0) {
-            const double S = sh[0];
-            if (p.mode == kReduceExchange) {
-                const T hi = (T)S;
-                p.exch[3 * p.n_pad] = hi;
-                p.exch[3 * p.n_pad + 1] = (T)(S - (double)hi);
-            } else if (p.mode == kReducePeer) {
-                const T hi = (T)S, lo = (T)(S - (double)hi);
-                for (int q = 0; q < (peer_live ? p.n_peers : 0); ++q) {
-                    p.peer->dst[q][3 * p.n_pad] = hi;
-                    p.peer->dst[q][3 * p.n_pad + 1] = lo;
-                }
-            } else {
-                p.stress_out[b] = S;
-            }
-        }
-    }
-    if (p.mode == kReducePeer && peer_live) {
-        // Every workgroup makes its stores visible system-wide and checks in; the
-        // last one to do so raises this rank's flag on every peer (release).
-        __shared__ int last;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");   // system scope
-        __syncthreads();
-        if (tid == 0) last = atomicAdd(p.peer_counter, 1u) == gridDim.x * gridDim.y - 1;
-        __syncthreads();
-        if (last) {
-            if (tid == 0) atomicExch(p.peer_counter, 0u);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            if (tid < p.n_peers)
-                __hip_atomic_store(p.peer->flag[tid], p.seq, __ATOMIC_RELEASE,
-                                   __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-}
+constexpr int kRedWG = 128;  // elements a reduce workgroup sums
 
 
 // ---- the reduce in ONE launch of one memory round trip (round 3) ------------------
-// reduce_kernel above walks a block's list with one thread per element: a list of L chunks
-// is ceil(L / 16) dependent round trips behind three more (kernel arguments -> blk_ptr ->
-// blk_chunk), and lists beyond 128 chunks take a second launch.  The kernel trace has that
+// Round 2's reduce walked a block's list with one thread per element: a list of L chunks was
+// ceil(L / 16) dependent round trips behind three more (kernel arguments -> list pointer ->
+// list), and lists beyond 128 chunks took a second launch.  The kernel trace had that
 // chain at 6.2-7.4 us per iteration from N=8,000 to 17,700 and 11-13 us at N=24,926 -- 6 % of
 // a 1/8 share of N=50k.  Here a workgroup is 128 elements x S slices of the list (S = 4 or
 // 8): every thread has its whole slice -- 16 chunks per trip -- in flight at once, the
 // slices meet in LDS and are added in slice order (fixed: bitwise reproducible), and the
 // lists come as ONE table of fixed stride (`list_stride` entries per block, padded with the
-// offset of a chunk of zeros), so the table's address does not wait for a blk_ptr and no
+// offset of a chunk of zeros), so the table's address does not wait for a list pointer and no
 // load is predicated.  A wave is one slice of 64 elements: its table entries are
 // wave-uniform and travel through the scalar cache.
 template <typename T, bool W, int S>
@@ -1486,7 +1158,7 @@ __global__ __launch_bounds__(128 * S) void reduce_sliced_kernel(ReduceParams<T> 
         // workgroup, behind a barrier that every storing wave reaches with its stores
         // acknowledged (__syncthreads() waits vmcnt(0)): a release is a write-back of the
         // XCD's L2, and with all 16 waves of the workgroup issuing one the push cost 33 us
-        // instead of 12 (tools/exchange_timing.py; reduce_kernel's workgroups have 2 waves).
+        // instead of 12 (tools/exchange_timing.py).
         // The wait is spelled out in EVERY storing wave: that __syncthreads() emits one is a
         // code-generation detail (the memory model lets a workgroup-scope release omit it), and
         // a flag that overtakes the data would make a peer sum stale partials silently.  It

@@ -635,17 +635,21 @@ def test_row_owner_threshold_both_sides(oracle, monkeypatch):
         assert _rel(got[path][0], X_ref) < 1e-12
 
 
-@pytest.mark.parametrize("world", [2, 3, 8])
+@pytest.mark.parametrize("world", [2, 3, 8, 400])
 def test_rank_shares_sum_to_full_gradient(oracle, world):
     """Each rank of a `world`-way job computes the gradient of its own units;
-    the sum over ranks (what the all-reduce produces) is the full gradient."""
+    the sum over ranks (what the all-reduce produces) is the full gradient.  With more
+    ranks than units (world = 400: fp32 has 384 units here) some ranks own none; their
+    sweep still runs, and they contribute exactly zero."""
     n = 1000
     xs, w, x0 = _problem(n)
     s_ref, g_ref = oracle.stress_grad(w, x0)
     for dtype, tol in (("float64", 1e-12), ("float32", 2e-6)):
         g_sum, s_sum = numpy.zeros((n, 3)), 0.0
+        empty = 0
         for rank in range(world):
             e = HipEngine(n, dtype, rank=rank, world=world)
+            lay = e.layout()
             e.set_wish_dense(w, "wish", 3.0)
             e.set_coords(x0)
             e.grad()
@@ -654,7 +658,11 @@ def test_rank_shares_sum_to_full_gradient(oracle, world):
             g_sum += host[:3 * n].reshape(n, 3)
             s_sum += float(host[-2]) + float(host[-1])
             assert not host[3 * n:-2].any()                 # padding bins carry no force
+            if lay["u_end"] == lay["u_begin"]:
+                assert not host.any()                       # no units: nothing at all
+                empty += 1
             e.close()
+        assert empty == max(0, world - lay["n_units"])
         assert abs(s_sum / s_ref - 1) < tol
         assert numpy.abs(g_sum - g_ref).max() < tol * numpy.abs(g_ref).max()
 
@@ -2225,17 +2233,17 @@ def test_eigenvector_reports_no_convergence():
     assert abs(cm.eigenvalue_ - 2.0) < 1e-4 and abs(numpy.linalg.norm(v) - 1) < 1e-12
 
 
-# ---- the knobs that keep older code paths alive still give the oracle's result --------------
-@pytest.mark.parametrize("env", [{"BB_REDUCE_OLD": "1"}, {"BB_REDUCE_SLICES": "4"},
+# ---- the knobs that reach product paths at this size still give the oracle's result ---------
+# (the ids are those the cases had when the list also held retired variants)
+@pytest.mark.parametrize("env", [{"BB_REDUCE_SLICES": "4"},
                                  {"BB_REDUCE_SLICES": "8"}, {"BB_ARITH_DESC": "0"},
-                                 {"BB_WG_MAP": "77"}, {"BB_WG_MAP": "-1"},
-                                 {"BB_WAVES_PER_CU": "8"}, {"BB_WAVES_PER_CU": "4", "BB_PAIR": "0"}])
+                                 {"BB_WAVES_PER_CU": "8"}, {"BB_WAVES_PER_CU": "4", "BB_PAIR": "0"}],
+                         ids=["env1", "env2", "env3", "env6", "env7"])
 @pytest.mark.parametrize("dtype,tol", [("float32", 1e-5), ("float64", 1e-12)])
 def test_sweep_and_reduce_variants_vs_oracle(oracle, monkeypatch, env, dtype, tol):
-    """The unit sweep with each of its run-time variants -- the round-2 two-stage reduce, the
-    sliced reduce with 4 and 8 slices, table descriptors, permuted / XCD-contiguous block
-    maps, 8 and 4 waves per CU -- against the oracle (N=5,000: 13 strips, several list
-    lengths)."""
+    """The unit sweep with each of its run-time variants -- the sliced reduce with 4 and 8
+    slices, table descriptors, 8 and 4 waves per CU -- against the oracle (N=5,000: 13
+    strips, several list lengths)."""
     monkeypatch.setenv("BB_ROW_OWNER_MAX", "0")
     for k, v in env.items():
         monkeypatch.setenv(k, v)

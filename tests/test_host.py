@@ -591,7 +591,7 @@ def _kernel_metadata(so_path):
     return out
 
 
-def test_no_product_kernel_spills():
+def test_product_kernels_do_not_spill():
     """round 3 shipped a 20-byte scratch spill in the narrow fp64 sweep and
     nothing noticed.  Every kernel of the product library must compile without scratch
     (private_segment_fixed_size = 0 in the code object's metadata), and the dominant
@@ -600,13 +600,14 @@ def test_no_product_kernel_spills():
         pytest.skip("no LLVM binutils here")
     meta = _kernel_metadata(_lib.LIB_PATH)
     assert meta.pop("__images__") >= 4, "one code object per .hip translation unit"
-    assert len(meta) > 120, "kernel metadata not found in %s" % _lib.LIB_PATH
+    assert len(meta) > 100, "kernel metadata not found in %s" % _lib.LIB_PATH   # 108 kernels
     for name in ("gram_kernel", "normalize128_kernel", "band_count", "downsample_kernel"):
         assert any(name in k for k in meta), name          # every translation unit was read
     spills = {k: v["scratch"] for k, v in meta.items() if v["scratch"] > 0}
     assert not spills, "kernels with scratch: %r" % spills
     sweeps = {k: v for k, v in meta.items() if "stress_grad_kernel" in k}
-    assert len(sweeps) >= 12
+    # one per layout (fp32, fp64 wide, fp64 narrow) x NT x OP x WPB (4; 8 for the 512-wide)
+    assert len(sweeps) == 20, sorted(sweeps)
     for k, v in sweeps.items():
         if "IfLb" in k:                       # fp32: two workgroups of 8 waves per CU
             assert v["vgpr"] <= 128, (k, v)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build tools/variants/libabl_<NAME>.so = the product sources + extra compiler flags
-# (ablation / diagnostic builds; load one with BB_LIB=$PWD/tools/variants/libabl_<NAME>.so).
-#   usage: tools/build_variant.sh NAME [flags...]      e.g.  tools/build_variant.sh TRACE -DBB_WAVE_TRACE
+# (A/B builds; load one with BB_LIB=$PWD/tools/variants/libabl_<NAME>.so).
+#   usage: tools/build_variant.sh NAME [flags...]
 set -euo pipefail
 cd "$(dirname "$0")/.."
 mkdir -p tools/variants

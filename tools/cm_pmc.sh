@@ -21,7 +21,6 @@ pairs = d * (d + 1) // 2
 alg = {"normalize128_kernel": ("8 B read + 16 B written per upper pair", pairs * 24),
        "column_sums_kernel": ("8 B per element", d * d * 8),
        "symv_upper_kernel": ("8 B per upper pair", pairs * 8),
-       "symv_kernel": ("8 B per element (both triangles)", d * d * 8),
        "gram_kernel": ("the centred matrix once (8 B per element; tiles re-read it from L2 / MALL)", d * d * 8),
        "center_rows_kernel": ("8 B read + 8 B written per element", d * d * 16),
        "center_rows_reg_kernel": ("8 B read + 8 B written per element", d * d * 16),
@@ -63,12 +62,12 @@ print("calibration (tools/probes/rw_probe, %.2f GB known): bytes per counted KiB
 f_r8, f_r16 = fac["read8"] or 2.0, fac["read16"] or 2.0
 f_w8 = fac["write8"] or 1.0
 print("ContactMap stage at d = 24,927 (4.97 GB fp64 matrix): largest dispatch of each kernel; HBM = FETCH_SIZE x 1024 x "
-      "read factor + WRITE_SIZE x 1024 x write factor (8 B/lane kernels; symv_kernel and gram_kernel load 16 B/lane)")
+      "read factor + WRITE_SIZE x 1024 x write factor (8 B/lane kernels; gram_kernel loads 16 B/lane)")
 print("%-30s %10s %12s %12s %10s %8s  %s" % ("kernel", "us", "alg GB", "HBM GB", "HBM/alg", "TB/s alg", "algorithmic bytes"))
 for k, (what, b) in alg.items():
     if k not in dur:
         continue
-    fr = f_r16 if k in ("symv_kernel", "gram_kernel") else f_r8
+    fr = f_r16 if k == "gram_kernel" else f_r8
     hbm = fetch.get(k, 0.0) * 1024 * fr + write.get(k, 0.0) * 1024 * f_w8
     print("%-30s %10.1f %12.3f %12.3f %10.3f %8.2f  %s" % (k, dur[k], b / 1e9, hbm / 1e9, hbm / b, b / dur[k] / 1e6, what))
 PY

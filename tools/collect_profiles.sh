@@ -22,5 +22,4 @@ cp $O/spectral_final.txt $P/${r}_spectral_timing.txt
 cp $O/batch_final.txt $P/${r}_batch.txt
 cp $O/pipeline_final.txt $P/${r}_pipeline_timing.txt
 python3 tools/pmc_merge.py final
-[ -f $O/utrace_f64.txt ] && cp $O/utrace_f64.txt $P/${r}_unit_trace_f64_n24926.txt
 ls $P | grep -c $r
