@@ -109,6 +109,7 @@ struct bb_solver {
     bool row_owner_built = false;        // created with the row-owner buffers (bb_solver_set_maps
                                          // switches row_owner off)
     bool bin_steps = false;              // d_bin_scale set by bb_solver_set_bin_steps / _block_steps
+    int weight_power = 0;                // SPEC 2.3.1: w = delta^-q, q in {0, 1, 2}
     void *d_full = nullptr, *d_X2 = nullptr;
     int64_t full_ld = 0;
     double *d_ro_part = nullptr;   // 2 x ro_blocks per-workgroup stress sums (ping-pong)
@@ -375,6 +376,13 @@ int build_indices(bb_solver *s) {
                           : ((s)->wide ? F<double, true>(__VA_ARGS__)    \
                                        : F<double, false>(__VA_ARGS__)))
 
+// the sweep kernel of an OP: weighted_sweep_kernel for the weighted stress (SPEC 2.3.1)
+template <typename T, bool W, bool NT, int OP, int WPB>
+constexpr auto sweep_kernel() {
+    if constexpr (is_weighted_op<OP>()) return weighted_sweep_kernel<T, W, NT, OP, WPB>;
+    else return stress_grad_kernel<T, W, NT, OP, WPB>;
+}
+
 template <typename T, bool W>
 int launch_grad_t(bb_solver *s, int op, const void *x_in) {
     const T *units = (const T *)s->d_units;
@@ -388,9 +396,10 @@ int launch_grad_t(bb_solver *s, int op, const void *x_in) {
     // once per instantiation: one bit per (WPB, NT, OP).
 #define BB_LAUNCH(NTV, OPV, WPBV)                                                               \
     do {                                                                                        \
-        auto kern = stress_grad_kernel<T, W, NTV, OPV, WPBV>;                                   \
+        auto kern = sweep_kernel<T, W, NTV, OPV, WPBV>();                                       \
         constexpr unsigned bit =                                                                \
-            1u << ((WPBV == 8 ? 4 : 0) + (NTV ? 2 : 0) + (OPV == kOpMatvec2 ? 1 : 0));          \
+            1u << ((WPBV == 8 ? 4 : 0) + (NTV ? 2 : 0) + (OPV == kOpMatvec2 ? 1 : 0) +          \
+                   (OPV == kOpStressW1 ? 8 : 0) + (OPV == kOpStressW2 ? 16 : 0));               \
         if (s->defer_lds_bytes > 0 && !(s->defer_attr_done & bit)) {                            \
             BB_HIP_CHECK(hipFuncSetAttribute((const void *)kern,                                \
                                              hipFuncAttributeMaxDynamicSharedMemorySize,        \
@@ -412,6 +421,10 @@ int launch_grad_t(bb_solver *s, int op, const void *x_in) {
     } while (0)
     if (op == kOpMatvec2) {
         if (s->nontemporal) BB_LAUNCH_WPB(true, kOpMatvec2); else BB_LAUNCH_WPB(false, kOpMatvec2);
+    } else if (op == kOpStressW1) {
+        if (s->nontemporal) BB_LAUNCH_WPB(true, kOpStressW1); else BB_LAUNCH_WPB(false, kOpStressW1);
+    } else if (op == kOpStressW2) {
+        if (s->nontemporal) BB_LAUNCH_WPB(true, kOpStressW2); else BB_LAUNCH_WPB(false, kOpStressW2);
     } else {
         if (s->nontemporal) BB_LAUNCH_WPB(true, kOpStress); else BB_LAUNCH_WPB(false, kOpStress);
     }
@@ -508,6 +521,9 @@ int launch_reduce_t(bb_solver *s, int mode, double lr, double *stress_out, doubl
 
 int launch_grad(bb_solver *s, int op = kOpStress, const void *x_in = nullptr) {
     if (!x_in) x_in = s->d_X;
+    // the stress and its gradient: weighted (SPEC 2.3.1) once a weight power is set
+    if (op == kOpStress && s->weight_power != 0)
+        op = s->weight_power == 1 ? kOpStressW1 : kOpStressW2;
     return BB_BY_LAYOUT(s, launch_grad_t, s, op, x_in);
 }
 int launch_reduce(bb_solver *s, int mode, double lr, double *stress_out,
@@ -648,14 +664,21 @@ int launch_row_owner_t(bb_solver *s, double lr, bool fold_prev, bool update) {
     double *hist_prev = fold_prev ? s->d_stress_hist + (s->hist_n - 1) : nullptr;
     // fold only: a grid of one workgroup, which is then the "last" = the fold workgroup
     const unsigned grid = update ? (unsigned)s->ro_blocks + 1u : 1u;
-#define BB_ROW(WPRV)                                                                             \
-    BB_HIP_CHECK(bb::launch(row_owner_kernel<T, WPRV>, dim3(grid), dim3(256), 0, s->stream,          \
+#define BB_ROW(WPRV, QV)                                                                         \
+    BB_HIP_CHECK(bb::launch(row_owner_kernel<T, WPRV, QV>, dim3(grid), dim3(256), 0, s->stream,          \
                             (const T *)s->d_full, s->full_ld, (int)s->L.n_bins, (const T *)s->d_X,  \
                             (T *)s->d_X2, (T *)s->d_V, (T)lr, (T)s->momentum, prev, s->ro_blocks,   \
                             hist_prev, out, (const T *)s->d_bin_scale))
-    if (s->ro_wpr == 4) BB_ROW(4);
-    else if (s->ro_wpr == 2) BB_ROW(2);
-    else BB_ROW(1);
+#define BB_ROW_Q(WPRV)                                                                           \
+    do {                                                                                         \
+        if (s->weight_power == 1) BB_ROW(WPRV, 1);                                               \
+        else if (s->weight_power == 2) BB_ROW(WPRV, 2);                                          \
+        else BB_ROW(WPRV, 0);                                                                    \
+    } while (0)
+    if (s->ro_wpr == 4) BB_ROW_Q(4);
+    else if (s->ro_wpr == 2) BB_ROW_Q(2);
+    else BB_ROW_Q(1);
+#undef BB_ROW_Q
 #undef BB_ROW
     if (update) {
         std::swap(s->d_X, s->d_X2);
@@ -995,6 +1018,46 @@ int bb_solver_degrees(bb_solver *s, int64_t *degree, int64_t n_bins) {
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));
     BB_HIP_CHECK(hipMemcpy(host.data(), d_deg, (size_t)n_bins * sizeof(int), hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < n_bins; ++i) degree[i] = host[(size_t)i];
+    return BB_OK;
+}
+
+int bb_solver_set_weight_power(bb_solver *s, int q) {
+    BB_REQUIRE(s != nullptr, "bb_solver_set_weight_power: solver is NULL");
+    BB_REQUIRE(q >= 0 && q <= 2, "bb_solver_set_weight_power: q must be 0, 1 or 2");
+    if (s->grad_pending)
+        return bb::fail(BB_ERR_STATE, "bb_solver_set_weight_power: a bb_solver_grad is pending");
+    s->weight_power = q;           // (the stress history is kept: each entry is the S_q of its step)
+    return BB_OK;
+}
+
+int bb_solver_weight_sums(bb_solver *s, double *sums, int64_t n_bins) {
+    BB_REQUIRE(s != nullptr && sums != nullptr, "bb_solver_weight_sums: NULL argument");
+    BB_REQUIRE(n_bins == s->L.n_bins, "bb_solver_weight_sums: one sum per bin");
+    if (!s->have_wish) return bb::fail(BB_ERR_STATE, "bb_solver_weight_sums: no wish distances set");
+    BB_TRY(bb::enter_device(s->device));
+    if (s->weight_power == 0 || s->n_local == 0) {      // w = 1: the degrees, as doubles
+        std::vector<int64_t> deg((size_t)n_bins, 0);
+        if (s->n_local > 0) BB_TRY(bb_solver_degrees(s, deg.data(), n_bins));
+        for (int64_t i = 0; i < n_bins; ++i) sums[i] = (double)deg[(size_t)i];
+        return BB_OK;
+    }
+    // (the staging buffer of set_coords / get_coords: 3 n_pad doubles >= n_bins; see degrees)
+    double *d_sum = s->d_f64_tmp;
+    const dim3 grid((unsigned)((n_bins + 3) / 4));
+#define BB_WS(TT, WW, QV)                                                                          \
+    BB_HIP_CHECK(bb::launch(unit_weight_sums_kernel<TT, WW, QV>, grid, dim3(256), 0, s->stream,      \
+                            (const TT *)s->d_units, s->d_udesc, s->n_local, s->L.n_bins, d_sum))
+#define BB_WS_Q(TT, WW)                                                                            \
+    do {                                                                                           \
+        if (s->weight_power == 1) BB_WS(TT, WW, 1); else BB_WS(TT, WW, 2);                         \
+    } while (0)
+    if (s->dtype == BB_F32) BB_WS_Q(float, true);
+    else if (s->wide) BB_WS_Q(double, true);
+    else BB_WS_Q(double, false);
+#undef BB_WS_Q
+#undef BB_WS
+    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
+    BB_HIP_CHECK(hipMemcpy(sums, d_sum, (size_t)n_bins * sizeof(double), hipMemcpyDeviceToHost));
     return BB_OK;
 }
 

@@ -204,7 +204,12 @@ __device__ __forceinline__ void store_row3(__amdgpu_buffer_rsrc_t rsrc, unsigned
 //   kOpMatvec2: y_i += delta_ij^2 * x_j and y_j += delta_ij^2 * x_i for three
 //               right-hand sides held in the coordinate slots: Y = (D o D) X, the
 //               kernel of classical-MDS / spectral initialisation
-enum { kOpStress = 0, kOpMatvec2 = 1 };
+//   kOpStressW1, kOpStressW2: the weighted stress of SPEC 2.3.1, w = delta^-1 (Sammon) or
+//               delta^-2 (relative stress); r = 1/delta is computed in-kernel from the delta
+//               the sweep loads anyway (no extra bytes), and masked where delta = 0
+enum { kOpStress = 0, kOpMatvec2 = 1, kOpStressW1 = 2, kOpStressW2 = 3 };
+template <int OP>
+constexpr bool is_weighted_op() { return OP == kOpStressW1 || OP == kOpStressW2; }
 
 // 1/sqrt(d2) and sqrt(d2) in fp64 from the v_rsq_f64 seed (relative error <= 2^-23) by ONE
 // third-order step: with e = 1 - d2 r0^2, r = r0 (1 - e)^(-1/2) = r0 (1 + e/2 + 3 e^2/8 + ...);
@@ -226,6 +231,14 @@ __device__ __forceinline__ double weight01_f64(double delta) {
     return __builtin_fmin(__builtin_fmax(delta * 0x1p1000, 0.0), 1.0);
 }
 
+// 1/x in fp64 from the v_rcp_f64 seed (relative error ~2^-26) by one third-order step:
+// with e = 1 - x r0, 1/x = r0 (1 + e + e^2 + ...); the term dropped is e^3 < 2^-78.
+__device__ __forceinline__ double rcp_f64(double x) {
+    const double r0 = __builtin_amdgcn_rcp(x);
+    const double e = fma(-x, r0, 1.0);
+    return fma(r0, fma(e, e, e), r0);
+}
+
 // Pair math for one matrix row of a unit: VPL pairs per lane (fp64; fp32 has pair_step2).
 template <typename T, int C, int OP>
 __device__ __forceinline__ void pair_step(const typename Traits<T>::Vec &drow, T xi, T yi, T zi,
@@ -245,6 +258,27 @@ __device__ __forceinline__ void pair_step(const typename Traits<T>::Vec &drow, T
     // unit, so every instruction counts: 25 + v_rsq per pair
     T rinv, dist;
     rsqrt_sqrt_f64(d2, rinv, dist);
+    if constexpr (is_weighted_op<OP>()) {
+        // SPEC 2.3.1.  m = 1 (delta > 0) or 0; r = 1/delta, or 1/1 where delta = 0 so that
+        // nothing is inf (inf * 0 = NaN): res = 0 there and so is everything below
+        const T m = weight01_f64(delta);
+        const T res = fma(dist, m, -delta);
+        const T r = rcp_f64(delta + (1.0 - m));
+        const T u = res * r;                     // (d - delta) / delta
+        T coef;
+        if constexpr (OP == kOpStressW1) {
+            s = fma(res, u, s);                  // (d - delta)^2 / delta
+            coef = u * rinv;
+        } else {
+            s = fma(u, u, s);                    // ((d - delta) / delta)^2
+            coef = (u * r) * rinv;
+        }
+        gx = fma(coef, dx, gx); gy = fma(coef, dy, gy); gz = fma(coef, dz, gz);
+        gc[C][0] = fma(-coef, dx, gc[C][0]);
+        gc[C][1] = fma(-coef, dy, gc[C][1]);
+        gc[C][2] = fma(-coef, dz, gc[C][2]);
+        return;
+    }
     // (dist - delta) or 0 in ONE instruction: w is 1, or 0 exactly where delta is 0, so
     // dist * w - delta is dist - delta (the product is exact) or 0 - 0
     const T res = fma(dist, weight01_f64(delta), -delta);
@@ -468,6 +502,30 @@ __device__ __forceinline__ void pair_step2(f32x2 delta, f32x2 xi, f32x2 yi, f32x
     f32x2 rinv;
     rinv.x = __builtin_amdgcn_rsqf(d2.x);
     rinv.y = __builtin_amdgcn_rsqf(d2.y);
+    if constexpr (is_weighted_op<OP>()) {
+        // SPEC 2.3.1: the weight w = 1/delta resp. 1/delta^2 by one v_rcp_f32 per pair (the
+        // square first: as many live values as q = 1, where w (r) then r (rinv) would spill
+        // the 4-wave form), of max(., 2^-126) so that delta = 0 gives a finite w -- res is 0
+        // there and so is everything below (never inf * 0).  t = w (d - delta)
+        const f32x2 res = (d2 * rinv - delta) * weight01(delta);
+        f32x2 a = delta;
+        if constexpr (OP == kOpStressW2) a = delta * delta;
+        f32x2 w;
+        w.x = __builtin_amdgcn_rcpf(__builtin_fmaxf(a.x, 0x1p-126f));
+        w.y = __builtin_amdgcn_rcpf(__builtin_fmaxf(a.y, 0x1p-126f));
+        const f32x2 t = res * w;
+        s2 += res * t;
+        const f32x2 coef = t * rinv;
+        if constexpr (FIRST) {
+            rx = coef * dx; ry = coef * dy; rz = coef * dz;
+        } else {
+            rx += coef * dx; ry += coef * dy; rz += coef * dz;
+        }
+        st.g[K][H][0] -= coef * dx;
+        st.g[K][H][1] -= coef * dy;
+        st.g[K][H][2] -= coef * dz;
+        return;
+    }
     f32x2 res = d2 * rinv - delta;
     res *= weight01(delta);  // (dist - delta) or 0
     s2 += res * res;
@@ -661,306 +719,18 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
     int chunk_q, int chunk_r, const int2 *__restrict__ wave_slots, T *__restrict__ rowpart,
     T *__restrict__ colpart, double *__restrict__ stresspart, int cap_units, int lds_wave_floats,
     int dense_u0, double *__restrict__ stress_slot) {
-    using Vec = typename Traits<T>::Vec;
-    constexpr int VPL = Traits<T>::VPL;
-    constexpr int VW = Lay<T, W>::VW;
-    constexpr bool DEFER = sizeof(T) == 4 || W;
-    const int lane = threadIdx.x & 63;
-    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave in workgroup
-    // workgroup b sweeps the b-th run of WPB chunks (permuting that map by XCD changed
-    // nothing: docs/EXPERIMENTS.md)
-    const int wg = (int)blockIdx.x;
-    const int w = wg * WPB + wib;
-    // wave w owns units [w*q + min(w, r), +q (+1 if w < r)): arithmetic, not a table --
-    // one dependent memory round trip less before the wave's first matrix load
-    const int ua = w * chunk_q + (w < chunk_r ? w : chunk_r);
-    const int ub = ua + chunk_q + (w < chunk_r ? 1 : 0);
-    double stress = 0.0;
-    // the shared column slots of this workgroup's waves (epilogue), read NOW: behind the
-    // fences further down the compiler no longer takes them through the scalar cache, and a
-    // vector load there waits -- vmcnt is in order -- for every store the wave has in flight
-    int ws_shared[WPB];
-#pragma unroll
-    for (int k = 0; k < WPB; ++k) ws_shared[k] = wave_slots[(int64_t)wg * WPB + k].y;
-    // DEFER: this wave's parking space, cap_units * 12 floats + 4 dummy words
-    extern __shared__ __attribute__((aligned(16))) float row_lds[];
-    // this wave's LDS region: row-sum parking while it sweeps, its last column partial at
-    // the end (lds_wave_floats >= cap_units * 12 + 4 and >= 3 * VW elements of T)
-    const int stage0 = wib * lds_wave_floats;
-    // WPB = 8: progress words of the 8 waves, behind the regions
-    int *progress = reinterpret_cast<int *>(row_lds + WPB * lds_wave_floats);
-    int partner_done = 0;
-    const int park_from = (ub - ua) > cap_units ? (ub - ua) - cap_units : 0;
-    // fp64 2 x 512 units: column selectors of the MFMA row reduction (process_unit_f64w)
-    double sel[6];
-#pragma unroll
-    for (int v = 0; v < 6; ++v) sel[v] = (lane & 15) == v ? 1.0 : 0.0;
+#include "bb_sweep_body.inc"
+}
 
-    if (ua < ub) {
-        int slot = wave_slots[w].x;
-        Vec d[8];  // the unit's 8 wave-loads (8 KiB), in memory order
-        // column-strip state: coordinates + gradient accumulators of this lane's columns
-        struct Generic { T xj[(Lay<T, W>::LPR)][VPL][3], gc[(Lay<T, W>::LPR)][VPL][3]; };
-        using Strip = typename std::conditional<sizeof(T) == 4, StripF32, Generic>::type;
-        Strip st;
-        auto strip_load = [&](int j0) __attribute__((always_inline)) {
-            if constexpr (sizeof(T) == 4) {
-                load_strip_f32(st, X, j0, lane);
-            } else {
-                load_strip<T, W>(st.xj, X, j0, lane);
-#pragma unroll
-                for (int k = 0; k < Lay<T, W>::LPR; ++k)
-#pragma unroll
-                    for (int c = 0; c < VPL; ++c)
-                        st.gc[k][c][0] = st.gc[k][c][1] = st.gc[k][c][2] = T(0);
-            }
-        };
-        auto strip_store = [&](int sl) __attribute__((always_inline)) {
-            if constexpr (sizeof(T) == 4)
-                store_strip_f32(st, colpart + (int64_t)sl * (3 * VW), lane);
-            else
-                store_strip<T, W>(st.gc, colpart + (int64_t)sl * (3 * VW), lane);
-        };
-
-        // The wave's FIRST unit stands between the kernel's arguments and its first
-        // coordinate loads: a cold descriptor load there is one more dependent memory round
-        // trip (0.8 us of every launch).  A dense layout (dense_u0 >= 0: this rank's first
-        // global unit) has tile t = J (J + 1) / 2 + I in strip-major order (SPEC 3.1,
-        // bb_layout_dense_tiles), so that descriptor is arithmetic; the later ones come from
-        // the table as before, one unit ahead of their use.
-        int2 dc;
-        if (dense_u0 >= 0) {
-            constexpr int UPT = VW / Lay<T, W>::RPU;
-            const unsigned g = (unsigned)dense_u0 + (unsigned)ua;
-            const unsigned t = g / UPT, sub = g % UPT;
-            unsigned J = (unsigned)((__builtin_sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-            while (J * (J + 1) / 2 > t) --J;
-            while ((J + 1) * (J + 2) / 2 <= t) ++J;
-            const unsigned I = t - J * (J + 1) / 2;
-            dc = make_int2((int)(I * VW + sub * Lay<T, W>::RPU), (int)(J * VW));
-        } else {
-            dc = udesc[ua];                                    // current unit
-        }
-        int2 dn = udesc[ua + 1 < ub ? ua + 1 : ua];            // next unit
-        // Prologue: the x rows of the first unit, then its 8 matrix rows.
-        // Row coordinates of a unit, one unit ahead.  XRowS: 3*RPU wave-uniform scalars
-        // fetched through the scalar cache (X is read-only in this kernel) -- no VMEM
-        // slot, no v_readlane (12 floats or 6 doubles: 12 SGPRs, double-buffered).
-        // XRowV (fp64 narrow: 24 doubles): one per-lane load, v_readlane per use.
-        struct XRowS {
-            T v[3 * Lay<T, W>::RPU];
-            __device__ __forceinline__ T get(int q) const { return v[q]; }
-        };
-        struct XRowV {
-            T v;
-            __device__ __forceinline__ T get(int q) const { return lane_value(v, q); }
-        };
-        using XRow = typename std::conditional<Lay<T, W>::SCALAR_XROW, XRowS, XRowV>::type;
-        auto xrow_load = [&](int i0) __attribute__((always_inline)) {
-            XRow x;
-            if constexpr (std::is_same<XRow, XRowS>::value) {
-                const T *px = X + (int64_t)i0 * 3;
-#pragma unroll
-                for (int q = 0; q < 3 * Lay<T, W>::RPU; ++q) x.v[q] = px[q];
-            } else {
-                x.v = load_xrow<T, W>(X, i0, lane);
-            }
-            return x;
-        };
-        XRow xr = xrow_load(dc.x);
-        using Win = WinPtr<Vec>;
-        auto window_of = [&](int u_next) __attribute__((always_inline)) {
-            // The refills of the wave's LAST unit are never consumed.  They stay in the
-            // loop (a branch around them would cost every unit its exact wait counts),
-            // but all lanes ask for the same 16 bytes of the chunk's last unit: 8 lines
-            // instead of 8 KiB per wave and launch (1.3-2.7 % of the bytes of a 1/8 share
-            // of N=50k), back at once, so the epilogue gets the window's registers early.
-            const bool real = u_next < ub;
-            return Win{unit_ptr<T>(units, real ? u_next : ub - 1, real ? lane : 0)};
-        };
-        {
-            const Win first = window_of(ua);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) d[r] = first.template load<NT>(r);
-        }
-        // this wave's row partials: 3*RPU elements per unit of its group's chunk
-        constexpr unsigned kRowBytes = 3 * Lay<T, W>::RPU * sizeof(T);
-        const __amdgpu_buffer_rsrc_t row_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            rowpart + (int64_t)ua * (3 * Lay<T, W>::RPU), 0, (int)((unsigned)(ub - ua) * kRowBytes),
-            0x00020000);
-
-        // fp32: which of a unit's 12 row sums this lane holds -- lanes 0..3 / 16..19 / 32..35
-        // after the lane swaps (row_sum3_swap) -- and what follows from it for the unit's
-        // store offset and parking slot
-        const int f32_sl12 = swap_rowsum_slot(lane);
-        const unsigned f32_voff_lane = f32_sl12 >= 0 ? (unsigned)f32_sl12 * 4u : 0x40000000u;
-        const int f32_lds_dummy = stage0 + cap_units * 12 + (lane & 3);
-        const int f32_lds_real = f32_sl12 >= 0 ? stage0 + f32_sl12 : f32_lds_dummy;
-        const int f32_m12 = f32_sl12 >= 0 ? 12 : 0;
-        auto unit_step = [&](int u) __attribute__((always_inline)) {
-            if constexpr (WPB == 8) {
-                // pace keeping (see the kernel's comment): the partner's count was read
-                // one unit ago, so nothing here waits on LDS
-                const int mine = u - ua;
-                if (__builtin_amdgcn_readfirstlane(partner_done) > mine)
-                    __builtin_amdgcn_s_setprio(1);
-                else
-                    __builtin_amdgcn_s_setprio(0);
-                __hip_atomic_store(progress + wib, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                partner_done = __hip_atomic_load(progress + (wib ^ 4), __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            // (the descriptors of the units behind the wave's last one are never used)
-            const int un = u + 1 < ub ? u + 1 : u;
-            const XRow xrn = xrow_load(dn.x);
-            const int2 dnn = udesc[un + 1 < ub ? un + 1 : un];
-            unsigned row_voff;
-            int stage_slot = 0;
-            if constexpr (sizeof(T) == 4) {
-                // fp32: 12 lanes hold one of the unit's 12 sums each.  Units before
-                // park_from are stored directly; the later ones are parked in LDS slot
-                // (k - park_from) and their store is dropped (every lane out of range).
-                // per-lane parts are loop constants (f32_voff_lane, f32_lds_real / _dummy,
-                // f32_m12: below the lambda's captures), per-unit parts scalar: one v_add, one
-                // v_cndmask, one v_mad per unit instead of a chain of selects.  A store is out
-                // of range (dropped) unless the lane holds a sum AND the unit is not parked:
-                // 0x40000000 from either side puts the offset beyond any chunk.
-                const int k = u - ua;
-                const bool parked = k >= park_from;
-                row_voff = f32_voff_lane + (parked ? 0x40000000u : (unsigned)k * kRowBytes);
-                stage_slot = (parked ? f32_lds_real : f32_lds_dummy) +
-                             (parked ? k - park_from : 0) * f32_m12;
-            } else if constexpr (W) {
-                // fp64, 2 x 512 units: lanes 48..53 hold one of the unit's 6 sums each
-                // (parking as in fp32; an LDS slot is 4 bytes, a sum takes two)
-                const int k = u - ua;
-                const bool parked = k >= park_from;
-                const bool mine = lane >= 48 && lane < 54;
-                row_voff = (mine && !parked) ? (unsigned)k * kRowBytes + (unsigned)(lane - 48) * 8u
-                                             : kDropOffset;
-                stage_slot = stage0 + ((mine && parked) ? (k - park_from) * 12 + (lane - 48) * 2
-                                                        : cap_units * 12 + 2 * (lane & 1));
-            } else {                        // fp64, 8 x 128: lane 63 stores each row's three sums
-                row_voff = lane == 63 ? (unsigned)(u - ua) * kRowBytes : kDropOffset;
-            }
-            if constexpr (sizeof(T) == 4) {
-                float xs12[12];             // scalar registers
-#pragma unroll
-                for (int q = 0; q < 12; ++q) xs12[q] = xr.get(q);
-                process_unit_f32<NT, OP>(d, xs12, window_of(u + 1), st, stress, row_rsrc, row_voff,
-                                         stage_slot);
-            }
-            else if constexpr (W)
-                process_unit_f64w<NT, OP>(d, xr, window_of(u + 1), st.xj, st.gc, sel, stress,
-                                          row_rsrc, row_voff, stage_slot);
-            else
-                process_unit<T, W, NT, OP>(d, xr, window_of(u + 1), st.xj, st.gc, stress,
-                                       row_rsrc, row_voff);
-            xr = xrn;
-            dc = dn;
-            dn = dnn;
-        };
-        // Outer loop: one trip per column strip the wave's sweep crosses (rare).
-        // Inner loop: the units of that strip, with NO branch in the body.
-        int u = ua;
-        for (;;) {
-            const int curj = dc.y;
-            strip_load(curj);
-            // ONE copy of the unit body, entered with nothing in flight: hipcc's s_waitcnt
-            // counts are static and merged over every entry of a loop header, and a
-            // prologue- or strip-change-shaped entry would drain most of the 8-row prefetch
-            // window on every iteration.  The strip's coordinates have to be here anyway,
-            // and they were asked for after the window, so the wait counts inside the loop
-            // are those of the back edge alone.  Same speed as peeling the first unit at
-            // every size (profiles/archive/r02_peel_ab.txt), a third less code.
-            __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-            do {
-                unit_step(u);
-                ++u;
-            } while (u < ub && dc.y == curj);
-            if (u >= ub) break;      // the wave's last strip: its column partial goes out below
-            strip_store(slot);
-            // the stress of the strip left behind goes with its slot (rare: once per strip a
-            // wave crosses), so that every stress partial belongs to ONE strip -- and with
-            // several maps in one solver (bb_solver_set_maps) to one map
-            {
-                const double sv = wave_sum_hi(stress);
-                if (lane == 63) stress_slot[slot] = sv;
-                stress = 0.0;
-            }
-            ++slot;
-        }
-        if constexpr (WPB == 8) {
-            // done: the partner stops yielding
-            __hip_atomic_store(progress + wib, 0x7fffffff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __builtin_amdgcn_s_setprio(0);
-        }
-        if constexpr (DEFER) {
-            // the chunk's row sums, 48 bytes per unit in either precision (12 floats or
-            // 6 doubles), in one contiguous burst.
-            // Lanes read what other lanes of this wave parked: LDS operations of one
-            // wave execute in program order; the fence is for the compiler.
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const int n4 = ((ub - ua) - park_from) * 3;   // float4 count
-            float4 *dst = reinterpret_cast<float4 *>(rowpart + ((int64_t)ua + park_from) *
-                                                                   (3 * Lay<T, W>::RPU));
-            for (int q = lane; q < n4; q += 64) {
-                const float *src = row_lds + stage0 + 4 * q;
-                dst[q] = make_float4(src[0], src[1], src[2], src[3]);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the region is free again
-            __builtin_amdgcn_wave_barrier();
-        }
-        // the column partial of the wave's LAST strip: into its LDS region (same layout as a
-        // slot in HBM), to be added to its neighbours' below
-        {
-            T *mine = reinterpret_cast<T *>(row_lds + stage0);
-            if constexpr (sizeof(T) == 4)
-                store_strip_f32(st, mine, lane);
-            else
-                store_strip<T, W>(st.gc, mine, lane);
-        }
-    }
-    // One column partial per WORKGROUP and strip, not per wave: consecutive waves sweep
-    // consecutive chunks, almost always of the same strip, so the 4 or 8 partials of a
-    // workgroup are added here, in wave order (fixed), and leave as one slot -- an eighth
-    // of the bytes for the sweep to write and for the reduce to read back.  wave_slots[].y
-    // names the shared slot; waves of one workgroup that end in the same strip carry the
-    // same number (the host deals them).
-    // The barrier orders LDS only: __syncthreads() is also a release of the wave's global
-    // stores, and waiting here for the acknowledgement of the row-sum burst (s_waitcnt vmcnt
-    // in front of s_barrier) kept every wave 1-2 us at the end of every launch.
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-    {
-        constexpr int CH = 3 * VW, NTH = 64 * WPB;
-        int k = 0;
-        while (k < WPB) {
-            const int sl = ws_shared[k];       // wave-uniform (scalar registers)
-            if (sl < 0) { ++k; continue; }
-            int k2 = k + 1;
-            while (k2 < WPB && ws_shared[k2] == sl) ++k2;
-            T *dst = colpart + (int64_t)sl * CH;
-#pragma unroll
-            for (int j = 0; j < (CH + NTH - 1) / NTH; ++j) {
-                const int e = (int)threadIdx.x + NTH * j;
-                if (CH % NTH == 0 || e < CH) {
-                    T acc = T(0);
-                    for (int q = k; q < k2; ++q)
-                        acc += reinterpret_cast<const T *>(row_lds + q * lds_wave_floats)[e];
-                    dst[e] = acc;
-                }
-            }
-            k = k2;
-        }
-    }
-
-    // per-wave stress: fixed DPP tree, total in lane 63 (no LDS round trips at the very end
-    // of the launch: six __shfl_down steps of a double are twelve ds_bpermute)
-    stress = wave_sum_hi(stress);
-    if (lane == 63) stresspart[w] = stress;
+// The weighted stress of SPEC 2.3.1 (OP = kOpStressW1 / kOpStressW2): the same body under a
+// name of its own (the unweighted kernels above stay exactly what they were).
+template <typename T, bool W, bool NT, int OP, int WPB>
+__global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void weighted_sweep_kernel(
+    const T *__restrict__ units, const T *__restrict__ X, const int2 *__restrict__ udesc,
+    int chunk_q, int chunk_r, const int2 *__restrict__ wave_slots, T *__restrict__ rowpart,
+    T *__restrict__ colpart, double *__restrict__ stresspart, int cap_units, int lds_wave_floats,
+    int dense_u0, double *__restrict__ stress_slot) {
+#include "bb_sweep_body.inc"
 }
 
 // --------------------------------------------------------------------------
@@ -1744,7 +1514,8 @@ __global__ __launch_bounds__(256) void gen_units_kernel(const double *__restrict
 // four rows in part_out[block]; the fold is done by ONE extra workgroup of the NEXT
 // launch (blockIdx = gridDim - 1; it runs beside that launch's row workgroups) and by a
 // fold-only launch after the last iteration of a bb_solver_iterate call.
-template <typename T>
+// Q = weight power of SPEC 2.3.1 (0: unweighted)
+template <typename T, int Q>
 __device__ __forceinline__ void pair_row(T delta, T xi, T yi, T zi, T xj, T yj, T zj, T &gx,
                                          T &gy, T &gz, T &s) {
     const T dx = xi - xj, dy = yi - yj, dz = zi - zj;
@@ -1761,6 +1532,27 @@ __device__ __forceinline__ void pair_row(T delta, T xi, T yi, T zi, T xj, T yj, 
         res = delta > T(0) ? dist - delta : T(0);
     else
         res = fma(dist, weight01_f64(delta), -delta);        // as pair_step<double>
+    if constexpr (Q > 0) {
+        // SPEC 2.3.1: r = 1/delta, 0 where delta = 0 (res is 0 there too)
+        T r;
+        if constexpr (sizeof(T) == 4)
+            r = delta > T(0) ? __builtin_amdgcn_rcpf(delta) : T(0);
+        else
+            r = rcp_f64(delta + (1.0 - weight01_f64(delta))) * weight01_f64(delta);
+        const T u = res * r;
+        T coef;
+        if constexpr (Q == 1) {
+            s = fma(res, u, s);
+            coef = u * rinv;
+        } else {
+            s = fma(u, u, s);
+            coef = (u * r) * rinv;
+        }
+        gx = fma(coef, dx, gx);
+        gy = fma(coef, dy, gy);
+        gz = fma(coef, dz, gz);
+        return;
+    }
     s = fma(res, res, s);
     const T coef = res * rinv;
     gx = fma(coef, dx, gx);
@@ -1788,7 +1580,7 @@ template <typename T> struct RowTrip { static constexpr int COLS = 64 * (16 / (i
 // WPR waves share one row (1, 2 or 4: the host picks it so that a small map still
 // puts >= 16 waves on every CU): wave part p takes the 128-column trips p, p + WPR, ...;
 // the parts meet in LDS and are added in part order by the row's first wave.
-template <typename T, int WPR>
+template <typename T, int WPR, int Q>
 __global__ __launch_bounds__(256) void row_owner_kernel(
     const T *__restrict__ full, int64_t ld, int n, const T *__restrict__ Xin,
     T *__restrict__ Xout, T *__restrict__ V, T lr, T mu, const double *__restrict__ part_prev,
@@ -1828,7 +1620,7 @@ __global__ __launch_bounds__(256) void row_owner_kernel(
             for (int u = 0; u < COLS / 64; ++u) {
                 const int j = c + 64 * u + lane;
                 const T *xj = Xin + 3 * (int64_t)j;
-                pair_row<T>(row[j], xi, yi, zi, xj[0], xj[1], xj[2], gx, gy, gz, s);
+                pair_row<T, Q>(row[j], xi, yi, zi, xj[0], xj[1], xj[2], gx, gy, gz, s);
             }
 #else
             using Vec = typename Traits<T>::Vec;
@@ -1837,13 +1629,13 @@ __global__ __launch_bounds__(256) void row_owner_kernel(
             const Vec *px = reinterpret_cast<const Vec *>(Xin + 3 * (int64_t)c);
             const Vec a = px[0], b = px[1], q = px[2];
             if constexpr (sizeof(T) == 4) {      // x0 y0 z0 x1 | y1 z1 x2 y2 | z2 x3 y3 z3
-                pair_row<T>(dv.x, xi, yi, zi, a.x, a.y, a.z, gx, gy, gz, s);
-                pair_row<T>(dv.y, xi, yi, zi, a.w, b.x, b.y, gx, gy, gz, s);
-                pair_row<T>(dv.z, xi, yi, zi, b.z, b.w, q.x, gx, gy, gz, s);
-                pair_row<T>(dv.w, xi, yi, zi, q.y, q.z, q.w, gx, gy, gz, s);
+                pair_row<T, Q>(dv.x, xi, yi, zi, a.x, a.y, a.z, gx, gy, gz, s);
+                pair_row<T, Q>(dv.y, xi, yi, zi, a.w, b.x, b.y, gx, gy, gz, s);
+                pair_row<T, Q>(dv.z, xi, yi, zi, b.z, b.w, q.x, gx, gy, gz, s);
+                pair_row<T, Q>(dv.w, xi, yi, zi, q.y, q.z, q.w, gx, gy, gz, s);
             } else {                             // x0 y0 | z0 x1 | y1 z1
-                pair_row<T>(dv.x, xi, yi, zi, a.x, a.y, b.x, gx, gy, gz, s);
-                pair_row<T>(dv.y, xi, yi, zi, b.y, q.x, q.y, gx, gy, gz, s);
+                pair_row<T, Q>(dv.x, xi, yi, zi, a.x, a.y, b.x, gx, gy, gz, s);
+                pair_row<T, Q>(dv.y, xi, yi, zi, b.y, q.x, q.y, gx, gy, gz, s);
             }
 #endif
         };
@@ -1959,6 +1751,64 @@ __global__ __launch_bounds__(256) void unit_degrees_kernel(const T *__restrict__
         }
     }
     flush();
+}
+
+// Per bin: s_i = sum_j w_ij over this rank's stored pairs, w = delta^-Q (SPEC 2.4.1, weighted
+// degrees; once per map).  One wave per bin and no atomics, so the sum has a fixed order:
+// each lane adds its own entries in a fixed sequence and the lanes meet in the fixed DPP tree.
+// Row side: the unit holding row i in every strip J >= block(i), found by binary search in
+// udesc (local units are ordered by (j0, i0)); column side: the units of strip block(i), lane l
+// taking row groups l, l + 64, ... of it.  Which lane adds which pair, and in what order, thus
+// depends on the pair's position alone, not on which tiles the layout holds: a blocked-sparse
+// and a dense layout of one map give the same bits.  fp64 throughout: delta^-Q of an fp32 delta is exact
+// enough to sum in double.
+template <typename T, bool W, int Q>
+__global__ __launch_bounds__(256) void unit_weight_sums_kernel(const T *__restrict__ units,
+                                                               const int2 *__restrict__ udesc,
+                                                               int64_t n_local, int64_t n_bins,
+                                                               double *__restrict__ sums) {
+    constexpr int VW = Lay<T, W>::VW, RPU = Lay<T, W>::RPU;
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n_bins) return;
+    auto weight = [](T v) -> double {
+        const double d = (double)v;
+        return d > 0.0 ? (Q == 1 ? 1.0 / d : 1.0 / (d * d)) : 0.0;
+    };
+    // first local unit whose (j0, i0) is not below (j0, i0)
+    auto lower = [&](int j0, int i0) -> int64_t {
+        int64_t lo = 0, hi = n_local;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            const int2 d = udesc[mid];
+            if (d.y < j0 || (d.y == j0 && d.x < i0)) lo = mid + 1;
+            else hi = mid;
+        }
+        return lo;
+    };
+    const int b = (int)(i / VW);
+    const int n_blocks = (int)((n_bins + VW - 1) / VW);
+    const int i0 = (int)(i - i % RPU), r = (int)(i % RPU);
+    double acc = 0.0;
+    for (int J = b; J < n_blocks; ++J) {
+        const int64_t ul = lower(J * VW, i0);
+        if (ul >= n_local || udesc[ul].y != J * VW || udesc[ul].x != i0) continue;
+        const T *row = units + ul * (RPU * VW) + (int64_t)r * VW;
+        for (int c = lane; c < VW; c += 64) {
+            const int64_t j = (int64_t)J * VW + c;
+            if (j > i && j < n_bins) acc += weight(row[c]);
+        }
+    }
+    const int c = (int)(i - (int64_t)b * VW);
+    for (int64_t p = lane; p * RPU < i; p += 64) {   // lane: the rows p*RPU.. of strip b
+        const int64_t ul = lower(b * VW, (int)(p * RPU));
+        if (ul >= n_local || udesc[ul].y != b * VW || udesc[ul].x != (int)(p * RPU)) continue;
+        const T *col = units + ul * (RPU * VW) + c;
+        for (int q = 0; q < RPU; ++q)
+            if (p * RPU + q < i) acc += weight(col[q * VW]);
+    }
+    acc = wave_sum_hi(acc);
+    if (lane == 63) sums[i] = acc;
 }
 
 // Measurement only: the same waves read the same units with the same rolling

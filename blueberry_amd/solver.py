@@ -222,6 +222,20 @@ class HipEngine(object):
                    "bb_solver_degrees")
         return out
 
+    def set_weight_power(self, q):
+        """Weighted stress (SPEC 2.3.1): w = delta^-q, q in {0, 1, 2}
+        (`bb_solver_set_weight_power`)."""
+        _lib.check(self._lib.bb_solver_set_weight_power(self._h, int(q)),
+                   "bb_solver_set_weight_power")
+
+    def weight_sums(self):
+        """Per bin, s_i = sum_j delta_ij^-q over this rank's stored pairs, float64
+        (`bb_solver_weight_sums`; q = 0: the degrees)."""
+        out = numpy.zeros(self.n_bins, dtype=numpy.float64)
+        _lib.check(self._lib.bb_solver_weight_sums(self._h, _lib.as_f64_ptr(out), out.shape[0]),
+                   "bb_solver_weight_sums")
+        return out
+
     def stress_maps(self):
         out = numpy.empty(getattr(self, "n_maps", 1), dtype=numpy.float64)
         _lib.check(self._lib.bb_solver_stress_maps(self._h, _lib.as_f64_ptr(out), out.shape[0]),
@@ -634,18 +648,47 @@ def degree_step_factors(degree):
 
 
 def _sum_over_ranks(counts, eng, world):
-    """Element-wise sum of an int64 host array over the ranks (world 1: the array)."""
+    """Element-wise sum of an int64 host array over the ranks (world 1: the array); a float
+    array is summed in float64 (the weighted degrees of SPEC 2.4.1)."""
     if world <= 1:
         return counts
     import torch
     import torch.distributed as dist
-    t = torch.from_numpy(numpy.ascontiguousarray(counts, dtype=numpy.int64))
+    kind = numpy.float64 if numpy.asarray(counts).dtype.kind == "f" else numpy.int64
+    t = torch.from_numpy(numpy.ascontiguousarray(counts, dtype=kind))
     if dist.get_backend() == "nccl":
         t = t.to(torch.device("cuda", getattr(eng, "device", 0)))
         dist.all_reduce(t)
         return t.cpu().numpy()
     dist.all_reduce(t)
     return t.numpy()
+
+
+# fp32 with weight_power > 0: the largest weighted degree accepted (SPEC 2.3.1).  Every
+# weight is then <= 2^60, so the smallest wish distance is 2^-30 (q = 2) or 2^-60 (q = 1)
+# relative to a unit weight, and the terms and forces stay finite in float32.
+_F32_MAX_WEIGHT_SUM = 2.0 ** 60
+
+
+def weighted_steps(sums, n_bins, dtype, lr, degree_steps):
+    """(lr, scale) for weighted stress from the bins' weighted degrees s_i (SPEC 2.4.1):
+    lr='auto' is 1 / (2 max s); degree_steps: scale[i] = max s / s_i (1 where s_i = 0), else
+    None.  Raises ValueError for a map fp32 cannot weight without overflow, or whose weights
+    are not finite."""
+    s = numpy.asarray(sums, dtype=numpy.float64)
+    top = float(s.max()) if s.size else 0.0
+    if not numpy.isfinite(top):
+        raise ValueError("weight_power: the weights delta^-q of this map overflow float64")
+    if dtype == "float32" and top > _F32_MAX_WEIGHT_SUM:
+        raise ValueError("weight_power: the largest weighted degree of this map, %.3g, exceeds "
+                         "2^60: float32 would overflow (use dtype='float64' or rescale the wish "
+                         "distances)" % top)
+    if top <= 0.0:                                    # no constraint at all
+        return (1.0 / (2.0 * n_bins) if lr == "auto" else float(lr)), None
+    out_lr = 1.0 / (2.0 * top) if lr == "auto" else float(lr)
+    if not degree_steps:
+        return out_lr, None
+    return out_lr, numpy.where(s > 0.0, top / numpy.where(s > 0.0, s, 1.0), 1.0)
 
 
 def allreduce_exchange(t):
@@ -723,7 +766,16 @@ class StructureSolver(object):
         chromosomes differ in size, real maps whose long-range pairs have no contact -- that
         is each bin's own Guttman-like step: a genome-like map converges in about a third
         of the iterations.  A float `lr` is then the step of the bin with the most partners.
-        A complete map: no effect.
+        A complete map: no effect.  With weight_power > 0 the weighted degree
+        s_i = sum_j delta_ij^-q takes the place of deg_i: bin i steps by 1 / (2 s_i).
+    weight_power : 0, 1 or 2
+        Weight w = delta^-q of each pair's squared residual (SPEC 2.3.1).  0: raw stress, where
+        the long-range pairs (largest, noisiest delta) dominate.  1: Sammon stress, a middle
+        ground.  2: relative stress, sum ((d - delta) / delta)^2, every pair's relative error
+        counts alike -- the local structure, the best-measured part of a Hi-C map, gets its
+        share.  With q > 0, lr='auto' is 1 / (2 max_i s_i), s_i the weighted degree; `stress_`
+        reports the weighted stress.  float32 refuses (ValueError) a map whose largest s_i
+        exceeds 2^60.
     spectral_iter, spectral_tol : int, float
         The spectral start's block power iteration makes at most `spectral_iter` products
         and ends once B V lies within `spectral_tol` (relative) of span(V); 0 = always
@@ -758,7 +810,7 @@ class StructureSolver(object):
     def __init__(self, n_iter=100, lr="auto", dtype="float32", alpha=3.0, kind="counts",
                  seed=0, device=None, distributed=None, engine=None, momentum=0.0,
                  init="random", tol=None, check_every=10, spectral_iter=40, spectral_tol=1e-3,
-                 degree_steps=False):
+                 degree_steps=False, weight_power=0):
         if dtype not in _DTYPES:
             raise ValueError("dtype must be 'float32' or 'float64'")
         if kind not in _KINDS:
@@ -787,6 +839,9 @@ class StructureSolver(object):
             raise ValueError("need spectral_iter >= 0 and 0 <= spectral_tol < 1")
         self.spectral_iter, self.spectral_tol = int(spectral_iter), float(spectral_tol)
         self.degree_steps = bool(degree_steps)
+        if isinstance(weight_power, bool) or weight_power not in (0, 1, 2):
+            raise ValueError("weight_power must be 0, 1 or 2")
+        self.weight_power = int(weight_power)
         self.n_iter, self.lr, self.dtype, self.alpha, self.kind, self.seed = (
             int(n_iter), lr, dtype, float(alpha), kind, int(seed))
         self.device, self.distributed = device, distributed
@@ -856,7 +911,13 @@ class StructureSolver(object):
                 eng.set_wish_sparse(rows, cols, vals, self.kind, self.alpha, KRnorm, KRexpected)
             else:
                 eng.set_wish_dense(matrix, self.kind, self.alpha)
-            if self.degree_steps:
+            if self.weight_power:
+                eng.set_weight_power(self.weight_power)
+                lr, scale = weighted_steps(_sum_over_ranks(eng.weight_sums(), eng, world), n,
+                                           self.dtype, self.lr, self.degree_steps)
+                if scale is not None:
+                    eng.set_bin_steps(scale)
+            elif self.degree_steps:
                 lr_top, scale = degree_step_factors(_sum_over_ranks(eng.degrees(), eng, world))
                 if self.lr == "auto":
                     lr = lr_top
@@ -1017,7 +1078,8 @@ class StructureSolver(object):
                                         init=self.init, tol=self.tol, check_every=self.check_every,
                                         spectral_iter=self.spectral_iter,
                                         spectral_tol=self.spectral_tol,
-                                        degree_steps=self.degree_steps)
+                                        degree_steps=self.degree_steps,
+                                        weight_power=self.weight_power)
                 local._fit_many_local([maps[m] for m in mine[rank]], [inits[m] for m in mine[rank]])
                 part = (mine[rank], local.structures_, local.stresses_, local.lrs_)
             parts = [None] * world
@@ -1095,7 +1157,19 @@ class StructureSolver(object):
                 else:
                     m = src.to_host() if getattr(src, "is_resident", False) else src
                     eng.set_wish_dense_block(m, o, self.kind, self.alpha)
-            if self.degree_steps:
+            if self.weight_power:
+                # SPEC 2.3.1 / 2.4.1 per map, from the weighted degrees: lr='auto' is each
+                # map's 1 / (2 max s), degree_steps each bin's 1 / (2 s_i) (lr = 1 below)
+                eng.set_weight_power(self.weight_power)
+                ws = eng.weight_sums()
+                steps = numpy.ones(total)
+                for q, (o, n) in enumerate(zip(off, sizes)):
+                    top, scale = weighted_steps(ws[o:o + n], n, self.dtype, self.lr,
+                                                self.degree_steps)
+                    steps[o:o + n] = top if scale is None else top * scale
+                    lrs[q] = top
+                eng.set_bin_steps(steps)
+            elif self.degree_steps:
                 # SPEC 2.4.1 per map: bin i steps by 1 / (2 (deg_i + 1)) (lr = 1 below); a float
                 # `lr` stays the step of each map's best-connected bin
                 deg = eng.degrees()

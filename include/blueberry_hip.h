@@ -179,6 +179,25 @@ BB_API int bb_solver_stress_maps(bb_solver *s, double *stress, int n_maps);
 BB_API int bb_solver_degrees(bb_solver *s, int64_t *degree, int64_t n_bins);
 BB_API int bb_solver_set_bin_steps(bb_solver *s, const double *scale, int64_t n_bins);
 BB_API int bb_solver_set_block_steps(bb_solver *s, const double *scale, int64_t n_blocks);
+/* Weighted stress (docs/SPEC.md 2.3.1): every pair's residual weighted by w = delta^-q,
+ *   q = 0  raw stress (the default; bit for bit the unweighted solver)
+ *   q = 1  Sammon stress, w = 1 / delta
+ *   q = 2  relative stress, w = 1 / delta^2: sum ((d - delta) / delta)^2
+ * Pairs without a constraint (delta = 0) contribute 0.  Every entry point that evaluates the
+ * stress -- bb_solver_iterate / _dist / _peer, bb_solver_grad, bb_solver_stress, _stress_maps
+ * -- then reports and descends S_q; the spectral start (bb_solver_matvec_sq and
+ * bb_solver_spectral_init*) stays unweighted.
+ *   bb_solver_set_weight_power  q in {0, 1, 2} (else BB_ERR_INVALID); callable any time after
+ *                               bb_solver_create, also between iterate calls (BB_ERR_STATE
+ *                               while a bb_solver_grad is pending).  The stress history is
+ *                               NOT reset: each entry is the S_q in effect at its step
+ *   bb_solver_weight_sums       per bin, s_i = sum_j w_ij over THIS rank's stored pairs, in
+ *                               fp64 and in a fixed order (bitwise reproducible); q = 0 gives
+ *                               the degrees.  The weighted counterpart of bb_solver_degrees
+ *                               for SPEC 2.4.1's steps; world > 1: the caller sums over the
+ *                               ranks */
+BB_API int bb_solver_set_weight_power(bb_solver *s, int q);
+BB_API int bb_solver_weight_sums(bb_solver *s, double *sums, int64_t n_bins);
 /* Blocked-sparse input: nnz entries (rows[k], cols[k], vals[k]) of the symmetric
  * matrix, either triangle; an unordered pair that occurs more than once keeps its
  * LAST entry, as in the reference's scatter loop (blueberry/datatypes.pyx:110-116)
