@@ -25,7 +25,8 @@
  *      thread).  PARITY UNPINNED against the reference for these: they are
  *      pinned instead by closed-form known-answer tests and a finite-difference
  *      gradient check (tests/test_oracle.py).
- *        bbo_counts_to_wish, bbo_stress_grad, bbo_solve, bbo_stress_grad_units
+ *        bbo_counts_to_wish, bbo_stress_grad, bbo_solve, bbo_stress_grad_units,
+ *        bbo_stress_grad_units_weighted
  *
  * Plain C99, no dependencies beyond libm.  Build: see oracle/Makefile.
  */
@@ -261,6 +262,47 @@ BBO_API double bbo_stress_grad_units(const double *wish, long n, long ld, const 
                 double delta = wish[i * ld + j];
                 if (!(delta > 0.0)) continue;
                 s += pair_term(X + 3 * i, X + 3 * j, delta, eps2, g + 3 * i, g + 3 * j);
+            }
+    }
+    return s;
+}
+
+/* bbo_stress_grad_units for the weighted stress of docs/SPEC.md 2.3.1: the same pairs, each
+ * with the weight w = delta^-q (q in {0, 1, 2}) formed in float64 from its delta; the term is
+ * w (d - delta)^2 and the force coefficient 2 w (d - delta) / d.  q = 0 is bbo_stress_grad_units
+ * bit for bit.  If s_sums is not NULL, s_sums[i] += w over the same pairs at both ends: the
+ * weighted degrees of SPEC 2.4.1 (bb_solver_weight_sums).  Returns NaN for q outside {0, 1, 2}. */
+BBO_API double bbo_stress_grad_units_weighted(const double *wish, long n, long ld, const double *X,
+                                              int eps2_kind, const int32_t *tile_I,
+                                              const int32_t *tile_J, long units_per_tile, long vw,
+                                              long u_begin, long u_end, int q, double *g,
+                                              double *s_sums)
+{
+    double eps2 = eps2_kind ? BBO_EPS2_F64 : BBO_EPS2_F32;
+    double s = 0.0;
+    if (q < 0 || q > 2) return NAN;
+    memset(g, 0, sizeof(double) * 3 * (size_t)n);
+    for (long u = u_begin; u < u_end; u++) {
+        long t = u / units_per_tile, sub = u % units_per_tile;
+        long rpu = vw / units_per_tile;
+        long i0 = (long)tile_I[t] * vw + sub * rpu;
+        long j0 = (long)tile_J[t] * vw;
+        for (long i = i0; i < i0 + rpu && i < n; i++)
+            for (long j = j0; j < j0 + vw && j < n; j++) {
+                if (j <= i) continue;
+                double delta = wish[i * ld + j];
+                if (!(delta > 0.0)) continue;
+                double w = q == 0 ? 1.0 : (q == 1 ? 1.0 / delta : 1.0 / (delta * delta));
+                const double *xi = X + 3 * i, *xj = X + 3 * j;
+                double dx = xi[0] - xj[0], dy = xi[1] - xj[1], dz = xi[2] - xj[2];
+                double d = sqrt(dx * dx + dy * dy + dz * dz + eps2);
+                double r = d - delta;
+                double coef = 2.0 * w * r / d;
+                double *gi = g + 3 * i, *gj = g + 3 * j;
+                gi[0] += coef * dx; gi[1] += coef * dy; gi[2] += coef * dz;
+                gj[0] -= coef * dx; gj[1] -= coef * dy; gj[2] -= coef * dz;
+                s += w * r * r;
+                if (s_sums) { s_sums[i] += w; s_sums[j] += w; }
             }
     }
     return s;

@@ -243,3 +243,80 @@ BBO_API int bbo_solve_gen_steps_mt(const double *xstar, long n, const int *tile_
     return solve_gen_impl(xstar, n, tile_I, tile_J, n_tiles, vw, X, iters, lr, mu, eps2_kind,
                           delta_f32, flush, stress_hist, threads, bin_scale);
 }
+
+/* The weighted stress of docs/SPEC.md 2.3.1 on the same tile-list loop: S_q = sum w (d - delta)^2
+ * with w = delta^-q, q in {0, 1, 2} (q = 1 Sammon, q = 2 relative stress), force coefficient
+ * 2 w (d - delta) / d.  w is formed in float64 from the delta the pair uses (after the flush and
+ * the optional rounding to float), as the device forms it from the delta it stored.  A function
+ * of its own: solve_gen_impl above is what bench.py's cpu_baseline times and stays as it is.
+ * q = 0 gives w = 1 and the same bits as bbo_solve_gen_steps_mt.  bin_scale may be NULL.
+ * Returns 0, or -1 for q outside {0, 1, 2} or when the scratch memory cannot be allocated. */
+BBO_API int bbo_solve_gen_weighted_mt(const double *xstar, long n, const int *tile_I,
+                                      const int *tile_J, long n_tiles, long vw, double *X,
+                                      long iters, double lr, double mu, int eps2_kind,
+                                      int delta_f32, double flush, double *stress_hist,
+                                      int threads, const double *bin_scale, int q)
+{
+    const double eps2 = eps2_kind ? BBO_EPS2_F64 : BBO_EPS2_F32;
+    if (q < 0 || q > 2) return -1;
+    if (threads < 1) threads = 1;
+    double *G = (double *)malloc(sizeof(double) * 3 * (size_t)n * (size_t)threads);
+    double *S = (double *)malloc(sizeof(double) * (size_t)threads);
+    double *V = (double *)calloc(3 * (size_t)n, sizeof(double));
+    if (!G || !S || !V) { free(G); free(S); free(V); return -1; }
+    for (long k = 0; k < iters; k++) {
+#pragma omp parallel num_threads(threads)
+        {
+            const int t = omp_get_thread_num(), T = omp_get_num_threads();
+            double *g = G + 3 * (size_t)n * (size_t)t;
+            double s = 0.0;
+            memset(g, 0, sizeof(double) * 3 * (size_t)n);
+            for (long p = t; p < n_tiles; p += T) {
+                const long i0 = (long)tile_I[p] * vw, j0 = (long)tile_J[p] * vw;
+                const long i1 = i0 + vw < n ? i0 + vw : n, j1 = j0 + vw < n ? j0 + vw : n;
+                for (long i = i0; i < i1; i++) {
+                    const double *xi = X + 3 * i, *si = xstar + 3 * i;
+                    double gx = 0.0, gy = 0.0, gz = 0.0;
+                    for (long j = (j0 > i + 1 ? j0 : i + 1); j < j1; j++) {
+                        const double *sj = xstar + 3 * j;
+                        const double ax = si[0] - sj[0], ay = si[1] - sj[1], az = si[2] - sj[2];
+                        double delta = sqrt(ax * ax + ay * ay + az * az);
+                        if (delta < flush) delta = 0.0;
+                        if (delta_f32) delta = (double)(float)delta;
+                        if (!(delta > 0.0)) continue;
+                        const double w = q == 0 ? 1.0 : (q == 1 ? 1.0 / delta : 1.0 / (delta * delta));
+                        const double *xj = X + 3 * j;
+                        const double dx = xi[0] - xj[0], dy = xi[1] - xj[1], dz = xi[2] - xj[2];
+                        const double d = sqrt(dx * dx + dy * dy + dz * dz + eps2);
+                        const double r = d - delta;
+                        const double coef = 2.0 * w * r / d;
+                        gx += coef * dx; gy += coef * dy; gz += coef * dz;
+                        g[3 * j] -= coef * dx; g[3 * j + 1] -= coef * dy; g[3 * j + 2] -= coef * dz;
+                        s += w * r * r;
+                    }
+                    g[3 * i] += gx; g[3 * i + 1] += gy; g[3 * i + 2] += gz;
+                }
+            }
+            S[t] = s;
+#pragma omp barrier
+#pragma omp for schedule(static)
+            for (long e = 0; e < 3 * n; e++) {
+                double a = 0.0;
+                for (int u = 0; u < T; u++) a += G[3 * (size_t)n * (size_t)u + e];
+                if (bin_scale) a *= bin_scale[e / 3];
+                V[e] = mu * V[e] - lr * a;
+                X[e] += V[e];
+            }
+#pragma omp single
+            {
+                double a = 0.0;
+                for (int u = 0; u < T; u++) a += S[u];
+                if (stress_hist) stress_hist[k] = a;
+            }
+        }
+    }
+    free(G);
+    free(S);
+    free(V);
+    return 0;
+}

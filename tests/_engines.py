@@ -33,6 +33,7 @@ class OracleEngine(object):
         self.exch = numpy.zeros(3 * self.info.n_pad + 2)
         self.hist = []
         self.mu = 0.0
+        self.q = 0
 
     def close(self):
         pass
@@ -50,6 +51,21 @@ class OracleEngine(object):
 
     def set_bin_steps(self, scale):
         self.bin_scale = None if scale is None else numpy.asarray(scale, dtype=numpy.float64)
+
+    def set_weight_power(self, q):
+        """Weighted stress (SPEC 2.3.1), as bb_solver_set_weight_power: the history is kept."""
+        if q not in (0, 1, 2):
+            raise ValueError("q must be 0, 1 or 2")
+        self.q = int(q)
+
+    def weight_sums(self):
+        """Per bin, s_i = sum_j delta_ij^-q over this rank's stored pairs, float64 (q = 0: the
+        degrees), as bb_solver_weight_sums."""
+        sums = numpy.zeros(self.n_bins)
+        self.oracle.stress_grad_units(self.w, numpy.zeros((self.n_bins, 3)), self.ti, self.tj,
+                                      self.info.units_per_tile, self.info.vw, self.u_begin,
+                                      self.u_end, q=self.q, sums=sums)
+        return sums
 
     def _own_pairs(self):
         """Mask of the pairs i < j this rank's units hold."""
@@ -83,7 +99,7 @@ class OracleEngine(object):
     def grad(self):
         s, g = self.oracle.stress_grad_units(self.w, self.X, self.ti, self.tj,
                                              self.info.units_per_tile, self.info.vw,
-                                             self.u_begin, self.u_end)
+                                             self.u_begin, self.u_end, q=self.q)
         if getattr(self, "bin_scale", None) is not None:     # scaled where it leaves the sum
             g = g * self.bin_scale[:, None]
         self.exch[:] = 0

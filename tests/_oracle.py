@@ -50,6 +50,10 @@ class Oracle(object):
         L.bbo_stress_grad_units.restype = c_dbl
         L.bbo_stress_grad_units.argtypes = [p_dbl, c_long, c_long, p_dbl, c_int, p_i32, p_i32,
                                             c_long, c_long, c_long, c_long, p_dbl]
+        L.bbo_stress_grad_units_weighted.restype = c_dbl
+        L.bbo_stress_grad_units_weighted.argtypes = [p_dbl, c_long, c_long, p_dbl, c_int, p_i32,
+                                                     p_i32, c_long, c_long, c_long, c_long, c_int,
+                                                     p_dbl, p_dbl]
 
     # K1
     def count_band_regions(self, regions, low=25000, high=10000000):
@@ -122,17 +126,48 @@ class Oracle(object):
                                     float(mu), 1 if f64 else 0, _p(hist), _p(scratch))
         return X, hist
 
-    def stress_grad_units(self, wish, X, tile_I, tile_J, upt, vw, u_begin, u_end, f64=True):
+    def stress_grad_units(self, wish, X, tile_I, tile_J, upt, vw, u_begin, u_end, f64=True, q=0,
+                          sums=None):
+        """The stress and gradient of the pairs of units [u_begin, u_end).  q > 0: the weighted
+        stress of SPEC 2.3.1 (bbo_stress_grad_units_weighted); `sums` (n,) float64, if given,
+        has the weighted degrees of those pairs added to it."""
         w = numpy.ascontiguousarray(wish, dtype=numpy.float64)
         X = numpy.ascontiguousarray(X, dtype=numpy.float64)
         ti = numpy.ascontiguousarray(tile_I, dtype=numpy.int32)
         tj = numpy.ascontiguousarray(tile_J, dtype=numpy.int32)
         g = numpy.zeros_like(X)
-        s = self.lib.bbo_stress_grad_units(_p(w), w.shape[0], w.shape[1], _p(X),
-                                           1 if f64 else 0, ti.ctypes.data_as(p_i32),
-                                           tj.ctypes.data_as(p_i32), int(upt), int(vw),
-                                           int(u_begin), int(u_end), _p(g))
+        args = (_p(w), w.shape[0], w.shape[1], _p(X), 1 if f64 else 0, ti.ctypes.data_as(p_i32),
+                tj.ctypes.data_as(p_i32), int(upt), int(vw), int(u_begin), int(u_end))
+        if q == 0 and sums is None:
+            return float(self.lib.bbo_stress_grad_units(*(args + (_p(g),)))), g
+        if q not in (0, 1, 2):
+            raise ValueError("q must be 0, 1 or 2")
+        if sums is not None:
+            assert sums.dtype == numpy.float64 and sums.shape == (w.shape[0],) and \
+                sums.flags.c_contiguous
+        s = self.lib.bbo_stress_grad_units_weighted(*(args + (int(q), _p(g),
+                                                              None if sums is None else _p(sums))))
         return float(s), g
+
+    def stress_grad_weighted(self, wish, X, q, f64=True, sums=None):
+        """The weighted stress S_q and its gradient over the whole matrix (one unit covering it)."""
+        n = numpy.asarray(wish).shape[0]
+        one = numpy.zeros(1, dtype=numpy.int32)
+        return self.stress_grad_units(wish, X, one, one, 1, n, 0, 1, f64=f64, q=q, sums=sums)
+
+    def solve_weighted(self, wish, X0, iters, lr, q, mu=0.0, bin_scale=None, f64=True):
+        """K steps V <- mu V - lr * bin_scale * g_q, X <- X + V on a dense wish matrix (host loop
+        over stress_grad_weighted): (X_K, [S_q(X_0) .. S_q(X_{K-1})])."""
+        X = numpy.ascontiguousarray(X0, dtype=numpy.float64).copy()
+        V = numpy.zeros_like(X)
+        hist = numpy.zeros(iters)
+        for k in range(iters):
+            hist[k], g = self.stress_grad_weighted(wish, X, q, f64=f64)
+            if bin_scale is not None:
+                g = g * numpy.asarray(bin_scale, dtype=numpy.float64)[:, None]
+            V = mu * V - lr * g
+            X = X + V
+        return X, hist
 
 
 _cached = None
@@ -173,6 +208,8 @@ def _load_mt():
                                          ctypes.c_int]
         lib.bbo_solve_gen_steps_mt.restype = ctypes.c_int
         lib.bbo_solve_gen_steps_mt.argtypes = lib.bbo_solve_gen_mt.argtypes + [p_dbl]
+        lib.bbo_solve_gen_weighted_mt.restype = ctypes.c_int
+        lib.bbo_solve_gen_weighted_mt.argtypes = lib.bbo_solve_gen_steps_mt.argtypes + [ctypes.c_int]
         _cached_mt = lib
     return _cached_mt
 
@@ -215,13 +252,16 @@ def dense_tiles(n, vw=512):
 
 
 def solve_gen_mt(xstar, X0, iters, lr, threads, tiles=None, vw=512, mu=0.0, f64=True,
-                 delta_f32=None, blk_scale=None, bin_scale=None):
+                 delta_f32=None, blk_scale=None, bin_scale=None, q=0):
     """The solver loop with delta_ij = |x*_i - x*_j| formed on the fly over a tile list
     (None: the dense upper triangle) -- no matrix in memory, so N = 50,000 dense and
     BASELINE config 5 (N = 309,568 block-sparse) run on the host.  delta_f32 (default:
     not f64) rounds delta to float exactly as the device's fp32 pack does.  bin_scale: a
     step factor per bin (bb_solver_set_bin_steps); blk_scale: one per block of vw bins
-    (bb_solver_set_block_steps)."""
+    (bb_solver_set_block_steps).  q = 1, 2: the weighted stress of SPEC 2.3.1, w = delta^-q
+    (bbo_solve_gen_weighted_mt); q = 0 runs the unweighted functions bench.py times."""
+    if q not in (0, 1, 2):
+        raise ValueError("q must be 0, 1 or 2")
     lib = _load_mt()
     xs = numpy.ascontiguousarray(xstar, dtype=numpy.float64)
     X = numpy.ascontiguousarray(X0, dtype=numpy.float64).copy()
@@ -239,7 +279,11 @@ def solve_gen_mt(xstar, X0, iters, lr, threads, tiles=None, vw=512, mu=0.0, f64=
     if blk_scale is not None:
         assert numpy.shape(blk_scale) == (-(-n // int(vw)),)
         bin_scale = numpy.repeat(numpy.asarray(blk_scale, dtype=numpy.float64), int(vw))[:n]
-    if bin_scale is None:
+    if q:
+        sc = None if bin_scale is None else numpy.ascontiguousarray(bin_scale, dtype=numpy.float64)
+        assert sc is None or sc.shape == (n,)
+        rc = lib.bbo_solve_gen_weighted_mt(*(args + (None if sc is None else _p(sc), int(q))))
+    elif bin_scale is None:
         rc = lib.bbo_solve_gen_mt(*args)
     else:
         sc = numpy.ascontiguousarray(bin_scale, dtype=numpy.float64)

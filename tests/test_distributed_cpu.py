@@ -159,6 +159,73 @@ def test_degree_steps_on_two_ranks_equal_one_process(oracle):
     assert numpy.array_equal(results[0][1], results[1][1])
 
 
+# ---- weighted stress on several ranks: the weighted degrees are summed in float64 -------------
+def _weighted_worker(rank, world, port, n, k, q):
+    try:
+        sys.path.insert(0, ROOT)
+        os.environ["MASTER_ADDR"] = "127.0.0.1"
+        os.environ["MASTER_PORT"] = str(port)
+        import torch.distributed as dist
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+        import blueberry_amd as bb
+        from tests._engines import OracleEngine
+        from tests.test_weighted_stress import count_map, start, wish_of
+        C = count_map(n, seed=31)
+        x0 = start(n, wish_of(C, "float64"))
+        s = bb.StructureSolver(n_iter=k, dtype="float64", engine=OracleEngine, weight_power=2,
+                               degree_steps=True).fit(C, init=x0)
+        q.put((rank, s.structure_, s.stress_, s.lr_))
+        dist.barrier()
+        dist.destroy_process_group()
+    except Exception:
+        q.put((rank, traceback.format_exc(), None, None))
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_weighted_degree_steps_on_several_ranks_equal_one_process(oracle, world):
+    """StructureSolver(weight_power=2, degree_steps=True) on gloo ranks: every rank sums the
+    weights delta^-2 of its own units' pairs, the float64 sums are added over the ranks, and
+    every rank takes lr = 1 / (2 max s) and the factors max s / s_i.  The result is the
+    one-process run and the weighted oracle loop with those steps."""
+    import torch.multiprocessing as mp
+    import blueberry_amd as bb
+    from tests._engines import OracleEngine
+    from tests.test_weighted_stress import count_map, start, weights, wish_of
+    n, k = 600, 6
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_weighted_worker, args=(r, world, port, n, k, q))
+             for r in range(world)]
+    for p in procs:
+        p.start()
+    results = [q.get(timeout=240) for _ in procs]
+    for p in procs:
+        p.join(timeout=60)
+    for r in results:
+        assert not isinstance(r[1], str), r[1]
+    C = count_map(n, seed=31)
+    W = wish_of(C, "float64")
+    x0 = start(n, W)
+    s = weights(W, 2).sum(1)
+    lr, scale = 1.0 / (2.0 * s.max()), numpy.where(s > 0, s.max() / numpy.where(s > 0, s, 1), 1.0)
+    assert scale.max() > 2.0                       # the steps differ from bin to bin
+    X, hist = oracle.solve_weighted(W, x0, k, lr, 2, bin_scale=scale)
+    one = bb.StructureSolver(n_iter=k, dtype="float64", engine=OracleEngine, distributed=False,
+                             weight_power=2, degree_steps=True).fit(C, init=x0)
+    assert abs(one.lr_ / lr - 1) < 1e-14
+    assert numpy.abs(one.stress_ / hist - 1).max() < 1e-12
+    assert numpy.abs(one.structure_ - X).max() < 1e-12 * numpy.abs(X).max()
+    assert numpy.all(numpy.diff(one.stress_) <= 0.0)
+    results.sort(key=lambda t: t[0])
+    for rank, Xr, hr, lr_r in results:
+        assert abs(lr_r / one.lr_ - 1) < 1e-14
+        assert numpy.abs(hr / one.stress_ - 1).max() < 1e-11
+        assert numpy.abs(Xr - one.structure_).max() < 1e-11 * numpy.abs(X).max()
+    for rank, Xr, hr, _ in results[1:]:
+        assert numpy.array_equal(Xr, results[0][1]) and numpy.array_equal(hr, results[0][2])
+
+
 # ---- init='spectral' on several ranks: which form runs, and that the ranks agree --------
 def _spectral_worker(rank, world, port, n, fail_rank, q):
     """fit(init='spectral') on `world` gloo ranks with an engine that HAS a device-resident

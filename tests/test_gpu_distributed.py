@@ -810,6 +810,65 @@ def test_fit_with_degree_steps_across_processes(dtype, tol, world, comm):
         assert numpy.array_equal(r[1], results[0][1])
 
 
+def _worker_weighted_fit(rank, world, port, n, dtype, comm, q):
+    try:
+        sys.path.insert(0, ROOT)
+        os.environ["MASTER_ADDR"] = "127.0.0.1"
+        os.environ["MASTER_PORT"] = str(port)
+        os.environ["BB_COMM"] = comm
+        os.environ["BB_PEER_TIMEOUT_MS"] = "20000"
+        import torch.distributed as dist
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+        import blueberry_amd as bb
+        w, x0 = _degree_map(n)
+        s = bb.StructureSolver(n_iter=6, dtype=dtype, kind="wish", device=0, degree_steps=True,
+                               weight_power=2, momentum=0.3).fit(w, init=x0)
+        q.put((rank, s.structure_, s.stress_, s.exchange_, s.lr_))
+        dist.barrier()
+        dist.destroy_process_group()
+    except Exception:
+        q.put((rank, traceback.format_exc(), None, None, None))
+
+
+@pytest.mark.parametrize("dtype,tol,world,comm", [("float64", 1e-11, 2, "peer"),
+                                                   ("float32", 1e-5, 3, "peer"),
+                                                   ("float64", 1e-11, 3, "host")])
+def test_fit_weighted_with_degree_steps_across_processes(dtype, tol, world, comm):
+    """fit(weight_power=2, degree_steps=True) on real processes sharing the test GPU: every rank
+    sums the weights delta^-2 of its own units on the device, the float64 sums are added over
+    the ranks, lr = 1 / (2 max s) and the factors max s / s_i go to every rank, and the scaled
+    weighted gradients travel through the peer exchange or the host-staged sum.  Equal to one
+    process, whose weighted degrees are checked on the host."""
+    import torch.multiprocessing as mp
+    import blueberry_amd as bb
+    n = 2300
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker_weighted_fit, args=(r, world, port, n, dtype, comm, q))
+             for r in range(world)]
+    for p in procs:
+        p.start()
+    results = sorted((q.get(timeout=300) for _ in procs), key=lambda t: t[0])
+    for p in procs:
+        p.join(timeout=60)
+    for r in results:
+        assert not isinstance(r[1], str), r[1]
+        assert r[3] == comm
+    w, x0 = _degree_map(n)
+    one = bb.StructureSolver(n_iter=6, dtype=dtype, kind="wish", degree_steps=True, momentum=0.3,
+                             weight_power=2, distributed=False).fit(w, init=x0)
+    w32 = w.astype(dtype).astype(numpy.float64)
+    s = numpy.where(w32 > 0, 1.0 / numpy.where(w32 > 0, w32, 1.0) ** 2, 0.0).sum(1)
+    assert abs(one.lr_ * 2.0 * s.max() - 1) < 1e-13
+    for rank, X, h, _, lr in results:
+        assert abs(lr / one.lr_ - 1) < 1e-14
+        assert numpy.abs(h / one.stress_ - 1).max() < tol
+        assert numpy.abs(X - one.structure_).max() < tol * numpy.abs(one.structure_).max()
+    for r in results[1:]:
+        assert numpy.array_equal(r[1], results[0][1])
+
+
 def _worker_spectral_fit(rank, world, port, n, dtype, comm, q):
     try:
         sys.path.insert(0, ROOT)

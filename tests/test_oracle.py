@@ -382,3 +382,140 @@ def test_numpy_restatement_on_a_wish_matrix_with_bad_entries(oracle):
     s_np, g_np = _spec_stress_grad(w_np, X, 1e-300)
     assert abs(s_c / s_np - 1) < 1e-13
     assert numpy.abs(g_c - g_np).max() < 1e-13 * numpy.abs(g_np).max()
+
+
+# ---- the weighted stress of SPEC 2.3.1 (S_q = sum delta^-q (d - delta)^2) ----------------------
+def _weighted_model(W, X0, k, lr, q, mu=0.0, scale=None):
+    """The numpy float64 model of tests/test_weighted_stress.py with heavy-ball momentum."""
+    from tests.test_weighted_stress import stress_grad
+    X, V, hist = X0.copy(), numpy.zeros_like(X0), []
+    for _ in range(k):
+        S, g = stress_grad(W, X, q)
+        hist.append(S)
+        if scale is not None:
+            g = g * scale[:, None]
+        V = mu * V - lr * g
+        X = X + V
+    return X, numpy.array(hist)
+
+
+def _weighted_problem(n, seed):
+    from tests.test_weighted_stress import count_map, start, wish_of
+    W = wish_of(count_map(n, seed=seed), "float64")
+    return W, start(n, W, seed=seed + 1)
+
+
+@pytest.mark.parametrize("q", [1, 2])
+def test_weighted_units_oracle_equals_numpy_model(oracle, q):
+    """bbo_stress_grad_units_weighted over the device's unit partition (several ranges, both
+    layouts) sums to the numpy model's S_q, gradient and weighted degrees within 1e-13."""
+    from blueberry_amd import _lib
+    from tests.test_weighted_stress import stress_grad, weights
+    lib = _lib.load()
+    n = 290
+    W, X = _weighted_problem(n, 5)
+    s_ref, g_ref = stress_grad(W, X, q)
+    sums_ref = weights(W, q).sum(1)
+    rng = numpy.random.default_rng(q)
+    for dtype in (_lib.BB_F32, _lib.BB_F64):
+        info = _lib.LayoutInfo()
+        _lib.check(lib.bb_layout_dense_info(n, dtype, info))
+        ti = numpy.zeros(info.n_tiles, dtype=numpy.int32)
+        tj = numpy.zeros(info.n_tiles, dtype=numpy.int32)
+        _lib.check(lib.bb_layout_dense_tiles(n, dtype, ti.ctypes.data_as(_lib.p_i32),
+                                             tj.ctypes.data_as(_lib.p_i32), info.n_tiles))
+        cuts = sorted(set([0, info.n_units] + list(rng.integers(0, info.n_units, 3))))
+        s_sum, g_sum, sums = 0.0, numpy.zeros_like(X), numpy.zeros(n)
+        for a, b in zip(cuts, cuts[1:]):
+            s, g = oracle.stress_grad_units(W, X, ti, tj, info.units_per_tile, info.vw, a, b,
+                                            q=q, sums=sums)
+            s_sum += s
+            g_sum += g
+        assert abs(s_sum / s_ref - 1) < 1e-13
+        assert numpy.abs(g_sum - g_ref).max() < 1e-13 * numpy.abs(g_ref).max()
+        assert numpy.abs(sums - sums_ref).max() < 1e-13 * sums_ref.max()
+    s1, g1 = oracle.stress_grad_weighted(W, X, q)
+    assert abs(s1 / s_ref - 1) < 1e-13 and numpy.abs(g1 - g_ref).max() < 1e-13 * numpy.abs(g_ref).max()
+
+
+@pytest.mark.parametrize("q", [1, 2])
+@pytest.mark.parametrize("f64", [True, False])
+def test_weighted_generated_delta_oracle_equals_numpy_model(q, f64):
+    """bbo_solve_gen_weighted_mt on a blocked tile list, with momentum and a step per bin, equals
+    the numpy model on the explicit matrix of the same (float-rounded) deltas within 1e-13."""
+    n, vw, k, mu = 300, 64, 6, 0.4
+    xs = _oracle.random_walk(n)
+    xs[11] = xs[10]                               # a zero wish distance: no constraint
+    x0 = _oracle.noisy_init(xs)
+    w = _oracle.wish_from_coords(xs)
+    if not f64:
+        w = w.astype(numpy.float32).astype(numpy.float64)
+    ti, tj = _oracle.dense_tiles(n, vw)
+    keep = (tj - ti) <= 1
+    tiles = (ti[keep], tj[keep])
+    mask = numpy.zeros((n, n), dtype=bool)
+    for a, b in zip(*tiles):
+        mask[a * vw:(a + 1) * vw, b * vw:(b + 1) * vw] = True
+    mask |= mask.T
+    W = numpy.where(mask, w, 0.0)
+    numpy.fill_diagonal(W, 0.0)
+    from tests.test_weighted_stress import weights
+    s = weights(W, q).sum(1)
+    lr = 1.0 / (2.0 * s.max())
+    scale = s.max() / s
+    X_ref, h_ref = _weighted_model(W, x0, k, lr, q, mu, scale)
+    for threads in (1, 4):
+        X, h = _oracle.solve_gen_mt(xs, x0, k, lr, threads, tiles=tiles, vw=vw, mu=mu, f64=f64,
+                                    bin_scale=scale, q=q)
+        assert numpy.abs(h / h_ref - 1).max() < 1e-13
+        assert numpy.abs(X - X_ref).max() < 1e-13 * numpy.abs(X_ref).max()
+    X0, h0 = _oracle.solve_gen_mt(xs, x0, k, lr, 3, tiles=tiles, vw=vw, f64=f64, q=q)
+    X0_ref, h0_ref = _weighted_model(W, x0, k, lr, q)
+    assert numpy.abs(h0 / h0_ref - 1).max() < 1e-13
+    assert numpy.abs(X0 - X0_ref).max() < 1e-13 * numpy.abs(X0_ref).max()
+
+
+def test_weighted_oracles_at_q0_are_the_unweighted_ones_bit_for_bit(oracle):
+    """q = 0: the weighted entry points give exactly what the unweighted ones give."""
+    n, vw, k = 260, 64, 5
+    W, X = _weighted_problem(n, 8)
+    one = numpy.zeros(1, dtype=numpy.int32)
+    s0, g0 = oracle.stress_grad_units(W, X, one, one, 1, n, 0, 1)
+    s1, g1 = oracle.stress_grad_units(W, X, one, one, 1, n, 0, 1, q=0, sums=numpy.zeros(n))
+    assert s0 == s1 and numpy.array_equal(g0, g1)
+    lib = _oracle._load_mt()
+    xs = _oracle.random_walk(n)
+    x0 = _oracle.noisy_init(xs)
+    ti, tj = _oracle.dense_tiles(n, vw)
+    scale = numpy.linspace(0.5, 2.0, n)
+    for f64, bin_scale in ((True, None), (False, scale)):
+        X_ref, h_ref = _oracle.solve_gen_mt(xs, x0, k, 1e-3, 3, tiles=(ti, tj), vw=vw, mu=0.3,
+                                            f64=f64, bin_scale=bin_scale)
+        Xw = numpy.ascontiguousarray(x0, dtype=numpy.float64).copy()
+        hw = numpy.zeros(k)
+        rc = lib.bbo_solve_gen_weighted_mt(
+            _oracle._p(xs), n, ti.ctypes.data_as(_oracle.p_i32), tj.ctypes.data_as(_oracle.p_i32),
+            ti.shape[0], vw, _oracle._p(Xw), k, 1e-3, 0.3, 1 if f64 else 0, 0 if f64 else 1,
+            1e-290 if f64 else 1e-30, _oracle._p(hw), 3,
+            None if bin_scale is None else _oracle._p(bin_scale), 0)
+        assert rc == 0
+        assert numpy.array_equal(Xw, X_ref) and numpy.array_equal(hw, h_ref)
+
+
+@pytest.mark.parametrize("q", [1, 2])
+def test_weighted_oracle_gradient_matches_finite_differences(oracle, q):
+    n = 14
+    W, X = _weighted_problem(n, 4)
+    W[5, :] = W[:, 5] = 0.0                       # a dead bin
+    _, g = oracle.stress_grad_weighted(W, X, q)
+    h = 1e-6
+    fd = numpy.zeros_like(X)
+    for i in range(n):
+        for c in range(3):
+            Xp, Xm = X.copy(), X.copy()
+            Xp[i, c] += h
+            Xm[i, c] -= h
+            fd[i, c] = (oracle.stress_grad_weighted(W, Xp, q)[0] -
+                        oracle.stress_grad_weighted(W, Xm, q)[0]) / (2 * h)
+    assert numpy.all(g[5] == 0.0)
+    assert numpy.abs(fd - g).max() < 1e-6 * numpy.abs(g).max()

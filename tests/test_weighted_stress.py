@@ -1,6 +1,7 @@
 """Weighted stress (docs/SPEC.md 2.3.1): S_q = sum w (d - delta)^2 with w = delta^-q, q = 1
 (Sammon) and q = 2 (relative stress), against a numpy float64 model of SPEC 2.3.1 / 2.4 /
-2.4.1 that lives in this file (the C oracle knows only q = 0)."""
+2.4.1 that lives in this file.  tests/test_oracle.py pins the weighted C oracle to this model, and
+tests/test_gpu_weighted.py holds the kernels against that oracle at every size and variant."""
 import numpy
 import pytest
 
