@@ -1,7 +1,8 @@
 // bb_solver.hip -- host side of the 3D-structure solver of libblueberry_hip.so: the
 // bb_solver handle (layout, partition into ranks / waves / partial-sum slots, device
 // buffers), kernel launches, the multi-rank exchanges (RCCL, peer arenas) and the
-// bb_solver_* / bb_comm_* entry points of include/blueberry_hip.h.  The kernels are in
+// bb_solver_* / bb_comm_* entry points of include/blueberry_hip.h, and the groups of solvers
+// one process drives on several devices (bb_group_*).  The kernels are in
 // bb_solver_kernels.h.  gfx950 only.
 //
 // Specification: docs/SPEC.md (build-authored; the reference has no solver,
@@ -18,12 +19,15 @@
 #include <type_traits>
 #include <vector>
 
+#include <condition_variable>
 #include <map>
 #include <mutex>
+#include <thread>
 #include <tuple>
 
 #include "bb_comm.h"
 #include "bb_common.h"
+#include "bb_group_barrier.h"
 #include "bb_solver_kernels.h"
 
 // --------------------------------------------------------------------------
@@ -727,6 +731,25 @@ int64_t peer_arena_size(const bb_solver *s) {
     return peer_xpoison_offset(s) + bb::round_up((int64_t)s->world * 64, 256);
 }
 
+// Block b -> bit q set when rank q of `world` holds a unit of a tile in block row or column b:
+// the ranks whose partial for b is not zero by construction.  Every rank derives it alike from
+// the tile list and the partition; the peer exchange and a group's group_apply_kernel both
+// read it, and the two stay bit-identical only through this one table.
+int contributor_mask(const bb_solver *s, std::vector<unsigned> *mask) {
+    mask->assign((size_t)s->L.n_blocks, 0u);
+    const int64_t upt = s->L.units_per_tile;
+    for (int q = 0; q < s->world; ++q) {
+        int64_t ub = 0, ue = 0;
+        BB_TRY(bb_layout_rank_units(s->L.n_units, q, s->world, &ub, &ue));
+        if (ue <= ub) continue;
+        for (int64_t t = ub / upt; t <= (ue - 1) / upt; ++t) {
+            (*mask)[(size_t)s->tile_I[(size_t)t]] |= 1u << q;
+            (*mask)[(size_t)s->tile_J[(size_t)t]] |= 1u << q;
+        }
+    }
+    return BB_OK;
+}
+
 template <typename T>
 int build_peer_tables(bb_solver *s) {
     PeerTable<T> tab[2];
@@ -1125,8 +1148,25 @@ int bb_solver_set_wish_from_cm(bb_solver *s, const bb_cm *cm, int kind, double a
     BB_TRY(bb_cm_device_ptr(cm, &m, &d, &dev));
     BB_REQUIRE(d == s->L.n_bins,
                "bb_solver_set_wish_from_cm: the map's edge differs from the solver's n_bins");
-    BB_REQUIRE(dev == s->device,
-               "bb_solver_set_wish_from_cm: the map lives on another device than the solver");
+    if (dev != s->device) {
+        // a map on another GPU: the pack kernel reads it over peer access where the devices
+        // allow it (one member of a group per device, each packing its own units from one map)
+        int can = 0;
+        if (hipDeviceCanAccessPeer(&can, s->device, dev) != hipSuccess) {
+            (void)hipGetLastError();
+            can = 0;
+        }
+        BB_REQUIRE(can, "bb_solver_set_wish_from_cm: the map lives on another device than the "
+                        "solver, without peer access to it");
+        BB_TRY(bb::enter_device(dev));
+        BB_HIP_CHECK(hipDeviceSynchronize());          // the map's last operation has landed
+        BB_TRY(bb::enter_device(s->device));
+        hipError_t e = hipDeviceEnablePeerAccess(dev, 0);
+        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled)
+            return bb::fail(BB_ERR_HIP, std::string("bb_solver_set_wish_from_cm: peer access: ") +
+                                            hipGetErrorString(e));
+        (void)hipGetLastError();
+    }
     BB_TRY(bb::enter_device(s->device));
     if (s->n_local > 0) {
 #define BB_PACK(TT, WW)                                                                          \
@@ -1884,17 +1924,8 @@ int bb_solver_peer_connect(bb_solver *s, const void *handles) {
         hipFree(s->d_peer_mask);
         s->d_peer_mask = nullptr;
         if (!(env && atoi(env) == 0) && s->world <= 32) {
-            std::vector<unsigned> mask((size_t)s->L.n_blocks, 0u);
-            const int64_t upt = s->L.units_per_tile;
-            for (int q = 0; q < s->world; ++q) {
-                int64_t ub = 0, ue = 0;
-                BB_TRY(bb_layout_rank_units(s->L.n_units, q, s->world, &ub, &ue));
-                if (ue <= ub) continue;
-                for (int64_t t = ub / upt; t <= (ue - 1) / upt; ++t) {
-                    mask[(size_t)s->tile_I[(size_t)t]] |= 1u << q;
-                    mask[(size_t)s->tile_J[(size_t)t]] |= 1u << q;
-                }
-            }
+            std::vector<unsigned> mask;
+            BB_TRY(contributor_mask(s, &mask));
             BB_TRY(dev_alloc(&s->d_peer_mask, s->L.n_blocks));
             BB_HIP_CHECK(hipMemcpy(s->d_peer_mask, mask.data(), mask.size() * sizeof(unsigned),
                                    hipMemcpyHostToDevice));
@@ -2508,3 +2539,251 @@ extern "C" int bb_solver_spectral_init_tol(bb_solver *s, int n_iter, double tol,
     s->grad_pending = false;
     return BB_OK;
 }
+
+// ---- groups: several solvers of ONE process, one host thread each (bb_group_*) ----------
+// The exchange of a group is ordered by HIP events alone: no kernel waits for another, so
+// members may share a GPU (and its hardware queues) in any number.  DESIGN.md 6.9.
+namespace {
+
+constexpr int kGroupAborted = -1;   // a member that left because another one failed
+
+}  // namespace
+
+struct bb_group {
+    std::vector<bb_solver *> m;         // member r = rank r of world m.size()
+    std::vector<void *> exch;           // the members' exchange buffers the tables point to
+    std::vector<void *> d_src;          // per member, on its device: the R exchange pointers
+    std::vector<unsigned *> d_mask;     // per member, on its device: block -> contributing ranks
+    std::vector<hipEvent_t> ready, applied;
+    std::vector<std::thread> threads;
+    // one job at a time, handed to the threads under `mu`
+    std::mutex mu;
+    std::condition_variable cv_job, cv_done;
+    uint64_t job = 0;
+    int done = 0;
+    bool quit = false;
+    int64_t iters = 0;
+    double lr = 0.0;
+    bb::GroupBarrier bar;
+    std::vector<int> rc;
+    std::vector<std::string> err;
+};
+
+namespace {
+
+// Steps 1-2 of an iteration on member r's stream: wait until every member has applied the
+// previous step (its group_apply_kernel read this member's partial: WAR), grad, "ready".
+int group_grad(bb_group *g, int r) {
+    bb_solver *s = g->m[(size_t)r];
+    for (hipEvent_t e : g->applied) BB_HIP_CHECK(hipStreamWaitEvent(s->stream, e, 0));
+    BB_TRY(launch_grad(s));
+    BB_TRY(launch_reduce(s, kReduceExchange, 0.0, nullptr));
+    BB_HIP_CHECK(hipEventRecord(g->ready[(size_t)r], s->stream));
+    return BB_OK;
+}
+
+// Step 4: wait for every member's partial, sum in rank order and step, "applied".
+int group_apply(bb_group *g, int r) {
+    bb_solver *s = g->m[(size_t)r];
+    for (hipEvent_t e : g->ready) BB_HIP_CHECK(hipStreamWaitEvent(s->stream, e, 0));
+    const int64_t n3 = s->L.n_pad * 3;
+    const dim3 grid((unsigned)((n3 + 255) / 256)), block(256);
+    const int world = (int)g->m.size(), ch = (int)(3 * s->L.vw);
+    double *hist = s->d_stress_hist + s->hist_n;
+    if (s->dtype == BB_F32)
+        BB_HIP_CHECK(bb::launch(group_apply_kernel<float>, grid, block, 0, s->stream, (float *)s->d_X,
+                                (float *)s->d_V, (const float *const *)g->d_src[(size_t)r], world, n3,
+                                (float)g->lr, (float)s->momentum, hist, g->d_mask[(size_t)r], ch));
+    else
+        BB_HIP_CHECK(bb::launch(group_apply_kernel<double>, grid, block, 0, s->stream, (double *)s->d_X,
+                                (double *)s->d_V, (const double *const *)g->d_src[(size_t)r], world,
+                                n3, g->lr, s->momentum, hist, g->d_mask[(size_t)r], ch));
+    BB_HIP_CHECK(hipEventRecord(g->applied[(size_t)r], s->stream));
+    s->hist_n++;
+    return BB_OK;
+}
+
+// One member's share of a bb_group_iterate.  The barriers put every record of an event before
+// every wait that refers to it; a member that fails to enqueue makes all of them leave at the
+// next barrier, before anybody waits on something it will not record.
+int group_run(bb_group *g, int r) {
+    static_assert(BB_OK == 0, "bb::group_steps takes 0 for success");
+    return bb::group_steps(g->bar, g->iters, bb::enter_device(g->m[(size_t)r]->device),
+                           kGroupAborted, [&](int64_t) { return group_grad(g, r); },
+                           [&](int64_t) { return group_apply(g, r); });
+}
+
+void group_worker(bb_group *g, int r) {
+    (void)hipSetDevice(g->m[(size_t)r]->device);
+    uint64_t seen = 0;
+    for (;;) {
+        {
+            std::unique_lock<std::mutex> lk(g->mu);
+            g->cv_job.wait(lk, [&] { return g->quit || g->job != seen; });
+            if (g->quit) return;
+            seen = g->job;
+        }
+        const int rc = group_run(g, r);
+        std::lock_guard<std::mutex> lk(g->mu);
+        g->rc[(size_t)r] = rc;
+        g->err[(size_t)r] = rc > 0 ? std::string(bb_last_error()) : std::string();
+        if (++g->done == (int)g->m.size()) g->cv_done.notify_all();
+    }
+}
+
+void group_free(bb_group *g) {
+    {
+        std::lock_guard<std::mutex> lk(g->mu);
+        g->quit = true;
+    }
+    g->cv_job.notify_all();
+    for (std::thread &t : g->threads) t.join();
+    for (size_t r = 0; r < g->m.size(); ++r) {
+        hipSetDevice(g->m[r]->device);
+        hipStreamSynchronize(g->m[r]->stream);
+        if (r < g->ready.size() && g->ready[r]) hipEventDestroy(g->ready[r]);
+        if (r < g->applied.size() && g->applied[r]) hipEventDestroy(g->applied[r]);
+        if (r < g->d_src.size()) hipFree(g->d_src[r]);
+        if (r < g->d_mask.size()) hipFree(g->d_mask[r]);
+    }
+    delete g;
+    (void)hipGetLastError();
+}
+
+int group_setup(bb_group *g) {
+    const int n = (int)g->m.size();
+    // peer access between every pair of DISTINCT devices (a repeated device needs none)
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b < n; ++b) {
+            const int da = g->m[(size_t)a]->device, db = g->m[(size_t)b]->device;
+            if (da == db) continue;
+            int can = 0;
+            BB_HIP_CHECK(hipDeviceCanAccessPeer(&can, da, db));
+            if (!can)
+                return bb::fail(BB_ERR_HIP, "bb_group_create: device " + std::to_string(da) +
+                                                " has no peer access to device " + std::to_string(db));
+            BB_TRY(bb::enter_device(da));
+            hipError_t e = hipDeviceEnablePeerAccess(db, 0);
+            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled)
+                return bb::fail(BB_ERR_HIP, std::string("bb_group_create: hipDeviceEnablePeerAccess: ") +
+                                                hipGetErrorString(e));
+            (void)hipGetLastError();
+        }
+    std::vector<unsigned> mask;
+    BB_TRY(contributor_mask(g->m[0], &mask));
+    for (int r = 0; r < n; ++r) {
+        bb_solver *s = g->m[(size_t)r];
+        BB_TRY(bb::enter_device(s->device));
+        BB_HIP_CHECK(hipStreamSynchronize(s->stream));
+        BB_TRY(dev_alloc((char **)&g->d_src[(size_t)r], (int64_t)(n * sizeof(void *))));
+        BB_HIP_CHECK(hipMemcpy(g->d_src[(size_t)r], g->exch.data(), n * sizeof(void *),
+                               hipMemcpyHostToDevice));
+        BB_TRY(dev_alloc(&g->d_mask[(size_t)r], (int64_t)mask.size()));
+        BB_HIP_CHECK(hipMemcpy(g->d_mask[(size_t)r], mask.data(), mask.size() * sizeof(unsigned),
+                               hipMemcpyHostToDevice));
+        BB_HIP_CHECK(hipEventCreateWithFlags(&g->ready[(size_t)r], hipEventDisableTiming));
+        BB_HIP_CHECK(hipEventCreateWithFlags(&g->applied[(size_t)r], hipEventDisableTiming));
+        // recorded once, so that the first iteration's waits refer to a completed record
+        BB_HIP_CHECK(hipEventRecord(g->applied[(size_t)r], s->stream));
+        BB_HIP_CHECK(hipEventRecord(g->ready[(size_t)r], s->stream));
+    }
+    for (int r = 0; r < n; ++r) {
+        try {
+            g->threads.emplace_back(group_worker, g, r);
+        } catch (...) {
+            return bb::fail(BB_ERR_NOMEM, "bb_group_create: cannot start a host thread");
+        }
+    }
+    return BB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bb_group_create(bb_group **out, bb_solver *const *members, int n) {
+    BB_REQUIRE(out != nullptr && members != nullptr, "bb_group_create: NULL argument");
+    *out = nullptr;
+    BB_REQUIRE(n >= 1 && n <= kMaxPeers, "bb_group_create: need 1 <= n <= 16 members");
+    for (int r = 0; r < n; ++r) {
+        const bb_solver *s = members[r];
+        const bb_solver *s0 = members[0];
+        if (!s) return bb::fail(BB_ERR_INVALID, "bb_group_create: member " + std::to_string(r) + " is NULL");
+        if (s->rank != r || s->world != n)
+            return bb::fail(BB_ERR_INVALID, "bb_group_create: member " + std::to_string(r) +
+                                                " is rank " + std::to_string(s->rank) + " of world " +
+                                                std::to_string(s->world) + "; member r must be rank r "
+                                                "of world " + std::to_string(n));
+        if (s->L.n_bins != s0->L.n_bins)
+            return bb::fail(BB_ERR_INVALID, "bb_group_create: member " + std::to_string(r) +
+                                                " has n_bins " + std::to_string(s->L.n_bins) +
+                                                ", member 0 " + std::to_string(s0->L.n_bins));
+        if (s->dtype != s0->dtype)
+            return bb::fail(BB_ERR_INVALID, "bb_group_create: member " + std::to_string(r) +
+                                                " has another dtype than member 0");
+        if (s->tile_I != s0->tile_I || s->tile_J != s0->tile_J)
+            return bb::fail(BB_ERR_INVALID, "bb_group_create: member " + std::to_string(r) +
+                                                " has another tile list than member 0");
+        if (s->n_maps > 1)
+            return bb::fail(BB_ERR_INVALID, "bb_group_create: member " + std::to_string(r) +
+                                                " is a solver of several maps");
+    }
+    bb_group *g = new (std::nothrow) bb_group();
+    if (!g) return bb::fail(BB_ERR_NOMEM, "bb_group_create: out of host memory");
+    g->m.assign(members, members + n);
+    for (bb_solver *s : g->m) g->exch.push_back(s->d_exch);
+    g->d_src.assign((size_t)n, nullptr);
+    g->d_mask.assign((size_t)n, nullptr);
+    g->ready.assign((size_t)n, nullptr);
+    g->applied.assign((size_t)n, nullptr);
+    g->rc.assign((size_t)n, BB_OK);
+    g->err.assign((size_t)n, std::string());
+    g->bar.n = n;
+    const int rc = group_setup(g);
+    if (rc != BB_OK) {
+        std::string keep = bb_last_error();
+        group_free(g);
+        bb::set_error(keep);
+        return rc;
+    }
+    *out = g;
+    return BB_OK;
+}
+
+int bb_group_iterate(bb_group *g, int64_t iters, double lr) {
+    BB_REQUIRE(g != nullptr, "bb_group_iterate: group is NULL");
+    BB_REQUIRE(iters >= 0, "bb_group_iterate: iters < 0");
+    for (size_t r = 0; r < g->m.size(); ++r) {
+        bb_solver *s = g->m[r];
+        BB_TRY(check_ready(s, "bb_group_iterate"));
+        if (s->grad_pending)
+            return bb::fail(BB_ERR_STATE, "bb_group_iterate: member " + std::to_string(r) +
+                                              " has a bb_solver_grad pending");
+        if (s->hist_n + iters > s->hist_cap)
+            return bb::fail(BB_ERR_STATE, "bb_group_iterate: stress history full");
+        if (s->d_exch != g->exch[r])
+            return bb::fail(BB_ERR_STATE, "bb_group_iterate: member " + std::to_string(r) +
+                                              " changed its exchange buffer after bb_group_create");
+    }
+    if (iters == 0) return BB_OK;
+    std::unique_lock<std::mutex> lk(g->mu);
+    g->iters = iters;
+    g->lr = lr;
+    g->done = 0;
+    std::fill(g->rc.begin(), g->rc.end(), BB_OK);
+    ++g->job;
+    g->cv_job.notify_all();
+    g->cv_done.wait(lk, [&] { return g->done == (int)g->m.size(); });
+    for (size_t r = 0; r < g->m.size(); ++r)
+        if (g->rc[r] > 0)
+            return bb::fail(g->rc[r], "bb_group_iterate: member " + std::to_string(r) + ": " + g->err[r]);
+    return BB_OK;
+}
+
+int bb_group_destroy(bb_group *g) {
+    if (!g) return BB_OK;
+    group_free(g);
+    return BB_OK;
+}
+
+}  // extern "C"

@@ -1308,6 +1308,42 @@ __global__ __launch_bounds__(256) void apply_kernel(T *__restrict__ X, T *__rest
     if (e == 0 && stress_out) *stress_out = (double)exch[n3] + (double)exch[n3 + 1];
 }
 
+// ---- the event-ordered exchange of a group (bb_group_*: several solvers of ONE process) ----
+// src[r] (a device-side table, local or peer pointers) is member r's exchange buffer
+// [g (n_pad,3) | stress hi | lo], left there by bb_solver_grad's reduce: the same partial the
+// peer-mode reduce pushes (scale and per-bin factor applied the same way).  The host has
+// ordered this launch behind every member's grad by events, so nothing here waits or polls.
+// Per element: every member's contribution is requested before the first add, the sum runs in
+// member order from 0 with a masked-out member adding 0 -- peer_receive_kernel's order, bit for
+// bit -- then V <- mu V - lr g, X <- X + V.  The stress: (hi, lo) summed in double, in order.
+template <typename T>
+__global__ __launch_bounds__(256) void group_apply_kernel(
+    T *__restrict__ X, T *__restrict__ V, const T *const *__restrict__ src, int world, int64_t n3,
+    T lr, T mu, double *__restrict__ stress_out, const unsigned *__restrict__ peer_mask, int ch) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < n3) {
+        const unsigned mk = peer_mask != nullptr ? peer_mask[e / ch] : ~0u;
+        T g = T(0);
+        for (int r0 = 0; r0 < world; r0 += 8) {
+            T v[8];
+#pragma unroll
+            for (int p = 0; p < 8; ++p)
+                v[p] = (r0 + p < world && (mk >> (r0 + p) & 1u)) ? src[r0 + p][e] : T(0);
+#pragma unroll
+            for (int p = 0; p < 8; ++p)
+                if (r0 + p < world) g += v[p];
+        }
+        const T vv = mu * V[e] - lr * g;
+        V[e] = vv;
+        X[e] += vv;
+    }
+    if (e == 0) {
+        double S = 0.0;
+        for (int r = 0; r < world; ++r) S += (double)src[r][n3] + (double)src[r][n3 + 1];
+        *stress_out = S;
+    }
+}
+
 // --------------------------------------------------------------------------
 // packing kernels
 // --------------------------------------------------------------------------

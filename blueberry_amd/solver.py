@@ -8,7 +8,10 @@ reference has, `FitHiC(hyper-parameters).fit_transform(data)`
 specified in docs/SPEC.md and runs entirely in libblueberry_hip.so
 (include/blueberry_hip.h); this module only validates arguments, owns the
 handle and, for world_size > 1, drives one all-reduce per iteration through
-torch.distributed (backend "nccl" = RCCL over xGMI).
+torch.distributed (backend "nccl" = RCCL over xGMI) -- or, with
+`StructureSolver(devices=[...])`, drives several GPUs from this one process without
+torch (`GroupEngine`: one solver per device, one host thread each, the sum over them
+ordered by HIP events, `bb_group_*`).
 """
 import os
 import sys
@@ -520,6 +523,151 @@ class HipEngine(object):
         return {"unit_bytes": int(b.value), "pairs_dense": int(p.value)}
 
 
+class GroupEngine(object):
+    """Several GPUs from ONE process (`bb_group_*`): member r is a HipEngine playing rank r of
+    world R on devices[r] (a device may repeat: members then share it), each holding only its
+    own units; one host thread per member enqueues its iterations, and the partials are summed
+    by group_apply_kernel in rank order, ordered by HIP events.  To `StructureSolver` it looks
+    like one engine of world 1: every setter goes to all members, degrees, weight sums and
+    matvecs come back summed over the members in rank order (float64 / int64), coordinates and
+    stress history are member 0's -- all members hold the same bits."""
+
+    def __init__(self, n_bins, dtype, devices, tiles=None):
+        self._lib = _lib.load()
+        self.n_bins, self.dtype = int(n_bins), dtype
+        self.devices = [int(d) for d in devices]
+        self.device = self.devices[0]
+        self.world = 1                     # what the caller sees: one engine, summed results
+        self._comm_state = "group"
+        self._g = _lib.c_void_p()
+        self.members = []
+        try:
+            R = len(self.devices)
+            for r, d in enumerate(self.devices):
+                self.members.append(HipEngine(n_bins, dtype, rank=r, world=R, device=d, tiles=tiles))
+            handles = (_lib.c_void_p * R)(*[m._h.value for m in self.members])
+            _lib.check(self._lib.bb_group_create(self._g, handles, R), "bb_group_create")
+        except BaseException:
+            self.close()
+            raise
+
+    def close(self):
+        if self._g:
+            self._lib.bb_group_destroy(self._g)
+            self._g = _lib.c_void_p()
+        for m in self.members:
+            m.close()
+        self.members = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def layout(self):
+        return self.members[0].layout()
+
+    # -- inputs: every member packs its own units from the one input --------------------
+    def set_wish_dense(self, matrix, kind, alpha):
+        m = _check_square(matrix, self.n_bins)
+        for e in self.members:
+            e.set_wish_dense(m, kind, alpha)
+
+    def set_wish_sparse(self, rows, cols, vals, kind, alpha, KRnorm=None, KRexpected=None):
+        for e in self.members:
+            e.set_wish_sparse(rows, cols, vals, kind, alpha, KRnorm, KRexpected)
+
+    def set_wish_triples(self, dev_triples, kind, alpha, KRnorm=None, KRexpected=None):
+        """`dev_triples.per_device`: the triples uploaded once per distinct device."""
+        per_device = getattr(dev_triples, "per_device", {dev_triples.device: dev_triples})
+        for e in self.members:
+            e.set_wish_triples(per_device[e.device], kind, alpha, KRnorm, KRexpected)
+
+    def set_wish_from_coords(self, xstar):
+        x = _check_coords(xstar, self.n_bins)
+        for e in self.members:
+            e.set_wish_from_coords(x)
+
+    def set_wish_resident(self, cm, kind, alpha):
+        """A resident ContactMap: members on its device pack device to device, members on
+        other devices over peer access where the devices allow it; the rest share ONE host
+        download of it."""
+        dev = cm._resident()
+        host = None
+        for e in self.members:
+            if e.device != dev.device:
+                rc = self._lib.bb_solver_set_wish_from_cm(e._h, dev._h, _KINDS[kind], float(alpha))
+                if rc == _lib.BB_OK:
+                    continue
+                if not (rc == _lib.BB_ERR_INVALID and "without peer access" in _lib.last_error()):
+                    _lib.check(rc, "bb_solver_set_wish_from_cm")
+                if host is None:
+                    host = cm.to_host()
+                e.set_wish_dense(host, kind, alpha)
+            else:
+                e.set_wish_from_cm(dev, kind, alpha)
+
+    # -- per-bin steps, weighting: summed on the host in rank order ---------------------
+    def degrees(self):
+        out = self.members[0].degrees()
+        for e in self.members[1:]:
+            out = out + e.degrees()
+        return out
+
+    def set_weight_power(self, q):
+        for e in self.members:
+            e.set_weight_power(q)
+
+    def weight_sums(self):
+        out = self.members[0].weight_sums()
+        for e in self.members[1:]:
+            out = out + e.weight_sums()
+        return out
+
+    def set_bin_steps(self, scale):
+        for e in self.members:
+            e.set_bin_steps(scale)
+
+    def matvec_sq(self, x):
+        """(D o D) @ x over the whole map: the members' products summed in rank order (the
+        host-driven spectral start)."""
+        out = self.members[0].matvec_sq(x)
+        for e in self.members[1:]:
+            out = out + e.matvec_sq(x)
+        return out
+
+    # -- iterations -------------------------------------------------------
+    def set_coords(self, x0):
+        x = _check_coords(x0, self.n_bins)
+        for e in self.members:
+            e.set_coords(x)
+
+    def set_momentum(self, mu):
+        for e in self.members:
+            e.set_momentum(mu)
+
+    def iterate(self, iters, lr):
+        _lib.check(self._lib.bb_group_iterate(self._g, int(iters), float(lr)), "bb_group_iterate")
+
+    def get_coords(self):
+        return self.members[0].get_coords()
+
+    def stress_history(self):
+        return self.members[0].stress_history()
+
+    def member_coords(self):
+        """Every member's coordinates (identical bits: a check, not a result)."""
+        return [e.get_coords() for e in self.members]
+
+    def member_stress_histories(self):
+        return [e.stress_history() for e in self.members]
+
+    def sync(self):
+        for e in self.members:
+            e.sync()
+
+
 def _check_square(matrix, n_bins):
     m = numpy.asarray(matrix)
     if m.ndim != 2 or m.shape[0] != m.shape[1]:
@@ -729,6 +877,33 @@ def _dist_state(distributed):
     return 0, 1
 
 
+def _check_devices(devices, n_gpus, device, distributed):
+    """The device list of StructureSolver(devices=, n_gpus=), validated without a GPU, or
+    None when neither is given."""
+    if devices is None and n_gpus is None:
+        return None
+    if devices is not None and n_gpus is not None:
+        raise ValueError("give devices or n_gpus, not both")
+    if device is not None:
+        raise ValueError("give device or devices / n_gpus, not both")
+    if distributed:
+        raise ValueError("devices / n_gpus drive several GPUs from one process; distributed=True "
+                         "runs one GPU per process")
+    if n_gpus is not None:
+        if isinstance(n_gpus, bool) or int(n_gpus) != n_gpus or int(n_gpus) < 1:
+            raise ValueError("n_gpus must be a positive integer")
+        devices = list(range(int(n_gpus)))
+    devices = list(devices)
+    if not devices:
+        raise ValueError("devices must name at least one device")
+    for d in devices:
+        if isinstance(d, bool) or not isinstance(d, (int, numpy.integer)) or d < 0:
+            raise ValueError("devices must be non-negative device indices, got %r" % (d,))
+    if len(devices) > 16:
+        raise ValueError("devices: at most 16 members")
+    return [int(d) for d in devices]
+
+
 class StructureSolver(object):
     """Infer 3D bin coordinates from a Hi-C contact matrix (metric MDS).
 
@@ -784,6 +959,18 @@ class StructureSolver(object):
         Heavy-ball coefficient mu: V <- mu V - lr g, X <- X + V.  0 = plain steps.
     device : int or None
         HIP device index; None = LOCAL_RANK (distributed) or 0.
+    devices : list of int or None
+        Several GPUs driven from THIS process, no torch.distributed job needed: member r of
+        the group plays rank r of world len(devices) on devices[r], packs only its own units
+        from the one input, and a host thread per member enqueues its iterations; the
+        partials are summed in rank order by an exchange ordered with HIP events
+        (`GroupEngine`, `bb_group_*`), bit-identical to the process-per-rank peer exchange
+        (two-launch form) at the same world size.  One entry: as `device=`.  A device may
+        repeat -- members then take turns on it: a rehearsal, the one form a one-GPU box can
+        run.  Not with `device`, `n_gpus`, `distributed=True` or inside a torch.distributed
+        job; not for `fit_many`.
+    n_gpus : int or None
+        Shorthand for devices=list(range(n_gpus)).
     distributed : bool or None
         None: shard over the ranks of an initialised torch.distributed job if
         there is one.  Every rank passes the same matrix and gets the same result.
@@ -794,8 +981,9 @@ class StructureSolver(object):
     stress_ : numpy.ndarray, shape (n_iter,) -- stress BEFORE each step
     n_bins_, lr_ : the problem size and the step actually used
     exchange_ : how the ranks summed their partial gradients ('rccl', 'peer', 'torch',
-        'host'), None on one rank.  Results are reproducible bit for bit for a given
-        transport; fit() never picks one by timing (that is bench.py's trial).
+        'host', 'group' for devices=), None on one rank.  Results are reproducible bit for
+        bit for a given transport; fit() never picks one by timing (that is bench.py's trial).
+    devices_ : the devices of a `devices=` / `n_gpus=` fit, member by member; else None.
 
     Failure on several ranks.  A rank that fails mid-fit raises, and takes the library's
     communicator out of the cache (its peers may still sit in a collective on it).  With
@@ -810,7 +998,7 @@ class StructureSolver(object):
     def __init__(self, n_iter=100, lr="auto", dtype="float32", alpha=3.0, kind="counts",
                  seed=0, device=None, distributed=None, engine=None, momentum=0.0,
                  init="random", tol=None, check_every=10, spectral_iter=40, spectral_tol=1e-3,
-                 degree_steps=False, weight_power=0):
+                 degree_steps=False, weight_power=0, devices=None, n_gpus=None):
         if dtype not in _DTYPES:
             raise ValueError("dtype must be 'float32' or 'float64'")
         if kind not in _KINDS:
@@ -848,6 +1036,12 @@ class StructureSolver(object):
         # Engine factory: the HIP engine unless a test injects another one to
         # rehearse the multi-rank orchestration without a GPU.
         self._engine_factory = engine if engine is not None else HipEngine
+        self.devices, self.n_gpus = devices, n_gpus
+        self._group = _check_devices(devices, n_gpus, device, distributed)
+        if self._group is not None and len(self._group) == 1:
+            self.device = self._group[0]           # one entry: as device=
+        elif self._group is not None and engine is not None:
+            raise ValueError("devices= runs HIP engines of its own; it takes no engine=")
 
     def _pick_device(self, world):
         if self.device is not None:
@@ -881,7 +1075,9 @@ class StructureSolver(object):
         if n < 2:
             raise ValueError("need at least 2 bins (the contact map is empty)" if n == 0 else
                              "need at least 2 bins")
-        rank, world = _dist_state(self.distributed)
+        devices = self._group_devices()                 # checked for one entry as well
+        group = devices if devices and len(devices) > 1 else None
+        rank, world = (0, 1) if devices else _dist_state(self.distributed)
         lr = 1.0 / (2.0 * n) if self.lr == "auto" else float(self.lr)
         if init is None and self.init == "random":
             init = numpy.random.default_rng(self.seed).standard_normal((n, 3))
@@ -894,10 +1090,15 @@ class StructureSolver(object):
             tiles = tiles_from_entries(n, rows, cols, self.dtype)
         elif triples:
             tiles = matrix.tiles(n, self.dtype)
-        eng = self._engine_factory(n, self.dtype, rank=rank, world=world,
-                                   device=self._pick_device(world), tiles=tiles)
+        if group:
+            eng = GroupEngine(n, self.dtype, group, tiles=tiles)
+        else:
+            eng = self._engine_factory(n, self.dtype, rank=rank, world=world,
+                                       device=self._pick_device(world), tiles=tiles)
         try:
-            if resident:
+            if resident and hasattr(eng, "set_wish_resident"):
+                eng.set_wish_resident(matrix, self.kind, self.alpha)
+            elif resident:
                 dev = matrix._resident()
                 if dev.device == eng.device:
                     eng.set_wish_from_cm(dev, self.kind, self.alpha)
@@ -992,8 +1193,27 @@ class StructureSolver(object):
             raise
         finally:
             eng.close()
+        self.devices_ = devices
         self.n_bins_, self.lr_, self.n_iter_ = n, lr, int(self.stress_.shape[0])
         return self
+
+    def _group_devices(self):
+        """The devices of a devices= / n_gpus= fit (one entry included), checked against this
+        process (device count, no torch.distributed job), or None without them."""
+        if self._group is None:
+            return None
+        dist = sys.modules.get("torch.distributed")      # never imported here
+        if dist is not None and dist.is_available() and dist.is_initialized():
+            raise ValueError("devices= drives several GPUs from one process; inside a "
+                             "torch.distributed job every rank runs its own GPU (leave devices "
+                             "unset)")
+        count = _lib.c_int()
+        _lib.check(_lib.load().bb_device_count(count), "bb_device_count")
+        bad = [d for d in self._group if d >= count.value]
+        if bad:
+            raise ValueError("devices: index %d is out of range (%d HIP devices)"
+                             % (bad[0], count.value))
+        return list(self._group)
 
     def fit_triples(self, triples, resolution, n_bins, KRnorm=None, KRexpected=None, init=None):
         """Solve straight from a Rao-format sparse file's content, never building
@@ -1012,6 +1232,20 @@ class StructureSolver(object):
             # nan_to_num (pyx:102), the binning and the tile occupancy on the device: the host
             # never makes a pass over the triples (round 3: two isfinite passes, two divide +
             # astype passes and a scipy COO over 240 MB at chr1@10kb)
+            group = self._group_devices()
+            if group and len(group) > 1:
+                # uploaded once per distinct device; every member packs from its own device's copy
+                per_device = {}
+                try:
+                    for d in group:
+                        if d not in per_device:
+                            per_device[d] = DeviceTriples(triples, resolution, d)
+                    dev = per_device[group[0]]
+                    dev.per_device = per_device
+                    return self._fit_impl(dev, n, init, KRnorm, KRexpected)
+                finally:
+                    for t in per_device.values():
+                        t.close()
             _, world = _dist_state(self.distributed)
             dev = DeviceTriples(triples, resolution, self._pick_device(world))
             try:
@@ -1048,6 +1282,9 @@ class StructureSolver(object):
         map (None entries: the seeded default of `fit()`).
         Sets `structures_` (list of (n_m, 3) float64), `stresses_` (list of per-iteration
         arrays), `n_bins_many_`, `lrs_`, `n_iter_`; returns self."""
+        if self._group is not None and len(self._group) > 1:
+            raise ValueError("fit_many with devices= / n_gpus= is not supported: fit_many runs "
+                             "on one device, or one per rank of a torch.distributed job")
         if not hasattr(self._engine_factory, "set_maps"):
             raise TypeError("fit_many needs an engine that holds several maps (HipEngine)")
         maps = list(maps)

@@ -19,7 +19,8 @@
  *     returns a thread-local message for the last failure on this thread;
  *   - host pointers are borrowed for the duration of the call only; device
  *     memory is owned by opaque handles with explicit create/destroy;
- *   - one handle = one device = one host thread at a time; the library never
+ *   - one handle = one device = one host thread at a time (a bb_group's member
+ *     solvers belong to the group's own threads while bb_group_iterate runs); the library never
  *     calls the oracle or any CPU fallback: without a usable GPU every compute
  *     entry point fails with BB_ERR_HIP.
  */
@@ -370,6 +371,33 @@ BB_API int bb_solver_peer_form(bb_solver *s, int *one_launch);
  * where a trial has compared its coordinates with RCCL's (bench.py). */
 BB_API int bb_solver_peer_set_form(bb_solver *s, int one_launch);
 
+/* Several GPUs driven from ONE process: a group of existing solvers, member r = rank r of world
+ * n, all with the same n_bins, dtype and tile list (else BB_ERR_INVALID naming the mismatch).
+ * Every setter stays the per-solver call (wish distances, coordinates, momentum, bin steps,
+ * weight power: the same values on every member); the group only iterates them.
+ *   bb_group_create   enables peer access between the members' DISTINCT devices (a device may
+ *                     repeat: members then share it -- a rehearsal) and starts one host thread
+ *                     per member on the member's device
+ *   bb_group_iterate  `iters` x, on every member's stream: wait for every member's "applied"
+ *                     event of the previous step; grad (bb_solver_grad's two launches); record
+ *                     "ready"; host barrier; wait for every member's "ready"; group_apply_kernel
+ *                     (the R partials summed in rank order, read straight from the members'
+ *                     exchange buffers; the update; the stress); record "applied"; host barrier.
+ *                     No kernel waits for another, so members can share a GPU and its hardware
+ *                     queues in any number.  The sums are those of the two-launch peer exchange
+ *                     at the same world size: bit-identical members and results.  Stress history
+ *                     as bb_solver_iterate (BB_ERR_STATE past its capacity, nothing enqueued).  A
+ *                     member that fails to enqueue makes every thread stop at the next barrier;
+ *                     the call returns its error.  No synchronisation at the end.
+ *   bb_group_destroy  joins the threads and drains the members' streams; the members stay
+ *                     (destroy the group first, then them)
+ * No counterpart in the reference (it has no solver; its one multi-GPU idiom is a device list
+ * handed to one constructor). */
+typedef struct bb_group bb_group;
+BB_API int bb_group_create(bb_group **out, bb_solver *const *members, int n);
+BB_API int bb_group_iterate(bb_group *g, int64_t iters, double lr);
+BB_API int bb_group_destroy(bb_group *g);
+
 /* Host-staged access to the exchange buffer, widened to float64, for callers
  * whose collective runs on host memory (MPI, gloo): read after bb_solver_grad,
  * sum over ranks, write back, then bb_solver_apply.  n = bb_solver_exchange_size. */
@@ -521,7 +549,9 @@ BB_API int bb_cm_correlation(bb_cm *cm, double *tflops);
  * the next call that needs it). */
 BB_API int bb_cm_release_scratch(int device);
 /* Hand the resident matrix to a solver of n_bins = d bins on the same device, device
- * to device (same meaning of kind / alpha as bb_solver_set_wish_dense). */
+ * to device (same meaning of kind / alpha as bb_solver_set_wish_dense).  A solver on another
+ * device packs over peer access where hipDeviceCanAccessPeer allows it (enabled here); without
+ * it BB_ERR_INVALID "... on another device ...". */
 BB_API int bb_solver_set_wish_from_cm(bb_solver *s, const bb_cm *cm, int kind, double alpha);
 /* The same into the bins [bin_offset, bin_offset + d) of a solver of several maps
  * (bb_solver_set_maps), d = the map's edge. */
