@@ -374,11 +374,39 @@ int build_indices(bb_solver *s) {
     return BB_OK;
 }
 
-// (dtype, layout) -> template arguments.  F(float, wide), F(double, wide), F(double, narrow).
-#define BB_BY_LAYOUT(s, F, ...)                                          \
-    ((s)->dtype == BB_F32 ? F<float, true>(__VA_ARGS__)                  \
-                          : ((s)->wide ? F<double, true>(__VA_ARGS__)    \
-                                       : F<double, false>(__VA_ARGS__)))
+// Which instantiation a launch takes.  The kernels exist for three layouts, (float, wide),
+// (double, wide) and (double, narrow) (bb::wide_layout): by_layout(s, f) calls
+// f(LayoutTag<T, W>{}) with the solver's, by_dtype(s, f) calls f(TypeTag<T>{}) where only the
+// element type matters.  with_int<V...>(v, f) calls f(std::integral_constant<int, V>{}) for
+// the first V equal to v, the last V standing for every other value.
+template <typename TT>
+struct TypeTag {
+    using T = TT;
+};
+template <typename TT, bool WW>
+struct LayoutTag {
+    using T = TT;
+    static constexpr bool W = WW;
+};
+
+template <typename F>
+decltype(auto) by_layout(const bb_solver *s, F &&f) {
+    if (s->dtype == BB_F32) return f(LayoutTag<float, true>{});
+    if (s->wide) return f(LayoutTag<double, true>{});
+    return f(LayoutTag<double, false>{});
+}
+
+template <typename F>
+decltype(auto) by_dtype(const bb_solver *s, F &&f) {
+    if (s->dtype == BB_F32) return f(TypeTag<float>{});
+    return f(TypeTag<double>{});
+}
+
+template <int V, int... Rest, typename F>
+decltype(auto) with_int(int v, F &&f) {
+    if constexpr (sizeof...(Rest) == 0) return f(std::integral_constant<int, V>{});
+    else return v == V ? f(std::integral_constant<int, V>{}) : with_int<Rest...>(v, f);
+}
 
 // the sweep kernel of an OP: weighted_sweep_kernel for the weighted stress (SPEC 2.3.1)
 template <typename T, bool W, bool NT, int OP, int WPB>
@@ -387,54 +415,40 @@ constexpr auto sweep_kernel() {
     else return stress_grad_kernel<T, W, NT, OP, WPB>;
 }
 
-template <typename T, bool W>
-int launch_grad_t(bb_solver *s, int op, const void *x_in) {
-    const T *units = (const T *)s->d_units;
-    const T *X = (const T *)x_in;
+// One instantiation of the sweep.  Its dynamic-LDS ceiling (row-sum parking and the column
+// partials) is raised once: one bit of defer_attr_done per (WPB, NT, OP).
+template <bool NT, int OP, int WPB, typename T, bool W>
+int launch_sweep(LayoutTag<T, W>, bb_solver *s, const void *x_in) {
+    const auto kern = sweep_kernel<T, W, NT, OP, WPB>();
+    constexpr unsigned bit = 1u << ((WPB == 8 ? 4 : 0) + (NT ? 2 : 0) + (OP == kOpMatvec2 ? 1 : 0) +
+                                    (OP == kOpStressW1 ? 8 : 0) + (OP == kOpStressW2 ? 16 : 0));
+    if (s->defer_lds_bytes > 0 && !(s->defer_attr_done & bit)) {
+        BB_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)s->defer_lds_bytes));
+        s->defer_attr_done |= bit;
+    }
     // row partials are indexed by local unit; the buffer starts at the rank's first tile
     T *rowpart = (T *)s->d_part +
                  (s->u_begin - s->t_first * s->L.units_per_tile) * (3 * s->L.rows_per_unit);
     T *colpart = (T *)s->d_part + s->rowpart_elems;
-    const dim3 grid(s->n_waves / s->wpb), block(64 * s->wpb);
-    // The dynamic-LDS ceiling of a kernel (row-sum parking and the column partials) is raised
-    // once per instantiation: one bit per (WPB, NT, OP).
-#define BB_LAUNCH(NTV, OPV, WPBV)                                                               \
-    do {                                                                                        \
-        auto kern = sweep_kernel<T, W, NTV, OPV, WPBV>();                                       \
-        constexpr unsigned bit =                                                                \
-            1u << ((WPBV == 8 ? 4 : 0) + (NTV ? 2 : 0) + (OPV == kOpMatvec2 ? 1 : 0) +          \
-                   (OPV == kOpStressW1 ? 8 : 0) + (OPV == kOpStressW2 ? 16 : 0));               \
-        if (s->defer_lds_bytes > 0 && !(s->defer_attr_done & bit)) {                            \
-            BB_HIP_CHECK(hipFuncSetAttribute((const void *)kern,                                \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize,        \
-                                             (int)s->defer_lds_bytes));                         \
-            s->defer_attr_done |= bit;                                                          \
-        }                                                                                       \
-        BB_HIP_CHECK(bb::launch(kern, grid, block, (size_t)s->defer_lds_bytes, s->stream, units, \
-                                X, s->d_udesc, s->chunk_q, s->chunk_r, s->d_wave_slots, rowpart, \
-                                colpart, s->d_stresspart, s->defer_cap_units,                   \
-                                s->lds_wave_floats, s->dense_u0, s->d_stress_slot));            \
-    } while (0)
-    // 8 waves per workgroup only for the 512-wide layouts (fp32, fp64 wide)
-#define BB_LAUNCH_WPB(NTV, OPV)                                                                 \
-    do {                                                                                        \
-        if ((sizeof(T) == 4 || W) && s->wpb == 8)                                               \
-            BB_LAUNCH(NTV, OPV, ((sizeof(T) == 4 || W) ? 8 : 4));                               \
-        else                                                                                    \
-            BB_LAUNCH(NTV, OPV, 4);                                                             \
-    } while (0)
-    if (op == kOpMatvec2) {
-        if (s->nontemporal) BB_LAUNCH_WPB(true, kOpMatvec2); else BB_LAUNCH_WPB(false, kOpMatvec2);
-    } else if (op == kOpStressW1) {
-        if (s->nontemporal) BB_LAUNCH_WPB(true, kOpStressW1); else BB_LAUNCH_WPB(false, kOpStressW1);
-    } else if (op == kOpStressW2) {
-        if (s->nontemporal) BB_LAUNCH_WPB(true, kOpStressW2); else BB_LAUNCH_WPB(false, kOpStressW2);
-    } else {
-        if (s->nontemporal) BB_LAUNCH_WPB(true, kOpStress); else BB_LAUNCH_WPB(false, kOpStress);
-    }
-#undef BB_LAUNCH
-#undef BB_LAUNCH_WPB
+    BB_HIP_CHECK(bb::launch(kern, dim3(s->n_waves / s->wpb), dim3(64 * s->wpb), (size_t)s->defer_lds_bytes,
+                            s->stream, (const T *)s->d_units, (const T *)x_in, s->d_udesc, s->chunk_q,
+                            s->chunk_r, s->d_wave_slots, rowpart, colpart, s->d_stresspart,
+                            s->defer_cap_units, s->lds_wave_floats, s->dense_u0, s->d_stress_slot));
     return BB_OK;
+}
+
+// The sweep of OP with the solver's loads (nontemporal) and workgroup size (wpb): 8 waves per
+// workgroup only for the 512-wide layouts (fp32, fp64 wide).
+template <int OP, typename L>
+int launch_sweep_op(L lay, bb_solver *s, const void *x_in) {
+    constexpr int kPairWpb = sizeof(typename L::T) == 4 || L::W ? 8 : 4;
+    if (s->nontemporal) {
+        if (kPairWpb == 8 && s->wpb == 8) return launch_sweep<true, OP, kPairWpb>(lay, s, x_in);
+        return launch_sweep<true, OP, 4>(lay, s, x_in);
+    }
+    if (kPairWpb == 8 && s->wpb == 8) return launch_sweep<false, OP, kPairWpb>(lay, s, x_in);
+    return launch_sweep<false, OP, 4>(lay, s, x_in);
 }
 
 // What the reduce multiplies the summed partials by: 2 for the gradient (SPEC 2.3: the sweep
@@ -448,7 +462,7 @@ void fill_reduce_params(bb_solver *s, ReduceParams<T> &p, int mode, double lr, d
 
 // The peer exchange in one launch (reduce_exchange_kernel): the caller has bumped peer_seq.
 template <typename T, bool W>
-int launch_exchange_t(bb_solver *s, double lr, double *stress_out, double scale) {
+int launch_exchange_t(LayoutTag<T, W>, bb_solver *s, double lr, double *stress_out, double scale) {
     ReduceParams<T> p;
     fill_reduce_params<T>(s, p, kReducePeer, lr, stress_out, scale);
     const int64_t es = sizeof(T);
@@ -458,15 +472,13 @@ int launch_exchange_t(bb_solver *s, double lr, double *stress_out, double scale)
     const char *base = (const char *)s->peer_arena;
     const T *arena = (const T *)(base + (int64_t)(s->peer_seq & 1) * s->world * s->peer_slot_elems * es);
     const unsigned long long *my_poison = (const unsigned long long *)(base + peer_xpoison_offset(s));
-    if (s->red_slices == 4)
-        BB_HIP_CHECK(bb::launch(reduce_exchange_kernel<T, W, 4>, grid, dim3(128 * 4), 0, s->stream, p,
+    return with_int<4, 8>(s->red_slices, [&](auto slices) -> int {
+        constexpr int S = decltype(slices)::value;
+        BB_HIP_CHECK(bb::launch(reduce_exchange_kernel<T, W, S>, grid, dim3(128 * S), 0, s->stream, p,
                                 (const int64_t *)s->d_red_lists, s->red_stride, xt, arena, my_poison,
                                 s->peer_slot_elems, s->d_peer_state, s->peer_limit_ticks));
-    else
-        BB_HIP_CHECK(bb::launch(reduce_exchange_kernel<T, W, 8>, grid, dim3(128 * 8), 0, s->stream, p,
-                                (const int64_t *)s->d_red_lists, s->red_stride, xt, arena, my_poison,
-                                s->peer_slot_elems, s->d_peer_state, s->peer_limit_ticks));
-    return BB_OK;
+        return BB_OK;
+    });
 }
 
 template <typename T>
@@ -507,20 +519,19 @@ void fill_reduce_params(bb_solver *s, ReduceParams<T> &p, int mode, double lr, d
 }
 
 template <typename T, bool W>
-int launch_reduce_t(bb_solver *s, int mode, double lr, double *stress_out, double scale) {
+int launch_reduce_t(LayoutTag<T, W>, bb_solver *s, int mode, double lr, double *stress_out, double scale) {
     ReduceParams<T> p;
     fill_reduce_params<T>(s, p, mode, lr, stress_out, scale);
     const unsigned segs = 3 * Lay<T, W>::VW / kRedWG;   // workgroups per block of 3*vw elements
     // one launch: every list whole, 128 elements x 4 or 8 slices per workgroup
     const dim3 grid = mode == kReduceStressOnly ? dim3((unsigned)s->n_maps, 1)
                                                 : dim3((unsigned)s->L.n_blocks, segs);
-    if (s->red_slices == 4)
-        BB_HIP_CHECK(bb::launch(reduce_sliced_kernel<T, W, 4>, grid, dim3(128 * 4), 0, s->stream,
+    return with_int<4, 8>(s->red_slices, [&](auto slices) -> int {
+        constexpr int S = decltype(slices)::value;
+        BB_HIP_CHECK(bb::launch(reduce_sliced_kernel<T, W, S>, grid, dim3(128 * S), 0, s->stream,
                                 p, (const int64_t *)s->d_red_lists, s->red_stride));
-    else
-        BB_HIP_CHECK(bb::launch(reduce_sliced_kernel<T, W, 8>, grid, dim3(128 * 8), 0, s->stream,
-                                p, (const int64_t *)s->d_red_lists, s->red_stride));
-    return BB_OK;
+        return BB_OK;
+    });
 }
 
 int launch_grad(bb_solver *s, int op = kOpStress, const void *x_in = nullptr) {
@@ -528,22 +539,35 @@ int launch_grad(bb_solver *s, int op = kOpStress, const void *x_in = nullptr) {
     // the stress and its gradient: weighted (SPEC 2.3.1) once a weight power is set
     if (op == kOpStress && s->weight_power != 0)
         op = s->weight_power == 1 ? kOpStressW1 : kOpStressW2;
-    return BB_BY_LAYOUT(s, launch_grad_t, s, op, x_in);
+    return by_layout(s, [&](auto lay) {
+        return with_int<kOpMatvec2, kOpStressW1, kOpStressW2, kOpStress>(op, [&](auto opc) {
+            return launch_sweep_op<decltype(opc)::value>(lay, s, x_in);
+        });
+    });
 }
 int launch_reduce(bb_solver *s, int mode, double lr, double *stress_out,
                   double scale = kScaleGradient) {
-    return BB_BY_LAYOUT(s, launch_reduce_t, s, mode, lr, stress_out, scale);
+    return by_layout(s, [&](auto lay) { return launch_reduce_t(lay, s, mode, lr, stress_out, scale); });
 }
 int launch_exchange(bb_solver *s, double lr, double *stress_out, double scale = kScaleGradient) {
-    return BB_BY_LAYOUT(s, launch_exchange_t, s, lr, stress_out, scale);
+    return by_layout(s, [&](auto lay) { return launch_exchange_t(lay, s, lr, stress_out, scale); });
 }
 
-hipEvent_t *timing_slot(bb_solver *s) {
-    if (!s->timing) return nullptr;
-    if (s->timing_iter++ % s->timing_stride != 0 || s->ev_used + 3 > s->ev.size()) return nullptr;
-    hipEvent_t *e = &s->ev[s->ev_used];
-    s->ev_used += 3;
-    return e;
+// One iteration's two halves, sweep() and reduce(), with the timing events around them on
+// every timing_stride-th iteration while timing is on: ev[0] sweep ev[1] reduce ev[2].
+template <typename Sweep, typename Reduce>
+int timed_step(bb_solver *s, Sweep &&sweep, Reduce &&reduce) {
+    hipEvent_t *ev = nullptr;
+    if (s->timing && s->timing_iter++ % s->timing_stride == 0 && s->ev_used + 3 <= s->ev.size()) {
+        ev = &s->ev[s->ev_used];
+        s->ev_used += 3;
+    }
+    if (ev) BB_HIP_CHECK(hipEventRecord(ev[0], s->stream));
+    BB_TRY(sweep());
+    if (ev) BB_HIP_CHECK(hipEventRecord(ev[1], s->stream));
+    BB_TRY(reduce());
+    if (ev) BB_HIP_CHECK(hipEventRecord(ev[2], s->stream));
+    return BB_OK;
 }
 
 int check_ready(const bb_solver *s, const char *who) {
@@ -555,28 +579,37 @@ int check_ready(const bb_solver *s, const char *who) {
     return BB_OK;
 }
 
+// What every entry point that iterates checks before it enqueues anything: the solver is
+// ready, iters >= 0, and the stress history (n_maps values per iteration) has room for all of
+// the call -- (hist_n + iters) * n_maps <= hist_cap, in a form that cannot overflow.
+int check_iterate(const bb_solver *s, int64_t iters, const char *who) {
+    BB_TRY(check_ready(s, who));
+    BB_REQUIRE(iters >= 0, std::string(who) + ": iters < 0");
+    if (iters > s->hist_cap / s->n_maps - s->hist_n)
+        return bb::fail(BB_ERR_STATE, std::string(who) + ": stress history full");
+    return BB_OK;
+}
+
 // f64 <-> solver dtype conversions of n elements on the solver's stream.
 hipError_t widen(bb_solver *s, const void *in_T, double *out_f64, int64_t n) {
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    return s->dtype == BB_F32
-               ? bb::launch(T_to_f64_kernel<float>, grid, block, 0, s->stream, (const float *)in_T,
-                            out_f64, n)
-               : bb::launch(T_to_f64_kernel<double>, grid, block, 0, s->stream,
-                            (const double *)in_T, out_f64, n);
+    return by_dtype(s, [&](auto t) {
+        using T = typename decltype(t)::T;
+        return bb::launch(T_to_f64_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream,
+                          (const T *)in_T, out_f64, n);
+    });
 }
 hipError_t narrow(bb_solver *s, const double *in_f64, void *out_T, int64_t n) {
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    return s->dtype == BB_F32
-               ? bb::launch(f64_to_T_kernel<float>, grid, block, 0, s->stream, in_f64,
-                            (float *)out_T, n)
-               : bb::launch(f64_to_T_kernel<double>, grid, block, 0, s->stream, in_f64,
-                            (double *)out_T, n);
+    return by_dtype(s, [&](auto t) {
+        using T = typename decltype(t)::T;
+        return bb::launch(f64_to_T_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream,
+                          in_f64, (T *)out_T, n);
+    });
 }
 
 // host = the (n_sub, n_sub) matrix of the bins [off, off + n_sub) of the solver (the whole
 // map: off = 0, n_sub = n_bins); only units inside that block are touched
 template <typename T, bool W>
-int set_wish_dense_t(bb_solver *s, const double *host, int64_t ld, int kind, double alpha,
+int set_wish_dense_t(LayoutTag<T, W>, bb_solver *s, const double *host, int64_t ld, int kind, double alpha,
                      int64_t off, int64_t n_sub) {
     constexpr int VW = Lay<T, W>::VW;
     const int64_t upt = s->L.units_per_tile, n = off + n_sub;
@@ -643,16 +676,14 @@ int refresh_full(bb_solver *s) {
     if (!s->row_owner) return BB_OK;
     const int64_t es = bb::elem_size(s->dtype);
     BB_HIP_CHECK(hipMemsetAsync(s->d_full, 0, (size_t)(s->L.n_bins * s->full_ld * es), s->stream));
-    if (s->n_local > 0) {
-#define BB_FULL(TT, WW)                                                                         \
-    BB_HIP_CHECK(bb::launch(units_to_full_kernel<TT, WW>, dim3((unsigned)s->n_local), dim3(256), 0, \
-                            s->stream, (const TT *)s->d_units, s->d_udesc, (TT *)s->d_full,       \
-                            s->full_ld, s->L.n_bins))
-        if (s->dtype == BB_F32) BB_FULL(float, true);
-        else if (s->wide) BB_FULL(double, true);
-        else BB_FULL(double, false);
-#undef BB_FULL
-    }
+    if (s->n_local > 0)
+        BB_TRY(by_layout(s, [&](auto lay) -> int {
+            using T = typename decltype(lay)::T;
+            BB_HIP_CHECK(bb::launch(units_to_full_kernel<T, decltype(lay)::W>, dim3((unsigned)s->n_local),
+                                    dim3(256), 0, s->stream, (const T *)s->d_units, s->d_udesc,
+                                    (T *)s->d_full, s->full_ld, s->L.n_bins));
+            return BB_OK;
+        }));
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));
     return BB_OK;
 }
@@ -660,39 +691,116 @@ int refresh_full(bb_solver *s) {
 // One row-owner launch: iteration `hist_n` (reads d_X, writes d_X2, swaps them) and the
 // fold of the previous launch's stress into hist[hist_n - 1] when `fold_prev`.
 // update = false: fold only (after the last iteration of a call).
-template <typename T>
-int launch_row_owner_t(bb_solver *s, double lr, bool fold_prev, bool update) {
+int launch_row_owner(bb_solver *s, double lr, bool fold_prev, bool update) {
     const int par = (int)(s->ro_launches & 1);
     const double *prev = s->d_ro_part + (int64_t)(par ^ 1) * s->ro_blocks;
     double *out = s->d_ro_part + (int64_t)par * s->ro_blocks;
     double *hist_prev = fold_prev ? s->d_stress_hist + (s->hist_n - 1) : nullptr;
     // fold only: a grid of one workgroup, which is then the "last" = the fold workgroup
     const unsigned grid = update ? (unsigned)s->ro_blocks + 1u : 1u;
-#define BB_ROW(WPRV, QV)                                                                         \
-    BB_HIP_CHECK(bb::launch(row_owner_kernel<T, WPRV, QV>, dim3(grid), dim3(256), 0, s->stream,          \
-                            (const T *)s->d_full, s->full_ld, (int)s->L.n_bins, (const T *)s->d_X,  \
-                            (T *)s->d_X2, (T *)s->d_V, (T)lr, (T)s->momentum, prev, s->ro_blocks,   \
-                            hist_prev, out, (const T *)s->d_bin_scale))
-#define BB_ROW_Q(WPRV)                                                                           \
-    do {                                                                                         \
-        if (s->weight_power == 1) BB_ROW(WPRV, 1);                                               \
-        else if (s->weight_power == 2) BB_ROW(WPRV, 2);                                          \
-        else BB_ROW(WPRV, 0);                                                                    \
-    } while (0)
-    if (s->ro_wpr == 4) BB_ROW_Q(4);
-    else if (s->ro_wpr == 2) BB_ROW_Q(2);
-    else BB_ROW_Q(1);
-#undef BB_ROW_Q
-#undef BB_ROW
+    // waves per row 4, 2 or 1; weight power q = 1, 2 or 0
+    BB_TRY(by_dtype(s, [&](auto t) {
+        using T = typename decltype(t)::T;
+        return with_int<4, 2, 1>(s->ro_wpr, [&](auto wpr) {
+            return with_int<1, 2, 0>(s->weight_power, [&](auto q) -> int {
+                BB_HIP_CHECK(bb::launch(row_owner_kernel<T, decltype(wpr)::value, decltype(q)::value>,
+                                        dim3(grid), dim3(256), 0, s->stream, (const T *)s->d_full,
+                                        s->full_ld, (int)s->L.n_bins, (const T *)s->d_X, (T *)s->d_X2,
+                                        (T *)s->d_V, (T)lr, (T)s->momentum, prev, s->ro_blocks, hist_prev,
+                                        out, (const T *)s->d_bin_scale));
+                return BB_OK;
+            });
+        });
+    }));
     if (update) {
         std::swap(s->d_X, s->d_X2);
         s->ro_launches++;
     }
     return BB_OK;
 }
-int launch_row_owner(bb_solver *s, double lr, bool fold_prev, bool update) {
-    return s->dtype == BB_F32 ? launch_row_owner_t<float>(s, lr, fold_prev, update)
-                              : launch_row_owner_t<double>(s, lr, fold_prev, update);
+
+// Every set_wish_*, once the units are packed on the solver's stream: rebuild the row-owner
+// path's full matrix from them and mark the wish distances set.
+int inputs_done(bb_solver *s) {
+    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
+    BB_TRY(refresh_full(s));
+    s->have_wish = true;
+    return BB_OK;
+}
+
+// The units from a ContactMap's device matrix m (d x d), whose bin 0 is the solver's bin off
+// (the whole map: off = 0, d = n_bins).
+int pack_from_cm(bb_solver *s, const double *m, int64_t d, int64_t off, int kind, double alpha) {
+    BB_TRY(bb::enter_device(s->device));
+    if (s->n_local > 0)
+        BB_TRY(by_layout(s, [&](auto lay) -> int {
+            using T = typename decltype(lay)::T;
+            BB_HIP_CHECK(bb::launch(pack_units_from_matrix_kernel<T, decltype(lay)::W>,
+                                    dim3((unsigned)s->n_local), dim3(256), 0, s->stream, m, d,
+                                    (T *)s->d_units, s->d_udesc, off + d, kind, -1.0 / alpha, off));
+            return BB_OK;
+        }));
+    return inputs_done(s);
+}
+
+// host = the dense (n_sub, n_sub) block of the bins [off, off + n_sub), row stride ld
+int set_wish_dense(bb_solver *s, const double *host, int64_t ld, int kind, double alpha, int64_t off,
+                   int64_t n_sub) {
+    BB_TRY(bb::enter_device(s->device));
+    BB_TRY(by_layout(s, [&](auto lay) { return set_wish_dense_t(lay, s, host, ld, kind, alpha, off, n_sub); }));
+    return inputs_done(s);
+}
+
+// n entries (row, column, value) into the units (scatter_entries_kernel), chunk entries at a
+// time: stage(k0, m, &src) enqueues what entries [k0, k0 + m) need on the solver's stream and
+// describes them in src.  Every chunk runs in three phases -- clear / find the last entry per
+// cell / store it -- on top of the earlier ones, so "the last entry wins" holds across chunks.
+// Errors carry the caller's name, who; the caller has entered the solver's device.
+template <typename Stage>
+int scatter_entries(bb_solver *s, const char *who, int64_t n, int64_t chunk, int kind, double alpha,
+                    const double *KRnorm, const double *KRexpected, Stage &&stage) {
+    const auto hip = [&](hipError_t e) {
+        return e == hipSuccess ? (int)BB_OK : bb::fail(BB_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    };
+    const int64_t nb = s->L.n_blocks;
+    std::vector<int32_t> tilemap((size_t)(nb * nb), -1);
+    for (size_t t = 0; t < s->tile_I.size(); ++t)
+        tilemap[(size_t)s->tile_I[t] * nb + s->tile_J[t]] = (int32_t)t;
+    bb::DevBuf bmap, bbad, bkr, bke;
+    if (bmap.alloc(tilemap.size() * 4) != hipSuccess || bbad.alloc(sizeof(int)) != hipSuccess ||
+        (KRnorm && (bkr.alloc((size_t)s->L.n_bins * 8) != hipSuccess ||
+                    bke.alloc((size_t)s->L.n_bins * 8) != hipSuccess)))
+        return bb::fail(BB_ERR_NOMEM, std::string(who) + ": out of device memory");
+    hipStream_t st = s->stream;
+    BB_TRY(hip(hipMemcpyAsync(bmap.p, tilemap.data(), tilemap.size() * 4, hipMemcpyHostToDevice, st)));
+    if (KRnorm) {
+        BB_TRY(hip(hipMemcpyAsync(bkr.p, KRnorm, (size_t)s->L.n_bins * 8, hipMemcpyHostToDevice, st)));
+        BB_TRY(hip(hipMemcpyAsync(bke.p, KRexpected, (size_t)s->L.n_bins * 8, hipMemcpyHostToDevice, st)));
+    }
+    BB_TRY(hip(hipMemsetAsync(bbad.p, 0, sizeof(int), st)));
+    BB_TRY(hip(hipMemsetAsync(s->d_units, 0, (size_t)std::max<int64_t>(s->n_local, 1) * bb::kUnitBytes, st)));
+    for (int64_t k0 = 0; k0 < n; k0 += chunk) {
+        const int64_t m = std::min(chunk, n - k0);
+        EntrySrc src;
+        BB_TRY(hip(stage(k0, m, &src)));
+        for (int ph = 0; ph < 3; ++ph)
+            BB_TRY(hip(by_layout(s, [&](auto lay) {
+                using T = typename decltype(lay)::T;
+                return bb::launch(scatter_entries_kernel<T, decltype(lay)::W>, dim3((unsigned)((m + 255) / 256)),
+                                  dim3(256), 0, st, src, m, (const int32_t *)bmap.p, nb, s->L.n_bins,
+                                  s->u_begin, s->u_end, (T *)s->d_units, kind, -1.0 / alpha,
+                                  (const double *)bkr.p, (const double *)bke.p, (int *)bbad.p, ph);
+            })));
+    }
+    BB_TRY(hip(hipStreamSynchronize(st)));
+    int bad = 0;
+    BB_TRY(hip(hipMemcpy(&bad, bbad.p, sizeof(int), hipMemcpyDeviceToHost)));
+    if (bad == 1)
+        return bb::fail(BB_ERR_INVALID, std::string(who) + ": an index is outside [0, n_bins)");
+    if (bad == 2)
+        return bb::fail(BB_ERR_INVALID, std::string(who) + ": an entry falls in a tile that is not in "
+                                                           "the solver's tile list");
+    return inputs_done(s);
 }
 
 }  // namespace
@@ -751,7 +859,7 @@ int contributor_mask(const bb_solver *s, std::vector<unsigned> *mask) {
 }
 
 template <typename T>
-int build_peer_tables(bb_solver *s) {
+int build_peer_tables(TypeTag<T>, bb_solver *s) {
     PeerTable<T> tab[2];
     memset(tab, 0, sizeof(tab));
     const int64_t foff = peer_flags_offset(s);
@@ -913,11 +1021,7 @@ int bb_solver_set_wish_dense(bb_solver *s, const double *host, int64_t ld, int k
     BB_REQUIRE(kind == BB_KIND_WISH || kind == BB_KIND_COUNTS,
                "bb_solver_set_wish_dense: bad kind");
     BB_REQUIRE(kind == BB_KIND_WISH || alpha > 0.0, "bb_solver_set_wish_dense: alpha must be > 0");
-    BB_TRY(bb::enter_device(s->device));
-    int rc = BB_BY_LAYOUT(s, set_wish_dense_t, s, host, ld, kind, alpha, (int64_t)0, s->L.n_bins);
-    if (rc == BB_OK) rc = refresh_full(s);
-    if (rc == BB_OK) s->have_wish = true;
-    return rc;
+    return set_wish_dense(s, host, ld, kind, alpha, 0, s->L.n_bins);
 }
 
 int bb_solver_set_maps(bb_solver *s, int n_maps, const int64_t *bin_begin, const double *lr_scale) {
@@ -1026,17 +1130,15 @@ int bb_solver_degrees(bb_solver *s, int64_t *degree, int64_t n_bins) {
     // while this call runs -- every user of it synchronises before it returns)
     int *d_deg = (int *)s->d_f64_tmp;
     BB_HIP_CHECK(hipMemsetAsync(d_deg, 0, (size_t)s->L.n_pad * sizeof(int), s->stream));
-    if (s->n_local > 0) {
-#define BB_DEG(TT, WW)                                                                            \
-    BB_HIP_CHECK(bb::launch(unit_degrees_kernel<TT, WW>,                                           \
-                            dim3((unsigned)((s->n_local + kDegUnits - 1) / kDegUnits)), dim3(256), 0, \
-                            s->stream, (const TT *)s->d_units, s->d_udesc, s->n_local, s->L.n_bins,  \
-                            d_deg))
-        if (s->dtype == BB_F32) BB_DEG(float, true);
-        else if (s->wide) BB_DEG(double, true);
-        else BB_DEG(double, false);
-#undef BB_DEG
-    }
+    if (s->n_local > 0)
+        BB_TRY(by_layout(s, [&](auto lay) -> int {
+            using T = typename decltype(lay)::T;
+            BB_HIP_CHECK(bb::launch(unit_degrees_kernel<T, decltype(lay)::W>,
+                                    dim3((unsigned)((s->n_local + kDegUnits - 1) / kDegUnits)), dim3(256),
+                                    0, s->stream, (const T *)s->d_units, s->d_udesc, s->n_local,
+                                    s->L.n_bins, d_deg));
+            return BB_OK;
+        }));
     std::vector<int> host((size_t)n_bins);
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));
     BB_HIP_CHECK(hipMemcpy(host.data(), d_deg, (size_t)n_bins * sizeof(int), hipMemcpyDeviceToHost));
@@ -1067,18 +1169,15 @@ int bb_solver_weight_sums(bb_solver *s, double *sums, int64_t n_bins) {
     // (the staging buffer of set_coords / get_coords: 3 n_pad doubles >= n_bins; see degrees)
     double *d_sum = s->d_f64_tmp;
     const dim3 grid((unsigned)((n_bins + 3) / 4));
-#define BB_WS(TT, WW, QV)                                                                          \
-    BB_HIP_CHECK(bb::launch(unit_weight_sums_kernel<TT, WW, QV>, grid, dim3(256), 0, s->stream,      \
-                            (const TT *)s->d_units, s->d_udesc, s->n_local, s->L.n_bins, d_sum))
-#define BB_WS_Q(TT, WW)                                                                            \
-    do {                                                                                           \
-        if (s->weight_power == 1) BB_WS(TT, WW, 1); else BB_WS(TT, WW, 2);                         \
-    } while (0)
-    if (s->dtype == BB_F32) BB_WS_Q(float, true);
-    else if (s->wide) BB_WS_Q(double, true);
-    else BB_WS_Q(double, false);
-#undef BB_WS_Q
-#undef BB_WS
+    BB_TRY(by_layout(s, [&](auto lay) {
+        using T = typename decltype(lay)::T;
+        return with_int<1, 2>(s->weight_power, [&](auto q) -> int {
+            BB_HIP_CHECK(bb::launch(unit_weight_sums_kernel<T, decltype(lay)::W, decltype(q)::value>, grid,
+                                    dim3(256), 0, s->stream, (const T *)s->d_units, s->d_udesc, s->n_local,
+                                    s->L.n_bins, d_sum));
+            return BB_OK;
+        });
+    }));
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));
     BB_HIP_CHECK(hipMemcpy(sums, d_sum, (size_t)n_bins * sizeof(double), hipMemcpyDeviceToHost));
     return BB_OK;
@@ -1098,21 +1197,7 @@ int bb_solver_set_wish_from_cm_block(bb_solver *s, const bb_cm *cm, int64_t bin_
                "bb_solver_set_wish_from_cm_block: the map does not fit the solver at that offset");
     BB_REQUIRE(dev == s->device,
                "bb_solver_set_wish_from_cm_block: the map lives on another device than the solver");
-    BB_TRY(bb::enter_device(s->device));
-    if (s->n_local > 0) {
-#define BB_PACKB(TT, WW)                                                                         \
-    BB_HIP_CHECK(bb::launch(pack_units_from_matrix_kernel<TT, WW>, dim3((unsigned)s->n_local),       \
-                            dim3(256), 0, s->stream, m, d, (TT *)s->d_units, s->d_udesc,          \
-                            bin_offset + d, kind, -1.0 / alpha, bin_offset))
-        if (s->dtype == BB_F32) BB_PACKB(float, true);
-        else if (s->wide) BB_PACKB(double, true);
-        else BB_PACKB(double, false);
-#undef BB_PACKB
-    }
-    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-    BB_TRY(refresh_full(s));       // (a small one-map solver iterates over the full matrix)
-    s->have_wish = true;
-    return BB_OK;
+    return pack_from_cm(s, m, d, bin_offset, kind, alpha);
 }
 
 int bb_solver_set_wish_dense_block(bb_solver *s, const double *host, int64_t ld, int64_t n_sub,
@@ -1125,15 +1210,9 @@ int bb_solver_set_wish_dense_block(bb_solver *s, const double *host, int64_t ld,
     BB_REQUIRE(kind == BB_KIND_WISH || kind == BB_KIND_COUNTS,
                "bb_solver_set_wish_dense_block: bad kind");
     BB_REQUIRE(kind == BB_KIND_WISH || alpha > 0.0, "bb_solver_set_wish_dense_block: alpha must be > 0");
-    BB_TRY(bb::enter_device(s->device));
-    int rc = BB_BY_LAYOUT(s, set_wish_dense_t, s, host, ld, kind, alpha, bin_offset, n_sub);
-    if (rc == BB_OK) rc = refresh_full(s);
-    if (rc == BB_OK) s->have_wish = true;
-    return rc;
+    return set_wish_dense(s, host, ld, kind, alpha, bin_offset, n_sub);
 }
 
-int bb_solver_set_wish_from_cm_block(bb_solver *s, const bb_cm *cm, int64_t bin_offset, int kind,
-                                     double alpha);
 int bb_solver_set_wish_from_cm(bb_solver *s, const bb_cm *cm, int kind, double alpha) {
     BB_REQUIRE(s != nullptr && cm != nullptr, "bb_solver_set_wish_from_cm: NULL argument");
     if (s->n_maps > 1)
@@ -1167,21 +1246,7 @@ int bb_solver_set_wish_from_cm(bb_solver *s, const bb_cm *cm, int kind, double a
                                             hipGetErrorString(e));
         (void)hipGetLastError();
     }
-    BB_TRY(bb::enter_device(s->device));
-    if (s->n_local > 0) {
-#define BB_PACK(TT, WW)                                                                          \
-    BB_HIP_CHECK(bb::launch(pack_units_from_matrix_kernel<TT, WW>, dim3((unsigned)s->n_local),       \
-                            dim3(256), 0, s->stream, m, d, (TT *)s->d_units, s->d_udesc,          \
-                            s->L.n_bins, kind, -1.0 / alpha, (int64_t)0))
-        if (s->dtype == BB_F32) BB_PACK(float, true);
-        else if (s->wide) BB_PACK(double, true);
-        else BB_PACK(double, false);
-#undef BB_PACK
-    }
-    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-    BB_TRY(refresh_full(s));
-    s->have_wish = true;
-    return BB_OK;
+    return pack_from_cm(s, m, d, 0, kind, alpha);
 }
 
 int bb_solver_set_wish_sparse(bb_solver *s, const int64_t *rows, const int64_t *cols,
@@ -1195,83 +1260,23 @@ int bb_solver_set_wish_sparse(bb_solver *s, const int64_t *rows, const int64_t *
     BB_REQUIRE((KRnorm == nullptr) == (KRexpected == nullptr),
                "bb_solver_set_wish_sparse: KRnorm and KRexpected go together");
     BB_TRY(bb::enter_device(s->device));
-    const int64_t nb = s->L.n_blocks;
-    std::vector<int32_t> tilemap((size_t)(nb * nb), -1);
-    for (size_t t = 0; t < s->tile_I.size(); ++t)
-        tilemap[(size_t)s->tile_I[t] * nb + s->tile_J[t]] = (int32_t)t;
-    int32_t *d_map = nullptr;
-    int *d_bad = nullptr;
-    int64_t *d_rows = nullptr, *d_cols = nullptr;
-    double *d_vals = nullptr, *d_kr = nullptr, *d_ke = nullptr;
-    constexpr int64_t kChunk = 1 << 22;  // entries staged per copy
-    const int64_t cap = std::max<int64_t>(1, std::min(nnz, kChunk));
-    int rc = dev_alloc(&d_map, nb * nb);
-    if (rc == BB_OK) rc = dev_alloc(&d_bad, 1);
-    if (rc == BB_OK) rc = dev_alloc(&d_rows, cap);
-    if (rc == BB_OK) rc = dev_alloc(&d_cols, cap);
-    if (rc == BB_OK) rc = dev_alloc(&d_vals, cap);
-    if (rc == BB_OK && KRnorm) rc = dev_alloc(&d_kr, s->L.n_bins);
-    if (rc == BB_OK && KRnorm) rc = dev_alloc(&d_ke, s->L.n_bins);
-    hipError_t e = hipSuccess;
-    int host_bad = 0;
-    if (rc == BB_OK) {
-        e = hipMemcpyAsync(d_map, tilemap.data(), tilemap.size() * sizeof(int32_t),
-                           hipMemcpyHostToDevice, s->stream);
-        if (e == hipSuccess && KRnorm)
-            e = hipMemcpyAsync(d_kr, KRnorm, (size_t)s->L.n_bins * 8, hipMemcpyHostToDevice, s->stream);
-        if (e == hipSuccess && KRnorm)
-            e = hipMemcpyAsync(d_ke, KRexpected, (size_t)s->L.n_bins * 8, hipMemcpyHostToDevice,
-                               s->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, sizeof(int), s->stream);
+    // host entries staged through device buffers of kChunk entries; the next chunk reuses them
+    // in stream order
+    constexpr int64_t kChunk = 1 << 22;
+    const size_t cap = (size_t)std::max<int64_t>(1, std::min(nnz, kChunk)) * 8;
+    bb::DevBuf brows, bcols, bvals;
+    if (brows.alloc(cap) != hipSuccess || bcols.alloc(cap) != hipSuccess || bvals.alloc(cap) != hipSuccess)
+        return bb::fail(BB_ERR_NOMEM, "bb_solver_set_wish_sparse: out of device memory");
+    return scatter_entries(s, "bb_solver_set_wish_sparse", nnz, kChunk, kind, alpha, KRnorm, KRexpected,
+                           [&](int64_t k0, int64_t m, EntrySrc *src) {
+        *src = {(const int64_t *)brows.p, (const int64_t *)bcols.p, (const double *)bvals.p, nullptr, 0, 0, 1.0};
+        hipError_t e = hipMemcpyAsync(brows.p, rows + k0, (size_t)m * 8, hipMemcpyHostToDevice, s->stream);
         if (e == hipSuccess)
-            e = hipMemsetAsync(s->d_units, 0, (size_t)std::max<int64_t>(s->n_local, 1) * bb::kUnitBytes,
-                               s->stream);
-        for (int64_t k0 = 0; k0 < nnz && e == hipSuccess; k0 += kChunk) {
-            const int64_t m = std::min(kChunk, nnz - k0);
-            e = hipMemcpyAsync(d_rows, rows + k0, (size_t)m * 8, hipMemcpyHostToDevice, s->stream);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(d_cols, cols + k0, (size_t)m * 8, hipMemcpyHostToDevice, s->stream);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(d_vals, vals + k0, (size_t)m * 8, hipMemcpyHostToDevice, s->stream);
-            if (e != hipSuccess) break;
-            const unsigned grid = (unsigned)((m + 255) / 256);
-            const EntrySrc src = {d_rows, d_cols, d_vals, nullptr, 0, 0, 1.0};
-#define BB_SCATTER(TT, WW, PH)                                                                  \
-    bb::launch(scatter_entries_kernel<TT, WW>, dim3(grid), dim3(256), 0, s->stream, src, m, d_map, \
-               nb, s->L.n_bins, s->u_begin, s->u_end, (TT *)s->d_units, kind, -1.0 / alpha, d_kr,  \
-               d_ke, d_bad, PH)
-            // clear / find the last entry per cell / store it (later chunks simply
-            // repeat this on top of earlier ones, so "last wins" holds across chunks)
-            for (int ph = 0; ph < 3 && e == hipSuccess; ++ph) {
-                if (s->dtype == BB_F32) e = BB_SCATTER(float, true, ph);
-                else if (s->wide) e = BB_SCATTER(double, true, ph);
-                else e = BB_SCATTER(double, false, ph);
-            }
-#undef BB_SCATTER
-            // the staging buffers are reused by the next chunk: stream order makes that safe
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-        if (e == hipSuccess) e = hipMemcpy(&host_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost);
-    }
-    hipFree(d_map);
-    hipFree(d_bad);
-    hipFree(d_rows);
-    hipFree(d_cols);
-    hipFree(d_vals);
-    hipFree(d_kr);
-    hipFree(d_ke);
-    if (rc != BB_OK) return rc;
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_HIP, std::string("bb_solver_set_wish_sparse: ") + hipGetErrorString(e));
-    if (host_bad == 1)
-        return bb::fail(BB_ERR_INVALID, "bb_solver_set_wish_sparse: an index is outside [0, n_bins)");
-    if (host_bad == 2)
-        return bb::fail(BB_ERR_INVALID,
-                        "bb_solver_set_wish_sparse: an entry falls in a tile that is not in the "
-                        "solver's tile list");
-    BB_TRY(refresh_full(s));
-    s->have_wish = true;
-    return BB_OK;
+            e = hipMemcpyAsync(bcols.p, cols + k0, (size_t)m * 8, hipMemcpyHostToDevice, s->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(bvals.p, vals + k0, (size_t)m * 8, hipMemcpyHostToDevice, s->stream);
+        return e;
+    });
 }
 
 // ---- Rao-format triples resident on the device (fit_triples without host binning) --------
@@ -1358,54 +1363,14 @@ int bb_solver_set_wish_triples(bb_solver *s, const bb_triples *t, int kind, doub
     BB_REQUIRE(t->device == s->device,
                "bb_solver_set_wish_triples: the triples live on another device than the solver");
     BB_TRY(bb::enter_device(s->device));
-    const int64_t nb = s->L.n_blocks;
-    std::vector<int32_t> tilemap((size_t)(nb * nb), -1);
-    for (size_t q = 0; q < s->tile_I.size(); ++q)
-        tilemap[(size_t)s->tile_I[q] * nb + s->tile_J[q]] = (int32_t)q;
-    bb::DevBuf bmap, bbad, bkr, bke;
-    if (bmap.alloc((size_t)(nb * nb) * 4) != hipSuccess || bbad.alloc(sizeof(int)) != hipSuccess ||
-        (KRnorm && (bkr.alloc((size_t)s->L.n_bins * 8) != hipSuccess ||
-                    bke.alloc((size_t)s->L.n_bins * 8) != hipSuccess)))
-        return bb::fail(BB_ERR_NOMEM, "bb_solver_set_wish_triples: out of device memory");
-    hipStream_t st = s->stream;
-    BB_HIP_CHECK(hipMemcpyAsync(bmap.p, tilemap.data(), tilemap.size() * 4, hipMemcpyHostToDevice, st));
-    if (KRnorm) {
-        BB_HIP_CHECK(hipMemcpyAsync(bkr.p, KRnorm, (size_t)s->L.n_bins * 8, hipMemcpyHostToDevice, st));
-        BB_HIP_CHECK(hipMemcpyAsync(bke.p, KRexpected, (size_t)s->L.n_bins * 8, hipMemcpyHostToDevice, st));
-    }
-    BB_HIP_CHECK(hipMemsetAsync(bbad.p, 0, sizeof(int), st));
-    BB_HIP_CHECK(hipMemsetAsync(s->d_units, 0, (size_t)std::max<int64_t>(s->n_local, 1) * bb::kUnitBytes, st));
-    // chunks of 2^30 entries: an fp32 cell holds the index of the entry that wins it in 32 bits;
-    // later chunks run on top of earlier ones, so "the last entry wins" holds across them
+    // slices of 2^30 entries of the device copy: an fp32 cell holds the index of the entry that
+    // wins it in 32 bits
     constexpr int64_t kChunk = (int64_t)1 << 30;
-    for (int64_t k0 = 0; k0 < t->n; k0 += kChunk) {
-        const int64_t m = std::min(kChunk, t->n - k0);
-        const EntrySrc src = {nullptr, nullptr, nullptr, t->d + k0 * (t->st == 3 ? 3 : 1), t->st, t->sc,
-                              t->resolution};
-        const unsigned grid = (unsigned)((m + 255) / 256);
-        for (int ph = 0; ph < 3; ++ph) {
-#define BB_SCATTER_T(TT, WW)                                                                       \
-    BB_HIP_CHECK(bb::launch(scatter_entries_kernel<TT, WW>, dim3(grid), dim3(256), 0, st, src, m,   \
-                            (const int32_t *)bmap.p, nb, s->L.n_bins, s->u_begin, s->u_end,        \
-                            (TT *)s->d_units, kind, -1.0 / alpha, (const double *)bkr.p,            \
-                            (const double *)bke.p, (int *)bbad.p, ph))
-            if (s->dtype == BB_F32) BB_SCATTER_T(float, true);
-            else if (s->wide) BB_SCATTER_T(double, true);
-            else BB_SCATTER_T(double, false);
-#undef BB_SCATTER_T
-        }
-    }
-    BB_HIP_CHECK(hipStreamSynchronize(st));
-    int bad = 0;
-    BB_HIP_CHECK(hipMemcpy(&bad, bbad.p, sizeof(int), hipMemcpyDeviceToHost));
-    if (bad == 1)
-        return bb::fail(BB_ERR_INVALID, "bb_solver_set_wish_triples: an index is outside [0, n_bins)");
-    if (bad == 2)
-        return bb::fail(BB_ERR_INVALID, "bb_solver_set_wish_triples: an entry falls in a tile that is "
-                                        "not in the solver's tile list");
-    BB_TRY(refresh_full(s));
-    s->have_wish = true;
-    return BB_OK;
+    return scatter_entries(s, "bb_solver_set_wish_triples", t->n, kChunk, kind, alpha, KRnorm, KRexpected,
+                           [&](int64_t k0, int64_t, EntrySrc *src) {
+        *src = {nullptr, nullptr, nullptr, t->d + k0 * (t->st == 3 ? 3 : 1), t->st, t->sc, t->resolution};
+        return hipSuccess;
+    });
 }
 
 int bb_solver_set_wish_from_coords(bb_solver *s, const double *xstar) {
@@ -1414,19 +1379,15 @@ int bb_solver_set_wish_from_coords(bb_solver *s, const double *xstar) {
     BB_HIP_CHECK(hipMemsetAsync(s->d_f64_tmp, 0, (size_t)s->L.n_pad * 3 * sizeof(double), s->stream));
     BB_HIP_CHECK(hipMemcpyAsync(s->d_f64_tmp, xstar, (size_t)s->L.n_bins * 3 * sizeof(double),
                                 hipMemcpyHostToDevice, s->stream));
-    if (s->n_local > 0) {
-#define BB_GEN(TT, WW)                                                                         \
-    BB_HIP_CHECK(bb::launch(gen_units_kernel<TT, WW>, dim3((unsigned)s->n_local), dim3(256), 0,    \
-                            s->stream, s->d_f64_tmp, (TT *)s->d_units, s->d_udesc, s->L.n_bins))
-        if (s->dtype == BB_F32) BB_GEN(float, true);
-        else if (s->wide) BB_GEN(double, true);
-        else BB_GEN(double, false);
-#undef BB_GEN
-    }
-    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-    BB_TRY(refresh_full(s));
-    s->have_wish = true;
-    return BB_OK;
+    if (s->n_local > 0)
+        BB_TRY(by_layout(s, [&](auto lay) -> int {
+            using T = typename decltype(lay)::T;
+            BB_HIP_CHECK(bb::launch(gen_units_kernel<T, decltype(lay)::W>, dim3((unsigned)s->n_local),
+                                    dim3(256), 0, s->stream, s->d_f64_tmp, (T *)s->d_units, s->d_udesc,
+                                    s->L.n_bins));
+            return BB_OK;
+        }));
+    return inputs_done(s);
 }
 
 int bb_solver_set_coords(bb_solver *s, const double *xyz) {
@@ -1465,35 +1426,26 @@ int bb_solver_set_momentum(bb_solver *s, double mu) {
 }
 
 int bb_solver_iterate(bb_solver *s, int64_t iters, double lr) {
-    BB_TRY(check_ready(s, "bb_solver_iterate"));
-    BB_REQUIRE(iters >= 0, "bb_solver_iterate: iters < 0");
+    BB_TRY(check_iterate(s, iters, "bb_solver_iterate"));
     if (s->world != 1)
         return bb::fail(BB_ERR_STATE,
                         "bb_solver_iterate: world > 1 needs bb_solver_grad / all-reduce / "
                         "bb_solver_apply");
-    if ((s->hist_n + iters) * s->n_maps > s->hist_cap)
-        return bb::fail(BB_ERR_STATE, "bb_solver_iterate: stress history full");
     BB_TRY(bb::enter_device(s->device));
     if (s->row_owner) {
         // one launch per iteration; launch k also folds the stress of launch k-1
         for (int64_t k = 0; k < iters; ++k) {
-            hipEvent_t *ev = timing_slot(s);
-            if (ev) BB_HIP_CHECK(hipEventRecord(ev[0], s->stream));
-            BB_TRY(launch_row_owner(s, lr, k > 0, true));
-            if (ev) BB_HIP_CHECK(hipEventRecord(ev[1], s->stream));
-            if (ev) BB_HIP_CHECK(hipEventRecord(ev[2], s->stream));
+            BB_TRY(timed_step(s, [&] { return launch_row_owner(s, lr, k > 0, true); },
+                              [] { return (int)BB_OK; }));
             s->hist_n++;
         }
         if (iters > 0) BB_TRY(launch_row_owner(s, lr, true, false));
         return BB_OK;
     }
     for (int64_t k = 0; k < iters; ++k) {
-        hipEvent_t *ev = timing_slot(s);
-        if (ev) BB_HIP_CHECK(hipEventRecord(ev[0], s->stream));
-        BB_TRY(launch_grad(s));
-        if (ev) BB_HIP_CHECK(hipEventRecord(ev[1], s->stream));
-        BB_TRY(launch_reduce(s, kReduceApply, lr, s->d_stress_hist + s->hist_n * s->n_maps));
-        if (ev) BB_HIP_CHECK(hipEventRecord(ev[2], s->stream));
+        BB_TRY(timed_step(s, [&] { return launch_grad(s); }, [&] {
+            return launch_reduce(s, kReduceApply, lr, s->d_stress_hist + s->hist_n * s->n_maps);
+        }));
         s->hist_n++;
     }
     return BB_OK;
@@ -1505,12 +1457,8 @@ int bb_solver_grad(bb_solver *s) {
         return bb::fail(BB_ERR_STATE, "bb_solver_grad: a solver of several maps (bb_solver_set_maps) "
                                       "iterates with bb_solver_iterate only");
     BB_TRY(bb::enter_device(s->device));
-    hipEvent_t *ev = timing_slot(s);
-    if (ev) BB_HIP_CHECK(hipEventRecord(ev[0], s->stream));
-    BB_TRY(launch_grad(s));
-    if (ev) BB_HIP_CHECK(hipEventRecord(ev[1], s->stream));
-    BB_TRY(launch_reduce(s, kReduceExchange, 0.0, nullptr));
-    if (ev) BB_HIP_CHECK(hipEventRecord(ev[2], s->stream));
+    BB_TRY(timed_step(s, [&] { return launch_grad(s); },
+                      [&] { return launch_reduce(s, kReduceExchange, 0.0, nullptr); }));
     s->grad_pending = true;
     return BB_OK;
 }
@@ -1523,15 +1471,13 @@ int bb_solver_apply(bb_solver *s, double lr) {
         return bb::fail(BB_ERR_STATE, "bb_solver_apply: stress history full");
     BB_TRY(bb::enter_device(s->device));
     const int64_t n3 = s->L.n_pad * 3;
-    const unsigned grid = (unsigned)((n3 + 255) / 256);
-    if (s->dtype == BB_F32)
-        BB_HIP_CHECK(bb::launch(apply_kernel<float>, dim3(grid), dim3(256), 0, s->stream,
-                                (float *)s->d_X, (float *)s->d_V, (const float *)s->d_exch, n3,
-                                (float)lr, (float)s->momentum, s->d_stress_hist + s->hist_n));
-    else
-        BB_HIP_CHECK(bb::launch(apply_kernel<double>, dim3(grid), dim3(256), 0, s->stream,
-                                (double *)s->d_X, (double *)s->d_V, (const double *)s->d_exch, n3,
-                                lr, s->momentum, s->d_stress_hist + s->hist_n));
+    BB_TRY(by_dtype(s, [&](auto t) -> int {
+        using T = typename decltype(t)::T;
+        BB_HIP_CHECK(bb::launch(apply_kernel<T>, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, s->stream,
+                                (T *)s->d_X, (T *)s->d_V, (const T *)s->d_exch, n3, (T)lr, (T)s->momentum,
+                                s->d_stress_hist + s->hist_n));
+        return BB_OK;
+    }));
     s->hist_n++;
     s->grad_pending = false;
     return BB_OK;
@@ -1733,7 +1679,7 @@ int bb_solver_allreduce(bb_solver *s) {
 }
 
 int bb_solver_iterate_dist(bb_solver *s, int64_t iters, double lr) {
-    BB_REQUIRE(iters >= 0, "bb_solver_iterate_dist: iters < 0");
+    BB_TRY(check_iterate(s, iters, "bb_solver_iterate_dist"));
     for (int64_t k = 0; k < iters; ++k) {
         BB_TRY(bb_solver_grad(s));
         BB_TRY(bb_solver_allreduce(s));
@@ -1762,19 +1708,14 @@ int launch_peer_receive(bb_solver *s, void *X, double lr, double mu, double *str
     // the flag pointers are the second half of a PeerTable (same for both parities)
     unsigned long long *const *poison =
         (unsigned long long *const *)((const char *)s->d_peer_table + kMaxPeers * sizeof(void *));
-    if (s->dtype == BB_F32)
-        BB_HIP_CHECK(bb::launch(peer_receive_kernel<float>, dim3(grid), dim3(256), 0, s->stream,
-                                (float *)X, (float *)s->d_V, (const float *)arena, flags, poison,
-                                s->world, s->peer_slot_elems, n3, (float)lr, (float)mu, stress_out,
-                                s->peer_seq, s->d_peer_state, s->peer_limit_ticks,
-                                (const unsigned *)s->d_peer_mask, (int)(3 * s->L.vw)));
-    else
-        BB_HIP_CHECK(bb::launch(peer_receive_kernel<double>, dim3(grid), dim3(256), 0, s->stream,
-                                (double *)X, (double *)s->d_V, (const double *)arena, flags, poison,
-                                s->world, s->peer_slot_elems, n3, lr, mu, stress_out, s->peer_seq,
-                                s->d_peer_state, s->peer_limit_ticks,
-                                (const unsigned *)s->d_peer_mask, (int)(3 * s->L.vw)));
-    return BB_OK;
+    return by_dtype(s, [&](auto t) -> int {
+        using T = typename decltype(t)::T;
+        BB_HIP_CHECK(bb::launch(peer_receive_kernel<T>, dim3(grid), dim3(256), 0, s->stream, (T *)X,
+                                (T *)s->d_V, (const T *)arena, flags, poison, s->world, s->peer_slot_elems,
+                                n3, (T)lr, (T)mu, stress_out, s->peer_seq, s->d_peer_state,
+                                s->peer_limit_ticks, (const unsigned *)s->d_peer_mask, (int)(3 * s->L.vw)));
+        return BB_OK;
+    });
 }
 
 // The plain SUM over the ranks of what the last sweep left in the partials (scale 1: a
@@ -1912,7 +1853,7 @@ int bb_solver_peer_connect(bb_solver *s, const void *handles) {
             s->peer_opened.push_back(ptr);
         }
     }
-    BB_TRY(s->dtype == BB_F32 ? build_peer_tables<float>(s) : build_peer_tables<double>(s));
+    BB_TRY(by_dtype(s, [&](auto t) { return build_peer_tables(t, s); }));
     {
         // Who sends what: rank q's units lie in tiles (I, J) and carry gradient for the bins of
         // blocks I and J only; for every other block its partial is zero by construction.  Every
@@ -2027,31 +1968,25 @@ int bb_solver_peer_status(bb_solver *s, int *status) {
 }
 
 int bb_solver_iterate_peer(bb_solver *s, int64_t iters, double lr) {
-    BB_TRY(check_ready(s, "bb_solver_iterate_peer"));
-    BB_REQUIRE(iters >= 0, "bb_solver_iterate_peer: iters < 0");
+    BB_TRY(check_iterate(s, iters, "bb_solver_iterate_peer"));
     if (!s->peer_connected)
         return bb::fail(BB_ERR_STATE, "bb_solver_iterate_peer: bb_solver_peer_connect first");
     if (s->grad_pending)
         return bb::fail(BB_ERR_STATE, "bb_solver_iterate_peer: a bb_solver_grad is pending");
-    if (s->hist_n + iters > s->hist_cap)
-        return bb::fail(BB_ERR_STATE, "bb_solver_iterate_peer: stress history full");
+    // (the exchange kernels fold one stress per iteration into the history)
+    if (s->n_maps > 1)
+        return bb::fail(BB_ERR_STATE, "bb_solver_iterate_peer: a solver of several maps "
+                                      "(bb_solver_set_maps) iterates with bb_solver_iterate only");
     BB_TRY(bb::enter_device(s->device));
     for (int64_t k = 0; k < iters; ++k) {
-        hipEvent_t *ev = timing_slot(s);
-        if (ev) BB_HIP_CHECK(hipEventRecord(ev[0], s->stream));
-        BB_TRY(launch_grad(s));
-        if (ev) BB_HIP_CHECK(hipEventRecord(ev[1], s->stream));
-        s->peer_seq++;
-        if (s->peer_fused) {
-            // one launch: reduce, push, wait, sum, update (reduce_exchange_kernel)
-            BB_TRY(launch_exchange(s, lr, s->d_stress_hist + s->hist_n));
-            if (ev) BB_HIP_CHECK(hipEventRecord(ev[2], s->stream));
-            s->hist_n++;
-            continue;
-        }
-        BB_TRY(launch_reduce(s, kReducePeer, 0.0, nullptr));
-        if (ev) BB_HIP_CHECK(hipEventRecord(ev[2], s->stream));
-        BB_TRY(launch_peer_receive(s, s->d_X, lr, s->momentum, s->d_stress_hist + s->hist_n));
+        double *hist = s->d_stress_hist + s->hist_n;
+        // one launch: reduce, push, wait, sum, update (reduce_exchange_kernel); else the reduce
+        // pushes and peer_receive_kernel waits, sums and updates
+        BB_TRY(timed_step(s, [&] { return launch_grad(s); }, [&] {
+            s->peer_seq++;
+            return s->peer_fused ? launch_exchange(s, lr, hist) : launch_reduce(s, kReducePeer, 0.0, nullptr);
+        }));
+        if (!s->peer_fused) BB_TRY(launch_peer_receive(s, s->d_X, lr, s->momentum, hist));
         s->hist_n++;
     }
     return BB_OK;
@@ -2380,7 +2315,7 @@ void jacobi3(double *a, double *z) {   // a symmetric 3 x 3 -> eigenvalues on it
 }
 
 template <typename T>
-int spectral_init_t(bb_solver *s, int n_iter, const double *v0, double tol, int *iters_done,
+int spectral_init_t(TypeTag<T>, bb_solver *s, int n_iter, const double *v0, double tol, int *iters_done,
                     double *residual_out) {
     const int64_t n = s->L.n_bins, n_pad = s->L.n_pad, n3 = n_pad * 3;
     if (!s->d_mv_in) BB_TRY(dev_alloc((char **)&s->d_mv_in, n3 * (int64_t)sizeof(T)));
@@ -2531,9 +2466,7 @@ extern "C" int bb_solver_spectral_init_tol(bb_solver *s, int n_iter, double tol,
                                       "(start each map with a solver of its own)");
     BB_REQUIRE(s->L.n_bins >= 3, "bb_solver_spectral_init: needs at least 3 bins");
     BB_TRY(bb::enter_device(s->device));
-    const int rc = s->dtype == BB_F32 ? spectral_init_t<float>(s, n_iter, v0, tol, iters_done, residual)
-                                      : spectral_init_t<double>(s, n_iter, v0, tol, iters_done, residual);
-    if (rc != BB_OK) return rc;
+    BB_TRY(by_dtype(s, [&](auto t) { return spectral_init_t(t, s, n_iter, v0, tol, iters_done, residual); }));
     s->have_coords = true;
     s->hist_n = 0;
     s->grad_pending = false;
@@ -2590,14 +2523,13 @@ int group_apply(bb_group *g, int r) {
     const dim3 grid((unsigned)((n3 + 255) / 256)), block(256);
     const int world = (int)g->m.size(), ch = (int)(3 * s->L.vw);
     double *hist = s->d_stress_hist + s->hist_n;
-    if (s->dtype == BB_F32)
-        BB_HIP_CHECK(bb::launch(group_apply_kernel<float>, grid, block, 0, s->stream, (float *)s->d_X,
-                                (float *)s->d_V, (const float *const *)g->d_src[(size_t)r], world, n3,
-                                (float)g->lr, (float)s->momentum, hist, g->d_mask[(size_t)r], ch));
-    else
-        BB_HIP_CHECK(bb::launch(group_apply_kernel<double>, grid, block, 0, s->stream, (double *)s->d_X,
-                                (double *)s->d_V, (const double *const *)g->d_src[(size_t)r], world,
-                                n3, g->lr, s->momentum, hist, g->d_mask[(size_t)r], ch));
+    BB_TRY(by_dtype(s, [&](auto t) -> int {
+        using T = typename decltype(t)::T;
+        BB_HIP_CHECK(bb::launch(group_apply_kernel<T>, grid, block, 0, s->stream, (T *)s->d_X, (T *)s->d_V,
+                                (const T *const *)g->d_src[(size_t)r], world, n3, (T)g->lr, (T)s->momentum,
+                                hist, g->d_mask[(size_t)r], ch));
+        return BB_OK;
+    }));
     BB_HIP_CHECK(hipEventRecord(g->applied[(size_t)r], s->stream));
     s->hist_n++;
     return BB_OK;
@@ -2752,15 +2684,12 @@ int bb_group_create(bb_group **out, bb_solver *const *members, int n) {
 
 int bb_group_iterate(bb_group *g, int64_t iters, double lr) {
     BB_REQUIRE(g != nullptr, "bb_group_iterate: group is NULL");
-    BB_REQUIRE(iters >= 0, "bb_group_iterate: iters < 0");
     for (size_t r = 0; r < g->m.size(); ++r) {
         bb_solver *s = g->m[r];
-        BB_TRY(check_ready(s, "bb_group_iterate"));
+        BB_TRY(check_iterate(s, iters, "bb_group_iterate"));
         if (s->grad_pending)
             return bb::fail(BB_ERR_STATE, "bb_group_iterate: member " + std::to_string(r) +
                                               " has a bb_solver_grad pending");
-        if (s->hist_n + iters > s->hist_cap)
-            return bb::fail(BB_ERR_STATE, "bb_group_iterate: stress history full");
         if (s->d_exch != g->exch[r])
             return bb::fail(BB_ERR_STATE, "bb_group_iterate: member " + std::to_string(r) +
                                               " changed its exchange buffer after bb_group_create");

@@ -271,7 +271,9 @@ BB_API int bb_solver_set_exchange_buffer(bb_solver *s, void *dev_ptr);
  *   bb_comm_unique_id      one rank makes the 128-byte id (ncclGetUniqueId) ...
  *   bb_solver_comm_init    ... every rank passes it in (ncclCommInitRank; collective)
  *   bb_solver_allreduce    in-place sum of the exchange buffer, between grad and apply
- *   bb_solver_iterate_dist `iters` x { grad, allreduce, apply }
+ *   bb_solver_iterate_dist `iters` x { grad, allreduce, apply }; a call the stress history
+ *                          cannot hold is refused with BB_ERR_STATE before anything is
+ *                          enqueued, as bb_solver_iterate's
  * The id travels by whatever the caller has (MPI_Bcast, torch.distributed, a file). */
 BB_API int bb_comm_unique_id(void *id_out_128_bytes);
 BB_API int bb_solver_comm_init(bb_solver *s, const void *unique_id_128_bytes);
@@ -317,7 +319,10 @@ BB_API int bb_comm_cache_clear(void);
  *   bb_solver_peer_export   allocate the arena, write its handle (BB_PEER_HANDLE_BYTES)
  *   bb_solver_peer_connect  map the arenas of all ranks (handles in rank order;
  *                           collective: every rank must have exported)
- *   bb_solver_iterate_peer  `iters` x { grad, reduce+push, wait+sum+apply }
+ *   bb_solver_iterate_peer  `iters` x { grad, reduce+push, wait+sum+apply }; BB_ERR_STATE,
+ *                           nothing enqueued, for a call the stress history cannot hold (as
+ *                           bb_solver_iterate) and for a solver of several maps
+ *                           (bb_solver_set_maps: the exchange records one stress per iteration)
  *   bb_solver_peer_status   0 = healthy; 1 = a wait ran into the time limit
  *                           (BB_PEER_TIMEOUT_MS, default 10000) or a peer reported
  *                           its own failure: this call reports BB_ERR_STATE

@@ -562,7 +562,27 @@ def test_peer_exchange_call_sequence_errors():
     assert lib.bb_solver_peer_connect(a._h, ha.raw + hb.raw) == _lib.BB_ERR_STATE     # once only
     assert lib.bb_solver_peer_status(a._h, st) == _lib.BB_OK and st.value == 0
     assert lib.bb_solver_peer_export(None, ha) == _lib.BB_ERR_INVALID
-    for e in (a, b, other):
+    # refused before anything is enqueued: a call longer than the stress history, and a
+    # one-rank solver of several maps connected to its own arena (the exchange records one
+    # stress per iteration); history and coordinates stay as they were
+    x_a = a.get_coords()
+    assert lib.bb_solver_iterate_peer(a._h, (1 << 20) + 1, 0.1) == _lib.BB_ERR_STATE
+    assert b"stress history full" in lib.bb_last_error()
+    assert a.stress_history().shape == (0,) and numpy.array_equal(a.get_coords(), x_a)
+    m = HipEngine(1024, "float32", tiles=(numpy.array([0, 1], dtype=numpy.int32),
+                                          numpy.array([0, 1], dtype=numpy.int32)))
+    m.set_maps([0, 512, 1024], [1.0, 1.0])
+    xm = _oracle.random_walk(1024)
+    m.set_wish_from_coords(xm)
+    m.set_coords(xm)
+    hm = buf()
+    assert lib.bb_solver_peer_export(m._h, hm) == _lib.BB_OK
+    assert lib.bb_solver_peer_connect(m._h, hm.raw) == _lib.BB_OK
+    x_m = m.get_coords()
+    assert lib.bb_solver_iterate_peer(m._h, 1, 0.1) == _lib.BB_ERR_STATE
+    assert b"several maps" in lib.bb_last_error()
+    assert m.stress_history().shape == (0,) and numpy.array_equal(m.get_coords(), x_m)
+    for e in (a, b, other, m):
         e.close()
 
 

@@ -1883,6 +1883,11 @@ def test_solver_state_machine():
     r.set_coords(x0)
     with pytest.raises(RuntimeError, match="all-reduce"):
         r.iterate(1, 0.1)                             # world > 1 must go through grad/apply
+    with pytest.raises(RuntimeError, match="history"):
+        r.iterate_dist((1 << 20) + 1, 0.1)            # refused whole, before the communicator is needed
+    with pytest.raises(RuntimeError, match="no bb_solver_grad pending"):
+        r.apply(0.1)                                  # ... so no grad was enqueued
+    assert r.stress_history().shape == (0,) and numpy.array_equal(r.get_coords(), x0)
     r.close()
 
 
