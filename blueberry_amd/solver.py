@@ -13,6 +13,7 @@ torch.distributed (backend "nccl" = RCCL over xGMI) -- or, with
 torch (`GroupEngine`: one solver per device, one host thread each, the sum over them
 ordered by HIP events, `bb_group_*`).
 """
+import contextlib
 import os
 import sys
 
@@ -80,6 +81,8 @@ class DeviceTriples(object):
 class HipEngine(object):
     """One rank's device state: thin, 1:1 over the bb_solver_* C-ABI."""
 
+    n_maps = 1                      # several once set_maps() has laid them end to end
+
     def __init__(self, n_bins, dtype, rank=0, world=1, device=0, tiles=None):
         self._lib = _lib.load()
         self._h = _lib.c_void_p()
@@ -94,15 +97,27 @@ class HipEngine(object):
             if ti.shape != tj.shape or ti.ndim != 1:
                 raise ValueError("tiles must be a pair of equal-length 1-D index arrays")
             nt = ti.shape[0]
-        _lib.check(self._lib.bb_solver_create(
-            self._h, self.n_bins, _DTYPES[dtype], self.device, self.rank, self.world,
-            None if ti is None else ti.ctypes.data_as(_lib.p_i32),
-            None if tj is None else tj.ctypes.data_as(_lib.p_i32), nt), "bb_solver_create")
+        self._call("create", self.n_bins, _DTYPES[dtype], self.device, self.rank, self.world,
+                   None if ti is None else ti.ctypes.data_as(_lib.p_i32),
+                   None if tj is None else tj.ctypes.data_as(_lib.p_i32), nt)
         self._exch = None
         self._comm_state = None     # "peer" | "rccl" | "torch" | "host" once chosen
         self._peer = None           # outcome of peer_setup()
         self._peer_error = ""
         self._comm_trial = None     # timings of select_exchange's trial, if one ran
+        self._comm_trial_error = None   # what made a leg of that trial fail on this rank
+
+    def _call(self, name, *args):
+        """bb_solver_<name>(handle, *args); any status but BB_OK raises (`_lib.check`)."""
+        name = "bb_solver_" + name
+        _lib.check(getattr(self._lib, name)(self._h, *args), name)
+
+    def _get(self, ctype, name, *args):
+        """The one scalar bb_solver_<name>(handle, *args, &out) writes: ctype is c_int, c_dbl
+        or c_i64."""
+        out = ctype()
+        self._call(name, *args, out)
+        return out.value
 
     # -- lifetime ---------------------------------------------------------
     def close(self):
@@ -121,7 +136,7 @@ class HipEngine(object):
     def layout(self):
         info = _lib.LayoutInfo()
         ub, ue = _lib.c_i64(), _lib.c_i64()
-        _lib.check(self._lib.bb_solver_layout(self._h, info, ub, ue), "bb_solver_layout")
+        self._call("layout", info, ub, ue)
         d = info.as_dict()
         d["u_begin"], d["u_end"] = int(ub.value), int(ue.value)
         return d
@@ -129,15 +144,22 @@ class HipEngine(object):
     # -- inputs -----------------------------------------------------------
     def set_wish_dense(self, matrix, kind, alpha):
         m = _check_square(matrix, self.n_bins)
-        _lib.check(self._lib.bb_solver_set_wish_dense(
-            self._h, _lib.as_f64_ptr(m), m.strides[0] // 8, _KINDS[kind], float(alpha)),
-            "bb_solver_set_wish_dense")
+        self._call("set_wish_dense", _lib.as_f64_ptr(m), m.strides[0] // 8, _KINDS[kind],
+                   float(alpha))
 
     def set_wish_from_cm(self, dev_matrix, kind, alpha):
         """Device to device from a resident ContactMap matrix (datatypes._DeviceMatrix)."""
-        _lib.check(self._lib.bb_solver_set_wish_from_cm(self._h, dev_matrix._h, _KINDS[kind],
-                                                        float(alpha)),
-                   "bb_solver_set_wish_from_cm")
+        self._call("set_wish_from_cm", dev_matrix._h, _KINDS[kind], float(alpha))
+
+    def set_wish_resident(self, cm, kind, alpha):
+        """A resident ContactMap: device to device when it lives on this engine's GPU."""
+        dev = cm._resident()
+        if dev.device == self.device:
+            self.set_wish_from_cm(dev, kind, alpha)
+        else:
+            # the map lives on another GPU than this rank's solver (a ContactMap made with
+            # an explicit device): through the host once, like a plain matrix
+            self.set_wish_dense(cm.to_host(), kind, alpha)
 
     def set_wish_sparse(self, rows, cols, vals, kind, alpha, KRnorm=None, KRexpected=None):
         r = numpy.ascontiguousarray(rows, dtype=numpy.int64)
@@ -145,29 +167,15 @@ class HipEngine(object):
         v = numpy.ascontiguousarray(vals, dtype=numpy.float64)
         if not (r.ndim == c.ndim == v.ndim == 1 and r.shape == c.shape == v.shape):
             raise ValueError("rows, cols, vals must be 1-D arrays of equal length")
-        kr = ke = None
-        if KRnorm is not None or KRexpected is not None:
-            if KRnorm is None or KRexpected is None:
-                raise ValueError("KRnorm and KRexpected go together")
-            kr, ke = _pad_vector(KRnorm, self.n_bins), _pad_vector(KRexpected, self.n_bins)
-        _lib.check(self._lib.bb_solver_set_wish_sparse(
-            self._h, r.ctypes.data_as(_lib.p_i64), c.ctypes.data_as(_lib.p_i64),
-            _lib.as_f64_ptr(v), r.shape[0], _KINDS[kind], float(alpha),
-            None if kr is None else _lib.as_f64_ptr(kr),
-            None if ke is None else _lib.as_f64_ptr(ke)), "bb_solver_set_wish_sparse")
+        kr, ke = _kr_pair(KRnorm, KRexpected, self.n_bins)
+        self._call("set_wish_sparse", r.ctypes.data_as(_lib.p_i64), c.ctypes.data_as(_lib.p_i64),
+                   _lib.as_f64_ptr(v), r.shape[0], _KINDS[kind], float(alpha), kr, ke)
 
     def set_wish_triples(self, dev_triples, kind, alpha, KRnorm=None, KRexpected=None):
         """From triples resident on the device (`DeviceTriples`): binned, KR / O-E
         normalised and converted there."""
-        kr = ke = None
-        if KRnorm is not None or KRexpected is not None:
-            if KRnorm is None or KRexpected is None:
-                raise ValueError("KRnorm and KRexpected go together")
-            kr, ke = _pad_vector(KRnorm, self.n_bins), _pad_vector(KRexpected, self.n_bins)
-        _lib.check(self._lib.bb_solver_set_wish_triples(
-            self._h, dev_triples._h, _KINDS[kind], float(alpha),
-            None if kr is None else _lib.as_f64_ptr(kr),
-            None if ke is None else _lib.as_f64_ptr(ke)), "bb_solver_set_wish_triples")
+        kr, ke = _kr_pair(KRnorm, KRexpected, self.n_bins)
+        self._call("set_wish_triples", dev_triples._h, _KINDS[kind], float(alpha), kr, ke)
 
     # -- several maps in one solver (bb_solver_set_maps) -----------------------
     def set_maps(self, bin_begin, lr_scale):
@@ -177,110 +185,90 @@ class HipEngine(object):
         sc = numpy.ascontiguousarray(lr_scale, dtype=numpy.float64)
         if b.ndim != 1 or sc.ndim != 1 or b.shape[0] != sc.shape[0] + 1:
             raise ValueError("bin_begin needs one entry more than lr_scale")
-        _lib.check(self._lib.bb_solver_set_maps(self._h, sc.shape[0], b.ctypes.data_as(_lib.p_i64),
-                                                _lib.as_f64_ptr(sc)), "bb_solver_set_maps")
+        self._call("set_maps", sc.shape[0], b.ctypes.data_as(_lib.p_i64), _lib.as_f64_ptr(sc))
         self.n_maps = int(sc.shape[0])
 
     def set_wish_dense_block(self, matrix, bin_offset, kind, alpha):
         m = _check_square(matrix, numpy.asarray(matrix).shape[0])
-        _lib.check(self._lib.bb_solver_set_wish_dense_block(
-            self._h, _lib.as_f64_ptr(m), m.strides[0] // 8, m.shape[0], int(bin_offset),
-            _KINDS[kind], float(alpha)), "bb_solver_set_wish_dense_block")
+        self._call("set_wish_dense_block", _lib.as_f64_ptr(m), m.strides[0] // 8, m.shape[0],
+                   int(bin_offset), _KINDS[kind], float(alpha))
 
     def set_wish_from_cm_block(self, dev_matrix, bin_offset, kind, alpha):
-        _lib.check(self._lib.bb_solver_set_wish_from_cm_block(
-            self._h, dev_matrix._h, int(bin_offset), _KINDS[kind], float(alpha)),
-            "bb_solver_set_wish_from_cm_block")
+        self._call("set_wish_from_cm_block", dev_matrix._h, int(bin_offset), _KINDS[kind],
+                   float(alpha))
+
+    def _set_steps(self, name, scale, per):
+        if scale is None:
+            self._call(name, None, 0)
+            return
+        sc = numpy.ascontiguousarray(scale, dtype=numpy.float64)
+        if sc.ndim != 1:
+            raise ValueError("scale must be one factor per " + per)
+        self._call(name, _lib.as_f64_ptr(sc), sc.shape[0])
 
     def set_block_steps(self, scale):
         """A step per block of the layout (`bb_solver_set_block_steps`): bin i moves by
         lr * scale[i // vw] * g_i; None = one step for all again."""
-        if scale is None:
-            _lib.check(self._lib.bb_solver_set_block_steps(self._h, None, 0),
-                       "bb_solver_set_block_steps")
-            return
-        sc = numpy.ascontiguousarray(scale, dtype=numpy.float64)
-        if sc.ndim != 1:
-            raise ValueError("scale must be one factor per block")
-        _lib.check(self._lib.bb_solver_set_block_steps(self._h, _lib.as_f64_ptr(sc), sc.shape[0]),
-                   "bb_solver_set_block_steps")
+        self._set_steps("set_block_steps", scale, "block")
 
     def set_bin_steps(self, scale):
         """A step per bin (`bb_solver_set_bin_steps`): bin i moves by lr * scale[i] * g_i;
         None = one step for all again."""
-        if scale is None:
-            _lib.check(self._lib.bb_solver_set_bin_steps(self._h, None, 0), "bb_solver_set_bin_steps")
-            return
-        sc = numpy.ascontiguousarray(scale, dtype=numpy.float64)
-        if sc.ndim != 1:
-            raise ValueError("scale must be one factor per bin")
-        _lib.check(self._lib.bb_solver_set_bin_steps(self._h, _lib.as_f64_ptr(sc), sc.shape[0]),
-                   "bb_solver_set_bin_steps")
+        self._set_steps("set_bin_steps", scale, "bin")
 
     def degrees(self):
         """Per bin, the number of this rank's stored pairs that constrain it (delta > 0):
         `bb_solver_degrees`, one pass over the resident units."""
         out = numpy.zeros(self.n_bins, dtype=numpy.int64)
-        _lib.check(self._lib.bb_solver_degrees(self._h, out.ctypes.data_as(_lib.p_i64), out.shape[0]),
-                   "bb_solver_degrees")
+        self._call("degrees", out.ctypes.data_as(_lib.p_i64), out.shape[0])
         return out
 
     def set_weight_power(self, q):
         """Weighted stress (SPEC 2.3.1): w = delta^-q, q in {0, 1, 2}
         (`bb_solver_set_weight_power`)."""
-        _lib.check(self._lib.bb_solver_set_weight_power(self._h, int(q)),
-                   "bb_solver_set_weight_power")
+        self._call("set_weight_power", int(q))
 
     def weight_sums(self):
         """Per bin, s_i = sum_j delta_ij^-q over this rank's stored pairs, float64
         (`bb_solver_weight_sums`; q = 0: the degrees)."""
         out = numpy.zeros(self.n_bins, dtype=numpy.float64)
-        _lib.check(self._lib.bb_solver_weight_sums(self._h, _lib.as_f64_ptr(out), out.shape[0]),
-                   "bb_solver_weight_sums")
+        self._call("weight_sums", _lib.as_f64_ptr(out), out.shape[0])
         return out
 
     def stress_maps(self):
-        out = numpy.empty(getattr(self, "n_maps", 1), dtype=numpy.float64)
-        _lib.check(self._lib.bb_solver_stress_maps(self._h, _lib.as_f64_ptr(out), out.shape[0]),
-                   "bb_solver_stress_maps")
+        out = numpy.empty(self.n_maps, dtype=numpy.float64)
+        self._call("stress_maps", _lib.as_f64_ptr(out), out.shape[0])
         return out
 
     def set_wish_from_coords(self, xstar):
-        x = _check_coords(xstar, self.n_bins)
-        _lib.check(self._lib.bb_solver_set_wish_from_coords(self._h, _lib.as_f64_ptr(x)),
-                   "bb_solver_set_wish_from_coords")
+        self._call("set_wish_from_coords", _lib.as_f64_ptr(_check_coords(xstar, self.n_bins)))
 
     def set_coords(self, x0):
-        x = _check_coords(x0, self.n_bins)
-        _lib.check(self._lib.bb_solver_set_coords(self._h, _lib.as_f64_ptr(x)),
-                   "bb_solver_set_coords")
+        self._call("set_coords", _lib.as_f64_ptr(_check_coords(x0, self.n_bins)))
 
     def get_coords(self):
         out = numpy.empty((self.n_bins, 3), dtype=numpy.float64)
-        _lib.check(self._lib.bb_solver_get_coords(self._h, _lib.as_f64_ptr(out)),
-                   "bb_solver_get_coords")
+        self._call("get_coords", _lib.as_f64_ptr(out))
         return out
 
     # -- iterations -------------------------------------------------------
     def set_momentum(self, mu):
-        _lib.check(self._lib.bb_solver_set_momentum(self._h, float(mu)), "bb_solver_set_momentum")
+        self._call("set_momentum", float(mu))
 
     def iterate(self, iters, lr):
-        _lib.check(self._lib.bb_solver_iterate(self._h, int(iters), float(lr)),
-                   "bb_solver_iterate")
+        self._call("iterate", int(iters), float(lr))
 
     def grad(self):
-        _lib.check(self._lib.bb_solver_grad(self._h), "bb_solver_grad")
+        self._call("grad")
 
     def apply(self, lr):
-        _lib.check(self._lib.bb_solver_apply(self._h, float(lr)), "bb_solver_apply")
+        self._call("apply", float(lr))
 
     def matvec_sq(self, x):
         """(D o D) @ x for this rank's units; x is (n_bins, 3)."""
         x = _check_coords(x, self.n_bins)
         y = numpy.empty_like(x)
-        _lib.check(self._lib.bb_solver_matvec_sq(self._h, _lib.as_f64_ptr(x), _lib.as_f64_ptr(y)),
-                   "bb_solver_matvec_sq")
+        self._call("matvec_sq", _lib.as_f64_ptr(x), _lib.as_f64_ptr(y))
         return y
 
     def spectral_init_device(self, n_iter, v0, tol=0.0):
@@ -293,6 +281,7 @@ class HipEngine(object):
         distance read or -1).  Raises RankDeficient when the iterate lost rank."""
         v0 = _check_coords(v0, self.n_bins)
         done, res = _lib.c_int(), _lib.c_dbl()
+        # explicit: a lost rank is an outcome of its own (the caller takes the host-driven start)
         rc = self._lib.bb_solver_spectral_init_tol(self._h, int(n_iter), float(tol),
                                                    _lib.as_f64_ptr(v0), done, res)
         if rc == _lib.BB_ERR_STATE and "lost rank" in _lib.last_error():
@@ -301,39 +290,30 @@ class HipEngine(object):
         return int(done.value), float(res.value)
 
     def stress(self):
-        out = _lib.c_dbl()
-        _lib.check(self._lib.bb_solver_stress(self._h, out), "bb_solver_stress")
-        return float(out.value)
+        return float(self._get(_lib.c_dbl, "stress"))
 
     def stress_history(self):
-        n = _lib.c_i64()
-        _lib.check(self._lib.bb_solver_get_stress_history(self._h, None, 0, n),
-                   "bb_solver_get_stress_history")
-        out = numpy.empty(int(n.value), dtype=numpy.float64)
+        out = numpy.empty(int(self._get(_lib.c_i64, "get_stress_history", None, 0)),
+                          dtype=numpy.float64)
         if out.size:
-            _lib.check(self._lib.bb_solver_get_stress_history(
-                self._h, _lib.as_f64_ptr(out), out.size, n), "bb_solver_get_stress_history")
+            self._get(_lib.c_i64, "get_stress_history", _lib.as_f64_ptr(out), out.size)
         return out
 
     def sync(self):
-        _lib.check(self._lib.bb_solver_sync(self._h), "bb_solver_sync")
+        self._call("sync")
 
     def exchange_size(self):
-        n = _lib.c_i64()
-        _lib.check(self._lib.bb_solver_exchange_size(self._h, n), "bb_solver_exchange_size")
-        return int(n.value)
+        return int(self._get(_lib.c_i64, "exchange_size"))
 
     def read_exchange(self):
         """Exchange buffer [g (n_pad,3) | stress hi | lo] as float64 on the host."""
         out = numpy.empty(self.exchange_size(), dtype=numpy.float64)
-        _lib.check(self._lib.bb_solver_read_exchange(self._h, _lib.as_f64_ptr(out), out.size),
-                   "bb_solver_read_exchange")
+        self._call("read_exchange", _lib.as_f64_ptr(out), out.size)
         return out
 
     def write_exchange(self, host):
         host = numpy.ascontiguousarray(host, dtype=numpy.float64)
-        _lib.check(self._lib.bb_solver_write_exchange(self._h, _lib.as_f64_ptr(host), host.size),
-                   "bb_solver_write_exchange")
+        self._call("write_exchange", _lib.as_f64_ptr(host), host.size)
 
     # -- the all-reduce boundary (world > 1) --------------------------------
     def comm_setup(self):
@@ -352,6 +332,7 @@ class HipEngine(object):
         dist.broadcast_object_list(box, src=0)
         if box[0] is None:
             return False
+        # explicit: a failure here is this rank's vote, not an error
         ok = self._lib.bb_solver_comm_init(self._h, box[0]) == _lib.BB_OK
         # all ranks must take the same path: agree on the outcome
         import torch
@@ -378,6 +359,7 @@ class HipEngine(object):
         return int(gen.value) if have.value else 0
 
     def _comm_attach(self):
+        # explicit: the outcome is agreed between the ranks (`comm_reuse`), not raised
         return self._lib.bb_solver_comm_attach(self._h) == _lib.BB_OK
 
     def _comm_detach(self):
@@ -385,8 +367,7 @@ class HipEngine(object):
 
     def iterate_dist(self, iters, lr):
         """`iters` x { grad, RCCL all-reduce, apply }, all enqueued by one C call."""
-        _lib.check(self._lib.bb_solver_iterate_dist(self._h, int(iters), float(lr)),
-                   "bb_solver_iterate_dist")
+        self._call("iterate_dist", int(iters), float(lr))
 
     def peer_setup(self):
         """Connect the peer exchange (one-shot all-reduce inside the solver's own
@@ -399,6 +380,7 @@ class HipEngine(object):
         if self._peer is not None:
             return self._peer
         buf = ctypes.create_string_buffer(_lib.BB_PEER_HANDLE_BYTES)
+        # explicit, here and at the connect: a failure is this rank's vote, not an error
         mine = buf.raw if self._lib.bb_solver_peer_export(self._h, buf) == _lib.BB_OK else None
         handles = [None] * self.world
         dist.all_gather_object(handles, mine)
@@ -415,45 +397,38 @@ class HipEngine(object):
     def iterate_peer(self, iters, lr):
         """`iters` x { grad, reduce + push to every peer, wait + rank-ordered sum +
         update }, all enqueued by one C call."""
-        _lib.check(self._lib.bb_solver_iterate_peer(self._h, int(iters), float(lr)),
-                   "bb_solver_iterate_peer")
+        self._call("iterate_peer", int(iters), float(lr))
 
     def sync_timeout(self, milliseconds):
         """sync() that raises RuntimeError if the stream has not drained in time."""
-        _lib.check(self._lib.bb_solver_sync_timeout(self._h, int(milliseconds)),
-                   "bb_solver_sync_timeout")
+        self._call("sync_timeout", int(milliseconds))
 
     def comm_abort(self):
-        _lib.check(self._lib.bb_solver_comm_abort(self._h), "bb_solver_comm_abort")
+        self._call("comm_abort")
 
     def peer_form(self):
         """'one launch' (reduce, push, wait, sum and update in one kernel) or 'two launches'
         (include/blueberry_hip.h, peer exchange)."""
-        one = _lib.c_int()
-        _lib.check(self._lib.bb_solver_peer_form(self._h, one), "bb_solver_peer_form")
-        return "one launch" if one.value else "two launches"
+        return "one launch" if self._get(_lib.c_int, "peer_form") else "two launches"
 
     def peer_set_form(self, one_launch):
         """Choose the exchange's form before its first use (the same on every rank)."""
-        _lib.check(self._lib.bb_solver_peer_set_form(self._h, 1 if one_launch else 0),
-                   "bb_solver_peer_set_form")
+        self._call("peer_set_form", 1 if one_launch else 0)
 
     def peer_set_timeout(self, milliseconds):
-        _lib.check(self._lib.bb_solver_peer_set_timeout(self._h, int(milliseconds)),
-                   "bb_solver_peer_set_timeout")
+        self._call("peer_set_timeout", int(milliseconds))
 
     def comm_world(self):
         """Ranks RCCL reports for the library's communicator, or None without one."""
         n = _lib.c_int()
+        # explicit: no communicator is an answer (None), not an error
         if self._lib.bb_solver_comm_world(self._h, n) != _lib.BB_OK:
             return None
         return int(n.value)
 
     def peer_status(self):
         """Synchronise and raise if a peer wait ran into its time limit."""
-        st = _lib.c_int()
-        _lib.check(self._lib.bb_solver_peer_status(self._h, st), "bb_solver_peer_status")
-        return int(st.value)
+        return int(self._get(_lib.c_int, "peer_status"))
 
     def exchange_tensor(self):
         """A torch tensor aliasing the exchange buffer [g (n_pad,3) | hi | lo].
@@ -470,56 +445,43 @@ class HipEngine(object):
                     "two HIP runtimes are loaded (%s): import torch BEFORE the first "
                     "blueberry_amd compute call in a distributed job, so that "
                     "libblueberry_hip.so binds to the runtime torch uses" % ", ".join(rts))
-            n = _lib.c_i64()
-            _lib.check(self._lib.bb_solver_exchange_size(self._h, n), "bb_solver_exchange_size")
             tdt = torch.float32 if self.dtype == "float32" else torch.float64
             dev = torch.device("cuda", self.device)
-            self._exch = torch.zeros(int(n.value), dtype=tdt, device=dev)
+            self._exch = torch.zeros(self.exchange_size(), dtype=tdt, device=dev)
             stream = torch.cuda.current_stream(dev)
-            _lib.check(self._lib.bb_solver_set_stream(self._h, _lib.c_void_p(stream.cuda_stream)),
-                       "bb_solver_set_stream")
-            _lib.check(self._lib.bb_solver_set_exchange_buffer(
-                self._h, _lib.c_void_p(self._exch.data_ptr())), "bb_solver_set_exchange_buffer")
+            self._call("set_stream", _lib.c_void_p(stream.cuda_stream))
+            self._call("set_exchange_buffer", _lib.c_void_p(self._exch.data_ptr()))
         return self._exch
 
     # -- measurement ------------------------------------------------------
     def set_timing(self, enabled):
         """True / 1: HIP events around every iteration; k > 1: every k-th; False: off."""
-        _lib.check(self._lib.bb_solver_set_timing(self._h, int(enabled)),
-                   "bb_solver_set_timing")
+        self._call("set_timing", int(enabled))
 
     def timing(self):
         g, r, n = _lib.c_dbl(), _lib.c_dbl(), _lib.c_i64()
-        _lib.check(self._lib.bb_solver_get_timing(self._h, g, r, n), "bb_solver_get_timing")
-        st = _lib.c_dbl()
-        _lib.check(self._lib.bb_solver_get_step_timing(self._h, st), "bb_solver_get_step_timing")
+        self._call("get_timing", g, r, n)
         return {"grad_ms": float(g.value), "reduce_ms": float(r.value), "launches": int(n.value),
-                "step_ms": float(st.value)}
+                "step_ms": float(self._get(_lib.c_dbl, "get_step_timing"))}
 
     def event_gap_ms(self, pairs=16):
         """Average ms between two HIP events recorded back to back behind a sweep launch:
         what an event-timed interval contains besides its kernel (measurement aid)."""
-        ms = _lib.c_dbl()
-        _lib.check(self._lib.bb_solver_measure_event_gap(self._h, int(pairs), ms),
-                   "bb_solver_measure_event_gap")
-        return float(ms.value)
+        return float(self._get(_lib.c_dbl, "measure_event_gap", int(pairs)))
 
     def stream_read_ms(self, launches=10):
         """Average ms of a read-only sweep over the resident units (measurement aid)."""
-        ms = _lib.c_dbl()
-        _lib.check(self._lib.bb_solver_measure_stream_read(self._h, int(launches), ms),
-                   "bb_solver_measure_stream_read")
-        return float(ms.value)
+        return float(self._get(_lib.c_dbl, "measure_stream_read", int(launches)))
 
     def iteration_path(self):
         """'row_owner' (small one-rank maps: one launch per iteration) or 'units'."""
         ro, wpr = _lib.c_int(), _lib.c_int()
-        _lib.check(self._lib.bb_solver_iteration_path(self._h, ro, wpr), "bb_solver_iteration_path")
+        self._call("iteration_path", ro, wpr)
         return ("row_owner", int(wpr.value)) if ro.value else ("units", 0)
 
     def traffic(self):
         b, p = _lib.c_i64(), _lib.c_i64()
-        _lib.check(self._lib.bb_solver_traffic(self._h, b, p), "bb_solver_traffic")
+        self._call("traffic", b, p)
         return {"unit_bytes": int(b.value), "pairs_dense": int(p.value)}
 
 
@@ -565,18 +527,27 @@ class GroupEngine(object):
         except Exception:
             pass
 
+    def _each(self, name, *args):
+        """Every member's `name`(*args), in rank order."""
+        for e in self.members:
+            getattr(e, name)(*args)
+
+    def _summed(self, name, *args):
+        """The members' `name`(*args) added on the host in rank order: (m0 + m1) + m2 ..."""
+        out = getattr(self.members[0], name)(*args)
+        for e in self.members[1:]:
+            out = out + getattr(e, name)(*args)
+        return out
+
     def layout(self):
         return self.members[0].layout()
 
     # -- inputs: every member packs its own units from the one input --------------------
     def set_wish_dense(self, matrix, kind, alpha):
-        m = _check_square(matrix, self.n_bins)
-        for e in self.members:
-            e.set_wish_dense(m, kind, alpha)
+        self._each("set_wish_dense", _check_square(matrix, self.n_bins), kind, alpha)
 
     def set_wish_sparse(self, rows, cols, vals, kind, alpha, KRnorm=None, KRexpected=None):
-        for e in self.members:
-            e.set_wish_sparse(rows, cols, vals, kind, alpha, KRnorm, KRexpected)
+        self._each("set_wish_sparse", rows, cols, vals, kind, alpha, KRnorm, KRexpected)
 
     def set_wish_triples(self, dev_triples, kind, alpha, KRnorm=None, KRexpected=None):
         """`dev_triples.per_device`: the triples uploaded once per distinct device."""
@@ -585,9 +556,7 @@ class GroupEngine(object):
             e.set_wish_triples(per_device[e.device], kind, alpha, KRnorm, KRexpected)
 
     def set_wish_from_coords(self, xstar):
-        x = _check_coords(xstar, self.n_bins)
-        for e in self.members:
-            e.set_wish_from_coords(x)
+        self._each("set_wish_from_coords", _check_coords(xstar, self.n_bins))
 
     def set_wish_resident(self, cm, kind, alpha):
         """A resident ContactMap: members on its device pack device to device, members on
@@ -596,56 +565,43 @@ class GroupEngine(object):
         dev = cm._resident()
         host = None
         for e in self.members:
-            if e.device != dev.device:
-                rc = self._lib.bb_solver_set_wish_from_cm(e._h, dev._h, _KINDS[kind], float(alpha))
-                if rc == _lib.BB_OK:
-                    continue
-                if not (rc == _lib.BB_ERR_INVALID and "without peer access" in _lib.last_error()):
-                    _lib.check(rc, "bb_solver_set_wish_from_cm")
-                if host is None:
-                    host = cm.to_host()
-                e.set_wish_dense(host, kind, alpha)
-            else:
-                e.set_wish_from_cm(dev, kind, alpha)
+            if e.device == dev.device:
+                e.set_wish_resident(cm, kind, alpha)
+                continue
+            # explicit: "without peer access" sends this member through the host, not an error
+            rc = self._lib.bb_solver_set_wish_from_cm(e._h, dev._h, _KINDS[kind], float(alpha))
+            if rc == _lib.BB_OK:
+                continue
+            if not (rc == _lib.BB_ERR_INVALID and "without peer access" in _lib.last_error()):
+                _lib.check(rc, "bb_solver_set_wish_from_cm")
+            if host is None:
+                host = cm.to_host()
+            e.set_wish_dense(host, kind, alpha)
 
     # -- per-bin steps, weighting: summed on the host in rank order ---------------------
     def degrees(self):
-        out = self.members[0].degrees()
-        for e in self.members[1:]:
-            out = out + e.degrees()
-        return out
+        return self._summed("degrees")
 
     def set_weight_power(self, q):
-        for e in self.members:
-            e.set_weight_power(q)
+        self._each("set_weight_power", q)
 
     def weight_sums(self):
-        out = self.members[0].weight_sums()
-        for e in self.members[1:]:
-            out = out + e.weight_sums()
-        return out
+        return self._summed("weight_sums")
 
     def set_bin_steps(self, scale):
-        for e in self.members:
-            e.set_bin_steps(scale)
+        self._each("set_bin_steps", scale)
 
     def matvec_sq(self, x):
         """(D o D) @ x over the whole map: the members' products summed in rank order (the
         host-driven spectral start)."""
-        out = self.members[0].matvec_sq(x)
-        for e in self.members[1:]:
-            out = out + e.matvec_sq(x)
-        return out
+        return self._summed("matvec_sq", x)
 
     # -- iterations -------------------------------------------------------
     def set_coords(self, x0):
-        x = _check_coords(x0, self.n_bins)
-        for e in self.members:
-            e.set_coords(x)
+        self._each("set_coords", _check_coords(x0, self.n_bins))
 
     def set_momentum(self, mu):
-        for e in self.members:
-            e.set_momentum(mu)
+        self._each("set_momentum", mu)
 
     def iterate(self, iters, lr):
         _lib.check(self._lib.bb_group_iterate(self._g, int(iters), float(lr)), "bb_group_iterate")
@@ -664,20 +620,36 @@ class GroupEngine(object):
         return [e.stress_history() for e in self.members]
 
     def sync(self):
-        for e in self.members:
-            e.sync()
+        self._each("sync")
 
 
 def _check_square(matrix, n_bins):
     m = numpy.asarray(matrix)
-    if m.ndim != 2 or m.shape[0] != m.shape[1]:
-        raise ValueError("contact matrix must be square, got shape %r" % (m.shape,))
+    _square_bins(m.shape)
     if m.shape[0] != n_bins:
         raise ValueError("contact matrix has %d bins, solver was created for %d"
                          % (m.shape[0], n_bins))
     if m.dtype != numpy.float64 or m.strides[1] != 8 or m.strides[0] % 8 or m.strides[0] < 8 * n_bins:
         m = numpy.ascontiguousarray(m, dtype=numpy.float64)
     return m
+
+
+def _square_bins(shape):
+    """The number of bins of a contact matrix of this shape, which has to be n x n."""
+    if len(shape) != 2 or shape[0] != shape[1]:
+        raise ValueError("contact matrix must be square, got shape %r" % (shape,))
+    return int(shape[0])
+
+
+def _kr_pair(KRnorm, KRexpected, n_bins):
+    """The two KR vectors of an input, padded to n_bins and as the pointers the C-ABI takes
+    (they keep their arrays alive), or (None, None) without them."""
+    if KRnorm is None and KRexpected is None:
+        return None, None
+    if KRnorm is None or KRexpected is None:
+        raise ValueError("KRnorm and KRexpected go together")
+    return (_lib.as_f64_ptr(_pad_vector(KRnorm, n_bins)),
+            _lib.as_f64_ptr(_pad_vector(KRexpected, n_bins)))
 
 
 def _pad_vector(v, n):
@@ -805,7 +777,7 @@ def _sum_over_ranks(counts, eng, world):
     kind = numpy.float64 if numpy.asarray(counts).dtype.kind == "f" else numpy.int64
     t = torch.from_numpy(numpy.ascontiguousarray(counts, dtype=kind))
     if dist.get_backend() == "nccl":
-        t = t.to(torch.device("cuda", getattr(eng, "device", 0)))
+        t = t.to(torch.device("cuda", eng.device))
         dist.all_reduce(t)
         return t.cpu().numpy()
     dist.all_reduce(t)
@@ -902,6 +874,25 @@ def _check_devices(devices, n_gpus, device, distributed):
     if len(devices) > 16:
         raise ValueError("devices: at most 16 members")
     return [int(d) for d in devices]
+
+
+@contextlib.contextmanager
+def _teardown(eng):
+    """Close the engine when the fit ends, however it ends."""
+    try:
+        yield
+    except BaseException:
+        # this rank leaves a multi-rank job in the middle: its peers may sit in a collective
+        # on the library's communicator, which must then not go back into the cache for the
+        # next fit() to borrow (close() would return it as free)
+        if _exchange_state(eng) == "rccl" and hasattr(eng, "comm_abort"):
+            try:
+                eng.comm_abort()
+            except Exception:                  # noqa: BLE001 -- the first error is the one to report
+                pass
+        raise
+    finally:
+        eng.close()
 
 
 class StructureSolver(object):
@@ -1053,20 +1044,75 @@ class StructureSolver(object):
         scipy.sparse matrix (symmetric; either triangle is enough; of several
         COO entries for one pair the last is kept) -- the sparse form never builds
         the dense matrix."""
+        source, n = self._map_source(X)
+        return self._fit_impl(source, n, init, None, None)
+
+    # -- the stages fit() and fit_many() share -----------------------------------------
+    def _map_source(self, X, sparse=True):
+        """(source, n_bins) of one input map.  source is X itself for a ContactMap whose
+        matrix lives in HBM (packed device to device; only its shape is read), a COO matrix
+        for scipy.sparse input (`sparse` false -- fit_many, which packs dense blocks -- takes
+        it as an array), else the host matrix as an ndarray."""
         if getattr(X, "is_resident", False) and hasattr(self._engine_factory, "set_wish_from_cm"):
-            # a ContactMap whose matrix lives in HBM: packed device to device
-            n = X.shape[0]
-            return self._fit_impl(X, n, init, None, None)
+            return X, _square_bins(X.shape)
         matrix = getattr(X, "matrix", X)
-        sparse = hasattr(matrix, "tocoo")          # any scipy.sparse matrix
-        if sparse:
+        if sparse and hasattr(matrix, "tocoo"):    # any scipy.sparse matrix
             matrix = matrix.tocoo()
         else:
             matrix = numpy.asarray(matrix)
-        if matrix.ndim != 2 or matrix.shape[0] != matrix.shape[1]:
-            raise ValueError("contact matrix must be square, got shape %r" % (matrix.shape,))
-        n = matrix.shape[0]
-        return self._fit_impl(matrix, n, init, None, None)
+        return matrix, _square_bins(matrix.shape)
+
+    def _default_start(self, n):
+        return numpy.random.default_rng(self.seed).standard_normal((n, 3))
+
+    def _bin_sums(self, eng, world):
+        """What the per-bin steps of SPEC 2.4.1 are made from, summed over the ranks: the
+        weighted degrees (weight_power, which is switched on here), the degrees
+        (degree_steps), or None for the one step of SPEC 2.4."""
+        if self.weight_power:
+            eng.set_weight_power(self.weight_power)
+            return _sum_over_ranks(eng.weight_sums(), eng, world)
+        if self.degree_steps:
+            return _sum_over_ranks(eng.degrees(), eng, world)
+        return None
+
+    def _steps(self, sums, n):
+        """(lr, scale) for one map of n bins from its slice of `_bin_sums`: `weighted_steps`
+        or `degree_step_factors`, a float `lr` being the step of the best-connected bin."""
+        if self.weight_power:
+            return weighted_steps(sums, n, self.dtype, self.lr, self.degree_steps)
+        lr, scale = degree_step_factors(sums)
+        return (lr if self.lr == "auto" else float(self.lr)), scale
+
+    def _iterate(self, step, history, converged):
+        """`n_iter` iterations through step(k).  With `tol` (early stop) they go in chunks
+        of `check_every`: after each the stress history is read back (one sync) and the
+        loop ends once converged(history()).  Every rank sees the same all-reduced stress,
+        so all ranks stop at the same iteration."""
+        if self.tol is None:
+            step(self.n_iter)
+            return
+        done = 0
+        while done < self.n_iter:
+            k = min(self.check_every, self.n_iter - done)
+            step(k)
+            done += k
+            if converged(history()):
+                break
+
+    def _params(self):
+        """Every argument of the constructor as this solver holds it now."""
+        import inspect
+        p = {k: getattr(self, k) for k in inspect.signature(type(self).__init__).parameters
+             if k not in ("self", "engine")}
+        p["engine"] = None if self._engine_factory is HipEngine else self._engine_factory
+        if self._group is not None:
+            p["device"] = None                     # (set from a one-entry devices=)
+        return p
+
+    def _clone(self, **overrides):
+        """A solver with this one's parameters, but for `overrides`."""
+        return type(self)(**dict(self._params(), **overrides))
 
     def _fit_impl(self, matrix, n, init, KRnorm, KRexpected):
         resident = getattr(matrix, "is_resident", False)
@@ -1080,7 +1126,7 @@ class StructureSolver(object):
         rank, world = (0, 1) if devices else _dist_state(self.distributed)
         lr = 1.0 / (2.0 * n) if self.lr == "auto" else float(self.lr)
         if init is None and self.init == "random":
-            init = numpy.random.default_rng(self.seed).standard_normal((n, 3))
+            init = self._default_start(n)
 
         tiles = None
         if sparse:
@@ -1095,33 +1141,18 @@ class StructureSolver(object):
         else:
             eng = self._engine_factory(n, self.dtype, rank=rank, world=world,
                                        device=self._pick_device(world), tiles=tiles)
-        try:
-            if resident and hasattr(eng, "set_wish_resident"):
+        with _teardown(eng):
+            if resident:
                 eng.set_wish_resident(matrix, self.kind, self.alpha)
-            elif resident:
-                dev = matrix._resident()
-                if dev.device == eng.device:
-                    eng.set_wish_from_cm(dev, self.kind, self.alpha)
-                else:
-                    # the map lives on another GPU than this rank's solver (a ContactMap made
-                    # with an explicit device): through the host once, like a plain matrix
-                    eng.set_wish_dense(matrix.to_host(), self.kind, self.alpha)
             elif triples:
                 eng.set_wish_triples(matrix, self.kind, self.alpha, KRnorm, KRexpected)
             elif sparse:
                 eng.set_wish_sparse(rows, cols, vals, self.kind, self.alpha, KRnorm, KRexpected)
             else:
                 eng.set_wish_dense(matrix, self.kind, self.alpha)
-            if self.weight_power:
-                eng.set_weight_power(self.weight_power)
-                lr, scale = weighted_steps(_sum_over_ranks(eng.weight_sums(), eng, world), n,
-                                           self.dtype, self.lr, self.degree_steps)
-                if scale is not None:
-                    eng.set_bin_steps(scale)
-            elif self.degree_steps:
-                lr_top, scale = degree_step_factors(_sum_over_ranks(eng.degrees(), eng, world))
-                if self.lr == "auto":
-                    lr = lr_top
+            sums = self._bin_sums(eng, world)
+            if sums is not None:
+                lr, scale = self._steps(sums, n)
                 if scale is not None:
                     eng.set_bin_steps(scale)
             on_device = False
@@ -1133,12 +1164,12 @@ class StructureSolver(object):
                 # take -- fewer than 4 bins (centring leaves at most 2 directions), an empty
                 # or unconstrained map -- and transports that sum on the host (gloo, torch)
                 # go through the host-driven form below, so the same input runs everywhere.
-                v0 = numpy.random.default_rng(self.seed).standard_normal((n, 3))
+                v0 = self._default_start(n)
                 if world > 1:
                     eng.set_coords(v0)             # (a trial in select_exchange wants a start)
                     select_exchange(eng, lr)
                 device_form = hasattr(eng, "spectral_init_device") and n >= 4 and (
-                    world == 1 or getattr(eng, "_comm_state", None) in ("peer", "rccl"))
+                    world == 1 or _exchange_state(eng) in ("peer", "rccl"))
                 if device_form:
                     try:
                         info = eng.spectral_init_device(self.spectral_iter, v0, tol=self.spectral_tol)
@@ -1147,7 +1178,7 @@ class StructureSolver(object):
                     except RankDeficient:
                         pass
                     if world > 1:
-                        if getattr(eng, "_comm_state", None) == "peer":
+                        if _exchange_state(eng) == "peer":
                             eng.peer_status()
                         on_device = _all_ranks(on_device)
             if not on_device:
@@ -1160,39 +1191,15 @@ class StructureSolver(object):
                 eng.set_momentum(self.momentum)
             if world > 1:
                 select_exchange(eng, lr)
-            if self.tol is None:
-                run_iterations(eng, self.n_iter, lr, world)
-            else:
-                # early stop: every `check_every` steps the stress history is read
-                # back (one sync) and the loop ends once the relative decrease per
-                # step falls below tol.  Every rank sees the same all-reduced
-                # stress, so all ranks stop at the same iteration.
-                done = 0
-                while done < self.n_iter:
-                    k = min(self.check_every, self.n_iter - done)
-                    run_iterations(eng, k, lr, world)
-                    done += k
-                    h = eng.stress_history()
-                    if h.size >= 2 and h[-2] > 0 and \
-                            abs(h[-2] - h[-1]) <= self.tol * h[-2]:
-                        break
-            if getattr(eng, "_comm_state", None) == "peer":
+            # converged: the relative decrease of the last step is <= tol (never at stress 0)
+            self._iterate(lambda k: run_iterations(eng, k, lr, world), eng.stress_history,
+                          lambda h: h.size >= 2 and h[-2] > 0
+                          and abs(h[-2] - h[-1]) <= self.tol * h[-2])
+            if _exchange_state(eng) == "peer":
                 eng.peer_status()              # raises if a peer wait ran into its time limit
-            self.exchange_ = getattr(eng, "_comm_state", None)
+            self.exchange_ = _exchange_state(eng)
             self.structure_ = eng.get_coords()
             self.stress_ = eng.stress_history()
-        except BaseException:
-            # this rank leaves a multi-rank job in the middle: its peers may sit in a collective
-            # on the library's communicator, which must then not go back into the cache for the
-            # next fit() to borrow (close() would return it as free)
-            if getattr(eng, "_comm_state", None) == "rccl" and hasattr(eng, "comm_abort"):
-                try:
-                    eng.comm_abort()
-                except Exception:                  # noqa: BLE001 -- the first error is the one to report
-                    pass
-            raise
-        finally:
-            eng.close()
         self.devices_ = devices
         self.n_bins_, self.lr_, self.n_iter_ = n, lr, int(self.stress_.shape[0])
         return self
@@ -1300,7 +1307,7 @@ class StructureSolver(object):
             # own (dealt by size, largest first, to the rank with the least pairs so far) and
             # the results are gathered -- no exchange during the iterations at all.
             import torch.distributed as dist
-            sizes = [int(getattr(X, "shape", numpy.shape(getattr(X, "matrix", X)))[0]) for X in maps]
+            sizes = [self._map_source(X, sparse=False)[1] for X in maps]
             load, mine = [0] * world, [[] for _ in range(world)]
             for m in sorted(range(len(maps)), key=lambda q: (-sizes[q], q)):
                 r = min(range(world), key=lambda q: (load[q], q))
@@ -1308,15 +1315,8 @@ class StructureSolver(object):
                 mine[r].append(m)
             part = None
             if mine[rank]:
-                local = StructureSolver(n_iter=self.n_iter, lr=self.lr, dtype=self.dtype,
-                                        alpha=self.alpha, kind=self.kind, seed=self.seed,
-                                        device=self._pick_device(world), distributed=False,
-                                        engine=self._engine_factory, momentum=self.momentum,
-                                        init=self.init, tol=self.tol, check_every=self.check_every,
-                                        spectral_iter=self.spectral_iter,
-                                        spectral_tol=self.spectral_tol,
-                                        degree_steps=self.degree_steps,
-                                        weight_power=self.weight_power)
+                local = self._clone(device=self._pick_device(world), distributed=False,
+                                    devices=None, n_gpus=None)
                 local._fit_many_local([maps[m] for m in mine[rank]], [inits[m] for m in mine[rank]])
                 part = (mine[rank], local.structures_, local.stresses_, local.lrs_)
             parts = [None] * world
@@ -1335,17 +1335,8 @@ class StructureSolver(object):
 
     def _fit_many_local(self, maps, inits):
         """fit_many on this rank's GPU (see fit_many)."""
-        sizes, srcs = [], []
-        for X in maps:
-            if getattr(X, "is_resident", False):
-                sizes.append(int(X.shape[0]))
-                srcs.append(X)
-            else:
-                m = numpy.asarray(getattr(X, "matrix", X))
-                if m.ndim != 2 or m.shape[0] != m.shape[1]:
-                    raise ValueError("contact matrix must be square, got shape %r" % (m.shape,))
-                sizes.append(int(m.shape[0]))
-                srcs.append(m)
+        pairs = [self._map_source(X, sparse=False) for X in maps]
+        srcs, sizes = [src for src, _ in pairs], [n for _, n in pairs]
         if min(sizes) < 2:
             raise ValueError("every map needs at least 2 bins")
         # the tile edge of the joint layout: 128 only for a small fp64 problem
@@ -1374,19 +1365,16 @@ class StructureSolver(object):
         for m, (o, n) in enumerate(zip(off, sizes)):
             init = inits[m]
             if init is None and self.init == "spectral":
-                # each map's classical-MDS start from a solver of its own (device form)
-                one = StructureSolver(n_iter=0, lr=self.lr, dtype=self.dtype, alpha=self.alpha,
-                                      kind=self.kind, seed=self.seed, device=device,
-                                      distributed=False, init="spectral",
-                                      spectral_iter=self.spectral_iter,
-                                      spectral_tol=self.spectral_tol,
-                                      engine=self._engine_factory).fit(maps[m])
-                init = one.structure_
+                # each map's classical-MDS start from a solver of its own (device form), which
+                # only makes the start: unweighted, one step for all, no iterations
+                init = self._clone(n_iter=0, init="spectral", device=device, distributed=False,
+                                   devices=None, n_gpus=None, degree_steps=False, weight_power=0,
+                                   momentum=0.0, tol=None).fit(maps[m]).structure_
             elif init is None:
-                init = numpy.random.default_rng(self.seed).standard_normal((n, 3))
+                init = self._default_start(n)
             x0[o:o + n] = _check_coords(init, n)
         eng = self._engine_factory(total, self.dtype, rank=0, world=1, device=device, tiles=tiles)
-        try:
+        with _teardown(eng):
             eng.set_maps(off + [total], lrs)
             for o, n, src in zip(off, sizes, srcs):
                 if getattr(src, "is_resident", False) and src._resident().device == eng.device:
@@ -1394,49 +1382,34 @@ class StructureSolver(object):
                 else:
                     m = src.to_host() if getattr(src, "is_resident", False) else src
                     eng.set_wish_dense_block(m, o, self.kind, self.alpha)
-            if self.weight_power:
-                # SPEC 2.3.1 / 2.4.1 per map, from the weighted degrees: lr='auto' is each
-                # map's 1 / (2 max s), degree_steps each bin's 1 / (2 s_i) (lr = 1 below)
-                eng.set_weight_power(self.weight_power)
-                ws = eng.weight_sums()
+            sums = self._bin_sums(eng, 1)
+            if sums is not None:
+                # SPEC 2.3.1 / 2.4.1 per map: every bin's whole step goes into `steps`
+                # (lr = 1 below), each map's `lr` -- 'auto' or a float -- being the step of its
+                # best-connected bin
                 steps = numpy.ones(total)
                 for q, (o, n) in enumerate(zip(off, sizes)):
-                    top, scale = weighted_steps(ws[o:o + n], n, self.dtype, self.lr,
-                                                self.degree_steps)
-                    steps[o:o + n] = top if scale is None else top * scale
-                    lrs[q] = top
-                eng.set_bin_steps(steps)
-            elif self.degree_steps:
-                # SPEC 2.4.1 per map: bin i steps by 1 / (2 (deg_i + 1)) (lr = 1 below); a float
-                # `lr` stays the step of each map's best-connected bin
-                deg = eng.degrees()
-                steps = numpy.ones(total)
-                for q, (o, n) in enumerate(zip(off, sizes)):
-                    d = deg[o:o + n]
-                    top = 1.0 / (2.0 * (d.max() + 1.0)) if self.lr == "auto" else float(self.lr)
-                    steps[o:o + n] = top * (d.max() + 1.0) / (d + 1.0)
-                    lrs[q] = top
+                    part = sums[o:o + n]
+                    lrs[q], scale = self._steps(part, n)
+                    if self.weight_power:
+                        steps[o:o + n] = lrs[q] if scale is None else lrs[q] * scale
+                    else:
+                        # multiplied before it is divided: not the bits of lr * scale, the
+                        # factors fit() hands to set_bin_steps (`degree_step_factors`)
+                        steps[o:o + n] = lrs[q] * (part.max() + 1.0) / (part + 1.0)
                 eng.set_bin_steps(steps)
             eng.set_coords(x0)
             if self.momentum:
                 eng.set_momentum(self.momentum)
             nm = len(sizes)
-            if self.tol is None:
-                eng.iterate(self.n_iter, 1.0)
-            else:
-                done = 0
-                while done < self.n_iter:
-                    k = min(self.check_every, self.n_iter - done)
-                    eng.iterate(k, 1.0)
-                    done += k
-                    h = eng.stress_history().reshape(-1, nm)
-                    if h.shape[0] >= 2 and numpy.all(
-                            numpy.abs(h[-2] - h[-1]) <= self.tol * numpy.maximum(h[-2], 1e-300)):
-                        break
+            # converged: every map's last step decreased its stress by <= tol, relatively (a
+            # map at stress 0 counts as converged, which the single fit() never stops on)
+            self._iterate(lambda k: eng.iterate(k, 1.0),
+                          lambda: eng.stress_history().reshape(-1, nm),
+                          lambda h: h.shape[0] >= 2 and numpy.all(
+                              numpy.abs(h[-2] - h[-1]) <= self.tol * numpy.maximum(h[-2], 1e-300)))
             X = eng.get_coords()
             hist = eng.stress_history().reshape(-1, nm)
-        finally:
-            eng.close()
         self.structures_ = [X[o:o + n].copy() for o, n in zip(off, sizes)]
         self.stresses_ = [hist[:, m].copy() for m in range(nm)]
         self.n_bins_many_, self.lrs_, self.n_iter_ = sizes, lrs, int(hist.shape[0])
@@ -1462,17 +1435,7 @@ def spectral_init(eng, n, world, n_iter=40, seed=0, tol=0.0, return_iterations=F
     (`blueberry/datatypes.pyx:216-235`)."""
     def apply_B(V):
         U = V - V.mean(axis=0)
-        W = eng.matvec_sq(U)
-        if world > 1:
-            import torch
-            import torch.distributed as dist
-            t = torch.from_numpy(W)
-            if dist.get_backend() == "nccl":
-                t = t.to(torch.device("cuda", getattr(eng, "device", 0)))
-                dist.all_reduce(t)
-                W = t.cpu().numpy()
-            else:
-                dist.all_reduce(t)
+        W = _sum_over_ranks(eng.matvec_sq(U), eng, world)
         return -0.5 * (W - W.mean(axis=0))
 
     def orth(A):
@@ -1610,6 +1573,12 @@ def _comm_get(eng):
     return eng.comm_setup()
 
 
+def _exchange_state(eng):
+    """The transport `select_exchange` chose for this engine ('group' for a GroupEngine), or
+    None: nothing chosen yet, or an engine that never sums over ranks."""
+    return getattr(eng, "_comm_state", None)
+
+
 def select_exchange(eng, lr, trial=False):
     """Decide, once per engine and identically on every rank, how the partial
     gradients are summed over the ranks.  Collective.
@@ -1621,126 +1590,142 @@ def select_exchange(eng, lr, trial=False):
       host   exchange buffer staged through host memory (gloo / CPU rehearsals)
     auto on an RCCL job means rccl (torch if the communicator cannot be made).  With
     `trial` true -- bench.py, or BB_COMM_TRIAL=1 -- and the coordinates just set, auto
-    also sets up peer and runs a few iterations through both from the same start:
-    peer is taken only if its coordinates agree with RCCL's and it is faster on the
-    slowest rank; the start is restored afterwards.  Every stage of the trial ends
-    with an agreement between the ranks (`_trial_leg`), and the peer waits are cut
-    to 2 s while it runs, so a transport that fails on one rank is dropped by all of
-    them instead of leaving the others inside a collective.  The outcome is kept in
-    eng._comm_state / eng._comm_trial."""
-    if getattr(eng, "_comm_state", None):
+    also sets up peer and runs a few iterations through both from the same start
+    (`_exchange_trial`).  The outcome is kept in eng._comm_state / eng._comm_trial."""
+    if _exchange_state(eng):
         return eng._comm_state
-    import torch.distributed as dist
     want = os.environ.get("BB_COMM", "auto")
     if want not in ("auto", "peer", "rccl", "torch", "host"):
         raise ValueError("BB_COMM must be auto, peer, rccl, torch or host, not %r" % want)
     trial = bool(trial) or os.environ.get("BB_COMM_TRIAL") == "1"
+    state = _exchange_untried(eng, want, trial)
+    if state is None:
+        have_rccl = _comm_get(eng)
+        if eng.peer_setup() and (have_rccl or hasattr(eng, "exchange_tensor")):
+            state = _exchange_trial(eng, lr, have_rccl)
+        else:
+            state = "rccl" if have_rccl else "torch"
+    eng._comm_state = state
+    return state
+
+
+def _exchange_untried(eng, want, trial):
+    """The transport where no trial decides it, or None where one does (auto on an RCCL job
+    with `trial`)."""
+    import torch.distributed as dist
     native = hasattr(eng, "peer_setup")
     nccl = dist.get_backend() == "nccl"
-    state = None
     if not native or want == "host" or (not nccl and want != "peer"):
-        state = "host"
-    elif want == "peer":
+        return "host"
+    if want == "peer":
         if not eng.peer_setup():
             raise RuntimeError("BB_COMM=peer but the peer exchange could not be set up: %s"
                                % eng._peer_error)
         # No trial has compared this exchange with RCCL: keep the two-launch form, which
         # applies a step whole or not at all and whose flags are ordered by release / acquire.
         # The one-launch form (data as its own flag, no fences) is taken where a trial has
-        # validated it against RCCL on this very job (below), or on request (BB_PEER_FUSED=1).
+        # validated it against RCCL on this very job, or on request (BB_PEER_FUSED=1).
         if not trial and os.environ.get("BB_PEER_FUSED") is None and hasattr(eng, "peer_set_form"):
             eng.peer_set_form(False)
-        state = "peer"
-    elif want == "torch":
-        state = "torch"
-    elif want == "rccl" or not trial:
-        state = "rccl" if _comm_get(eng) else "torch"
-    else:
-        have_rccl = _comm_get(eng)
-        have_peer = eng.peer_setup()
-        # what the peer exchange is held against, and what runs if it loses: the library's
-        # communicator, or -- when that could not be made -- torch.distributed's all-reduce on
-        # the exchange buffer (round 3 gave the peer exchange up with it: no RCCL, no trial)
-        ref = "rccl" if have_rccl else "torch"
+        return "peer"
+    if want == "torch":
+        return "torch"
+    if want == "rccl" or not trial:
+        return "rccl" if _comm_get(eng) else "torch"
+    return None
 
-        def torch_step(k, step_lr):
-            t = eng.exchange_tensor()
-            for _ in range(k):
-                eng.grad()
-                allreduce_exchange(t)
-                eng.apply(step_lr)
 
-        ref_step = eng.iterate_dist if have_rccl else torch_step
-        if have_peer and (have_rccl or hasattr(eng, "exchange_tensor")):
-            x0 = eng.get_coords()
-            set_limit = getattr(eng, "peer_set_timeout", None)
-            if set_limit:
-                set_limit(_TRIAL_PEER_TIMEOUT_MS)
-            runs = {}
+def _exchange_trial(eng, lr, have_rccl):
+    """Run the peer exchange against a reference from the same start and return the one to
+    use: peer only if its coordinates agree with the reference's and it is faster on the
+    slowest rank; the start is restored afterwards.  The reference, which also runs if peer
+    loses, is the library's communicator or -- when that could not be made --
+    torch.distributed's all-reduce on the exchange buffer.  Every stage ends with an
+    agreement between the ranks (`_trial_leg`), and the peer waits are cut to 2 s while it
+    runs, so a transport that fails on one rank is dropped by all of them instead of leaving
+    the others inside a collective.  Collective; the figures go to eng._comm_trial."""
+    import torch.distributed as dist
+    ref = "rccl" if have_rccl else "torch"
+    ref_step = _stepper(eng, ref)
+    x0 = eng.get_coords()
+    set_limit = getattr(eng, "peer_set_timeout", None)
+    if set_limit:
+        set_limit(_TRIAL_PEER_TIMEOUT_MS)
+    eng._comm_trial_error = None
 
-            def abort_if_failed(name):
-                if name == "rccl" and not runs[name][0] and hasattr(eng, "comm_abort"):
-                    # the library's communicator is suspect (this rank may still sit in a
-                    # collective a peer never joined): abort it -- every rank does,
-                    # the leg's outcome is shared -- so that the stream drains again
-                    try:
-                        eng.comm_abort()
-                    except Exception as exc:
-                        eng._comm_trial_error = "%s; abort: %s" % (
-                            getattr(eng, "_comm_trial_error", None), exc)
+    def reference_leg():
+        run = _trial_leg(eng, ref, ref_step, lr, x0, 30)
+        if have_rccl and not run[0] and hasattr(eng, "comm_abort"):
+            # the library's communicator is suspect (this rank may still sit in a
+            # collective a peer never joined): abort it -- every rank does,
+            # the leg's outcome is shared -- so that the stream drains again
+            try:
+                eng.comm_abort()
+            except Exception as exc:
+                eng._comm_trial_error = "%s; abort: %s" % (eng._comm_trial_error, exc)
+        return run
 
-            for name, step in ((ref, ref_step), ("peer", eng.iterate_peer)):
-                runs[name] = _trial_leg(eng, name, step, lr, x0, 30)
-                abort_if_failed(name)
-            runs["rccl"] = runs[ref]            # (the reference leg, whichever transport it is)
-            if runs["rccl"][0] and runs["peer"][0]:
-                # the leg that runs first is timed on a chip whose clocks have not settled
-                # (a block right after idle runs 4-19 % slow, DESIGN.md 5): RCCL gets a
-                # second timing behind the peer leg and keeps its better one.  (Leg outcomes
-                # are agreed between the ranks, so every rank takes this branch or none.)
-                again = _trial_leg(eng, ref, ref_step, lr, x0, 30)
-                if again[0]:
-                    runs["rccl"] = (True, runs["rccl"][1], min(runs["rccl"][2], again[2]))
-                else:
-                    runs["rccl"] = runs[ref] = (False, None, float("inf"))
-                    abort_if_failed(ref)
-            if set_limit and runs["peer"][0]:
-                set_limit(int(os.environ.get("BB_PEER_TIMEOUT_MS", "10000")))
-            eng.set_coords(x0)
-            scale = float(numpy.abs(x0).max() + 1e-30)
-            # one step: 1e-4 (the transports add the ranks' partials in different orders); the
-            # whole leg, 41 steps: 1e-3 -- far above what the order of a sum does over that
-            # many steps in fp32 (1e-5), far below what a lost or torn partial does
-            agree = bool(runs["rccl"][0] and runs["peer"][0]
-                         and numpy.allclose(runs["rccl"][1][0], runs["peer"][1][0], rtol=1e-4,
-                                            atol=1e-6 * scale)
-                         and numpy.allclose(runs["rccl"][1][1], runs["peer"][1][1], rtol=1e-3,
-                                            atol=1e-5 * scale))
-            mine = (agree, runs["rccl"][2], runs["peer"][2])
-            every = [None] * eng.world
-            dist.all_gather_object(every, mine)
-            t_rccl = max(e[1] for e in every)
-            t_peer = max(e[2] for e in every)
-            # the library communicator is the plain path: the peer exchange has to win by
-            # more than the trial's own noise (3 %), not by a coin flip
-            use_peer = all(e[0] for e in every) and t_peer < 0.97 * t_rccl
-            ms = lambda t: t * 1e3 if numpy.isfinite(t) else None
-            eng._comm_trial = {"agree": all(e[0] for e in every), "reference": ref,
-                               "rccl_ms": ms(t_rccl),      # (the reference leg's time)
-                               "peer_ms": ms(t_peer),
-                               "error": getattr(eng, "_comm_trial_error", None)}
-            if use_peer:
-                state = "peer"
-            elif runs["rccl"][0]:
-                state = ref
-            else:
-                state = "torch"
-        elif have_rccl:
-            state = "rccl"
+    runs = {"reference": reference_leg()}
+    runs["peer"] = _trial_leg(eng, "peer", eng.iterate_peer, lr, x0, 30)
+    if runs["reference"][0] and runs["peer"][0]:
+        # the leg that runs first is timed on a chip whose clocks have not settled
+        # (a block right after idle runs 4-19 % slow, DESIGN.md 5): the reference gets a
+        # second timing behind the peer leg and keeps its better one.  (Leg outcomes
+        # are agreed between the ranks, so every rank takes this branch or none.)
+        again = reference_leg()
+        if again[0]:
+            runs["reference"] = (True, runs["reference"][1], min(runs["reference"][2], again[2]))
         else:
-            state = "torch"
-    eng._comm_state = state
-    return state
+            runs["reference"] = again
+    if set_limit and runs["peer"][0]:
+        set_limit(int(os.environ.get("BB_PEER_TIMEOUT_MS", "10000")))
+    eng.set_coords(x0)
+    scale = float(numpy.abs(x0).max() + 1e-30)
+    # one step: 1e-4 (the transports add the ranks' partials in different orders); the
+    # whole leg, 41 steps: 1e-3 -- far above what the order of a sum does over that
+    # many steps in fp32 (1e-5), far below what a lost or torn partial does
+    agree = bool(runs["reference"][0] and runs["peer"][0]
+                 and numpy.allclose(runs["reference"][1][0], runs["peer"][1][0], rtol=1e-4,
+                                    atol=1e-6 * scale)
+                 and numpy.allclose(runs["reference"][1][1], runs["peer"][1][1], rtol=1e-3,
+                                    atol=1e-5 * scale))
+    mine = (agree, runs["reference"][2], runs["peer"][2])
+    every = [None] * eng.world
+    dist.all_gather_object(every, mine)
+    t_ref = max(e[1] for e in every)
+    t_peer = max(e[2] for e in every)
+    # the reference is the plain path: the peer exchange has to win by more than the
+    # trial's own noise (3 %), not by a coin flip
+    use_peer = all(e[0] for e in every) and t_peer < 0.97 * t_ref
+    ms = lambda t: t * 1e3 if numpy.isfinite(t) else None
+    eng._comm_trial = {"agree": all(e[0] for e in every), "reference": ref,
+                       "rccl_ms": ms(t_ref),      # (the reference leg's time)
+                       "peer_ms": ms(t_peer),
+                       "error": eng._comm_trial_error}
+    if use_peer:
+        return "peer"
+    return ref if runs["reference"][0] else "torch"
+
+
+def _stepper(eng, state):
+    """The callable (k, lr) that runs k iterations of `eng` with the transport `state`
+    summing the ranks' partial gradients."""
+    if state == "peer":
+        return eng.iterate_peer
+    if state == "rccl":
+        return eng.iterate_dist
+
+    def step(k, lr):
+        # per iteration: local partial gradient -> sum over ranks -> identical update
+        t = eng.exchange_tensor() if state == "torch" else None
+        for _ in range(k):
+            eng.grad()
+            if t is None:
+                allreduce_exchange_host(eng)
+            else:
+                allreduce_exchange(t)
+            eng.apply(lr)
+    return step
 
 
 def run_iterations(eng, n_iter, lr, world):
@@ -1752,20 +1737,5 @@ def run_iterations(eng, n_iter, lr, world):
     transport."""
     if world == 1:
         eng.iterate(n_iter, lr)
-        return
-    state = select_exchange(eng, lr)
-    if state == "peer":
-        eng.iterate_peer(n_iter, lr)
-    elif state == "rccl":
-        eng.iterate_dist(n_iter, lr)
-    elif state == "torch":
-        t = eng.exchange_tensor()
-        for _ in range(n_iter):
-            eng.grad()
-            allreduce_exchange(t)
-            eng.apply(lr)
     else:
-        for _ in range(n_iter):
-            eng.grad()
-            allreduce_exchange_host(eng)
-            eng.apply(lr)
+        _stepper(eng, select_exchange(eng, lr))(n_iter, lr)

@@ -291,6 +291,58 @@ def test_fit_many_host_logic_with_the_oracle_engine(oracle, dtype):
         bb.StructureSolver(engine=OracleEngine, distributed=False).fit_many([numpy.zeros((1, 1))])
 
 
+def test_clone_carries_every_constructor_argument():
+    """fit_many makes its per-rank and per-map solvers with `_clone`: an argument the
+    constructor takes and `_params` does not carry would silently fall back to its default."""
+    import inspect
+    from tests._engines import OracleEngine
+    given = dict(n_iter=7, lr=0.25, dtype="float64", alpha=2.5, kind="wish", seed=11, device=3,
+                 distributed=False, engine=OracleEngine, momentum=0.4, init="spectral", tol=1e-4,
+                 check_every=3, spectral_iter=17, spectral_tol=0.01, degree_steps=True,
+                 weight_power=2, devices=None, n_gpus=None)
+    names = [k for k in inspect.signature(bb.StructureSolver.__init__).parameters if k != "self"]
+    assert sorted(given) == sorted(names)             # a new argument belongs in `given` too
+    defaults = bb.StructureSolver()._params()
+    assert all(given[k] != defaults[k] for k in names if k not in ("devices", "n_gpus"))
+    # (device and engine do not go with devices= / n_gpus=)
+    for several in (dict(), dict(device=None, engine=None, devices=[2, 0]),
+                    dict(device=None, engine=None, n_gpus=1)):
+        args = dict(given, **several)
+        s = bb.StructureSolver(**args)
+        assert s._params() == args
+        c = s._clone()
+        assert c is not s and c._params() == args and c._group == s._group
+        assert c._engine_factory is s._engine_factory and c.device == s.device
+        assert s._clone(n_iter=0, seed=1)._params() == dict(args, n_iter=0, seed=1)
+
+
+def test_fit_many_deal_reads_only_the_shape_of_a_resident_map(monkeypatch):
+    """Several ranks: the maps are dealt by size, and a map that lives in HBM has a shape --
+    its `matrix` (a download of the whole map on every rank) is never asked for."""
+    from blueberry_amd import solver
+
+    class Reached(Exception):
+        pass
+
+    class ResidentMap(object):
+        is_resident, shape = True, (700, 700)
+
+        @property
+        def matrix(self):
+            raise AssertionError("the deal downloaded a resident map")
+
+    class Engine(object):
+        set_maps = set_wish_from_cm = None            # what fit_many and residency ask of an engine
+
+        def __init__(self, n_bins, dtype, **kwargs):
+            raise Reached(n_bins)
+
+    monkeypatch.setattr(solver, "_dist_state", lambda distributed: (0, 2))
+    with pytest.raises(Reached) as info:
+        bb.StructureSolver(engine=Engine).fit_many([ResidentMap()])
+    assert info.value.args == (700,)
+
+
 def test_count_band_regions_input_checks():
     with pytest.raises(ValueError):
         bb.band._as_regions(numpy.zeros((2, 2)))
