@@ -19,23 +19,9 @@
 #include <mutex>
 #include <vector>
 
+#include "bb_cm_internal.h"
 #include "bb_common.h"
 #include <cstdlib>
-
-struct bb_cm {
-    int device = 0;
-    int64_t d = 0;            // current edge (shrinks in filter)
-    double *m = nullptr;      // (d, d) row-major, resident
-    hipStream_t stream = nullptr;
-    // grow-only scratch of the symmetric matrix-vector product (symv_upper_kernel): the work
-    // list and the row / column partial sums; made by the first product, kept with the handle
-    void *sv_buf = nullptr;
-    size_t sv_bytes = 0;
-    int64_t sv_d = -1;        // the edge the work list was built for
-    int sv_items = 0;
-    // scratch of bb_cm_correlation (centred rows + Gram matrix), kept between calls: the
-    // first touch of a fresh matrix-sized allocation costs 0.2-0.35 s on this platform
-};
 
 namespace {
 
@@ -888,16 +874,15 @@ __global__ __launch_bounds__(256) void scale_by_kernel(const double *__restrict_
     if (i < d) out[i] = scale[0] * in[i];
 }
 
+}  // namespace
+
 // correlation's two matrix-sized temporaries (centred rows, Gram matrix): ONE grow-only
 // allocation per DEVICE, shared by every map on it and guarded by a mutex (calls on one device
 // serialise, as bb_band.hip's context does).  Round 3 kept one per HANDLE for the map's
 // lifetime: a genome-wide loop holding one ContactMap per chromosome then held 3x the
-// matrices' memory.  bb_cm_release_scratch gives it back.
-struct CorrScratch {
-    std::mutex mu;
-    void *buf = nullptr;
-    size_t bytes = 0;
-};
+// matrices' memory.  bb_cm_release_scratch gives it back.  bb_cm_shortest_paths
+// (bb_shortest.hip) takes its work matrix from the same scratch (bb_cm_internal.h).
+namespace bb {
 CorrScratch *corr_scratch(int device) {
     static std::mutex table_mu;
     static std::map<int, CorrScratch *> table;
@@ -908,7 +893,9 @@ CorrScratch *corr_scratch(int device) {
     table[device] = c;
     return c;
 }
-}  // namespace
+}  // namespace bb
+using bb::corr_scratch;
+using bb::CorrScratch;
 
 extern "C" {
 

@@ -460,6 +460,36 @@ class ContactMap(object):
         _lib.check(dev._lib.bb_cm_correlation(dev._h, tf), "bb_cm_correlation")
         self.correlation_tflops_ = float(tf.value)
 
+    def shortest_paths(self, alpha=3.0, kind="counts"):
+        """Complete the map by graph shortest paths (docs/SPEC.md 2.1.1; ShRec3D, Isomap): a
+        NEW ContactMap (same celltype, chromosome, resolution, regions, n_bins; no KR vectors)
+        whose resident matrix is G, G_ij = the length of the shortest chain of wish distances
+        between bins i and j -- `count ** (-1 / alpha)` of every finite positive count for
+        kind='counts', the entries themselves for kind='wish' -- with a 0 diagonal and 0 ("no
+        constraint") where no chain exists (dead bins, separate components);
+        `unreachable_pairs_` counts those pairs.  G is a kind='wish' input for
+        `StructureSolver`.  A measured pair may get shorter: G is the metric closure.  Blocked
+        Floyd-Warshall on the device in float64 (`bb_cm_shortest_paths`), the same bits on
+        every run.  This map is left as it is and stays resident.
+
+        The work matrix is a second matrix-sized allocation (5 GB at chr1@10kb; freed by
+        `bb_cm_release_scratch`).  A whole-genome map that is only ever held blocked-sparse
+        (720 GB dense at 10 kb) cannot be completed this way: the allocation fails with
+        MemoryError."""
+        kind_code, alpha = _completion_arguments(kind, alpha)
+        if self.shape[0] == 0:
+            raise ValueError("the contact map is empty (every bin was filtered out)")
+        src = self._dev if self._dev is not None else self._resident()
+        out = ContactMap.__new__(ContactMap)
+        out.resolution, out.chromosome, out.celltype = self.resolution, self.chromosome, self.celltype
+        out.device, out.filename, out.n_bins = src.device, self.filename, self.n_bins
+        out.regions = None if self.regions is None else numpy.array(self.regions)
+        out._KRnorm = out._KRexpected = None
+        out._host = out._view = None
+        out._dev = _DeviceMatrix(src.d, src.device)
+        out.unreachable_pairs_ = _shortest_paths_device(src, out._dev, kind_code, alpha)
+        return out
+
     def plot(self, arcsinh=True, **kwargs):
         """Plot the contact map onto the current palette (pyx:190-214)."""
         import matplotlib.pyplot as plt
@@ -497,6 +527,72 @@ class ContactMap(object):
                 % (self.eigen_residual_, self.eigen_matvecs_, tol, self.eigenvalue_),
                 self.eigenvalue_, vec)
         return vec
+
+
+_COMPLETION_KINDS = {"wish": _lib.BB_KIND_WISH, "counts": _lib.BB_KIND_COUNTS}
+
+
+def _completion_arguments(kind, alpha):
+    """(kind code, alpha) of a shortest-path completion, checked without a device."""
+    if kind not in _COMPLETION_KINDS:
+        raise ValueError("kind must be 'counts' or 'wish'")
+    if not float(alpha) > 0:
+        raise ValueError("alpha must be positive")
+    return _COMPLETION_KINDS[kind], float(alpha)
+
+
+def _shortest_paths_device(src, dst, kind_code, alpha):
+    """`bb_cm_shortest_paths` from one _DeviceMatrix into another (or itself); returns the
+    number of unreachable pairs."""
+    n = _lib.c_i64()
+    _lib.check(src._lib.bb_cm_shortest_paths(src._h, dst._h, kind_code, alpha, n),
+               "bb_cm_shortest_paths")
+    return int(n.value)
+
+
+def _dense_from_any(X):
+    """A square float64 host matrix from an ndarray or a scipy.sparse matrix.  Sparse: either
+    triangle names a pair, of several entries for one pair the last is kept (as
+    `StructureSolver.fit` treats it), the diagonal is dropped, unnamed pairs are 0."""
+    if hasattr(X, "tocoo"):
+        coo = X.tocoo()
+        if coo.shape[0] != coo.shape[1]:
+            raise ValueError("contact matrix must be square, got shape %r" % (coo.shape,))
+        keep = coo.row != coo.col
+        r, c = coo.row[keep].astype(numpy.int64), coo.col[keep].astype(numpy.int64)
+        upper = numpy.zeros(coo.shape, dtype=numpy.float64)
+        _assign_last_wins(upper, numpy.minimum(r, c), numpy.maximum(r, c), coo.data[keep])
+        return upper + upper.T
+    m = numpy.ascontiguousarray(X, dtype=numpy.float64)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError("contact matrix must be square, got shape %r" % (m.shape,))
+    return m
+
+
+def complete_map(X, kind="counts", alpha=3.0, device=None):
+    """The shortest-path completion of `X` as a resident ContactMap (`ContactMap.
+    shortest_paths`): X a ContactMap (completed on its own device), a square ndarray or a
+    scipy.sparse matrix (uploaded to `device` and completed in place)."""
+    kind_code, alpha = _completion_arguments(kind, alpha)
+    if isinstance(X, ContactMap):
+        return X.shortest_paths(alpha=alpha, kind=kind)
+    m = _dense_from_any(X)
+    if m.shape[0] < 1:
+        raise ValueError("the contact matrix is empty")
+    out = ContactMap.from_matrix(m, device=device)
+    dev = out._resident()
+    out.unreachable_pairs_ = _shortest_paths_device(dev, dev, kind_code, alpha)
+    return out
+
+
+def shortest_paths(X, kind="counts", alpha=3.0, device=None):
+    """All-pairs shortest-path lengths G over the graph of `X`'s wish distances
+    (docs/SPEC.md 2.1.1), as a host ndarray: X a square ndarray, a ContactMap or a
+    scipy.sparse matrix (scattered to a dense matrix, last entry of a pair wins).  0 on the
+    diagonal and where no path exists.  Computed on the GPU (`bb_cm_shortest_paths`);
+    `device=None`: as `ContactMap` picks it.  The dense matrix and a work matrix of the same
+    size must fit on the device."""
+    return complete_map(X, kind=kind, alpha=alpha, device=device).to_host()
 
 
 DATA_DIR = RAO + ("results/Rao-Cell2014/fixedWindowSize/fithic/afterICE/{2}/"

@@ -876,6 +876,12 @@ def _check_devices(devices, n_gpus, device, distributed):
     return [int(d) for d in devices]
 
 
+def _check_complete(complete):
+    """The `complete=` argument of fit / fit_many / fit_triples, checked before any device call."""
+    if complete is not None and complete != "shortest_path":
+        raise ValueError("complete must be None or 'shortest_path', got %r" % (complete,))
+
+
 @contextlib.contextmanager
 def _teardown(eng):
     """Close the engine when the fit ends, however it ends."""
@@ -1039,13 +1045,46 @@ class StructureSolver(object):
             return int(self.device)
         return int(os.environ.get("LOCAL_RANK", "0")) if world > 1 else 0
 
-    def fit(self, X, init=None):
+    def fit(self, X, init=None, complete=None):
         """Solve for the structure of `X`: a ContactMap, a square ndarray, or a
         scipy.sparse matrix (symmetric; either triangle is enough; of several
         COO entries for one pair the last is kept) -- the sparse form never builds
-        the dense matrix."""
-        source, n = self._map_source(X)
-        return self._fit_impl(source, n, init, None, None)
+        the dense matrix.
+
+        complete : None or 'shortest_path'
+            None: pairs without a contact are no constraint (SPEC 2.1).  'shortest_path': the
+            map is first completed on the device by graph shortest paths over its wish
+            distances (SPEC 2.1.1, `ContactMap.shortest_paths` with this solver's `kind` and
+            `alpha`) -- what a real Hi-C map, with counts only between nearby bins, needs for
+            its global fold to be determined -- and the fit is that of
+            `StructureSolver(kind='wish', ...).fit(completed)`, dense tiles, bit for bit.
+            `completed_unreachable_pairs_` tells how many pairs stayed without a path.  With
+            `devices=[...]` the completion runs once on devices[0]; inside a torch.distributed
+            job every rank completes the same input on its own GPU.  The dense matrix and a
+            work matrix of its size must fit on one device: a whole-genome blocked-sparse map
+            (720 GB dense at 10 kb) cannot be completed this way (MemoryError)."""
+        _check_complete(complete)
+        if complete is None:
+            source, n = self._map_source(X)
+            return self._fit_impl(source, n, init, None, None)
+        cm = self._completed(X)
+        self.completed_unreachable_pairs_ = cm.unreachable_pairs_
+        source, n = self._map_source(cm)
+        return self._fit_impl(source, n, init, None, None, kind="wish")
+
+    def _completion_device(self):
+        """Where a fit's completion runs: devices[0] of a group, else this rank's device."""
+        devices = self._group_devices()
+        if devices:
+            return devices[0]
+        return self._pick_device(_dist_state(self.distributed)[1])
+
+    def _completed(self, X, device=None):
+        """The shortest-path completion of one input map under this solver's kind and alpha,
+        as a resident ContactMap of wish distances."""
+        from .datatypes import complete_map
+        return complete_map(X, kind=self.kind, alpha=self.alpha,
+                            device=self._completion_device() if device is None else device)
 
     # -- the stages fit() and fit_many() share -----------------------------------------
     def _map_source(self, X, sparse=True):
@@ -1114,7 +1153,8 @@ class StructureSolver(object):
         """A solver with this one's parameters, but for `overrides`."""
         return type(self)(**dict(self._params(), **overrides))
 
-    def _fit_impl(self, matrix, n, init, KRnorm, KRexpected):
+    def _fit_impl(self, matrix, n, init, KRnorm, KRexpected, kind=None):
+        kind = self.kind if kind is None else kind      # 'wish' for a completed map
         resident = getattr(matrix, "is_resident", False)
         triples = getattr(matrix, "is_triples", False)
         sparse = hasattr(matrix, "row") and not resident
@@ -1143,13 +1183,13 @@ class StructureSolver(object):
                                        device=self._pick_device(world), tiles=tiles)
         with _teardown(eng):
             if resident:
-                eng.set_wish_resident(matrix, self.kind, self.alpha)
+                eng.set_wish_resident(matrix, kind, self.alpha)
             elif triples:
-                eng.set_wish_triples(matrix, self.kind, self.alpha, KRnorm, KRexpected)
+                eng.set_wish_triples(matrix, kind, self.alpha, KRnorm, KRexpected)
             elif sparse:
-                eng.set_wish_sparse(rows, cols, vals, self.kind, self.alpha, KRnorm, KRexpected)
+                eng.set_wish_sparse(rows, cols, vals, kind, self.alpha, KRnorm, KRexpected)
             else:
-                eng.set_wish_dense(matrix, self.kind, self.alpha)
+                eng.set_wish_dense(matrix, kind, self.alpha)
             sums = self._bin_sums(eng, world)
             if sums is not None:
                 lr, scale = self._steps(sums, n)
@@ -1222,7 +1262,8 @@ class StructureSolver(object):
                              % (bad[0], count.value))
         return list(self._group)
 
-    def fit_triples(self, triples, resolution, n_bins, KRnorm=None, KRexpected=None, init=None):
+    def fit_triples(self, triples, resolution, n_bins, KRnorm=None, KRexpected=None, init=None,
+                    complete=None):
         """Solve straight from a Rao-format sparse file's content, never building
         the dense matrix: `triples` is the (n, 3) array [pos_i, pos_j, count] that
         `ContactMap.__init__` reads (reference `blueberry/datatypes.pyx:100-102`),
@@ -1230,11 +1271,22 @@ class StructureSolver(object):
         `n_bins + 1` bins (pyx:97), and with KRnorm / KRexpected each count is
         balanced and O/E-normalised on the device as `ContactMap.normalize`
         would (pyx:166-169).  A bin pair that occurs more than once keeps its last
-        count, as in the reference's scatter (pyx:115-116)."""
+        count, as in the reference's scatter (pyx:115-116).
+        complete='shortest_path' (see `fit`): the triples are scattered into a dense resident
+        matrix (`ContactMap.from_triples`), normalised there if KR vectors are given, and that
+        map is completed and fitted."""
+        _check_complete(complete)
         n = int(n_bins) + 1
         if KRnorm is not None and (numpy.any(numpy.asarray(KRnorm) == 0.0)
                                    or numpy.any(numpy.asarray(KRexpected)[:n_bins] == 0.0)):
             raise ZeroDivisionError("float division")      # as ContactMap.normalize
+        if complete is not None:
+            from .datatypes import ContactMap
+            cm = ContactMap.from_triples(triples, resolution, n_bins, KRnorm=KRnorm,
+                                         KRexpected=KRexpected, device=self._completion_device())
+            if KRnorm is not None or KRexpected is not None:
+                cm.normalize()
+            return self.fit(cm, init=init, complete=complete)
         if hasattr(self._engine_factory, "set_wish_triples"):
             # nan_to_num (pyx:102), the binning and the tile occupancy on the device: the host
             # never makes a pass over the triples (round 3: two isfinite passes, two divide +
@@ -1271,7 +1323,7 @@ class StructureSolver(object):
         sp = scipy.sparse.coo_matrix((t[keep, 2], (rows[keep], cols[keep])), shape=(n, n))
         return self._fit_impl(sp, n, init, KRnorm, KRexpected)
 
-    def fit_many(self, maps, inits=None):
+    def fit_many(self, maps, inits=None, complete=None):
         """Solve SEVERAL maps at once on one GPU -- e.g. the 23 per-chromosome ContactMaps
         of a genome (the reference's ContactMap is per chromosome, `blueberry/
         datatypes.pyx:88`), each of which alone is launch-bound (5-20 us per iteration
@@ -1286,12 +1338,15 @@ class StructureSolver(object):
 
         maps: sequence of ContactMaps (resident ones are packed device to device), square
         ndarrays or anything `numpy.asarray` takes.  inits: None, or one (n_m, 3) start per
-        map (None entries: the seeded default of `fit()`).
+        map (None entries: the seeded default of `fit()`).  complete='shortest_path' (see
+        `fit`): every map is completed on the device that solves it and the fit is that of the
+        completed maps under kind='wish'; `completed_unreachable_pairs_` is then a list.
         Sets `structures_` (list of (n_m, 3) float64), `stresses_` (list of per-iteration
         arrays), `n_bins_many_`, `lrs_`, `n_iter_`; returns self."""
         if self._group is not None and len(self._group) > 1:
             raise ValueError("fit_many with devices= / n_gpus= is not supported: fit_many runs "
                              "on one device, or one per rank of a torch.distributed job")
+        _check_complete(complete)
         if not hasattr(self._engine_factory, "set_maps"):
             raise TypeError("fit_many needs an engine that holds several maps (HipEngine)")
         maps = list(maps)
@@ -1317,24 +1372,36 @@ class StructureSolver(object):
             if mine[rank]:
                 local = self._clone(device=self._pick_device(world), distributed=False,
                                     devices=None, n_gpus=None)
-                local._fit_many_local([maps[m] for m in mine[rank]], [inits[m] for m in mine[rank]])
-                part = (mine[rank], local.structures_, local.stresses_, local.lrs_)
+                local._fit_many_local([maps[m] for m in mine[rank]], [inits[m] for m in mine[rank]],
+                                      complete)
+                part = (mine[rank], local.structures_, local.stresses_, local.lrs_,
+                        getattr(local, "completed_unreachable_pairs_", None))
             parts = [None] * world
             dist.all_gather_object(parts, part)
             n = len(maps)
             self.structures_, self.stresses_, self.lrs_ = [None] * n, [None] * n, [None] * n
+            unreachable = [None] * n
             for p in parts:
                 if p is not None:
                     for k, m in enumerate(p[0]):
                         self.structures_[m], self.stresses_[m], self.lrs_[m] = p[1][k], p[2][k], p[3][k]
+                        if p[4] is not None:
+                            unreachable[m] = p[4][k]
+            if complete is not None:
+                self.completed_unreachable_pairs_ = unreachable
             self.n_bins_many_ = sizes
             self.n_iter_ = max(int(h.shape[0]) for h in self.stresses_)
             self.ranks_of_maps_ = [next(r for r in range(world) if m in mine[r]) for m in range(n)]
             return self
-        return self._fit_many_local(maps, inits)
+        return self._fit_many_local(maps, inits, complete)
 
-    def _fit_many_local(self, maps, inits):
+    def _fit_many_local(self, maps, inits, complete=None):
         """fit_many on this rank's GPU (see fit_many)."""
+        kind = self.kind
+        if complete is not None:
+            maps = [self._completed(X, device=self._pick_device(1)) for X in maps]
+            self.completed_unreachable_pairs_ = [cm.unreachable_pairs_ for cm in maps]
+            kind = "wish"
         pairs = [self._map_source(X, sparse=False) for X in maps]
         srcs, sizes = [src for src, _ in pairs], [n for _, n in pairs]
         if min(sizes) < 2:
@@ -1369,7 +1436,7 @@ class StructureSolver(object):
                 # only makes the start: unweighted, one step for all, no iterations
                 init = self._clone(n_iter=0, init="spectral", device=device, distributed=False,
                                    devices=None, n_gpus=None, degree_steps=False, weight_power=0,
-                                   momentum=0.0, tol=None).fit(maps[m]).structure_
+                                   momentum=0.0, tol=None, kind=kind).fit(maps[m]).structure_
             elif init is None:
                 init = self._default_start(n)
             x0[o:o + n] = _check_coords(init, n)
@@ -1378,10 +1445,10 @@ class StructureSolver(object):
             eng.set_maps(off + [total], lrs)
             for o, n, src in zip(off, sizes, srcs):
                 if getattr(src, "is_resident", False) and src._resident().device == eng.device:
-                    eng.set_wish_from_cm_block(src._resident(), o, self.kind, self.alpha)
+                    eng.set_wish_from_cm_block(src._resident(), o, kind, self.alpha)
                 else:
                     m = src.to_host() if getattr(src, "is_resident", False) else src
-                    eng.set_wish_dense_block(m, o, self.kind, self.alpha)
+                    eng.set_wish_dense_block(m, o, kind, self.alpha)
             sums = self._bin_sums(eng, 1)
             if sums is not None:
                 # SPEC 2.3.1 / 2.4.1 per map: every bin's whole step goes into `steps`

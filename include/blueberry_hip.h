@@ -553,6 +553,19 @@ BB_API int bb_cm_correlation(bb_cm *cm, double *tflops);
  * grow-only scratch per device, shared by every map on it; this frees it (it is made again by
  * the next call that needs it). */
 BB_API int bb_cm_release_scratch(int device);
+/* Completion by shortest paths (docs/SPEC.md 2.1.1): dst <- the all-pairs shortest-path lengths
+ * of the graph whose edges are src's wish distances -- c^(-1/alpha) of every finite positive
+ * entry of the upper triangle for kind = BB_KIND_COUNTS, the entry itself for BB_KIND_WISH; any
+ * other entry is no edge and the diagonal is ignored.  dst gets a 0 diagonal and 0 ("no
+ * constraint") where no path exists; it is symmetric bit for bit, float64, and a BB_KIND_WISH
+ * input for the solver.  Blocked Floyd-Warshall on the device, no atomics, the same bits on
+ * every run.  dst has src's edge and device; dst == src works in place.  The work matrix (the
+ * edge rounded up to 64, squared, x 8 bytes) comes from the scratch bb_cm_release_scratch
+ * frees; if it cannot be allocated: BB_ERR_NOMEM with both sizes in the message, nothing
+ * changed.  alpha <= 0, an unknown kind, a mismatch of edge or device: BB_ERR_INVALID.
+ * unreachable_pairs (may be NULL): the number of pairs i < j without a path. */
+BB_API int bb_cm_shortest_paths(const bb_cm *src, bb_cm *dst, int kind, double alpha,
+                                int64_t *unreachable_pairs);
 /* Hand the resident matrix to a solver of n_bins = d bins on the same device, device
  * to device (same meaning of kind / alpha as bb_solver_set_wish_dense).  A solver on another
  * device packs over peer access where hipDeviceCanAccessPeer allows it (enabled here); without
