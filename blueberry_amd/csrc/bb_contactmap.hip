@@ -25,10 +25,7 @@
 
 namespace {
 
-#ifndef BB_CM_TILE
-#define BB_CM_TILE 32
-#endif
-constexpr int kT = BB_CM_TILE;  // tile edge of the normalise / finalise kernels (kT x 8 threads)
+constexpr int kT = 32;  // tile edge of the normalise / finalise kernels (kT x 8 threads)
 
 __device__ __forceinline__ double nan_to_num(double v) {
     // numpy.nan_to_num defaults: NaN -> 0, +/-inf -> +/-DBL_MAX
@@ -118,11 +115,7 @@ __global__ __launch_bounds__(kT * 8) void normalize_kernel(double *m, int64_t d,
 // loads of its next pair are in flight while the mirror of the current one goes out
 // (one workgroup per CU has nobody else to cover its load latency).  Same arithmetic,
 // same order, same bits as normalize_kernel.  Dynamic LDS: tile[128][129] doubles.
-#ifdef BB_CM_PLAIN_STORES
-__device__ __forceinline__ void nt_store(double *p, double v) { *p = v; }
-#else
 __device__ __forceinline__ void nt_store(double *p, double v) { __builtin_nontemporal_store(v, p); }
-#endif
 constexpr int kNT = 128;   // tile edge: one 1024-thread workgroup per CU
 __global__ __launch_bounds__(kNT * 8) void normalize128_kernel(double *m, int64_t d, int64_t n_bins,
                                                                const double *__restrict__ kr,
@@ -239,14 +232,8 @@ __global__ void scatter_store_kernel(const double *__restrict__ tr, int64_t n, i
 // Column marginals: one thread per column, rows added IN ORDER (that is numpy's
 // sum(axis=0) for a C-contiguous matrix, bit for bit); kUnroll loads are in flight
 // before the dependent adds so that the sweep runs near HBM speed all the same.
-#ifndef BB_CM_SUM_UNROLL
-#define BB_CM_SUM_UNROLL 64
-#endif
-constexpr int kSumUnroll = BB_CM_SUM_UNROLL;
-#ifndef BB_CM_SUM_WG
-#define BB_CM_SUM_WG 128
-#endif
-constexpr int kSumWG = BB_CM_SUM_WG;
+constexpr int kSumUnroll = 64;
+constexpr int kSumWG = 128;
 __global__ __launch_bounds__(kSumWG) void column_sums_kernel(const double *__restrict__ m, int64_t d,
                                                           double *__restrict__ sums) {
     const int64_t c = (int64_t)blockIdx.x * kSumWG + threadIdx.x;
@@ -333,12 +320,8 @@ __global__ __launch_bounds__(256) void gather_kernel(const double *__restrict__ 
 constexpr int kSvRows = 64, kSvSeg = 4096, kSvGroup = 8;
 // plain loads: the 512-byte segments of a wave are not line-aligned (odd d), neighbouring
 // chunks share their end lines, and a non-temporal load does not leave them in L2 for the
-// neighbour -- 481 against 505 us per product at d = 24,927 (-DBB_CM_SYMV_NT for the A/B)
-#ifdef BB_CM_SYMV_NT
-__device__ __forceinline__ double sv_load(const double *p) { return __builtin_nontemporal_load(p); }
-#else
+// neighbour -- 481 against 505 us per product at d = 24,927
 __device__ __forceinline__ double sv_load(const double *p) { return *p; }
-#endif
 __global__ __launch_bounds__(256, 2) void symv_upper_kernel(const double *__restrict__ m, int64_t d,
                                                             const double *__restrict__ x,
                                                             const int2 *__restrict__ items,
@@ -710,12 +693,10 @@ __global__ __launch_bounds__(256, 2) void gram_kernel(const double *__restrict__
         // matrix pipe: the loads have long landed).  Left alone the scheduler hoists the
         // stores -- and with them `s_waitcnt vmcnt(0)` -- to four MFMAs below the loads, and
         // every K-tile then waits out the memory latency with the pipe idle: 58.7 TFLOP/s,
-        // 75 % of the peak (round 3); -DBB_GRAM_NO_SCHED restores that for an A/B.  (Weaving the
+        // 75 % of the peak (round 3; the A/B is recorded in docs/EXPERIMENTS.md).  (Weaving the
         // eight stores between the LAST sixteen MFMAs with sched_group_barrier instead: 66.5
         // against 67.4 TFLOP/s -- the operand reads of the last K-step then issue late.)
-#ifndef BB_GRAM_NO_SCHED
         __builtin_amdgcn_sched_barrier(0);
-#endif
         BB_LSTORE(buf ^ 1);
         __syncthreads();
     }

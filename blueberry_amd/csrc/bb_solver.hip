@@ -408,18 +408,11 @@ decltype(auto) with_int(int v, F &&f) {
     else return v == V ? f(std::integral_constant<int, V>{}) : with_int<Rest...>(v, f);
 }
 
-// the sweep kernel of an OP: weighted_sweep_kernel for the weighted stress (SPEC 2.3.1)
-template <typename T, bool W, bool NT, int OP, int WPB>
-constexpr auto sweep_kernel() {
-    if constexpr (is_weighted_op<OP>()) return weighted_sweep_kernel<T, W, NT, OP, WPB>;
-    else return stress_grad_kernel<T, W, NT, OP, WPB>;
-}
-
 // One instantiation of the sweep.  Its dynamic-LDS ceiling (row-sum parking and the column
 // partials) is raised once: one bit of defer_attr_done per (WPB, NT, OP).
 template <bool NT, int OP, int WPB, typename T, bool W>
 int launch_sweep(LayoutTag<T, W>, bb_solver *s, const void *x_in) {
-    const auto kern = sweep_kernel<T, W, NT, OP, WPB>();
+    const auto kern = stress_grad_kernel<T, W, NT, OP, WPB>;
     constexpr unsigned bit = 1u << ((WPB == 8 ? 4 : 0) + (NT ? 2 : 0) + (OP == kOpMatvec2 ? 1 : 0) +
                                     (OP == kOpStressW1 ? 8 : 0) + (OP == kOpStressW2 ? 16 : 0));
     if (s->defer_lds_bytes > 0 && !(s->defer_attr_done & bit)) {
@@ -443,12 +436,11 @@ int launch_sweep(LayoutTag<T, W>, bb_solver *s, const void *x_in) {
 template <int OP, typename L>
 int launch_sweep_op(L lay, bb_solver *s, const void *x_in) {
     constexpr int kPairWpb = sizeof(typename L::T) == 4 || L::W ? 8 : 4;
-    if (s->nontemporal) {
-        if (kPairWpb == 8 && s->wpb == 8) return launch_sweep<true, OP, kPairWpb>(lay, s, x_in);
-        return launch_sweep<true, OP, 4>(lay, s, x_in);
-    }
-    if (kPairWpb == 8 && s->wpb == 8) return launch_sweep<false, OP, kPairWpb>(lay, s, x_in);
-    return launch_sweep<false, OP, 4>(lay, s, x_in);
+    return with_int<1, 0>(s->nontemporal ? 1 : 0, [&](auto nt) {
+        return with_int<kPairWpb, 4>(s->wpb, [&](auto wpb) {
+            return launch_sweep<decltype(nt)::value != 0, OP, decltype(wpb)::value>(lay, s, x_in);
+        });
+    });
 }
 
 // What the reduce multiplies the summed partials by: 2 for the gradient (SPEC 2.3: the sweep

@@ -91,19 +91,6 @@ struct Lay<double, false> {
                                                 // one per-lane load + v_readlane instead
 };
 
-template <int C>
-__device__ __forceinline__ float elem(const float4 &v) {
-    if constexpr (C == 0) return v.x;
-    if constexpr (C == 1) return v.y;
-    if constexpr (C == 2) return v.z;
-    return v.w;
-}
-template <int C>
-__device__ __forceinline__ double elem(const double2 &v) {
-    if constexpr (C == 0) return v.x;
-    return v.y;
-}
-
 // --------------------------------------------------------------------------
 // cross-lane helpers (wave64, DPP; no LDS)
 // --------------------------------------------------------------------------
@@ -239,13 +226,13 @@ __device__ __forceinline__ double rcp_f64(double x) {
     return fma(r0, fma(e, e, e), r0);
 }
 
-// Pair math for one matrix row of a unit: VPL pairs per lane (fp64; fp32 has pair_step2).
-template <typename T, int C, int OP>
-__device__ __forceinline__ void pair_step(const typename Traits<T>::Vec &drow, T xi, T yi, T zi,
-                                          const T (&xj)[Traits<T>::VPL][3],
-                                          T (&gc)[Traits<T>::VPL][3], T &gx, T &gy, T &gz, T &s) {
-    static_assert(sizeof(T) == 8, "fp32 pairs go through pair_step2");
-    const T delta = elem<C>(drow);
+// Pair math of one fp64 pair: column C (0, 1) of a 16-byte load (fp32 has pair_step2).
+template <int C, int OP>
+__device__ __forceinline__ void pair_step(const double2 &drow, double xi, double yi, double zi,
+                                          const double (&xj)[2][3], double (&gc)[2][3], double &gx,
+                                          double &gy, double &gz, double &s) {
+    using T = double;
+    const T delta = C == 0 ? drow.x : drow.y;
     if constexpr (OP == kOpMatvec2) {
         const T a = delta * delta;
         gx += a * xj[C][0]; gy += a * xj[C][1]; gz += a * xj[C][2];
@@ -325,42 +312,33 @@ struct WinPtr {
     __device__ __forceinline__ Vec load(int k) const { return stream_load<NT>(p + k * 64); }
 };
 
-// One unit, generic (fp64) form: RPU matrix rows of LPR wave-loads each.  Load k of
-// row r of the CURRENT unit is consumed from d[r*LPR + k], which is then refilled at
-// once with the same load of the NEXT unit, so 8 KiB per wave stay in flight with a
-// single register window.  xrow.get(q): the unit's q-th row coordinate, wave-uniform.
-template <typename T, bool W, bool NT, int OP, typename XR, typename WIN>
-__device__ __forceinline__ void process_unit(typename Traits<T>::Vec (&d)[8], const XR &xrow,
-                                             const WIN &next,
-                                             const T (&xj)[(Lay<T, W>::LPR)][Traits<T>::VPL][3],
-                                             T (&gc)[(Lay<T, W>::LPR)][Traits<T>::VPL][3],
-                                             double &stress, __amdgpu_buffer_rsrc_t row_rsrc,
-                                             unsigned row_voff) {
-    constexpr int VPL = Traits<T>::VPL, LPR = Lay<T, W>::LPR;
-    static_assert(Lay<T, W>::RPU * LPR == 8, "a unit is 8 wave-loads");
-    T s = T(0);
+// The three unit forms (fp64 narrow, fp64 wide, fp32) share one shape: load k of row r of
+// the CURRENT unit is consumed from d[r*LPR + k], which is then refilled at once with the same
+// load of the NEXT unit, so 8 KiB per wave stay in flight with a single register window.
+// xrow.get(q): the unit's q-th row coordinate, wave-uniform.
+//
+// ---- fp64, 8 x 128 units: one wave-load per matrix row, row sums by the DPP tree ----
+template <bool NT, int OP, typename XR, typename WIN>
+__device__ __forceinline__ void process_unit_f64n(double2 (&d)[8], const XR &xrow, const WIN &next,
+                                                  const double (&xj)[1][2][3], double (&gc)[1][2][3],
+                                                  double &stress, __amdgpu_buffer_rsrc_t row_rsrc,
+                                                  unsigned row_voff) {
+    double s = 0.0;
 #pragma unroll
-    for (int r = 0; r < Lay<T, W>::RPU; ++r) {
-        const T xi = xrow.get(3 * r), yi = xrow.get(3 * r + 1), zi = xrow.get(3 * r + 2);
-        T gx = T(0), gy = T(0), gz = T(0);
-#pragma unroll
-        for (int k = 0; k < LPR; ++k) {
-            pair_step<T, 0, OP>(d[r * LPR + k], xi, yi, zi, xj[k], gc[k], gx, gy, gz, s);
-            pair_step<T, 1, OP>(d[r * LPR + k], xi, yi, zi, xj[k], gc[k], gx, gy, gz, s);
-            if constexpr (VPL == 4) {
-                pair_step<T, 2, OP>(d[r * LPR + k], xi, yi, zi, xj[k], gc[k], gx, gy, gz, s);
-                pair_step<T, 3, OP>(d[r * LPR + k], xi, yi, zi, xj[k], gc[k], gx, gy, gz, s);
-            }
-            d[r * LPR + k] = next.template load<NT>(r * LPR + k);
-        }
+    for (int r = 0; r < 8; ++r) {
+        const double xi = xrow.get(3 * r), yi = xrow.get(3 * r + 1), zi = xrow.get(3 * r + 2);
+        double gx = 0.0, gy = 0.0, gz = 0.0;
+        pair_step<0, OP>(d[r], xi, yi, zi, xj[0], gc[0], gx, gy, gz, s);
+        pair_step<1, OP>(d[r], xi, yi, zi, xj[0], gc[0], gx, gy, gz, s);
+        d[r] = next.template load<NT>(r);
         wave_sum_hi3(gx, gy, gz);
         // one 3-element store per matrix row, from the lane holding the sums
-        store_row3(row_rsrc, row_voff + r * 3 * (unsigned)sizeof(T), gx, gy, gz);
+        store_row3(row_rsrc, row_voff + r * 24u, gx, gy, gz);
         // keep the rows in program order: otherwise the scheduler interleaves the
         // rows for ILP and spills
         __builtin_amdgcn_sched_barrier(0);
     }
-    stress += (double)s;
+    stress += s;
 }
 
 // ---- fp64, 2 x 512 units: the row sums go through the matrix pipe ---------------
@@ -436,8 +414,8 @@ __device__ __forceinline__ void process_unit_f64w(double2 (&d)[8], const XR &xro
         double gx = 0.0, gy = 0.0, gz = 0.0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            pair_step<double, 0, OP>(d[r * 4 + k], xi, yi, zi, xj[k], gc[k], gx, gy, gz, s);
-            pair_step<double, 1, OP>(d[r * 4 + k], xi, yi, zi, xj[k], gc[k], gx, gy, gz, s);
+            pair_step<0, OP>(d[r * 4 + k], xi, yi, zi, xj[k], gc[k], gx, gy, gz, s);
+            pair_step<1, OP>(d[r * 4 + k], xi, yi, zi, xj[k], gc[k], gx, gy, gz, s);
             d[r * 4 + k] = next.template load<NT>(r * 4 + k);
         }
         acc = __builtin_amdgcn_mfma_f64_16x16x4f64(gx, sel[3 * r + 0], acc, 0, 0, 0);
@@ -586,8 +564,10 @@ __device__ __forceinline__ void process_unit_f32(float4 (&d)[8], const float (&x
     stress += (double)(s2.x + s2.y);
 }
 
-__device__ __forceinline__ void load_strip_f32(StripF32 &st, const float *__restrict__ X, int j0,
-                                               int lane) {
+// load_strip(st, X, j0, lane): the strip's coordinates, accumulators zeroed; store_strip(st,
+// slot, lane): its column partial in the layout of a slot -- one overload per strip state
+__device__ __forceinline__ void load_strip(StripF32 &st, const float *__restrict__ X, int j0,
+                                           int lane) {
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const float4 *p = reinterpret_cast<const float4 *>(
@@ -604,8 +584,8 @@ __device__ __forceinline__ void load_strip_f32(StripF32 &st, const float *__rest
     }
 }
 
-__device__ __forceinline__ void store_strip_f32(const StripF32 &st, float *__restrict__ slot,
-                                                int lane) {
+__device__ __forceinline__ void store_strip(const StripF32 &st, float *__restrict__ slot,
+                                            int lane) {
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         float4 *p = reinterpret_cast<float4 *>(slot + (k * 256 + (int64_t)lane * 4) * 3);
@@ -629,51 +609,40 @@ __device__ __forceinline__ T load_xrow(const T *__restrict__ X, int i0, int lane
     return X[(int64_t)i0 * 3 + (lane < 3 * Lay<T, W>::RPU ? lane : 0)];
 }
 
-// Generic (fp64) column-strip state: load k of a row brings columns
-// k*64*VPL + lane*VPL .. +VPL-1, so lane l owns 3*VPL consecutive coordinates per k.
-template <typename T, bool W>
-__device__ __forceinline__ void load_strip(T (&xj)[(Lay<T, W>::LPR)][Traits<T>::VPL][3],
-                                           const T *__restrict__ X, int j0, int lane) {
-    using Vec = typename Traits<T>::Vec;
-    constexpr int VPL = Traits<T>::VPL;
+// fp64 column-strip state: load k of a row brings columns k*128 + lane*2, +1, so lane l owns
+// 6 consecutive coordinates per k.
+template <int LPR>
+struct StripF64 {
+    double xj[LPR][2][3], gc[LPR][2][3];
+};
+template <int LPR>
+__device__ __forceinline__ void load_strip(StripF64<LPR> &st, const double *__restrict__ X, int j0,
+                                           int lane) {
 #pragma unroll
-    for (int k = 0; k < Lay<T, W>::LPR; ++k) {
-        const Vec *p = reinterpret_cast<const Vec *>(
-            X + ((int64_t)j0 + k * 64 * VPL + (int64_t)lane * VPL) * 3);
-        Vec a = p[0], b = p[1], c = p[2];
-        if constexpr (VPL == 4) {
-            xj[k][0][0] = a.x; xj[k][0][1] = a.y; xj[k][0][2] = a.z;
-            xj[k][1][0] = a.w; xj[k][1][1] = b.x; xj[k][1][2] = b.y;
-            xj[k][2][0] = b.z; xj[k][2][1] = b.w; xj[k][2][2] = c.x;
-            xj[k][3][0] = c.y; xj[k][3][1] = c.z; xj[k][3][2] = c.w;
-        } else {
-            xj[k][0][0] = a.x; xj[k][0][1] = a.y; xj[k][0][2] = b.x;
-            xj[k][1][0] = b.y; xj[k][1][1] = c.x; xj[k][1][2] = c.y;
-        }
+    for (int k = 0; k < LPR; ++k) {
+        const double2 *p =
+            reinterpret_cast<const double2 *>(X + ((int64_t)j0 + k * 128 + (int64_t)lane * 2) * 3);
+        const double2 a = p[0], b = p[1], c = p[2];
+        st.xj[k][0][0] = a.x; st.xj[k][0][1] = a.y; st.xj[k][0][2] = b.x;
+        st.xj[k][1][0] = b.y; st.xj[k][1][1] = c.x; st.xj[k][1][2] = c.y;
+    }
+#pragma unroll
+    for (int k = 0; k < LPR; ++k)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) st.gc[k][c][0] = st.gc[k][c][1] = st.gc[k][c][2] = 0.0;
+}
+template <int LPR>
+__device__ __forceinline__ void store_strip(const StripF64<LPR> &st, double *__restrict__ slot,
+                                            int lane) {
+#pragma unroll
+    for (int k = 0; k < LPR; ++k) {
+        double2 *p = reinterpret_cast<double2 *>(slot + ((int64_t)k * 128 + (int64_t)lane * 2) * 3);
+        const auto &g = st.gc[k];
+        p[0] = make_double2(g[0][0], g[0][1]);
+        p[1] = make_double2(g[0][2], g[1][0]);
+        p[2] = make_double2(g[1][1], g[1][2]);
     }
 }
-
-template <typename T, bool W>
-__device__ __forceinline__ void store_strip(const T (&gc)[(Lay<T, W>::LPR)][Traits<T>::VPL][3],
-                                            T *__restrict__ slot, int lane) {
-    using Vec = typename Traits<T>::Vec;
-    constexpr int VPL = Traits<T>::VPL;
-#pragma unroll
-    for (int k = 0; k < Lay<T, W>::LPR; ++k) {
-        Vec *p = reinterpret_cast<Vec *>(slot + ((int64_t)k * 64 * VPL + (int64_t)lane * VPL) * 3);
-        const auto &g = gc[k];
-        if constexpr (VPL == 4) {
-            p[0] = make_float4(g[0][0], g[0][1], g[0][2], g[1][0]);
-            p[1] = make_float4(g[1][1], g[1][2], g[2][0], g[2][1]);
-            p[2] = make_float4(g[2][2], g[3][0], g[3][1], g[3][2]);
-        } else {
-            p[0] = make_double2(g[0][0], g[0][1]);
-            p[1] = make_double2(g[0][2], g[1][0]);
-            p[2] = make_double2(g[1][1], g[1][2]);
-        }
-    }
-}
-
 // One wave = one contiguous chunk of units; 4 independent waves per workgroup.
 // No LDS, no barriers, no atomics: results are bitwise reproducible.
 //
@@ -719,18 +688,284 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
     int chunk_q, int chunk_r, const int2 *__restrict__ wave_slots, T *__restrict__ rowpart,
     T *__restrict__ colpart, double *__restrict__ stresspart, int cap_units, int lds_wave_floats,
     int dense_u0, double *__restrict__ stress_slot) {
-#include "bb_sweep_body.inc"
-}
+    using Vec = typename Traits<T>::Vec;
+    constexpr int VW = Lay<T, W>::VW;
+    constexpr bool DEFER = sizeof(T) == 4 || W;
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave in workgroup
+    // workgroup b sweeps the b-th run of WPB chunks (permuting that map by XCD changed
+    // nothing: docs/EXPERIMENTS.md)
+    const int wg = (int)blockIdx.x;
+    const int w = wg * WPB + wib;
+    // wave w owns units [w*q + min(w, r), +q (+1 if w < r)): arithmetic, not a table --
+    // one dependent memory round trip less before the wave's first matrix load
+    const int ua = w * chunk_q + (w < chunk_r ? w : chunk_r);
+    const int ub = ua + chunk_q + (w < chunk_r ? 1 : 0);
+    double stress = 0.0;
+    // the shared column slots of this workgroup's waves (epilogue), read NOW: behind the
+    // fences further down the compiler no longer takes them through the scalar cache, and a
+    // vector load there waits -- vmcnt is in order -- for every store the wave has in flight
+    int ws_shared[WPB];
+#pragma unroll
+    for (int k = 0; k < WPB; ++k) ws_shared[k] = wave_slots[(int64_t)wg * WPB + k].y;
+    // DEFER: this wave's parking space, cap_units * 12 floats + 4 dummy words
+    extern __shared__ __attribute__((aligned(16))) float row_lds[];
+    // this wave's LDS region: row-sum parking while it sweeps, its last column partial at
+    // the end (lds_wave_floats >= cap_units * 12 + 4 and >= 3 * VW elements of T)
+    const int stage0 = wib * lds_wave_floats;
+    // WPB = 8: progress words of the 8 waves, behind the regions
+    int *progress = reinterpret_cast<int *>(row_lds + WPB * lds_wave_floats);
+    int partner_done = 0;
+    const int park_from = (ub - ua) > cap_units ? (ub - ua) - cap_units : 0;
+    // fp64 2 x 512 units: column selectors of the MFMA row reduction (process_unit_f64w)
+    double sel[6];
+#pragma unroll
+    for (int v = 0; v < 6; ++v) sel[v] = (lane & 15) == v ? 1.0 : 0.0;
 
-// The weighted stress of SPEC 2.3.1 (OP = kOpStressW1 / kOpStressW2): the same body under a
-// name of its own (the unweighted kernels above stay exactly what they were).
-template <typename T, bool W, bool NT, int OP, int WPB>
-__global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void weighted_sweep_kernel(
-    const T *__restrict__ units, const T *__restrict__ X, const int2 *__restrict__ udesc,
-    int chunk_q, int chunk_r, const int2 *__restrict__ wave_slots, T *__restrict__ rowpart,
-    T *__restrict__ colpart, double *__restrict__ stresspart, int cap_units, int lds_wave_floats,
-    int dense_u0, double *__restrict__ stress_slot) {
-#include "bb_sweep_body.inc"
+    if (ua < ub) {
+        int slot = wave_slots[w].x;
+        Vec d[8];  // the unit's 8 wave-loads (8 KiB), in memory order
+        // column-strip state: coordinates + gradient accumulators of this lane's columns
+        using Strip = typename std::conditional<sizeof(T) == 4, StripF32,
+                                                StripF64<Lay<T, W>::LPR>>::type;
+        Strip st;
+        // (closures on purpose: with load_strip / store_strip called directly at the two sites
+        // hipcc allocates the registers of 18 of the 40 instantiations differently, three words
+        // of scratch in the fp32 weighted ones -- tools/kernel_resources.sh --digest)
+        auto strip_load = [&](int j0) __attribute__((always_inline)) { load_strip(st, X, j0, lane); };
+        auto strip_store = [&](int sl) __attribute__((always_inline)) {
+            store_strip(st, colpart + (int64_t)sl * (3 * VW), lane);
+        };
+
+        // The wave's FIRST unit stands between the kernel's arguments and its first
+        // coordinate loads: a cold descriptor load there is one more dependent memory round
+        // trip (0.8 us of every launch).  A dense layout (dense_u0 >= 0: this rank's first
+        // global unit) has tile t = J (J + 1) / 2 + I in strip-major order (SPEC 3.1,
+        // bb_layout_dense_tiles), so that descriptor is arithmetic; the later ones come from
+        // the table as before, one unit ahead of their use.
+        int2 dc;
+        if (dense_u0 >= 0) {
+            constexpr int UPT = VW / Lay<T, W>::RPU;
+            const unsigned g = (unsigned)dense_u0 + (unsigned)ua;
+            const unsigned t = g / UPT, sub = g % UPT;
+            unsigned J = (unsigned)((__builtin_sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
+            while (J * (J + 1) / 2 > t) --J;
+            while ((J + 1) * (J + 2) / 2 <= t) ++J;
+            const unsigned I = t - J * (J + 1) / 2;
+            dc = make_int2((int)(I * VW + sub * Lay<T, W>::RPU), (int)(J * VW));
+        } else {
+            dc = udesc[ua];                                    // current unit
+        }
+        int2 dn = udesc[ua + 1 < ub ? ua + 1 : ua];            // next unit
+        // Prologue: the x rows of the first unit, then its 8 matrix rows.
+        // Row coordinates of a unit, one unit ahead.  XRowS: 3*RPU wave-uniform scalars
+        // fetched through the scalar cache (X is read-only in this kernel) -- no VMEM
+        // slot, no v_readlane (12 floats or 6 doubles: 12 SGPRs, double-buffered).
+        // XRowV (fp64 narrow: 24 doubles): one per-lane load, v_readlane per use.
+        struct XRowS {
+            T v[3 * Lay<T, W>::RPU];
+            __device__ __forceinline__ T get(int q) const { return v[q]; }
+        };
+        struct XRowV {
+            T v;
+            __device__ __forceinline__ T get(int q) const { return lane_value(v, q); }
+        };
+        using XRow = typename std::conditional<Lay<T, W>::SCALAR_XROW, XRowS, XRowV>::type;
+        auto xrow_load = [&](int i0) __attribute__((always_inline)) {
+            XRow x;
+            if constexpr (std::is_same<XRow, XRowS>::value) {
+                const T *px = X + (int64_t)i0 * 3;
+#pragma unroll
+                for (int q = 0; q < 3 * Lay<T, W>::RPU; ++q) x.v[q] = px[q];
+            } else {
+                x.v = load_xrow<T, W>(X, i0, lane);
+            }
+            return x;
+        };
+        XRow xr = xrow_load(dc.x);
+        using Win = WinPtr<Vec>;
+        auto window_of = [&](int u_next) __attribute__((always_inline)) {
+            // The refills of the wave's LAST unit are never consumed.  They stay in the
+            // loop (a branch around them would cost every unit its exact wait counts),
+            // but all lanes ask for the same 16 bytes of the chunk's last unit: 8 lines
+            // instead of 8 KiB per wave and launch (1.3-2.7 % of the bytes of a 1/8 share
+            // of N=50k), back at once, so the epilogue gets the window's registers early.
+            const bool real = u_next < ub;
+            return Win{unit_ptr<T>(units, real ? u_next : ub - 1, real ? lane : 0)};
+        };
+        {
+            const Win first = window_of(ua);
+#pragma unroll
+            for (int r = 0; r < 8; ++r) d[r] = first.template load<NT>(r);
+        }
+        // this wave's row partials: 3*RPU elements per unit of its group's chunk
+        constexpr unsigned kRowBytes = 3 * Lay<T, W>::RPU * sizeof(T);
+        const __amdgpu_buffer_rsrc_t row_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+            rowpart + (int64_t)ua * (3 * Lay<T, W>::RPU), 0, (int)((unsigned)(ub - ua) * kRowBytes),
+            0x00020000);
+
+        // fp32: which of a unit's 12 row sums this lane holds -- lanes 0..3 / 16..19 / 32..35
+        // after the lane swaps (row_sum3_swap) -- and what follows from it for the unit's
+        // store offset and parking slot
+        const int f32_sl12 = swap_rowsum_slot(lane);
+        const unsigned f32_voff_lane = f32_sl12 >= 0 ? (unsigned)f32_sl12 * 4u : 0x40000000u;
+        const int f32_lds_dummy = stage0 + cap_units * 12 + (lane & 3);
+        const int f32_lds_real = f32_sl12 >= 0 ? stage0 + f32_sl12 : f32_lds_dummy;
+        const int f32_m12 = f32_sl12 >= 0 ? 12 : 0;
+        auto unit_step = [&](int u) __attribute__((always_inline)) {
+            if constexpr (WPB == 8) {
+                // pace keeping (see the kernel's comment): the partner's count was read
+                // one unit ago, so nothing here waits on LDS
+                const int mine = u - ua;
+                if (__builtin_amdgcn_readfirstlane(partner_done) > mine)
+                    __builtin_amdgcn_s_setprio(1);
+                else
+                    __builtin_amdgcn_s_setprio(0);
+                __hip_atomic_store(progress + wib, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                partner_done = __hip_atomic_load(progress + (wib ^ 4), __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            // (the descriptors of the units behind the wave's last one are never used)
+            const int un = u + 1 < ub ? u + 1 : u;
+            const XRow xrn = xrow_load(dn.x);
+            const int2 dnn = udesc[un + 1 < ub ? un + 1 : un];
+            // the unit, in the form of <T, W>: where its row sums go, then its math
+            const int k = u - ua;
+            const bool parked = k >= park_from;
+            if constexpr (sizeof(T) == 4) {
+                // fp32: 12 lanes hold one of the unit's 12 sums each.  Units before
+                // park_from are stored directly; the later ones are parked in LDS slot
+                // (k - park_from) and their store is dropped (every lane out of range).
+                // per-lane parts are loop constants (f32_voff_lane, f32_lds_real / _dummy,
+                // f32_m12: below the lambda's captures), per-unit parts scalar: one v_add, one
+                // v_cndmask, one v_mad per unit instead of a chain of selects.  A store is out
+                // of range (dropped) unless the lane holds a sum AND the unit is not parked:
+                // 0x40000000 from either side puts the offset beyond any chunk.
+                const unsigned row_voff =
+                    f32_voff_lane + (parked ? 0x40000000u : (unsigned)k * kRowBytes);
+                const int stage_slot = (parked ? f32_lds_real : f32_lds_dummy) +
+                                       (parked ? k - park_from : 0) * f32_m12;
+                float xs12[12];             // scalar registers
+#pragma unroll
+                for (int q = 0; q < 12; ++q) xs12[q] = xr.get(q);
+                process_unit_f32<NT, OP>(d, xs12, window_of(u + 1), st, stress, row_rsrc, row_voff,
+                                         stage_slot);
+            } else if constexpr (W) {
+                // fp64, 2 x 512 units: lanes 48..53 hold one of the unit's 6 sums each
+                // (parking as in fp32; an LDS slot is 4 bytes, a sum takes two)
+                const bool mine = lane >= 48 && lane < 54;
+                const unsigned row_voff =
+                    (mine && !parked) ? (unsigned)k * kRowBytes + (unsigned)(lane - 48) * 8u
+                                      : kDropOffset;
+                const int stage_slot =
+                    stage0 + ((mine && parked) ? (k - park_from) * 12 + (lane - 48) * 2
+                                               : cap_units * 12 + 2 * (lane & 1));
+                process_unit_f64w<NT, OP>(d, xr, window_of(u + 1), st.xj, st.gc, sel, stress,
+                                          row_rsrc, row_voff, stage_slot);
+            } else {                        // fp64, 8 x 128: lane 63 stores each row's three sums
+                const unsigned row_voff = lane == 63 ? (unsigned)k * kRowBytes : kDropOffset;
+                process_unit_f64n<NT, OP>(d, xr, window_of(u + 1), st.xj, st.gc, stress,
+                                          row_rsrc, row_voff);
+            }
+            xr = xrn;
+            dc = dn;
+            dn = dnn;
+        };
+        // Outer loop: one trip per column strip the wave's sweep crosses (rare).
+        // Inner loop: the units of that strip, with NO branch in the body.
+        int u = ua;
+        for (;;) {
+            const int curj = dc.y;
+            strip_load(curj);
+            // ONE copy of the unit body, entered with nothing in flight: hipcc's s_waitcnt
+            // counts are static and merged over every entry of a loop header, and a
+            // prologue- or strip-change-shaped entry would drain most of the 8-row prefetch
+            // window on every iteration.  The strip's coordinates have to be here anyway,
+            // and they were asked for after the window, so the wait counts inside the loop
+            // are those of the back edge alone.  Same speed as peeling the first unit at
+            // every size (profiles/archive/r02_peel_ab.txt), a third less code.
+            __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+            do {
+                unit_step(u);
+                ++u;
+            } while (u < ub && dc.y == curj);
+            if (u >= ub) break;      // the wave's last strip: its column partial goes out below
+            strip_store(slot);
+            // the stress of the strip left behind goes with its slot (rare: once per strip a
+            // wave crosses), so that every stress partial belongs to ONE strip -- and with
+            // several maps in one solver (bb_solver_set_maps) to one map
+            {
+                const double sv = wave_sum_hi(stress);
+                if (lane == 63) stress_slot[slot] = sv;
+                stress = 0.0;
+            }
+            ++slot;
+        }
+        if constexpr (WPB == 8) {
+            // done: the partner stops yielding
+            __hip_atomic_store(progress + wib, 0x7fffffff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __builtin_amdgcn_s_setprio(0);
+        }
+        if constexpr (DEFER) {
+            // the chunk's row sums, 48 bytes per unit in either precision (12 floats or
+            // 6 doubles), in one contiguous burst.
+            // Lanes read what other lanes of this wave parked: LDS operations of one
+            // wave execute in program order; the fence is for the compiler.
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            const int n4 = ((ub - ua) - park_from) * 3;   // float4 count
+            float4 *dst = reinterpret_cast<float4 *>(rowpart + ((int64_t)ua + park_from) *
+                                                                   (3 * Lay<T, W>::RPU));
+            for (int q = lane; q < n4; q += 64) {
+                const float *src = row_lds + stage0 + 4 * q;
+                dst[q] = make_float4(src[0], src[1], src[2], src[3]);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the region is free again
+            __builtin_amdgcn_wave_barrier();
+        }
+        // the column partial of the wave's LAST strip: into its LDS region (same layout as a
+        // slot in HBM), to be added to its neighbours' below
+        store_strip(st, reinterpret_cast<T *>(row_lds + stage0), lane);
+    }
+    // One column partial per WORKGROUP and strip, not per wave: consecutive waves sweep
+    // consecutive chunks, almost always of the same strip, so the 4 or 8 partials of a
+    // workgroup are added here, in wave order (fixed), and leave as one slot -- an eighth
+    // of the bytes for the sweep to write and for the reduce to read back.  wave_slots[].y
+    // names the shared slot; waves of one workgroup that end in the same strip carry the
+    // same number (the host deals them).
+    // The barrier orders LDS only: __syncthreads() is also a release of the wave's global
+    // stores, and waiting here for the acknowledgement of the row-sum burst (s_waitcnt vmcnt
+    // in front of s_barrier) kept every wave 1-2 us at the end of every launch.
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+    {
+        constexpr int CH = 3 * VW, NTH = 64 * WPB;
+        int k = 0;
+        while (k < WPB) {
+            const int sl = ws_shared[k];       // wave-uniform (scalar registers)
+            if (sl < 0) { ++k; continue; }
+            int k2 = k + 1;
+            while (k2 < WPB && ws_shared[k2] == sl) ++k2;
+            T *dst = colpart + (int64_t)sl * CH;
+#pragma unroll
+            for (int j = 0; j < (CH + NTH - 1) / NTH; ++j) {
+                const int e = (int)threadIdx.x + NTH * j;
+                if (CH % NTH == 0 || e < CH) {
+                    T acc = T(0);
+                    for (int q = k; q < k2; ++q)
+                        acc += reinterpret_cast<const T *>(row_lds + q * lds_wave_floats)[e];
+                    dst[e] = acc;
+                }
+            }
+            k = k2;
+        }
+    }
+
+    // per-wave stress: fixed DPP tree, total in lane 63 (no LDS round trips at the very end
+    // of the launch: six __shfl_down steps of a double are twelve ds_bpermute)
+    stress = wave_sum_hi(stress);
+    if (lane == 63) stresspart[w] = stress;
 }
 
 // --------------------------------------------------------------------------
@@ -825,6 +1060,68 @@ __device__ __forceinline__ double stress_share(const ReduceParams<T> &p, int m, 
 
 constexpr int kRedWG = 128;  // elements a reduce workgroup sums
 
+// SPEC 2.4: V <- mu V - lr g ; X <- X + V   (mu = 0: X -= lr g).  The new velocity; for element
+// o with the old values xo, vo at hand (the reduces load them early, independent of the sum);
+// in place.  row_owner_kernel writes X to a second buffer, three elements at a time: it takes
+// the velocities and stores for itself.
+template <typename T>
+__device__ __forceinline__ T momentum_velocity(T mu, T vo, T lr, T g) { return mu * vo - lr * g; }
+template <typename T>
+__device__ __forceinline__ void momentum_step(T *__restrict__ X, T *__restrict__ V, int64_t o, T xo, T vo,
+                                              T mu, T lr, T g) {
+    const T v = momentum_velocity(mu, vo, lr, g);
+    V[o] = v;
+    X[o] = xo + v;
+}
+template <typename T>
+__device__ __forceinline__ void momentum_step(T *__restrict__ X, T *__restrict__ V, int64_t o, T mu, T lr,
+                                              T g) {
+    const T vo = V[o];
+    momentum_step(X, V, o, X[o], vo, mu, lr, g);
+}
+
+// The sum over ranks of N elements, in rank order from 0 (part of the specification: every
+// transport gives the same bits).  Eight ranks at a time: the words of all N elements are
+// requested before the first add -- one memory round trip per eight ranks, not one per rank and
+// element -- and a rank outside an element's mask mk[q] adds 0.  load(q, r): rank r's word of
+// element q, asked for only where live[q] and the rank is in the mask.
+template <int N, typename T, typename L>
+__device__ __forceinline__ void rank_ordered_sums(T (&g)[N], const bool (&live)[N],
+                                                  const unsigned (&mk)[N], int world, L load) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) g[q] = T(0);
+    for (int r0 = 0; r0 < world; r0 += 8) {
+        T v[N][8];
+#pragma unroll
+        for (int q = 0; q < N; ++q)
+#pragma unroll
+            for (int p = 0; p < 8; ++p)
+                v[q][p] = (live[q] && r0 + p < world && (mk[q] >> (r0 + p) & 1u)) ? load(q, r0 + p) : T(0);
+#pragma unroll
+        for (int q = 0; q < N; ++q)
+#pragma unroll
+            for (int p = 0; p < 8; ++p)
+                if (r0 + p < world) g[q] += v[q][p];
+    }
+}
+
+// The stress travels in the solver's type as a pair: hi = (T)S, lo = (T)(S - hi).
+template <typename T>
+__device__ __forceinline__ void split_hi_lo(double S, T &hi, T &lo) {
+    hi = (T)S;
+    lo = (T)(S - (double)hi);
+}
+
+// sh[0] <- sh[0] + ... + sh[n - 1] by a fixed tree (bitwise reproducible); n = the workgroup's
+// threads, a power of two.  Called by every thread, behind the barrier that follows its own
+// store to sh[tid].
+__device__ __forceinline__ void lds_tree_fold(double *sh, int tid, int n) {
+    for (int off = n >> 1; off > 0; off >>= 1) {
+        if (tid < off) sh[tid] += sh[tid + off];
+        __syncthreads();
+    }
+}
+
 
 // ---- the reduce in ONE launch of one memory round trip (round 3) ------------------
 // Round 2's reduce walked a block's list with one thread per element: a list of L chunks was
@@ -838,6 +1135,37 @@ constexpr int kRedWG = 128;  // elements a reduce workgroup sums
 // offset of a chunk of zeros), so the table's address does not wait for a list pointer and no
 // load is predicated.  A wave is one slice of 64 elements: its table entries are
 // wave-uniform and travel through the scalar cache.
+// slice sl of block b's list, summed for element e in list order, 16 chunks per trip in flight
+template <int S, typename T>
+__device__ __forceinline__ T list_slice_sum(const T *__restrict__ part, const int64_t *__restrict__ lists,
+                                            int list_stride, int b, int sl, int e) {
+    const int lps = list_stride / S;                              // a multiple of 16
+    const int64_t *list = lists + (int64_t)b * list_stride + (int64_t)sl * lps;
+    T acc = T(0);
+    for (int k = 0; k < lps; k += 16) {
+        T v[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) v[q] = part[list[k + q] + e];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc += v[q];
+    }
+    return acc;
+}
+// the S slices of element el, where they met in LDS, added in slice order
+template <int S, typename T>
+__device__ __forceinline__ T slices_total(const T (&meet)[S][kRedWG], int el) {
+    T tot = meet[0][el];
+#pragma unroll
+    for (int q = 1; q < S; ++q) tot += meet[q][el];
+    return tot;
+}
+// the gradient element o from the total of its partials: times scale (2, SPEC 2.3; 1 for a
+// matvec) and the bin's step factor (ReduceParams::bin_scale)
+template <typename T>
+__device__ __forceinline__ T gradient_element(const ReduceParams<T> &p, int64_t o, T tot) {
+    return p.bin_scale ? p.bin_scale[o / 3] * (p.scale * tot) : p.scale * tot;
+}
+
 template <typename T, bool W, int S>
 __global__ __launch_bounds__(128 * S) void reduce_sliced_kernel(ReduceParams<T> p,
                                                                 const int64_t *__restrict__ lists,
@@ -854,31 +1182,15 @@ __global__ __launch_bounds__(128 * S) void reduce_sliced_kernel(ReduceParams<T> 
         p.mode != kReducePeer ||
         __hip_atomic_load(&p.peer_state->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
     if (p.mode != kReduceStressOnly) {
-        const int lps = list_stride / S;                          // a multiple of 16
-        const int64_t *list = lists + (int64_t)b * list_stride + (int64_t)sl * lps;
         const int64_t o = (int64_t)b * CH + e;
         T xo = T(0), vo = T(0);
         if (p.mode == kReduceApply && sl == 0) { xo = p.X[o]; vo = p.V[o]; }   // early: independent
-        T acc = T(0);
-        for (int k = 0; k < lps; k += 16) {
-            T v[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) v[q] = p.part[list[k + q] + e];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc += v[q];
-        }
-        meet[sl][el] = acc;
+        meet[sl][el] = list_slice_sum<S>(p.part, lists, list_stride, b, sl, e);
         __syncthreads();
         if (sl == 0) {
-            T tot = meet[0][el];
-#pragma unroll
-            for (int q = 1; q < S; ++q) tot += meet[q][el];
-            const T g = p.bin_scale ? p.bin_scale[o / 3] * (p.scale * tot) : p.scale * tot;
+            const T g = gradient_element(p, o, slices_total(meet, el));
             if (p.mode == kReduceApply) {
-                // SPEC 2.4: V <- mu V - lr g ; X <- X + V   (mu = 0: X -= lr g)
-                const T v = p.mu * vo - p.lr * g;
-                p.V[o] = v;
-                p.X[o] = xo + v;
+                momentum_step(p.X, p.V, o, xo, vo, p.mu, p.lr, g);
             } else if (p.mode == kReducePeer) {
                 meet[0][el] = g;
             } else {
@@ -901,18 +1213,15 @@ __global__ __launch_bounds__(128 * S) void reduce_sliced_kernel(ReduceParams<T> 
         __shared__ double sh[128 * S];
         sh[tid] = stress_share(p, b, tid, 128 * S);
         __syncthreads();
-        for (int off = 64 * S; off > 0; off >>= 1) {
-            if (tid < off) sh[tid] += sh[tid + off];
-            __syncthreads();
-        }
+        lds_tree_fold(sh, tid, 128 * S);
         if (tid == 0) {
             const double Sx = sh[0];
+            T hi, lo;
+            split_hi_lo(Sx, hi, lo);
             if (p.mode == kReduceExchange) {
-                const T hi = (T)Sx;
                 p.exch[3 * p.n_pad] = hi;
-                p.exch[3 * p.n_pad + 1] = (T)(Sx - (double)hi);
+                p.exch[3 * p.n_pad + 1] = lo;
             } else if (p.mode == kReducePeer) {
-                const T hi = (T)Sx, lo = (T)(Sx - (double)hi);
                 for (int q = 0; q < (peer_live ? p.n_peers : 0); ++q) {
                     p.peer->dst[q][3 * p.n_pad] = hi;
                     p.peer->dst[q][3 * p.n_pad + 1] = lo;
@@ -1098,36 +1407,18 @@ __global__ __launch_bounds__(128 * S) void reduce_exchange_kernel(
     const int dead_here =
         tid == 0 ? __hip_atomic_load(&state->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
 
-    const int lps = list_stride / S;                              // a multiple of 16
-    const int64_t *list = lists + (int64_t)b * list_stride + (int64_t)sl * lps;
     const int64_t o = (int64_t)b * CH + e;
     T xo = T(0), vo = T(0);
     if (sl == 0) { xo = p.X[o]; vo = p.V[o]; }                    // early: independent
-    T acc = T(0);
-    for (int k = 0; k < lps; k += 16) {
-        T v[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) v[q] = p.part[list[k + q] + e];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc += v[q];
-    }
-    meet[sl][el] = acc;
+    meet[sl][el] = list_slice_sum<S>(p.part, lists, list_stride, b, sl, e);
     const bool first = b == 0 && blockIdx.y == 0;
     if (first)                                // the stress: the sweep's partials, fixed tree
         sh[tid] = stress_share(p, 0, tid, 128 * S);
     if (__syncthreads_or(dead_here) != 0) return;
-    if (first) {
-        for (int off = 64 * S; off > 0; off >>= 1) {
-            if (tid < off) sh[tid] += sh[tid + off];
-            __syncthreads();
-        }
-    }
+    if (first) lds_tree_fold(sh, tid, 128 * S);
     if (sl == 0) {
         // the two waves that own the workgroup's 128 elements: push, wait, sum, update
-        T tot = meet[0][el];
-#pragma unroll
-        for (int q = 1; q < S; ++q) tot += meet[q][el];
-        const T mine = peer_sendable(p.bin_scale ? p.bin_scale[o / 3] * (p.scale * tot) : p.scale * tot);
+        const T mine = peer_sendable(gradient_element(p, o, slices_total(meet, el)));
         const unsigned mask = p.peer_mask ? p.peer_mask[b] : ~0u;
         if (mask >> p.rank & 1u)
             for (int q = 0; q < R; ++q)
@@ -1135,10 +1426,8 @@ __global__ __launch_bounds__(128 * S) void reduce_exchange_kernel(
         T g;
         double unused;
         if (peer_wait_sum<T, 1>(arena + o, true, R, slot_elems, xt, my_poison, state, limit, g, unused, mask)) {
-            // SPEC 2.4: V <- mu V - lr g ; X <- X + V, g = the sum over ranks in rank order
-            const T vv = p.mu * vo - p.lr * g;
-            p.V[o] = vv;
-            p.X[o] = xo + vv;
+            // g = the sum over ranks in rank order
+            momentum_step(p.X, p.V, o, xo, vo, p.mu, p.lr, g);
         }
     } else if (first && tid >= 128 && tid < 192) {
         // the stress travels the same way, as a pair (hi, lo) behind the 3 * n_pad elements:
@@ -1146,9 +1435,8 @@ __global__ __launch_bounds__(128 * S) void reduce_exchange_kernel(
         const bool lane0 = tid == 128;
         const int64_t n3 = 3 * p.n_pad;
         if (lane0) {
-            const double Sx = sh[0];
-            const T hi = (T)Sx;
-            const T lo = (T)(Sx - (double)hi);
+            T hi, lo;
+            split_hi_lo(sh[0], hi, lo);
             for (int q = 0; q < R; ++q) {
                 __hip_atomic_store(xt->dst[q] + n3, peer_sendable(hi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 __hip_atomic_store(xt->dst[q] + n3 + 1, peer_sendable(lo), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1243,44 +1531,26 @@ __global__ __launch_bounds__(256) void peer_receive_kernel(
     constexpr int EPT = 4;
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t base = (int64_t)blockIdx.x * 256 + tid; base < n3; base += EPT * stride) {
-        // all slots of all of the thread's elements are requested before the first add (one
-        // memory round trip per eight ranks, not one per rank and element); the sum of an
-        // element runs in rank order
+        // all slots of all of the thread's elements are requested before the first add; the
+        // sum of an element runs in rank order (rank_ordered_sums)
         T g[EPT];
-#pragma unroll
-        for (int q = 0; q < EPT; ++q) g[q] = T(0);
+        int64_t el[EPT];
+        bool live[EPT];
         unsigned mk[EPT];                       // the ranks that sent something for the element's block
 #pragma unroll
         for (int q = 0; q < EPT; ++q) {
-            const int64_t e = base + q * stride;
-            mk[q] = (peer_mask != nullptr && e < n3) ? peer_mask[e / ch] : ~0u;
+            el[q] = base + q * stride;
+            live[q] = el[q] < n3;
+            mk[q] = (peer_mask != nullptr && live[q]) ? peer_mask[el[q] / ch] : ~0u;
         }
-        for (int r0 = 0; r0 < world; r0 += 8) {
-            T v[EPT][8];
-#pragma unroll
-            for (int q = 0; q < EPT; ++q) {
-                const int64_t e = base + q * stride;
-#pragma unroll
-                for (int p = 0; p < 8; ++p)
-                    v[q][p] = (e < n3 && r0 + p < world && (mk[q] >> (r0 + p) & 1u))
-                                  ? __hip_atomic_load(arena + (r0 + p) * slot_elems + e,
-                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
-                                  : T(0);
-            }
-#pragma unroll
-            for (int q = 0; q < EPT; ++q)
-#pragma unroll
-                for (int p = 0; p < 8; ++p)
-                    if (r0 + p < world) g[q] += v[q][p];
-        }
+        rank_ordered_sums(g, live, mk, world, [&](int q, int r) {
+            return __hip_atomic_load(arena + r * slot_elems + el[q], __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_SYSTEM);
+        });
 #pragma unroll
         for (int q = 0; q < EPT; ++q) {
             const int64_t e = base + q * stride;
-            if (e < n3) {
-                const T vv = mu * V[e] - lr * g[q];
-                V[e] = vv;
-                X[e] += vv;
-            }
+            if (e < n3) momentum_step(X, V, e, mu, lr, g[q]);
         }
     }
     if (blockIdx.x == 0 && tid == 0) {
@@ -1300,11 +1570,7 @@ __global__ __launch_bounds__(256) void apply_kernel(T *__restrict__ X, T *__rest
                                                     const T *__restrict__ exch, int64_t n3, T lr,
                                                     T mu, double *stress_out) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e < n3) {
-        const T v = mu * V[e] - lr * exch[e];
-        V[e] = v;
-        X[e] += v;
-    }
+    if (e < n3) momentum_step(X, V, e, mu, lr, exch[e]);
     if (e == 0 && stress_out) *stress_out = (double)exch[n3] + (double)exch[n3 + 1];
 }
 
@@ -1313,29 +1579,20 @@ __global__ __launch_bounds__(256) void apply_kernel(T *__restrict__ X, T *__rest
 // [g (n_pad,3) | stress hi | lo], left there by bb_solver_grad's reduce: the same partial the
 // peer-mode reduce pushes (scale and per-bin factor applied the same way).  The host has
 // ordered this launch behind every member's grad by events, so nothing here waits or polls.
-// Per element: every member's contribution is requested before the first add, the sum runs in
-// member order from 0 with a masked-out member adding 0 -- peer_receive_kernel's order, bit for
-// bit -- then V <- mu V - lr g, X <- X + V.  The stress: (hi, lo) summed in double, in order.
+// Per element: the sum over members is peer_receive_kernel's (rank_ordered_sums: member order
+// from 0, a masked-out member adds 0), then V <- mu V - lr g, X <- X + V.  The stress: (hi, lo)
+// summed in double, in order.
 template <typename T>
 __global__ __launch_bounds__(256) void group_apply_kernel(
     T *__restrict__ X, T *__restrict__ V, const T *const *__restrict__ src, int world, int64_t n3,
     T lr, T mu, double *__restrict__ stress_out, const unsigned *__restrict__ peer_mask, int ch) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e < n3) {
-        const unsigned mk = peer_mask != nullptr ? peer_mask[e / ch] : ~0u;
-        T g = T(0);
-        for (int r0 = 0; r0 < world; r0 += 8) {
-            T v[8];
-#pragma unroll
-            for (int p = 0; p < 8; ++p)
-                v[p] = (r0 + p < world && (mk >> (r0 + p) & 1u)) ? src[r0 + p][e] : T(0);
-#pragma unroll
-            for (int p = 0; p < 8; ++p)
-                if (r0 + p < world) g += v[p];
-        }
-        const T vv = mu * V[e] - lr * g;
-        V[e] = vv;
-        X[e] += vv;
+        const unsigned mk[1] = {peer_mask != nullptr ? peer_mask[e / ch] : ~0u};
+        const bool live[1] = {true};
+        T g[1];
+        rank_ordered_sums(g, live, mk, world, [&](int, int r) { return src[r][e]; });
+        momentum_step(X, V, e, mu, lr, g[0]);
     }
     if (e == 0) {
         double S = 0.0;
@@ -1347,34 +1604,52 @@ __global__ __launch_bounds__(256) void group_apply_kernel(
 // --------------------------------------------------------------------------
 // packing kernels
 // --------------------------------------------------------------------------
+// What becomes a stored wish distance -- the ONE place that says so; the sweep's 0/1 weight
+// depends on the flush (wish_floor).  flush_wish: a distance below the floor is 0 = "no
+// constraint" (fp32: the kernel's 0/1 weight needs delta >= 2^-100; anything that small is
+// below the distance clamp eps = 1e-15 anyway).  wish_from_value: an input value v of `kind` --
+// finite and positive, else no constraint; counts -> v^(-1/alpha) -- then the flush.
+template <typename T>
+__device__ __forceinline__ T flush_wish(double v) {
+    return (T)(v < wish_floor<T>() ? 0.0 : v);
+}
+template <typename T>
+__device__ __forceinline__ T wish_from_value(double v, int kind, double neg_inv_alpha) {
+    const bool ok = (v > 0.0) && (v <= 1.7976931348623157e308);  // finite, positive
+    if (!ok)
+        v = 0.0;
+    else if (kind == BB_KIND_COUNTS)
+        v = pow(v, neg_inv_alpha);
+    return flush_wish<T>(v);
+}
+
+// The cell walk of unit `dsc` = {i0, j0} by a workgroup of 256 threads: f(e, i, j, stored) for
+// the cells e = r * VW + c of the thread, (i, j) = (i0 + r, j0 + c) its bin pair, stored =
+// whether the cell holds a pair at all (upper triangle, inside the map).
+template <typename T, bool W, typename F>
+__device__ __forceinline__ void for_each_cell(int2 dsc, int64_t n_bins, F f) {
+    constexpr int VW = Lay<T, W>::VW, RPU = Lay<T, W>::RPU;
+    for (int e = threadIdx.x; e < RPU * VW; e += 256) {
+        const int r = e / VW, c = e % VW;
+        const int64_t i = (int64_t)dsc.x + r, j = (int64_t)dsc.y + c;
+        f(e, i, j, j > i && j < n_bins);
+    }
+}
+
 // staged fp64 rows (row-major, ld = VW) -> units of one run of tiles.
 template <typename T, bool W>
 __global__ __launch_bounds__(256) void convert_units_kernel(
     const double *__restrict__ stage, T *__restrict__ units_out, const int2 *__restrict__ udesc,
     int64_t ul0, int64_t stage_row0 /* global row of stage row 0 */, int64_t n_bins, int kind,
     double neg_inv_alpha) {
-    constexpr int VW = Lay<T, W>::VW;
+    constexpr int VW = Lay<T, W>::VW, RPU = Lay<T, W>::RPU;
     const int64_t ul = ul0 + blockIdx.x;
     const int2 dsc = udesc[ul];
-    constexpr int RPU = Lay<T, W>::RPU;
     T *out = units_out + ul * (RPU * VW);
-    for (int e = threadIdx.x; e < RPU * VW; e += 256) {
-        const int r = e / VW, c = e % VW;
-        const int64_t i = (int64_t)dsc.x + r, j = (int64_t)dsc.y + c;
-        double v = 0.0;
-        if (j > i && j < n_bins) {
-            v = stage[(i - stage_row0) * VW + c];
-            const bool ok = (v > 0.0) && (v <= 1.7976931348623157e308);  // finite, positive
-            if (!ok)
-                v = 0.0;
-            else if (kind == BB_KIND_COUNTS)
-                v = pow(v, neg_inv_alpha);
-        }
-        // fp32: the kernel's 0/1 weight needs delta >= 2^-100; anything that small
-        // is below the distance clamp eps = 1e-15 anyway and is stored as "none"
-        if (v < wish_floor<T>()) v = 0.0;
-        out[e] = (T)v;
-    }
+    for_each_cell<T, W>(dsc, n_bins, [&](int e, int64_t i, int64_t j, bool stored) {
+        const double v = stored ? stage[(i - stage_row0) * VW + (j - dsc.y)] : 0.0;
+        out[e] = wish_from_value<T>(v, kind, neg_inv_alpha);
+    });
 }
 
 // A (d, d) float64 matrix that is ALREADY in HBM (a device-resident ContactMap,
@@ -1391,21 +1666,10 @@ __global__ __launch_bounds__(256) void pack_units_from_matrix_kernel(
     const int2 dsc = udesc[ul];
     if (dsc.y < off || dsc.y >= n_bins || dsc.x < off) return;
     T *out = units_out + ul * (RPU * VW);
-    for (int e = threadIdx.x; e < RPU * VW; e += 256) {
-        const int r = e / VW, c = e % VW;
-        const int64_t i = (int64_t)dsc.x + r, j = (int64_t)dsc.y + c;
-        double v = 0.0;
-        if (j > i && j < n_bins) {
-            v = m[(i - off) * ld + (j - off)];
-            const bool ok = (v > 0.0) && (v <= 1.7976931348623157e308);  // finite, positive
-            if (!ok)
-                v = 0.0;
-            else if (kind == BB_KIND_COUNTS)
-                v = pow(v, neg_inv_alpha);
-        }
-        if (v < wish_floor<T>()) v = 0.0;
-        out[e] = (T)v;
-    }
+    for_each_cell<T, W>(dsc, n_bins, [&](int e, int64_t i, int64_t j, bool stored) {
+        const double v = stored ? m[(i - off) * ld + (j - off)] : 0.0;
+        out[e] = wish_from_value<T>(v, kind, neg_inv_alpha);
+    });
 }
 
 // Sparse (i, j, value) entries -> resident units (blocked-sparse input).  The
@@ -1434,14 +1698,25 @@ __device__ __forceinline__ double nan_to_num_f64(double v) {
     return v != v ? 0.0 : (v > 1.7976931348623157e308 ? 1.7976931348623157e308
                                                       : (v < -1.7976931348623157e308 ? -1.7976931348623157e308 : v));
 }
-// the entry's bin pair; false: a position outside what an int can hold
-__device__ __forceinline__ bool entry_bins(const EntrySrc &src, int64_t k, int64_t &i, int64_t &j) {
-    if (src.tr == nullptr) { i = src.rows[k]; j = src.cols[k]; return true; }
-    const double qi = nan_to_num_f64(src.tr[k * src.st]) / src.resolution,
-                 qj = nan_to_num_f64(src.tr[k * src.st + src.sc]) / src.resolution;
-    if (!(qi > -2147483648.0 && qi < 2147483648.0 && qj > -2147483648.0 && qj < 2147483648.0))
-        return false;
-    i = (int)qi; j = (int)qj;
+// Entry k's bin pair, ordered i < j.  False: an entry to skip -- the diagonal, which carries no
+// pair, or a bad one (a position outside what an int can hold, a bin outside the map), which
+// sets *bad.
+__device__ __forceinline__ bool entry_pair(const EntrySrc &src, int64_t k, int64_t n_bins, int64_t &i,
+                                           int64_t &j, int *__restrict__ bad) {
+    if (src.tr == nullptr) {
+        i = src.rows[k]; j = src.cols[k];
+    } else {
+        const double qi = nan_to_num_f64(src.tr[k * src.st]) / src.resolution,
+                     qj = nan_to_num_f64(src.tr[k * src.st + src.sc]) / src.resolution;
+        if (!(qi > -2147483648.0 && qi < 2147483648.0 && qj > -2147483648.0 && qj < 2147483648.0)) {
+            atomicExch(bad, 1);
+            return false;
+        }
+        i = (int)qi; j = (int)qj;
+    }
+    if (i == j) return false;
+    if (i > j) { const int64_t t = i; i = j; j = t; }
+    if (i < 0 || j >= n_bins) { atomicExch(bad, 1); return false; }
     return true;
 }
 
@@ -1454,10 +1729,7 @@ __global__ __launch_bounds__(256) void entries_tiles_kernel(EntrySrc src, int64_
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= nnz) return;
     int64_t i, j;
-    if (!entry_bins(src, k, i, j)) { atomicExch(bad, 1); return; }
-    if (i == j) return;
-    if (i > j) { const int64_t t = i; i = j; j = t; }
-    if (i < 0 || j >= n_bins) { atomicExch(bad, 1); return; }
+    if (!entry_pair(src, k, n_bins, i, j, bad)) return;
     present[(i / vw) * n_blocks + j / vw] = 1;
 }
 
@@ -1472,10 +1744,7 @@ __global__ __launch_bounds__(256) void scatter_entries_kernel(
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= nnz) return;
     int64_t i, j;
-    if (!entry_bins(src, k, i, j)) { atomicExch(bad, 1); return; }
-    if (i == j) return;                     // the diagonal carries no pair
-    if (i > j) { const int64_t t = i; i = j; j = t; }
-    if (i < 0 || j >= n_bins) { atomicExch(bad, 1); return; }
+    if (!entry_pair(src, k, n_bins, i, j, bad)) return;
     const int64_t I = i / VW, J = j / VW;
     const int32_t t = tilemap[I * n_blocks + J];
     if (t < 0) { atomicExch(bad, 2); return; }   // entry outside the tile list
@@ -1498,13 +1767,7 @@ __global__ __launch_bounds__(256) void scatter_entries_kernel(
     // (... followed by the reference's nan_to_num over the matrix, pyx:171: a NaN quotient is 0 =
     // no constraint, an overflowing one the largest double -- as ContactMap.normalize leaves it)
     if (kr != nullptr) v = nan_to_num_f64(v / (kr[i] * kr[j] * krexp[j - i]));
-    const bool ok = (v > 0.0) && (v <= 1.7976931348623157e308);
-    if (!ok)
-        v = 0.0;
-    else if (kind == BB_KIND_COUNTS)
-        v = pow(v, neg_inv_alpha);
-    if (v < wish_floor<T>()) v = 0.0;
-    *cell = (T)v;
+    *cell = wish_from_value<T>(v, kind, neg_inv_alpha);
 }
 
 // delta_ij = |x*_i - x*_j| generated in place (synthetic inputs).
@@ -1513,23 +1776,18 @@ __global__ __launch_bounds__(256) void gen_units_kernel(const double *__restrict
                                                         T *__restrict__ units_out,
                                                         const int2 *__restrict__ udesc,
                                                         int64_t n_bins) {
-    constexpr int VW = Lay<T, W>::VW;
+    constexpr int VW = Lay<T, W>::VW, RPU = Lay<T, W>::RPU;
     const int64_t ul = blockIdx.x;
-    const int2 dsc = udesc[ul];
-    constexpr int RPU = Lay<T, W>::RPU;
     T *out = units_out + ul * (RPU * VW);
-    for (int e = threadIdx.x; e < RPU * VW; e += 256) {
-        const int r = e / VW, c = e % VW;
-        const int64_t i = (int64_t)dsc.x + r, j = (int64_t)dsc.y + c;
+    for_each_cell<T, W>(udesc[ul], n_bins, [&](int e, int64_t i, int64_t j, bool stored) {
         double v = 0.0;
-        if (j > i && j < n_bins) {
+        if (stored) {
             const double dx = xs[3 * i] - xs[3 * j], dy = xs[3 * i + 1] - xs[3 * j + 1],
                          dz = xs[3 * i + 2] - xs[3 * j + 2];
             v = sqrt(dx * dx + dy * dy + dz * dz);
         }
-        if (v < wish_floor<T>()) v = 0.0;
-        out[e] = (T)v;
-    }
+        out[e] = flush_wish<T>(v);
+    });
 }
 
 // --------------------------------------------------------------------------
@@ -1602,16 +1860,10 @@ __device__ __forceinline__ void pair_row(T delta, T xi, T yi, T zi, T xj, T yj, 
 // load of the row and three 16-byte loads of the 12 (6) contiguous coordinates of those
 // columns -- one load per pair (two in fp64) instead of four: fp64 -9 % at N=963, -12 % at
 // 2,500, -19 % at 4,096 (28.4 -> 23.0 us); fp32 -4 % at 2,500, -8 % at 4,096
-// (profiles/r04_row_owner_ab.txt; -DBB_ROW_OWNER_SCALAR keeps the old trip for the A/B).
+// (profiles/r04_row_owner_ab.txt, measured against the old trip).
 // Packed fp32 pair math on top of it (v_pk_* straight on the AoS register pairs) changed
 // nothing: from N ~ 4,000 the kernel moves both triangles at ~5 TB/s and that is its bound.
-#ifdef BB_ROW_OWNER_SCALAR
-constexpr int kRowTrip = 128;
-template <typename T> struct RowTrip { static constexpr int COLS = 128; };
-#else
-constexpr int kRowTrip = 256;   // (the larger of the two: what `ld` is rounded up to)
 template <typename T> struct RowTrip { static constexpr int COLS = 64 * (16 / (int)sizeof(T)); };
-#endif
 
 // WPR waves share one row (1, 2 or 4: the host picks it so that a small map still
 // puts >= 16 waves on every CU): wave part p takes the 128-column trips p, p + WPR, ...;
@@ -1633,10 +1885,7 @@ __global__ __launch_bounds__(256) void row_owner_kernel(
         for (int q = tid; q < n_prev; q += 256) a += part_prev[q];
         sh[tid] = a;
         __syncthreads();
-        for (int off = 128; off > 0; off >>= 1) {
-            if (tid < off) sh[tid] += sh[tid + off];
-            __syncthreads();
-        }
+        lds_tree_fold(sh, tid, 256);
         if (tid == 0) *hist_prev = 0.5 * sh[0];
         return;
     }
@@ -1650,15 +1899,6 @@ __global__ __launch_bounds__(256) void row_owner_kernel(
         constexpr int COLS = RowTrip<T>::COLS;
         const int trips = ((int)(ld / COLS) - part + WPR - 1) / WPR;   // trips part, part + WPR, ...
         auto trip = [&](int tr) __attribute__((always_inline)) {
-#ifdef BB_ROW_OWNER_SCALAR
-            const int c = (part + tr * WPR) * COLS;
-#pragma unroll
-            for (int u = 0; u < COLS / 64; ++u) {
-                const int j = c + 64 * u + lane;
-                const T *xj = Xin + 3 * (int64_t)j;
-                pair_row<T, Q>(row[j], xi, yi, zi, xj[0], xj[1], xj[2], gx, gy, gz, s);
-            }
-#else
             using Vec = typename Traits<T>::Vec;
             const int c = (part + tr * WPR) * COLS + lane * Traits<T>::VPL;
             const Vec dv = *reinterpret_cast<const Vec *>(row + c);
@@ -1673,7 +1913,6 @@ __global__ __launch_bounds__(256) void row_owner_kernel(
                 pair_row<T, Q>(dv.x, xi, yi, zi, a.x, a.y, b.x, gx, gy, gz, s);
                 pair_row<T, Q>(dv.y, xi, yi, zi, b.y, q.x, q.y, gx, gy, gz, s);
             }
-#endif
         };
         // fp32: 4 trips (8 pairs per lane) in flight; fp64: unrolling costs more in
         // registers than it hides (N=2,500: 18.3 us per iteration unrolled, 14.4 rolled)
@@ -1706,9 +1945,9 @@ __global__ __launch_bounds__(256) void row_owner_kernel(
             const T c = bin_scale[i];
             g0 = c * g0; g1 = c * g1; g2 = c * g2;
         }
-        const T vx = mu * V[o] - lr * g0;
-        const T vy = mu * V[o + 1] - lr * g1;
-        const T vz = mu * V[o + 2] - lr * g2;
+        const T vx = momentum_velocity(mu, V[o], lr, g0);
+        const T vy = momentum_velocity(mu, V[o + 1], lr, g1);
+        const T vz = momentum_velocity(mu, V[o + 2], lr, g2);
         V[o] = vx; V[o + 1] = vy; V[o + 2] = vz;
         Xout[o] = xi + vx; Xout[o + 1] = yi + vy; Xout[o + 2] = zi + vz;
     }
@@ -1725,17 +1964,14 @@ __global__ __launch_bounds__(256) void units_to_full_kernel(const T *__restrict_
                                                             int64_t n_bins) {
     constexpr int VW = Lay<T, W>::VW, RPU = Lay<T, W>::RPU;
     const int64_t ul = blockIdx.x;
-    const int2 dsc = udesc[ul];
     const T *in = units + ul * (RPU * VW);
-    for (int e = threadIdx.x; e < RPU * VW; e += 256) {
-        const int r = e / VW, c = e % VW;
-        const int64_t i = (int64_t)dsc.x + r, j = (int64_t)dsc.y + c;
-        if (j > i && j < n_bins) {
+    for_each_cell<T, W>(udesc[ul], n_bins, [&](int e, int64_t i, int64_t j, bool stored) {
+        if (stored) {
             const T v = in[e];
             full[i * ld + j] = v;
             full[j * ld + i] = v;
         }
-    }
+    });
 }
 
 // Per bin: how many of this rank's stored pairs constrain it (delta > 0) -- the degrees a step

@@ -658,8 +658,9 @@ def test_product_kernels_do_not_spill():
     spills = {k: v["scratch"] for k, v in meta.items() if v["scratch"] > 0}
     assert not spills, "kernels with scratch: %r" % spills
     sweeps = {k: v for k, v in meta.items() if "stress_grad_kernel" in k}
-    # one per layout (fp32, fp64 wide, fp64 narrow) x NT x OP x WPB (4; 8 for the 512-wide)
-    assert len(sweeps) == 20, sorted(sweeps)
+    # one per layout (fp32, fp64 wide, fp64 narrow) x NT x OP (stress, matvec, W1, W2) x WPB
+    # (4; 8 for the 512-wide)
+    assert len(sweeps) == 40, sorted(sweeps)
     for k, v in sweeps.items():
         if "IfLb" in k:                       # fp32: two workgroups of 8 waves per CU
             assert v["vgpr"] <= 128, (k, v)
