@@ -369,34 +369,80 @@ __device__ __forceinline__ double swap_sum32(double t) {
     return __hiloint2double((int)b[0], (int)a[0]) + __hiloint2double((int)b[1], (int)a[1]);
 }
 
-// The three sums of a matrix row (x, y, z components) over the 64 lanes in 10 VALU
-// instructions instead of 18 (round 3; the sweep is issue-bound at the clock the chip runs it
-// at, see the kernel's comment).  gfx950's lane swaps exchange half of one register with the
-// other half of a second one, so ONE swap + ONE add both adds across the halves and sorts two
-// sums apart: after the 32-lane step the lower half holds x, the upper y (z is folded with
-// itself); after the 16-lane step the even 16-lane rows hold x | y, the odd ones z; four DPP
-// steps then add up each row.  Result: the row's x total in every lane 0..15, z in 16..31
-// and 48..63, y in 32..47.  Fixed tree: bitwise reproducible.
-__device__ __forceinline__ float row_sum3_swap(float gx, float gy, float gz) {
-    const auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(gx), __float_as_uint(gy), false, false);
-    const float xy = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(gz), __float_as_uint(gz), false, false);
-    const float zz = __uint_as_float(b[0]) + __uint_as_float(b[1]);
-    const auto c = __builtin_amdgcn_permlane16_swap(__float_as_uint(xy), __float_as_uint(zz), false, false);
-    float w = __uint_as_float(c[0]) + __uint_as_float(c[1]);
-    w += dpp_get<0xB1, 0xF>(w);   // quad_perm [1,0,3,2]
-    w += dpp_get<0x4E, 0xF>(w);   // quad_perm [2,3,0,1]
-    w += dpp_get<0x141, 0xF>(w);  // row_half_mirror
-    w += dpp_get<0x140, 0xF>(w);  // row_mirror
+// The 12 row sums of an fp32 unit (4 matrix rows x 3 components) over the 64 lanes, as ONE
+// transposed reduction: 12 registers of per-lane partials in, one register out that holds
+// every total.  gfx950's lane swaps exchange half of one register with the other half of a
+// second one, so ONE swap + ONE add both adds across the halves and sorts two sums apart --
+// registers and lane span halve together:
+//   v_permlane32_swap + add   12 -> 6 registers: lanes 0..31 hold the first sum of a pair,
+//                             lanes 32..63 the second
+//   v_permlane16_swap + add    6 -> 3 registers: the even 16-lane rows hold the first register's
+//                             two sums, the odd rows the second's
+//   row16_sum3                 3 -> 1: the totals of the 16-lane rows of three registers
+// 6 + 3 swaps, 9 adds and 7 DPP adds per unit, against 4 x (3 swaps + 3 adds + 4 DPP adds + one
+// select) for a tree per matrix row.  Fixed tree: bitwise reproducible.
+__device__ __forceinline__ float swap_add32(float a, float b) {
+    const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return __uint_as_float(s[0]) + __uint_as_float(s[1]);
+}
+__device__ __forceinline__ float swap_add16(float a, float b) {
+    const auto s = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return __uint_as_float(s[0]) + __uint_as_float(s[1]);
+}
+// Sums over each 16-lane row of a, b and c.  The write mask of a DPP instruction has a bit per
+// bank of 4 lanes, which lets the DPP steps halve the registers too: after row_mirror a row's
+// lanes 0..7 hold all there is of it, so lanes 8..15 of the same register take c's; after
+// row_half_mirror lanes 0..3 do, and lanes 4..7 take b's.  Result: in every 16-lane row, a's
+// total in lanes 0..3, b's in 4..7, c's in 8..11 (12..15: c's again).  One asm block for the
+// same reason as wave_sum_hi3: a DPP read needs 2 wait states after the VALU write of its
+// source, and the block places its own (the inputs were just written by VALU code).
+__device__ __forceinline__ float row16_sum3(float a, float b, float c) {
+    float t, u, w;
+    asm("s_nop 1\n\t"
+        "v_add_f32_dpp %0, %3, %3 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %0, %5, %5 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %1, %4, %4 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_add_f32_dpp %2, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %2, %1, %1 row_half_mirror row_mask:0xf bank_mask:0x2\n\t"
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %2, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %2, %2, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
+        : "=&v"(t), "=v"(u), "=v"(w)   // u and w are written when a, b and c have been read
+        : "v"(a), "v"(b), "v"(c));
     return w;
 }
-// which of a unit's 12 row sums a lane keeps under row_sum3_swap: row r = lane % 16 (< 4) of
-// component x (lanes 0..3), z (16..19) or y (32..35); -1: none
-__device__ __forceinline__ int swap_rowsum_slot(int lane) {
-    const int r = lane & 15;
-    if (r >= 4 || lane >= 48) return -1;
-    return 3 * r + (lane < 16 ? 0 : (lane < 32 ? 2 : 1));
+// The tree above the 16-lane rows.  g[3 * r + c]: this lane's partial of component c of matrix
+// row r = the unit's row sum number 3 r + c.  Pairs (2i, 2i + 1) meet in the 32-lane step (h),
+// registers (2m, 2m + 1) in the 16-lane step (m), so register m of the last step holds the sums
+// 4m, 4m + 2, 4m + 1, 4m + 3 in its rows 0..3 (swap_rowsum_slot is the inverse of this).
+// row_sums_step<R> does every step whose inputs are there after matrix row R -- the tree is the
+// same wherever its steps are issued, and at most three registers of it live across a row's
+// pair math instead of nine.
+template <int R>
+__device__ __forceinline__ void row_sums_step(const float (&g)[12], float (&h)[6], float (&m)[3]) {
+    if constexpr (R == 0) h[0] = swap_add32(g[0], g[1]);
+    if constexpr (R == 1) {
+        h[1] = swap_add32(g[2], g[3]); h[2] = swap_add32(g[4], g[5]);
+        m[0] = swap_add16(h[0], h[1]);
+    }
+    if constexpr (R == 2) { h[3] = swap_add32(g[6], g[7]); m[1] = swap_add16(h[2], h[3]); }
+    if constexpr (R == 3) {
+        h[4] = swap_add32(g[8], g[9]); h[5] = swap_add32(g[10], g[11]);
+        m[2] = swap_add16(h[4], h[5]);
+    }
 }
+// which of a unit's 12 row sums a lane holds after row_sums_step + row16_sum3.  EVERY lane holds
+// one: the four lanes of a bank carry the same bits (the last two steps add the same four
+// values, and a + b = b + a bit for bit), and so do banks 2 and 3 (what lanes 12..15 add up is
+// what lanes 11..8 do, operands swapped).
+__device__ __forceinline__ int swap_rowsum_slot(int lane) {
+    const int row = lane >> 4, bank = (lane >> 2) & 3;
+    return 4 * (bank < 3 ? bank : 2) + ((row & 1) << 1) + (row >> 1);
+}
+// the lane that stores the sum: the first of the banks 0..2 of every 16-lane row
+__device__ __forceinline__ bool swap_rowsum_stores(int lane) { return (lane & 3) == 0 && (lane & 12) != 12; }
 
 template <bool NT, int OP, typename XR, typename WIN>
 __device__ __forceinline__ void process_unit_f64w(double2 (&d)[8], const XR &xrow,
@@ -519,12 +565,15 @@ __device__ __forceinline__ void pair_step2(f32x2 delta, f32x2 xi, f32x2 yi, f32x
 }
 
 // d[] holds the unit's 8 wave-loads in row order: d[2*r + k] = row r, load k.
-// Row sums: row_sum3_swap per matrix row (10 VALU instructions against 18 for the 64-lane DPP
-// tree: profiles/r03_swap_rowsum_ab.txt).  Through the matrix pipe, as the fp64 unit does, they
-// measured 2.7-6 % slower at every size (164 VGPRs, the wait for the accumulator at the end of
-// every unit: profiles/r03_mfma_rowsum_ab.txt).  At two waves per SIMD the chip runs this kernel
-// at 1.75-1.83 GHz (power) and the SIMD's VALU is then busy most of a unit's time (418 VALU
-// instructions per unit and wave, 32 of them quarter-rate v_rsq_f32).
+// Row side: both loads of a matrix row run into ONE chain of packed accumulators (load 1
+// continues load 0's), whose halves are added once per row; the 12 per-lane partials of the
+// unit then go through one transposed reduction (row_sums_step, row16_sum3: 25 cross-lane and add
+// instructions per unit where a tree per matrix row took 56, and no select).  Through the
+// matrix pipe, as the fp64 unit does, the row sums measured 2.7-6 % slower at every size (164
+// VGPRs, the wait for the accumulator at the end of every unit:
+// profiles/r03_mfma_rowsum_ab.txt).  At two waves per SIMD the chip runs this kernel at
+// 1.75-1.83 GHz (power) and the SIMD's VALU is then busy most of a unit's time, so an
+// instruction less per unit is time (docs/MEASUREMENTS.md, machine code against the parent).
 template <bool NT, int OP, typename WIN>
 __device__ __forceinline__ void process_unit_f32(float4 (&d)[8], const float (&xrow)[12],
                                                  const WIN &next, StripF32 &st,
@@ -532,33 +581,32 @@ __device__ __forceinline__ void process_unit_f32(float4 (&d)[8], const float (&x
                                                  unsigned row_voff, int stage_idx) {
     extern __shared__ __attribute__((aligned(16))) float row_lds[];
     f32x2 s2 = {0.f, 0.f};
-    // The 12 row sums of the unit are collected into lanes 0..3, 16..19 and 32..35 of one
-    // register and leave with ONE 48-byte store per unit: a 12-byte store per row costs as
-    // much VMEM issue as a 1-KiB load and measured 5.6 % of the kernel.
-    float keep = 0.f;
-    // the matrix row of the unit whose sum this lane keeps, or -1
-    const int swap_role = (((threadIdx.x & 15) < 4) && ((threadIdx.x & 63) < 48)) ? (int)(threadIdx.x & 15) : -1;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
+    float g[12], h[6], m[3];  // the unit's 12 row sums on their way through the tree
+    auto row = [&](auto rc) __attribute__((always_inline)) {
+        constexpr int r = decltype(rc)::value;
         const float xs = xrow[3 * r], ys = xrow[3 * r + 1], zs = xrow[3 * r + 2];
         const f32x2 xi = {xs, xs}, yi = {ys, ys}, zi = {zs, zs};
-        f32x2 rx, ry, rz, qx, qy, qz;  // row-side sums of load 0 / load 1
+        f32x2 rx, ry, rz;  // row-side sums of the row's 8 pairs
         pair_step2<0, 0, true, OP>(f32x2{d[2 * r].x, d[2 * r].y}, xi, yi, zi, st, rx, ry, rz, s2);
         pair_step2<0, 1, false, OP>(f32x2{d[2 * r].z, d[2 * r].w}, xi, yi, zi, st, rx, ry, rz, s2);
         d[2 * r] = next.template load<NT>(2 * r);
         // (no sched_barrier here: letting the scheduler mix the rows of a unit measured
         // 1 % faster at N=50k and 6 % faster at 1/8 size; it stays within 125 VGPRs)
-        pair_step2<1, 0, true, OP>(f32x2{d[2 * r + 1].x, d[2 * r + 1].y}, xi, yi, zi, st, qx, qy, qz, s2);
-        pair_step2<1, 1, false, OP>(f32x2{d[2 * r + 1].z, d[2 * r + 1].w}, xi, yi, zi, st, qx, qy, qz, s2);
+        pair_step2<1, 0, false, OP>(f32x2{d[2 * r + 1].x, d[2 * r + 1].y}, xi, yi, zi, st, rx, ry, rz, s2);
+        pair_step2<1, 1, false, OP>(f32x2{d[2 * r + 1].z, d[2 * r + 1].w}, xi, yi, zi, st, rx, ry, rz, s2);
         d[2 * r + 1] = next.template load<NT>(2 * r + 1);
-        rx += qx; ry += qy; rz += qz;
-        const float gx = rx.x + rx.y, gy = ry.x + ry.y, gz = rz.x + rz.y;
-        const float w = row_sum3_swap(gx, gy, gz);
-        keep = (swap_role == r) ? w : keep;
-    }
-    // both are issued for every unit and exactly one of them lands -- the LDS slot is a
-    // dummy word while the unit is stored directly, the store's lanes are all out of
-    // range (free) while the unit is parked (see the kernel's DEFER)
+        g[3 * r] = rx.x + rx.y; g[3 * r + 1] = ry.x + ry.y; g[3 * r + 2] = rz.x + rz.y;
+        row_sums_step<r>(g, h, m);
+    };
+    row(std::integral_constant<int, 0>{});
+    row(std::integral_constant<int, 1>{});
+    row(std::integral_constant<int, 2>{});
+    row(std::integral_constant<int, 3>{});
+    const float keep = row16_sum3(m[0], m[1], m[2]);   // every sum in its lane (swap_rowsum_slot)
+    // both are issued for every unit and exactly one of them counts -- while the unit is
+    // stored directly the LDS write goes to the wave's parking slot 0, which the first parked
+    // unit overwrites; the store's lanes are all out of range (free) while the unit is
+    // parked (see the kernel's DEFER)
     row_lds[stage_idx] = keep;
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(keep), row_rsrc, row_voff, 0, 0);
     stress += (double)(s2.x + s2.y);
@@ -804,14 +852,12 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
             rowpart + (int64_t)ua * (3 * Lay<T, W>::RPU), 0, (int)((unsigned)(ub - ua) * kRowBytes),
             0x00020000);
 
-        // fp32: which of a unit's 12 row sums this lane holds -- lanes 0..3 / 16..19 / 32..35
-        // after the lane swaps (row_sum3_swap) -- and what follows from it for the unit's
-        // store offset and parking slot
+        // fp32: which of a unit's 12 row sums this lane holds after the unit's reduction
+        // (row16_sum3: every lane holds one, lanes 0, 4 and 8 of every 16-lane row store it)
+        // and what follows from it for the unit's store offset and parking slot
         const int f32_sl12 = swap_rowsum_slot(lane);
-        const unsigned f32_voff_lane = f32_sl12 >= 0 ? (unsigned)f32_sl12 * 4u : 0x40000000u;
-        const int f32_lds_dummy = stage0 + cap_units * 12 + (lane & 3);
-        const int f32_lds_real = f32_sl12 >= 0 ? stage0 + f32_sl12 : f32_lds_dummy;
-        const int f32_m12 = f32_sl12 >= 0 ? 12 : 0;
+        const unsigned f32_voff_lane = swap_rowsum_stores(lane) ? (unsigned)f32_sl12 * 4u : 0x40000000u;
+        const int f32_lds_lane = stage0 + f32_sl12;
         auto unit_step = [&](int u) __attribute__((always_inline)) {
             if constexpr (WPB == 8) {
                 // pace keeping (see the kernel's comment): the partner's count was read
@@ -833,18 +879,20 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
             const int k = u - ua;
             const bool parked = k >= park_from;
             if constexpr (sizeof(T) == 4) {
-                // fp32: 12 lanes hold one of the unit's 12 sums each.  Units before
+                // fp32: every lane holds one of the unit's 12 sums.  Units before
                 // park_from are stored directly; the later ones are parked in LDS slot
                 // (k - park_from) and their store is dropped (every lane out of range).
-                // per-lane parts are loop constants (f32_voff_lane, f32_lds_real / _dummy,
-                // f32_m12: below the lambda's captures), per-unit parts scalar: one v_add, one
-                // v_cndmask, one v_mad per unit instead of a chain of selects.  A store is out
-                // of range (dropped) unless the lane holds a sum AND the unit is not parked:
-                // 0x40000000 from either side puts the offset beyond any chunk.
+                // Per-lane parts are loop constants (f32_voff_lane, f32_lds_lane: below the
+                // lambda's captures), per-unit parts scalar: one v_add each per unit.  A store
+                // is out of range (dropped) unless the lane is the one that stores its sum AND
+                // the unit is not parked: 0x40000000 from either side puts the offset beyond
+                // any chunk.  The LDS write of a unit that is stored directly goes to slot 0:
+                // the parked units come after it, and the first of them overwrites that slot
+                // (LDS operations of one wave execute in program order).  The lanes that hold
+                // the same sum write the same bits to the same word.
                 const unsigned row_voff =
                     f32_voff_lane + (parked ? 0x40000000u : (unsigned)k * kRowBytes);
-                const int stage_slot = (parked ? f32_lds_real : f32_lds_dummy) +
-                                       (parked ? k - park_from : 0) * f32_m12;
+                const int stage_slot = f32_lds_lane + (parked ? k - park_from : 0) * 12;
                 float xs12[12];             // scalar registers
 #pragma unroll
                 for (int q = 0; q < 12; ++q) xs12[q] = xr.get(q);
@@ -916,7 +964,11 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
             const int n4 = ((ub - ua) - park_from) * 3;   // float4 count
             float4 *dst = reinterpret_cast<float4 *>(rowpart + ((int64_t)ua + park_from) *
                                                                    (3 * Lay<T, W>::RPU));
-            for (int q = lane; q < n4; q += 64) {
+            // (the lane number afresh: hipcc otherwise keeps the prologue's 64-bit `lane` alive
+            // through the whole sweep for this loop's index, two registers the fp32 unit
+            // does not have -- scratch in the 4-wave matvec form)
+            const int lane_q = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            for (int q = lane_q; q < n4; q += 64) {
                 const float *src = row_lds + stage0 + 4 * q;
                 dst[q] = make_float4(src[0], src[1], src[2], src[3]);
             }
