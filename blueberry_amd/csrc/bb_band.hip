@@ -11,8 +11,6 @@
 // shuffle reduction, one integer atomic per workgroup).
 #include <algorithm>
 #include <cstdlib>
-#include <map>
-#include <mutex>
 
 #include "bb_common.h"
 
@@ -124,29 +122,14 @@ __global__ __launch_bounds__(kIB) void band_count_sorted_kernel(
     }
 }
 
-// Per-device scratch kept between calls (stream, device buffers): creating a
-// stream and two allocations per call cost ~4 ms, ten times the reference's CPU
-// time for a 1,000-bin chromosome.  Guarded by a mutex: calls on one device
-// serialise, which is what one stream would do anyway.
-struct BandCtx {
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    double *d_r = nullptr;
-    int64_t cap = 0;
-    unsigned long long *d_out = nullptr;
+// Per-device scratch kept between calls (stream, device arena, pinned result words):
+// creating a stream and two allocations per call cost ~4 ms, ten times the reference's CPU
+// time for a 1,000-bin chromosome.  The arena holds the two counter words the kernels add
+// into, then the regions; it is kept, whatever its size.
+constexpr size_t kOutBytes = 2 * sizeof(unsigned long long), kRegionsAt = 256;
+struct BandScratch : bb::DeviceScratch {
     unsigned long long *h_out = nullptr;  // pinned
 };
-
-BandCtx *band_ctx(int device) {
-    static std::mutex table_mu;
-    static std::map<int, BandCtx *> table;
-    std::lock_guard<std::mutex> lock(table_mu);
-    auto it = table.find(device);
-    if (it != table.end()) return it->second;
-    BandCtx *c = new BandCtx();   // lives for the process: freed by the runtime at exit
-    table[device] = c;
-    return c;
-}
 
 }  // namespace
 
@@ -165,65 +148,51 @@ int bb_band_count_rows(const double *regions, int64_t n, int32_t low, int32_t hi
     if (i_end > n) i_end = n;
     if (n < 2 || i_begin >= i_end || i_end < 2) return BB_OK;  // no (i, j < i) pair
 
-    BandCtx *c = band_ctx(device);
+    BandScratch *c = bb::per_device<BandScratch>(device);
     std::lock_guard<std::mutex> lock(c->mu);
-    hipError_t e = hipSuccess;
-    if (!c->stream) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e == hipSuccess && !c->d_out) e = hipMalloc((void **)&c->d_out, 2 * sizeof(unsigned long long));
-    if (e == hipSuccess && !c->h_out)
-        e = hipHostMalloc((void **)&c->h_out, 2 * sizeof(unsigned long long), hipHostMallocDefault);
-    if (e == hipSuccess && c->cap < n) {
-        (void)hipFree(c->d_r);
-        c->d_r = nullptr;
-        c->cap = 0;
-        e = hipMalloc((void **)&c->d_r, (size_t)n * sizeof(double));
-        if (e == hipSuccess) c->cap = n;
-    }
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_NOMEM, std::string("bb_band_count: ") + hipGetErrorString(e));
+    hipError_t e = c->reserve(kRegionsAt + (size_t)n * sizeof(double));
+    if (e == hipSuccess && !c->h_out) e = hipHostMalloc((void **)&c->h_out, kOutBytes, hipHostMallocDefault);
+    BB_TRY(bb::hip_status("bb_band_count", e, BB_ERR_NOMEM));
     hipStream_t st = c->stream;
-    e = hipMemcpyAsync(c->d_r, regions, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st);
+    unsigned long long *d_out = (unsigned long long *)c->buf.p;
+    double *d_r = (double *)((char *)c->buf.p + kRegionsAt);
+    e = hipMemcpyAsync(d_r, regions, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st);
     const int64_t rows = i_end - i_begin;
     // sorted input (every ContactMap's regions): two binary searches per row; the kernel
     // reports in out[1] if the order it relies on does not hold.  BB_BAND_SORTED=0: never.
     const char *env = getenv("BB_BAND_SORTED");
     bool brute = env && atoi(env) == 0;
     if (!brute) {
-        if (e == hipSuccess) e = hipMemsetAsync(c->d_out, 0, 2 * sizeof(unsigned long long), st);
+        if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, kOutBytes, st);
         if (e == hipSuccess) {
             const int64_t want = std::max<int64_t>(rows, std::min<int64_t>(n, 1 << 16));
             e = bb::launch(band_count_sorted_kernel, dim3((unsigned)((want + kIB - 1) / kIB)), dim3(kIB),
-                           0, st, c->d_r, n, (double)low, (double)high, i_begin, i_end, c->d_out);
+                           0, st, d_r, n, (double)low, (double)high, i_begin, i_end, d_out);
         }
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(c->h_out, c->d_out, 2 * sizeof(unsigned long long),
-                               hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->h_out, d_out, kOutBytes, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess)
-            return bb::fail(BB_ERR_HIP, std::string("bb_band_count: ") + hipGetErrorString(e));
+        BB_TRY(bb::hip_status("bb_band_count", e));
         if (c->h_out[1] == 0) {
             *count = (int64_t)c->h_out[0];
             return BB_OK;
         }
         brute = true;                      // not sorted (or not finite): the double loop
     }
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_out, 0, sizeof(unsigned long long), st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, sizeof(unsigned long long), st);
     if (e == hipSuccess) {
         const dim3 grid((unsigned)((i_end - 1 + kJC - 1) / kJC), (unsigned)((rows + kIB - 1) / kIB));
         if (grid.y > 65535u) {
             e = hipErrorInvalidValue;
         } else {
-            e = bb::launch(band_count_kernel, grid, dim3(kIB), 0, st, c->d_r, n, (double)low,
-                           (double)high, i_begin, i_end, c->d_out);
+            e = bb::launch(band_count_kernel, grid, dim3(kIB), 0, st, d_r, n, (double)low,
+                           (double)high, i_begin, i_end, d_out);
         }
     }
     if (e == hipSuccess)
-        e = hipMemcpyAsync(c->h_out, c->d_out, sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+        e = hipMemcpyAsync(c->h_out, d_out, sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_HIP, std::string("bb_band_count: ") + hipGetErrorString(e));
-    const unsigned long long host_out = *c->h_out;
-    *count = (int64_t)host_out;
+    BB_TRY(bb::hip_status("bb_band_count", e));
+    *count = (int64_t)*c->h_out;
     return BB_OK;
 }
 

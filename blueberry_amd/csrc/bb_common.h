@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <map>
+#include <mutex>
 #include <string>
 #include <tuple>
 #include <utility>
@@ -16,6 +18,12 @@ namespace bb {
 // Thread-local last-error message behind bb_last_error().
 void set_error(const std::string &msg);
 int fail(int code, const std::string &msg);
+
+// The status of a HIP call as the library's return code: BB_OK, or `code` with "<who>: <HIP's
+// text>" as the last error.  An allocation stage passes BB_ERR_NOMEM whatever HIP said.
+inline int hip_status(const char *who, hipError_t e, int code = BB_ERR_HIP) {
+    return e == hipSuccess ? (int)BB_OK : fail(code, std::string(who) + ": " + hipGetErrorString(e));
+}
 
 #define BB_HIP_CHECK(expr)                                                              \
     do {                                                                                \
@@ -102,5 +110,41 @@ struct DevBuf {
     ~DevBuf() { (void)hipFree(p); }
     hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
 };
+
+// A grow-only device allocation: reserve() keeps what is there when it is large enough, else
+// frees it and allocates anew (the contents are lost).  A failed reserve leaves the buffer
+// empty and consumes the failed hipMalloc's error on the spot (see launch() above).
+struct GrowBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    hipError_t reserve(size_t need);
+    void release();
+};
+
+// Scratch kept per device between calls: a stream made on first use and ONE grow-only arena,
+// guarded by a mutex -- calls that share a scratch serialise, which is what one stream would
+// do anyway.  What it saves, and when the arena is given back, is told where each is used.
+struct DeviceScratch {
+    std::mutex mu;
+    hipStream_t stream = nullptr;
+    GrowBuf buf;
+    // the stream (created now if there is none yet) and at least `bytes` of arena
+    hipError_t reserve(size_t bytes) {
+        const hipError_t e = stream ? hipSuccess : hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+        return e == hipSuccess ? buf.reserve(bytes) : e;
+    }
+};
+
+// The T of a device, one table per type T: never NULL, made on first use, lives for the
+// process (freed by the runtime at exit).
+template <typename T>
+T *per_device(int device) {
+    static std::mutex table_mu;
+    static std::map<int, T *> table;
+    std::lock_guard<std::mutex> lock(table_mu);
+    T *&slot = table[device];
+    if (!slot) slot = new T();
+    return slot;
+}
 
 }  // namespace bb

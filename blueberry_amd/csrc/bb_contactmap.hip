@@ -15,8 +15,6 @@
 #include <math.h>
 
 #include <algorithm>
-#include <map>
-#include <mutex>
 #include <vector>
 
 #include "bb_cm_internal.h"
@@ -181,11 +179,19 @@ __global__ __launch_bounds__(kNT * 8) void normalize128_kernel(double *m, int64_
 // array (pyx:111-113), (3, 1) for C-ordered (n, 3) rows.  `present` (d bytes, may be NULL)
 // gets a 1 for every bin a position falls in, `offgrid` a 1 if some position is not exactly
 // bin * resolution -- what the caller needs to write down `regions` without sorting.
-// numpy.nan_to_num with its defaults (pyx:102), applied to a triple's values as they are read:
-// the 240 MB of a chr1@10kb file need no pass over them on the host
-__device__ __forceinline__ double scatter_value(double v) {
-    return v != v ? 0.0 : (v > 1.7976931348623157e308 ? 1.7976931348623157e308
-                                                      : (v < -1.7976931348623157e308 ? -1.7976931348623157e308 : v));
+// numpy.nan_to_num with its defaults (pyx:102) is applied to a triple's values as they are
+// read: the 240 MB of a chr1@10kb file need no pass over them on the host.
+//
+// The two bins of a triple with the (nan_to_num'ed) positions pj, pk; false if one of them is
+// outside [0, d).  (A position beyond the int range -- an infinity turned into 1.8e308 -- is
+// out of range whatever the cast would make of it.)
+__device__ __forceinline__ bool triple_bins(double pj, double pk, double resolution, int64_t d,
+                                            int &j, int &k) {
+    const double qj = pj / resolution, qk = pk / resolution;
+    const bool wild = !(qj > -2147483648.0 && qj < 2147483648.0 && qk > -2147483648.0 && qk < 2147483648.0);
+    j = wild ? -1 : (int)qj;
+    k = wild ? -1 : (int)qk;
+    return !(j < 0 || k < 0 || j >= d || k >= d);
 }
 
 __global__ void scatter_mark_kernel(const double *__restrict__ tr, int64_t n, int64_t st, int64_t sc,
@@ -193,13 +199,9 @@ __global__ void scatter_mark_kernel(const double *__restrict__ tr, int64_t n, in
                                     unsigned char *__restrict__ present, int *__restrict__ offgrid) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
-    const double pj = scatter_value(tr[t * st]), pk = scatter_value(tr[t * st + sc]);
-    // (a position beyond the int range -- an infinity turned into 1.8e308 -- is out of range
-    // whatever the cast would make of it)
-    const double qj = pj / resolution, qk = pk / resolution;
-    const bool wild = !(qj > -2147483648.0 && qj < 2147483648.0 && qk > -2147483648.0 && qk < 2147483648.0);
-    const int j = wild ? -1 : (int)qj, k = wild ? -1 : (int)qk;
-    if (j < 0 || k < 0 || j >= d || k >= d) {
+    const double pj = nan_to_num(tr[t * st]), pk = nan_to_num(tr[t * st + sc]);
+    int j, k;
+    if (!triple_bins(pj, pk, resolution, d, j, k)) {
         atomicExch(bad, 1);
         return;
     }
@@ -218,11 +220,9 @@ __global__ void scatter_store_kernel(const double *__restrict__ tr, int64_t n, i
                                      double resolution, int64_t d, double *m) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
-    const double qj = scatter_value(tr[t * st]) / resolution, qk = scatter_value(tr[t * st + sc]) / resolution;
-    const bool wild = !(qj > -2147483648.0 && qj < 2147483648.0 && qk > -2147483648.0 && qk < 2147483648.0);
-    const int j = wild ? -1 : (int)qj, k = wild ? -1 : (int)qk;
-    if (j < 0 || k < 0 || j >= d || k >= d) return;
-    const double c = scatter_value(tr[t * st + 2 * sc]);
+    int j, k;
+    if (!triple_bins(nan_to_num(tr[t * st]), nan_to_num(tr[t * st + sc]), resolution, d, j, k)) return;
+    const double c = nan_to_num(tr[t * st + 2 * sc]);
     unsigned long long *cells = reinterpret_cast<unsigned long long *>(m);
     // a cell still holding t + 1 is ours; j == k names one cell twice, harmlessly
     if (cells[(int64_t)j * d + k] == (unsigned long long)(t + 1)) m[(int64_t)j * d + k] = c;
@@ -424,44 +424,24 @@ __global__ __launch_bounds__(1024) void symv_reduce_kernel(const double *__restr
     }
 }
 
-// out[j] = V[j] . w for the basis vectors j < k (one workgroup each); fixed-order sums
+// part[j * S + s] = segment s of V[j] . w for the basis vectors j < k: one workgroup per
+// (vector, segment), S = gridDim.y segments, fixed-order sums.  S = 1 is the whole dot, written
+// straight to its place; for long vectors S = kDotSegs, and lanczos_scalars_kernel adds a
+// vector's segments in order.  One workgroup per vector walked d = 25k doubles in 19-30 us on
+// 1 to 48 CUs, three times per Lanczos step: more than a tenth of the step.
+constexpr int kDotSegs = 16;
 __global__ __launch_bounds__(256) void basis_dots_kernel(const double *__restrict__ V, int64_t d,
                                                          const double *__restrict__ w,
-                                                         double *__restrict__ out) {
+                                                         double *__restrict__ part) {
     __shared__ double sh[256];
     const double *v = V + (int64_t)blockIdx.x * d;
-    double a = 0.0;
-    for (int64_t i = threadIdx.x; i < d; i += 256) a = fma(v[i], w[i], a);
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
-}
-
-// The same in two stages for long vectors: segment s of kDotSegs of vector j -> part[j *
-// kDotSegs + s]; lanczos_finish_kernel adds a vector's segments in order.  One workgroup
-// per vector walked d = 25k doubles in 19-30 us on 1 to 48 CUs, three times per Lanczos
-// step: more than a tenth of the step.
-constexpr int kDotSegs = 16;
-__global__ __launch_bounds__(256) void basis_dots_part_kernel(const double *__restrict__ V, int64_t d,
-                                                              const double *__restrict__ w,
-                                                              double *__restrict__ part) {
-    __shared__ double sh[256];
-    const double *v = V + (int64_t)blockIdx.x * d;
-    const int64_t per = (d + kDotSegs - 1) / kDotSegs;
+    // (a 32-bit division: the edge of a map is at most 2,000,000, bb_cm_create)
+    const int64_t per = ((unsigned)d + gridDim.y - 1) / gridDim.y;
     const int64_t i0 = (int64_t)blockIdx.y * per, i1 = std::min<int64_t>(d, i0 + per);
     double a = 0.0;
     for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) a = fma(v[i], w[i], a);
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[(int64_t)blockIdx.x * kDotSegs + blockIdx.y] = sh[0];
+    a = bb::block_sum_256(a, sh);
+    if (threadIdx.x == 0) part[(int64_t)blockIdx.x * gridDim.y + blockIdx.y] = a;
 }
 
 // w -= sum_{j<k} c[j] V[j]
@@ -787,30 +767,45 @@ hipError_t symv_enqueue(bb_cm *cm, const double *dx, double *dy) {
         });
         const size_t item_bytes = (items.size() * sizeof(int2) + 255) & ~(size_t)255;
         const size_t need = item_bytes + (size_t)(nseg + nrb) * (size_t)d * 8;
-        if (need > cm->sv_bytes) {
-            (void)hipFree(cm->sv_buf);
-            cm->sv_buf = nullptr;
-            cm->sv_bytes = 0;
-            hipError_t e = hipMalloc(&cm->sv_buf, need);
-            if (e != hipSuccess) return e;
-            cm->sv_bytes = need;
-        }
-        hipError_t e = hipMemcpyAsync(cm->sv_buf, items.data(), items.size() * sizeof(int2),
-                                      hipMemcpyHostToDevice, cm->stream);
+        hipError_t e = cm->sv.reserve(need);
+        if (e != hipSuccess) return e;
+        e = hipMemcpyAsync(cm->sv.p, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice,
+                           cm->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(cm->stream);   // `items` dies with this scope
         if (e != hipSuccess) return e;
         cm->sv_items = (int)items.size();
         cm->sv_d = d;
     }
     const size_t item_bytes = ((size_t)cm->sv_items * sizeof(int2) + 255) & ~(size_t)255;
-    double *rowpart = (double *)((char *)cm->sv_buf + item_bytes);
+    double *rowpart = (double *)((char *)cm->sv.p + item_bytes);
     double *colpart = rowpart + nseg * d;
     hipError_t e = bb::launch(symv_upper_kernel, dim3((unsigned)cm->sv_items), dim3(256), 0, cm->stream,
-                              (const double *)cm->m, d, dx, (const int2 *)cm->sv_buf, rowpart, colpart);
+                              (const double *)cm->m, d, dx, (const int2 *)cm->sv.p, rowpart, colpart);
     if (e == hipSuccess)
         e = bb::launch(symv_reduce_kernel, dim3((unsigned)((d + 127) / 128)), dim3(1024), 0, cm->stream,
                        (const double *)rowpart, (const double *)colpart, d, (int)nseg, dy);
     return e;
+}
+
+// sums[c] = column c's marginal (column_sums_kernel), enqueued on the handle's stream
+hipError_t column_sums_enqueue(const bb_cm *cm, double *sums) {
+    return bb::launch(column_sums_kernel, dim3((unsigned)((cm->d + kSumWG - 1) / kSumWG)), dim3(kSumWG), 0,
+                      cm->stream, (const double *)cm->m, cm->d, sums);
+}
+
+// The round-1 entry points' shape: a handle around a host matrix for the length of one call --
+// create, upload if asked, run, download, destroy -- reporting the error of the step that failed.
+template <typename Run>
+int with_host_matrix(double *matrix, int64_t d, int device, bool upload, Run &&run) {
+    bb_cm *cm = nullptr;
+    int rc = bb_cm_create(&cm, d, device);
+    if (rc == BB_OK && upload) rc = bb_cm_upload(cm, matrix, d);
+    if (rc == BB_OK) rc = run(cm);
+    if (rc == BB_OK) rc = bb_cm_download(cm, matrix, d);
+    const std::string keep = bb_last_error();
+    bb_cm_destroy(cm);
+    if (rc != BB_OK) bb::set_error(keep);
+    return rc;
 }
 
 // One Lanczos step's scalars, on the device (no host round trip inside a cycle):
@@ -857,26 +852,12 @@ __global__ __launch_bounds__(256) void scale_by_kernel(const double *__restrict_
 
 }  // namespace
 
-// correlation's two matrix-sized temporaries (centred rows, Gram matrix): ONE grow-only
-// allocation per DEVICE, shared by every map on it and guarded by a mutex (calls on one device
-// serialise, as bb_band.hip's context does).  Round 3 kept one per HANDLE for the map's
-// lifetime: a genome-wide loop holding one ContactMap per chromosome then held 3x the
-// matrices' memory.  bb_cm_release_scratch gives it back.  bb_cm_shortest_paths
-// (bb_shortest.hip) takes its work matrix from the same scratch (bb_cm_internal.h).
-namespace bb {
-CorrScratch *corr_scratch(int device) {
-    static std::mutex table_mu;
-    static std::map<int, CorrScratch *> table;
-    std::lock_guard<std::mutex> lock(table_mu);
-    auto it = table.find(device);
-    if (it != table.end()) return it->second;
-    CorrScratch *c = new CorrScratch();   // lives for the process
-    table[device] = c;
-    return c;
-}
-}  // namespace bb
-using bb::corr_scratch;
-using bb::CorrScratch;
+// correlation's two matrix-sized temporaries (centred rows, Gram matrix) live in the device's
+// CmScratch (bb_cm_internal.h): ONE grow-only allocation per DEVICE, shared by every map on it.
+// Round 3 kept one per HANDLE for the map's lifetime: a genome-wide loop holding one ContactMap
+// per chromosome then held 3x the matrices' memory.  bb_cm_release_scratch gives it
+// back.  bb_cm_shortest_paths (bb_shortest.hip) takes its work matrix from the same scratch.
+using bb::CmScratch;
 
 extern "C" {
 
@@ -896,8 +877,7 @@ int bb_cm_create(bb_cm **out, int64_t d, int device) {
     if (e == hipSuccess) e = hipStreamSynchronize(cm->stream);
     if (e != hipSuccess) {
         bb_cm_destroy(cm);
-        return bb::fail(e == hipErrorOutOfMemory ? BB_ERR_NOMEM : BB_ERR_HIP,
-                        std::string("bb_cm_create: ") + hipGetErrorString(e));
+        return bb::hip_status("bb_cm_create", e, e == hipErrorOutOfMemory ? BB_ERR_NOMEM : BB_ERR_HIP);
     }
     *out = cm;
     return BB_OK;
@@ -908,7 +888,7 @@ int bb_cm_destroy(bb_cm *cm) {
     (void)hipSetDevice(cm->device);
     bb::release_stream(cm->device, cm->stream);     // synchronises it
     (void)hipFree(cm->m);
-    (void)hipFree(cm->sv_buf);
+    cm->sv.release();
     delete cm;
     (void)hipGetLastError();   // tear-down is best effort; its errors end here
     return BB_OK;
@@ -962,8 +942,7 @@ int bb_cm_scatter_ex(bb_cm *cm, const double *triples, int64_t n, int32_t resolu
     hipError_t e = tr.alloc((size_t)n * 3 * sizeof(double));
     if (e == hipSuccess) e = bad.alloc(2 * sizeof(int));          // {bad, off the grid}
     if (e == hipSuccess && want) e = pres.alloc((size_t)d);
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_NOMEM, std::string("bb_cm_scatter: ") + hipGetErrorString(e));
+    BB_TRY(bb::hip_status("bb_cm_scatter", e, BB_ERR_NOMEM));
     hipStream_t st = cm->stream;
     int host_flags[2] = {0, 0};
     if (n > 0) e = hipMemcpyAsync(tr.p, triples, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, st);
@@ -983,8 +962,7 @@ int bb_cm_scatter_ex(bb_cm *cm, const double *triples, int64_t n, int32_t resolu
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipMemcpy(host_flags, bad.p, 2 * sizeof(int), hipMemcpyDeviceToHost);
     if (e == hipSuccess && want) e = hipMemcpy(present, pres.p, (size_t)d, hipMemcpyDeviceToHost);
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_HIP, std::string("bb_cm_scatter: ") + hipGetErrorString(e));
+    BB_TRY(bb::hip_status("bb_cm_scatter", e));
     if (host_flags[0]) {
         // marks of valid triples may be left in the matrix: clear it, the map is unusable
         (void)hipMemset(cm->m, 0, (size_t)d * d * sizeof(double));
@@ -1008,8 +986,7 @@ int bb_cm_normalize(bb_cm *cm, int64_t n_bins, const double *KRnorm, const doubl
     bb::DevBuf kr, ke;
     hipError_t e = kr.alloc((size_t)n_bins * sizeof(double));
     if (e == hipSuccess) e = ke.alloc((size_t)n_bins * sizeof(double));
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_NOMEM, std::string("bb_cm_normalize: ") + hipGetErrorString(e));
+    BB_TRY(bb::hip_status("bb_cm_normalize", e, BB_ERR_NOMEM));
     hipStream_t st = cm->stream;
     if (n_bins > 0) {
         e = hipMemcpyAsync(kr.p, KRnorm, (size_t)n_bins * sizeof(double), hipMemcpyHostToDevice, st);
@@ -1039,9 +1016,7 @@ int bb_cm_normalize(bb_cm *cm, int64_t n_bins, const double *KRnorm, const doubl
                        (const double *)kr.p, (const double *)ke.p);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_HIP, std::string("bb_cm_normalize: ") + hipGetErrorString(e));
-    return BB_OK;
+    return bb::hip_status("bb_cm_normalize", e);
 }
 
 int bb_cm_marginals(bb_cm *cm, double *sums) {
@@ -1049,15 +1024,11 @@ int bb_cm_marginals(bb_cm *cm, double *sums) {
     BB_REQUIRE(sums != nullptr, "bb_cm_marginals: sums is NULL");
     bb::DevBuf s;
     hipError_t e = s.alloc((size_t)cm->d * 8);
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_NOMEM, std::string("bb_cm_marginals: ") + hipGetErrorString(e));
-    e = bb::launch(column_sums_kernel, dim3((unsigned)((cm->d + kSumWG - 1) / kSumWG)), dim3(kSumWG), 0,
-                   cm->stream, (const double *)cm->m, cm->d, (double *)s.p);
+    BB_TRY(bb::hip_status("bb_cm_marginals", e, BB_ERR_NOMEM));
+    e = column_sums_enqueue(cm, (double *)s.p);
     if (e == hipSuccess) e = hipStreamSynchronize(cm->stream);
     if (e == hipSuccess) e = hipMemcpy(sums, s.p, (size_t)cm->d * 8, hipMemcpyDeviceToHost);
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_HIP, std::string("bb_cm_marginals: ") + hipGetErrorString(e));
-    return BB_OK;
+    return bb::hip_status("bb_cm_marginals", e);
 }
 
 int bb_cm_filter(bb_cm *cm, double threshold, int64_t *d_new, uint8_t *keep_out) {
@@ -1068,11 +1039,9 @@ int bb_cm_filter(bb_cm *cm, double threshold, int64_t *d_new, uint8_t *keep_out)
     if (e == hipSuccess) e = keep.alloc((size_t)d);
     if (e == hipSuccess) e = idx.alloc((size_t)d * 4);
     if (e == hipSuccess) e = cnt.alloc(8);
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_NOMEM, std::string("bb_cm_filter: ") + hipGetErrorString(e));
+    BB_TRY(bb::hip_status("bb_cm_filter", e, BB_ERR_NOMEM));
     hipStream_t st = cm->stream;
-    e = bb::launch(column_sums_kernel, dim3((unsigned)((d + kSumWG - 1) / kSumWG)), dim3(kSumWG), 0, st,
-                   (const double *)cm->m, d, (double *)sums.p);
+    e = column_sums_enqueue(cm, (double *)sums.p);
     if (e == hipSuccess)
         e = bb::launch(keep_scan_kernel, dim3(1), dim3(1024), 0, st, (const double *)sums.p, d,
                        threshold, (unsigned char *)keep.p, (int *)idx.p, (int64_t *)cnt.p);
@@ -1080,8 +1049,7 @@ int bb_cm_filter(bb_cm *cm, double threshold, int64_t *d_new, uint8_t *keep_out)
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipMemcpy(&dn, cnt.p, 8, hipMemcpyDeviceToHost);
     if (e == hipSuccess && keep_out) e = hipMemcpy(keep_out, keep.p, (size_t)d, hipMemcpyDeviceToHost);
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_HIP, std::string("bb_cm_filter: ") + hipGetErrorString(e));
+    BB_TRY(bb::hip_status("bb_cm_filter", e));
     // Compaction IN PLACE, a band of rows at a time through a small bounce buffer: the
     // new matrix is the old one read in order with elements left out, so new row r lands at
     // [r dn, (r+1) dn), in front of every element a later row still needs (those start at
@@ -1096,8 +1064,7 @@ int bb_cm_filter(bb_cm *cm, double threshold, int64_t *d_new, uint8_t *keep_out)
         const int64_t band = std::max<int64_t>(1, std::min<int64_t>(dn, bounce / dn));
         bb::DevBuf tmp;
         e = tmp.alloc((size_t)(band * dn) * sizeof(double));
-        if (e != hipSuccess)
-            return bb::fail(BB_ERR_NOMEM, std::string("bb_cm_filter: ") + hipGetErrorString(e));
+        BB_TRY(bb::hip_status("bb_cm_filter", e, BB_ERR_NOMEM));
         for (int64_t r0 = 0; r0 < dn && e == hipSuccess; r0 += band) {
             const int64_t r1 = std::min(dn, r0 + band);
             e = bb::launch(gather_kernel,
@@ -1109,8 +1076,7 @@ int bb_cm_filter(bb_cm *cm, double threshold, int64_t *d_new, uint8_t *keep_out)
                                    hipMemcpyDeviceToDevice, st);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess)
-            return bb::fail(BB_ERR_HIP, std::string("bb_cm_filter: ") + hipGetErrorString(e));
+        BB_TRY(bb::hip_status("bb_cm_filter", e));
     }
     cm->d = dn;
     if (d_new) *d_new = dn;
@@ -1124,13 +1090,12 @@ int bb_cm_symv(bb_cm *cm, const double *x, double *y) {
     bb::DevBuf dx, dy;
     hipError_t e = dx.alloc((size_t)d * 8);
     if (e == hipSuccess) e = dy.alloc((size_t)d * 8);
-    if (e != hipSuccess) return bb::fail(BB_ERR_NOMEM, std::string("bb_cm_symv: ") + hipGetErrorString(e));
+    BB_TRY(bb::hip_status("bb_cm_symv", e, BB_ERR_NOMEM));
     e = hipMemcpyAsync(dx.p, x, (size_t)d * 8, hipMemcpyHostToDevice, cm->stream);
     if (e == hipSuccess) e = symv_enqueue(cm, (const double *)dx.p, (double *)dy.p);
     if (e == hipSuccess) e = hipStreamSynchronize(cm->stream);
     if (e == hipSuccess) e = hipMemcpy(y, dy.p, (size_t)d * 8, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return bb::fail(BB_ERR_HIP, std::string("bb_cm_symv: ") + hipGetErrorString(e));
-    return BB_OK;
+    return bb::hip_status("bb_cm_symv", e);
 }
 
 // Restarted Lanczos with full re-orthogonalisation for the eigenpair of largest
@@ -1154,8 +1119,7 @@ int bb_cm_eigenvector(bb_cm *cm, double *vec, double *eigenvalue, double tol, in
     if (e == hipSuccess) e = w.alloc((size_t)d * 8);
     if (e == hipSuccess) e = coef.alloc((size_t)(m + 1) * 8);
     if (e == hipSuccess) e = yv.alloc((size_t)(m + 1) * 8);
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_NOMEM, std::string("bb_cm_eigenvector: ") + hipGetErrorString(e));
+    BB_TRY(bb::hip_status("bb_cm_eigenvector", e, BB_ERR_NOMEM));
     hipStream_t st = cm->stream;
     double *dV = (double *)V.p, *dw = (double *)w.p, *dc = (double *)coef.p, *dy = (double *)yv.p;
     const dim3 gvec((unsigned)((d + 255) / 256)), b256(256);
@@ -1183,7 +1147,12 @@ int bb_cm_eigenvector(bb_cm *cm, double *vec, double *eigenvalue, double tol, in
     bb::DevBuf sc;
     if (e == hipSuccess) e = sc.alloc((size_t)(2 * m + 1 + (m + 1) * kDotSegs) * 8);
     double *d_alpha = (double *)sc.p, *d_beta = d_alpha + m, *d_inv = d_beta + m, *d_part = d_inv + 1;
+    // the dots of long vectors go in kDotSegs segments each through d_part, which
+    // lanczos_scalars_kernel then adds up into dc; short ones straight into dc
     const bool two_stage = d >= 4096;
+    const unsigned dot_segs = two_stage ? kDotSegs : 1;
+    double *dots = two_stage ? d_part : dc;
+    const double *part = two_stage ? d_part : nullptr;
     bool done = false;
     while (e == hipSuccess && !done) {
         const int steps = (int)std::min<int64_t>(m, std::max<int64_t>(1, max_matvecs - used));
@@ -1195,33 +1164,24 @@ int bb_cm_eigenvector(bb_cm *cm, double *vec, double *eigenvalue, double tol, in
             // coefficients against the whole basis (alpha_k is the last one), subtract, and
             // once more for the rounding the first pass leaves (classical Gram-Schmidt x 2)
             for (int pass = 0; pass < 2 && e == hipSuccess; ++pass) {
-                // the dots (in two stages for long vectors) and alpha_k, THEN the subtraction
-                // (which overwrites w; dc is not written again before it has been read)
-                if (two_stage)
-                    e = bb::launch(basis_dots_part_kernel, dim3((unsigned)(k + 1), kDotSegs), b256, 0, st,
-                                   (const double *)dV, d, (const double *)dw, d_part);
-                else
-                    e = bb::launch(basis_dots_kernel, dim3((unsigned)(k + 1)), b256, 0, st,
-                                   (const double *)dV, d, (const double *)dw, dc);
+                // the dots and alpha_k, THEN the subtraction (which overwrites w; dc is not
+                // written again before it has been read)
+                e = bb::launch(basis_dots_kernel, dim3((unsigned)(k + 1), dot_segs), b256, 0, st,
+                               (const double *)dV, d, (const double *)dw, dots);
                 if (e == hipSuccess)
                     e = bb::launch(lanczos_scalars_kernel, dim3(1), dim3(64), 0, st, dc, k, pass, d_alpha,
-                                   d_beta, d_inv, (const double *)(two_stage ? d_part : nullptr), k + 1);
+                                   d_beta, d_inv, part, k + 1);
                 if (e == hipSuccess)
                     e = bb::launch(basis_subtract_kernel, gvec, b256, 0, st, (const double *)dV, d,
                                    k + 1, (const double *)dc, dw);
             }
             // beta_k = |w|, v_{k+1} = w / beta_k (0 once the direction has vanished)
-            if (e == hipSuccess) {
-                if (two_stage)
-                    e = bb::launch(basis_dots_part_kernel, dim3(1, kDotSegs), b256, 0, st,
-                                   (const double *)dw, d, (const double *)dw, d_part);
-                else
-                    e = bb::launch(basis_dots_kernel, dim3(1), b256, 0, st, (const double *)dw, d,
-                                   (const double *)dw, dc);
-            }
+            if (e == hipSuccess)
+                e = bb::launch(basis_dots_kernel, dim3(1, dot_segs), b256, 0, st, (const double *)dw, d,
+                               (const double *)dw, dots);
             if (e == hipSuccess)
                 e = bb::launch(lanczos_scalars_kernel, dim3(1), dim3(64), 0, st, dc, k, 2, d_alpha,
-                               d_beta, d_inv, (const double *)(two_stage ? d_part : nullptr), 1);
+                               d_beta, d_inv, part, 1);
             if (k + 1 <= m && e == hipSuccess)
                 e = bb::launch(scale_by_kernel, gvec, b256, 0, st, (const double *)dw,
                                (const double *)d_inv, dV + (int64_t)(k + 1) * d, d);
@@ -1269,8 +1229,7 @@ int bb_cm_eigenvector(bb_cm *cm, double *vec, double *eigenvalue, double tol, in
         done = resid <= tol * fabs(theta) || resid == 0.0 || used >= max_matvecs || n == (int)d;
     }
     if (e == hipSuccess) e = hipMemcpy(host.data(), dV, (size_t)d * 8, hipMemcpyDeviceToHost);
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_HIP, std::string("bb_cm_eigenvector: ") + hipGetErrorString(e));
+    BB_TRY(bb::hip_status("bb_cm_eigenvector", e));
     // sign: the component of largest magnitude is positive (first one on ties)
     int64_t big = 0;
     for (int64_t i = 1; i < d; ++i)
@@ -1285,11 +1244,9 @@ int bb_cm_eigenvector(bb_cm *cm, double *vec, double *eigenvalue, double tol, in
 
 int bb_cm_release_scratch(int device) {
     BB_TRY(bb::enter_device(device));
-    CorrScratch *sc = corr_scratch(device);
+    CmScratch *sc = bb::per_device<CmScratch>(device);
     std::lock_guard<std::mutex> lock(sc->mu);
-    (void)hipFree(sc->buf);
-    sc->buf = nullptr;
-    sc->bytes = 0;
+    sc->buf.release();
     return BB_OK;
 }
 
@@ -1297,7 +1254,7 @@ int bb_cm_correlation(bb_cm *cm, double *tflops) {
     BB_TRY(cm_check(cm, "bb_cm_correlation"));
     const int64_t d = cm->d;
     const int64_t dp = bb::round_up(d, kGT), ldx = bb::round_up(d, kGK);
-    CorrScratch *scr = corr_scratch(cm->device);
+    CmScratch *scr = bb::per_device<CmScratch>(cm->device);
     std::lock_guard<std::mutex> scratch_lock(scr->mu);
     // centred rows | Gram matrix | standard deviations: ONE grow-only allocation kept with
     // the handle.  Round 2 allocated the two matrix-sized temporaries per call, and on this
@@ -1307,19 +1264,11 @@ int bb_cm_correlation(bb_cm *cm, double *tflops) {
     const size_t xc_bytes = ((size_t)dp * ldx * 8 + 255) & ~(size_t)255;
     const size_t g_bytes = ((size_t)dp * dp * 8 + 255) & ~(size_t)255;
     const size_t need = xc_bytes + g_bytes + (size_t)d * 8;
-    hipError_t e = hipSuccess;
-    if (need > scr->bytes) {
-        (void)hipFree(scr->buf);
-        scr->buf = nullptr;
-        scr->bytes = 0;
-        e = hipMalloc(&scr->buf, need);
-        if (e == hipSuccess) scr->bytes = need;
-    }
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_NOMEM, std::string("bb_cm_correlation: ") + hipGetErrorString(e));
-    xc.p = scr->buf;
-    g.p = (char *)scr->buf + xc_bytes;
-    sd.p = (char *)scr->buf + xc_bytes + g_bytes;
+    hipError_t e = scr->buf.reserve(need);
+    BB_TRY(bb::hip_status("bb_cm_correlation", e, BB_ERR_NOMEM));
+    xc.p = scr->buf.p;
+    g.p = (char *)scr->buf.p + xc_bytes;
+    sd.p = (char *)scr->buf.p + xc_bytes + g_bytes;
     hipStream_t st = cm->stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const double fact_inv = 1.0 / (double)(d - 1);   // numpy: true_divide(1, N - ddof); d = 1 -> inf
@@ -1368,9 +1317,7 @@ int bb_cm_correlation(bb_cm *cm, double *tflops) {
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_HIP, std::string("bb_cm_correlation: ") + hipGetErrorString(e));
-    return BB_OK;
+    return bb::hip_status("bb_cm_correlation", e);
 }
 
 // ---- round-1 entry points: the same kernels around a host matrix -------------------
@@ -1378,14 +1325,8 @@ int bb_cm_correlation(bb_cm *cm, double *tflops) {
 int bb_contactmap_scatter(const double *triples, int64_t n, int32_t resolution, double *matrix,
                           int64_t d, int device) {
     BB_REQUIRE(matrix != nullptr && d >= 1, "bb_contactmap_scatter: bad matrix");
-    bb_cm *cm = nullptr;
-    int rc = bb_cm_create(&cm, d, device);
-    if (rc == BB_OK) rc = bb_cm_scatter(cm, triples, n, resolution);
-    if (rc == BB_OK) rc = bb_cm_download(cm, matrix, d);
-    const std::string keep = bb_last_error();
-    bb_cm_destroy(cm);
-    if (rc != BB_OK) bb::set_error(keep);
-    return rc;
+    return with_host_matrix(matrix, d, device, false,
+                            [&](bb_cm *cm) { return bb_cm_scatter(cm, triples, n, resolution); });
 }
 
 int bb_contactmap_normalize(double *matrix, int64_t n_bins, const double *KRnorm,
@@ -1393,15 +1334,8 @@ int bb_contactmap_normalize(double *matrix, int64_t n_bins, const double *KRnorm
     BB_REQUIRE(matrix != nullptr && KRnorm != nullptr && KRexpected != nullptr,
                "bb_contactmap_normalize: NULL argument");
     BB_REQUIRE(n_bins >= 0, "bb_contactmap_normalize: n_bins < 0");
-    bb_cm *cm = nullptr;
-    int rc = bb_cm_create(&cm, n_bins + 1, device);
-    if (rc == BB_OK) rc = bb_cm_upload(cm, matrix, n_bins + 1);
-    if (rc == BB_OK) rc = bb_cm_normalize(cm, n_bins, KRnorm, KRexpected);
-    if (rc == BB_OK) rc = bb_cm_download(cm, matrix, n_bins + 1);
-    const std::string keep = bb_last_error();
-    bb_cm_destroy(cm);
-    if (rc != BB_OK) bb::set_error(keep);
-    return rc;
+    return with_host_matrix(matrix, n_bins + 1, device, true,
+                            [&](bb_cm *cm) { return bb_cm_normalize(cm, n_bins, KRnorm, KRexpected); });
 }
 
 }  // extern "C"

@@ -5,53 +5,19 @@
 // in the reference's operation order, NaN behaviour included), pinned by golden vectors.
 #include "bb_common.h"
 
-#include <map>
-#include <mutex>
-
 namespace {
 
 // Per-device scratch kept between calls: a stream and ONE grow-only arena.  A fresh
 // allocation is not what costs -- the first use of a freshly mapped block is, 0.17-0.35 s on
 // this platform (tools/alloc_probe.py), and a stream costs 3-4 ms to make and destroy:
 // small calls spent 3 ms around 0.1 ms of work.  Arenas above kKeepBytes are given
-// back after the call.  Guarded by a mutex: calls on one device serialise, which is what
-// one stream would do anyway.
+// back after the call.
 constexpr size_t kKeepBytes = (size_t)1 << 30;
-struct MiscCtx {
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    char *arena = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        hipError_t e = hipSuccess;
-        if (!stream) e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-        if (e == hipSuccess && cap < bytes) {
-            (void)hipFree(arena);
-            arena = nullptr;
-            cap = 0;
-            e = hipMalloc((void **)&arena, bytes);
-            if (e == hipSuccess) cap = bytes;
-        }
-        return e;
-    }
+struct MiscScratch : bb::DeviceScratch {
     void trim() {
-        if (cap > kKeepBytes) {
-            (void)hipFree(arena);
-            arena = nullptr;
-            cap = 0;
-        }
+        if (buf.bytes > kKeepBytes) buf.release();
     }
 };
-MiscCtx *misc_ctx(int device) {
-    static std::mutex table_mu;
-    static std::map<int, MiscCtx *> table;
-    std::lock_guard<std::mutex> lock(table_mu);
-    auto it = table.find(device);
-    if (it != table.end()) return it->second;
-    MiscCtx *c = new MiscCtx();   // lives for the process: freed by the runtime at exit
-    table[device] = c;
-    return c;
-}
 constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 constexpr int kScanBlock = 256;
@@ -228,17 +194,17 @@ int bb_benjamini_hochberg(const double *p_values, int64_t d, int64_t n, double *
     if (d == 0) return BB_OK;
     const int64_t per_block = (int64_t)kScanBlock * kItems;
     const int64_t nblocks = (d + per_block - 1) / per_block;
-    MiscCtx *c = misc_ctx(device);
+    MiscScratch *c = bb::per_device<MiscScratch>(device);
     std::lock_guard<std::mutex> lock(c->mu);
     const size_t o_q = align256((size_t)d * 8), o_bm = o_q + align256((size_t)d * 8),
                  o_bc = o_bm + align256((size_t)nblocks * 8), o_fc = o_bc + align256((size_t)nblocks * 4),
                  total = o_fc + align256((size_t)nblocks * 4);
-    hipError_t e = c->ensure(total);
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_NOMEM, std::string("bb_benjamini_hochberg: ") + hipGetErrorString(e));
+    hipError_t e = c->reserve(total);
+    BB_TRY(bb::hip_status("bb_benjamini_hochberg", e, BB_ERR_NOMEM));
     hipStream_t st = c->stream;
-    double *p = (double *)c->arena, *q = (double *)(c->arena + o_q), *bm = (double *)(c->arena + o_bm);
-    int *bc = (int *)(c->arena + o_bc), *fc = (int *)(c->arena + o_fc);
+    char *arena = (char *)c->buf.p;
+    double *p = (double *)arena, *q = (double *)(arena + o_q), *bm = (double *)(arena + o_bm);
+    int *bc = (int *)(arena + o_bc), *fc = (int *)(arena + o_fc);
     e = hipMemcpyAsync(p, p_values, (size_t)d * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
         e = bb::launch(bh_local_kernel, dim3((unsigned)nblocks), dim3(kScanBlock), 0, st,
@@ -253,9 +219,7 @@ int bb_benjamini_hochberg(const double *p_values, int64_t d, int64_t n, double *
         e = hipMemcpyAsync(q_values, q, (size_t)d * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     c->trim();
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_HIP, std::string("bb_benjamini_hochberg: ") + hipGetErrorString(e));
-    return BB_OK;
+    return bb::hip_status("bb_benjamini_hochberg", e);
 }
 
 int bb_downsample(const float *yp1, int64_t n1, float *yp5i, int64_t n5, int device) {
@@ -264,14 +228,13 @@ int bb_downsample(const float *yp1, int64_t n1, float *yp5i, int64_t n5, int dev
     int rc = bb::use_device(device);
     if (rc != BB_OK) return rc;
     if (n5 < 2) return BB_OK;
-    MiscCtx *c = misc_ctx(device);
+    MiscScratch *c = bb::per_device<MiscScratch>(device);
     std::lock_guard<std::mutex> lock(c->mu);
     const size_t o_b = align256((size_t)n1 * n1 * 4), total = o_b + align256((size_t)n5 * n5 * 4);
-    hipError_t e = c->ensure(total);
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_NOMEM, std::string("bb_downsample: ") + hipGetErrorString(e));
+    hipError_t e = c->reserve(total);
+    BB_TRY(bb::hip_status("bb_downsample", e, BB_ERR_NOMEM));
     hipStream_t st = c->stream;
-    float *a = (float *)c->arena, *b = (float *)(c->arena + o_b);
+    float *a = (float *)c->buf.p, *b = (float *)((char *)c->buf.p + o_b);
     e = hipMemcpyAsync(a, yp1, (size_t)n1 * n1 * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
         e = hipMemcpyAsync(b, yp5i, (size_t)n5 * n5 * 4, hipMemcpyHostToDevice, st);
@@ -283,9 +246,7 @@ int bb_downsample(const float *yp1, int64_t n1, float *yp5i, int64_t n5, int dev
         e = hipMemcpyAsync(yp5i, b, (size_t)n5 * n5 * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     c->trim();
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_HIP, std::string("bb_downsample: ") + hipGetErrorString(e));
-    return BB_OK;
+    return bb::hip_status("bb_downsample", e);
 }
 
 }  // extern "C"

@@ -233,13 +233,8 @@ __global__ __launch_bounds__(256) void fw_store_kernel(const double *__restrict_
         out[i * d + j] = none ? 0.0 : v;
         n += (none && j > i) ? 1 : 0;
     }
-    part[threadIdx.x] = n;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) counts[i] = part[0];
+    n = bb::block_sum_256(n, part);
+    if (threadIdx.x == 0) counts[i] = n;
 }
 
 }  // namespace
@@ -260,31 +255,21 @@ extern "C" int bb_cm_shortest_paths(const bb_cm *src, bb_cm *dst, int kind, doub
     // work matrix | row panel of the round (nt tiles of 64 x 64) | per-row counts
     const size_t w_bytes = (size_t)ld * (size_t)ld * 8, panel_bytes = (size_t)ld * kFT * 8;
     const size_t need = w_bytes + panel_bytes + (size_t)d * 8;
-    bb::CorrScratch *scr = bb::corr_scratch(src->device);
+    bb::CmScratch *scr = bb::per_device<bb::CmScratch>(src->device);
     std::lock_guard<std::mutex> scratch_lock(scr->mu);
-    if (need > scr->bytes) {
-        (void)hipFree(scr->buf);
-        scr->buf = nullptr;
-        scr->bytes = 0;
-        const hipError_t e = hipMalloc(&scr->buf, need);
-        if (e != hipSuccess) {
-            scr->buf = nullptr;
-            (void)hipGetLastError();
-            return bb::fail(BB_ERR_NOMEM,
-                            "bb_cm_shortest_paths: cannot allocate the work matrix: " +
-                                std::to_string(need) + " bytes (edge " + std::to_string(d) +
-                                " padded to " + std::to_string(ld) + ") beside the resident matrix of " +
-                                std::to_string((size_t)d * (size_t)d * 8) + " bytes: " +
-                                hipGetErrorString(e));
-        }
-        scr->bytes = need;
-    }
-    double *w = (double *)scr->buf;
-    double *panel = (double *)((char *)scr->buf + w_bytes);
-    int64_t *counts = (int64_t *)((char *)scr->buf + w_bytes + panel_bytes);
+    hipError_t e = scr->buf.reserve(need);
+    if (e != hipSuccess)
+        return bb::fail(BB_ERR_NOMEM,
+                        "bb_cm_shortest_paths: cannot allocate the work matrix: " +
+                            std::to_string(need) + " bytes (edge " + std::to_string(d) +
+                            " padded to " + std::to_string(ld) + ") beside the resident matrix of " +
+                            std::to_string((size_t)d * (size_t)d * 8) + " bytes: " +
+                            hipGetErrorString(e));
+    double *w = (double *)scr->buf.p, *panel = w + ld * ld;
+    int64_t *counts = (int64_t *)(panel + ld * kFT);
     hipStream_t st = src->stream;
-    hipError_t e = bb::launch(fw_load_kernel, dim3((unsigned)((ld + 255) / 256), (unsigned)std::min<int64_t>(ld, 65535)), dim3(256),
-                              0, st, (const double *)src->m, d, w, ld, kind, -1.0 / alpha);
+    e = bb::launch(fw_load_kernel, dim3((unsigned)((ld + 255) / 256), (unsigned)std::min<int64_t>(ld, 65535)), dim3(256),
+                   0, st, (const double *)src->m, d, w, ld, kind, -1.0 / alpha);
     for (int K = 0; K < nt && e == hipSuccess; ++K) {
         e = bb::launch(fw_diag_kernel, dim3(1), dim3(256), 0, st, w, ld, K);
         if (nt == 1) break;
@@ -303,8 +288,7 @@ extern "C" int bb_cm_shortest_paths(const bb_cm *src, bb_cm *dst, int kind, doub
         host.resize((size_t)d);
         e = hipMemcpy(host.data(), counts, (size_t)d * 8, hipMemcpyDeviceToHost);
     }
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_HIP, std::string("bb_cm_shortest_paths: ") + hipGetErrorString(e));
+    BB_TRY(bb::hip_status("bb_cm_shortest_paths", e));
     if (unreachable_pairs) {
         int64_t total = 0;
         for (int64_t v : host) total += v;

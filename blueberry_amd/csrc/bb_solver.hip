@@ -140,9 +140,7 @@ int dev_alloc(T **p, int64_t count) {
     *p = nullptr;
     if (count <= 0) count = 1;
     hipError_t e = hipMalloc((void **)p, (size_t)count * sizeof(T));
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
-    return BB_OK;
+    return bb::hip_status("hipMalloc failed", e, BB_ERR_NOMEM);
 }
 
 // Waves per CU (4 waves = one workgroup).  Measured on MI355X: with the rolling
@@ -639,12 +637,12 @@ int set_wish_dense_t(LayoutTag<T, W>, bb_solver *s, const double *host, int64_t 
                            -1.0 / alpha);
         }
         if (e != hipSuccess)
-            rc = bb::fail(BB_ERR_HIP, std::string("set_wish_dense: ") + hipGetErrorString(e));
+            rc = bb::hip_status("set_wish_dense", e);
         ul = ue;
     }
     hipError_t e = hipStreamSynchronize(s->stream);
     if (rc == BB_OK && e != hipSuccess)
-        rc = bb::fail(BB_ERR_HIP, std::string("set_wish_dense: ") + hipGetErrorString(e));
+        rc = bb::hip_status("set_wish_dense", e);
     hipFree(stage);
     return rc;
 }
@@ -751,9 +749,7 @@ int set_wish_dense(bb_solver *s, const double *host, int64_t ld, int kind, doubl
 template <typename Stage>
 int scatter_entries(bb_solver *s, const char *who, int64_t n, int64_t chunk, int kind, double alpha,
                     const double *KRnorm, const double *KRexpected, Stage &&stage) {
-    const auto hip = [&](hipError_t e) {
-        return e == hipSuccess ? (int)BB_OK : bb::fail(BB_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    };
+    const auto hip = [&](hipError_t e) { return bb::hip_status(who, e); };
     const int64_t nb = s->L.n_blocks;
     std::vector<int32_t> tilemap((size_t)(nb * nb), -1);
     for (size_t t = 0; t < s->tile_I.size(); ++t)
@@ -934,7 +930,7 @@ int bb_solver_create(bb_solver **out, int64_t n_bins, int dtype, int device, int
     if (rc == BB_OK) {
         hipError_t e = bb::acquire_stream(device, &s->stream);
         if (e != hipSuccess)
-            rc = bb::fail(BB_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+            rc = bb::hip_status("hipStreamCreate", e);
         else
             s->own_stream = true;
     }
@@ -1296,7 +1292,7 @@ int bb_triples_create(bb_triples **out, const double *triples, int64_t n, int32_
     if (rc == BB_OK && n > 0) {
         const hipError_t e = hipMemcpy(t->d, triples, (size_t)n * 24, hipMemcpyHostToDevice);
         if (e != hipSuccess)
-            rc = bb::fail(BB_ERR_HIP, std::string("bb_triples_create: ") + hipGetErrorString(e));
+            rc = bb::hip_status("bb_triples_create", e);
     }
     if (rc != BB_OK) {
         hipFree(t->d);
@@ -2017,9 +2013,7 @@ int bb_solver_read_exchange(bb_solver *s, double *host, int64_t n) {
         e = hipMemcpyAsync(host, tmp, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
     hipFree(tmp);
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_HIP, std::string("bb_solver_read_exchange: ") + hipGetErrorString(e));
-    return BB_OK;
+    return bb::hip_status("bb_solver_read_exchange", e);
 }
 
 int bb_solver_write_exchange(bb_solver *s, const double *host, int64_t n) {
@@ -2033,9 +2027,7 @@ int bb_solver_write_exchange(bb_solver *s, const double *host, int64_t n) {
     if (e == hipSuccess) e = narrow(s, tmp, s->d_exch, n);
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
     hipFree(tmp);
-    if (e != hipSuccess)
-        return bb::fail(BB_ERR_HIP, std::string("bb_solver_write_exchange: ") + hipGetErrorString(e));
-    return BB_OK;
+    return bb::hip_status("bb_solver_write_exchange", e);
 }
 
 int bb_solver_matvec_sq(bb_solver *s, const double *x, double *y) {
@@ -2055,7 +2047,7 @@ int bb_solver_matvec_sq(bb_solver *s, const double *x, double *y) {
         e = hipMemcpyAsync(s->d_f64_tmp, x, (size_t)s->L.n_bins * 24, hipMemcpyHostToDevice, s->stream);
     if (e == hipSuccess) e = narrow(s, s->d_f64_tmp, d_in, n3);
     int rc = BB_OK;
-    if (e != hipSuccess) rc = bb::fail(BB_ERR_HIP, std::string("bb_solver_matvec_sq: ") + hipGetErrorString(e));
+    if (e != hipSuccess) rc = bb::hip_status("bb_solver_matvec_sq", e);
     if (rc == BB_OK) rc = launch_grad(s, kOpMatvec2, d_in);
     if (rc == BB_OK) rc = launch_reduce(s, kReduceExchange, 0.0, nullptr, kScalePlainSum);
     if (rc == BB_OK) {
@@ -2065,7 +2057,7 @@ int bb_solver_matvec_sq(bb_solver *s, const double *x, double *y) {
                                s->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
         if (e != hipSuccess)
-            rc = bb::fail(BB_ERR_HIP, std::string("bb_solver_matvec_sq: ") + hipGetErrorString(e));
+            rc = bb::hip_status("bb_solver_matvec_sq", e);
     }
     if (hipStreamSynchronize(s->stream) != hipSuccess && rc == BB_OK)
         rc = bb::fail(BB_ERR_HIP, "bb_solver_matvec_sq: the stream did not drain");
@@ -2135,7 +2127,7 @@ int bb_solver_sync_timeout(bb_solver *s, int64_t milliseconds) {
         const hipError_t e = hipStreamQuery(s->stream);
         if (e == hipSuccess) return BB_OK;
         if (e != hipErrorNotReady)
-            return bb::fail(BB_ERR_HIP, std::string("hipStreamQuery: ") + hipGetErrorString(e));
+            return bb::hip_status("hipStreamQuery", e);
         (void)hipGetLastError();   // "not ready" is an answer, not a failure
         timespec t;
         clock_gettime(CLOCK_MONOTONIC, &t);
@@ -2222,7 +2214,7 @@ int bb_solver_measure_event_gap(bb_solver *s, int pairs, double *ms_avg) {
     for (auto x : ev)
         if (x) (void)hipEventDestroy(x);
     if (e != hipSuccess)
-        return bb::fail(BB_ERR_HIP, std::string("bb_solver_measure_event_gap: ") + hipGetErrorString(e));
+        return bb::hip_status("bb_solver_measure_event_gap", e);
     *ms_avg = t / pairs;
     return BB_OK;
 }
