@@ -23,6 +23,8 @@
 
 namespace {
 
+using bb::lds_barrier;   // bb_cm_internal.h
+
 constexpr int kT = 32;  // tile edge of the normalise / finalise kernels (kT x 8 threads)
 
 __device__ __forceinline__ double nan_to_num(double v) {
@@ -31,17 +33,6 @@ __device__ __forceinline__ double nan_to_num(double v) {
     if (v > 1.7976931348623157e308) return 1.7976931348623157e308;
     if (v < -1.7976931348623157e308) return -1.7976931348623157e308;
     return v;
-}
-
-// A workgroup barrier that orders LDS only.  __syncthreads() is also a release of the
-// wave's GLOBAL stores: s_waitcnt vmcnt(0) in front of every s_barrier, i.e. the write
-// acknowledgements of a whole tile (and the next tile's loads) twice per tile.  The tile
-// pair belongs to this workgroup alone and no thread reads a global cell another thread
-// of the launch writes, so nothing global needs ordering here.
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
 // One workgroup per tile pair (TJ <= TK) of the (d,d) matrix, IN PLACE: computes the
@@ -317,7 +308,7 @@ __global__ __launch_bounds__(256) void gather_kernel(const double *__restrict__ 
 //               column partials (<= d / 64 + 1) in a fixed order, 8 slices in parallel.
 // All loads are 8 bytes per lane, 512 contiguous bytes per wave: rows of an odd-d matrix
 // start 8 bytes off every other time, and 16 loads of a wave are in flight per chunk.
-constexpr int kSvRows = 64, kSvSeg = 4096, kSvGroup = 8;
+using bb::kSvRows; using bb::kSvSeg; using bb::kSvGroup;   // bb_cm_internal.h
 // plain loads: the 512-byte segments of a wave are not line-aligned (odd d), neighbouring
 // chunks share their end lines, and a non-temporal load does not leave them in L2 for the
 // neighbour -- 481 against 505 us per product at d = 24,927
@@ -390,39 +381,7 @@ __global__ __launch_bounds__(256, 2) void symv_upper_kernel(const double *__rest
     }
 }
 
-// y[c] = sum of c's row partials (segments c / 4096 ..) + its column partials (row blocks
-// 0 .. c / 64), each list in order, cut into 8 slices that are added in slice order.
-__global__ __launch_bounds__(1024) void symv_reduce_kernel(const double *__restrict__ rowpart,
-                                                           const double *__restrict__ colpart,
-                                                           int64_t d, int nseg, double *__restrict__ y) {
-    __shared__ double meet[8][128];
-    const int el = threadIdx.x & 127, sl = threadIdx.x >> 7;
-    const int64_t c = (int64_t)blockIdx.x * 128 + el;
-    double acc = 0.0;
-    if (c < d) {
-        const int64_t s0 = c / kSvSeg, nrow = nseg - s0, ncol = c / kSvRows + 1, n = nrow + ncol;
-        const int64_t per = (n + 7) / 8, k0 = sl * per, k1 = std::min<int64_t>(n, k0 + per);
-        for (int64_t k = k0; k < k1; k += 16) {
-            double v[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int64_t kk = k + q;
-                v[q] = kk >= k1 ? 0.0
-                                : (kk < nrow ? rowpart[(s0 + kk) * d + c] : colpart[(kk - nrow) * d + c]);
-            }
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc += v[q];
-        }
-    }
-    meet[sl][el] = acc;
-    __syncthreads();
-    if (sl == 0 && c < d) {
-        double t = meet[0][el];
-#pragma unroll
-        for (int q = 1; q < 8; ++q) t += meet[q][el];
-        y[c] = t;
-    }
-}
+using bb::symv_reduce_kernel;   // bb_cm_internal.h
 
 // part[j * S + s] = segment s of V[j] . w for the basis vectors j < k: one workgroup per
 // (vector, segment), S = gridDim.y segments, fixed-order sums.  S = 1 is the whole dot, written
@@ -752,19 +711,7 @@ hipError_t symv_enqueue(bb_cm *cm, const double *dx, double *dy) {
     const int64_t d = cm->d;
     const int64_t nrb = (d + kSvRows - 1) / kSvRows, nseg = (d + kSvSeg - 1) / kSvSeg;
     if (cm->sv_d != d) {
-        std::vector<int2> items;
-        // longest items first: the dispatcher hands them out in order
-        for (int64_t S = nseg - 1; S >= 0; --S)
-            for (int64_t I = 0; I < nrb && I * kSvRows < (S + 1) * (int64_t)kSvSeg; ++I)
-                if (std::max<int64_t>(I * kSvRows, S * kSvSeg) < std::min<int64_t>(d, (S + 1) * (int64_t)kSvSeg))
-                    items.push_back(make_int2((int)I, (int)S));
-        std::stable_sort(items.begin(), items.end(), [&](const int2 &a, const int2 &b) {
-            auto len = [&](const int2 &t) {
-                return std::min<int64_t>(d, (t.y + 1) * (int64_t)kSvSeg) -
-                       std::max<int64_t>((int64_t)t.x * kSvRows, (int64_t)t.y * kSvSeg);
-            };
-            return len(a) > len(b);
-        });
+        const std::vector<int2> items = bb::symv_items(d);
         const size_t item_bytes = (items.size() * sizeof(int2) + 255) & ~(size_t)255;
         const size_t need = item_bytes + (size_t)(nseg + nrb) * (size_t)d * 8;
         hipError_t e = cm->sv.reserve(need);
@@ -889,6 +836,7 @@ int bb_cm_destroy(bb_cm *cm) {
     bb::release_stream(cm->device, cm->stream);     // synchronises it
     (void)hipFree(cm->m);
     cm->sv.release();
+    cm->bal.release();
     delete cm;
     (void)hipGetLastError();   // tear-down is best effort; its errors end here
     return BB_OK;

@@ -165,6 +165,15 @@ class _DeviceMatrix(object):
             pass
 
 
+def expected_from_sums(sums, counts):
+    """e[k] = sums[k] / counts[k], NaN where counts[k] == 0 or sums[k] == 0 (docs/SPEC.md 2.5.2)."""
+    sums = numpy.asarray(sums, dtype=numpy.float64)
+    ok = (numpy.asarray(counts) > 0) & (sums != 0.0)
+    e = numpy.full(sums.shape, numpy.nan)
+    e[ok] = sums[ok] / numpy.asarray(counts)[ok]
+    return e
+
+
 class EigenNoConvergence(RuntimeError):
     """`ContactMap.eigenvector` used up `max_matvecs` before its residual reached the
     tolerance (the counterpart of scipy's ArpackNoConvergence, which the reference's
@@ -424,6 +433,9 @@ class ContactMap(object):
             # KR vectors describe the unfiltered map: normalize() first, then filter()
             self._KRnorm = None
             self._KRexpected = None
+            # and so do what balance() / expected() left beside them
+            self.balance_masked_ = None
+            self.expected_sums_ = self.expected_counts_ = None
 
     def normalize(self):
         """KR matrix balancing and observed/expected normalisation, in place.
@@ -446,6 +458,112 @@ class ContactMap(object):
         dev = self._resident()
         _lib.check(dev._lib.bb_cm_normalize(dev._h, n, _lib.as_f64_ptr(kr), _lib.as_f64_ptr(ke)),
                    "bb_cm_normalize")
+
+    # -- balancing a raw map (docs/SPEC.md 2.5.2) --------------------------
+    def _balance_target(self):
+        """The device handle for balance() / expected(), which read the leading n_bins x n_bins
+        block and leave the matrix as it is (a host copy handed out by `matrix` stays valid)."""
+        n = self.n_bins
+        if self.shape[0] == 0:
+            raise ValueError("the contact map is empty (every bin was filtered out)")
+        if self.shape != (n + 1, n + 1):
+            raise ValueError("matrix shape does not match n_bins (was filter() used with "
+                             "keep_stale=True?)")
+        return self._dev if self._dev is not None else self._resident()
+
+    def _divide(self, bias, expected):
+        """The existing normalize path with the two vectors given (the map's own stay)."""
+        keep = self._KRnorm, self._KRexpected
+        self._KRnorm, self._KRexpected = bias, expected
+        try:
+            self.normalize()
+        finally:
+            self._KRnorm, self._KRexpected = keep
+
+    def balance(self, ignore_diags=0, min_nnz=0, tol=1e-5, max_iter=200, row_sum=None, apply=False):
+        """The bias vector of iterative correction (ICE; Imakaev et al. 2012) of the raw map,
+        computed on the resident matrix (`bb_cm_balance`; the definition is docs/SPEC.md 2.5.2).
+
+        The counted cells are those of the bins 0 .. n_bins - 1 with |i - j| >= `ignore_diags`.
+        A bin is masked if it has fewer than `min_nnz` non-zero counted cells or no count in
+        common with an unmasked bin.  The loop stops when the variance of the live bins' row sums,
+        relative to their mean, is below `tol`, or after `max_iter` updates.  The vector is scaled
+        so that the balanced map's mean row sum is `row_sum` -- None: the raw map's, so that the
+        counts keep their magnitude; 1.0: cooler's convention.
+
+        Returns the length-n_bins float64 vector b, NaN at masked bins (as Rao's KRnorm files
+        mark them), and keeps it as the map's KRnorm, so that `normalize()` and `fit_triples(
+        KRnorm=...)` can use it.  Sets `balance_iterations_` (updates made), `balance_variance_`,
+        `balance_converged_` and `balance_masked_` (bool array).  A negative or non-finite counted
+        cell raises ValueError.  apply=False leaves the matrix as it is, bit for bit; apply=True
+        then divides it in place by b_i b_j (`normalize()` with an all-ones expected vector:
+        masked bins become 0).  The same bits on every run."""
+        import ctypes
+        import math
+        ignore_diags, min_nnz, max_iter = int(ignore_diags), int(min_nnz), int(max_iter)
+        tol = float(tol)
+        if ignore_diags < 0 or min_nnz < 0:
+            raise ValueError("ignore_diags and min_nnz must not be negative")
+        if not (tol >= 0.0 and math.isfinite(tol)):
+            raise ValueError("tol must be finite and not negative")
+        if max_iter < 0:
+            raise ValueError("max_iter must not be negative")
+        if row_sum is not None and not (float(row_sum) > 0.0 and math.isfinite(float(row_sum))):
+            raise ValueError("row_sum must be positive and finite")
+        dev = self._balance_target()
+        n = self.n_bins
+        bias = numpy.empty(n, dtype=numpy.float64)
+        masked = numpy.zeros(n, dtype=numpy.uint8)
+        it, var = _lib.c_i64(), _lib.c_dbl()
+        _lib.check(dev._lib.bb_cm_balance(
+            dev._h, n, ignore_diags, min_nnz, tol, max_iter, 0.0 if row_sum is None else float(row_sum),
+            _lib.as_f64_ptr(bias), masked.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), it, var),
+            "bb_cm_balance")
+        self._KRnorm = bias
+        self.balance_iterations_, self.balance_variance_ = int(it.value), float(var.value)
+        self.balance_converged_ = self.balance_variance_ < tol
+        self.balance_masked_ = masked.astype(bool)
+        if apply:
+            self._divide(bias, numpy.ones(n))
+        return bias
+
+    def expected(self, bias="auto", apply=False):
+        """The distance-decay expected of the balanced map: e[k] = the mean over the live pairs
+        at distance k of M[i, i+k] / (bias[i] bias[i+k]), k = 0 .. n_bins - 1, in one sweep of the
+        resident upper triangle (`bb_cm_expected`; docs/SPEC.md 2.5.2).  A pair with a NaN bias
+        is not a live pair.  e[k] is NaN where no live pair exists or their sum is 0 -- never 0 --
+        so that `normalize()` turns such cells into 0.
+
+        `bias`: 'auto' -- the map's KRnorm (what `balance()` left, or what the constructor was
+        given) if there is one, else all ones; None -- all ones; or a length-n_bins vector.
+        Returns e and keeps it as the map's KRexpected; `expected_sums_` and `expected_counts_`
+        (int64) hold the two raw vectors.  apply=True then divides the map in place by
+        e[|i - j|] alone (`normalize()` with an all-ones bias).  After `balance()` and
+        `expected()` without `apply`, `normalize()` applies both, as on a Rao map."""
+        n = self.n_bins
+        if isinstance(bias, str):
+            if bias != "auto":
+                raise ValueError("bias must be 'auto', None or a vector of n_bins values")
+            bias = None if self._KRnorm is None else self._KRnorm
+            if bias is not None:
+                if bias.shape[0] < n:
+                    raise ValueError("KRnorm shorter than n_bins")
+                bias = bias[:n]
+        if bias is not None:
+            bias = numpy.ascontiguousarray(bias, dtype=numpy.float64)
+            if bias.shape != (n,):
+                raise ValueError("bias must have n_bins = %d values, got shape %r" % (n, bias.shape))
+        dev = self._balance_target()
+        sums = numpy.zeros(n, dtype=numpy.float64)
+        counts = numpy.zeros(n, dtype=numpy.int64)
+        _lib.check(dev._lib.bb_cm_expected(
+            dev._h, n, None if bias is None else _lib.as_f64_ptr(bias), _lib.as_f64_ptr(sums),
+            counts.ctypes.data_as(_lib.p_i64)), "bb_cm_expected")
+        self._KRexpected = expected_from_sums(sums, counts)
+        self.expected_sums_, self.expected_counts_ = sums, counts
+        if apply:
+            self._divide(numpy.ones(n), self._KRexpected)
+        return self._KRexpected
 
     def correlation(self):
         """Convert the map to a correlation map, in place (pyx:173-188:

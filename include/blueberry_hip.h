@@ -566,6 +566,35 @@ BB_API int bb_cm_release_scratch(int device);
  * unreachable_pairs (may be NULL): the number of pairs i < j without a path. */
 BB_API int bb_cm_shortest_paths(const bb_cm *src, bb_cm *dst, int kind, double alpha,
                                 int64_t *unreachable_pairs);
+/* Balancing of a raw map (docs/SPEC.md 2.5.2), over the leading n_bins x n_bins block of the
+ * resident matrix (d must be n_bins + 1; row and column n_bins are never read).  Only the upper
+ * triangle is read and the matrix is taken to be symmetric, as bb_cm_symv takes it.  Float64, no
+ * floating-point atomics, every sum in an order fixed by n_bins alone: the same bits on every
+ * run.  Neither call changes the matrix.
+ *
+ * bb_cm_balance: the bias vector of iterative correction (Imakaev et al. 2012) over the counted
+ * cells A_ij = M_ij, |i - j| >= ignore_diags.  A counted cell of the upper triangle that is
+ * negative or not finite: BB_ERR_INVALID with their number in the message.  Bin i is masked if
+ * it has fewer than min_nnz non-zero counted cells, or if its marginal over the cells shared
+ * with unmasked bins is 0 (repeated to the fixed point); no bin left: BB_ERR_INVALID.  From
+ * b = 1, x = 1 (0 at masked bins), it = 0:  s_i = x_i sum_j A_ij x_j over the live bins, mean =
+ * sum s_i / n_live, var = sum (s_i / mean - 1)^2 / n_live; stop if var < tol or it == max_iter;
+ * else b_i *= s_i / mean, x_i = 1 / b_i, ++it.  Then b *= sqrt(mean / target), target = row_sum,
+ * or (row_sum <= 0) the mean of iteration 0, so that the counts keep their magnitude.  The loop
+ * runs on the device, one sweep of the upper triangle per iteration (8 B per pair), a batch of
+ * iterations per scalar read-back.
+ * bias: n_bins doubles, NaN at masked bins (as Rao's KRnorm files mark them); masked: n_bins
+ * bytes, 1 = masked; iterations (updates made) and variance (the last var) may be NULL. */
+BB_API int bb_cm_balance(bb_cm *cm, int64_t n_bins, int64_t ignore_diags, int64_t min_nnz, double tol,
+                         int64_t max_iter, double row_sum, double *bias, uint8_t *masked,
+                         int64_t *iterations, double *variance);
+/* The distance decay of the balanced map, per diagonal k = 0 .. n_bins - 1, in one sweep of the
+ * upper triangle:  sums[k] = sum_i M[i][i+k] x_i x_{i+k} and counts[k] = #{i : x_i x_{i+k} != 0},
+ * x = 1 / bias and 0 where the bias is NaN; bias == NULL: all ones.  A pair with x_i x_{i+k} == 0
+ * is left out whatever its cell holds.  counts are exact; sums[k] / counts[k] is the expected
+ * vector bb_cm_normalize takes. */
+BB_API int bb_cm_expected(bb_cm *cm, int64_t n_bins, const double *bias, double *sums,
+                          int64_t *counts);
 /* Hand the resident matrix to a solver of n_bins = d bins on the same device, device
  * to device (same meaning of kind / alpha as bb_solver_set_wish_dense).  A solver on another
  * device packs over peer access where hipDeviceCanAccessPeer allows it (enabled here); without
