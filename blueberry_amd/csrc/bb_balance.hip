@@ -4,15 +4,12 @@
 // (d, d) float64 matrix.  Row and column n_bins are never read.  Like symv, only the UPPER
 // triangle is read (8 B per pair) and the matrix is taken to be symmetric.
 //
-//   band_symv_kernel   y = A x, A_ij = M_ij for |i - j| >= ignore_diags: symv_upper_kernel's
-//                      layout (64 rows x up to 4,096 columns per work item, 16 loads of 512
-//                      contiguous bytes in flight per wave, row partials per segment, column
-//                      partials per row block) with the band test where the products are
-//                      formed -- a cell inside the band is SELECTED out, never multiplied by 0
-//                      and never subtracted afterwards, so every sum is a sum of non-negative
-//                      terms.  Three cell rules share the kernel: the value (the iteration and
-//                      the mask's fixed point), "is not 0" (min_nnz) and "is negative or not
-//                      finite" (the input check).  bb::symv_reduce_kernel adds the partials.
+//   band_symv_kernel   y = A x, A_ij = M_ij for |i - j| >= ignore_diags: the product's one body
+//                      (bb::symv_item, bb_cm_internal.h) over the leading n x n block, row
+//                      stride d, the band's edge as the offsets from which a cell counts.  Every
+//                      sum is a sum of non-negative terms.  Three cell rules: the value (the
+//                      iteration, the mask's fixed point), "is not 0" (min_nnz), "is negative
+//                      or not finite" (the input check).  bb::symv_reduce_kernel adds the partials.
 //   balance_*_kernel   the mask, and one step of the loop (s, mean, var, the stopping rule,
 //                      b and x) in ONE workgroup: every sum in a fixed order, the loop's state
 //                      on the device.  A stopped loop turns later launches into no-ops, so the
@@ -23,8 +20,8 @@
 //                      (no cross-lane traffic); the 4 waves meet in LDS; one partial per (row
 //                      block, diagonal).  diag_reduce_kernel adds a diagonal's partials in
 //                      list order, in 8 slices.
-// No floating-point atomics anywhere: the same bits on every run (SPEC 2.7).  Traffic and the
-// reasons for a second product kernel beside symv's: DESIGN.md 4.15.
+// No floating-point atomics anywhere: the same bits on every run (SPEC 2.7).  Traffic, and why
+// the product has two entry points and no runtime flag: DESIGN.md 4.15.
 #include <float.h>
 #include <math.h>
 
@@ -37,25 +34,18 @@
 
 namespace {
 
+using bb::kCellBad;
+using bb::kCellNonzero;
+using bb::kCellValue;
 using bb::kSvGroup;
 using bb::kSvRows;
 using bb::kSvSeg;
 using bb::lds_barrier;
 
 // ---- the banded product -----------------------------------------------------------------------
-enum { kCellValue = 0, kCellNonzero = 1, kCellBad = 2 };
-
-// What a cell contributes, formed as the cell is loaded.  Under kCellBad the column side is
-// switched off (its multiplier x_row is taken as 0), so that every cell of the counted upper
-// triangle is seen once, by the row side: sum(y) = the number of offending cells.
-template <int MODE>
-__device__ __forceinline__ double cell_term(double a) {
-    if (MODE == kCellValue) return a;
-    if (MODE == kCellNonzero) return a != 0.0 ? 1.0 : 0.0;
-    return !(a >= 0.0 && a <= DBL_MAX) ? 1.0 : 0.0;      // negative, NaN, +inf
-}
-
 // `stop` (may be NULL): the loop's "stopped" word; a launch enqueued behind the stop returns.
+// A cell (row, c) counts on the row side from c = row + ignore on; on the column side the
+// diagonal never counts either.
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void band_symv_kernel(const double *__restrict__ m, int64_t ld,
                                                            int64_t n, int64_t ignore,
@@ -65,71 +55,7 @@ __global__ __launch_bounds__(256, 2) void band_symv_kernel(const double *__restr
                                                            double *__restrict__ colpart,
                                                            const int *__restrict__ stop) {
     if (stop != nullptr && *stop != 0) return;
-    __shared__ double meet[4][kSvGroup][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int2 it = items[blockIdx.x];
-    const int64_t I = it.x, S = it.y;
-    const int64_t row0 = I * kSvRows + wave * 16;
-    const int64_t c_begin = std::max<int64_t>(I * kSvRows, S * kSvSeg);
-    const int64_t c_end = std::min<int64_t>(n, (S + 1) * (int64_t)kSvSeg);
-    // a cell (row, c) counts on the row side from c = row + ignore on; on the column side the
-    // diagonal never counts (it would add m_ii x_i twice)
-    const int64_t off_row = ignore, off_col = std::max<int64_t>(ignore, 1);
-    double xr[16], racc[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        xr[r] = (MODE != kCellBad && row0 + r < n) ? x[row0 + r] : 0.0;
-        racc[r] = 0.0;
-    }
-    for (int64_t cg = c_begin; cg < c_end; cg += 64 * kSvGroup) {
-        double cacc[kSvGroup];
-#pragma unroll
-        for (int g = 0; g < kSvGroup; ++g) {
-            cacc[g] = 0.0;
-            const int64_t c0 = cg + 64 * g;              // chunk start (uniform)
-            if (c0 >= c_end) continue;
-            const int64_t c = c0 + lane;
-            const bool in_c = c < c_end;
-            const double xc = in_c ? x[c] : 0.0;
-            double a[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                a[r] = (in_c && row0 + r < n) ? cell_term<MODE>(m[(row0 + r) * ld + c]) : 0.0;
-            if (c0 < row0 + 16 + off_col) {
-                // the chunk reaches into the band (or below the diagonal) of this wave's rows
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int64_t row = row0 + r;
-                    const double v = a[r];
-                    racc[r] = fma(c >= row + off_row ? v : 0.0, xc, racc[r]);
-                    cacc[g] = fma(c >= row + off_col ? v : 0.0, xr[r], cacc[g]);
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    racc[r] = fma(a[r], xc, racc[r]);
-                    cacc[g] = fma(a[r], xr[r], cacc[g]);
-                }
-            }
-        }
-#pragma unroll
-        for (int g = 0; g < kSvGroup; ++g) meet[wave][g][lane] = cacc[g];
-        lds_barrier();   // (LDS only: nobody reads the global cells stored here)
-        for (int j = threadIdx.x; j < 64 * kSvGroup; j += 256) {
-            const int g = j >> 6, l = j & 63;
-            const int64_t c = cg + j;
-            if (c < c_end)
-                colpart[I * n + c] = ((meet[0][g][l] + meet[1][g][l]) + meet[2][g][l]) + meet[3][g][l];
-        }
-        lds_barrier();
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        double v = racc[r];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-        if (lane == 0 && row0 + r < n) rowpart[S * n + row0 + r] = v;
-    }
+    bb::symv_item<MODE>(m, ld, n, ignore, std::max<int64_t>(ignore, 1), x, items, rowpart, colpart);
 }
 
 // ---- the loop's vectors and state --------------------------------------------------------------
@@ -141,20 +67,6 @@ struct BalanceState {
     double mean, var;     // of the last evaluated iteration
     double mean0;         // of iteration 0
 };
-
-// Sum of one value per thread of a 1024-thread workgroup through sh[1024]: a binary tree in a
-// fixed order; every thread gets the total.
-template <typename T>
-__device__ __forceinline__ T block_sum_1024(T v, T *sh) {
-    __syncthreads();                       // sh may still be read from the sum before
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 512; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
-        __syncthreads();
-    }
-    return sh[0];
-}
 
 __global__ __launch_bounds__(256) void fill_kernel(double *__restrict__ v, double value, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -189,8 +101,9 @@ __global__ __launch_bounds__(1024) void balance_mask_kernel(const double *__rest
         live[i] = now ? 1 : 0;
         x[i] = now ? 1.0 : 0.0;
     }
-    killed = block_sum_1024(killed, sh);
-    alive = block_sum_1024(alive, sh);
+    killed = bb::block_sum<1024>(killed, sh);
+    __syncthreads();                              // sh[0] has been read: sh is free again
+    alive = bb::block_sum<1024>(alive, sh);
     if (threadIdx.x == 0) {
         st->changed = (int)std::min<long long>(killed, 1);
         st->n_live = alive;
@@ -212,14 +125,15 @@ __global__ __launch_bounds__(1024) void balance_step_kernel(const double *__rest
     double acc = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += 1024)
         if (live[i]) acc += x[i] * y[i];
-    const double mean = block_sum_1024(acc, sh) / n_live;
+    const double mean = bb::block_sum<1024>(acc, sh) / n_live;
     acc = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += 1024)
         if (live[i]) {
             const double t = x[i] * y[i] / mean - 1.0;
             acc += t * t;
         }
-    const double var = block_sum_1024(acc, sh) / n_live;
+    __syncthreads();                              // sh[0] has been read: sh is free again
+    const double var = bb::block_sum<1024>(acc, sh) / n_live;
     const bool stop = var < tol || it == max_iter;
     if (!stop)
         for (int64_t i = threadIdx.x; i < n; i += 1024)
@@ -360,82 +274,15 @@ __global__ __launch_bounds__(1024) void diag_reduce_kernel(const double *__restr
 }
 
 // ---- host side ---------------------------------------------------------------------------------
-inline size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// The work list of the diagonal pass: every (row block I, diagonal segment S) with a cell,
-// longest first.
-std::vector<int2> diag_items(int64_t n) {
-    const int64_t nrb = (n + kSvRows - 1) / kSvRows;
-    auto len = [&](const int2 &t) {
-        return std::min<int64_t>(n - (int64_t)t.x * kSvRows, (t.y + 1) * (int64_t)kSvSeg) -
-               (int64_t)t.y * kSvSeg;
-    };
-    std::vector<int2> items;
-    for (int64_t I = 0; I < nrb; ++I)
-        for (int64_t S = 0; S * kSvSeg < n - I * kSvRows; ++S) items.push_back(make_int2((int)I, (int)S));
-    std::stable_sort(items.begin(), items.end(),
-                     [&](const int2 &a, const int2 &b) { return len(a) > len(b); });
-    return items;
-}
-
-// The handle's scratch for an n x n leading block: product work list | diagonal work list |
-// partial sums (of whichever call runs: the product's row and column partials, or the diagonal
-// pass's sums and counts).  Made on first use and whenever n has changed (filter).
-struct BalanceScratch {
-    const int2 *items, *diag;
-    void *part;
-    int64_t nseg, nrb;
-};
-hipError_t balance_scratch(bb_cm *cm, int64_t n, BalanceScratch *out) {
-    const int64_t nrb = (n + kSvRows - 1) / kSvRows, nseg = (n + kSvSeg - 1) / kSvSeg;
-    const size_t part_bytes = std::max((size_t)(nseg + nrb) * (size_t)n * 8, (size_t)nrb * (size_t)n * 12);
-    if (cm->bal_n != n) {
-        const std::vector<int2> items = bb::symv_items(n), diag = diag_items(n);
-        const size_t ib = round256(items.size() * sizeof(int2)), db = round256(diag.size() * sizeof(int2));
-        cm->bal_n = -1;
-        hipError_t e = cm->bal.reserve(ib + db + part_bytes);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(cm->bal.p, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice,
-                               cm->stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync((char *)cm->bal.p + ib, diag.data(), diag.size() * sizeof(int2),
-                               hipMemcpyHostToDevice, cm->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(cm->stream);   // the lists die with this scope
-        if (e != hipSuccess) return e;
-        cm->bal_items = (int)items.size();
-        cm->bal_diag_items = (int)diag.size();
-        cm->bal_n = n;
-    }
-    const size_t ib = round256((size_t)cm->bal_items * sizeof(int2));
-    const size_t db = round256((size_t)cm->bal_diag_items * sizeof(int2));
-    out->items = (const int2 *)cm->bal.p;
-    out->diag = (const int2 *)((char *)cm->bal.p + ib);
-    out->part = (char *)cm->bal.p + ib + db;
-    out->nseg = nseg;
-    out->nrb = nrb;
-    return hipSuccess;
-}
-
-// y = A x under cell rule MODE, enqueued on the handle's stream
+// y = A x under cell rule MODE over the handle's prepared scratch, enqueued on its stream
 template <int MODE>
-hipError_t band_symv_enqueue(bb_cm *cm, const BalanceScratch &sc, int64_t n, int64_t ignore,
-                             const double *dx, double *dy, const int *stop) {
-    double *rowpart = (double *)sc.part, *colpart = rowpart + sc.nseg * n;
-    hipError_t e = bb::launch(band_symv_kernel<MODE>, dim3((unsigned)cm->bal_items), dim3(256), 0, cm->stream,
-                              (const double *)cm->m, cm->d, n, ignore, dx, sc.items, rowpart, colpart, stop);
-    if (e == hipSuccess)
-        e = bb::launch(bb::symv_reduce_kernel, dim3((unsigned)((n + 127) / 128)), dim3(1024), 0, cm->stream,
-                       (const double *)rowpart, (const double *)colpart, n, (int)sc.nseg, dy);
-    return e;
-}
-
-int cm_enter(const bb_cm *cm, int64_t n_bins, const char *who) {
-    if (!cm) return bb::fail(BB_ERR_INVALID, std::string(who) + ": contact map is NULL");
-    BB_TRY(bb::enter_device(cm->device));
-    if (!(n_bins >= 0 && n_bins + 1 == cm->d))
-        return bb::fail(BB_ERR_INVALID,
-                        std::string(who) + ": the matrix edge is not n_bins + 1 (filtered already?)");
-    return BB_OK;
+hipError_t band_symv_enqueue(bb_cm *cm, int64_t ignore, const double *dx, double *dy, const int *stop) {
+    return bb::product_enqueue(cm->bal, cm->stream, dy,
+                               [&](dim3 grid, const int2 *items, double *rowpart, double *colpart) {
+                                   return bb::launch(band_symv_kernel<MODE>, grid, dim3(256), 0, cm->stream,
+                                                     (const double *)cm->m, cm->d, cm->bal.n, ignore, dx,
+                                                     items, rowpart, colpart, stop);
+                               });
 }
 
 // iterations enqueued per read-back of the loop's state: a launch behind the stop costs a few
@@ -449,7 +296,8 @@ extern "C" {
 int bb_cm_balance(bb_cm *cm, int64_t n_bins, int64_t ignore_diags, int64_t min_nnz, double tol,
                   int64_t max_iter, double row_sum, double *bias, uint8_t *masked, int64_t *iterations,
                   double *variance) {
-    BB_TRY(cm_enter(cm, n_bins, "bb_cm_balance"));
+    BB_TRY(bb::cm_check(cm, "bb_cm_balance"));
+    BB_TRY(bb::cm_check_bins(cm, n_bins, "bb_cm_balance"));
     BB_REQUIRE(bias != nullptr && masked != nullptr, "bb_cm_balance: NULL argument");
     BB_REQUIRE(ignore_diags >= 0 && min_nnz >= 0, "bb_cm_balance: ignore_diags / min_nnz is negative");
     BB_REQUIRE(tol >= 0.0 && tol <= DBL_MAX && max_iter >= 0, "bb_cm_balance: bad tol / max_iter");
@@ -457,8 +305,7 @@ int bb_cm_balance(bb_cm *cm, int64_t n_bins, int64_t ignore_diags, int64_t min_n
     const int64_t n = n_bins;
     ignore_diags = std::min(ignore_diags, n);         // (beyond n - 1 nothing is counted anyway)
     BB_REQUIRE(n >= 1, "bb_cm_balance: no bin is left to balance (the map has no bins)");
-    BalanceScratch sc;
-    BB_TRY(bb::hip_status("bb_cm_balance", balance_scratch(cm, n, &sc), BB_ERR_NOMEM));
+    BB_TRY(bb::hip_status("bb_cm_balance", cm->bal.prepare(n, true, cm->stream), BB_ERR_NOMEM));
     bb::DevBuf bx, bbias, by, blive, bst;
     hipError_t e = bx.alloc((size_t)n * 8);
     if (e == hipSuccess) e = bbias.alloc((size_t)n * 8);
@@ -476,7 +323,7 @@ int bb_cm_balance(bb_cm *cm, int64_t n_bins, int64_t ignore_diags, int64_t min_n
     // 1. the input check: one pass over the counted upper triangle
     e = hipMemsetAsync(dst, 0, sizeof(BalanceState), st);
     if (e == hipSuccess) e = bb::launch(fill_kernel, gvec, b256, 0, st, x, 1.0, n);
-    if (e == hipSuccess) e = band_symv_enqueue<kCellBad>(cm, sc, n, ignore_diags, x, y, nullptr);
+    if (e == hipSuccess) e = band_symv_enqueue<kCellBad>(cm, ignore_diags, x, y, nullptr);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipMemcpy(host.data(), y, (size_t)n * 8, hipMemcpyDeviceToHost);
     BB_TRY(bb::hip_status("bb_cm_balance", e));
@@ -490,7 +337,7 @@ int bb_cm_balance(bb_cm *cm, int64_t n_bins, int64_t ignore_diags, int64_t min_n
     // 2. the mask: min_nnz on the raw map, once; then zero marginals over the live bins, to the
     //    fixed point (the product of the round that changes nothing is iteration 0's)
     if (min_nnz > 0) {
-        e = band_symv_enqueue<kCellNonzero>(cm, sc, n, ignore_diags, x, y, nullptr);
+        e = band_symv_enqueue<kCellNonzero>(cm, ignore_diags, x, y, nullptr);
         if (e == hipSuccess)
             e = bb::launch(balance_start_kernel, gvec, b256, 0, st, (const double *)y, (double)min_nnz, n,
                            live, x, b);
@@ -501,7 +348,7 @@ int bb_cm_balance(bb_cm *cm, int64_t n_bins, int64_t ignore_diags, int64_t min_n
     hs.changed = 1;
     hs.n_live = 0;
     while (e == hipSuccess && hs.changed != 0) {
-        e = band_symv_enqueue<kCellValue>(cm, sc, n, ignore_diags, x, y, nullptr);
+        e = band_symv_enqueue<kCellValue>(cm, ignore_diags, x, y, nullptr);
         if (e == hipSuccess)
             e = bb::launch(balance_mask_kernel, dim3(1), dim3(1024), 0, st, (const double *)y, n, live, x, dst);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -522,7 +369,7 @@ int bb_cm_balance(bb_cm *cm, int64_t n_bins, int64_t ignore_diags, int64_t min_n
         // at most the updates that are left, and the evaluation at which `it == max_iter` stops
         const int batch = (int)std::min<int64_t>(kBalanceBatch, max_iter - hs.it + 1);
         for (int q = 0; q < batch && e == hipSuccess; ++q) {
-            e = band_symv_enqueue<kCellValue>(cm, sc, n, ignore_diags, x, y, &dst->stopped);
+            e = band_symv_enqueue<kCellValue>(cm, ignore_diags, x, y, &dst->stopped);
             if (e == hipSuccess)
                 e = bb::launch(balance_step_kernel, dim3(1), dim3(1024), 0, st, (const double *)y, n,
                                (const unsigned char *)live, x, b, tol, (long long)max_iter, dst);
@@ -548,12 +395,12 @@ int bb_cm_balance(bb_cm *cm, int64_t n_bins, int64_t ignore_diags, int64_t min_n
 }
 
 int bb_cm_expected(bb_cm *cm, int64_t n_bins, const double *bias, double *sums, int64_t *counts) {
-    BB_TRY(cm_enter(cm, n_bins, "bb_cm_expected"));
+    BB_TRY(bb::cm_check(cm, "bb_cm_expected"));
+    BB_TRY(bb::cm_check_bins(cm, n_bins, "bb_cm_expected"));
     BB_REQUIRE(sums != nullptr && counts != nullptr, "bb_cm_expected: NULL argument");
     const int64_t n = n_bins;
     if (n == 0) return BB_OK;
-    BalanceScratch sc;
-    BB_TRY(bb::hip_status("bb_cm_expected", balance_scratch(cm, n, &sc), BB_ERR_NOMEM));
+    BB_TRY(bb::hip_status("bb_cm_expected", cm->bal.prepare(n, true, cm->stream), BB_ERR_NOMEM));
     bb::DevBuf bx, bs, bc;
     hipError_t e = bx.alloc((size_t)n * 8);
     if (e == hipSuccess) e = bs.alloc((size_t)n * 8);
@@ -561,9 +408,10 @@ int bb_cm_expected(bb_cm *cm, int64_t n_bins, const double *bias, double *sums, 
     BB_TRY(bb::hip_status("bb_cm_expected", e, BB_ERR_NOMEM));
     hipStream_t st = cm->stream;
     double *x = (double *)bx.p;
-    double *sumpart = (double *)sc.part;
-    int *cntpart = (int *)(sumpart + sc.nrb * n);
-    const dim3 grid((unsigned)cm->bal_diag_items), b256(256);
+    const int2 *diag = cm->bal.diag();
+    double *sumpart = (double *)cm->bal.part();
+    int *cntpart = (int *)(sumpart + cm->bal.nrb() * n);
+    const dim3 grid((unsigned)cm->bal.n_diag), b256(256);
     if (bias != nullptr) {
         // (the sums vector doubles as the staging place of the bias)
         e = hipMemcpyAsync(bs.p, bias, (size_t)n * 8, hipMemcpyHostToDevice, st);
@@ -572,10 +420,10 @@ int bb_cm_expected(bb_cm *cm, int64_t n_bins, const double *bias, double *sums, 
                            (const double *)bs.p, x, n);
         if (e == hipSuccess)
             e = bb::launch(diag_sums_kernel<true>, grid, b256, 0, st, (const double *)cm->m, cm->d, n,
-                           (const double *)x, sc.diag, sumpart, cntpart);
+                           (const double *)x, diag, sumpart, cntpart);
     } else {
         e = bb::launch(diag_sums_kernel<false>, grid, b256, 0, st, (const double *)cm->m, cm->d, n,
-                       (const double *)nullptr, sc.diag, sumpart, cntpart);
+                       (const double *)nullptr, diag, sumpart, cntpart);
     }
     if (e == hipSuccess)
         e = bb::launch(diag_reduce_kernel, dim3((unsigned)((n + 127) / 128)), dim3(1024), 0, st,

@@ -64,6 +64,8 @@ inline int64_t rows_per_unit(int dtype, int64_t n_bins) {
     return dtype != BB_F64 ? 4 : (wide_layout(dtype, n_bins) ? 2 : 8);
 }
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
+// the next 256-byte boundary: where a part of a device buffer cut into several starts
+constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // Select the device, failing loudly when there is none.
 int use_device(int device);

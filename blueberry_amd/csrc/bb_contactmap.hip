@@ -290,98 +290,17 @@ __global__ __launch_bounds__(256) void gather_kernel(const double *__restrict__ 
 }
 
 // ---- eigenvector (datatypes.pyx:216-235): Lanczos on the resident matrix -----------
-// y = M x from the UPPER triangle alone (round 3).  Reading both triangles of a symmetric
-// matrix costs 8 B per element where 8 B per PAIR will do (round 2's kernel did that: 4.25
-// TB/s, 53 % of peak, on its own accounting).  Here element (i, j),
-// j >= i, is read once and serves both ends, y_i += m_ij x_j and y_j += m_ij x_i -- the
-// pattern of the solver's sweep (kOpMatvec2).  The matrix is taken to be symmetric, as the
-// reference's eigsh call takes it (datatypes.pyx:234) and as every ContactMap is built.
-//   work item   64 rows (4 waves x 16) x up to 4096 columns of the upper triangle; the list
-//               is cut by rows AND columns so that no item is long (a row block alone would
-//               be 0.2 to 12.8 MB at d = 25k and the launch as slow as its longest)
-//   row side    16 per-lane accumulators per wave, reduced across the lanes once per item
-//               -> rowpart[segment][row]
-//   column side a lane owns one column of a 64-column chunk; the 16 rows of the wave add
-//               into one register; after 8 chunks the 4 waves' sums meet in LDS and leave
-//               as one value per column -> colpart[row block][column] (1.5 % of the bytes read)
-//   symv_reduce_kernel adds, per element of y, its row partials (<= d / 4096 + 1) and its
-//               column partials (<= d / 64 + 1) in a fixed order, 8 slices in parallel.
-// All loads are 8 bytes per lane, 512 contiguous bytes per wave: rows of an odd-d matrix
-// start 8 bytes off every other time, and 16 loads of a wave are in flight per chunk.
-using bb::kSvRows; using bb::kSvSeg; using bb::kSvGroup;   // bb_cm_internal.h
-// plain loads: the 512-byte segments of a wave are not line-aligned (odd d), neighbouring
-// chunks share their end lines, and a non-temporal load does not leave them in L2 for the
-// neighbour -- 481 against 505 us per product at d = 24,927
-__device__ __forceinline__ double sv_load(const double *p) { return *p; }
+// y = M x from the upper triangle: the plain instantiation of the product's one body
+// (bb::symv_item, bb_cm_internal.h, where the layout is told) -- the whole d x d matrix, the
+// diagonal on the row side only.  A kernel of its own and no flag on a shared one: this is the
+// Lanczos inner loop, and every difference from the banded product is a constant here.
 __global__ __launch_bounds__(256, 2) void symv_upper_kernel(const double *__restrict__ m, int64_t d,
                                                             const double *__restrict__ x,
                                                             const int2 *__restrict__ items,
                                                             double *__restrict__ rowpart,
                                                             double *__restrict__ colpart) {
-    __shared__ double meet[4][kSvGroup][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int2 it = items[blockIdx.x];
-    const int64_t I = it.x, S = it.y;
-    const int64_t row0 = I * kSvRows + wave * 16;
-    const int64_t c_begin = std::max<int64_t>(I * kSvRows, S * kSvSeg);
-    const int64_t c_end = std::min<int64_t>(d, (S + 1) * (int64_t)kSvSeg);
-    double xr[16], racc[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        xr[r] = row0 + r < d ? x[row0 + r] : 0.0;
-        racc[r] = 0.0;
-    }
-    for (int64_t cg = c_begin; cg < c_end; cg += 64 * kSvGroup) {
-        double cacc[kSvGroup];
-#pragma unroll
-        for (int g = 0; g < kSvGroup; ++g) {
-            cacc[g] = 0.0;
-            const int64_t c0 = cg + 64 * g;              // chunk start (uniform)
-            if (c0 >= c_end) continue;
-            const int64_t c = c0 + lane;
-            const bool in_c = c < c_end;
-            const double xc = in_c ? x[c] : 0.0;
-            double a[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                a[r] = (in_c && row0 + r < d) ? sv_load(m + (row0 + r) * d + c) : 0.0;
-            if (c0 < row0 + 16) {
-                // the chunk crosses this wave's rows: below the diagonal nothing counts, on it
-                // only the row side (the column side would count m_ii x_i twice)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    racc[r] = fma(c >= row0 + r ? a[r] : 0.0, xc, racc[r]);
-                    cacc[g] = fma(c > row0 + r ? a[r] : 0.0, xr[r], cacc[g]);
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    racc[r] = fma(a[r], xc, racc[r]);
-                    cacc[g] = fma(a[r], xr[r], cacc[g]);
-                }
-            }
-        }
-#pragma unroll
-        for (int g = 0; g < kSvGroup; ++g) meet[wave][g][lane] = cacc[g];
-        lds_barrier();   // (LDS only: nobody reads the global cells stored here)
-        for (int j = threadIdx.x; j < 64 * kSvGroup; j += 256) {
-            const int g = j >> 6, l = j & 63;
-            const int64_t c = cg + j;
-            if (c < c_end)
-                colpart[I * d + c] = ((meet[0][g][l] + meet[1][g][l]) + meet[2][g][l]) + meet[3][g][l];
-        }
-        lds_barrier();   // (LDS only: nobody reads the global cells stored here)
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        double v = racc[r];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-        if (lane == 0 && row0 + r < d) rowpart[S * d + row0 + r] = v;
-    }
+    bb::symv_item<bb::kCellValue>(m, d, d, 0, 1, x, items, rowpart, colpart);
 }
-
-using bb::symv_reduce_kernel;   // bb_cm_internal.h
 
 // part[j * S + s] = segment s of V[j] . w for the basis vectors j < k: one workgroup per
 // (vector, segment), S = gridDim.y segments, fixed-order sums.  S = 1 is the whole dot, written
@@ -399,7 +318,7 @@ __global__ __launch_bounds__(256) void basis_dots_kernel(const double *__restric
     const int64_t i0 = (int64_t)blockIdx.y * per, i1 = std::min<int64_t>(d, i0 + per);
     double a = 0.0;
     for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) a = fma(v[i], w[i], a);
-    a = bb::block_sum_256(a, sh);
+    a = bb::block_sum<256>(a, sh);
     if (threadIdx.x == 0) part[(int64_t)blockIdx.x * gridDim.y + blockIdx.y] = a;
 }
 
@@ -699,39 +618,19 @@ __global__ __launch_bounds__(kT * 8) void corr_finalize_kernel(const double *__r
     }
 }
 
-int cm_check(const bb_cm *cm, const char *who) {
-    if (!cm) return bb::fail(BB_ERR_INVALID, std::string(who) + ": contact map is NULL");
-    return bb::enter_device(cm->device);
-}
+using bb::cm_check;   // bb_cm_internal.h
 
 // y = M x from the upper triangle (symv_upper_kernel + symv_reduce_kernel), x and y on the
 // device, enqueued on the handle's stream.  The work list and the partial-sum buffers are
 // made on first use and whenever the edge has changed (filter), and kept with the handle.
 hipError_t symv_enqueue(bb_cm *cm, const double *dx, double *dy) {
-    const int64_t d = cm->d;
-    const int64_t nrb = (d + kSvRows - 1) / kSvRows, nseg = (d + kSvSeg - 1) / kSvSeg;
-    if (cm->sv_d != d) {
-        const std::vector<int2> items = bb::symv_items(d);
-        const size_t item_bytes = (items.size() * sizeof(int2) + 255) & ~(size_t)255;
-        const size_t need = item_bytes + (size_t)(nseg + nrb) * (size_t)d * 8;
-        hipError_t e = cm->sv.reserve(need);
-        if (e != hipSuccess) return e;
-        e = hipMemcpyAsync(cm->sv.p, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice,
-                           cm->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(cm->stream);   // `items` dies with this scope
-        if (e != hipSuccess) return e;
-        cm->sv_items = (int)items.size();
-        cm->sv_d = d;
-    }
-    const size_t item_bytes = ((size_t)cm->sv_items * sizeof(int2) + 255) & ~(size_t)255;
-    double *rowpart = (double *)((char *)cm->sv.p + item_bytes);
-    double *colpart = rowpart + nseg * d;
-    hipError_t e = bb::launch(symv_upper_kernel, dim3((unsigned)cm->sv_items), dim3(256), 0, cm->stream,
-                              (const double *)cm->m, d, dx, (const int2 *)cm->sv.p, rowpart, colpart);
-    if (e == hipSuccess)
-        e = bb::launch(symv_reduce_kernel, dim3((unsigned)((d + 127) / 128)), dim3(1024), 0, cm->stream,
-                       (const double *)rowpart, (const double *)colpart, d, (int)nseg, dy);
-    return e;
+    const hipError_t e = cm->sv.prepare(cm->d, false, cm->stream);
+    if (e != hipSuccess) return e;
+    return bb::product_enqueue(cm->sv, cm->stream, dy,
+                               [&](dim3 grid, const int2 *items, double *rowpart, double *colpart) {
+                                   return bb::launch(symv_upper_kernel, grid, dim3(256), 0, cm->stream,
+                                                     (const double *)cm->m, cm->d, dx, items, rowpart, colpart);
+                               });
 }
 
 // sums[c] = column c's marginal (column_sums_kernel), enqueued on the handle's stream
@@ -835,8 +734,8 @@ int bb_cm_destroy(bb_cm *cm) {
     (void)hipSetDevice(cm->device);
     bb::release_stream(cm->device, cm->stream);     // synchronises it
     (void)hipFree(cm->m);
-    cm->sv.release();
-    cm->bal.release();
+    cm->sv.buf.release();
+    cm->bal.buf.release();
     delete cm;
     (void)hipGetLastError();   // tear-down is best effort; its errors end here
     return BB_OK;
@@ -928,8 +827,7 @@ int bb_cm_scatter(bb_cm *cm, const double *triples, int64_t n, int32_t resolutio
 int bb_cm_normalize(bb_cm *cm, int64_t n_bins, const double *KRnorm, const double *KRexpected) {
     BB_TRY(cm_check(cm, "bb_cm_normalize"));
     BB_REQUIRE(KRnorm != nullptr && KRexpected != nullptr, "bb_cm_normalize: NULL argument");
-    BB_REQUIRE(n_bins >= 0 && n_bins + 1 == cm->d,
-               "bb_cm_normalize: the matrix edge is not n_bins + 1 (filtered already?)");
+    BB_TRY(bb::cm_check_bins(cm, n_bins, "bb_cm_normalize"));
     const int64_t d = cm->d;
     bb::DevBuf kr, ke;
     hipError_t e = kr.alloc((size_t)n_bins * sizeof(double));
@@ -1209,8 +1107,8 @@ int bb_cm_correlation(bb_cm *cm, double *tflops) {
     // platform the first touch of a fresh block of that size costs 0.17-0.35 s
     // (tools/alloc_probe.py): the whole call took 1.5x its Gram kernel.
     struct View { void *p; } xc, g, sd;
-    const size_t xc_bytes = ((size_t)dp * ldx * 8 + 255) & ~(size_t)255;
-    const size_t g_bytes = ((size_t)dp * dp * 8 + 255) & ~(size_t)255;
+    const size_t xc_bytes = bb::align256((size_t)dp * ldx * 8);
+    const size_t g_bytes = bb::align256((size_t)dp * dp * 8);
     const size_t need = xc_bytes + g_bytes + (size_t)d * 8;
     hipError_t e = scr->buf.reserve(need);
     BB_TRY(bb::hip_status("bb_cm_correlation", e, BB_ERR_NOMEM));

@@ -18,7 +18,6 @@ struct MiscScratch : bb::DeviceScratch {
         if (buf.bytes > kKeepBytes) buf.release();
     }
 };
-constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 constexpr int kScanBlock = 256;
 constexpr int kItems = 4;  // per thread -> 1024 elements per workgroup
@@ -196,9 +195,9 @@ int bb_benjamini_hochberg(const double *p_values, int64_t d, int64_t n, double *
     const int64_t nblocks = (d + per_block - 1) / per_block;
     MiscScratch *c = bb::per_device<MiscScratch>(device);
     std::lock_guard<std::mutex> lock(c->mu);
-    const size_t o_q = align256((size_t)d * 8), o_bm = o_q + align256((size_t)d * 8),
-                 o_bc = o_bm + align256((size_t)nblocks * 8), o_fc = o_bc + align256((size_t)nblocks * 4),
-                 total = o_fc + align256((size_t)nblocks * 4);
+    const size_t o_q = bb::align256((size_t)d * 8), o_bm = o_q + bb::align256((size_t)d * 8),
+                 o_bc = o_bm + bb::align256((size_t)nblocks * 8), o_fc = o_bc + bb::align256((size_t)nblocks * 4),
+                 total = o_fc + bb::align256((size_t)nblocks * 4);
     hipError_t e = c->reserve(total);
     BB_TRY(bb::hip_status("bb_benjamini_hochberg", e, BB_ERR_NOMEM));
     hipStream_t st = c->stream;
@@ -230,7 +229,7 @@ int bb_downsample(const float *yp1, int64_t n1, float *yp5i, int64_t n5, int dev
     if (n5 < 2) return BB_OK;
     MiscScratch *c = bb::per_device<MiscScratch>(device);
     std::lock_guard<std::mutex> lock(c->mu);
-    const size_t o_b = align256((size_t)n1 * n1 * 4), total = o_b + align256((size_t)n5 * n5 * 4);
+    const size_t o_b = bb::align256((size_t)n1 * n1 * 4), total = o_b + bb::align256((size_t)n5 * n5 * 4);
     hipError_t e = c->reserve(total);
     BB_TRY(bb::hip_status("bb_downsample", e, BB_ERR_NOMEM));
     hipStream_t st = c->stream;

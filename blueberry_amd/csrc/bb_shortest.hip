@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256) void fw_store_kernel(const double *__restrict_
         out[i * d + j] = none ? 0.0 : v;
         n += (none && j > i) ? 1 : 0;
     }
-    n = bb::block_sum_256(n, part);
+    n = bb::block_sum<256>(n, part);
     if (threadIdx.x == 0) counts[i] = n;
 }
 

@@ -33,6 +33,12 @@ from tests import _large_maps as lm
 pytestmark = pytest.mark.gpu
 
 SIZES = [2, 3, 64, 65, 66, 129, 4096, 4097, 4098, 4161, 4162, 8193]
+# ignore_diags = 17: with 0 (the plain product's offsets) the one band at which a 64-column chunk
+# starts exactly 15 + max(ignore_diags, 1) columns after a wave's first row -- the chunk at which
+# the product's body chooses between its select branch and its plain one; one row block, and a
+# whole row block in the second segment.  The model leaves 125 and 4,025 live bins of the
+# Hi-C-like map under that band, 113 and 3,893 of the integer map at min_nnz = 5.
+BAND17_SIZES = [129, 4161]
 EPS = 2.0 ** -52
 
 
@@ -80,14 +86,11 @@ def test_expected_sums_and_counts_equal_the_model_on_integer_maps(d):
     assert same_bits(cm.to_host(), m)                             # nothing was written
 
 
-@pytest.mark.parametrize("d", SIZES)
-def test_mask_equals_the_model_on_integer_maps(d):
-    """ignore_diags in {0, 1, 2, 65} x min_nnz in {0, 5}: dead rows, the thin bins (min_nnz), the
-    hanger (the mask's fixed point) and the bin whose counts all lie inside a band of 65."""
+def check_mask_equals_the_model(d, bands):
     m, special = bm.integer_map(d, d)
     cm = bb.ContactMap.from_matrix(m)
     seen_hanger = False
-    for ignore_diags in (0, 1, 2, 65):
+    for ignore_diags in bands:
         a = bm.counted_cells(m, ignore_diags)
         for min_nnz in (0, 5):
             live = bm.balance_mask(a, min_nnz)
@@ -105,8 +108,20 @@ def test_mask_equals_the_model_on_integer_maps(d):
             if special and min_nnz == 5 and ignore_diags == 0:
                 h = special["hanger"]
                 seen_hanger = (a[h] != 0).sum() >= 5 and cm.balance_masked_[h]
-    assert seen_hanger == bool(special)
+    assert seen_hanger == (bool(special) and 0 in bands)      # (the hanger is looked for at band 0)
     assert same_bits(cm.to_host(), m)
+
+
+@pytest.mark.parametrize("d", SIZES)
+def test_mask_equals_the_model_on_integer_maps(d):
+    """ignore_diags in {0, 1, 2, 65} x min_nnz in {0, 5}: dead rows, the thin bins (min_nnz), the
+    hanger (the mask's fixed point) and the bin whose counts all lie inside a band of 65."""
+    check_mask_equals_the_model(d, (0, 1, 2, 65))
+
+
+@pytest.mark.parametrize("d", BAND17_SIZES)
+def test_mask_equals_the_model_under_a_band_of_17(d):
+    check_mask_equals_the_model(d, (17,))
 
 
 def test_a_map_inside_the_ignored_band_masks_every_bin():
@@ -141,9 +156,7 @@ def test_junk_in_row_and_column_n_bins_changes_nothing():
 
 
 # ---- 2. toleranced: the Hi-C-like generator ------------------------------------------------------
-@pytest.mark.parametrize("ignore_diags", [0, 2])
-@pytest.mark.parametrize("d", SIZES)
-def test_twenty_updates_match_the_model(d, ignore_diags):
+def check_twenty_updates_match_the_model(d, ignore_diags):
     want = bm.hic_like_balance(d, ignore_diags, 0, 0.0, 20)
     cm = bb.ContactMap.from_matrix(bm.hic_like_raw(d))
     if want is None:                                               # (d = 2, 3 under a band of 2)
@@ -160,6 +173,17 @@ def test_twenty_updates_match_the_model(d, ignore_diags):
     assert numpy.array_equal(cm.balance_masked_, want["masked"])
     assert err <= bound
     assert b is cm._KRnorm and b.dtype == numpy.float64 and b.shape == (d - 1,)
+
+
+@pytest.mark.parametrize("ignore_diags", [0, 2])
+@pytest.mark.parametrize("d", SIZES)
+def test_twenty_updates_match_the_model(d, ignore_diags):
+    check_twenty_updates_match_the_model(d, ignore_diags)
+
+
+@pytest.mark.parametrize("d", BAND17_SIZES)
+def test_twenty_updates_match_the_model_under_a_band_of_17(d):
+    check_twenty_updates_match_the_model(d, 17)
 
 
 @pytest.mark.parametrize("d", SIZES)
