@@ -164,8 +164,14 @@ __global__ __launch_bounds__(kNT * 8) void normalize128_kernel(double *m, int64_
 }
 
 // Scatter, pass 1: every cell a triple names records the LAST triple that names it
-// (integer atomicMax of t + 1 on the cell's own 8 bytes: the matrix was zeroed first,
-// and a count is only stored in pass 2).  No winner array the size of the matrix.
+// (integer atomicMax of triple t's mark on the cell's own 8 bytes: the matrix was zeroed
+// first, and a count is only stored in pass 2).  No winner array the size of the matrix.
+// The mark is t + 1 in the payload of a negative quiet NaN: pass 2 stores counts into cells
+// that other threads of pass 2 are still comparing with their marks, and a count is
+// nan_to_num'ed as it is read, so it is never a NaN and can equal no mark.  (A bare t + 1 is
+// the bit pattern of a denormal count: a later triple's count of those bits made an earlier
+// triple of the same cell take the cell for its own and store over it.)  The marks order as
+// the triples do on the unsigned view, above every count and the cleared cell's 0.
 // Element c of triple t is tr[t * st + c * sc]: (1, n) for the reference's column-major
 // array (pyx:111-113), (3, 1) for C-ordered (n, 3) rows.  `present` (d bytes, may be NULL)
 // gets a 1 for every bin a position falls in, `offgrid` a 1 if some position is not exactly
@@ -176,6 +182,10 @@ __global__ __launch_bounds__(kNT * 8) void normalize128_kernel(double *m, int64_
 // The two bins of a triple with the (nan_to_num'ed) positions pj, pk; false if one of them is
 // outside [0, d).  (A position beyond the int range -- an infinity turned into 1.8e308 -- is
 // out of range whatever the cast would make of it.)
+__device__ __forceinline__ unsigned long long scatter_mark(int64_t t) {
+    return 0xFFF8000000000000ull | (unsigned long long)(t + 1);     // t + 1 < 2^31 (bb_cm_scatter_ex)
+}
+
 __device__ __forceinline__ bool triple_bins(double pj, double pk, double resolution, int64_t d,
                                             int &j, int &k) {
     const double qj = pj / resolution, qk = pk / resolution;
@@ -202,8 +212,8 @@ __global__ void scatter_mark_kernel(const double *__restrict__ tr, int64_t n, in
         if ((double)j * resolution != pj || (double)k * resolution != pk) *offgrid = 1;
     }
     unsigned long long *cells = reinterpret_cast<unsigned long long *>(m);
-    atomicMax(&cells[(int64_t)j * d + k], (unsigned long long)(t + 1));
-    atomicMax(&cells[(int64_t)k * d + j], (unsigned long long)(t + 1));
+    atomicMax(&cells[(int64_t)j * d + k], scatter_mark(t));
+    atomicMax(&cells[(int64_t)k * d + j], scatter_mark(t));
 }
 
 // Pass 2: the winning triple stores its count (plain stores, as pyx:115-116).
@@ -215,9 +225,9 @@ __global__ void scatter_store_kernel(const double *__restrict__ tr, int64_t n, i
     if (!triple_bins(nan_to_num(tr[t * st]), nan_to_num(tr[t * st + sc]), resolution, d, j, k)) return;
     const double c = nan_to_num(tr[t * st + 2 * sc]);
     unsigned long long *cells = reinterpret_cast<unsigned long long *>(m);
-    // a cell still holding t + 1 is ours; j == k names one cell twice, harmlessly
-    if (cells[(int64_t)j * d + k] == (unsigned long long)(t + 1)) m[(int64_t)j * d + k] = c;
-    if (cells[(int64_t)k * d + j] == (unsigned long long)(t + 1)) m[(int64_t)k * d + j] = c;
+    // a cell still holding our mark is ours; j == k names one cell twice, harmlessly
+    if (cells[(int64_t)j * d + k] == scatter_mark(t)) m[(int64_t)j * d + k] = c;
+    if (cells[(int64_t)k * d + j] == scatter_mark(t)) m[(int64_t)k * d + j] = c;
 }
 
 // Column marginals: one thread per column, rows added IN ORDER (that is numpy's

@@ -1804,15 +1804,21 @@ __global__ __launch_bounds__(256) void scatter_entries_kernel(
     const int64_t u = (int64_t)t * UPT + ri / RPU;
     if (u < u_begin || u >= u_end) return;  // another rank's unit
     T *cell = units + (u - u_begin) * (RPU * VW) + (ri % RPU) * VW + (j - J * VW);
+    // Entry k's mark: k + 1 under the sign bit.  Phase 2 stores wish distances into cells that
+    // other threads of phase 2 are still comparing with their marks; a stored distance is 0 or
+    // positive (wish_from_value), so it can equal no mark.  (A bare k + 1 is the bit pattern of
+    // a float: from 228,737,632 entries in one chunk on, that of a distance >= wish_floor.)
+    // k + 1 <= 2^30 (the callers' chunks), and the marks order as the entries do.
+    const Bits mark = ((Bits)1 << (8 * sizeof(Bits) - 1)) | (Bits)(k + 1);
     if (phase == 0) {
         *reinterpret_cast<Bits *>(cell) = 0;
         return;
     }
     if (phase == 1) {
-        atomicMax(reinterpret_cast<Bits *>(cell), (Bits)(k + 1));
+        atomicMax(reinterpret_cast<Bits *>(cell), mark);
         return;
     }
-    if (*reinterpret_cast<const Bits *>(cell) != (Bits)(k + 1)) return;   // a later entry won
+    if (*reinterpret_cast<const Bits *>(cell) != mark) return;   // a later entry won
     double v = src.tr ? nan_to_num_f64(src.tr[k * src.st + 2 * src.sc]) : src.vals[k];
     // KR balancing + observed/expected, the element-wise form of the loop at
     // reference datatypes.pyx:166-169 (same operation order)
