@@ -34,25 +34,6 @@ int enter_device(int device) {
     return BB_OK;
 }
 
-hipError_t GrowBuf::reserve(size_t need) {
-    if (need <= bytes) return hipSuccess;
-    release();
-    const hipError_t e = hipMalloc(&p, need);
-    if (e == hipSuccess) {
-        bytes = need;
-    } else {
-        p = nullptr;
-        (void)hipGetLastError();
-    }
-    return e;
-}
-
-void GrowBuf::release() {
-    (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-}
-
 namespace {
 constexpr size_t kPooledStreams = 8;
 std::mutex g_stream_mu;

@@ -196,7 +196,7 @@ inline std::vector<int2> diag_items(int64_t n) {
 // call runs: the product's row and column partials ((n/4096 + n/64) n doubles), or the
 // diagonal pass's sums and counts (n/64 n doubles and ints).
 struct ProductScratch {
-    GrowBuf buf;
+    DevBuf buf;
     int64_t n = -1;               // the size the work lists were built for
     int n_items = 0, n_diag = 0;
     int64_t nrb() const { return (n + kSvRows - 1) / kSvRows; }

@@ -103,24 +103,77 @@ inline hipError_t launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds
     return launch_impl(kernel, grid, block, lds, stream, vals, std::index_sequence_for<P...>{});
 }
 
-// A device allocation that frees itself (host-staged entry points).
+// THE owner of a device allocation: what it holds is freed when it is reset, re-allocated,
+// assigned over or destroyed, and by nobody else.  A handle keeps its buffers as members of
+// this type, a host-staged entry point as locals; a plain pointer into one is a view.  Movable,
+// not copyable.  alloc() frees what is there and allocates anew (at least one byte); reserve()
+// is the grow-only form a scratch arena uses: it keeps what is there when that is large enough
+// (else the contents are lost).  A failed allocation leaves the buffer empty and consumes the
+// failed hipMalloc's error on the spot (see launch() above).  adopt() takes over memory made
+// elsewhere that hipFree releases (hipExtMallocWithFlags).
 struct DevBuf {
     void *p = nullptr;
+    size_t bytes = 0;
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+    DevBuf(DevBuf &&o) noexcept { *this = std::move(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept {   // (what this held goes with o)
+        std::swap(p, o.p);
+        std::swap(bytes, o.bytes);
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    explicit operator bool() const { return p != nullptr; }
+    template <class T>
+    T *as() const { return (T *)p; }
+    void reset() {
+        if (p) (void)hipFree(p);
+        p = nullptr, bytes = 0;
+    }
+    void adopt(void *mem, size_t n = 0) {
+        reset();
+        p = mem, bytes = n;
+    }
+    hipError_t alloc(size_t n) {
+        reset();
+        const hipError_t e = hipMalloc(&p, n ? n : 1);
+        if (e == hipSuccess) {
+            bytes = n;
+        } else {
+            p = nullptr;
+            (void)hipGetLastError();
+        }
+        return e;
+    }
+    hipError_t reserve(size_t need) { return need <= bytes ? hipSuccess : alloc(need); }
 };
+// b.alloc(bytes) as the library's status: BB_ERR_NOMEM with "hipMalloc failed: <HIP's text>".
+inline int alloc_status(DevBuf &b, size_t bytes) {
+    return hip_status("hipMalloc failed", b.alloc(bytes), BB_ERR_NOMEM);
+}
 
-// A grow-only device allocation: reserve() keeps what is there when it is large enough, else
-// frees it and allocates anew (the contents are lost).  A failed reserve leaves the buffer
-// empty and consumes the failed hipMalloc's error on the spot (see launch() above).
-struct GrowBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    hipError_t reserve(size_t need);
-    void release();
+// The owner of a HIP event, as DevBuf is of memory: movable, not copyable, empty or valid.
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    Event(Event &&o) noexcept { std::swap(e, o.e); }
+    Event &operator=(Event &&o) noexcept {   // (what this held goes with o)
+        std::swap(e, o.e);
+        return *this;
+    }
+    ~Event() { reset(); }
+    operator hipEvent_t() const { return e; }
+    void reset() {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    hipError_t create(unsigned flags = hipEventDefault) {
+        reset();
+        return hipEventCreateWithFlags(&e, flags);   // (writes e on success only)
+    }
 };
 
 // Scratch kept per device between calls: a stream made on first use and ONE grow-only arena,
@@ -129,7 +182,7 @@ struct GrowBuf {
 struct DeviceScratch {
     std::mutex mu;
     hipStream_t stream = nullptr;
-    GrowBuf buf;
+    DevBuf buf;
     // the stream (created now if there is none yet) and at least `bytes` of arena
     hipError_t reserve(size_t bytes) {
         const hipError_t e = stream ? hipSuccess : hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);

@@ -744,8 +744,8 @@ int bb_cm_destroy(bb_cm *cm) {
     (void)hipSetDevice(cm->device);
     bb::release_stream(cm->device, cm->stream);     // synchronises it
     (void)hipFree(cm->m);
-    cm->sv.buf.release();
-    cm->bal.buf.release();
+    cm->sv.buf.reset();
+    cm->bal.buf.reset();
     delete cm;
     (void)hipGetLastError();   // tear-down is best effort; its errors end here
     return BB_OK;
@@ -1102,7 +1102,7 @@ int bb_cm_release_scratch(int device) {
     BB_TRY(bb::enter_device(device));
     CmScratch *sc = bb::per_device<CmScratch>(device);
     std::lock_guard<std::mutex> lock(sc->mu);
-    sc->buf.release();
+    sc->buf.reset();
     return BB_OK;
 }
 

@@ -15,7 +15,7 @@ namespace {
 constexpr size_t kKeepBytes = (size_t)1 << 30;
 struct MiscScratch : bb::DeviceScratch {
     void trim() {
-        if (buf.bytes > kKeepBytes) buf.release();
+        if (buf.bytes > kKeepBytes) buf.reset();
     }
 };
 

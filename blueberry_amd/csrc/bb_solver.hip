@@ -5,6 +5,13 @@
 // one process drives on several devices (bb_group_*).  The kernels are in
 // bb_solver_kernels.h.  gfx950 only.
 //
+// Who owns what: every device allocation and event of a handle (bb_solver, bb_triples, bb_group)
+// is a bb::DevBuf / bb::Event member of it (bb_common.h) and goes with the handle, or earlier
+// by reset(); a staging buffer is such an owner as a local.  Plain pointers are views: into the
+// solver's arena, or -- d_exch -- of own_exch or of a caller's memory.  The destroy functions
+// keep only what has an order: the stream (the pool's), the communicator (the cache's, or the
+// solver's own) and the peers' arenas it opened.
+//
 // Specification: docs/SPEC.md (build-authored; the reference has no solver,
 // SURVEY.md section 0).  Data layout and kernel design: DESIGN.md 3-4.
 #include <math.h>
@@ -46,13 +53,16 @@ struct bb_solver {
     bool own_stream = false;
     bool stream_stuck = false;     // behind a collective that cannot be aborted: never waited on again
 
-    void *d_units = nullptr, *d_X = nullptr, *d_V = nullptr, *d_part = nullptr, *d_exch = nullptr;
+    void *d_units = nullptr, *d_X = nullptr, *d_V = nullptr, *d_part = nullptr;
+    // the exchange buffer: a view of own_exch, or -- own_exch empty -- the memory a caller gave
+    // (bb_solver_set_exchange_buffer), which is never freed here
+    void *d_exch = nullptr;
+    bb::DevBuf own_exch;
     double momentum = 0.0;
-    bool own_exch = false;
     int2 *d_udesc = nullptr;
     int chunk_q = 0, chunk_r = 0;  // units per wave: n_local = n_waves * q + r
     bool nontemporal = true;
-    char *d_arena = nullptr;       // the one allocation behind every d_* below but d_exch / peer / mv_in
+    bb::DevBuf d_arena;            // the one allocation behind every plain d_* pointer here (views of it)
     int2 *d_wave_slots = nullptr;  // per wave {first private slot, the workgroup's shared slot}
     int lds_wave_floats = 0;       // LDS region per wave of the sweep, in 4-byte words
     double *d_stresspart = nullptr;
@@ -61,15 +71,15 @@ struct bb_solver {
     std::vector<int32_t> wave_last_strip;  // strip each wave ends in, -1: no units
     // several maps in one solver (bb_solver_set_maps)
     int n_maps = 1;
-    void *d_bin_scale = nullptr;         // T per bin (n_pad): the factor on its gradient
-    int *d_map_ptr = nullptr, *d_map_idx = nullptr;
-    double *d_map_scalar = nullptr;      // per-map stress of bb_solver_stress_maps
+    bb::DevBuf d_bin_scale;              // T per bin (n_pad): the factor on its gradient
+    bb::DevBuf d_map_ptr, d_map_idx;     // int: the maps' lists of stress partials (CSR)
+    bb::DevBuf d_map_scalar;             // double: per-map stress of bb_solver_stress_maps
     std::vector<int64_t> map_begin;      // first bin of every map, + n_bins
     int64_t *d_red_lists = nullptr;   // reduce_sliced_kernel: one padded chunk list per block
     int red_stride = 0, red_slices = 0;   // entries per block (multiple of 16 * slices); 4 or 8 slices
     double *d_stress_hist = nullptr, *d_stress_scalar = nullptr;
     double *d_f64_tmp = nullptr;  // (n_pad,3) staging for coordinate I/O
-    void *d_mv_in = nullptr;      // (n_pad,3) right-hand sides of bb_solver_matvec_sq, kept
+    bb::DevBuf d_mv_in;           // (n_pad,3) right-hand sides of bb_solver_matvec_sq, kept
     int64_t rowpart_elems = 0, colpart_elems = 0;
     int n_waves = 0, n_slots = 0;
     int wpb = 4;                   // waves per workgroup of the sweep: 4, or 8 (paired, see kernel)
@@ -90,18 +100,18 @@ struct bb_solver {
     bool comm_suspect = false;      // a collective on it failed to enqueue: never handed out again
 
     // peer exchange (bb_solver_peer_*)
-    void *peer_arena = nullptr;             // this rank's receive arena (uncached)
+    bb::DevBuf peer_arena;                  // this rank's receive arena (uncached)
     int64_t peer_slot_elems = 0, peer_arena_bytes = 0;
     std::vector<void *> peer_mapped;        // arenas of all ranks as mapped here (own = peer_arena)
     std::vector<void *> peer_opened;        // the ones that came from hipIpcOpenMemHandle
-    void *d_peer_table = nullptr;           // PeerTable<T>[2], one per parity
-    void *d_peer_table_x = nullptr;         // PeerTableX<T>[2]: the one-launch exchange
+    bb::DevBuf d_peer_table;                // PeerTable<T>[2], one per parity
+    bb::DevBuf d_peer_table_x;              // PeerTableX<T>[2]: the one-launch exchange
     bool peer_fused = true;                 // reduce_exchange_kernel (BB_PEER_FUSED=0: two launches)
-    PeerState *d_peer_state = nullptr;      // sticky failure flag + last complete exchange
+    bb::DevBuf d_peer_state;                // PeerState: sticky failure flag + last complete exchange
     int peer_clock_khz = 100000;            // constant-rate clock behind wall_clock64()
     int peer_ranks_on_gpu = 1;              // most ranks of the job on one GPU (a rehearsal: > 1)
-    unsigned *d_peer_mask = nullptr;        // per block: the ranks whose units touch it (bit r)
-    unsigned *d_peer_counter = nullptr;
+    bb::DevBuf d_peer_mask;                 // unsigned per block: the ranks whose units touch it (bit r)
+    bb::DevBuf d_peer_counter;              // unsigned: the reduce's two-level check-in
     unsigned long long peer_seq = 0;        // iterations exchanged so far
     long long peer_limit_ticks = 0;
     bool peer_connected = false;
@@ -123,24 +133,63 @@ struct bb_solver {
     bool timing = false;
     int timing_stride = 1;      // events on every timing_stride-th iteration
     int64_t timing_iter = 0;    // iterations seen since timing was (re-)enabled
-    std::vector<hipEvent_t> ev;  // triples: start, after grad, after reduce
+    std::vector<bb::Event> ev;   // triples: start, after grad, after reduce
     size_t ev_used = 0;
 };
 
 namespace {
 
 void comm_release(bb_solver *s, bool destroy);   // the communicator cache, further down
-int64_t peer_xpoison_offset(const bb_solver *s);  // the peer arena's layout, further down
 
 constexpr int64_t kHistCap = 1 << 20;
 constexpr size_t kMaxTimedLaunches = 4096;
 
-template <typename T>
-int dev_alloc(T **p, int64_t count) {
-    *p = nullptr;
-    if (count <= 0) count = 1;
-    hipError_t e = hipMalloc((void **)p, (size_t)count * sizeof(T));
-    return bb::hip_status("hipMalloc failed", e, BB_ERR_NOMEM);
+// The kind / alpha rule of every set_wish_* entry point, in who's name.
+int check_kind_alpha(const char *who, int kind, double alpha) {
+    BB_REQUIRE(kind == BB_KIND_WISH || kind == BB_KIND_COUNTS, std::string(who) + ": bad kind");
+    BB_REQUIRE(kind == BB_KIND_WISH || alpha > 0.0, std::string(who) + ": alpha must be > 0");
+    return BB_OK;
+}
+
+// (n_bins, 3) float64 rows of the host -> the (n_pad, 3) device buffer dst, its padding rows
+// zero; both enqueued on `stream`.
+hipError_t upload_padded(const bb_solver *s, double *dst, const double *rows, hipStream_t stream) {
+    const hipError_t e = hipMemsetAsync(dst, 0, (size_t)s->L.n_pad * 3 * sizeof(double), stream);
+    if (e != hipSuccess) return e;
+    return hipMemcpyAsync(dst, rows, (size_t)s->L.n_bins * 3 * sizeof(double), hipMemcpyHostToDevice, stream);
+}
+
+// Peer access from the current device to `device`; "already enabled" is success, and what it
+// leaves in the thread's error word is consumed here.  A failure reads "<who>: <HIP's text>".
+int enable_peer_access(const char *who, int device) {
+    const hipError_t e = hipDeviceEnablePeerAccess(device, 0);
+    if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return bb::hip_status(who, e);
+    (void)hipGetLastError();
+    return BB_OK;
+}
+
+// A create that failed with rc: tear down what there is, the failure's text staying the last
+// error across the tear-down.
+template <typename TearDown>
+int failed_create(int rc, TearDown &&tear_down) {
+    const std::string keep = bb_last_error();
+    tear_down();
+    bb::set_error(keep);
+    return rc;
+}
+
+// The peer arena's layout: 2 parities x world slots of data | per-rank flags | poison words.
+int64_t peer_flags_offset(const bb_solver *s) {
+    return 2 * (int64_t)s->world * s->peer_slot_elems * bb::elem_size(s->dtype);
+}
+// the one-launch exchange (reduce_exchange_kernel): one poison word per source rank behind
+// the per-rank flags of the two-launch form (its data words say by themselves whether they
+// have arrived)
+int64_t peer_xpoison_offset(const bb_solver *s) {
+    return peer_flags_offset(s) + bb::round_up((int64_t)s->world * 64, 256);
+}
+int64_t peer_arena_size(const bb_solver *s) {
+    return peer_xpoison_offset(s) + bb::round_up((int64_t)s->world * 64, 256);
 }
 
 // Waves per CU (4 waves = one workgroup).  Measured on MI355X: with the rolling
@@ -340,15 +389,15 @@ int build_indices(bb_solver *s) {
         }
         size_t total = 0;
         for (auto &w : want) total += (w.second + 255) & ~(size_t)255;
-        BB_TRY(dev_alloc(&s->d_arena, (int64_t)total));
+        BB_TRY(bb::alloc_status(s->d_arena, total));
         size_t off = 0;
         for (auto &w : want) {
-            *w.first = s->d_arena + off;
+            *w.first = s->d_arena.as<char>() + off;
             off += (w.second + 255) & ~(size_t)255;
         }
     }
-    BB_TRY(dev_alloc((char **)&s->d_exch, (3 * s->L.n_pad + 2) * es));
-    s->own_exch = true;
+    BB_TRY(bb::alloc_status(s->own_exch, (size_t)((3 * s->L.n_pad + 2) * es)));
+    s->d_exch = s->own_exch.p;
 
     hipStream_t st = s->stream;
     BB_HIP_CHECK(hipMemcpyAsync(s->d_udesc, s->udesc.data(), s->udesc.size() * sizeof(int2),
@@ -458,15 +507,16 @@ int launch_exchange_t(LayoutTag<T, W>, bb_solver *s, double lr, double *stress_o
     const int64_t es = sizeof(T);
     const unsigned segs = 3 * Lay<T, W>::VW / kRedWG;
     const dim3 grid((unsigned)s->L.n_blocks, segs);
-    const PeerTableX<T> *xt = (const PeerTableX<T> *)s->d_peer_table_x + (s->peer_seq & 1);
-    const char *base = (const char *)s->peer_arena;
+    const PeerTableX<T> *xt = s->d_peer_table_x.as<const PeerTableX<T>>() + (s->peer_seq & 1);
+    const char *base = s->peer_arena.as<const char>();
     const T *arena = (const T *)(base + (int64_t)(s->peer_seq & 1) * s->world * s->peer_slot_elems * es);
     const unsigned long long *my_poison = (const unsigned long long *)(base + peer_xpoison_offset(s));
     return with_int<4, 8>(s->red_slices, [&](auto slices) -> int {
         constexpr int S = decltype(slices)::value;
         BB_HIP_CHECK(bb::launch(reduce_exchange_kernel<T, W, S>, grid, dim3(128 * S), 0, s->stream, p,
                                 (const int64_t *)s->d_red_lists, s->red_stride, xt, arena, my_poison,
-                                s->peer_slot_elems, s->d_peer_state, s->peer_limit_ticks));
+                                s->peer_slot_elems, s->d_peer_state.as<PeerState>(),
+                                s->peer_limit_ticks));
         return BB_OK;
     });
 }
@@ -486,13 +536,13 @@ void fill_reduce_params(bb_solver *s, ReduceParams<T> &p, int mode, double lr, d
     p.n_waves = s->n_waves;
     p.lr = s->sum_target ? T(-1) : (T)lr;
     p.peer = nullptr;
-    p.peer_counter = s->d_peer_counter;
-    p.peer_state = s->d_peer_state;
+    p.peer_counter = s->d_peer_counter.as<unsigned>();
+    p.peer_state = s->d_peer_state.as<PeerState>();
     p.seq = 0;
     p.n_peers = 0;
     if (mode == kReducePeer) {
         // the caller has bumped peer_seq: iteration k (1-based) uses parity k & 1
-        p.peer = (const PeerTable<T> *)s->d_peer_table + (s->peer_seq & 1);
+        p.peer = s->d_peer_table.as<const PeerTable<T>>() + (s->peer_seq & 1);
         p.seq = s->peer_seq;
         p.n_peers = s->world;
     }
@@ -500,11 +550,11 @@ void fill_reduce_params(bb_solver *s, ReduceParams<T> &p, int mode, double lr, d
     p.stress_slot = s->d_stress_slot;
     p.n_slots = s->n_slots;
     // (a plain sum -- the matvec, the spectral start's products -- is never scaled)
-    p.bin_scale = scale == kScalePlainSum ? nullptr : (const T *)s->d_bin_scale;
-    p.map_ptr = s->d_map_ptr;
-    p.map_idx = s->d_map_idx;
+    p.bin_scale = scale == kScalePlainSum ? nullptr : s->d_bin_scale.as<const T>();
+    p.map_ptr = s->d_map_ptr.as<int>();
+    p.map_idx = s->d_map_idx.as<int>();
     p.n_maps = s->n_maps;
-    p.peer_mask = s->d_peer_mask;
+    p.peer_mask = s->d_peer_mask.as<unsigned>();
     p.rank = s->rank;
 }
 
@@ -547,7 +597,7 @@ int launch_exchange(bb_solver *s, double lr, double *stress_out, double scale = 
 // every timing_stride-th iteration while timing is on: ev[0] sweep ev[1] reduce ev[2].
 template <typename Sweep, typename Reduce>
 int timed_step(bb_solver *s, Sweep &&sweep, Reduce &&reduce) {
-    hipEvent_t *ev = nullptr;
+    bb::Event *ev = nullptr;
     if (s->timing && s->timing_iter++ % s->timing_stride == 0 && s->ev_used + 3 <= s->ev.size()) {
         ev = &s->ev[s->ev_used];
         s->ev_used += 3;
@@ -604,8 +654,9 @@ int set_wish_dense_t(LayoutTag<T, W>, bb_solver *s, const double *host, int64_t 
     constexpr int VW = Lay<T, W>::VW;
     const int64_t upt = s->L.units_per_tile, n = off + n_sub;
     constexpr int64_t kRunTiles = 4;  // tiles staged per copy
-    double *stage = nullptr;
-    BB_TRY(dev_alloc(&stage, kRunTiles * VW * VW));
+    bb::DevBuf stage_buf;
+    BB_TRY(bb::alloc_status(stage_buf, (size_t)(kRunTiles * VW * VW) * sizeof(double)));
+    double *stage = stage_buf.as<double>();
     // Copy, convert and the next copy are all enqueued on the solver's stream,
     // so one staging buffer is enough and nothing depends on null-stream rules.
     int rc = BB_OK;
@@ -643,7 +694,6 @@ int set_wish_dense_t(LayoutTag<T, W>, bb_solver *s, const double *host, int64_t 
     hipError_t e = hipStreamSynchronize(s->stream);
     if (rc == BB_OK && e != hipSuccess)
         rc = bb::hip_status("set_wish_dense", e);
-    hipFree(stage);
     return rc;
 }
 
@@ -656,8 +706,8 @@ int upload_bin_scale(bb_solver *s, const double *padded) {
         else ((double *)host.data())[i] = padded[i];
     }
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-    if (!s->d_bin_scale) BB_TRY(dev_alloc((char **)&s->d_bin_scale, n * es));
-    BB_HIP_CHECK(hipMemcpy(s->d_bin_scale, host.data(), host.size(), hipMemcpyHostToDevice));
+    if (!s->d_bin_scale) BB_TRY(bb::alloc_status(s->d_bin_scale, (size_t)(n * es)));
+    BB_HIP_CHECK(hipMemcpy(s->d_bin_scale.p, host.data(), host.size(), hipMemcpyHostToDevice));
     return BB_OK;
 }
 
@@ -697,7 +747,7 @@ int launch_row_owner(bb_solver *s, double lr, bool fold_prev, bool update) {
                                         dim3(grid), dim3(256), 0, s->stream, (const T *)s->d_full,
                                         s->full_ld, (int)s->L.n_bins, (const T *)s->d_X, (T *)s->d_X2,
                                         (T *)s->d_V, (T)lr, (T)s->momentum, prev, s->ro_blocks, hist_prev,
-                                        out, (const T *)s->d_bin_scale));
+                                        out, s->d_bin_scale.as<const T>()));
                 return BB_OK;
             });
         });
@@ -814,19 +864,6 @@ static_assert(offsetof(PeerTable<float>, flag) == kMaxPeers * sizeof(void *) &&
               "peer_receive_kernel takes the flag pointers as the second half of a PeerTable");
 constexpr uint64_t kPeerMagic = 0x6262706565723031ull;  // "bbpeer01"
 
-int64_t peer_flags_offset(const bb_solver *s) {
-    return 2 * (int64_t)s->world * s->peer_slot_elems * bb::elem_size(s->dtype);
-}
-// the one-launch exchange (reduce_exchange_kernel): one poison word per source rank behind
-// the per-rank flags of the two-launch form (its data words say by themselves whether they
-// have arrived)
-int64_t peer_xpoison_offset(const bb_solver *s) {
-    return peer_flags_offset(s) + bb::round_up((int64_t)s->world * 64, 256);
-}
-int64_t peer_arena_size(const bb_solver *s) {
-    return peer_xpoison_offset(s) + bb::round_up((int64_t)s->world * 64, 256);
-}
-
 // Block b -> bit q set when rank q of `world` holds a unit of a tile in block row or column b:
 // the ranks whose partial for b is not zero by construction.  Every rank derives it alike from
 // the tile list and the partition; the peer exchange and a group's group_apply_kernel both
@@ -857,8 +894,8 @@ int build_peer_tables(TypeTag<T>, bb_solver *s) {
             tab[par].dst[q] = (T *)base + ((int64_t)par * s->world + s->rank) * s->peer_slot_elems;
             tab[par].flag[q] = (unsigned long long *)(base + foff) + 8 * s->rank;
         }
-    BB_TRY(dev_alloc((char **)&s->d_peer_table, (int64_t)sizeof(tab)));
-    BB_HIP_CHECK(hipMemcpy(s->d_peer_table, tab, sizeof(tab), hipMemcpyHostToDevice));
+    BB_TRY(bb::alloc_status(s->d_peer_table, sizeof(tab)));
+    BB_HIP_CHECK(hipMemcpy(s->d_peer_table.p, tab, sizeof(tab), hipMemcpyHostToDevice));
     PeerTableX<T> tx[2];
     memset(tx, 0, sizeof(tx));
     for (int par = 0; par < 2; ++par)
@@ -867,8 +904,8 @@ int build_peer_tables(TypeTag<T>, bb_solver *s) {
             tx[par].dst[q] = tab[par].dst[q];
             tx[par].poison[q] = (unsigned long long *)(base + peer_xpoison_offset(s)) + 8 * s->rank;
         }
-    BB_TRY(dev_alloc((char **)&s->d_peer_table_x, (int64_t)sizeof(tx)));
-    BB_HIP_CHECK(hipMemcpy(s->d_peer_table_x, tx, sizeof(tx), hipMemcpyHostToDevice));
+    BB_TRY(bb::alloc_status(s->d_peer_table_x, sizeof(tx)));
+    BB_HIP_CHECK(hipMemcpy(s->d_peer_table_x.p, tx, sizeof(tx), hipMemcpyHostToDevice));
     return BB_OK;
 }
 
@@ -935,12 +972,7 @@ int bb_solver_create(bb_solver **out, int64_t n_bins, int dtype, int device, int
             s->own_stream = true;
     }
     if (rc == BB_OK) rc = build_indices(s);
-    if (rc != BB_OK) {
-        std::string keep = bb_last_error();
-        bb_solver_destroy(s);
-        bb::set_error(keep);
-        return rc;
-    }
+    if (rc != BB_OK) return failed_create(rc, [&] { bb_solver_destroy(s); });
     *out = s;
     return BB_OK;
 }
@@ -960,24 +992,12 @@ int bb_solver_destroy(bb_solver *s) {
         }
     }
     for (void *m : s->peer_opened) hipIpcCloseMemHandle(m);
-    hipFree(s->peer_arena);
-    hipFree(s->d_peer_table);
-    hipFree(s->d_peer_table_x);
-    hipFree(s->d_peer_state);
-    hipFree(s->d_peer_counter);
-    hipFree(s->d_peer_mask);
-    for (hipEvent_t e : s->ev) hipEventDestroy(e);
-    hipFree(s->d_arena);
-    hipFree(s->d_bin_scale);
-    hipFree(s->d_map_ptr);
-    hipFree(s->d_map_idx);
-    hipFree(s->d_map_scalar);
-    if (s->own_exch) hipFree(s->d_exch);
-    hipFree(s->d_mv_in);
-    // (a stream abandoned behind a hung collective is not returned to the pool: the pool
-    // synchronises what it takes back)
-    if (s->own_stream && s->stream && !s->stream_stuck) bb::release_stream(s->device, s->stream);
+    // buffers and events go with the handle, the stream back to the pool after them (one
+    // abandoned behind a hung collective does not: the pool synchronises what it takes back)
+    const int device = s->device;
+    hipStream_t pooled = s->own_stream && !s->stream_stuck ? s->stream : nullptr;
     delete s;
+    if (pooled) bb::release_stream(device, pooled);
     // tear-down is best effort (a free can fail when a peer process has already gone
     // away): whatever it left in the thread's error word is consumed here
     (void)hipGetLastError();
@@ -1006,9 +1026,7 @@ int bb_solver_set_wish_dense(bb_solver *s, const double *host, int64_t ld, int k
                              double alpha) {
     BB_REQUIRE(s != nullptr && host != nullptr, "bb_solver_set_wish_dense: NULL argument");
     BB_REQUIRE(ld >= s->L.n_bins, "bb_solver_set_wish_dense: ld < n_bins");
-    BB_REQUIRE(kind == BB_KIND_WISH || kind == BB_KIND_COUNTS,
-               "bb_solver_set_wish_dense: bad kind");
-    BB_REQUIRE(kind == BB_KIND_WISH || alpha > 0.0, "bb_solver_set_wish_dense: alpha must be > 0");
+    BB_TRY(check_kind_alpha("bb_solver_set_wish_dense", kind, alpha));
     return set_wish_dense(s, host, ld, kind, alpha, 0, s->L.n_bins);
 }
 
@@ -1050,17 +1068,16 @@ int bb_solver_set_maps(bb_solver *s, int n_maps, const int64_t *bin_begin, const
         ptr.push_back((int)idx.size());
     }
     if (idx.empty()) idx.push_back(0);
-    hipFree(s->d_bin_scale); hipFree(s->d_map_ptr); hipFree(s->d_map_idx); hipFree(s->d_map_scalar);
-    s->d_bin_scale = nullptr; s->d_map_ptr = s->d_map_idx = nullptr; s->d_map_scalar = nullptr;
+    s->d_bin_scale.reset(); s->d_map_ptr.reset(); s->d_map_idx.reset(); s->d_map_scalar.reset();
     s->bin_steps = false;          // (the maps' steps replace a bb_solver_set_bin_steps)
     s->n_maps = 1;                 // (what holds if an allocation below fails: one map, no tables)
     s->map_begin.clear();
     BB_TRY(upload_bin_scale(s, scale.data()));
-    BB_TRY(dev_alloc(&s->d_map_ptr, (int64_t)ptr.size()));
-    BB_TRY(dev_alloc(&s->d_map_idx, (int64_t)idx.size()));
-    BB_TRY(dev_alloc(&s->d_map_scalar, n_maps));
-    BB_HIP_CHECK(hipMemcpy(s->d_map_ptr, ptr.data(), ptr.size() * sizeof(int), hipMemcpyHostToDevice));
-    BB_HIP_CHECK(hipMemcpy(s->d_map_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
+    BB_TRY(bb::alloc_status(s->d_map_ptr, ptr.size() * sizeof(int)));
+    BB_TRY(bb::alloc_status(s->d_map_idx, idx.size() * sizeof(int)));
+    BB_TRY(bb::alloc_status(s->d_map_scalar, (size_t)n_maps * sizeof(double)));
+    BB_HIP_CHECK(hipMemcpy(s->d_map_ptr.p, ptr.data(), ptr.size() * sizeof(int), hipMemcpyHostToDevice));
+    BB_HIP_CHECK(hipMemcpy(s->d_map_idx.p, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
     // (a map that is never set carries no constraint)
     BB_HIP_CHECK(hipMemsetAsync(s->d_units, 0, (size_t)std::max<int64_t>(s->n_local, 1) * bb::kUnitBytes,
                                 s->stream));
@@ -1082,8 +1099,7 @@ int bb_solver_set_bin_steps(bb_solver *s, const double *scale, int64_t n_bins) {
     BB_TRY(bb::enter_device(s->device));
     if (scale == nullptr) {                       // back to one step for all
         BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-        hipFree(s->d_bin_scale);
-        s->d_bin_scale = nullptr;
+        s->d_bin_scale.reset();
         s->bin_steps = false;
         return BB_OK;
     }
@@ -1174,9 +1190,7 @@ int bb_solver_weight_sums(bb_solver *s, double *sums, int64_t n_bins) {
 int bb_solver_set_wish_from_cm_block(bb_solver *s, const bb_cm *cm, int64_t bin_offset, int kind,
                                      double alpha) {
     BB_REQUIRE(s != nullptr && cm != nullptr, "bb_solver_set_wish_from_cm_block: NULL argument");
-    BB_REQUIRE(kind == BB_KIND_WISH || kind == BB_KIND_COUNTS,
-               "bb_solver_set_wish_from_cm_block: bad kind");
-    BB_REQUIRE(kind == BB_KIND_WISH || alpha > 0.0, "bb_solver_set_wish_from_cm_block: alpha must be > 0");
+    BB_TRY(check_kind_alpha("bb_solver_set_wish_from_cm_block", kind, alpha));
     const double *m = nullptr;
     int64_t d = 0;
     int dev = -1;
@@ -1195,9 +1209,7 @@ int bb_solver_set_wish_dense_block(bb_solver *s, const double *host, int64_t ld,
                "bb_solver_set_wish_dense_block: the block does not fit the solver");
     BB_REQUIRE(bin_offset % s->L.vw == 0,
                "bb_solver_set_wish_dense_block: a block starts at a multiple of the tile edge");
-    BB_REQUIRE(kind == BB_KIND_WISH || kind == BB_KIND_COUNTS,
-               "bb_solver_set_wish_dense_block: bad kind");
-    BB_REQUIRE(kind == BB_KIND_WISH || alpha > 0.0, "bb_solver_set_wish_dense_block: alpha must be > 0");
+    BB_TRY(check_kind_alpha("bb_solver_set_wish_dense_block", kind, alpha));
     return set_wish_dense(s, host, ld, kind, alpha, bin_offset, n_sub);
 }
 
@@ -1206,9 +1218,7 @@ int bb_solver_set_wish_from_cm(bb_solver *s, const bb_cm *cm, int kind, double a
     if (s->n_maps > 1)
         return bb::fail(BB_ERR_STATE, "bb_solver_set_wish_from_cm: a solver of several maps takes "
                                       "them one by one (bb_solver_set_wish_from_cm_block)");
-    BB_REQUIRE(kind == BB_KIND_WISH || kind == BB_KIND_COUNTS,
-               "bb_solver_set_wish_from_cm: bad kind");
-    BB_REQUIRE(kind == BB_KIND_WISH || alpha > 0.0, "bb_solver_set_wish_from_cm: alpha must be > 0");
+    BB_TRY(check_kind_alpha("bb_solver_set_wish_from_cm", kind, alpha));
     const double *m = nullptr;
     int64_t d = 0;
     int dev = -1;
@@ -1228,11 +1238,7 @@ int bb_solver_set_wish_from_cm(bb_solver *s, const bb_cm *cm, int kind, double a
         BB_TRY(bb::enter_device(dev));
         BB_HIP_CHECK(hipDeviceSynchronize());          // the map's last operation has landed
         BB_TRY(bb::enter_device(s->device));
-        hipError_t e = hipDeviceEnablePeerAccess(dev, 0);
-        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled)
-            return bb::fail(BB_ERR_HIP, std::string("bb_solver_set_wish_from_cm: peer access: ") +
-                                            hipGetErrorString(e));
-        (void)hipGetLastError();
+        BB_TRY(enable_peer_access("bb_solver_set_wish_from_cm: peer access", dev));
     }
     return pack_from_cm(s, m, d, 0, kind, alpha);
 }
@@ -1243,8 +1249,7 @@ int bb_solver_set_wish_sparse(bb_solver *s, const int64_t *rows, const int64_t *
     BB_REQUIRE(s != nullptr, "bb_solver_set_wish_sparse: solver is NULL");
     BB_REQUIRE(nnz >= 0 && (nnz == 0 || (rows && cols && vals)),
                "bb_solver_set_wish_sparse: NULL entries");
-    BB_REQUIRE(kind == BB_KIND_WISH || kind == BB_KIND_COUNTS, "bb_solver_set_wish_sparse: bad kind");
-    BB_REQUIRE(kind == BB_KIND_WISH || alpha > 0.0, "bb_solver_set_wish_sparse: alpha must be > 0");
+    BB_TRY(check_kind_alpha("bb_solver_set_wish_sparse", kind, alpha));
     BB_REQUIRE((KRnorm == nullptr) == (KRexpected == nullptr),
                "bb_solver_set_wish_sparse: KRnorm and KRexpected go together");
     BB_TRY(bb::enter_device(s->device));
@@ -1272,7 +1277,8 @@ struct bb_triples {
     int device = 0;
     int64_t n = 0, st = 3, sc = 1;      // element (t, c) at d[t * st + c * sc]
     double resolution = 1.0;
-    double *d = nullptr;
+    bb::DevBuf d;                       // 3 n doubles
+    const double *from(int64_t t0) const { return d.as<double>() + t0 * (st == 3 ? 3 : 1); }
 };
 
 int bb_triples_create(bb_triples **out, const double *triples, int64_t n, int32_t resolution,
@@ -1288,14 +1294,11 @@ int bb_triples_create(bb_triples **out, const double *triples, int64_t n, int32_
     t->n = n;
     t->resolution = (double)resolution;
     if (row_major) { t->st = 3; t->sc = 1; } else { t->st = 1; t->sc = n; }
-    int rc = dev_alloc(&t->d, 3 * n);
-    if (rc == BB_OK && n > 0) {
-        const hipError_t e = hipMemcpy(t->d, triples, (size_t)n * 24, hipMemcpyHostToDevice);
-        if (e != hipSuccess)
-            rc = bb::hip_status("bb_triples_create", e);
-    }
+    int rc = bb::alloc_status(t->d, (size_t)(3 * n) * sizeof(double));
+    if (rc == BB_OK && n > 0)
+        rc = bb::hip_status("bb_triples_create",
+                            hipMemcpy(t->d.p, triples, (size_t)n * 24, hipMemcpyHostToDevice));
     if (rc != BB_OK) {
-        hipFree(t->d);
         delete t;
         return rc;
     }
@@ -1306,7 +1309,6 @@ int bb_triples_create(bb_triples **out, const double *triples, int64_t n, int32_
 int bb_triples_destroy(bb_triples *t) {
     if (!t) return BB_OK;
     hipSetDevice(t->device);
-    hipFree(t->d);
     delete t;
     (void)hipGetLastError();
     return BB_OK;
@@ -1328,8 +1330,7 @@ int bb_triples_tiles(const bb_triples *t, int64_t n_bins, int dtype, uint8_t *pr
     constexpr int64_t kChunk = (int64_t)1 << 30;
     for (int64_t k0 = 0; k0 < t->n; k0 += kChunk) {
         const int64_t m = std::min(kChunk, t->n - k0);
-        const EntrySrc src = {nullptr, nullptr, nullptr, t->d + k0 * (t->st == 3 ? 3 : 1), t->st, t->sc,
-                              t->resolution};
+        const EntrySrc src = {nullptr, nullptr, nullptr, t->from(k0), t->st, t->sc, t->resolution};
         BB_HIP_CHECK(bb::launch(entries_tiles_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0,
                                 (hipStream_t) nullptr, src, m, L.vw, n_blocks, n_bins,
                                 (unsigned char *)bp.p, (int *)bb_.p));
@@ -1344,8 +1345,7 @@ int bb_triples_tiles(const bb_triples *t, int64_t n_bins, int dtype, uint8_t *pr
 int bb_solver_set_wish_triples(bb_solver *s, const bb_triples *t, int kind, double alpha,
                                const double *KRnorm, const double *KRexpected) {
     BB_REQUIRE(s != nullptr && t != nullptr, "bb_solver_set_wish_triples: NULL argument");
-    BB_REQUIRE(kind == BB_KIND_WISH || kind == BB_KIND_COUNTS, "bb_solver_set_wish_triples: bad kind");
-    BB_REQUIRE(kind == BB_KIND_WISH || alpha > 0.0, "bb_solver_set_wish_triples: alpha must be > 0");
+    BB_TRY(check_kind_alpha("bb_solver_set_wish_triples", kind, alpha));
     BB_REQUIRE((KRnorm == nullptr) == (KRexpected == nullptr),
                "bb_solver_set_wish_triples: KRnorm and KRexpected go together");
     BB_REQUIRE(t->device == s->device,
@@ -1356,7 +1356,7 @@ int bb_solver_set_wish_triples(bb_solver *s, const bb_triples *t, int kind, doub
     constexpr int64_t kChunk = (int64_t)1 << 30;
     return scatter_entries(s, "bb_solver_set_wish_triples", t->n, kChunk, kind, alpha, KRnorm, KRexpected,
                            [&](int64_t k0, int64_t, EntrySrc *src) {
-        *src = {nullptr, nullptr, nullptr, t->d + k0 * (t->st == 3 ? 3 : 1), t->st, t->sc, t->resolution};
+        *src = {nullptr, nullptr, nullptr, t->from(k0), t->st, t->sc, t->resolution};
         return hipSuccess;
     });
 }
@@ -1364,9 +1364,7 @@ int bb_solver_set_wish_triples(bb_solver *s, const bb_triples *t, int kind, doub
 int bb_solver_set_wish_from_coords(bb_solver *s, const double *xstar) {
     BB_REQUIRE(s != nullptr && xstar != nullptr, "bb_solver_set_wish_from_coords: NULL argument");
     BB_TRY(bb::enter_device(s->device));
-    BB_HIP_CHECK(hipMemsetAsync(s->d_f64_tmp, 0, (size_t)s->L.n_pad * 3 * sizeof(double), s->stream));
-    BB_HIP_CHECK(hipMemcpyAsync(s->d_f64_tmp, xstar, (size_t)s->L.n_bins * 3 * sizeof(double),
-                                hipMemcpyHostToDevice, s->stream));
+    BB_HIP_CHECK(upload_padded(s, s->d_f64_tmp, xstar, s->stream));
     if (s->n_local > 0)
         BB_TRY(by_layout(s, [&](auto lay) -> int {
             using T = typename decltype(lay)::T;
@@ -1382,9 +1380,7 @@ int bb_solver_set_coords(bb_solver *s, const double *xyz) {
     BB_REQUIRE(s != nullptr && xyz != nullptr, "bb_solver_set_coords: NULL argument");
     BB_TRY(bb::enter_device(s->device));
     const int64_t n3 = s->L.n_pad * 3;
-    BB_HIP_CHECK(hipMemsetAsync(s->d_f64_tmp, 0, (size_t)n3 * sizeof(double), s->stream));
-    BB_HIP_CHECK(hipMemcpyAsync(s->d_f64_tmp, xyz, (size_t)s->L.n_bins * 3 * sizeof(double),
-                                hipMemcpyHostToDevice, s->stream));
+    BB_HIP_CHECK(upload_padded(s, s->d_f64_tmp, xyz, s->stream));
     BB_HIP_CHECK(narrow(s, s->d_f64_tmp, s->d_X, n3));
     BB_HIP_CHECK(hipMemsetAsync(s->d_V, 0, (size_t)n3 * bb::elem_size(s->dtype), s->stream));
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));
@@ -1508,6 +1504,13 @@ uint64_t comm_generation_of(const void *unique_id) {
 std::mutex g_comm_mu;
 std::map<std::tuple<int, int, int>, CachedComm> g_comm_cache;
 
+// The cache's entry of (device, rank, world) if it is there, holds a communicator and is
+// free, else NULL.  The caller holds g_comm_mu.
+CachedComm *cached_comm(int device, int rank, int world) {
+    auto it = g_comm_cache.find(std::make_tuple(device, rank, world));
+    return it != g_comm_cache.end() && it->second.comm && !it->second.in_use ? &it->second : nullptr;
+}
+
 void comm_release(bb_solver *s, bool destroy) {
     if (!s->comm) return;
     std::lock_guard<std::mutex> lock(g_comm_mu);
@@ -1531,30 +1534,26 @@ int bb_comm_cached_generation(int device, int rank, int world, int *available,
     BB_REQUIRE(available != nullptr && generation != nullptr,
                "bb_comm_cached_generation: NULL argument");
     std::lock_guard<std::mutex> lock(g_comm_mu);
-    auto it = g_comm_cache.find(std::make_tuple(device, rank, world));
-    const bool have = it != g_comm_cache.end() && it->second.comm && !it->second.in_use;
-    *available = have ? 1 : 0;
-    *generation = have ? it->second.generation : 0;
+    const CachedComm *c = cached_comm(device, rank, world);
+    *available = c ? 1 : 0;
+    *generation = c ? c->generation : 0;
     return BB_OK;
 }
 
 int bb_comm_cached(int device, int rank, int world, int *available) {
     BB_REQUIRE(available != nullptr, "bb_comm_cached: available is NULL");
-    std::lock_guard<std::mutex> lock(g_comm_mu);
-    auto it = g_comm_cache.find(std::make_tuple(device, rank, world));
-    *available = (it != g_comm_cache.end() && it->second.comm && !it->second.in_use) ? 1 : 0;
-    return BB_OK;
+    uint64_t generation = 0;
+    return bb_comm_cached_generation(device, rank, world, available, &generation);
 }
 
 int bb_solver_comm_attach(bb_solver *s) {
     BB_REQUIRE(s != nullptr, "bb_solver_comm_attach: solver is NULL");
     if (s->comm) return bb::fail(BB_ERR_STATE, "bb_solver_comm_attach: communicator already made");
     std::lock_guard<std::mutex> lock(g_comm_mu);
-    auto it = g_comm_cache.find(std::make_tuple(s->device, s->rank, s->world));
-    if (it == g_comm_cache.end() || !it->second.comm || it->second.in_use)
-        return bb::fail(BB_ERR_STATE, "bb_solver_comm_attach: no free cached communicator");
-    it->second.in_use = true;
-    s->comm = it->second.comm;
+    CachedComm *c = cached_comm(s->device, s->rank, s->world);
+    if (!c) return bb::fail(BB_ERR_STATE, "bb_solver_comm_attach: no free cached communicator");
+    c->in_use = true;
+    s->comm = c->comm;
     s->comm_cached = true;
     return BB_OK;
 }
@@ -1689,19 +1688,19 @@ int launch_peer_receive(bb_solver *s, void *X, double lr, double mu, double *str
     // divided among them; a thread then takes more elements.
     const int64_t cap = std::max<int64_t>(8, (int64_t)kPeerReceiveWGs / (s->peer_ranks_on_gpu > 2 ? s->peer_ranks_on_gpu / 2 : 1));
     const unsigned grid = (unsigned)std::min<int64_t>((n3 + 255) / 256, cap);
-    const char *arena = (const char *)s->peer_arena +
+    const char *arena = s->peer_arena.as<const char>() +
                         (int64_t)(s->peer_seq & 1) * s->world * s->peer_slot_elems * es;
     const unsigned long long *flags =
-        (const unsigned long long *)((const char *)s->peer_arena + peer_flags_offset(s));
+        (const unsigned long long *)(s->peer_arena.as<const char>() + peer_flags_offset(s));
     // the flag pointers are the second half of a PeerTable (same for both parities)
     unsigned long long *const *poison =
-        (unsigned long long *const *)((const char *)s->d_peer_table + kMaxPeers * sizeof(void *));
+        (unsigned long long *const *)(s->d_peer_table.as<const char>() + kMaxPeers * sizeof(void *));
     return by_dtype(s, [&](auto t) -> int {
         using T = typename decltype(t)::T;
         BB_HIP_CHECK(bb::launch(peer_receive_kernel<T>, dim3(grid), dim3(256), 0, s->stream, (T *)X,
                                 (T *)s->d_V, (const T *)arena, flags, poison, s->world, s->peer_slot_elems,
-                                n3, (T)lr, (T)mu, stress_out, s->peer_seq, s->d_peer_state,
-                                s->peer_limit_ticks, (const unsigned *)s->d_peer_mask, (int)(3 * s->L.vw)));
+                                n3, (T)lr, (T)mu, stress_out, s->peer_seq, s->d_peer_state.as<PeerState>(),
+                                s->peer_limit_ticks, s->d_peer_mask.as<const unsigned>(), (int)(3 * s->L.vw)));
         return BB_OK;
     });
 }
@@ -1750,30 +1749,28 @@ int bb_solver_peer_export(bb_solver *s, void *handle_out) {
     s->peer_arena_bytes = peer_arena_size(s);
     // Uncached: written by the peers' kernels while ours is running, so nothing of
     // it may live in this GPU's L2.  (RCCL allocates its own buffers the same way.)
-    hipError_t e = hipExtMallocWithFlags(&s->peer_arena, (size_t)s->peer_arena_bytes,
-                                         hipDeviceMallocUncached);
+    void *arena = nullptr;
+    hipError_t e = hipExtMallocWithFlags(&arena, (size_t)s->peer_arena_bytes, hipDeviceMallocUncached);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        e = hipExtMallocWithFlags(&s->peer_arena, (size_t)s->peer_arena_bytes,
-                                  hipDeviceMallocFinegrained);
+        e = hipExtMallocWithFlags(&arena, (size_t)s->peer_arena_bytes, hipDeviceMallocFinegrained);
     }
     if (e != hipSuccess) {
-        s->peer_arena = nullptr;
         return bb::fail(BB_ERR_NOMEM, std::string("bb_solver_peer_export: arena: ") +
                                           hipGetErrorString(e));
     }
     // every data word starts out EMPTY (all bits set: reduce_exchange_kernel), flags and poison
     // words at 0
-    BB_HIP_CHECK(hipMemset(s->peer_arena, 0xff, (size_t)peer_flags_offset(s)));
-    BB_HIP_CHECK(hipMemset((char *)s->peer_arena + peer_flags_offset(s), 0,
+    s->peer_arena.adopt(arena, (size_t)s->peer_arena_bytes);
+    BB_HIP_CHECK(hipMemset(s->peer_arena.p, 0xff, (size_t)peer_flags_offset(s)));
+    BB_HIP_CHECK(hipMemset(s->peer_arena.as<char>() + peer_flags_offset(s), 0,
                            (size_t)(s->peer_arena_bytes - peer_flags_offset(s))));
     BB_HIP_CHECK(hipDeviceSynchronize());
     PeerHandle h;
     memset(&h, 0, sizeof(h));
-    e = hipIpcGetMemHandle(&h.ipc, s->peer_arena);
+    e = hipIpcGetMemHandle(&h.ipc, s->peer_arena.p);
     if (e != hipSuccess) {
-        hipFree(s->peer_arena);
-        s->peer_arena = nullptr;
+        s->peer_arena.reset();
         return bb::fail(BB_ERR_HIP, std::string("bb_solver_peer_export: hipIpcGetMemHandle: ") +
                                         hipGetErrorString(e));
     }
@@ -1781,7 +1778,7 @@ int bb_solver_peer_export(bb_solver *s, void *handle_out) {
     h.arena_bytes = s->peer_arena_bytes;
     h.slot_elems = s->peer_slot_elems;
     h.pid = (int64_t)getpid();
-    h.raw = (uint64_t)(uintptr_t)s->peer_arena;
+    h.raw = (uint64_t)(uintptr_t)s->peer_arena.p;
     h.rank = s->rank;
     h.world = s->world;
     h.dtype = s->dtype;
@@ -1819,17 +1816,12 @@ int bb_solver_peer_connect(bb_solver *s, const void *handles) {
                                                 " does not match this solver (rank order, world, "
                                                 "dtype and n_bins must agree)");
         if (r == s->rank) {
-            s->peer_mapped[r] = s->peer_arena;
+            s->peer_mapped[r] = s->peer_arena.p;
         } else if (h.pid == (int64_t)getpid()) {
             // same process: the exporter's pointer is valid here, but only from the
             // same device or with peer access
-            if (h.device != s->device) {
-                hipError_t pe = hipDeviceEnablePeerAccess(h.device, 0);
-                if (pe != hipSuccess && pe != hipErrorPeerAccessAlreadyEnabled)
-                    return bb::fail(BB_ERR_HIP, std::string("bb_solver_peer_connect: peer access: ") +
-                                                    hipGetErrorString(pe));
-                (void)hipGetLastError();
-            }
+            if (h.device != s->device)
+                BB_TRY(enable_peer_access("bb_solver_peer_connect: peer access", h.device));
             s->peer_mapped[r] = (void *)(uintptr_t)h.raw;
         } else {
             void *ptr = nullptr;
@@ -1850,23 +1842,22 @@ int bb_solver_peer_connect(bb_solver *s, const void *handles) {
         // a third of the blocks (28 % fewer bytes on the links over all ranks); the whole genome
         // as blocks: a rank touches the blocks of a few chromosomes (BB_PEER_MASK=0: all send all).
         const char *env = getenv("BB_PEER_MASK");
-        hipFree(s->d_peer_mask);
-        s->d_peer_mask = nullptr;
+        s->d_peer_mask.reset();
         if (!(env && atoi(env) == 0) && s->world <= 32) {
             std::vector<unsigned> mask;
             BB_TRY(contributor_mask(s, &mask));
-            BB_TRY(dev_alloc(&s->d_peer_mask, s->L.n_blocks));
-            BB_HIP_CHECK(hipMemcpy(s->d_peer_mask, mask.data(), mask.size() * sizeof(unsigned),
+            BB_TRY(bb::alloc_status(s->d_peer_mask, mask.size() * sizeof(unsigned)));
+            BB_HIP_CHECK(hipMemcpy(s->d_peer_mask.p, mask.data(), mask.size() * sizeof(unsigned),
                                    hipMemcpyHostToDevice));
         }
     }
-    BB_TRY(dev_alloc(&s->d_peer_state, 1));
+    BB_TRY(bb::alloc_status(s->d_peer_state, sizeof(PeerState)));
     // the top counter + one per block on a line of its own (reduce_sliced_kernel's two-level
     // check-in)
     const int64_t n_counters = 32 * (s->L.n_blocks + 1);
-    BB_TRY(dev_alloc(&s->d_peer_counter, n_counters));
-    BB_HIP_CHECK(hipMemset(s->d_peer_state, 0, sizeof(PeerState)));
-    BB_HIP_CHECK(hipMemset(s->d_peer_counter, 0, (size_t)n_counters * sizeof(unsigned)));
+    BB_TRY(bb::alloc_status(s->d_peer_counter, (size_t)n_counters * sizeof(unsigned)));
+    BB_HIP_CHECK(hipMemset(s->d_peer_state.p, 0, sizeof(PeerState)));
+    BB_HIP_CHECK(hipMemset(s->d_peer_counter.p, 0, (size_t)n_counters * sizeof(unsigned)));
     // ticks of wall_clock64(): ask the runtime, fall back to gfx9's 100 MHz.  The query
     // is allowed to fail (older runtimes); its error is consumed here, on the spot.
     int khz = 0;
@@ -1937,7 +1928,7 @@ int bb_solver_peer_status(bb_solver *s, int *status) {
     PeerState st;
     memset(&st, 0, sizeof(st));
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-    BB_HIP_CHECK(hipMemcpy(&st, s->d_peer_state, sizeof(st), hipMemcpyDeviceToHost));
+    BB_HIP_CHECK(hipMemcpy(&st, s->d_peer_state.p, sizeof(st), hipMemcpyDeviceToHost));
     if (status) *status = st.status;
     if (st.status != 0) {
         const bool one = s->peer_fused;
@@ -1996,9 +1987,8 @@ int bb_solver_set_exchange_buffer(bb_solver *s, void *dev_ptr) {
     BB_REQUIRE(s != nullptr && dev_ptr != nullptr, "bb_solver_set_exchange_buffer: NULL argument");
     BB_TRY(bb::enter_device(s->device));
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-    if (s->own_exch) hipFree(s->d_exch);
+    s->own_exch.reset();
     s->d_exch = dev_ptr;
-    s->own_exch = false;
     return BB_OK;
 }
 
@@ -2006,13 +1996,13 @@ int bb_solver_read_exchange(bb_solver *s, double *host, int64_t n) {
     BB_REQUIRE(s != nullptr && host != nullptr, "bb_solver_read_exchange: NULL argument");
     BB_REQUIRE(n == 3 * s->L.n_pad + 2, "bb_solver_read_exchange: n != exchange size");
     BB_TRY(bb::enter_device(s->device));
-    double *tmp = nullptr;
-    BB_TRY(dev_alloc(&tmp, n));
+    bb::DevBuf buf;
+    BB_TRY(bb::alloc_status(buf, (size_t)n * sizeof(double)));
+    double *tmp = buf.as<double>();
     hipError_t e = widen(s, s->d_exch, tmp, n);
     if (e == hipSuccess)
         e = hipMemcpyAsync(host, tmp, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    hipFree(tmp);
     return bb::hip_status("bb_solver_read_exchange", e);
 }
 
@@ -2020,13 +2010,13 @@ int bb_solver_write_exchange(bb_solver *s, const double *host, int64_t n) {
     BB_REQUIRE(s != nullptr && host != nullptr, "bb_solver_write_exchange: NULL argument");
     BB_REQUIRE(n == 3 * s->L.n_pad + 2, "bb_solver_write_exchange: n != exchange size");
     BB_TRY(bb::enter_device(s->device));
-    double *tmp = nullptr;
-    BB_TRY(dev_alloc(&tmp, n));
+    bb::DevBuf buf;
+    BB_TRY(bb::alloc_status(buf, (size_t)n * sizeof(double)));
+    double *tmp = buf.as<double>();
     hipError_t e = hipMemcpyAsync(tmp, host, (size_t)n * sizeof(double), hipMemcpyHostToDevice,
                                   s->stream);
     if (e == hipSuccess) e = narrow(s, tmp, s->d_exch, n);
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    hipFree(tmp);
     return bb::hip_status("bb_solver_write_exchange", e);
 }
 
@@ -2040,11 +2030,9 @@ int bb_solver_matvec_sq(bb_solver *s, const double *x, double *y) {
     BB_TRY(bb::enter_device(s->device));
     const int64_t n3 = s->L.n_pad * 3, es = bb::elem_size(s->dtype);
     // (a spectral start calls this ~40 times: the buffer is allocated once and kept)
-    if (!s->d_mv_in) BB_TRY(dev_alloc((char **)&s->d_mv_in, n3 * es));
-    void *d_in = s->d_mv_in;
-    hipError_t e = hipMemsetAsync(s->d_f64_tmp, 0, (size_t)n3 * 8, s->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(s->d_f64_tmp, x, (size_t)s->L.n_bins * 24, hipMemcpyHostToDevice, s->stream);
+    if (!s->d_mv_in) BB_TRY(bb::alloc_status(s->d_mv_in, (size_t)(n3 * es)));
+    void *d_in = s->d_mv_in.p;
+    hipError_t e = upload_padded(s, s->d_f64_tmp, x, s->stream);
     if (e == hipSuccess) e = narrow(s, s->d_f64_tmp, d_in, n3);
     int rc = BB_OK;
     if (e != hipSuccess) rc = bb::hip_status("bb_solver_matvec_sq", e);
@@ -2067,21 +2055,11 @@ int bb_solver_matvec_sq(bb_solver *s, const double *x, double *y) {
 int bb_solver_stress(bb_solver *s, double *stress) {
     BB_TRY(check_ready(s, "bb_solver_stress"));
     BB_REQUIRE(stress != nullptr, "bb_solver_stress: stress is NULL");
-    BB_TRY(bb::enter_device(s->device));
-    BB_TRY(launch_grad(s));
-    if (s->n_maps > 1) {                       // the sum over the maps
-        std::vector<double> per((size_t)s->n_maps);
-        BB_TRY(launch_reduce(s, kReduceStressOnly, 0.0, s->d_map_scalar));
-        BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-        BB_HIP_CHECK(hipMemcpy(per.data(), s->d_map_scalar, per.size() * sizeof(double),
-                               hipMemcpyDeviceToHost));
-        *stress = 0.0;
-        for (double v : per) *stress += v;
-        return BB_OK;
-    }
-    BB_TRY(launch_reduce(s, kReduceStressOnly, 0.0, s->d_stress_scalar));
-    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-    BB_HIP_CHECK(hipMemcpy(stress, s->d_stress_scalar, sizeof(double), hipMemcpyDeviceToHost));
+    // the sum over the maps, in index order (one map: its value as it is)
+    std::vector<double> per((size_t)s->n_maps);
+    BB_TRY(bb_solver_stress_maps(s, per.data(), s->n_maps));
+    *stress = per[0];
+    for (size_t m = 1; m < per.size(); ++m) *stress += per[m];
     return BB_OK;
 }
 
@@ -2090,7 +2068,7 @@ int bb_solver_stress_maps(bb_solver *s, double *stress, int n_maps) {
     BB_REQUIRE(stress != nullptr && n_maps == s->n_maps, "bb_solver_stress_maps: bad argument");
     BB_TRY(bb::enter_device(s->device));
     BB_TRY(launch_grad(s));
-    double *out = s->n_maps > 1 ? s->d_map_scalar : s->d_stress_scalar;
+    double *out = s->n_maps > 1 ? s->d_map_scalar.as<double>() : s->d_stress_scalar;
     BB_TRY(launch_reduce(s, kReduceStressOnly, 0.0, out));
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));
     BB_HIP_CHECK(hipMemcpy(stress, out, (size_t)s->n_maps * sizeof(double), hipMemcpyDeviceToHost));
@@ -2145,7 +2123,7 @@ int bb_solver_set_timing(bb_solver *s, int enabled) {
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));
     if (enabled && s->ev.empty()) {
         s->ev.resize(3 * kMaxTimedLaunches);
-        for (auto &e : s->ev) BB_HIP_CHECK(hipEventCreate(&e));
+        for (bb::Event &e : s->ev) BB_HIP_CHECK(e.create());
     }
     s->timing = enabled != 0;
     s->timing_stride = enabled > 1 ? enabled : 1;
@@ -2194,10 +2172,10 @@ int bb_solver_measure_event_gap(bb_solver *s, int pairs, double *ms_avg) {
     BB_REQUIRE(pairs >= 1 && pairs <= 256, "bb_solver_measure_event_gap: bad pairs");
     BB_TRY(check_ready(s, "bb_solver_measure_event_gap"));
     BB_TRY(bb::enter_device(s->device));
-    std::vector<hipEvent_t> ev((size_t)2 * pairs, nullptr);
+    std::vector<bb::Event> ev((size_t)2 * pairs);
     hipError_t e = hipSuccess;
-    for (auto &x : ev)
-        if (e == hipSuccess) e = hipEventCreate(&x);
+    for (bb::Event &x : ev)
+        if (e == hipSuccess) e = x.create();
     for (int k = 0; k < pairs && e == hipSuccess; ++k) {
         // behind a sweep launch, as the timed intervals are (the sweep only writes partials)
         if (!s->row_owner && launch_grad(s) != BB_OK) e = hipErrorUnknown;
@@ -2211,8 +2189,6 @@ int bb_solver_measure_event_gap(bb_solver *s, int pairs, double *ms_avg) {
         e = hipEventElapsedTime(&a, ev[(size_t)2 * k], ev[(size_t)2 * k + 1]);
         t += a;
     }
-    for (auto x : ev)
-        if (x) (void)hipEventDestroy(x);
     if (e != hipSuccess)
         return bb::hip_status("bb_solver_measure_event_gap", e);
     *ms_avg = t / pairs;
@@ -2225,9 +2201,9 @@ int bb_solver_measure_stream_read(bb_solver *s, int launches, double *ms_avg) {
     if (!s->have_wish)
         return bb::fail(BB_ERR_STATE, "bb_solver_measure_stream_read: no wish distances set");
     BB_TRY(bb::enter_device(s->device));
-    hipEvent_t e0, e1;
-    BB_HIP_CHECK(hipEventCreate(&e0));
-    BB_HIP_CHECK(hipEventCreate(&e1));
+    bb::Event e0, e1;
+    BB_HIP_CHECK(e0.create());
+    BB_HIP_CHECK(e1.create());
     auto launch = [&]() {
         return bb::launch(s->nontemporal ? stream_read_kernel<true> : stream_read_kernel<false>,
                           dim3(s->n_waves / 4), dim3(256), 0, s->stream,
@@ -2241,8 +2217,6 @@ int bb_solver_measure_stream_read(bb_solver *s, int launches, double *ms_avg) {
     BB_HIP_CHECK(hipEventSynchronize(e1));
     float ms = 0.f;
     BB_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
     *ms_avg = ms / launches;
     return BB_OK;
 }
@@ -2302,7 +2276,7 @@ template <typename T>
 int spectral_init_t(TypeTag<T>, bb_solver *s, int n_iter, const double *v0, double tol, int *iters_done,
                     double *residual_out) {
     const int64_t n = s->L.n_bins, n_pad = s->L.n_pad, n3 = n_pad * 3;
-    if (!s->d_mv_in) BB_TRY(dev_alloc((char **)&s->d_mv_in, n3 * (int64_t)sizeof(T)));
+    if (!s->d_mv_in) BB_TRY(bb::alloc_status(s->d_mv_in, (size_t)n3 * sizeof(T)));
     // V, Z: (n_pad,3) doubles; dS: 12 sums (the two host steps at the end); dP0 / dP1: the
     // per-workgroup partial sums a pass leaves for the next one (two buffers: a pass reads its
     // producer's while it writes its own); dF: rank-loss flag
@@ -2332,13 +2306,13 @@ int spectral_init_t(TypeTag<T>, bb_solver *s, int n_iter, const double *v0, doub
         BB_HIP_CHECK(bb::launch(sp_affine_stats_kernel<double>, ggrp, bwg, 0, st, (const double *)dZ, dV,
                                 n, n_pad, (const double *)dP1, groups, (int)kSpChol, 1.0, dF, dP0));
         BB_HIP_CHECK(bb::launch(sp_affine_centre_kernel<T>, gvec, bwg, 0, st, (const double *)dV, dV,
-                                (T *)s->d_mv_in, n, n_pad, (const double *)dP0, groups, dF));
+                                s->d_mv_in.as<T>(), n, n_pad, (const double *)dP0, groups, dF));
         return BB_OK;
     };
     // dZ = -1/2 J (D o D) J V  (J = I - 11'/n) from the centred V in d_mv_in: sweep, sum over
     // the ranks, centre; the 12 sums of dZ are left in dP1
     auto apply_B = [&]() -> int {
-        BB_TRY(launch_grad(s, kOpMatvec2, s->d_mv_in));
+        BB_TRY(launch_grad(s, kOpMatvec2, s->d_mv_in.p));
         BB_TRY(exchange_sum(s));
         BB_HIP_CHECK(bb::launch(sp_stats_kernel<T>, ggrp, bwg, 0, st, (const T *)s->d_exch, n, n_pad, dP0));
         BB_HIP_CHECK(bb::launch(sp_affine_stats_kernel<T>, ggrp, bwg, 0, st, (const T *)s->d_exch, dZ, n,
@@ -2347,8 +2321,7 @@ int spectral_init_t(TypeTag<T>, bb_solver *s, int n_iter, const double *v0, doub
     };
     BB_HIP_CHECK(hipMemsetAsync(dF, 0, sizeof(int), st));
     BB_HIP_CHECK(hipMemsetAsync(s->d_V, 0, (size_t)n3 * sizeof(T), st));   // exchange_sum reads it
-    BB_HIP_CHECK(hipMemsetAsync(dZ, 0, (size_t)n3 * 8, st));
-    BB_HIP_CHECK(hipMemcpyAsync(dZ, v0, (size_t)n * 24, hipMemcpyHostToDevice, st));
+    BB_HIP_CHECK(upload_padded(s, dZ, v0, st));
     BB_HIP_CHECK(bb::launch(sp_stats_kernel<double>, ggrp, bwg, 0, st, (const double *)dZ, n, n_pad, dP1));
     BB_TRY(orthonormalise());
     // tol > 0: after every product but the first (a random V cannot have converged), the
@@ -2405,8 +2378,7 @@ int spectral_init_t(TypeTag<T>, bb_solver *s, int n_iter, const double *v0, doub
     // An eigenvector's sign is arbitrary: every Ritz vector V z_c is turned to the side of
     // the start's first column p (p . V z_c >= 0), as solver.py's spectral_init does, so one
     // seed gives one start whichever of the two computed it.
-    BB_HIP_CHECK(hipMemsetAsync(dZ, 0, (size_t)n3 * 8, st));
-    BB_HIP_CHECK(hipMemcpyAsync(dZ, v0, (size_t)n * 24, hipMemcpyHostToDevice, st));
+    BB_HIP_CHECK(upload_padded(s, dZ, v0, st));
     BB_HIP_CHECK(bb::launch(gram3_kernel<double, double>, dim3(1), dim3(1024), 0, st, (const double *)dV,
                             (const double *)dZ, n, dS));
     BB_TRY(fetch_sums());                                  // sums[r * 3 + 0] = V[:, r] . p
@@ -2469,9 +2441,9 @@ constexpr int kGroupAborted = -1;   // a member that left because another one fa
 struct bb_group {
     std::vector<bb_solver *> m;         // member r = rank r of world m.size()
     std::vector<void *> exch;           // the members' exchange buffers the tables point to
-    std::vector<void *> d_src;          // per member, on its device: the R exchange pointers
-    std::vector<unsigned *> d_mask;     // per member, on its device: block -> contributing ranks
-    std::vector<hipEvent_t> ready, applied;
+    std::vector<bb::DevBuf> d_src;      // per member, on its device: the R exchange pointers
+    std::vector<bb::DevBuf> d_mask;     // per member, on its device: block -> contributing ranks (unsigned)
+    std::vector<bb::Event> ready, applied;
     std::vector<std::thread> threads;
     // one job at a time, handed to the threads under `mu`
     std::mutex mu;
@@ -2492,7 +2464,7 @@ namespace {
 // previous step (its group_apply_kernel read this member's partial: WAR), grad, "ready".
 int group_grad(bb_group *g, int r) {
     bb_solver *s = g->m[(size_t)r];
-    for (hipEvent_t e : g->applied) BB_HIP_CHECK(hipStreamWaitEvent(s->stream, e, 0));
+    for (const bb::Event &e : g->applied) BB_HIP_CHECK(hipStreamWaitEvent(s->stream, e, 0));
     BB_TRY(launch_grad(s));
     BB_TRY(launch_reduce(s, kReduceExchange, 0.0, nullptr));
     BB_HIP_CHECK(hipEventRecord(g->ready[(size_t)r], s->stream));
@@ -2502,7 +2474,7 @@ int group_grad(bb_group *g, int r) {
 // Step 4: wait for every member's partial, sum in rank order and step, "applied".
 int group_apply(bb_group *g, int r) {
     bb_solver *s = g->m[(size_t)r];
-    for (hipEvent_t e : g->ready) BB_HIP_CHECK(hipStreamWaitEvent(s->stream, e, 0));
+    for (const bb::Event &e : g->ready) BB_HIP_CHECK(hipStreamWaitEvent(s->stream, e, 0));
     const int64_t n3 = s->L.n_pad * 3;
     const dim3 grid((unsigned)((n3 + 255) / 256)), block(256);
     const int world = (int)g->m.size(), ch = (int)(3 * s->L.vw);
@@ -2510,8 +2482,8 @@ int group_apply(bb_group *g, int r) {
     BB_TRY(by_dtype(s, [&](auto t) -> int {
         using T = typename decltype(t)::T;
         BB_HIP_CHECK(bb::launch(group_apply_kernel<T>, grid, block, 0, s->stream, (T *)s->d_X, (T *)s->d_V,
-                                (const T *const *)g->d_src[(size_t)r], world, n3, (T)g->lr, (T)s->momentum,
-                                hist, g->d_mask[(size_t)r], ch));
+                                g->d_src[(size_t)r].as<const T *const>(), world, n3, (T)g->lr, (T)s->momentum,
+                                hist, g->d_mask[(size_t)r].as<unsigned>(), ch));
         return BB_OK;
     }));
     BB_HIP_CHECK(hipEventRecord(g->applied[(size_t)r], s->stream));
@@ -2557,10 +2529,11 @@ void group_free(bb_group *g) {
     for (size_t r = 0; r < g->m.size(); ++r) {
         hipSetDevice(g->m[r]->device);
         hipStreamSynchronize(g->m[r]->stream);
-        if (r < g->ready.size() && g->ready[r]) hipEventDestroy(g->ready[r]);
-        if (r < g->applied.size() && g->applied[r]) hipEventDestroy(g->applied[r]);
-        if (r < g->d_src.size()) hipFree(g->d_src[r]);
-        if (r < g->d_mask.size()) hipFree(g->d_mask[r]);
+        // (each is made or empty: a setup that failed half way leaves the rest empty)
+        g->ready[r].reset();
+        g->applied[r].reset();
+        g->d_src[r].reset();
+        g->d_mask[r].reset();
     }
     delete g;
     (void)hipGetLastError();
@@ -2579,11 +2552,7 @@ int group_setup(bb_group *g) {
                 return bb::fail(BB_ERR_HIP, "bb_group_create: device " + std::to_string(da) +
                                                 " has no peer access to device " + std::to_string(db));
             BB_TRY(bb::enter_device(da));
-            hipError_t e = hipDeviceEnablePeerAccess(db, 0);
-            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled)
-                return bb::fail(BB_ERR_HIP, std::string("bb_group_create: hipDeviceEnablePeerAccess: ") +
-                                                hipGetErrorString(e));
-            (void)hipGetLastError();
+            BB_TRY(enable_peer_access("bb_group_create: hipDeviceEnablePeerAccess", db));
         }
     std::vector<unsigned> mask;
     BB_TRY(contributor_mask(g->m[0], &mask));
@@ -2591,14 +2560,14 @@ int group_setup(bb_group *g) {
         bb_solver *s = g->m[(size_t)r];
         BB_TRY(bb::enter_device(s->device));
         BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-        BB_TRY(dev_alloc((char **)&g->d_src[(size_t)r], (int64_t)(n * sizeof(void *))));
-        BB_HIP_CHECK(hipMemcpy(g->d_src[(size_t)r], g->exch.data(), n * sizeof(void *),
+        BB_TRY(bb::alloc_status(g->d_src[(size_t)r], n * sizeof(void *)));
+        BB_HIP_CHECK(hipMemcpy(g->d_src[(size_t)r].p, g->exch.data(), n * sizeof(void *),
                                hipMemcpyHostToDevice));
-        BB_TRY(dev_alloc(&g->d_mask[(size_t)r], (int64_t)mask.size()));
-        BB_HIP_CHECK(hipMemcpy(g->d_mask[(size_t)r], mask.data(), mask.size() * sizeof(unsigned),
+        BB_TRY(bb::alloc_status(g->d_mask[(size_t)r], mask.size() * sizeof(unsigned)));
+        BB_HIP_CHECK(hipMemcpy(g->d_mask[(size_t)r].p, mask.data(), mask.size() * sizeof(unsigned),
                                hipMemcpyHostToDevice));
-        BB_HIP_CHECK(hipEventCreateWithFlags(&g->ready[(size_t)r], hipEventDisableTiming));
-        BB_HIP_CHECK(hipEventCreateWithFlags(&g->applied[(size_t)r], hipEventDisableTiming));
+        BB_HIP_CHECK(g->ready[(size_t)r].create(hipEventDisableTiming));
+        BB_HIP_CHECK(g->applied[(size_t)r].create(hipEventDisableTiming));
         // recorded once, so that the first iteration's waits refer to a completed record
         BB_HIP_CHECK(hipEventRecord(g->applied[(size_t)r], s->stream));
         BB_HIP_CHECK(hipEventRecord(g->ready[(size_t)r], s->stream));
@@ -2648,20 +2617,15 @@ int bb_group_create(bb_group **out, bb_solver *const *members, int n) {
     if (!g) return bb::fail(BB_ERR_NOMEM, "bb_group_create: out of host memory");
     g->m.assign(members, members + n);
     for (bb_solver *s : g->m) g->exch.push_back(s->d_exch);
-    g->d_src.assign((size_t)n, nullptr);
-    g->d_mask.assign((size_t)n, nullptr);
-    g->ready.assign((size_t)n, nullptr);
-    g->applied.assign((size_t)n, nullptr);
+    g->d_src.resize((size_t)n);
+    g->d_mask.resize((size_t)n);
+    g->ready.resize((size_t)n);
+    g->applied.resize((size_t)n);
     g->rc.assign((size_t)n, BB_OK);
     g->err.assign((size_t)n, std::string());
     g->bar.n = n;
     const int rc = group_setup(g);
-    if (rc != BB_OK) {
-        std::string keep = bb_last_error();
-        group_free(g);
-        bb::set_error(keep);
-        return rc;
-    }
+    if (rc != BB_OK) return failed_create(rc, [&] { group_free(g); });
     *out = g;
     return BB_OK;
 }
