@@ -12,6 +12,7 @@ Drop-in names (same meaning as in `blueberry.*`, reference
                                   blueberry/utils.py:23-26
 Net-new (the reference has no solver; docs/SPEC.md):
     StructureSolver               contact matrix -> 3D coordinates
+    FitScore                      how well a structure fits a map (SPEC 2.8)
     shortest_paths                sparse map -> complete wish distances (SPEC 2.1.1)
 
 All compute runs in libblueberry_hip.so (hand-written HIP for gfx950) behind
@@ -24,7 +25,7 @@ from .utils import (HIGH_FITHIC_CUTOFF, LOW_FITHIC_CUTOFF, Q_LOWER_BOUND,  # noq
 from .band import count_band_regions  # noqa: F401
 from .datatypes import (ContactMap, EigenNoConvergence, FithicContactMap,  # noqa: F401
                         shortest_paths)
-from .solver import HipEngine, RankDeficient, StructureSolver  # noqa: F401
+from .solver import FitScore, HipEngine, RankDeficient, StructureSolver  # noqa: F401
 from .stats import benjamini_hochberg, downsample  # noqa: F401
 
 __version__ = "0.1.0"

@@ -35,6 +35,7 @@
 #include "bb_comm.h"
 #include "bb_common.h"
 #include "bb_group_barrier.h"
+#include "bb_score.h"
 #include "bb_solver_kernels.h"
 
 // --------------------------------------------------------------------------
@@ -135,6 +136,7 @@ struct bb_solver {
     int64_t timing_iter = 0;    // iterations seen since timing was (re-)enabled
     std::vector<bb::Event> ev;   // triples: start, after grad, after reduce
     size_t ev_used = 0;
+    double score_ms[3] = {0.0, 0.0, 0.0};   // the last timed bb_solver_score: profile, fold, per bin
 };
 
 namespace {
@@ -1184,6 +1186,44 @@ int bb_solver_weight_sums(bb_solver *s, double *sums, int64_t n_bins) {
     }));
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));
     BB_HIP_CHECK(hipMemcpy(sums, d_sum, (size_t)n_bins * sizeof(double), hipMemcpyDeviceToHost));
+    return BB_OK;
+}
+
+// SPEC 2.8: the sums a fit is judged by, over this rank's units.  The coordinates go through the
+// staging buffer of set_coords / get_coords as float64 (the caller's, or the solver's own
+// widened); the pass itself is bb_score.hip's and keeps what it allocates for the call only.
+// Coordinates, velocity, stress history and per-bin steps are not touched.
+int bb_solver_score(bb_solver *s, const double *xyz, double *profile, double *bins) {
+    BB_REQUIRE(s != nullptr && profile != nullptr && bins != nullptr, "bb_solver_score: NULL argument");
+    if (s->n_maps > 1) return bb::fail(BB_ERR_STATE, "bb_solver_score: not for a solver of several maps");
+    if (!s->have_wish) return bb::fail(BB_ERR_STATE, "bb_solver_score: no wish distances set");
+    if (s->grad_pending) return bb::fail(BB_ERR_STATE, "bb_solver_score: a bb_solver_grad is pending");
+    if (xyz == nullptr && !s->have_coords)
+        return bb::fail(BB_ERR_STATE, "bb_solver_score: no coordinates set");
+    if (xyz != nullptr)
+        for (int64_t q = 0; q < s->L.n_bins * 3; ++q)
+            BB_REQUIRE(std::isfinite(xyz[q]), "bb_solver_score: coordinates must be finite");
+    BB_TRY(bb::enter_device(s->device));
+    if (xyz != nullptr) BB_HIP_CHECK(upload_padded(s, s->d_f64_tmp, xyz, s->stream));
+    else BB_HIP_CHECK(widen(s, s->d_X, s->d_f64_tmp, s->L.n_pad * 3));
+    bb::ScoreInput in;
+    in.dtype = s->dtype, in.wide = s->wide;
+    in.n_bins = s->L.n_bins, in.n_local = s->n_local;
+    in.d_units = s->d_units, in.d_udesc = s->d_udesc, in.udesc = s->udesc.data();
+    in.d_xyz = s->d_f64_tmp, in.stream = s->stream;
+    const int rc = bb::score_pass(in, profile, bins, s->timing ? s->score_ms : nullptr);
+    // (whatever happened, nothing of the call is left on the stream: the host arrays behind the
+    // upload above belong to the caller)
+    if (hipStreamSynchronize(s->stream) != hipSuccess && rc == BB_OK)
+        return bb::fail(BB_ERR_HIP, "bb_solver_score: the stream did not drain");
+    return rc;
+}
+
+int bb_solver_get_score_timing(bb_solver *s, double *profile_ms, double *fold_ms, double *bins_ms) {
+    BB_REQUIRE(s != nullptr, "bb_solver_get_score_timing: solver is NULL");
+    if (profile_ms) *profile_ms = s->score_ms[0];
+    if (fold_ms) *fold_ms = s->score_ms[1];
+    if (bins_ms) *bins_ms = s->score_ms[2];
     return BB_OK;
 }
 

@@ -235,6 +235,16 @@ class HipEngine(object):
         self._call("weight_sums", _lib.as_f64_ptr(out), out.shape[0])
         return out
 
+    def score(self, xyz=None):
+        """The sums of SPEC 2.8 over this rank's units (`bb_solver_score`): (profile, bins),
+        float64 of shape (n_bins, 9) and (n_bins, 3).  xyz: the structure to score; None: the
+        engine's own coordinates."""
+        profile = numpy.zeros((self.n_bins, 9), dtype=numpy.float64)
+        bins = numpy.zeros((self.n_bins, 3), dtype=numpy.float64)
+        self._call("score", None if xyz is None else _lib.as_f64_ptr(_check_coords(xyz, self.n_bins)),
+                   _lib.as_f64_ptr(profile), _lib.as_f64_ptr(bins))
+        return profile, bins
+
     def stress_maps(self):
         out = numpy.empty(self.n_maps, dtype=numpy.float64)
         self._call("stress_maps", _lib.as_f64_ptr(out), out.shape[0])
@@ -464,6 +474,12 @@ class HipEngine(object):
         return {"grad_ms": float(g.value), "reduce_ms": float(r.value), "launches": int(n.value),
                 "step_ms": float(self._get(_lib.c_dbl, "get_step_timing"))}
 
+    def score_timing(self):
+        """(profile_ms, fold_ms, bins_ms) of the last `score` made with timing on."""
+        t = [_lib.c_dbl() for _ in range(3)]
+        self._call("get_score_timing", *t)
+        return tuple(float(v.value) for v in t)
+
     def event_gap_ms(self, pairs=16):
         """Average ms between two HIP events recorded back to back behind a sweep launch:
         what an event-timed interval contains besides its kernel (measurement aid)."""
@@ -490,8 +506,8 @@ class GroupEngine(object):
     world R on devices[r] (a device may repeat: members then share it), each holding only its
     own units; one host thread per member enqueues its iterations, and the partials are summed
     by group_apply_kernel in rank order, ordered by HIP events.  To `StructureSolver` it looks
-    like one engine of world 1: every setter goes to all members, degrees, weight sums and
-    matvecs come back summed over the members in rank order (float64 / int64), coordinates and
+    like one engine of world 1: every setter goes to all members, degrees, weight sums, matvecs
+    and scores come back summed over the members in rank order (float64 / int64), coordinates and
     stress history are member 0's -- all members hold the same bits."""
 
     def __init__(self, n_bins, dtype, devices, tiles=None):
@@ -590,6 +606,14 @@ class GroupEngine(object):
 
     def set_bin_steps(self, scale):
         self._each("set_bin_steps", scale)
+
+    def score(self, xyz=None):
+        """SPEC 2.8 over the whole map: each of the members' two arrays summed in rank order."""
+        profile, bins = self.members[0].score(xyz)
+        for e in self.members[1:]:
+            p, b = e.score(xyz)
+            profile, bins = profile + p, bins + b
+        return profile, bins
 
     def matvec_sq(self, x):
         """(D o D) @ x over the whole map: the members' products summed in rank order (the
@@ -901,6 +925,62 @@ def _teardown(eng):
         eng.close()
 
 
+class FitScore(object):
+    """How well a structure fits a map, from the device's sums (SPEC 2.8, `StructureSolver.score`).
+
+    sums : (n_bins, 9) float64, row k = the constrained pairs of separation j - i = k: pairs,
+        sum d, sum delta, sum d^2, sum delta^2, sum d delta, sum (d - delta)^2,
+        sum (d - delta)^2 / delta, sum ((d - delta) / delta)^2
+    bin_sums : (n_bins, 3) float64, row i = the pairs that hold bin i: pairs, sum (d - delta)^2,
+        sum ((d - delta) / delta)^2
+
+    Derived on the host in float64:
+    n_pairs : the constrained pairs
+    stress : array of 3, S_q of SPEC 2.3.1 for q = 0, 1, 2 -- comparable between fits made
+        with different weight_power
+    normalized_stress : stress[0] / sum delta^2
+    pearson : Pearson r of (d, delta) over the pairs; NaN with fewer than 2 pairs or no variance
+    pairs, mean_distance, mean_wish, rms_relative_error : per separation k (int64; the others
+        NaN where pairs == 0); rms_relative_error = sqrt(mean ((d - delta) / delta)^2)
+    bin_pairs, bin_stress, bin_relative : per bin: its pairs (int64), its sum (d - delta)^2
+        (every pair counts at both of its bins: the bins add up to 2 stress[0]) and the rms
+        relative error of its pairs (NaN for a bin without pairs)
+    """
+
+    def __init__(self, sums, bin_sums):
+        self.sums = numpy.ascontiguousarray(sums, dtype=numpy.float64)
+        self.bin_sums = numpy.ascontiguousarray(bin_sums, dtype=numpy.float64)
+        if self.sums.ndim != 2 or self.sums.shape[1] != 9 or self.bin_sums.shape != (self.sums.shape[0], 3):
+            raise ValueError("FitScore: sums must be (n_bins, 9) and bin_sums (n_bins, 3)")
+        tot = self.sums.sum(axis=0)
+        n, sd, sw, sdd, sww, sdw = (float(v) for v in tot[:6])
+        self.n_pairs = int(round(n))
+        self.stress = tot[6:9].copy()
+        self.normalized_stress = float(tot[6] / sww) if sww > 0 else float("nan")
+        # (a variance the rounding of its own sums could have made counts as none: each of the
+        # moments is good to n 2^-53 of itself)
+        var_d, var_w, noise = n * sdd - sd * sd, n * sww - sw * sw, 8.0 * n * n * 2.0 ** -53
+        self.pearson = (float((n * sdw - sd * sw) / numpy.sqrt(var_d * var_w))
+                        if self.n_pairs >= 2 and var_d > noise * sdd and var_w > noise * sww
+                        else float("nan"))
+
+        def per(total, count):
+            return numpy.where(count > 0, total / numpy.where(count > 0, count, 1.0), numpy.nan)
+        cnt = self.sums[:, 0]
+        self.pairs = numpy.rint(cnt).astype(numpy.int64)
+        self.mean_distance = per(self.sums[:, 1], cnt)
+        self.mean_wish = per(self.sums[:, 2], cnt)
+        self.rms_relative_error = numpy.sqrt(per(self.sums[:, 8], cnt))
+        self.bin_pairs = numpy.rint(self.bin_sums[:, 0]).astype(numpy.int64)
+        self.bin_stress = self.bin_sums[:, 1].copy()
+        self.bin_relative = numpy.sqrt(per(self.bin_sums[:, 2], self.bin_sums[:, 0]))
+
+    def __repr__(self):
+        return ("FitScore(n_pairs=%d, stress=%s, normalized_stress=%.6g, pearson=%.6g)"
+                % (self.n_pairs, numpy.array2string(self.stress, precision=6),
+                   self.normalized_stress, self.pearson))
+
+
 class StructureSolver(object):
     """Infer 3D bin coordinates from a Hi-C contact matrix (metric MDS).
 
@@ -1155,41 +1235,12 @@ class StructureSolver(object):
 
     def _fit_impl(self, matrix, n, init, KRnorm, KRexpected, kind=None):
         kind = self.kind if kind is None else kind      # 'wish' for a completed map
-        resident = getattr(matrix, "is_resident", False)
-        triples = getattr(matrix, "is_triples", False)
-        sparse = hasattr(matrix, "row") and not resident
-        if n < 2:
-            raise ValueError("need at least 2 bins (the contact map is empty)" if n == 0 else
-                             "need at least 2 bins")
-        devices = self._group_devices()                 # checked for one entry as well
-        group = devices if devices and len(devices) > 1 else None
-        rank, world = (0, 1) if devices else _dist_state(self.distributed)
+        eng, world, devices, pack = self._engine_for(matrix, n)
         lr = 1.0 / (2.0 * n) if self.lr == "auto" else float(self.lr)
         if init is None and self.init == "random":
             init = self._default_start(n)
-
-        tiles = None
-        if sparse:
-            # blocked-sparse: only the tiles that hold an entry exist on the device
-            keep = matrix.row != matrix.col
-            rows, cols, vals = matrix.row[keep], matrix.col[keep], matrix.data[keep]
-            tiles = tiles_from_entries(n, rows, cols, self.dtype)
-        elif triples:
-            tiles = matrix.tiles(n, self.dtype)
-        if group:
-            eng = GroupEngine(n, self.dtype, group, tiles=tiles)
-        else:
-            eng = self._engine_factory(n, self.dtype, rank=rank, world=world,
-                                       device=self._pick_device(world), tiles=tiles)
         with _teardown(eng):
-            if resident:
-                eng.set_wish_resident(matrix, kind, self.alpha)
-            elif triples:
-                eng.set_wish_triples(matrix, kind, self.alpha, KRnorm, KRexpected)
-            elif sparse:
-                eng.set_wish_sparse(rows, cols, vals, kind, self.alpha, KRnorm, KRexpected)
-            else:
-                eng.set_wish_dense(matrix, kind, self.alpha)
+            pack(kind, KRnorm, KRexpected)
             sums = self._bin_sums(eng, world)
             if sums is not None:
                 lr, scale = self._steps(sums, n)
@@ -1243,6 +1294,67 @@ class StructureSolver(object):
         self.devices_ = devices
         self.n_bins_, self.lr_, self.n_iter_ = n, lr, int(self.stress_.shape[0])
         return self
+
+    def _engine_for(self, matrix, n):
+        """The engine one input map runs on, the map not yet in it: (eng, world, devices, pack).
+        pack(kind, KRnorm, KRexpected) packs the map as the form of `matrix` asks -- resident
+        ContactMap, device triples, scipy.sparse (blocked-sparse: only the tiles that hold an
+        entry exist on the device) or a host matrix.  The caller closes the engine."""
+        resident = getattr(matrix, "is_resident", False)
+        triples = getattr(matrix, "is_triples", False)
+        sparse = hasattr(matrix, "row") and not resident
+        if n < 2:
+            raise ValueError("need at least 2 bins (the contact map is empty)" if n == 0 else
+                             "need at least 2 bins")
+        devices = self._group_devices()                 # checked for one entry as well
+        group = devices if devices and len(devices) > 1 else None
+        rank, world = (0, 1) if devices else _dist_state(self.distributed)
+        tiles = None
+        if sparse:
+            keep = matrix.row != matrix.col
+            rows, cols, vals = matrix.row[keep], matrix.col[keep], matrix.data[keep]
+            tiles = tiles_from_entries(n, rows, cols, self.dtype)
+        elif triples:
+            tiles = matrix.tiles(n, self.dtype)
+        if group:
+            eng = GroupEngine(n, self.dtype, group, tiles=tiles)
+        else:
+            eng = self._engine_factory(n, self.dtype, rank=rank, world=world,
+                                       device=self._pick_device(world), tiles=tiles)
+
+        def pack(kind, KRnorm, KRexpected):
+            if resident:
+                eng.set_wish_resident(matrix, kind, self.alpha)
+            elif triples:
+                eng.set_wish_triples(matrix, kind, self.alpha, KRnorm, KRexpected)
+            elif sparse:
+                eng.set_wish_sparse(rows, cols, vals, kind, self.alpha, KRnorm, KRexpected)
+            else:
+                eng.set_wish_dense(matrix, kind, self.alpha)
+        return eng, world, devices, pack
+
+    def score(self, X, structure=None):
+        """How well a structure fits the map `X` (SPEC 2.8): a `FitScore`.  `X` takes every
+        form `fit` takes and is packed the same way, under this solver's kind, alpha, dtype and
+        devices; no iteration runs -- one pass over the packed map forms float64 sums per
+        genomic separation and per bin, summed over the ranks of a torch.distributed job or
+        the members of `devices=`.  structure: (n_bins, 3); None: `structure_` of the last fit.
+        The score is against the pairs `X` holds: to score against a completed map, pass
+        `ContactMap.shortest_paths(...)` to a kind='wish' solver.  Comparable across
+        weight_power: `FitScore.stress` holds all three S_q."""
+        source, n = self._map_source(X)
+        if structure is None:
+            structure = getattr(self, "structure_", None)
+            if structure is None:
+                raise ValueError("score: no structure given and none fitted yet (structure_)")
+        xyz = _check_coords(structure, n)
+        eng, world, _, pack = self._engine_for(source, n)
+        with _teardown(eng):
+            pack(self.kind, None, None)
+            profile, bins = eng.score(xyz)
+            profile = _sum_over_ranks(profile, eng, world)
+            bins = _sum_over_ranks(bins, eng, world)
+        return FitScore(profile, bins)
 
     def _group_devices(self):
         """The devices of a devices= / n_gpus= fit (one entry included), checked against this

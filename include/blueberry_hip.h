@@ -449,6 +449,31 @@ BB_API int bb_solver_spectral_init_tol(bb_solver *s, int n_iter, double tol, con
 
 /* Stress of the current coordinates (one gradient pass, no update). */
 BB_API int bb_solver_stress(bb_solver *s, double *stress);
+/* How well a structure fits the resident map (docs/SPEC.md 2.8): ONE pass over this rank's
+ * units, no iteration, float64 sums over the stored pairs i < j < n_bins with delta > 0,
+ * d = |x_i - x_j| without a floor.
+ *   profile  (n_bins, 9), row k = the pairs of genomic separation j - i = k (row 0 is zero):
+ *            pairs, sum d, sum delta, sum d^2, sum delta^2, sum d delta, sum (d - delta)^2,
+ *            sum (d - delta)^2 / delta, sum ((d - delta) / delta)^2
+ *   bins     (n_bins, 3), row i = the pairs that hold bin i: pairs, sum (d - delta)^2,
+ *            sum ((d - delta) / delta)^2
+ * The counts are exact doubles; the residual columns are summed as written, never formed from
+ * the moments.  xyz: the (n_bins, 3) structure to score, or NULL for the solver's own
+ * coordinates widened to float64.  No floating-point atomics, every sum in an order fixed by
+ * the layout and the rank's unit range: the same bits on every call.  world > 1: the caller
+ * sums both arrays over the ranks (as bb_solver_degrees); a rank without units gives zeros.
+ * Nothing of the solver changes: coordinates, velocity, stress history and per-bin steps stay.
+ * BB_ERR_STATE before wish distances are set, while a bb_solver_grad is pending, for a solver
+ * of several maps, and for xyz == NULL before coordinates are set; BB_ERR_INVALID for xyz that
+ * is not finite.  The scratch of a call, released before it returns:
+ * runs * (2 vw - 1) * 72 bytes, a run being this rank's units of one tile, + 96 n_bins.
+ *   bb_solver_get_score_timing  HIP-event times (ms) of the last call's three kernels --
+ *                               profile, fold, per bin -- made while bb_solver_set_timing was
+ *                               on (else 0); any pointer may be NULL
+ * No counterpart in the reference (it has no solver). */
+BB_API int bb_solver_score(bb_solver *s, const double *xyz, double *profile, double *bins);
+BB_API int bb_solver_get_score_timing(bb_solver *s, double *profile_ms, double *fold_ms,
+                                      double *bins_ms);
 /* Copies the stress history (one value per completed iteration since the
  * last bb_solver_set_coords) to the host; synchronises the stream. */
 BB_API int bb_solver_get_stress_history(bb_solver *s, double *out, int64_t cap, int64_t *n);
