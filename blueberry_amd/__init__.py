@@ -14,6 +14,8 @@ Net-new (the reference has no solver; docs/SPEC.md):
     StructureSolver               contact matrix -> 3D coordinates
     FitScore                      how well a structure fits a map (SPEC 2.8)
     shortest_paths                sparse map -> complete wish distances (SPEC 2.1.1)
+    balance_triples, DeviceTriples
+                                  ICE bias and expected straight from a pixel list (SPEC 2.5.3)
 
 All compute runs in libblueberry_hip.so (hand-written HIP for gfx950) behind
 the C-ABI of include/blueberry_hip.h.  Importing this package needs neither
@@ -25,7 +27,8 @@ from .utils import (HIGH_FITHIC_CUTOFF, LOW_FITHIC_CUTOFF, Q_LOWER_BOUND,  # noq
 from .band import count_band_regions  # noqa: F401
 from .datatypes import (ContactMap, EigenNoConvergence, FithicContactMap,  # noqa: F401
                         shortest_paths)
-from .solver import FitScore, HipEngine, RankDeficient, StructureSolver  # noqa: F401
+from .solver import (DeviceTriples, FitScore, HipEngine, RankDeficient,  # noqa: F401
+                     StructureSolver, TriplesBalance, balance_triples)
 from .stats import benjamini_hochberg, downsample  # noqa: F401
 
 __version__ = "0.1.0"

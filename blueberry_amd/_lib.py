@@ -121,6 +121,10 @@ SIGNATURES = {
     "bb_cm_balance": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_dbl, c_i64, c_dbl, p_dbl,
                               ctypes.POINTER(ctypes.c_uint8), p_i64, p_dbl]),
     "bb_cm_expected": (c_int, [c_void_p, c_i64, p_dbl, p_dbl, p_i64]),
+    "bb_triples_balance": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_dbl, c_i64, c_dbl, p_dbl,
+                                   ctypes.POINTER(ctypes.c_uint8), p_i64, p_dbl]),
+    "bb_triples_expected": (c_int, [c_void_p, c_i64, p_dbl, p_dbl, p_i64]),
+    "bb_triples_pairs": (c_int, [c_void_p, c_i64, p_i64]),
     "bb_solver_set_wish_from_cm": (c_int, [c_void_p, c_void_p, c_int, c_dbl]),
     "bb_solver_set_wish_from_cm_block": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_dbl]),
     "bb_solver_set_maps": (c_int, [c_void_p, c_int, p_i64, p_dbl]),

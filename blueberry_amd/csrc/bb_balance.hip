@@ -14,6 +14,9 @@
 //                      b and x) in ONE workgroup: every sum in a fixed order, the loop's state
 //                      on the device.  A stopped loop turns later launches into no-ops, so the
 //                      host enqueues a batch of iterations per scalar read-back.
+//   bb::balance_loop   the whole of 2.5.2 around a product it is GIVEN (bb_balance_loop.h):
+//                      bb_cm_balance passes the banded product, bb_triples_balance.hip the
+//                      product over its index of resident triples (SPEC 2.5.3).
 //   diag_sums_kernel   sum_k and cnt_k of every diagonal in one read of the upper triangle:
 //                      row r of a wave loads its 64-element chunk r columns later, so that a
 //                      lane holds ONE diagonal for all 16 rows and adds them into one register
@@ -29,6 +32,7 @@
 #include <string>
 #include <vector>
 
+#include "bb_balance_loop.h"
 #include "bb_cm_internal.h"
 #include "bb_common.h"
 
@@ -291,29 +295,23 @@ constexpr int kBalanceBatch = 16;
 
 }  // namespace
 
-extern "C" {
+namespace bb {
 
-int bb_cm_balance(bb_cm *cm, int64_t n_bins, int64_t ignore_diags, int64_t min_nnz, double tol,
-                  int64_t max_iter, double row_sum, double *bias, uint8_t *masked, int64_t *iterations,
-                  double *variance) {
-    BB_TRY(bb::cm_check(cm, "bb_cm_balance"));
-    BB_TRY(bb::cm_check_bins(cm, n_bins, "bb_cm_balance"));
-    BB_REQUIRE(bias != nullptr && masked != nullptr, "bb_cm_balance: NULL argument");
-    BB_REQUIRE(ignore_diags >= 0 && min_nnz >= 0, "bb_cm_balance: ignore_diags / min_nnz is negative");
-    BB_REQUIRE(tol >= 0.0 && tol <= DBL_MAX && max_iter >= 0, "bb_cm_balance: bad tol / max_iter");
-    BB_REQUIRE(row_sum == row_sum && row_sum <= DBL_MAX, "bb_cm_balance: row_sum is not finite");
-    const int64_t n = n_bins;
-    ignore_diags = std::min(ignore_diags, n);         // (beyond n - 1 nothing is counted anyway)
-    BB_REQUIRE(n >= 1, "bb_cm_balance: no bin is left to balance (the map has no bins)");
-    BB_TRY(bb::hip_status("bb_cm_balance", cm->bal.prepare(n, true, cm->stream), BB_ERR_NOMEM));
-    bb::DevBuf bx, bbias, by, blive, bst;
+hipError_t inverse_bias_enqueue(const double *bias, double *x, int64_t n, hipStream_t st) {
+    return launch(inverse_bias_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, bias, x, n);
+}
+
+int balance_loop(const char *who_, int64_t n, hipStream_t st, const BalanceProduct &product,
+                 int64_t min_nnz, double tol, int64_t max_iter, double row_sum, double *bias,
+                 uint8_t *masked, int64_t *iterations, double *variance) {
+    const std::string who(who_);
+    DevBuf bx, bbias, by, blive, bst;
     hipError_t e = bx.alloc((size_t)n * 8);
     if (e == hipSuccess) e = bbias.alloc((size_t)n * 8);
     if (e == hipSuccess) e = by.alloc((size_t)n * 8);
     if (e == hipSuccess) e = blive.alloc((size_t)n);
     if (e == hipSuccess) e = bst.alloc(sizeof(BalanceState));
-    BB_TRY(bb::hip_status("bb_cm_balance", e, BB_ERR_NOMEM));
-    hipStream_t st = cm->stream;
+    BB_TRY(hip_status(who_, e, BB_ERR_NOMEM));
     double *x = (double *)bx.p, *b = (double *)bbias.p, *y = (double *)by.p;
     unsigned char *live = (unsigned char *)blive.p;
     BalanceState *dst = (BalanceState *)bst.p;
@@ -322,57 +320,57 @@ int bb_cm_balance(bb_cm *cm, int64_t n_bins, int64_t ignore_diags, int64_t min_n
 
     // 1. the input check: one pass over the counted upper triangle
     e = hipMemsetAsync(dst, 0, sizeof(BalanceState), st);
-    if (e == hipSuccess) e = bb::launch(fill_kernel, gvec, b256, 0, st, x, 1.0, n);
-    if (e == hipSuccess) e = band_symv_enqueue<kCellBad>(cm, ignore_diags, x, y, nullptr);
+    if (e == hipSuccess) e = launch(fill_kernel, gvec, b256, 0, st, x, 1.0, n);
+    if (e == hipSuccess) e = product(kCellBad, x, y, nullptr);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipMemcpy(host.data(), y, (size_t)n * 8, hipMemcpyDeviceToHost);
-    BB_TRY(bb::hip_status("bb_cm_balance", e));
+    BB_TRY(hip_status(who_, e));
     double n_bad = 0.0;
     for (int64_t i = 0; i < n; ++i) n_bad += host[(size_t)i];     // small integers: exact
     if (n_bad != 0.0)
-        return bb::fail(BB_ERR_INVALID, "bb_cm_balance: " + std::to_string((long long)n_bad) +
-                                            " counted cells of the upper triangle are negative or not "
-                                            "finite; the map was left as it is");
+        return fail(BB_ERR_INVALID, who + ": " + std::to_string((long long)n_bad) +
+                                        " counted cells of the upper triangle are negative or not "
+                                        "finite; the map was left as it is");
 
     // 2. the mask: min_nnz on the raw map, once; then zero marginals over the live bins, to the
     //    fixed point (the product of the round that changes nothing is iteration 0's)
     if (min_nnz > 0) {
-        e = band_symv_enqueue<kCellNonzero>(cm, ignore_diags, x, y, nullptr);
+        e = product(kCellNonzero, x, y, nullptr);
         if (e == hipSuccess)
-            e = bb::launch(balance_start_kernel, gvec, b256, 0, st, (const double *)y, (double)min_nnz, n,
-                           live, x, b);
+            e = launch(balance_start_kernel, gvec, b256, 0, st, (const double *)y, (double)min_nnz, n,
+                       live, x, b);
     } else {
-        e = bb::launch(balance_start_kernel, gvec, b256, 0, st, (const double *)nullptr, 0.0, n, live, x, b);
+        e = launch(balance_start_kernel, gvec, b256, 0, st, (const double *)nullptr, 0.0, n, live, x, b);
     }
     BalanceState hs;
     hs.changed = 1;
     hs.n_live = 0;
     while (e == hipSuccess && hs.changed != 0) {
-        e = band_symv_enqueue<kCellValue>(cm, ignore_diags, x, y, nullptr);
+        e = product(kCellValue, x, y, nullptr);
         if (e == hipSuccess)
-            e = bb::launch(balance_mask_kernel, dim3(1), dim3(1024), 0, st, (const double *)y, n, live, x, dst);
+            e = launch(balance_mask_kernel, dim3(1), dim3(1024), 0, st, (const double *)y, n, live, x, dst);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e == hipSuccess) e = hipMemcpy(&hs, dst, sizeof(hs), hipMemcpyDeviceToHost);
     }
-    BB_TRY(bb::hip_status("bb_cm_balance", e));
+    BB_TRY(hip_status(who_, e));
     if (hs.n_live == 0)
-        return bb::fail(BB_ERR_INVALID,
-                        "bb_cm_balance: no live bin is left (every bin is masked: min_nnz, or no "
-                        "count outside the ignored diagonals)");
+        return fail(BB_ERR_INVALID,
+                    who + ": no live bin is left (every bin is masked: min_nnz, or no "
+                          "count outside the ignored diagonals)");
 
     // 3. the loop: y holds A x of iteration 0
-    e = bb::launch(balance_step_kernel, dim3(1), dim3(1024), 0, st, (const double *)y, n,
-                   (const unsigned char *)live, x, b, tol, (long long)max_iter, dst);
+    e = launch(balance_step_kernel, dim3(1), dim3(1024), 0, st, (const double *)y, n,
+               (const unsigned char *)live, x, b, tol, (long long)max_iter, dst);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipMemcpy(&hs, dst, sizeof(hs), hipMemcpyDeviceToHost);
     while (e == hipSuccess && hs.stopped == 0) {
         // at most the updates that are left, and the evaluation at which `it == max_iter` stops
         const int batch = (int)std::min<int64_t>(kBalanceBatch, max_iter - hs.it + 1);
         for (int q = 0; q < batch && e == hipSuccess; ++q) {
-            e = band_symv_enqueue<kCellValue>(cm, ignore_diags, x, y, &dst->stopped);
+            e = product(kCellValue, x, y, &dst->stopped);
             if (e == hipSuccess)
-                e = bb::launch(balance_step_kernel, dim3(1), dim3(1024), 0, st, (const double *)y, n,
-                               (const unsigned char *)live, x, b, tol, (long long)max_iter, dst);
+                e = launch(balance_step_kernel, dim3(1), dim3(1024), 0, st, (const double *)y, n,
+                           (const unsigned char *)live, x, b, tol, (long long)max_iter, dst);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e == hipSuccess) e = hipMemcpy(&hs, dst, sizeof(hs), hipMemcpyDeviceToHost);
@@ -380,7 +378,7 @@ int bb_cm_balance(bb_cm *cm, int64_t n_bins, int64_t ignore_diags, int64_t min_n
     std::vector<unsigned char> hlive((size_t)n);
     if (e == hipSuccess) e = hipMemcpy(host.data(), b, (size_t)n * 8, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(hlive.data(), live, (size_t)n, hipMemcpyDeviceToHost);
-    BB_TRY(bb::hip_status("bb_cm_balance", e));
+    BB_TRY(hip_status(who_, e));
 
     // 4. the scale: the balanced map's mean row sum becomes row_sum, or stays the input's
     const double target = row_sum > 0.0 ? row_sum : hs.mean0;
@@ -392,6 +390,30 @@ int bb_cm_balance(bb_cm *cm, int64_t n_bins, int64_t ignore_diags, int64_t min_n
     if (iterations) *iterations = hs.it;
     if (variance) *variance = hs.var;
     return BB_OK;
+}
+
+}  // namespace bb
+
+extern "C" {
+
+int bb_cm_balance(bb_cm *cm, int64_t n_bins, int64_t ignore_diags, int64_t min_nnz, double tol,
+                  int64_t max_iter, double row_sum, double *bias, uint8_t *masked, int64_t *iterations,
+                  double *variance) {
+    BB_TRY(bb::cm_check(cm, "bb_cm_balance"));
+    BB_TRY(bb::cm_check_bins(cm, n_bins, "bb_cm_balance"));
+    BB_TRY(bb::balance_check_args("bb_cm_balance", n_bins, ignore_diags, min_nnz, tol, max_iter, row_sum,
+                                  bias, masked));
+    const int64_t n = n_bins;
+    ignore_diags = std::min(ignore_diags, n);         // (beyond n - 1 nothing is counted anyway)
+    BB_TRY(bb::hip_status("bb_cm_balance", cm->bal.prepare(n, true, cm->stream), BB_ERR_NOMEM));
+    return bb::balance_loop(
+        "bb_cm_balance", n, cm->stream,
+        [&](int mode, const double *x, double *y, const int *stop) {
+            if (mode == kCellBad) return band_symv_enqueue<kCellBad>(cm, ignore_diags, x, y, stop);
+            if (mode == kCellNonzero) return band_symv_enqueue<kCellNonzero>(cm, ignore_diags, x, y, stop);
+            return band_symv_enqueue<kCellValue>(cm, ignore_diags, x, y, stop);
+        },
+        min_nnz, tol, max_iter, row_sum, bias, masked, iterations, variance);
 }
 
 int bb_cm_expected(bb_cm *cm, int64_t n_bins, const double *bias, double *sums, int64_t *counts) {

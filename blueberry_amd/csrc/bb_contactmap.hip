@@ -19,21 +19,16 @@
 
 #include "bb_cm_internal.h"
 #include "bb_common.h"
+#include "bb_triples.h"
 #include <cstdlib>
 
 namespace {
 
 using bb::lds_barrier;   // bb_cm_internal.h
+using bb::nan_to_num;    // bb_triples.h
+using bb::triple_bins;
 
 constexpr int kT = 32;  // tile edge of the normalise / finalise kernels (kT x 8 threads)
-
-__device__ __forceinline__ double nan_to_num(double v) {
-    // numpy.nan_to_num defaults: NaN -> 0, +/-inf -> +/-DBL_MAX
-    if (v != v) return 0.0;
-    if (v > 1.7976931348623157e308) return 1.7976931348623157e308;
-    if (v < -1.7976931348623157e308) return -1.7976931348623157e308;
-    return v;
-}
 
 // One workgroup per tile pair (TJ <= TK) of the (d,d) matrix, IN PLACE: computes the
 // upper tile, writes it back, and writes its mirror through LDS so that every global
@@ -178,21 +173,10 @@ __global__ __launch_bounds__(kNT * 8) void normalize128_kernel(double *m, int64_
 // bin * resolution -- what the caller needs to write down `regions` without sorting.
 // numpy.nan_to_num with its defaults (pyx:102) is applied to a triple's values as they are
 // read: the 240 MB of a chr1@10kb file need no pass over them on the host.
-//
-// The two bins of a triple with the (nan_to_num'ed) positions pj, pk; false if one of them is
-// outside [0, d).  (A position beyond the int range -- an infinity turned into 1.8e308 -- is
-// out of range whatever the cast would make of it.)
+// The binning (bb::triple_bins) and nan_to_num are bb_triples.h's: bb_triples_balance.hip reads
+// triples by the same two rules.
 __device__ __forceinline__ unsigned long long scatter_mark(int64_t t) {
     return 0xFFF8000000000000ull | (unsigned long long)(t + 1);     // t + 1 < 2^31 (bb_cm_scatter_ex)
-}
-
-__device__ __forceinline__ bool triple_bins(double pj, double pk, double resolution, int64_t d,
-                                            int &j, int &k) {
-    const double qj = pj / resolution, qk = pk / resolution;
-    const bool wild = !(qj > -2147483648.0 && qj < 2147483648.0 && qk > -2147483648.0 && qk < 2147483648.0);
-    j = wild ? -1 : (int)qj;
-    k = wild ? -1 : (int)qk;
-    return !(j < 0 || k < 0 || j >= d || k >= d);
 }
 
 __global__ void scatter_mark_kernel(const double *__restrict__ tr, int64_t n, int64_t st, int64_t sc,

@@ -37,6 +37,7 @@
 #include "bb_group_barrier.h"
 #include "bb_score.h"
 #include "bb_solver_kernels.h"
+#include "bb_triples.h"
 
 // --------------------------------------------------------------------------
 // host side
@@ -1313,14 +1314,7 @@ int bb_solver_set_wish_sparse(bb_solver *s, const int64_t *rows, const int64_t *
 }
 
 // ---- Rao-format triples resident on the device (fit_triples without host binning) --------
-struct bb_triples {
-    int device = 0;
-    int64_t n = 0, st = 3, sc = 1;      // element (t, c) at d[t * st + c * sc]
-    double resolution = 1.0;
-    bb::DevBuf d;                       // 3 n doubles
-    const double *from(int64_t t0) const { return d.as<double>() + t0 * (st == 3 ? 3 : 1); }
-};
-
+// (struct bb_triples: bb_triples.h, shared with bb_triples_balance.hip)
 int bb_triples_create(bb_triples **out, const double *triples, int64_t n, int32_t resolution,
                       int32_t row_major, int device) {
     BB_REQUIRE(out != nullptr, "bb_triples_create: out is NULL");

@@ -165,6 +165,23 @@ class _DeviceMatrix(object):
             pass
 
 
+def check_balance_args(ignore_diags=0, min_nnz=0, tol=1e-5, max_iter=200, row_sum=None):
+    """The arguments `ContactMap.balance`, `DeviceTriples.balance` and `balance_triples` share,
+    converted and checked (ValueError) without touching the library."""
+    import math
+    ignore_diags, min_nnz, max_iter = int(ignore_diags), int(min_nnz), int(max_iter)
+    tol = float(tol)
+    if ignore_diags < 0 or min_nnz < 0:
+        raise ValueError("ignore_diags and min_nnz must not be negative")
+    if not (tol >= 0.0 and math.isfinite(tol)):
+        raise ValueError("tol must be finite and not negative")
+    if max_iter < 0:
+        raise ValueError("max_iter must not be negative")
+    if row_sum is not None and not (float(row_sum) > 0.0 and math.isfinite(float(row_sum))):
+        raise ValueError("row_sum must be positive and finite")
+    return ignore_diags, min_nnz, tol, max_iter, row_sum
+
+
 def expected_from_sums(sums, counts):
     """e[k] = sums[k] / counts[k], NaN where counts[k] == 0 or sums[k] == 0 (docs/SPEC.md 2.5.2)."""
     sums = numpy.asarray(sums, dtype=numpy.float64)
@@ -499,17 +516,8 @@ class ContactMap(object):
         then divides it in place by b_i b_j (`normalize()` with an all-ones expected vector:
         masked bins become 0).  The same bits on every run."""
         import ctypes
-        import math
-        ignore_diags, min_nnz, max_iter = int(ignore_diags), int(min_nnz), int(max_iter)
-        tol = float(tol)
-        if ignore_diags < 0 or min_nnz < 0:
-            raise ValueError("ignore_diags and min_nnz must not be negative")
-        if not (tol >= 0.0 and math.isfinite(tol)):
-            raise ValueError("tol must be finite and not negative")
-        if max_iter < 0:
-            raise ValueError("max_iter must not be negative")
-        if row_sum is not None and not (float(row_sum) > 0.0 and math.isfinite(float(row_sum))):
-            raise ValueError("row_sum must be positive and finite")
+        ignore_diags, min_nnz, tol, max_iter, row_sum = check_balance_args(
+            ignore_diags, min_nnz, tol, max_iter, row_sum)
         dev = self._balance_target()
         n = self.n_bins
         bias = numpy.empty(n, dtype=numpy.float64)

@@ -35,13 +35,17 @@ class DeviceTriples(object):
     """The (n, 3) array [pos_i, pos_j, count] of a Rao-format file -- what
     `ContactMap.__init__` reads (`blueberry/datatypes.pyx:100-102`) -- copied to the device
     once (`bb_triples_*`): nan_to_num, binning and the scatter into the solver's tiles all
-    happen there.  C-ordered rows and the reference's column-major array are read in place."""
+    happen there.  C-ordered rows and the reference's column-major array are read in place.
+
+    `balance` and `expected` are `ContactMap.balance` / `ContactMap.expected` on the matrix the
+    triples define -- `ContactMap.from_triples(triples, resolution, n_bins)` -- without that
+    matrix (docs/SPEC.md 2.5.3): the first call builds an index of the stored cells on the
+    device, which stays with the handle."""
     is_triples = True
 
     def __init__(self, triples, resolution, device):
-        t = numpy.asarray(triples, dtype=numpy.float64)
-        if t.ndim != 2 or t.shape[1] != 3:
-            raise ValueError("triples must have shape (n, 3)")
+        t = _check_triples(triples)
+        self.resolution = int(resolution)
         if t.flags.c_contiguous:
             buf, row_major = t, 1
         elif t.flags.f_contiguous:
@@ -66,6 +70,58 @@ class DeviceTriples(object):
         tj, ti = numpy.nonzero(present.T)            # J ascending, then I
         return ti.astype(numpy.int32), tj.astype(numpy.int32)
 
+    def pairs(self, n_bins):
+        """The number of distinct bin pairs i <= j < n_bins the triples store."""
+        out = _lib.c_i64()
+        _lib.check(self._lib.bb_triples_pairs(self._h, int(n_bins), out), "bb_triples_pairs")
+        return int(out.value)
+
+    def balance(self, n_bins, ignore_diags=0, min_nnz=0, tol=1e-5, max_iter=200, row_sum=None):
+        """The ICE bias vector of the map the triples define over bins 0 .. n_bins - 1
+        (`bb_triples_balance`): the arguments, the result (length n_bins, NaN at masked bins)
+        and the attributes `balance_iterations_`, `balance_variance_`, `balance_converged_`,
+        `balance_masked_` of `ContactMap.balance`.  The same bits on every run, and for every
+        duplicate-free list of the same pairs."""
+        import ctypes
+        from .datatypes import check_balance_args
+        ignore_diags, min_nnz, tol, max_iter, row_sum = check_balance_args(
+            ignore_diags, min_nnz, tol, max_iter, row_sum)
+        n = int(n_bins)
+        if n < 0:
+            raise ValueError("n_bins must not be negative")
+        bias = numpy.empty(n, dtype=numpy.float64)
+        masked = numpy.zeros(n, dtype=numpy.uint8)
+        it, var = _lib.c_i64(), _lib.c_dbl()
+        _lib.check(self._lib.bb_triples_balance(
+            self._h, n, ignore_diags, min_nnz, tol, max_iter, 0.0 if row_sum is None else float(row_sum),
+            _lib.as_f64_ptr(bias), masked.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), it, var),
+            "bb_triples_balance")
+        self.balance_iterations_, self.balance_variance_ = int(it.value), float(var.value)
+        self.balance_converged_ = self.balance_variance_ < tol
+        self.balance_masked_ = masked.astype(bool)
+        return bias
+
+    def expected(self, n_bins, bias=None):
+        """The distance-decay expected e of the balanced map (`bb_triples_expected`,
+        `ContactMap.expected`): bias None -- all ones -- or a length-n_bins vector, NaN = not a
+        live bin.  `expected_sums_` and `expected_counts_` (int64) hold the two raw vectors;
+        pairs without a triple are zero cells and count."""
+        from .datatypes import expected_from_sums
+        n = int(n_bins)
+        if n < 0:
+            raise ValueError("n_bins must not be negative")
+        if bias is not None:
+            bias = numpy.ascontiguousarray(bias, dtype=numpy.float64)
+            if bias.shape != (n,):
+                raise ValueError("bias must have n_bins = %d values, got shape %r" % (n, bias.shape))
+        sums = numpy.zeros(n, dtype=numpy.float64)
+        counts = numpy.zeros(n, dtype=numpy.int64)
+        _lib.check(self._lib.bb_triples_expected(
+            self._h, n, None if bias is None else _lib.as_f64_ptr(bias), _lib.as_f64_ptr(sums),
+            counts.ctypes.data_as(_lib.p_i64)), "bb_triples_expected")
+        self.expected_sums_, self.expected_counts_ = sums, counts
+        return expected_from_sums(sums, counts)
+
     def close(self):
         if self._h:
             self._lib.bb_triples_destroy(self._h)
@@ -76,6 +132,71 @@ class DeviceTriples(object):
             self.close()
         except Exception:
             pass
+
+
+def _check_triples(triples):
+    """The float64 (n, 3) view of `triples`, or ValueError."""
+    t = numpy.asarray(triples, dtype=numpy.float64)
+    if t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError("triples must have shape (n, 3)")
+    return t
+
+
+_BALANCE_KEYS = ("ignore_diags", "min_nnz", "tol", "max_iter", "row_sum")
+
+
+def _balance_options(balance):
+    """`fit_triples(balance=...)` as (checked keyword arguments of `DeviceTriples.balance`, whether
+    the expected is wanted), without touching the library."""
+    from .datatypes import check_balance_args
+    if balance is True:
+        balance = {}
+    if not isinstance(balance, dict):
+        raise ValueError("balance must be None, True or a dict of balance_triples' arguments")
+    unknown = sorted(set(balance) - set(_BALANCE_KEYS) - {"expected"})
+    if unknown:
+        raise ValueError("balance: unknown argument %r" % (unknown[0],))
+    args = {k: balance[k] for k in _BALANCE_KEYS if k in balance}
+    return dict(zip(_BALANCE_KEYS, check_balance_args(**args))), bool(balance.get("expected", False))
+
+
+class TriplesBalance(object):
+    """What `balance_triples` returns: `bias` (length n_bins, NaN at masked bins), `masked` (bool),
+    `iterations`, `variance`, `converged`; `expected`, `expected_sums`, `expected_counts` (None
+    unless asked for)."""
+
+    def __init__(self, dev, bias, expected=None):
+        self.bias, self.masked = bias, dev.balance_masked_
+        self.iterations, self.variance = dev.balance_iterations_, dev.balance_variance_
+        self.converged = dev.balance_converged_
+        self.expected = expected
+        self.expected_sums = None if expected is None else dev.expected_sums_
+        self.expected_counts = None if expected is None else dev.expected_counts_
+
+
+def balance_triples(triples, resolution, n_bins, ignore_diags=0, min_nnz=0, tol=1e-5, max_iter=200,
+                    row_sum=None, expected=False, device=None):
+    """Balance a raw map straight from its Rao-format (n, 3) triples [pos_i, pos_j, count],
+    never building the dense matrix (docs/SPEC.md 2.5.3): the ICE bias vector -- and with
+    expected=True the distance-decay expected of the balanced map -- that
+    `ContactMap.from_triples(triples, resolution, n_bins)` followed by `balance(...)` and
+    `expected()` defines.  Returns a `TriplesBalance`.  `triples` may be a `DeviceTriples`
+    (its own resolution and device are used; it stays open)."""
+    from .datatypes import _pick_device, check_balance_args
+    args = dict(zip(_BALANCE_KEYS, check_balance_args(ignore_diags, min_nnz, tol, max_iter, row_sum)))
+    n = int(n_bins)
+    if n < 0:
+        raise ValueError("n_bins must not be negative")
+    own = not isinstance(triples, DeviceTriples)
+    if own and int(resolution) <= 0:
+        raise ValueError("resolution must be positive")
+    dev = DeviceTriples(_check_triples(triples), resolution, _pick_device(device)) if own else triples
+    try:
+        bias = dev.balance(n, **args)
+        return TriplesBalance(dev, bias, dev.expected(n, bias) if expected else None)
+    finally:
+        if own:
+            dev.close()
 
 
 class HipEngine(object):
@@ -1374,8 +1495,25 @@ class StructureSolver(object):
                              % (bad[0], count.value))
         return list(self._group)
 
+    def _balance_on(self, source, n_bins, args, want_expected):
+        """fit_triples(balance=...): the bias (and the expected, or all ones) of `source`, a
+        DeviceTriples or a ContactMap; the results kept on the solver."""
+        if getattr(source, "is_triples", False):
+            bias = source.balance(n_bins, **args)
+            e = source.expected(n_bins, bias) if want_expected else None
+        else:
+            bias = source.balance(**args)
+            e = source.expected() if want_expected else None
+        self.bias_, self.balance_masked_ = bias, source.balance_masked_
+        self.balance_iterations_ = source.balance_iterations_
+        self.balance_converged_ = source.balance_converged_
+        self.balance_variance_ = source.balance_variance_
+        if want_expected:
+            self.expected_ = e
+        return bias, (numpy.ones(n_bins) if e is None else e)
+
     def fit_triples(self, triples, resolution, n_bins, KRnorm=None, KRexpected=None, init=None,
-                    complete=None):
+                    complete=None, balance=None):
         """Solve straight from a Rao-format sparse file's content, never building
         the dense matrix: `triples` is the (n, 3) array [pos_i, pos_j, count] that
         `ContactMap.__init__` reads (reference `blueberry/datatypes.pyx:100-102`),
@@ -1386,9 +1524,27 @@ class StructureSolver(object):
         count, as in the reference's scatter (pyx:115-116).
         complete='shortest_path' (see `fit`): the triples are scattered into a dense resident
         matrix (`ContactMap.from_triples`), normalised there if KR vectors are given, and that
-        map is completed and fitted."""
+        map is completed and fitted.
+        balance: None, True or a dict of `balance_triples`' arguments (ignore_diags, min_nnz,
+        tol, max_iter, row_sum, expected=False): the raw map is balanced first, on the device
+        and from the very triples the fit reads (docs/SPEC.md 2.5.3), and the fit is that of
+        `fit_triples(KRnorm=bias, KRexpected=ones)` -- with expected=True `KRexpected=e` -- bit
+        for bit.  Leaves `bias_`, `balance_masked_`, `balance_iterations_`,
+        `balance_converged_` and (expected=True) `expected_`.  It takes the place of KRnorm /
+        KRexpected; with several devices the first one balances, in a distributed job every
+        rank its own copy (the same bits); with complete='shortest_path' the dense map is
+        balanced (`ContactMap.balance`).  `triples` may be a `DeviceTriples` on this solver's
+        device (one-device fits without `complete`), which stays open."""
         _check_complete(complete)
         n = int(n_bins) + 1
+        if balance is not None:
+            if KRnorm is not None or KRexpected is not None:
+                raise ValueError("balance= computes the bias itself: it takes no KRnorm / KRexpected")
+            bal_args, bal_expected = _balance_options(balance)
+            if not isinstance(triples, DeviceTriples):
+                _check_triples(triples)
+            if complete is None and not hasattr(self._engine_factory, "set_wish_triples"):
+                raise ValueError("balance= runs on the device: this solver's engine has none")
         if KRnorm is not None and (numpy.any(numpy.asarray(KRnorm) == 0.0)
                                    or numpy.any(numpy.asarray(KRexpected)[:n_bins] == 0.0)):
             raise ZeroDivisionError("float division")      # as ContactMap.normalize
@@ -1396,7 +1552,9 @@ class StructureSolver(object):
             from .datatypes import ContactMap
             cm = ContactMap.from_triples(triples, resolution, n_bins, KRnorm=KRnorm,
                                          KRexpected=KRexpected, device=self._completion_device())
-            if KRnorm is not None or KRexpected is not None:
+            if balance is not None:
+                cm._KRnorm, cm._KRexpected = self._balance_on(cm, int(n_bins), bal_args, bal_expected)
+            if KRnorm is not None or KRexpected is not None or balance is not None:
                 cm.normalize()
             return self.fit(cm, init=init, complete=complete)
         if hasattr(self._engine_factory, "set_wish_triples"):
@@ -1413,16 +1571,22 @@ class StructureSolver(object):
                             per_device[d] = DeviceTriples(triples, resolution, d)
                     dev = per_device[group[0]]
                     dev.per_device = per_device
+                    if balance is not None:
+                        KRnorm, KRexpected = self._balance_on(dev, int(n_bins), bal_args, bal_expected)
                     return self._fit_impl(dev, n, init, KRnorm, KRexpected)
                 finally:
                     for t in per_device.values():
                         t.close()
             _, world = _dist_state(self.distributed)
-            dev = DeviceTriples(triples, resolution, self._pick_device(world))
+            own = not isinstance(triples, DeviceTriples)
+            dev = DeviceTriples(triples, resolution, self._pick_device(world)) if own else triples
             try:
+                if balance is not None:
+                    KRnorm, KRexpected = self._balance_on(dev, int(n_bins), bal_args, bal_expected)
                 return self._fit_impl(dev, n, init, KRnorm, KRexpected)
             finally:
-                dev.close()
+                if own:
+                    dev.close()
         # engines without a device (tests): bin on the host, as round 3 did
         from .datatypes import _nan_to_num
         t = _nan_to_num(triples)          # pyx:102 (no copy when every value is finite)

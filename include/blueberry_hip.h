@@ -620,6 +620,32 @@ BB_API int bb_cm_balance(bb_cm *cm, int64_t n_bins, int64_t ignore_diags, int64_
  * vector bb_cm_normalize takes. */
 BB_API int bb_cm_expected(bb_cm *cm, int64_t n_bins, const double *bias, double *sums,
                           int64_t *counts);
+/* Balancing without the dense matrix (docs/SPEC.md 2.5.3): the calls above on the matrix that
+ * resident triples DEFINE -- what bb_cm_scatter_ex would build from them over n_bins + 1 bins:
+ * nan_to_num of every value read, bin = (int)(pos / resolution), a triple names the unordered
+ * pair of its bins, the LAST triple of a pair wins, a pair that touches bin n_bins is never read
+ * -- which is never formed.  The first call for a given n_bins builds the canonical index of the
+ * stored cells on the handle (a stable sort by cell and a keep-last compaction into a CSR of the
+ * symmetric matrix: 12 B per directed entry resident, 64 B per triple plus the sort's counters
+ * while it is built; bb_triples_destroy frees it); a later call with another n_bins rebuilds it.
+ * A position that maps to a bin outside [0, n_bins]: BB_ERR_INVALID, as the scatter; device
+ * memory that cannot be had: BB_ERR_NOMEM; either way nothing half-built stays on the handle.
+ * Float64, no floating-point atomics, every sum in an order fixed by the index and n_bins alone:
+ * the same bits on every run and for every duplicate-free triple list of the same matrix
+ * (permuted, either orientation, row- or column-major).  One device: the handle's.
+ *
+ * bb_triples_balance: the arguments, the results and the refusals of bb_cm_balance.  One pass
+ * over the index per iteration (12 B per directed entry).
+ * bb_triples_expected: those of bb_cm_expected.  counts[k] is the number of pairs (i, i + k) of
+ * bins with x_i != 0 and x_{i+k} != 0, with or without a triple; sums[k] runs over the stored
+ * pairs, in a diagonal-major ordering of the index made by the first call.
+ * bb_triples_pairs: the number of distinct stored pairs i <= j < n_bins. */
+BB_API int bb_triples_balance(bb_triples *t, int64_t n_bins, int64_t ignore_diags, int64_t min_nnz,
+                              double tol, int64_t max_iter, double row_sum, double *bias,
+                              uint8_t *masked, int64_t *iterations, double *variance);
+BB_API int bb_triples_expected(bb_triples *t, int64_t n_bins, const double *bias, double *sums,
+                               int64_t *counts);
+BB_API int bb_triples_pairs(bb_triples *t, int64_t n_bins, int64_t *n_pairs);
 /* Hand the resident matrix to a solver of n_bins = d bins on the same device, device
  * to device (same meaning of kind / alpha as bb_solver_set_wish_dense).  A solver on another
  * device packs over peer access where hipDeviceCanAccessPeer allows it (enabled here); without
