@@ -53,6 +53,16 @@ struct Traits<double> {
 // 2^1000 saturates to 1 for every delta that survives the flush).
 template <typename T>
 __host__ __device__ constexpr double wish_floor() { return sizeof(T) == 4 ? 1e-30 : 1e-290; }
+// ... and the largest one: a float64 distance far above the largest finite T would become
+// +inf in the cast (1e39 as 'wish', the count 1e-120) -- a pair that counts as a constraint and
+// makes every stress non-finite.  Every distance above this value AS A DOUBLE is "no
+// constraint", like one below the floor: the doubles within half a float32 step above
+// FLT_MAX, which the cast would round down to it, included; so is +inf (generated coordinates
+// whose squared separation overflows).
+template <typename T>
+__host__ __device__ constexpr double wish_ceiling() {
+    return sizeof(T) == 4 ? 3.4028234663852886e38 : 1.7976931348623157e308;
+}
 
 // Shape of a unit (8 KiB = 8 wave-loads) and of a strip.  LPR 16-byte loads per lane
 // and matrix row, VW = 64 * VPL * LPR columns per strip, RPU = 8 / LPR matrix rows.
@@ -1659,11 +1669,12 @@ __global__ __launch_bounds__(256) void group_apply_kernel(
 // What becomes a stored wish distance -- the ONE place that says so; the sweep's 0/1 weight
 // depends on the flush (wish_floor).  flush_wish: a distance below the floor is 0 = "no
 // constraint" (fp32: the kernel's 0/1 weight needs delta >= 2^-100; anything that small is
-// below the distance clamp eps = 1e-15 anyway).  wish_from_value: an input value v of `kind` --
+// below the distance clamp eps = 1e-15 anyway), and so is one above the largest finite T
+// (wish_ceiling: the units never hold +inf).  wish_from_value: an input value v of `kind` --
 // finite and positive, else no constraint; counts -> v^(-1/alpha) -- then the flush.
 template <typename T>
 __device__ __forceinline__ T flush_wish(double v) {
-    return (T)(v < wish_floor<T>() ? 0.0 : v);
+    return (T)((v < wish_floor<T>() || v > wish_ceiling<T>()) ? 0.0 : v);
 }
 template <typename T>
 __device__ __forceinline__ T wish_from_value(double v, int kind, double neg_inv_alpha) {

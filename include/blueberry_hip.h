@@ -123,7 +123,9 @@ BB_API int bb_solver_layout(const bb_solver *s, bb_layout_info *info, int64_t *u
  * only elements [i][j] with i < j are read.  kind = BB_KIND_WISH: entries are
  * wish distances (<= 0 / non-finite = no constraint).  kind = BB_KIND_COUNTS:
  * entries are contact counts, converted on the device with
- * delta = c^(-1/alpha) (SPEC 2.1).  This is the matrix a ContactMap holds
+ * delta = c^(-1/alpha) (SPEC 2.1).  On every input route a distance below the wish
+ * floor or above the largest finite value of the solver's dtype (SPEC 2.1: 1e-30 and
+ * 3.4e38 in fp32) is no constraint.  This is the matrix a ContactMap holds
  * (reference: blueberry/datatypes.pyx:78-86 `matrix`, float64, C-contiguous).
  * Each rank uploads only its own units. */
 BB_API int bb_solver_set_wish_dense(bb_solver *s, const double *host, int64_t ld, int kind,
@@ -415,7 +417,10 @@ BB_API int bb_solver_write_exchange(bb_solver *s, const double *host, int64_t n)
  * sweep of the same kernel and layout as the gradient.  With world > 1 the
  * caller sums y over the ranks.  It is the operator of classical-MDS / spectral
  * initialisation -- the role SURVEY.md 8(f)-2 gives the reference's
- * ContactMap.eigenvector (blueberry/datatypes.pyx:216-235). */
+ * ContactMap.eigenvector (blueberry/datatypes.pyx:216-235).  A stored distance whose
+ * square overflows the solver's dtype (above 1.8e19 in fp32, 1.3e154 in fp64) makes
+ * delta^2 = +inf: the rows of that pair are then not finite, and rows next to them may be
+ * NaN as well (the sweep folds the sums of neighbouring rows in one reduction, inf * 0). */
 BB_API int bb_solver_matvec_sq(bb_solver *s, const double *x, double *y);
 
 /* Classical-MDS start computed and LEFT on the device: `n_iter` block power iterations on

@@ -11,16 +11,18 @@ import numpy
 from tests._engines import OracleEngine
 
 WISH_FLOOR = {"float32": 1e-30, "float64": 1e-290}        # SPEC 2.1
+WISH_CEILING = {"float32": float(numpy.finfo(numpy.float32).max),
+                "float64": float(numpy.finfo(numpy.float64).max)}     # SPEC 2.1
 
 
 def stored_wish(wish, dtype="float64"):
     """The delta the units hold for a kind='wish' input, widened to float64: the upper triangle,
-    rounded to the run's dtype, 0 = no constraint for anything not finite, not positive or
-    below the wish floor."""
+    0 = no constraint for anything not finite, not positive, below the wish floor or above
+    the largest finite value of the run's dtype (both compared in float64), then rounded to
+    that dtype."""
     w = numpy.triu(numpy.asarray(wish, dtype=numpy.float64), 1)
-    if dtype == "float32":
-        w = w.astype(numpy.float32).astype(numpy.float64)
-    return numpy.where(numpy.isfinite(w) & (w >= WISH_FLOOR[dtype]), w, 0.0)
+    w = numpy.where(numpy.isfinite(w) & (w >= WISH_FLOOR[dtype]) & (w <= WISH_CEILING[dtype]), w, 0.0)
+    return w.astype(dtype).astype(numpy.float64)
 
 
 def _segment_sums(values, keys, n):

@@ -17,7 +17,10 @@ TOL_EXACT = {"float64": 1e-9, "float32": 1e-3}
 def clean_wish(m, kind="wish", alpha=3.0):
     """What the packers make of an input matrix (`wish_from_value`): only the upper triangle is
     read; a value that is finite and positive is kept (counts: v ** (-1 / alpha)), everything
-    else is 0 = no constraint; zero diagonal, symmetric."""
+    else is 0 = no constraint; zero diagonal, symmetric.  (SPEC 2.1 also drops a distance below
+    the wish floor or above the largest finite value of the solver's dtype -- 1e-30 and 3.4e38
+    in fp32: tests/_input_model.wish_from_value has the rule per dtype; no map of the spectral
+    tests comes near either.)"""
     u = numpy.triu(numpy.asarray(m, dtype=numpy.float64), 1)
     ok = numpy.isfinite(u) & (u > 0.0)
     v = numpy.zeros_like(u)

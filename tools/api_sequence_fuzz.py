@@ -33,9 +33,9 @@ class Model(object):
             raise RuntimeError("not ready")
 
     def set_wish(self, w):
-        if not self.f64:                             # below the fp32 wish floor = no constraint
-            floor = float(numpy.finfo(numpy.float32).tiny)
-            w = numpy.where(w < floor, 0.0, w)
+        if not self.f64:                             # SPEC 2.1: below the fp32 wish floor or above
+            floor = float(numpy.finfo(numpy.float32).tiny)           # the largest float32 = no constraint
+            w = numpy.where((w < floor) | (w > float(numpy.finfo(numpy.float32).max)), 0.0, w)
         self.w = numpy.ascontiguousarray(w)
 
     def set_coords(self, x):

@@ -40,9 +40,11 @@ for n_bins in (3, 17, 127, 128, 129, 511, 513, 1000, 2048, 3000):
         mat = oracle.contactmap_normalize(raw, kr, ke) if kr is not None else raw
         wish = oracle.counts_to_wish(mat, 3.0)
         for dtype, tol in (("float64", 1e-12), ("float32", 1e-5)):
-            # SPEC 2.1: a wish distance below the dtype's floor is "no constraint" (an infinite
-            # count becomes the largest double, delta = 1.8e-103: a constraint in fp64 only)
-            w = numpy.where(wish < (1e-290 if dtype == "float64" else 1e-30), 0.0, wish)
+            # SPEC 2.1: a wish distance below the dtype's floor or above its largest finite value
+            # is "no constraint" (an infinite count becomes the largest double, delta = 1.8e-103:
+            # a constraint in fp64 only)
+            w = numpy.where((wish < (1e-290 if dtype == "float64" else 1e-30))
+                            | (wish > float(numpy.finfo(dtype).max)), 0.0, wish)
             X_ref, h_ref = oracle.solve(w, x0, 3, lr, f64=dtype == "float64")
             s = bb.StructureSolver(n_iter=3, lr=lr, dtype=dtype).fit_triples(tr, res, n_bins, KRnorm=kr,
                                                                              KRexpected=ke, init=x0)
