@@ -16,6 +16,8 @@ Net-new (the reference has no solver; docs/SPEC.md):
     shortest_paths                sparse map -> complete wish distances (SPEC 2.1.1)
     balance_triples, DeviceTriples
                                   ICE bias and expected straight from a pixel list (SPEC 2.5.3)
+    FitHiC, binomial_sf           Fit-Hi-C p- and q-values of a resident raw map (SPEC 2.9; the
+                                  computation of blueberry/fithic.py:76-108 without its files)
 
 All compute runs in libblueberry_hip.so (hand-written HIP for gfx950) behind
 the C-ABI of include/blueberry_hip.h.  Importing this package needs neither
@@ -27,6 +29,7 @@ from .utils import (HIGH_FITHIC_CUTOFF, LOW_FITHIC_CUTOFF, Q_LOWER_BOUND,  # noq
 from .band import count_band_regions  # noqa: F401
 from .datatypes import (ContactMap, EigenNoConvergence, FithicContactMap,  # noqa: F401
                         shortest_paths)
+from .fithic import FitHiC, binomial_sf  # noqa: F401
 from .solver import (DeviceTriples, FitScore, HipEngine, RankDeficient,  # noqa: F401
                      StructureSolver, TriplesBalance, balance_triples)
 from .stats import benjamini_hochberg, downsample  # noqa: F401

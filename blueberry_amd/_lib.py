@@ -125,6 +125,15 @@ SIGNATURES = {
                                    ctypes.POINTER(ctypes.c_uint8), p_i64, p_dbl]),
     "bb_triples_expected": (c_int, [c_void_p, c_i64, p_dbl, p_dbl, p_i64]),
     "bb_triples_pairs": (c_int, [c_void_p, c_i64, p_i64]),
+    "bb_binomial_sf": (c_int, [p_i64, c_dbl, p_dbl, p_dbl, c_i64, c_int]),
+    "bb_cm_significance": (c_int, [c_void_p, c_i64, c_i64, c_i64, p_dbl, c_dbl, c_dbl, p_dbl, c_dbl,
+                                   ctypes.POINTER(c_void_p)]),
+    "bb_triples_significance": (c_int, [c_void_p, c_i64, c_i64, c_i64, p_dbl, c_dbl, c_dbl, p_dbl,
+                                        c_dbl, ctypes.POINTER(c_void_p)]),
+    "bb_sig_size": (c_int, [c_void_p, p_i64, p_i64]),
+    "bb_sig_read": (c_int, [c_void_p, p_i32, p_i32, p_dbl, p_dbl]),
+    "bb_sig_timing": (c_int, [c_void_p, p_dbl, p_dbl]),
+    "bb_sig_destroy": (c_int, [c_void_p]),
     "bb_solver_set_wish_from_cm": (c_int, [c_void_p, c_void_p, c_int, c_dbl]),
     "bb_solver_set_wish_from_cm_block": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_dbl]),
     "bb_solver_set_maps": (c_int, [c_void_p, c_int, p_i64, p_dbl]),

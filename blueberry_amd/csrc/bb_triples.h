@@ -34,6 +34,7 @@ __device__ __forceinline__ bool triple_bins(double pj, double pk, double resolut
 // A list of (other index, value) entries grouped by an owner index, CSR style, and the cut of
 // every owner's entries into segments of kTbSeg for the segmented sum (bb_triples_balance.hip):
 // segment w belongs to owner seg_owner[w] and is the (w - seg_ptr[owner])-th of its entries.
+constexpr int kTbSeg = 1024;   // entries of one owner (row or diagonal) that one wave works on
 struct SegmentedList {
     int64_t n_entries = 0, n_seg = 0;
     DevBuf ptr;        // int64, owners + 1
@@ -65,3 +66,9 @@ struct bb_triples {
     bb::TriplesIndex index;             // (bb_triples_balance.hip; freed with the handle)
     const double *from(int64_t t0) const { return d.as<double>() + t0 * (st == 3 ? 3 : 1); }
 };
+
+namespace bb {
+// The handle's index for n_bins, built if it is not there (bb_triples_balance.hip); `who` names
+// the entry point in an error.
+int triples_ensure_index(bb_triples *t, int64_t n_bins, const char *who);
+}  // namespace bb

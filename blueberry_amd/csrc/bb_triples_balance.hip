@@ -58,8 +58,7 @@ using bb::kCellValue;
 using bb::SegmentedList;
 using bb::TriplesIndex;
 
-// entries of one owner (row or diagonal) that one wave sums
-constexpr int kTbSeg = 1024;
+using bb::kTbSeg;   // entries of one owner (row or diagonal) that one wave sums
 // the two further rules of the diagonal sums: weights x_row x_{row + k}, or all weights 1
 enum { kDiagWeighted = 3, kDiagPlain = 4 };
 
@@ -445,8 +444,10 @@ unsigned bits_below(u64 bound) {
     return b;
 }
 
+}  // namespace
+
 // The handle's index for n_bins, built if it is not there.
-int ensure_index(bb_triples *t, int64_t n_bins, const char *who) {
+int bb::triples_ensure_index(bb_triples *t, int64_t n_bins, const char *who) {
     BB_REQUIRE(t != nullptr, std::string(who) + ": triples is NULL");
     BB_REQUIRE(n_bins >= 0 && n_bins < 2147483647, std::string(who) + ": n_bins is out of range");
     BB_TRY(bb::enter_device(t->device));
@@ -481,6 +482,8 @@ int ensure_index(bb_triples *t, int64_t n_bins, const char *who) {
     t->index = std::move(ix);
     return BB_OK;
 }
+
+namespace {
 
 // The diagonal-major ordering of the stored upper entries, made on first use.
 int ensure_diags(bb_triples *t, const char *who) {
@@ -526,7 +529,7 @@ extern "C" {
 
 int bb_triples_pairs(bb_triples *t, int64_t n_bins, int64_t *n_pairs) {
     BB_REQUIRE(n_pairs != nullptr, "bb_triples_pairs: NULL argument");
-    BB_TRY(ensure_index(t, n_bins, "bb_triples_pairs"));
+    BB_TRY(bb::triples_ensure_index(t, n_bins, "bb_triples_pairs"));
     *n_pairs = t->index.n_pairs;
     return BB_OK;
 }
@@ -537,7 +540,7 @@ int bb_triples_balance(bb_triples *t, int64_t n_bins, int64_t ignore_diags, int6
     BB_REQUIRE(t != nullptr, "bb_triples_balance: triples is NULL");
     BB_TRY(bb::balance_check_args("bb_triples_balance", n_bins, ignore_diags, min_nnz, tol, max_iter,
                                   row_sum, bias, masked));
-    BB_TRY(ensure_index(t, n_bins, "bb_triples_balance"));
+    BB_TRY(bb::triples_ensure_index(t, n_bins, "bb_triples_balance"));
     const int64_t n = n_bins;
     ignore_diags = std::min(ignore_diags, n);         // (beyond n - 1 nothing is counted anyway)
     const SegmentedList &rows = t->index.rows;
@@ -557,7 +560,7 @@ int bb_triples_balance(bb_triples *t, int64_t n_bins, int64_t ignore_diags, int6
 int bb_triples_expected(bb_triples *t, int64_t n_bins, const double *bias, double *sums, int64_t *counts) {
     BB_REQUIRE(t != nullptr, "bb_triples_expected: triples is NULL");
     BB_REQUIRE(sums != nullptr && counts != nullptr, "bb_triples_expected: NULL argument");
-    BB_TRY(ensure_index(t, n_bins, "bb_triples_expected"));
+    BB_TRY(bb::triples_ensure_index(t, n_bins, "bb_triples_expected"));
     const int64_t n = n_bins;
     if (n == 0) return BB_OK;
     BB_TRY(ensure_diags(t, "bb_triples_expected"));

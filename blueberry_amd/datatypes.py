@@ -573,6 +573,14 @@ class ContactMap(object):
             self._divide(numpy.ones(n), self._KRexpected)
         return self._KRexpected
 
+    def significance(self, **kwargs):
+        """The Fit-Hi-C p- and q-values of this raw map's contacts as a `FithicContactMap`
+        (docs/SPEC.md 2.9): `FitHiC(resolution=self.resolution, **kwargs).fit_transform(self)`,
+        with `biases` ('auto': the map's KRnorm, e.g. what `balance()` left) passed on to
+        `fit_transform`.  The map stays as it is and stays resident."""
+        from .fithic import _significance
+        return _significance(self, None, kwargs)
+
     def correlation(self):
         """Convert the map to a correlation map, in place (pyx:173-188:
         `numpy.corrcoef(matrix)`), on the resident matrix: rows centred, Gram matrix on

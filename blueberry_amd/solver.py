@@ -122,6 +122,13 @@ class DeviceTriples(object):
         self.expected_sums_, self.expected_counts_ = sums, counts
         return expected_from_sums(sums, counts)
 
+    def significance(self, map_bins, **kwargs):
+        """The Fit-Hi-C p- and q-values of the map the triples define over bins 0 .. map_bins - 1
+        (`ContactMap.significance`; docs/SPEC.md 2.9), bit for bit what `ContactMap.from_triples(
+        ...).significance(...)` gives, without that matrix.  One chromosome."""
+        from .fithic import _significance
+        return _significance(self, int(map_bins), kwargs)
+
     def close(self):
         if self._h:
             self._lib.bb_triples_destroy(self._h)

@@ -651,6 +651,51 @@ BB_API int bb_triples_balance(bb_triples *t, int64_t n_bins, int64_t ignore_diag
 BB_API int bb_triples_expected(bb_triples *t, int64_t n_bins, const double *bias, double *sums,
                                int64_t *counts);
 BB_API int bb_triples_pairs(bb_triples *t, int64_t n_bins, int64_t *n_pairs);
+/* The Fit-Hi-C significance call on a resident map (docs/SPEC.md 2.9; reference:
+ * blueberry/fithic.py:413-435, one text line at a time through scipy.special.bdtrc).
+ *
+ * bb_binomial_sf: out[i] = P(X >= k[i]), X ~ Binomial(n, p[i]), for m host values; n a whole
+ * number in [0, 2^53].  Float64: Loader's saddle-point pmf at the first term, then the ratio
+ * recurrence of the tail (upward above the mode, else the lower tail and 1 - sum), within 1.2e-13
+ * of an 80-digit sum over the table on which scipy's bdtrc is off by up to 1.7e-3
+ * (docs/MEASUREMENTS.md).  k <= 0: 1; k > n: 0; p outside
+ * [0, 1]: NaN.  An element with 0 < p < 1 and n p > 1,048,576 -- the limit the sum's cap of terms
+ * was derived for -- is BB_ERR_INVALID, nothing written; a sum that reaches the cap all the same
+ * is BB_ERR_STATE, nothing written.
+ *
+ * bb_cm_significance: over the leading n_bins x n_bins block of the resident matrix (d must be
+ * n_bins + 1; row and column n_bins are never read; the matrix stays as it is), the cells (i, j),
+ * i <= j, k_lo <= j - i <= k_hi (0 <= k_lo <= k_hi < n_bins), are the counted cells.  One that is
+ * negative, not finite or not a whole number: BB_ERR_INVALID "significance needs raw counts".
+ * A counted cell is LISTED if its count is >= 1, bias_lo <= bias[i], bias[j] <= bias_hi (a NaN
+ * bias fails; pass -inf / +inf for no bounds) and its prior pi = prior_by_distance[j - i] *
+ * bias[i] * bias[j] lies in [0, 1]; bias and prior_by_distance hold n_bins doubles.  The result is
+ * the list in canonical order -- row-major, i ascending, then j -- with p = P(Binomial(n_total,
+ * pi) >= count) for every listed cell, made by a count, an exclusive scan and a write (no atomic
+ * cursor): the same bits on every run.  A listed cell with pi < 1 and n_total * pi > 1,048,576:
+ * BB_ERR_INVALID.  The matrix is read twice.
+ * bb_triples_significance: the same on the matrix resident triples define (bb_triples_balance's
+ * rules; the canonical index is built on the handle if it is not there, and stays): the same
+ * list, bit for bit, as bb_cm_significance on the scattered matrix.  One chromosome: a list with
+ * chromosome boundaries is out of scope.
+ * The results live in a bb_sig, which owns its device memory; *out is NULL after an error.
+ *   bb_sig_size    the number of listed cells; terms (may be NULL): pmf values summed over all
+ *   bb_sig_read    row, col (int32), count, p (float64) to the host, bb_sig_size values each
+ *   bb_sig_timing  HIP-event times (ms) of the call: count + scan + write, and the p-value pass
+ *   bb_sig_destroy frees it (NULL is fine) */
+typedef struct bb_sig bb_sig;
+BB_API int bb_binomial_sf(const int64_t *k, double n, const double *p, double *out, int64_t m,
+                          int device);
+BB_API int bb_cm_significance(bb_cm *cm, int64_t n_bins, int64_t k_lo, int64_t k_hi,
+                              const double *bias, double bias_lo, double bias_hi,
+                              const double *prior_by_distance, double n_total, bb_sig **out);
+BB_API int bb_triples_significance(bb_triples *t, int64_t n_bins, int64_t k_lo, int64_t k_hi,
+                                   const double *bias, double bias_lo, double bias_hi,
+                                   const double *prior_by_distance, double n_total, bb_sig **out);
+BB_API int bb_sig_size(const bb_sig *s, int64_t *n_listed, int64_t *terms);
+BB_API int bb_sig_read(const bb_sig *s, int32_t *row, int32_t *col, double *count, double *p);
+BB_API int bb_sig_timing(const bb_sig *s, double *list_ms, double *p_ms);
+BB_API int bb_sig_destroy(bb_sig *s);
 /* Hand the resident matrix to a solver of n_bins = d bins on the same device, device
  * to device (same meaning of kind / alpha as bb_solver_set_wish_dense).  A solver on another
  * device packs over peer access where hipDeviceCanAccessPeer allows it (enabled here); without
