@@ -101,6 +101,7 @@ SIGNATURES = {
     "bb_solver_measure_stream_read": (c_int, [c_void_p, c_int, p_dbl]),
     "bb_solver_iteration_path": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "bb_solver_traffic": (c_int, [c_void_p, p_i64, p_i64]),
+    "bb_solver_stream_info": (c_int, [c_void_p, p_i64, p_i64, p_i64, p_i64]),
     "bb_cm_create": (c_int, [ctypes.POINTER(c_void_p), c_i64, c_int]),
     "bb_cm_destroy": (c_int, [c_void_p]),
     "bb_cm_dim": (c_int, [c_void_p, p_i64]),

@@ -132,6 +132,14 @@ struct bb_solver {
     int ro_blocks = 0, ro_wpr = 1;  // workgroups holding rows; waves per row (1, 2, 4)
     int64_t ro_launches = 0;       // row-owner launches so far (parity of the ping-pong)
 
+    // the 24-bit stream of the fp32 sweep (SPEC 3.7): derived from d_units, rebuilt by
+    // ensure_pk24() before the first sweep after a writer of d_units (pk_stale)
+    int pk_mode = -1;              // BB_PACK24 at create: 0 never, 1 whenever a unit packs, else the rule
+    int64_t pk_min_run = 64;       // BB_PACK24_MIN_RUN at create: shortest run of units stored packed
+    bool pk_stale = true, pk_valid = false;
+    bb::DevBuf pk_stream, pk_table;   // outside the arena: the solver runs raw without them
+    int64_t pk_packed = 0, pk_bytes = 0, pk_switches = 0;
+
     bool timing = false;
     int timing_stride = 1;      // events on every timing_stride-th iteration
     int64_t timing_iter = 0;    // iterations seen since timing was (re-)enabled
@@ -145,6 +153,9 @@ namespace {
 void comm_release(bb_solver *s, bool destroy);   // the communicator cache, further down
 
 constexpr int64_t kHistCap = 1 << 20;
+// 24-bit stream: a packable unit is stored packed only inside a run of at least this many
+// (docs/MEASUREMENTS.md, "fp32 sweep: the 24-bit stream")
+constexpr int64_t kPk24MinRun = 64;
 constexpr size_t kMaxTimedLaunches = 4096;
 
 // The kind / alpha rule of every set_wish_* entry point, in who's name.
@@ -263,6 +274,14 @@ int build_indices(bb_solver *s) {
     // (N=8,000 / 10,000: kernel -8 %, step -3.5 / -6 %; equal at N=12,000 = 288 MB;
     // non-temporal 3-4 % better at N=17,700; profiles/archive/r02_nt_ab.txt).
     s->nontemporal = s->n_local * bb::kUnitBytes > ((int64_t)240 << 20);
+    {
+        // the 24-bit stream of the fp32 sweep (ensure_pk24): BB_PACK24=0 never, =1 whenever a
+        // unit packs; BB_PACK24_MIN_RUN: the shortest run of packable units stored packed
+        const char *e = getenv("BB_PACK24");
+        s->pk_mode = e ? (atoi(e) != 0 ? 1 : 0) : -1;
+        const char *r = getenv("BB_PACK24_MIN_RUN");
+        s->pk_min_run = r ? std::max<int64_t>(1, atoll(r)) : kPk24MinRun;
+    }
     // wave w owns the contiguous chunk [w*q + min(w, r), +q (+1 if w < r)), q = n_local / nw,
     // r = n_local % nw: the kernels compute it the same way (no table to load)
     s->chunk_q = (int)(s->n_local / nw);
@@ -458,13 +477,107 @@ decltype(auto) with_int(int v, F &&f) {
     else return v == V ? f(std::integral_constant<int, V>{}) : with_int<Rest...>(v, f);
 }
 
+// The 24-bit stream pays only where it takes bytes off the sweep: its kernel carries a second
+// copy of the unit body and drains its window at every change of format, and a packed unit
+// costs 48 more VALU instructions than a raw one.  Below a saving of an eighth of the raw bytes
+// (all a sparse raw map with zeros in most units can offer is 0) the solver keeps reading
+// d_units with the kernel it always had.
+constexpr int64_t kPk24MinSavingDiv = 8;   // stream bytes <= raw bytes * (1 - 1/8)
+constexpr int64_t kPk24PackedKiB = 6, kPk24RawKiB = bb::kUnitBytes / 1024;
+
+// The stream up to date with d_units (SPEC 3.7), or pk_valid = false: the sweep then reads
+// d_units.  fp32 only; by default only where the sweep streams from HBM.  One pass for the
+// smallest and largest word of every unit, the run rule and the offsets on the host (one D2H
+// of 8 bytes per unit, once per map), one pass that writes the stream.
+int ensure_pk24(bb_solver *s) {
+    if (!s->pk_stale) return BB_OK;
+    s->pk_stale = false, s->pk_valid = false;
+    s->pk_packed = s->pk_bytes = s->pk_switches = 0;
+    const int64_t n = s->n_local;
+    // Never where ranks share a GPU (a rehearsal: peer_ranks_on_gpu > 1).  The packed sweep takes
+    // the registers of the one or two waves per SIMD it runs with; beside the waiting receive
+    // kernels of the other ranks its workgroups find no CU to start on, and every rank waits for
+    // a partial nobody can compute (tools/world8_rehearsal.py ran into its time limit that way).
+    const bool want = s->dtype == BB_F32 && n > 0 && s->pk_mode != 0 && s->peer_ranks_on_gpu <= 1 &&
+                      (s->pk_mode == 1 || s->nontemporal);
+    if (!want) {
+        s->pk_stream.reset(), s->pk_table.reset();
+        return BB_OK;
+    }
+    bb::DevBuf d_minmax;
+    if (d_minmax.alloc((size_t)n * sizeof(uint2)) != hipSuccess) return BB_OK;   // raw: no error
+    BB_HIP_CHECK(bb::launch(pk24_minmax_kernel, dim3((unsigned)n), dim3(256), 0, s->stream,
+                            (const uint4 *)s->d_units, d_minmax.as<uint2>()));
+    std::vector<uint2> mm((size_t)n);
+    BB_HIP_CHECK(hipMemcpyAsync(mm.data(), d_minmax.p, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost,
+                                s->stream));
+    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
+    // packable: max - min < 2^24; stored packed: inside a run of >= pk_min_run packable units
+    std::vector<int4> table((size_t)n);
+    int64_t kib = 0, packed = 0, switches = 0;
+    for (int64_t a = 0; a < n;) {
+        const bool pk = mm[(size_t)a].y - mm[(size_t)a].x < (1u << 24);
+        int64_t b = a + 1;
+        while (b < n && (mm[(size_t)b].y - mm[(size_t)b].x < (1u << 24)) == pk) ++b;
+        const bool store_packed = pk && b - a >= s->pk_min_run;
+        for (int64_t u = a; u < b; ++u) {
+            table[(size_t)u] = make_int4(s->udesc[(size_t)u].x, s->udesc[(size_t)u].y,
+                                         (int)((uint32_t)kib | (store_packed ? 0x80000000u : 0u)),
+                                         store_packed ? (int)mm[(size_t)u].x : 0);
+            kib += store_packed ? kPk24PackedKiB : kPk24RawKiB;
+        }
+        if (store_packed) packed += b - a;
+        a = b;
+    }
+    for (int64_t u = 1; u < n; ++u) switches += (table[(size_t)u].z < 0) != (table[(size_t)u - 1].z < 0);
+    const int64_t raw_kib = n * kPk24RawKiB;
+    const bool pays = s->pk_mode == 1 ? packed > 0 : kib * kPk24MinSavingDiv <= raw_kib * (kPk24MinSavingDiv - 1);
+    if (!pays || kib >= ((int64_t)1 << 31)) {
+        s->pk_stream.reset(), s->pk_table.reset();
+        return BB_OK;
+    }
+    // 8 KiB behind the last unit: no refill address a body can form lies outside
+    if (s->pk_stream.reserve((size_t)(kib + kPk24RawKiB) * 1024) != hipSuccess ||
+        s->pk_table.reserve((size_t)n * sizeof(int4)) != hipSuccess) {
+        s->pk_stream.reset(), s->pk_table.reset();
+        return BB_OK;                                                              // raw: no error
+    }
+    BB_HIP_CHECK(hipMemcpyAsync(s->pk_table.p, table.data(), (size_t)n * sizeof(int4), hipMemcpyHostToDevice,
+                                s->stream));
+    BB_HIP_CHECK(hipMemsetAsync(s->pk_stream.as<char>() + kib * 1024, 0, (size_t)kPk24RawKiB * 1024, s->stream));
+    BB_HIP_CHECK(bb::launch(pk24_pack_kernel, dim3((unsigned)n), dim3(256), 0, s->stream,
+                            (const uint4 *)s->d_units, s->pk_table.as<const int4>(), s->pk_stream.as<uint4>()));
+    BB_HIP_CHECK(hipStreamSynchronize(s->stream));   // the host table dies with this scope
+    s->pk_valid = true;
+    s->pk_packed = packed, s->pk_bytes = kib * 1024, s->pk_switches = switches;
+    return BB_OK;
+}
+
 // One instantiation of the sweep.  Its dynamic-LDS ceiling (row-sum parking and the column
-// partials) is raised once: one bit of defer_attr_done per (WPB, NT, OP).
+// partials) is raised once: one bit of defer_attr_done per (WPB, NT, OP, PK).  THE place that
+// takes the packed instantiation (PK: the fp32 stress sweep reading the 24-bit stream) when the
+// stream is valid -- for iterate, grad, the peer and RCCL paths and the stress-only sweep alike.
+// The matvec and the weighted sweeps keep reading d_units.
+template <bool NT, int OP, int WPB, bool PK, typename T, bool W>
+int launch_sweep_pk(LayoutTag<T, W>, bb_solver *s, const void *x_in);
+
 template <bool NT, int OP, int WPB, typename T, bool W>
-int launch_sweep(LayoutTag<T, W>, bb_solver *s, const void *x_in) {
-    const auto kern = stress_grad_kernel<T, W, NT, OP, WPB>;
+int launch_sweep(LayoutTag<T, W> lay, bb_solver *s, const void *x_in) {
+    if constexpr (sizeof(T) == 4 && OP == kOpStress) {
+        BB_TRY(ensure_pk24(s));
+        if (s->pk_valid) return launch_sweep_pk<NT, OP, WPB, true>(lay, s, x_in);
+    }
+    return launch_sweep_pk<NT, OP, WPB, false>(lay, s, x_in);
+}
+
+template <bool NT, int OP, int WPB, bool PK, typename T, bool W>
+int launch_sweep_pk(LayoutTag<T, W>, bb_solver *s, const void *x_in) {
+    const auto kern = [] {
+        if constexpr (PK) return stream24_grad_kernel<T, W, NT, OP, WPB>;
+        else return stress_grad_kernel<T, W, NT, OP, WPB>;
+    }();
     constexpr unsigned bit = 1u << ((WPB == 8 ? 4 : 0) + (NT ? 2 : 0) + (OP == kOpMatvec2 ? 1 : 0) +
-                                    (OP == kOpStressW1 ? 8 : 0) + (OP == kOpStressW2 ? 16 : 0));
+                                    (OP == kOpStressW1 ? 8 : 0) + (OP == kOpStressW2 ? 16 : 0) + (PK ? 24 : 0));
     if (s->defer_lds_bytes > 0 && !(s->defer_attr_done & bit)) {
         BB_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)s->defer_lds_bytes));
@@ -475,7 +588,8 @@ int launch_sweep(LayoutTag<T, W>, bb_solver *s, const void *x_in) {
                  (s->u_begin - s->t_first * s->L.units_per_tile) * (3 * s->L.rows_per_unit);
     T *colpart = (T *)s->d_part + s->rowpart_elems;
     BB_HIP_CHECK(bb::launch(kern, dim3(s->n_waves / s->wpb), dim3(64 * s->wpb), (size_t)s->defer_lds_bytes,
-                            s->stream, (const T *)s->d_units, (const T *)x_in, s->d_udesc, s->chunk_q,
+                            s->stream, PK ? s->pk_stream.as<const T>() : (const T *)s->d_units,
+                            (const T *)x_in, PK ? s->pk_table.as<const int2>() : s->d_udesc, s->chunk_q,
                             s->chunk_r, s->d_wave_slots, rowpart, colpart, s->d_stresspart,
                             s->defer_cap_units, s->lds_wave_floats, s->dense_u0, s->d_stress_slot));
     return BB_OK;
@@ -767,6 +881,7 @@ int launch_row_owner(bb_solver *s, double lr, bool fold_prev, bool update) {
 int inputs_done(bb_solver *s) {
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));
     BB_TRY(refresh_full(s));
+    s->pk_stale = true;   // (every writer has said so before its first write; once more for a new one)
     s->have_wish = true;
     return BB_OK;
 }
@@ -775,6 +890,7 @@ int inputs_done(bb_solver *s) {
 // (the whole map: off = 0, d = n_bins).
 int pack_from_cm(bb_solver *s, const double *m, int64_t d, int64_t off, int kind, double alpha) {
     BB_TRY(bb::enter_device(s->device));
+    s->pk_stale = true;   // d_units is about to be written: whatever happens, the 24-bit stream is not of it
     if (s->n_local > 0)
         BB_TRY(by_layout(s, [&](auto lay) -> int {
             using T = typename decltype(lay)::T;
@@ -790,6 +906,7 @@ int pack_from_cm(bb_solver *s, const double *m, int64_t d, int64_t off, int kind
 int set_wish_dense(bb_solver *s, const double *host, int64_t ld, int kind, double alpha, int64_t off,
                    int64_t n_sub) {
     BB_TRY(bb::enter_device(s->device));
+    s->pk_stale = true;   // d_units is about to be written: whatever happens, the 24-bit stream is not of it
     BB_TRY(by_layout(s, [&](auto lay) { return set_wish_dense_t(lay, s, host, ld, kind, alpha, off, n_sub); }));
     return inputs_done(s);
 }
@@ -818,6 +935,7 @@ int scatter_entries(bb_solver *s, const char *who, int64_t n, int64_t chunk, int
         BB_TRY(hip(hipMemcpyAsync(bkr.p, KRnorm, (size_t)s->L.n_bins * 8, hipMemcpyHostToDevice, st)));
         BB_TRY(hip(hipMemcpyAsync(bke.p, KRexpected, (size_t)s->L.n_bins * 8, hipMemcpyHostToDevice, st)));
     }
+    s->pk_stale = true;   // d_units is about to be written: whatever happens, the 24-bit stream is not of it
     BB_TRY(hip(hipMemsetAsync(bbad.p, 0, sizeof(int), st)));
     BB_TRY(hip(hipMemsetAsync(s->d_units, 0, (size_t)std::max<int64_t>(s->n_local, 1) * bb::kUnitBytes, st)));
     for (int64_t k0 = 0; k0 < n; k0 += chunk) {
@@ -1082,6 +1200,7 @@ int bb_solver_set_maps(bb_solver *s, int n_maps, const int64_t *bin_begin, const
     BB_HIP_CHECK(hipMemcpy(s->d_map_ptr.p, ptr.data(), ptr.size() * sizeof(int), hipMemcpyHostToDevice));
     BB_HIP_CHECK(hipMemcpy(s->d_map_idx.p, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
     // (a map that is never set carries no constraint)
+    s->pk_stale = true;   // d_units is about to be written: whatever happens, the 24-bit stream is not of it
     BB_HIP_CHECK(hipMemsetAsync(s->d_units, 0, (size_t)std::max<int64_t>(s->n_local, 1) * bb::kUnitBytes,
                                 s->stream));
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));
@@ -1399,6 +1518,7 @@ int bb_solver_set_wish_from_coords(bb_solver *s, const double *xstar) {
     BB_REQUIRE(s != nullptr && xstar != nullptr, "bb_solver_set_wish_from_coords: NULL argument");
     BB_TRY(bb::enter_device(s->device));
     BB_HIP_CHECK(upload_padded(s, s->d_f64_tmp, xstar, s->stream));
+    s->pk_stale = true;   // d_units is about to be written: whatever happens, the 24-bit stream is not of it
     if (s->n_local > 0)
         BB_TRY(by_layout(s, [&](auto lay) -> int {
             using T = typename decltype(lay)::T;
@@ -1920,6 +2040,7 @@ int bb_solver_peer_connect(bb_solver *s, const void *handles) {
         const char *env = getenv("BB_PEER_FUSED");
         s->peer_fused = env ? atoi(env) != 0 : most_on_one_gpu == 1;
         s->peer_ranks_on_gpu = most_on_one_gpu;
+        if (most_on_one_gpu > 1) s->pk_stale = true;   // a stream built before this goes (ensure_pk24)
     }
     s->peer_connected = true;
     BB_HIP_CHECK(hipDeviceSynchronize());
@@ -2238,7 +2359,14 @@ int bb_solver_measure_stream_read(bb_solver *s, int launches, double *ms_avg) {
     bb::Event e0, e1;
     BB_HIP_CHECK(e0.create());
     BB_HIP_CHECK(e1.create());
+    if (s->dtype == BB_F32) BB_TRY(ensure_pk24(s));
     auto launch = [&]() {
+        // what the sweep reads: the 24-bit stream when it is in use
+        if (s->pk_valid)
+            return bb::launch(s->nontemporal ? stream_read_pk24_kernel<true> : stream_read_pk24_kernel<false>,
+                              dim3(s->n_waves / 4), dim3(256), 0, s->stream, s->pk_stream.as<const float4>(),
+                              s->pk_table.as<const int4>(), (int)s->n_local, (int)(s->pk_bytes / 1024),
+                              s->chunk_q, s->chunk_r, (float *)s->d_f64_tmp);
         return bb::launch(s->nontemporal ? stream_read_kernel<true> : stream_read_kernel<false>,
                           dim3(s->n_waves / 4), dim3(256), 0, s->stream,
                           (const float4 *)s->d_units, s->chunk_q, s->chunk_r,
@@ -2255,6 +2383,20 @@ int bb_solver_measure_stream_read(bb_solver *s, int launches, double *ms_avg) {
     return BB_OK;
 }
 
+int bb_solver_stream_info(bb_solver *s, int64_t *packed_units, int64_t *raw_units, int64_t *stream_bytes,
+                          int64_t *format_switches) {
+    BB_REQUIRE(s != nullptr, "bb_solver_stream_info: solver is NULL");
+    if (!s->have_wish)
+        return bb::fail(BB_ERR_STATE, "bb_solver_stream_info: no wish distances set");
+    BB_TRY(bb::enter_device(s->device));
+    BB_TRY(ensure_pk24(s));
+    if (packed_units) *packed_units = s->pk_valid ? s->pk_packed : 0;
+    if (raw_units) *raw_units = s->pk_valid ? s->n_local - s->pk_packed : s->n_local;
+    if (stream_bytes) *stream_bytes = s->pk_valid ? s->pk_bytes : 0;
+    if (format_switches) *format_switches = s->pk_valid ? s->pk_switches : 0;
+    return BB_OK;
+}
+
 int bb_solver_iteration_path(const bb_solver *s, int *row_owner, int *waves_per_row) {
     BB_REQUIRE(s != nullptr, "bb_solver_iteration_path: solver is NULL");
     if (row_owner) *row_owner = s->row_owner ? 1 : 0;
@@ -2262,9 +2404,14 @@ int bb_solver_iteration_path(const bb_solver *s, int *row_owner, int *waves_per_
     return BB_OK;
 }
 
-int bb_solver_traffic(const bb_solver *s, int64_t *unit_bytes, int64_t *pairs_dense) {
+int bb_solver_traffic(bb_solver *s, int64_t *unit_bytes, int64_t *pairs_dense) {
     BB_REQUIRE(s != nullptr, "bb_solver_traffic: solver is NULL");
-    if (unit_bytes) *unit_bytes = s->n_local * bb::kUnitBytes;
+    // the bytes a stress sweep reads: those of the 24-bit stream when it is in use
+    if (s->have_wish && s->dtype == BB_F32) {
+        BB_TRY(bb::enter_device(s->device));
+        BB_TRY(ensure_pk24(s));
+    }
+    if (unit_bytes) *unit_bytes = s->pk_valid && !s->pk_stale ? s->pk_bytes : s->n_local * bb::kUnitBytes;
     if (pairs_dense) *pairs_dense = s->L.n_bins * (s->L.n_bins - 1) / 2;
     return BB_OK;
 }

@@ -584,11 +584,55 @@ __device__ __forceinline__ void pair_step2(f32x2 delta, f32x2 xi, f32x2 yi, f32x
 // profiles/r03_mfma_rowsum_ab.txt).  At two waves per SIMD the chip runs this kernel at
 // 1.75-1.83 GHz (power) and the SIMD's VALU is then busy most of a unit's time, so an
 // instruction less per unit is time (docs/MEASUREMENTS.md, machine code against the parent).
-template <bool NT, int OP, typename WIN>
+//
+// PK: the unit is a PACKED unit of the 24-bit stream (SPEC 3.7), 6 wave-loads.  Dword c of
+// load L = 2r + k (rows 0..2) carries the code of the pair (r, k, c) in its low 24 bits and one
+// byte of a row-3 code on top: the codes of row 3, load 0 lie on loads 0, 1, 2 (bytes 0, 1, 2),
+// those of row 3, load 1 on loads 4, 5, 3.  So the two loads of row 0 give up their top bytes
+// together and are refilled as in a raw unit, as are those of row 2; only load 3 waits one row
+// for its refill.  Decode: one v_mad_u32_u24 per pair of rows 0..2 (mask to 24 bits, add the
+// unit's base from a scalar register), two v_perm_b32 and one add per pair of row 3 -- 48 per
+// unit, and 4 moves.  The pair math, its order and every sum are those of the raw unit: the
+// bits are the same.
+template <bool ROW3>
+__device__ __forceinline__ void pk24_decode(float &word, unsigned base) {
+    // volatile: memory operations keep their side of such a statement, so the refills stay in
+    // the row that issues them.  Their only reader is the NEXT trip of the loop, and left alone
+    // hipcc decodes the whole unit up front (waiting for all six loads at once) and sinks all
+    // six refills to the end of the body: the window then stands empty for most of a unit.
+    // That hipcc keeps plain loads on their side of these statements is what it does, not what
+    // the language promises, and no test fails if it stops: after a compiler update rerun
+    // `tools/vmcnt_pattern.sh stream24_grad_kernelIfLb1ELb1ELi0ELi8` and look for the packed
+    // body's waits 5 6 5 4 (docs/MEASUREMENTS.md, "the 24-bit stream").
+    if constexpr (ROW3) {   // the collected code of a row-3 pair: its top byte is 0
+        asm volatile("v_add_u32 %0, %0, %1" : "+v"(word) : "s"(base));
+    } else {
+        asm volatile("v_mad_u32_u24 %0, %0, 1, %1" : "+v"(word) : "s"(base));
+    }
+}
+template <bool ROW3>
+__device__ __forceinline__ void pk24_decode(float4 &w, unsigned base) {
+    pk24_decode<ROW3>(w.x, base); pk24_decode<ROW3>(w.y, base);
+    pk24_decode<ROW3>(w.z, base); pk24_decode<ROW3>(w.w, base);
+}
+constexpr unsigned kPk24SelPair = 0x0c0c0703u;   // {0, 0, top of S0, top of S1}
+constexpr unsigned kPk24SelThird = 0x0c070100u;  // {0, top of S0, byte 1 of S1, byte 0 of S1}
+__device__ __forceinline__ float pk24_tops(float hi, float lo, unsigned sel) {
+    float v;   // (volatile for the reason given at pk24_decode: it needs its row's loads, no others)
+    asm volatile("v_perm_b32 %0, %1, %2, %3" : "=v"(v) : "v"(hi), "v"(lo), "s"(sel));
+    return v;
+}
+__device__ __forceinline__ float4 pk24_tops(float4 hi, float4 lo, unsigned sel) {
+    return make_float4(pk24_tops(hi.x, lo.x, sel), pk24_tops(hi.y, lo.y, sel),
+                       pk24_tops(hi.z, lo.z, sel), pk24_tops(hi.w, lo.w, sel));
+}
+
+template <bool NT, int OP, bool PK = false, typename WIN>
 __device__ __forceinline__ void process_unit_f32(float4 (&d)[8], const float (&xrow)[12],
                                                  const WIN &next, StripF32 &st,
                                                  double &stress, __amdgpu_buffer_rsrc_t row_rsrc,
-                                                 unsigned row_voff, int stage_idx) {
+                                                 unsigned row_voff, int stage_idx,
+                                                 unsigned base = 0u) {
     extern __shared__ __attribute__((aligned(16))) float row_lds[];
     f32x2 s2 = {0.f, 0.f};
     float g[12], h[6], m[3];  // the unit's 12 row sums on their way through the tree
@@ -597,6 +641,35 @@ __device__ __forceinline__ void process_unit_f32(float4 (&d)[8], const float (&x
         const float xs = xrow[3 * r], ys = xrow[3 * r + 1], zs = xrow[3 * r + 2];
         const f32x2 xi = {xs, xs}, yi = {ys, ys}, zi = {zs, zs};
         f32x2 rx, ry, rz;  // row-side sums of the row's 8 pairs
+        if constexpr (PK) {
+            // The codes become distances IN the window's registers, and d[6], d[7] -- which a
+            // packed unit has no loads for -- collect the codes of row 3: the body holds what
+            // the raw one holds (alone in the kernel it takes 124 VGPRs).  Row 1 decodes its
+            // second load into the registers of its first (done with by then), because load 3
+            // keeps its top bytes for row 2.
+            constexpr int A = r < 3 ? 2 * r : 6, B = r == 0 ? 1 : (r == 1 ? 2 : (r == 2 ? 5 : 7));
+            if constexpr (r == 0) d[6] = pk24_tops(d[1], d[0], kPk24SelPair);
+            if constexpr (r == 1) d[6] = pk24_tops(d[2], d[6], kPk24SelThird);
+            if constexpr (r == 2) {
+                d[7] = pk24_tops(d[3], pk24_tops(d[5], d[4], kPk24SelPair), kPk24SelThird);
+                d[3] = next.template load<NT>(3);
+            }
+            pk24_decode<r == 3>(d[A], base);
+            pair_step2<0, 0, true, OP>(f32x2{d[A].x, d[A].y}, xi, yi, zi, st, rx, ry, rz, s2);
+            pair_step2<0, 1, false, OP>(f32x2{d[A].z, d[A].w}, xi, yi, zi, st, rx, ry, rz, s2);
+            if constexpr (r == 0) d[0] = next.template load<NT>(0);
+            if constexpr (r == 2) d[4] = next.template load<NT>(4);
+            if constexpr (r == 1) d[2] = d[3];
+            pk24_decode<r == 3>(d[B], base);
+            pair_step2<1, 0, false, OP>(f32x2{d[B].x, d[B].y}, xi, yi, zi, st, rx, ry, rz, s2);
+            pair_step2<1, 1, false, OP>(f32x2{d[B].z, d[B].w}, xi, yi, zi, st, rx, ry, rz, s2);
+            if constexpr (r == 0) d[1] = next.template load<NT>(1);
+            if constexpr (r == 1) d[2] = next.template load<NT>(2);
+            if constexpr (r == 2) d[5] = next.template load<NT>(5);
+            g[3 * r] = rx.x + rx.y; g[3 * r + 1] = ry.x + ry.y; g[3 * r + 2] = rz.x + rz.y;
+            row_sums_step<r>(g, h, m);
+            return;
+        }
         pair_step2<0, 0, true, OP>(f32x2{d[2 * r].x, d[2 * r].y}, xi, yi, zi, st, rx, ry, rz, s2);
         pair_step2<0, 1, false, OP>(f32x2{d[2 * r].z, d[2 * r].w}, xi, yi, zi, st, rx, ry, rz, s2);
         d[2 * r] = next.template load<NT>(2 * r);
@@ -701,6 +774,15 @@ __device__ __forceinline__ void store_strip(const StripF64<LPR> &st, double *__r
         p[2] = make_double2(g[1][1], g[1][2]);
     }
 }
+// An entry of the 24-bit stream's table (stress_grad_kernel, PK): where the unit begins in the
+// stream, in 16-byte words, and its base; nothing for a plain descriptor.
+__device__ __forceinline__ int64_t pk24_word_offset(const int4 &e) { return (int64_t)(e.z & 0x7fffffff) * 64; }
+__device__ __forceinline__ int64_t pk24_word_offset(const int2 &) { return 0; }
+__device__ __forceinline__ bool pk24_packed(const int4 &e) { return e.z < 0; }
+__device__ __forceinline__ bool pk24_packed(const int2 &) { return false; }
+__device__ __forceinline__ unsigned pk24_base(const int4 &e) { return (unsigned)e.w; }
+__device__ __forceinline__ unsigned pk24_base(const int2 &) { return 0u; }
+
 // One wave = one contiguous chunk of units; 4 independent waves per workgroup.
 // No LDS, no barriers, no atomics: results are bitwise reproducible.
 //
@@ -740,294 +822,44 @@ __device__ __forceinline__ void store_strip(const StripF64<LPR> &st, double *__r
 // bytes in flight.  Each wave posts the number of units it has done in LDS and reads its
 // partner's; whoever is behind raises its priority (s_setprio) for the next unit.  The
 // results do not depend on any of it: chunks, slots and summation order stay static.
+//
+// PK (fp32 only): `units` is the rank's 24-bit STREAM (SPEC 3.7) -- the same units in the same
+// order, each packed (6 KiB) or raw (8 KiB) -- and `udesc` its int4 table {i0, j0, offset of
+// the unit in the stream in KiB | packed << 31, base}, fetched one unit ahead like the
+// descriptor it contains.  The inner loop then exists twice, one copy per format, and the
+// outer loop makes one trip per (strip, format) run: see the loops below.  Chunks, slots,
+// parking and every sum are the same, so are the results, bit for bit.
+// With two unit bodies hipcc does not keep the kernel within 128 VGPRs (either body alone
+// fits; side by side, in any arrangement of the loops, it spills 400-800 bytes), so PK is
+// built for two waves per SIMD (<= 256 VGPRs: stream24_grad_kernel).  The sweep never runs more (waves_per_cu: 4 or 8
+// waves per CU), so that costs no occupancy.
+// The sweep's body is bb_sweep_body.inc, compiled under two kernels with their own names and
+// register budgets: stress_grad_kernel (PK = false: what it always was, instruction for
+// instruction) and stream24_grad_kernel (PK = true), below it.
 template <typename T, bool W, bool NT, int OP, int WPB>
 __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_kernel(
     const T *__restrict__ units, const T *__restrict__ X, const int2 *__restrict__ udesc,
     int chunk_q, int chunk_r, const int2 *__restrict__ wave_slots, T *__restrict__ rowpart,
     T *__restrict__ colpart, double *__restrict__ stresspart, int cap_units, int lds_wave_floats,
     int dense_u0, double *__restrict__ stress_slot) {
-    using Vec = typename Traits<T>::Vec;
-    constexpr int VW = Lay<T, W>::VW;
-    constexpr bool DEFER = sizeof(T) == 4 || W;
-    const int lane = threadIdx.x & 63;
-    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave in workgroup
-    // workgroup b sweeps the b-th run of WPB chunks (permuting that map by XCD changed
-    // nothing: docs/EXPERIMENTS.md)
-    const int wg = (int)blockIdx.x;
-    const int w = wg * WPB + wib;
-    // wave w owns units [w*q + min(w, r), +q (+1 if w < r)): arithmetic, not a table --
-    // one dependent memory round trip less before the wave's first matrix load
-    const int ua = w * chunk_q + (w < chunk_r ? w : chunk_r);
-    const int ub = ua + chunk_q + (w < chunk_r ? 1 : 0);
-    double stress = 0.0;
-    // the shared column slots of this workgroup's waves (epilogue), read NOW: behind the
-    // fences further down the compiler no longer takes them through the scalar cache, and a
-    // vector load there waits -- vmcnt is in order -- for every store the wave has in flight
-    int ws_shared[WPB];
-#pragma unroll
-    for (int k = 0; k < WPB; ++k) ws_shared[k] = wave_slots[(int64_t)wg * WPB + k].y;
-    // DEFER: this wave's parking space, cap_units * 12 floats + 4 dummy words
-    extern __shared__ __attribute__((aligned(16))) float row_lds[];
-    // this wave's LDS region: row-sum parking while it sweeps, its last column partial at
-    // the end (lds_wave_floats >= cap_units * 12 + 4 and >= 3 * VW elements of T)
-    const int stage0 = wib * lds_wave_floats;
-    // WPB = 8: progress words of the 8 waves, behind the regions
-    int *progress = reinterpret_cast<int *>(row_lds + WPB * lds_wave_floats);
-    int partner_done = 0;
-    const int park_from = (ub - ua) > cap_units ? (ub - ua) - cap_units : 0;
-    // fp64 2 x 512 units: column selectors of the MFMA row reduction (process_unit_f64w)
-    double sel[6];
-#pragma unroll
-    for (int v = 0; v < 6; ++v) sel[v] = (lane & 15) == v ? 1.0 : 0.0;
+    constexpr bool PK = sizeof(T) == 0;   // false, and dependent: what is for PK is not instantiated
+#include "bb_sweep_body.inc"
+}
 
-    if (ua < ub) {
-        int slot = wave_slots[w].x;
-        Vec d[8];  // the unit's 8 wave-loads (8 KiB), in memory order
-        // column-strip state: coordinates + gradient accumulators of this lane's columns
-        using Strip = typename std::conditional<sizeof(T) == 4, StripF32,
-                                                StripF64<Lay<T, W>::LPR>>::type;
-        Strip st;
-        // (closures on purpose: with load_strip / store_strip called directly at the two sites
-        // hipcc allocates the registers of 18 of the 40 instantiations differently, three words
-        // of scratch in the fp32 weighted ones -- tools/kernel_resources.sh --digest)
-        auto strip_load = [&](int j0) __attribute__((always_inline)) { load_strip(st, X, j0, lane); };
-        auto strip_store = [&](int sl) __attribute__((always_inline)) {
-            store_strip(st, colpart + (int64_t)sl * (3 * VW), lane);
-        };
-
-        // The wave's FIRST unit stands between the kernel's arguments and its first
-        // coordinate loads: a cold descriptor load there is one more dependent memory round
-        // trip (0.8 us of every launch).  A dense layout (dense_u0 >= 0: this rank's first
-        // global unit) has tile t = J (J + 1) / 2 + I in strip-major order (SPEC 3.1,
-        // bb_layout_dense_tiles), so that descriptor is arithmetic; the later ones come from
-        // the table as before, one unit ahead of their use.
-        int2 dc;
-        if (dense_u0 >= 0) {
-            constexpr int UPT = VW / Lay<T, W>::RPU;
-            const unsigned g = (unsigned)dense_u0 + (unsigned)ua;
-            const unsigned t = g / UPT, sub = g % UPT;
-            unsigned J = (unsigned)((__builtin_sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-            while (J * (J + 1) / 2 > t) --J;
-            while ((J + 1) * (J + 2) / 2 <= t) ++J;
-            const unsigned I = t - J * (J + 1) / 2;
-            dc = make_int2((int)(I * VW + sub * Lay<T, W>::RPU), (int)(J * VW));
-        } else {
-            dc = udesc[ua];                                    // current unit
-        }
-        int2 dn = udesc[ua + 1 < ub ? ua + 1 : ua];            // next unit
-        // Prologue: the x rows of the first unit, then its 8 matrix rows.
-        // Row coordinates of a unit, one unit ahead.  XRowS: 3*RPU wave-uniform scalars
-        // fetched through the scalar cache (X is read-only in this kernel) -- no VMEM
-        // slot, no v_readlane (12 floats or 6 doubles: 12 SGPRs, double-buffered).
-        // XRowV (fp64 narrow: 24 doubles): one per-lane load, v_readlane per use.
-        struct XRowS {
-            T v[3 * Lay<T, W>::RPU];
-            __device__ __forceinline__ T get(int q) const { return v[q]; }
-        };
-        struct XRowV {
-            T v;
-            __device__ __forceinline__ T get(int q) const { return lane_value(v, q); }
-        };
-        using XRow = typename std::conditional<Lay<T, W>::SCALAR_XROW, XRowS, XRowV>::type;
-        auto xrow_load = [&](int i0) __attribute__((always_inline)) {
-            XRow x;
-            if constexpr (std::is_same<XRow, XRowS>::value) {
-                const T *px = X + (int64_t)i0 * 3;
-#pragma unroll
-                for (int q = 0; q < 3 * Lay<T, W>::RPU; ++q) x.v[q] = px[q];
-            } else {
-                x.v = load_xrow<T, W>(X, i0, lane);
-            }
-            return x;
-        };
-        XRow xr = xrow_load(dc.x);
-        using Win = WinPtr<Vec>;
-        auto window_of = [&](int u_next) __attribute__((always_inline)) {
-            // The refills of the wave's LAST unit are never consumed.  They stay in the
-            // loop (a branch around them would cost every unit its exact wait counts),
-            // but all lanes ask for the same 16 bytes of the chunk's last unit: 8 lines
-            // instead of 8 KiB per wave and launch (1.3-2.7 % of the bytes of a 1/8 share
-            // of N=50k), back at once, so the epilogue gets the window's registers early.
-            const bool real = u_next < ub;
-            return Win{unit_ptr<T>(units, real ? u_next : ub - 1, real ? lane : 0)};
-        };
-        {
-            const Win first = window_of(ua);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) d[r] = first.template load<NT>(r);
-        }
-        // this wave's row partials: 3*RPU elements per unit of its group's chunk
-        constexpr unsigned kRowBytes = 3 * Lay<T, W>::RPU * sizeof(T);
-        const __amdgpu_buffer_rsrc_t row_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            rowpart + (int64_t)ua * (3 * Lay<T, W>::RPU), 0, (int)((unsigned)(ub - ua) * kRowBytes),
-            0x00020000);
-
-        // fp32: which of a unit's 12 row sums this lane holds after the unit's reduction
-        // (row16_sum3: every lane holds one, lanes 0, 4 and 8 of every 16-lane row store it)
-        // and what follows from it for the unit's store offset and parking slot
-        const int f32_sl12 = swap_rowsum_slot(lane);
-        const unsigned f32_voff_lane = swap_rowsum_stores(lane) ? (unsigned)f32_sl12 * 4u : 0x40000000u;
-        const int f32_lds_lane = stage0 + f32_sl12;
-        auto unit_step = [&](int u) __attribute__((always_inline)) {
-            if constexpr (WPB == 8) {
-                // pace keeping (see the kernel's comment): the partner's count was read
-                // one unit ago, so nothing here waits on LDS
-                const int mine = u - ua;
-                if (__builtin_amdgcn_readfirstlane(partner_done) > mine)
-                    __builtin_amdgcn_s_setprio(1);
-                else
-                    __builtin_amdgcn_s_setprio(0);
-                __hip_atomic_store(progress + wib, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                partner_done = __hip_atomic_load(progress + (wib ^ 4), __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            // (the descriptors of the units behind the wave's last one are never used)
-            const int un = u + 1 < ub ? u + 1 : u;
-            const XRow xrn = xrow_load(dn.x);
-            const int2 dnn = udesc[un + 1 < ub ? un + 1 : un];
-            // the unit, in the form of <T, W>: where its row sums go, then its math
-            const int k = u - ua;
-            const bool parked = k >= park_from;
-            if constexpr (sizeof(T) == 4) {
-                // fp32: every lane holds one of the unit's 12 sums.  Units before
-                // park_from are stored directly; the later ones are parked in LDS slot
-                // (k - park_from) and their store is dropped (every lane out of range).
-                // Per-lane parts are loop constants (f32_voff_lane, f32_lds_lane: below the
-                // lambda's captures), per-unit parts scalar: one v_add each per unit.  A store
-                // is out of range (dropped) unless the lane is the one that stores its sum AND
-                // the unit is not parked: 0x40000000 from either side puts the offset beyond
-                // any chunk.  The LDS write of a unit that is stored directly goes to slot 0:
-                // the parked units come after it, and the first of them overwrites that slot
-                // (LDS operations of one wave execute in program order).  The lanes that hold
-                // the same sum write the same bits to the same word.
-                const unsigned row_voff =
-                    f32_voff_lane + (parked ? 0x40000000u : (unsigned)k * kRowBytes);
-                const int stage_slot = f32_lds_lane + (parked ? k - park_from : 0) * 12;
-                float xs12[12];             // scalar registers
-#pragma unroll
-                for (int q = 0; q < 12; ++q) xs12[q] = xr.get(q);
-                process_unit_f32<NT, OP>(d, xs12, window_of(u + 1), st, stress, row_rsrc, row_voff,
-                                         stage_slot);
-            } else if constexpr (W) {
-                // fp64, 2 x 512 units: lanes 48..53 hold one of the unit's 6 sums each
-                // (parking as in fp32; an LDS slot is 4 bytes, a sum takes two)
-                const bool mine = lane >= 48 && lane < 54;
-                const unsigned row_voff =
-                    (mine && !parked) ? (unsigned)k * kRowBytes + (unsigned)(lane - 48) * 8u
-                                      : kDropOffset;
-                const int stage_slot =
-                    stage0 + ((mine && parked) ? (k - park_from) * 12 + (lane - 48) * 2
-                                               : cap_units * 12 + 2 * (lane & 1));
-                process_unit_f64w<NT, OP>(d, xr, window_of(u + 1), st.xj, st.gc, sel, stress,
-                                          row_rsrc, row_voff, stage_slot);
-            } else {                        // fp64, 8 x 128: lane 63 stores each row's three sums
-                const unsigned row_voff = lane == 63 ? (unsigned)k * kRowBytes : kDropOffset;
-                process_unit_f64n<NT, OP>(d, xr, window_of(u + 1), st.xj, st.gc, stress,
-                                          row_rsrc, row_voff);
-            }
-            xr = xrn;
-            dc = dn;
-            dn = dnn;
-        };
-        // Outer loop: one trip per column strip the wave's sweep crosses (rare).
-        // Inner loop: the units of that strip, with NO branch in the body.
-        int u = ua;
-        for (;;) {
-            const int curj = dc.y;
-            strip_load(curj);
-            // ONE copy of the unit body, entered with nothing in flight: hipcc's s_waitcnt
-            // counts are static and merged over every entry of a loop header, and a
-            // prologue- or strip-change-shaped entry would drain most of the 8-row prefetch
-            // window on every iteration.  The strip's coordinates have to be here anyway,
-            // and they were asked for after the window, so the wait counts inside the loop
-            // are those of the back edge alone.  Same speed as peeling the first unit at
-            // every size (profiles/archive/r02_peel_ab.txt), a third less code.
-            __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-            do {
-                unit_step(u);
-                ++u;
-            } while (u < ub && dc.y == curj);
-            if (u >= ub) break;      // the wave's last strip: its column partial goes out below
-            strip_store(slot);
-            // the stress of the strip left behind goes with its slot (rare: once per strip a
-            // wave crosses), so that every stress partial belongs to ONE strip -- and with
-            // several maps in one solver (bb_solver_set_maps) to one map
-            {
-                const double sv = wave_sum_hi(stress);
-                if (lane == 63) stress_slot[slot] = sv;
-                stress = 0.0;
-            }
-            ++slot;
-        }
-        if constexpr (WPB == 8) {
-            // done: the partner stops yielding
-            __hip_atomic_store(progress + wib, 0x7fffffff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __builtin_amdgcn_s_setprio(0);
-        }
-        if constexpr (DEFER) {
-            // the chunk's row sums, 48 bytes per unit in either precision (12 floats or
-            // 6 doubles), in one contiguous burst.
-            // Lanes read what other lanes of this wave parked: LDS operations of one
-            // wave execute in program order; the fence is for the compiler.
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const int n4 = ((ub - ua) - park_from) * 3;   // float4 count
-            float4 *dst = reinterpret_cast<float4 *>(rowpart + ((int64_t)ua + park_from) *
-                                                                   (3 * Lay<T, W>::RPU));
-            // (the lane number afresh: hipcc otherwise keeps the prologue's 64-bit `lane` alive
-            // through the whole sweep for this loop's index, two registers the fp32 unit
-            // does not have -- scratch in the 4-wave matvec form)
-            const int lane_q = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-            for (int q = lane_q; q < n4; q += 64) {
-                const float *src = row_lds + stage0 + 4 * q;
-                dst[q] = make_float4(src[0], src[1], src[2], src[3]);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the region is free again
-            __builtin_amdgcn_wave_barrier();
-        }
-        // the column partial of the wave's LAST strip: into its LDS region (same layout as a
-        // slot in HBM), to be added to its neighbours' below
-        store_strip(st, reinterpret_cast<T *>(row_lds + stage0), lane);
-    }
-    // One column partial per WORKGROUP and strip, not per wave: consecutive waves sweep
-    // consecutive chunks, almost always of the same strip, so the 4 or 8 partials of a
-    // workgroup are added here, in wave order (fixed), and leave as one slot -- an eighth
-    // of the bytes for the sweep to write and for the reduce to read back.  wave_slots[].y
-    // names the shared slot; waves of one workgroup that end in the same strip carry the
-    // same number (the host deals them).
-    // The barrier orders LDS only: __syncthreads() is also a release of the wave's global
-    // stores, and waiting here for the acknowledgement of the row-sum burst (s_waitcnt vmcnt
-    // in front of s_barrier) kept every wave 1-2 us at the end of every launch.
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-    {
-        constexpr int CH = 3 * VW, NTH = 64 * WPB;
-        int k = 0;
-        while (k < WPB) {
-            const int sl = ws_shared[k];       // wave-uniform (scalar registers)
-            if (sl < 0) { ++k; continue; }
-            int k2 = k + 1;
-            while (k2 < WPB && ws_shared[k2] == sl) ++k2;
-            T *dst = colpart + (int64_t)sl * CH;
-#pragma unroll
-            for (int j = 0; j < (CH + NTH - 1) / NTH; ++j) {
-                const int e = (int)threadIdx.x + NTH * j;
-                if (CH % NTH == 0 || e < CH) {
-                    T acc = T(0);
-                    for (int q = k; q < k2; ++q)
-                        acc += reinterpret_cast<const T *>(row_lds + q * lds_wave_floats)[e];
-                    dst[e] = acc;
-                }
-            }
-            k = k2;
-        }
-    }
-
-    // per-wave stress: fixed DPP tree, total in lane 63 (no LDS round trips at the very end
-    // of the launch: six __shfl_down steps of a double are twelve ds_bpermute)
-    stress = wave_sum_hi(stress);
-    if (lane == 63) stresspart[w] = stress;
+// The fp32 sweep over the 24-bit stream: `units` is the stream, `udesc` its int4 table.  Built
+// for the waves per SIMD the sweep runs with (waves_per_cu): two in workgroups of 8 waves, one
+// in workgroups of 4 -- hipcc needs 222 resp. 266 registers for the two bodies.  Ranks that
+// share a GPU do not use it (ensure_pk24): their kernels share the wave slots.
+// (T = float, W = true only; parameters so that the body's choices by type stay dependent)
+template <typename T, bool W, bool NT, int OP, int WPB>
+__global__ __launch_bounds__(64 * WPB, (WPB == 8 ? 2 : 1)) void stream24_grad_kernel(
+    const T *__restrict__ units, const T *__restrict__ X, const int2 *__restrict__ udesc,
+    int chunk_q, int chunk_r, const int2 *__restrict__ wave_slots, T *__restrict__ rowpart,
+    T *__restrict__ colpart, double *__restrict__ stresspart, int cap_units, int lds_wave_floats,
+    int dense_u0, double *__restrict__ stress_slot) {
+    static_assert(sizeof(T) == 4 && W, "the 24-bit stream is fp32 only");
+    constexpr bool PK = sizeof(T) == 4;
+#include "bb_sweep_body.inc"
 }
 
 // --------------------------------------------------------------------------
@@ -2176,6 +2008,90 @@ __global__ __launch_bounds__(256, 4) void stream_read_kernel(const float4 *__res
             for (int r = 0; r < 8; ++r) {
                 acc.x += d[r].x; acc.y += d[r].y; acc.z += d[r].z; acc.w += d[r].w;
                 d[r] = stream_load<NT>(next + r * 64);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+    if (acc.x + acc.y + acc.z + acc.w == 12345.678f) sink[w] = acc.x;  // keep the loads alive
+}
+
+// --------------------------------------------------------------------------
+// The 24-bit stream of the fp32 sweep (SPEC 3.7): built from the units once per map
+// --------------------------------------------------------------------------
+// One workgroup per unit: the smallest and the largest of its 2,048 stored words, as uint32.
+__global__ __launch_bounds__(256) void pk24_minmax_kernel(const uint4 *__restrict__ units,
+                                                          uint2 *__restrict__ minmax) {
+    __shared__ unsigned lo_s[4], hi_s[4];
+    const uint4 *p = units + (int64_t)blockIdx.x * 512 + threadIdx.x;
+    const uint4 a = p[0], b = p[256];
+    unsigned lo = min(min(min(a.x, a.y), min(a.z, a.w)), min(min(b.x, b.y), min(b.z, b.w)));
+    unsigned hi = max(max(max(a.x, a.y), max(a.z, a.w)), max(max(b.x, b.y), max(b.z, b.w)));
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = min(lo, (unsigned)__shfl_xor((int)lo, o));
+        hi = max(hi, (unsigned)__shfl_xor((int)hi, o));
+    }
+    if ((threadIdx.x & 63) == 0) lo_s[threadIdx.x >> 6] = lo, hi_s[threadIdx.x >> 6] = hi;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        minmax[blockIdx.x] = make_uint2(min(min(lo_s[0], lo_s[1]), min(lo_s[2], lo_s[3])),
+                                        max(max(hi_s[0], hi_s[1]), max(hi_s[2], hi_s[3])));
+}
+
+// One workgroup per unit: its place in the stream from the table ({., ., KiB offset | packed
+// << 31, base}); a raw unit is copied, a packed one written in the layout process_unit_f32
+// decodes -- dword c of lane l of load L (0..5) holds the code of word L*256 + 4l + c and, on
+// top, byte kPk24Byte[L] of the code of the row-3 word of load kPk24Load[L].
+__global__ __launch_bounds__(256) void pk24_pack_kernel(const uint4 *__restrict__ units,
+                                                        const int4 *__restrict__ table,
+                                                        uint4 *__restrict__ stream) {
+    const int4 e = table[blockIdx.x];
+    const uint4 *src = units + (int64_t)blockIdx.x * 512;
+    uint4 *dst = stream + (int64_t)(e.z & 0x7fffffff) * 64;
+    const int t = threadIdx.x;
+    if (e.z >= 0) {
+        dst[t] = src[t];
+        dst[t + 256] = src[t + 256];
+        return;
+    }
+    const unsigned base = (unsigned)e.w;
+    // thread t packs lane l = t & 63 of loads L = t >> 6 (0..3) and, t < 128, L + 4
+    for (int L = t >> 6; L < 6; L += 4) {
+        const int l = t & 63;
+        const int k3 = L < 3 ? 0 : 1;                       // kPk24Load
+        const int sh = 8 * (L < 3 ? L : (L == 3 ? 2 : L - 4));   // 8 * kPk24Byte
+        const uint4 w = src[L * 64 + l], r3 = src[(6 + k3) * 64 + l];
+        dst[L * 64 + l] = make_uint4((w.x - base) | ((((r3.x - base) >> sh) & 0xffu) << 24),
+                                     (w.y - base) | ((((r3.y - base) >> sh) & 0xffu) << 24),
+                                     (w.z - base) | ((((r3.z - base) >> sh) & 0xffu) << 24),
+                                     (w.w - base) | ((((r3.w - base) >> sh) & 0xffu) << 24));
+    }
+}
+
+// Measurement only, as stream_read_kernel: the same waves read the stream of their units, KiB
+// by KiB with 8 KiB in flight (unit u begins at table[u].z KiB, the stream ends at end_kib).
+template <bool NT>
+__global__ __launch_bounds__(256, 4) void stream_read_pk24_kernel(const float4 *__restrict__ stream,
+                                                                  const int4 *__restrict__ table,
+                                                                  int n_units, int end_kib,
+                                                                  int chunk_q, int chunk_r,
+                                                                  float *__restrict__ sink) {
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    const int ua = w * chunk_q + (w < chunk_r ? w : chunk_r);
+    const int ub = ua + chunk_q + (w < chunk_r ? 1 : 0);
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ua < ub) {
+        const int ka = table[ua].z & 0x7fffffff;
+        const int kb = ub < n_units ? table[ub].z & 0x7fffffff : end_kib;
+        float4 d[8];
+        const float4 *base = stream + lane;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) d[r] = stream_load<NT>(base + (int64_t)min(ka + r, kb - 1) * 64);
+        for (int k = ka; k < kb; k += 8) {
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                acc.x += d[r].x; acc.y += d[r].y; acc.z += d[r].z; acc.w += d[r].w;
+                d[r] = stream_load<NT>(base + (int64_t)min(k + 8 + r, kb - 1) * 64);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }

@@ -628,6 +628,15 @@ class HipEngine(object):
         self._call("traffic", b, p)
         return {"unit_bytes": int(b.value), "pairs_dense": int(p.value)}
 
+    def stream_info(self):
+        """The 24-bit stream the fp32 stress sweep reads instead of the units, where it is in
+        use (`bb_solver_stream_info`): units held packed and raw, its bytes and the changes of
+        format between consecutive units; packed_units 0 and stream_bytes 0 with no stream."""
+        v = [_lib.c_i64() for _ in range(4)]
+        self._call("stream_info", *v)
+        return dict(zip(("packed_units", "raw_units", "stream_bytes", "format_switches"),
+                        (int(x.value) for x in v)))
+
 
 class GroupEngine(object):
     """Several GPUs from ONE process (`bb_group_*`): member r is a HipEngine playing rank r of

@@ -515,8 +515,19 @@ BB_API int bb_solver_measure_stream_read(bb_solver *s, int launches, double *ms_
  * 0 for the unit sweep + reduce.  Either pointer may be NULL. */
 BB_API int bb_solver_iteration_path(const bb_solver *s, int *row_owner, int *waves_per_row);
 /* Bytes of wish-distance data the stress+gradient kernel streams per launch on
- * this rank (resident units * unit bytes), and pairs evaluated. */
-BB_API int bb_solver_traffic(const bb_solver *s, int64_t *unit_bytes, int64_t *pairs_dense);
+ * this rank (resident units * unit bytes, or the bytes of the 24-bit stream where the
+ * fp32 sweep reads that: bb_solver_stream_info), and pairs evaluated. */
+BB_API int bb_solver_traffic(bb_solver *s, int64_t *unit_bytes, int64_t *pairs_dense);
+/* The 24-bit stream of the fp32 stress sweep (docs/SPEC.md 3.7): a copy of this rank's units
+ * in which every unit whose 2,048 stored words, as uint32, span less than 2^24 is held as 6 KiB
+ * of lossless offset codes where at least BB_PACK24_MIN_RUN (64) such units follow each other,
+ * and as its 8 KiB otherwise.  Built from the units before the first sweep after the wish
+ * distances were set, where it saves an eighth of the bytes of a sweep that streams from HBM
+ * (BB_PACK24=1 at create: wherever a unit packs, =0: never); results do not depend on it.
+ * Returns the units held packed and raw, the stream's bytes and the changes of format between
+ * consecutive units; with no stream in use: 0, all units, 0, 0.  Pointers may be NULL. */
+BB_API int bb_solver_stream_info(bb_solver *s, int64_t *packed_units, int64_t *raw_units,
+                                 int64_t *stream_bytes, int64_t *format_switches);
 
 /* ---------------------------------------------------------------------- */
 /* A2/A3/A4  the ContactMap stage, resident on the device                   */

@@ -24,7 +24,7 @@ for sub in ("sq","fetch","write","sq2"):
         acc=collections.defaultdict(lambda: [0.0,0])
         kname=None
         for row in csv.DictReader(open(f)):
-            if "stress_grad" in row["Kernel_Name"]:
+            if "stress_grad" in row["Kernel_Name"] or "stream24_grad" in row["Kernel_Name"]:
                 kname=row["Kernel_Name"]
                 a=acc[row["Counter_Name"]]; a[0]+=float(row["Counter_Value"]); a[1]+=1
         for k,(v,n) in sorted(acc.items()):
@@ -42,7 +42,7 @@ if "$wl" == "genome10kb":
 if "FETCH_SIZE" in avg and "WRITE_SIZE" in avg:
     hbm = avg["FETCH_SIZE"][0]*1024*2 + avg["WRITE_SIZE"][0]*1024
     entry = {"bins": n, "dtype": "$dtype", "gpus": 1, "workload": "$wl", "kernel": kname,
-             "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only), python3 bench.py --steps 10 --warmup 2 --bins %d --dtype $dtype --workload $wl, averaged over the kernel's %d dispatches; profiles/r04_pmc_${tag}_n%d$sfx.txt" % (n, avg["FETCH_SIZE"][1], n),
+             "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only), python3 bench.py --steps 10 --warmup 2 --bins %d --dtype $dtype --workload $wl, averaged over the kernel's %d dispatches; profiles/pmc_${tag}_n%d$sfx.txt" % (n, avg["FETCH_SIZE"][1], n),
              "FETCH_SIZE_KB_avg": avg["FETCH_SIZE"][0], "WRITE_SIZE_KB_avg": avg["WRITE_SIZE"][0],
              "correction": "gfx950: FETCH_SIZE reports 1/2 of a wide coalesced read stream -> x2; WRITE_SIZE exact (MI355X_MICROARCH.md, HBM)",
              "hbm_bytes_per_launch": hbm, "algorithmic_bytes_per_launch": alg,
