@@ -18,6 +18,8 @@ Net-new (the reference has no solver; docs/SPEC.md):
                                   ICE bias and expected straight from a pixel list (SPEC 2.5.3)
     FitHiC, binomial_sf           Fit-Hi-C p- and q-values of a resident raw map (SPEC 2.9; the
                                   computation of blueberry/fithic.py:76-108 without its files)
+    q_values                      Benjamini-Hochberg q-values of p-values in any order: stable
+                                  sort, scan and scatter on the device (SPEC 2.9.7)
 
 All compute runs in libblueberry_hip.so (hand-written HIP for gfx950) behind
 the C-ABI of include/blueberry_hip.h.  Importing this package needs neither
@@ -32,6 +34,6 @@ from .datatypes import (ContactMap, EigenNoConvergence, FithicContactMap,  # noq
 from .fithic import FitHiC, binomial_sf  # noqa: F401
 from .solver import (DeviceTriples, FitScore, HipEngine, RankDeficient,  # noqa: F401
                      StructureSolver, TriplesBalance, balance_triples)
-from .stats import benjamini_hochberg, downsample  # noqa: F401
+from .stats import benjamini_hochberg, downsample, q_values  # noqa: F401
 
 __version__ = "0.1.0"

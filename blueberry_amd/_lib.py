@@ -134,6 +134,9 @@ SIGNATURES = {
     "bb_sig_size": (c_int, [c_void_p, p_i64, p_i64]),
     "bb_sig_read": (c_int, [c_void_p, p_i32, p_i32, p_dbl, p_dbl]),
     "bb_sig_timing": (c_int, [c_void_p, p_dbl, p_dbl]),
+    "bb_sig_q_values": (c_int, [c_void_p, c_i64, p_dbl, p_dbl]),
+    "bb_sig_read_q": (c_int, [c_void_p, p_dbl]),
+    "bb_sig_select": (c_int, [c_void_p, c_dbl, ctypes.POINTER(c_void_p)]),
     "bb_sig_destroy": (c_int, [c_void_p]),
     "bb_solver_set_wish_from_cm": (c_int, [c_void_p, c_void_p, c_int, c_dbl]),
     "bb_solver_set_wish_from_cm_block": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_dbl]),
@@ -150,6 +153,7 @@ SIGNATURES = {
     "bb_contactmap_scatter": (c_int, [p_dbl, c_i64, c_i32, p_dbl, c_i64, c_int]),
     "bb_contactmap_normalize": (c_int, [p_dbl, c_i64, p_dbl, p_dbl, c_int]),
     "bb_benjamini_hochberg": (c_int, [p_dbl, c_i64, c_i64, p_dbl, c_int]),
+    "bb_q_values": (c_int, [p_dbl, c_i64, c_i64, p_dbl, p_i64, c_int]),
     "bb_downsample": (c_int, [ctypes.POINTER(ctypes.c_float), c_i64,
                               ctypes.POINTER(ctypes.c_float), c_i64, c_int]),
 }

@@ -3,7 +3,22 @@
 //   downsample           blueberry/blueberry.pyx:93-104  (5x5 max-pool, in place)
 // Both are exact (max / min only, plus one multiply and one divide per element
 // in the reference's operation order, NaN behaviour included), pinned by golden vectors.
+//
+// And the q-value rule of docs/SPEC.md 2.9.7 around that scan, for p-values that are NOT sorted:
+//   qv_key_kernel      a 64-bit key per value whose unsigned order is numpy's sort order of
+//                      float64 (NaN last, -0.0 == +0.0), and the value's place in the list
+//   the sort           bb::stable_sort_pairs (bb_sort.h) of (key, place) over all 64 bits: ties
+//                      keep list order, as numpy.argsort(kind="stable") keeps them
+//   qv_gather_kernel   the ORIGINAL values in sorted order (the key is never inverted: a zero's
+//                      sign and a NaN's payload reach the scan as they were)
+//   the scan           bb::bh_scan_enqueue: the three bh_*_kernel launches, the one copy
+//   qv_scatter_kernel  q[place[i]] = q_sorted[i]
+// No floating-point atomics, no atomic cursor: the same bits on every run.
+#include <vector>
+
 #include "bb_common.h"
+#include "bb_qvalues.h"
+#include "bb_sort.h"
 
 namespace {
 
@@ -179,7 +194,110 @@ __global__ __launch_bounds__(256) void downsample_kernel(const float *__restrict
     yp5i[i * n5 + j] = m;
 }
 
+// ---- the q-value rule (docs/SPEC.md 2.9.7) -------------------------------------------------------
+typedef bb::sort_key u64;
+
+// numpy's order of float64 as the unsigned order of 64 bits: negatives (bits inverted) below the
+// zeros (both signs one key) below the positives (sign bit set), every NaN above them all
+__device__ __forceinline__ u64 qv_key(double v) {
+    const u64 b = (u64)__double_as_longlong(v), top = (u64)1 << 63;
+    if (v != v) return ~(u64)0;
+    if (v == 0.0) return top;
+    return (b & top) ? ~b : (b | top);
+}
+
+__global__ __launch_bounds__(256) void qv_key_kernel(const double *__restrict__ p, int64_t m,
+                                                     u64 *__restrict__ keys, uint32_t *__restrict__ place) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    keys[i] = qv_key(p[i]);
+    place[i] = (uint32_t)i;
+}
+
+__global__ __launch_bounds__(256) void qv_gather_kernel(const double *__restrict__ p,
+                                                        const uint32_t *__restrict__ place, int64_t m,
+                                                        double *__restrict__ sorted) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < m) sorted[i] = p[place[i]];
+}
+
+__global__ __launch_bounds__(256) void qv_scatter_kernel(const double *__restrict__ sorted,
+                                                         const uint32_t *__restrict__ place, int64_t m,
+                                                         double *__restrict__ q) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < m) q[place[i]] = sorted[i];
+}
+
+inline int64_t bh_blocks(int64_t d) {
+    const int64_t per_block = (int64_t)kScanBlock * kItems;
+    return (d + per_block - 1) / per_block;
+}
+
 }  // namespace
+
+size_t bb::bh_scan_work_bytes(int64_t d) {
+    const size_t nblocks = (size_t)bh_blocks(d);
+    return bb::align256(nblocks * 8) + 2 * bb::align256(nblocks * 4);
+}
+
+// work: per workgroup its summary value | its cut mark | the index of its first NaN
+hipError_t bb::bh_scan_enqueue(const double *p, int64_t d, double n, double *q, void *work, hipStream_t st) {
+    const int64_t nblocks = bh_blocks(d);
+    char *w = (char *)work;
+    double *bm = (double *)w;
+    int *bc = (int *)(w + bb::align256((size_t)nblocks * 8)), *fc = bc + bb::align256((size_t)nblocks * 4) / 4;
+    hipError_t e = bb::launch(bh_local_kernel, dim3((unsigned)nblocks), dim3(kScanBlock), 0, st, p, d, n, q, bm,
+                              bc, fc);
+    if (e == hipSuccess) e = bb::launch(bh_blockscan_kernel, dim3(1), dim3(kScanBlock), 0, st, bm, bc, nblocks);
+    if (e == hipSuccess)
+        e = bb::launch(bh_apply_kernel, dim3((unsigned)nblocks), dim3(kScanBlock), 0, st, q, d,
+                       (const double *)bm, (const int *)fc);
+    return e;
+}
+
+int bb::q_values_device(const char *who, const double *p, int64_t m, int64_t n_tests, double *q,
+                        uint32_t *order, hipStream_t st, double *sort_ms, double *scan_ms) {
+    if (sort_ms) *sort_ms = 0.0;
+    if (scan_ms) *scan_ms = 0.0;
+    BB_REQUIRE(m >= 0 && m < ((int64_t)1 << 32),
+               std::string(who) + ": the number of p-values must be in [0, 2^32)");
+    if (m == 0) return BB_OK;
+    // keys A | keys B | places A | places B | the gathered p | the sorted q | the scan's summaries
+    const size_t k8 = bb::align256((size_t)m * 8), k4 = bb::align256((size_t)m * 4);
+    bb::DevBuf work;
+    BB_TRY(bb::hip_status(who, work.alloc(4 * k8 + 2 * k4 + bb::bh_scan_work_bytes(m)), BB_ERR_NOMEM));
+    char *base = (char *)work.p;
+    u64 *ka = (u64 *)base, *kb = (u64 *)(base + k8);
+    uint32_t *ia = (uint32_t *)(base + 2 * k8), *ib = (uint32_t *)(base + 2 * k8 + k4);
+    double *ps = (double *)(base + 2 * k8 + 2 * k4), *qs = (double *)(base + 3 * k8 + 2 * k4);
+    void *bh_work = base + 4 * k8 + 2 * k4;
+    const dim3 grid((unsigned)((m + 255) / 256)), block(256);
+    bb::Event ev[3];
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = ev[i].create();
+    if (e == hipSuccess) e = hipEventRecord(ev[0], st);
+    if (e == hipSuccess) e = bb::launch(qv_key_kernel, grid, block, 0, st, p, m, ka, ia);
+    if (e == hipSuccess) {
+        e = bb::stable_sort_pairs<uint32_t>(ka, ia, kb, ib, m, 64, st);   // (ia: the sorted order)
+        if (e == hipErrorOutOfMemory) return bb::hip_status(who, e, BB_ERR_NOMEM);
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[1], st);
+    if (e == hipSuccess) e = bb::launch(qv_gather_kernel, grid, block, 0, st, p, (const uint32_t *)ia, m, ps);
+    if (e == hipSuccess) e = bb::bh_scan_enqueue(ps, m, (double)n_tests, qs, bh_work, st);
+    if (e == hipSuccess)
+        e = bb::launch(qv_scatter_kernel, grid, block, 0, st, (const double *)qs, (const uint32_t *)ia, m, q);
+    if (e == hipSuccess) e = hipEventRecord(ev[2], st);
+    if (e == hipSuccess && order != nullptr)
+        e = hipMemcpyAsync(order, ia, (size_t)m * 4, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    float a = 0.f, b = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&a, ev[0], ev[1]);
+    if (e == hipSuccess) e = hipEventElapsedTime(&b, ev[1], ev[2]);
+    BB_TRY(bb::hip_status(who, e));
+    if (sort_ms) *sort_ms = a;
+    if (scan_ms) *scan_ms = b;
+    return BB_OK;
+}
 
 extern "C" {
 
@@ -191,34 +309,54 @@ int bb_benjamini_hochberg(const double *p_values, int64_t d, int64_t n, double *
     int rc = bb::use_device(device);
     if (rc != BB_OK) return rc;
     if (d == 0) return BB_OK;
-    const int64_t per_block = (int64_t)kScanBlock * kItems;
-    const int64_t nblocks = (d + per_block - 1) / per_block;
     MiscScratch *c = bb::per_device<MiscScratch>(device);
     std::lock_guard<std::mutex> lock(c->mu);
-    const size_t o_q = bb::align256((size_t)d * 8), o_bm = o_q + bb::align256((size_t)d * 8),
-                 o_bc = o_bm + bb::align256((size_t)nblocks * 8), o_fc = o_bc + bb::align256((size_t)nblocks * 4),
-                 total = o_fc + bb::align256((size_t)nblocks * 4);
+    const size_t o_q = bb::align256((size_t)d * 8), o_work = o_q + bb::align256((size_t)d * 8),
+                 total = o_work + bb::bh_scan_work_bytes(d);
     hipError_t e = c->reserve(total);
     BB_TRY(bb::hip_status("bb_benjamini_hochberg", e, BB_ERR_NOMEM));
     hipStream_t st = c->stream;
     char *arena = (char *)c->buf.p;
-    double *p = (double *)arena, *q = (double *)(arena + o_q), *bm = (double *)(arena + o_bm);
-    int *bc = (int *)(arena + o_bc), *fc = (int *)(arena + o_fc);
+    double *p = (double *)arena, *q = (double *)(arena + o_q);
     e = hipMemcpyAsync(p, p_values, (size_t)d * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        e = bb::launch(bh_local_kernel, dim3((unsigned)nblocks), dim3(kScanBlock), 0, st,
-                       (const double *)p, d, (double)n, q, bm, bc, fc);
-        if (e == hipSuccess)
-            e = bb::launch(bh_blockscan_kernel, dim3(1), dim3(kScanBlock), 0, st, bm, bc, nblocks);
-        if (e == hipSuccess)
-            e = bb::launch(bh_apply_kernel, dim3((unsigned)nblocks), dim3(kScanBlock), 0, st, q, d,
-                           (const double *)bm, (const int *)fc);
-    }
+    if (e == hipSuccess) e = bb::bh_scan_enqueue(p, d, (double)n, q, arena + o_work, st);
     if (e == hipSuccess)
         e = hipMemcpyAsync(q_values, q, (size_t)d * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     c->trim();
     return bb::hip_status("bb_benjamini_hochberg", e);
+}
+
+int bb_q_values(const double *p, int64_t m, int64_t n_tests, double *q, int64_t *order, int device) {
+    BB_REQUIRE(m >= 0 && m < ((int64_t)1 << 32), "bb_q_values: the number of p-values must be in [0, 2^32)");
+    BB_REQUIRE(n_tests >= 0, "bb_q_values: negative n_tests");
+    BB_REQUIRE(m == 0 || (p != nullptr && q != nullptr), "bb_q_values: NULL argument");
+    BB_TRY(bb::use_device(device));
+    if (m == 0) return BB_OK;
+    MiscScratch *c = bb::per_device<MiscScratch>(device);
+    std::lock_guard<std::mutex> lock(c->mu);
+    // the arena stages p | q | the order; the sort's own buffers are the call's (bb::q_values_device)
+    const size_t o_q = bb::align256((size_t)m * 8), o_ord = 2 * o_q,
+                 total = o_ord + (order ? bb::align256((size_t)m * 4) : 0);
+    BB_TRY(bb::hip_status("bb_q_values", c->reserve(total), BB_ERR_NOMEM));
+    hipStream_t st = c->stream;
+    char *arena = (char *)c->buf.p;
+    double *dp = (double *)arena, *dq = (double *)(arena + o_q);
+    uint32_t *dord = order ? (uint32_t *)(arena + o_ord) : nullptr;
+    int rc = bb::hip_status("bb_q_values", hipMemcpyAsync(dp, p, (size_t)m * 8, hipMemcpyHostToDevice, st));
+    if (rc == BB_OK) rc = bb::q_values_device("bb_q_values", dp, m, n_tests, dq, dord, st, nullptr, nullptr);
+    if (rc == BB_OK) {
+        std::vector<uint32_t> ord(order ? (size_t)m : 0);
+        hipError_t e = hipMemcpyAsync(q, dq, (size_t)m * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && order)
+            e = hipMemcpyAsync(ord.data(), dord, (size_t)m * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        rc = bb::hip_status("bb_q_values", e);
+        if (rc == BB_OK)
+            for (size_t i = 0; i < ord.size(); ++i) order[i] = (int64_t)ord[i];
+    }
+    c->trim();
+    return rc;
 }
 
 int bb_downsample(const float *yp1, int64_t n1, float *yp5i, int64_t n5, int device) {

@@ -25,6 +25,10 @@
 //   sig_p_kernel  one lane per LISTED cell, so that no lane idles on an empty one; neighbouring
 //               lanes are neighbouring columns of a row and carry similar priors, hence similar
 //               term counts.  Both routes end in this kernel.
+//   q-values    of the resident p-values, kept on the handle (bb_sig_q_values): the rule of SPEC
+//               2.9.7 through bb::q_values_device (bb_qvalues.h: key, stable sort, BH scan,
+//               scatter).  bb_sig_select makes the list of the cells with q <= q_max as the list
+//               itself is made: a flag per cell, an exclusive scan, a write -- list order stays.
 // Integer atomics only (counters whose sum does not depend on the order); the same bits on
 // every run and on both routes.
 #include <float.h>
@@ -37,6 +41,7 @@
 
 #include "bb_cm_internal.h"
 #include "bb_common.h"
+#include "bb_qvalues.h"
 #include "bb_triples.h"
 
 namespace bb {
@@ -130,6 +135,8 @@ struct bb_sig {
     int64_t terms = 0;               // pmf values summed over all of them
     double list_ms = 0.0, p_ms = 0.0;
     bb::DevBuf row, col, count, p;   // int32, int32, float64, float64
+    bb::DevBuf q;                    // float64, once bb_sig_q_values has run (have_q)
+    bool have_q = false;
 };
 
 namespace {
@@ -297,6 +304,30 @@ __global__ __launch_bounds__(kSfBlock) void binomial_sf_kernel(const long long *
     int terms = 0, capped = 0;
     if (e < m) out[e] = bb::binomial_sf(k[e], n, p[e], &terms, &capped);
     sf_account(terms, capped, status);
+}
+
+// ---- the selection: the cells with q <= q_max, as the list itself is made -------------------------
+// keep[e] = 1 for a cell with q <= q_max (a NaN q fails the comparison: never selected)
+__global__ __launch_bounds__(kSfBlock) void sig_keep_kernel(const double *__restrict__ q, int64_t m,
+                                                           double q_max, u64 *__restrict__ keep) {
+    const int64_t e = (int64_t)blockIdx.x * kSfBlock + threadIdx.x;
+    if (e < m) keep[e] = q[e] <= q_max ? 1 : 0;
+}
+
+// the kept cells to their places pos[e] (the exclusive scan of keep): list order stays
+__global__ __launch_bounds__(kSfBlock) void sig_pick_kernel(
+    const u64 *__restrict__ keep, const u64 *__restrict__ pos, int64_t m, const int *__restrict__ row,
+    const int *__restrict__ col, const double *__restrict__ cnt, const double *__restrict__ p,
+    const double *__restrict__ q, int *__restrict__ orow, int *__restrict__ ocol, double *__restrict__ ocnt,
+    double *__restrict__ op, double *__restrict__ oq) {
+    const int64_t e = (int64_t)blockIdx.x * kSfBlock + threadIdx.x;
+    if (e >= m || keep[e] == 0) return;
+    const u64 at = pos[e];
+    orow[at] = row[e];
+    ocol[at] = col[e];
+    ocnt[at] = cnt[e];
+    op[at] = p[e];
+    oq[at] = q[e];
 }
 
 // ---- host side ---------------------------------------------------------------------------------
@@ -518,6 +549,88 @@ int bb_sig_read(const bb_sig *s, int32_t *row, int32_t *col, double *count, doub
     if (e == hipSuccess) e = hipMemcpy(count, s->count.p, m * 8, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(p, s->p.p, m * 8, hipMemcpyDeviceToHost);
     return bb::hip_status("bb_sig_read", e);
+}
+
+int bb_sig_q_values(bb_sig *s, int64_t n_tests, double *sort_ms, double *scan_ms) {
+    BB_REQUIRE(s != nullptr, "bb_sig_q_values: results are NULL");
+    BB_REQUIRE(n_tests >= 0, "bb_sig_q_values: negative n_tests");
+    BB_TRY(bb::enter_device(s->device));
+    s->have_q = false;                            // (a call that fails leaves the handle without q)
+    s->q.reset();
+    bb::DevBuf q;
+    BB_TRY(bb::hip_status("bb_sig_q_values", q.alloc((size_t)s->n * 8), BB_ERR_NOMEM));
+    BB_TRY(bb::q_values_device("bb_sig_q_values", (const double *)s->p.p, s->n, n_tests, q.as<double>(),
+                               nullptr, (hipStream_t) nullptr, sort_ms, scan_ms));
+    s->q = std::move(q);
+    s->have_q = true;
+    return BB_OK;
+}
+
+int bb_sig_read_q(const bb_sig *s, double *q) {
+    BB_REQUIRE(s != nullptr, "bb_sig_read_q: results are NULL");
+    if (!s->have_q) return bb::fail(BB_ERR_STATE, "bb_sig_read_q: no q-values yet (bb_sig_q_values)");
+    if (s->n == 0) return BB_OK;
+    BB_REQUIRE(q != nullptr, "bb_sig_read_q: NULL argument");
+    BB_TRY(bb::enter_device(s->device));
+    return bb::hip_status("bb_sig_read_q", hipMemcpy(q, s->q.p, (size_t)s->n * 8, hipMemcpyDeviceToHost));
+}
+
+int bb_sig_select(const bb_sig *s, double q_max, bb_sig **out) {
+    const char *who = "bb_sig_select";
+    BB_REQUIRE(out != nullptr, "bb_sig_select: NULL argument");
+    *out = nullptr;
+    BB_REQUIRE(s != nullptr, "bb_sig_select: results are NULL");
+    BB_REQUIRE(q_max == q_max, "bb_sig_select: q_max is NaN");
+    if (!s->have_q) return bb::fail(BB_ERR_STATE, "bb_sig_select: no q-values yet (bb_sig_q_values)");
+    BB_TRY(bb::enter_device(s->device));
+    hipStream_t st = nullptr;
+    const int64_t m = s->n;
+    std::unique_ptr<bb_sig> sel(new bb_sig());
+    sel->device = s->device;
+    sel->have_q = true;
+    bb::DevBuf work;
+    u64 *keep = nullptr, *pos = nullptr;
+    hipError_t e = hipSuccess;
+    if (m > 0) {
+        // keep | pos | the scan's temporary storage
+        const size_t cells = bb::align256((size_t)m * 8);
+        size_t scan_bytes = 0;
+        e = rocprim::exclusive_scan(nullptr, scan_bytes, (u64 *)nullptr, (u64 *)nullptr, (u64)0, (size_t)m,
+                                    rocprim::plus<u64>(), st);
+        BB_TRY(bb::hip_status(who, e));
+        BB_TRY(bb::hip_status(who, work.alloc(2 * cells + scan_bytes), BB_ERR_NOMEM));
+        keep = (u64 *)work.p;
+        pos = (u64 *)((char *)work.p + cells);
+        e = bb::launch(sig_keep_kernel, dim3((unsigned)((m + kSfBlock - 1) / kSfBlock)), dim3(kSfBlock), 0, st,
+                       (const double *)s->q.p, m, q_max, keep);
+        if (e == hipSuccess)
+            e = rocprim::exclusive_scan((char *)work.p + 2 * cells, scan_bytes, keep, pos, (u64)0, (size_t)m,
+                                        rocprim::plus<u64>(), st);
+        u64 last_pos = 0, last_keep = 0;
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = hipMemcpy(&last_pos, pos + (m - 1), 8, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(&last_keep, keep + (m - 1), 8, hipMemcpyDeviceToHost);
+        BB_TRY(bb::hip_status(who, e));
+        sel->n = (int64_t)(last_pos + last_keep);
+    }
+    const size_t k = (size_t)sel->n;
+    e = sel->row.alloc(k * 4);
+    if (e == hipSuccess) e = sel->col.alloc(k * 4);
+    if (e == hipSuccess) e = sel->count.alloc(k * 8);
+    if (e == hipSuccess) e = sel->p.alloc(k * 8);
+    if (e == hipSuccess) e = sel->q.alloc(k * 8);
+    BB_TRY(bb::hip_status(who, e, BB_ERR_NOMEM));
+    if (k > 0) {
+        e = bb::launch(sig_pick_kernel, dim3((unsigned)((m + kSfBlock - 1) / kSfBlock)), dim3(kSfBlock), 0, st,
+                       (const u64 *)keep, (const u64 *)pos, m, (const int *)s->row.p, (const int *)s->col.p,
+                       (const double *)s->count.p, (const double *)s->p.p, (const double *)s->q.p,
+                       sel->row.as<int>(), sel->col.as<int>(), sel->count.as<double>(), sel->p.as<double>(),
+                       sel->q.as<double>());
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        BB_TRY(bb::hip_status(who, e));
+    }
+    *out = sel.release();
+    return BB_OK;
 }
 
 int bb_sig_destroy(bb_sig *s) {

@@ -5,7 +5,7 @@
 //   the index   every triple with both bins below n_bins emits its directed entries (a, b) and
 //               (b, a) -- one if a == b -- into slots 2 t and 2 t + 1, keyed a n_bins + b; a
 //               triple that emits nothing leaves the slot's key above every real one.  A STABLE
-//               radix sort by key (below) keeps equal keys in triple order, so the LAST entry
+//               radix sort by key (bb_sort.h) keeps equal keys in triple order, so the LAST entry
 //               of a run of equal keys is the winner of its cell; the winners are compacted
 //               into a CSR of the symmetric matrix: row_ptr (int64), col (int32), val
 //               (float64), 12 B per directed entry.  Keys are 64 bits: n_bins^2 passes 2^32 at
@@ -13,7 +13,7 @@
 //               distinct), so a row's length always fits 31 bits; row_ptr is 64 bits.
 //               Memory: 12 B per directed entry resident (at most 24 B per triple); while it
 //               is built, 2 slots x (8 B key + 8 B value) x 2 (the sort's two buffers) = 64 B
-//               per triple plus the sort's counters (0.5 B per slot), all given back before the call
+//               per triple plus the sort's counters (1 B per slot), all given back before the call
 //               returns.  An allocation that fails is BB_ERR_NOMEM; nothing half-built is
 //               kept (the index is assembled aside and moved into the handle when complete).
 //   seg_sum_kernel   the hot path: y_i = sum of row i's counted entries val_k x[col_k].  Rows
@@ -48,6 +48,7 @@
 #include "bb_balance_loop.h"
 #include "bb_cm_internal.h"
 #include "bb_common.h"
+#include "bb_sort.h"
 #include "bb_triples.h"
 
 namespace {
@@ -56,6 +57,7 @@ using bb::kCellBad;
 using bb::kCellNonzero;
 using bb::kCellValue;
 using bb::SegmentedList;
+using bb::stable_sort_pairs;   // the stable radix sort (bb_sort.h), here with double payloads
 using bb::TriplesIndex;
 
 using bb::kTbSeg;   // entries of one owner (row or diagonal) that one wave sums
@@ -87,71 +89,6 @@ __global__ __launch_bounds__(256) void emit_kernel(const double *__restrict__ tr
     keys[2 * t + 1] = k1;
     vals[2 * t] = c;
     vals[2 * t + 1] = c;
-}
-
-// ---- the stable sort: LSD radix, 8 bits per pass ---------------------------------------------------
-// A pass moves every (key, value) to its place by one digit of the key and keeps the order of
-// equal digits, so after the passes over all the key's bits equal KEYS are still in slot order.
-// A workgroup owns kSortTile consecutive slots: digit_hist_kernel counts its digits (integer LDS
-// atomics), an exclusive scan of hist[digit][workgroup] -- digits outermost -- gives where each
-// workgroup's run of each digit starts, and digit_scatter_kernel walks its tile in rounds of 256
-// consecutive slots: within a wave a slot's rank among the equal digits comes from ballots, across
-// the 4 waves and the rounds from LDS counters.  (rocprim's radix sort is not used: its one-sweep
-// kernel needs scratch memory, and no kernel of this library does.)
-constexpr int kSortRounds = 16, kSortTile = 256 * kSortRounds;
-
-__global__ __launch_bounds__(256) void digit_hist_kernel(const u64 *__restrict__ keys, int64_t m, int shift,
-                                                         int64_t n_wg, u64 *__restrict__ hist) {
-    __shared__ unsigned h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const int64_t base = (int64_t)blockIdx.x * kSortTile;
-    for (int r = 0; r < kSortRounds; ++r) {
-        const int64_t i = base + r * 256 + threadIdx.x;
-        if (i < m) atomicAdd(&h[(keys[i] >> shift) & 255], 1u);
-    }
-    __syncthreads();
-    hist[(int64_t)threadIdx.x * n_wg + blockIdx.x] = h[threadIdx.x];
-}
-
-__global__ __launch_bounds__(256) void digit_scatter_kernel(const u64 *__restrict__ keys,
-                                                            const double *__restrict__ vals, int64_t m,
-                                                            int shift, int64_t n_wg,
-                                                            const u64 *__restrict__ start,
-                                                            u64 *__restrict__ okeys,
-                                                            double *__restrict__ ovals) {
-    __shared__ u64 run[256];                      // where the next slot of each digit goes
-    __shared__ unsigned cnt[4][256];              // this round's slots per wave and digit
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    run[tid] = start[(int64_t)tid * n_wg + blockIdx.x];
-    for (int w = 0; w < 4; ++w) cnt[w][tid] = 0;
-    __syncthreads();
-    const int64_t base = (int64_t)blockIdx.x * kSortTile;
-    for (int r = 0; r < kSortRounds; ++r) {       // (uniform: every thread meets every barrier)
-        const int64_t i = base + r * 256 + tid;
-        const bool in = i < m;
-        const u64 k = in ? keys[i] : 0;
-        const int dg = (int)((k >> shift) & 255);
-        u64 peers = __ballot(in);                 // the wave's slots with this slot's digit
-        for (int b = 0; b < 8; ++b) {
-            const bool bit = (dg >> b) & 1;
-            const u64 vote = __ballot(bit);
-            peers &= bit ? vote : ~vote;
-        }
-        const unsigned rank = (unsigned)__popcll(peers & (((u64)1 << lane) - 1));
-        if (in && rank == 0) cnt[wave][dg] = (unsigned)__popcll(peers);
-        __syncthreads();
-        if (in) {
-            u64 pos = run[dg] + rank;
-            for (int w = 0; w < wave; ++w) pos += cnt[w][dg];
-            okeys[pos] = k;
-            ovals[pos] = vals[i];
-        }
-        __syncthreads();
-        run[tid] += (u64)cnt[0][tid] + cnt[1][tid] + cnt[2][tid] + cnt[3][tid];
-        for (int w = 0; w < 4; ++w) cnt[w][tid] = 0;
-        __syncthreads();
-    }
 }
 
 // keep[i] = 1 for the last entry of every run of equal real keys
@@ -336,32 +273,6 @@ __global__ __launch_bounds__(256) void pair_counts_kernel(const u64 *__restrict_
     } while (0)
 
 inline dim3 grid256(int64_t n) { return dim3((unsigned)((std::max<int64_t>(n, 1) + 255) / 256)); }
-
-// (k, v) sorted by the low `bits` bits of k, equal keys in their order; (k2, v2) are the second
-// buffers.  On return k / v point at the sorted arrays and k2 / v2 at the other pair.
-hipError_t stable_sort_pairs(u64 *&k, double *&v, u64 *&k2, double *&v2, int64_t m, unsigned bits,
-                             hipStream_t st) {
-    const int64_t n_wg = (m + kSortTile - 1) / kSortTile;
-    const size_t cells = (size_t)n_wg * 256;
-    bb::DevBuf hist, start, tmp;
-    TB_HIP(hist.alloc(cells * 8));
-    TB_HIP(start.alloc(cells * 8));
-    size_t scan_bytes = 0;
-    TB_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, hist.as<u64>(), start.as<u64>(), (u64)0, cells,
-                                   rocprim::plus<u64>(), st));
-    TB_HIP(tmp.alloc(scan_bytes));
-    for (unsigned shift = 0; shift < bits; shift += 8) {
-        TB_HIP(bb::launch(digit_hist_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, (const u64 *)k, m,
-                          (int)shift, n_wg, hist.as<u64>()));
-        TB_HIP(rocprim::exclusive_scan(tmp.p, scan_bytes, hist.as<u64>(), start.as<u64>(), (u64)0, cells,
-                                       rocprim::plus<u64>(), st));
-        TB_HIP(bb::launch(digit_scatter_kernel, dim3((unsigned)n_wg), dim3(256), 0, st, (const u64 *)k,
-                          (const double *)v, m, (int)shift, n_wg, (const u64 *)start.p, k2, v2));
-        std::swap(k, k2);
-        std::swap(v, v2);
-    }
-    return hipStreamSynchronize(st);              // (hist, start and tmp die with this scope)
-}
 
 // keys / vals (m slots; `none` marks an empty one) -> list: sort, keep the last of equal keys,
 // pointers for `owners` owners of key / n_bins.  `upper` (may be NULL): the entries with

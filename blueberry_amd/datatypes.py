@@ -576,8 +576,9 @@ class ContactMap(object):
     def significance(self, **kwargs):
         """The Fit-Hi-C p- and q-values of this raw map's contacts as a `FithicContactMap`
         (docs/SPEC.md 2.9): `FitHiC(resolution=self.resolution, **kwargs).fit_transform(self)`,
-        with `biases` ('auto': the map's KRnorm, e.g. what `balance()` left) passed on to
-        `fit_transform`.  The map stays as it is and stays resident."""
+        with `biases` ('auto': the map's KRnorm, e.g. what `balance()` left) and `q_max` (only the
+        contacts with q <= q_max, selected on the device) passed on to `fit_transform`.  The map
+        stays as it is and stays resident."""
         from .fithic import _significance
         return _significance(self, None, kwargs)
 

@@ -21,7 +21,6 @@ import numpy
 
 from . import _lib
 from .datatypes import ContactMap, FithicContactMap, _pick_device
-from .stats import benjamini_hochberg
 
 _DIST_SCALING = 10000.0            # `distScaling`, blueberry/fithic.py:45
 
@@ -151,6 +150,27 @@ class _Results(object):
                                          _lib.as_f64_ptr(p)), "bb_sig_read")
         return row, col, count, p
 
+    def q_values(self, n_tests):
+        """Compute the q-values of the resident p-values with `n_tests` tests and keep them on the
+        handle (`bb_sig_q_values`; again: recomputed).  Returns the HIP-event times (ms) of keys +
+        sort and of gather + scan + scatter."""
+        a, b = _lib.c_dbl(), _lib.c_dbl()
+        _lib.check(self._lib.bb_sig_q_values(self._h, int(n_tests), a, b), "bb_sig_q_values")
+        return float(a.value), float(b.value)
+
+    def read_q(self):
+        """The q-values, in list order; RuntimeError before `q_values`."""
+        q = numpy.empty(self.size()[0], dtype=numpy.float64)
+        _lib.check(self._lib.bb_sig_read_q(self._h, _lib.as_f64_ptr(q)), "bb_sig_read_q")
+        return q
+
+    def select(self, q_max):
+        """The cells with q <= `q_max` as a new `_Results` (close it), in list order; a NaN q is
+        never selected.  RuntimeError before `q_values`, ValueError for a NaN `q_max`."""
+        out = _lib.c_void_p()
+        _lib.check(self._lib.bb_sig_select(self._h, float(q_max), ctypes.byref(out)), "bb_sig_select")
+        return _Results(self._lib, out)
+
     def close(self):
         if self._h:
             self._lib.bb_sig_destroy(self._h)
@@ -220,7 +240,8 @@ class FitHiC(object):
     non-increasing spline), `prior_by_distance_` (its lookup table per diagonal), `n_reads_` (N: the
     in-range reads), `n_tests_` (T: the possible in-range pairs), `n_listed_` (the contacts listed);
     `terms_` (pmf values the device summed), `list_ms_` and `p_ms_` (HIP-event times of the call's
-    two device passes).
+    two device passes), `sort_ms_` and `bh_ms_` (those of the q-values: keys and sort; gather, scan
+    and scatter), `n_selected_` (the contacts returned: `n_listed_` without `q_max`).
     """
 
     def __init__(self, libname=None, resolution=None, n_bins=100, n_passes=2, max_dist=-1,
@@ -283,10 +304,15 @@ class FitHiC(object):
                              % (self.min_dist, self.max_dist))
         return n, bias, k_lo, k_hi
 
-    def fit_transform(self, X, biases="auto", map_bins=None):
+    def fit_transform(self, X, biases="auto", map_bins=None, q_max=None):
         """The p- and q-values of `X`'s contacts, as a `FithicContactMap` with rows (mid1, mid2,
         count, p, q), mid = bin * resolution + resolution // 2, in canonical order (row-major over
-        i <= j).
+        i <= j).  The q-values are made on the device from the resident p-values
+        (`bb_sig_q_values`, docs/SPEC.md 2.9.7).
+
+        q_max : None -- every listed contact; a number -- only the contacts with q <= q_max (e.g.
+            `Q_LOWER_BOUND`), selected on the device, so that only they are read back: the rows
+            of the full result with `map[:, 4] <= q_max`, bit for bit and in order.
 
         X : a `ContactMap` holding raw counts, or a `DeviceTriples` together with `map_bins` (the
             n_bins of the map the triples define).  One chromosome.
@@ -298,6 +324,10 @@ class FitHiC(object):
         pass, which a diagonal sum that is itself no count brings forward.  The map stays as it
         is."""
         n, bias, k_lo, k_hi = self._arguments(X, biases, map_bins)
+        if q_max is not None:
+            q_max = float(q_max)
+            if q_max != q_max:
+                raise ValueError("FitHiC: q_max is NaN")
         r = self.resolution
         observed = diagonal_sums(X, n)
         observed[:k_lo] = 0.0
@@ -319,18 +349,23 @@ class FitHiC(object):
                              "(fewer reads than bins, or too narrow a range?)" % x.shape[0])
         sx, sy, prior = prior_by_distance(x, y, n, r, k_lo, k_hi)
         res = significance_list(X, n, k_lo, k_hi, bias, self.bias_range, prior, n_reads)
+        picked = None
         try:
-            row, col, count, p = res.read()
-            self.terms_, (self.list_ms_, self.p_ms_) = res.size()[1], res.timing()
+            (n_listed, self.terms_), (self.list_ms_, self.p_ms_) = res.size(), res.timing()
+            self.sort_ms_, self.bh_ms_ = res.q_values(n_tests)
+            if q_max is not None:
+                picked = res.select(q_max)
+            source = res if picked is None else picked
+            row, col, count, p = source.read()
+            q = source.read_q()
         finally:
+            if picked is not None:
+                picked.close()
             res.close()
-        q = numpy.empty_like(p)
-        if p.shape[0]:
-            order = numpy.argsort(p, kind="stable")
-            q[order] = benjamini_hochberg(p[order], n_tests, device=_device_handle(X)[2])
         self.bins_x_, self.bins_y_, self.spline_x_, self.spline_y_ = x, y, sx, sy
         self.prior_by_distance_ = prior
-        self.n_reads_, self.n_tests_, self.n_listed_ = n_reads, n_tests, int(p.shape[0])
+        self.n_reads_, self.n_tests_, self.n_listed_ = n_reads, n_tests, n_listed
+        self.n_selected_ = int(p.shape[0])
         mids = numpy.column_stack([row, col]).astype(numpy.float64) * r + r // 2
         return FithicContactMap.from_array(
             numpy.column_stack([mids, count, p, q]).reshape(-1, 5), r,
@@ -339,8 +374,9 @@ class FitHiC(object):
 
 def _significance(X, map_bins, kwargs):
     """`ContactMap.significance` / `DeviceTriples.significance`: FitHiC's constructor arguments and
-    `biases` as keywords; the map's own resolution."""
+    `biases` and `q_max` as keywords; the map's own resolution."""
     kwargs = dict(kwargs)
     biases = kwargs.pop("biases", "auto")
+    q_max = kwargs.pop("q_max", None)
     kwargs.setdefault("resolution", X.resolution)
-    return FitHiC(**kwargs).fit_transform(X, biases=biases, map_bins=map_bins)
+    return FitHiC(**kwargs).fit_transform(X, biases=biases, map_bins=map_bins, q_max=q_max)

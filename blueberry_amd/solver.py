@@ -125,7 +125,8 @@ class DeviceTriples(object):
     def significance(self, map_bins, **kwargs):
         """The Fit-Hi-C p- and q-values of the map the triples define over bins 0 .. map_bins - 1
         (`ContactMap.significance`; docs/SPEC.md 2.9), bit for bit what `ContactMap.from_triples(
-        ...).significance(...)` gives, without that matrix.  One chromosome."""
+        ...).significance(...)` gives, without that matrix; `biases` and `q_max` go on to
+        `FitHiC.fit_transform`.  One chromosome."""
         from .fithic import _significance
         return _significance(self, int(map_bins), kwargs)
 

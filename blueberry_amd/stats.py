@@ -1,5 +1,6 @@
 """benjamini_hochberg and downsample -- host side of the two remaining numeric
-Cython helpers of the reference (`blueberry/blueberry.pyx:40-75`, `:93-104`)."""
+Cython helpers of the reference (`blueberry/blueberry.pyx:40-75`, `:93-104`) -- and q_values,
+the first of them for p-values that are not sorted yet (docs/SPEC.md 2.9.7)."""
 import ctypes
 
 import numpy
@@ -21,6 +22,32 @@ def benjamini_hochberg(p_values, n, device=0):
                                                  _lib.as_f64_ptr(q), int(device)),
                "bb_benjamini_hochberg")
     return q
+
+
+def q_values(p_values, n_tests=None, device=0, return_order=False):
+    """The Benjamini-Hochberg q-values of p-values in ANY order and of any shape (docs/SPEC.md
+    2.9.7): with `order = numpy.argsort(p, kind="stable")` over the values in C order,
+    `q[order] = benjamini_hochberg(p[order], n_tests)`, bit for bit -- the sort (a stable radix sort
+    by a 64-bit key whose order is numpy's order of float64: NaN last, ties in list order), the scan
+    and the scatter all run on the device (`bb_q_values`).  `n_tests=None`: the number of
+    p-values.  Returns a float64 array shaped like `p_values`; with `return_order` also the
+    stable sorted order (int64, one-dimensional).  ValueError for a non-numeric input or a negative
+    `n_tests`, raised before any device call."""
+    p = numpy.asarray(p_values)
+    if p.dtype.kind not in "biuf":
+        raise ValueError("q_values: p_values must be real numbers, not dtype %s" % p.dtype)
+    shape = p.shape
+    p = numpy.ascontiguousarray(p, dtype=numpy.float64).reshape(-1)
+    n = p.shape[0] if n_tests is None else int(n_tests)
+    if n < 0:
+        raise ValueError("q_values: n_tests must not be negative")
+    q = numpy.zeros_like(p)
+    order = numpy.zeros(p.shape[0], dtype=numpy.int64) if return_order else None
+    _lib.check(_lib.load().bb_q_values(_lib.as_f64_ptr(p), p.shape[0], n, _lib.as_f64_ptr(q),
+                                       order.ctypes.data_as(_lib.p_i64) if return_order else None,
+                                       int(device)), "bb_q_values")
+    q = q.reshape(shape)
+    return (q, order) if return_order else q
 
 
 def downsample(yp1, yp5, yp5i, device=0):

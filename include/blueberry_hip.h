@@ -693,7 +693,27 @@ BB_API int bb_triples_pairs(bb_triples *t, int64_t n_bins, int64_t *n_pairs);
  *   bb_sig_size    the number of listed cells; terms (may be NULL): pmf values summed over all
  *   bb_sig_read    row, col (int32), count, p (float64) to the host, bb_sig_size values each
  *   bb_sig_timing  HIP-event times (ms) of the call: count + scan + write, and the p-value pass
- *   bb_sig_destroy frees it (NULL is fine) */
+ *   bb_sig_destroy frees it (NULL is fine)
+ *
+ * The q-values of the list, on the device (docs/SPEC.md 2.9.7):
+ *   bb_sig_q_values  q of the resident p-values with n_tests tests, kept on the handle: q[order] =
+ *                  the Benjamini-Hochberg scan of p[order], order = the STABLE sorted order of p
+ *                  (numpy's order of float64: NaN last, -0.0 equal to 0.0, ties in list order).
+ *                  A 64-bit key per value, a stable radix sort of (key, place), a gather of the
+ *                  original values, the scan of bb_benjamini_hochberg, a scatter: bit for bit what
+ *                  that function gives on the host-sorted values, the same bits on every run.
+ *                  Calling it again recomputes.  sort_ms / scan_ms (may be NULL): HIP-event times
+ *                  of keys + sort, and of gather + scan + scatter.  Its buffers (40 B per cell
+ *                  plus the sort's counters) are freed before it returns; one that cannot be
+ *                  allocated is BB_ERR_NOMEM and leaves the handle without q.  A list of 2^32
+ *                  cells or more is BB_ERR_INVALID.
+ *   bb_sig_read_q  q (float64) to the host, bb_sig_size values; BB_ERR_STATE before
+ *                  bb_sig_q_values.
+ *   bb_sig_select  a NEW bb_sig of the cells with q <= q_max -- row, col, count, p and q -- in
+ *                  canonical order (a flag, an exclusive scan, a write); a NaN q is never
+ *                  selected.  NaN q_max: BB_ERR_INVALID; before bb_sig_q_values: BB_ERR_STATE;
+ *                  *out is NULL after an error.  bb_sig_size (terms: 0), bb_sig_read,
+ *                  bb_sig_read_q and bb_sig_destroy work on the result. */
 typedef struct bb_sig bb_sig;
 BB_API int bb_binomial_sf(const int64_t *k, double n, const double *p, double *out, int64_t m,
                           int device);
@@ -706,6 +726,9 @@ BB_API int bb_triples_significance(bb_triples *t, int64_t n_bins, int64_t k_lo, 
 BB_API int bb_sig_size(const bb_sig *s, int64_t *n_listed, int64_t *terms);
 BB_API int bb_sig_read(const bb_sig *s, int32_t *row, int32_t *col, double *count, double *p);
 BB_API int bb_sig_timing(const bb_sig *s, double *list_ms, double *p_ms);
+BB_API int bb_sig_q_values(bb_sig *s, int64_t n_tests, double *sort_ms, double *scan_ms);
+BB_API int bb_sig_read_q(const bb_sig *s, double *q);
+BB_API int bb_sig_select(const bb_sig *s, double q_max, bb_sig **out);
 BB_API int bb_sig_destroy(bb_sig *s);
 /* Hand the resident matrix to a solver of n_bins = d bins on the same device, device
  * to device (same meaning of kind / alpha as bb_solver_set_wish_dense).  A solver on another
@@ -739,6 +762,13 @@ BB_API int bb_contactmap_normalize(double *matrix, int64_t n_bins, const double 
  * (reference: blueberry/blueberry.pyx:40-75; a parallel prefix-max, exact). */
 BB_API int bb_benjamini_hochberg(const double *p_values, int64_t d, int64_t n, double *q_values,
                                  int device);
+/* The q-values of m host p-values in ANY order (docs/SPEC.md 2.9.7): q[order] =
+ * bb_benjamini_hochberg(p[order], n_tests) with order the stable sorted order of p (numpy's order
+ * of float64), bit for bit, sorted on the device.  order (may be NULL) receives that order.  m = 0
+ * is fine; m >= 2^32 or a negative n_tests is BB_ERR_INVALID.  Host in, host out, on the
+ * per-device stream and staging arena of bb_benjamini_hochberg. */
+BB_API int bb_q_values(const double *p, int64_t m, int64_t n_tests, double *q, int64_t *order,
+                       int device);
 /* yp5i (n5,n5) float32, in place: yp5i[i][j] = max(yp5i[i][j], 5x5 block of yp1
  * (n1,n1)) for i, j < n5-1 (reference: blueberry/blueberry.pyx:93-104). */
 BB_API int bb_downsample(const float *yp1, int64_t n1, float *yp5i, int64_t n5, int device);

@@ -5,8 +5,11 @@ two device passes by the HIP events of the call itself (`bb_sig_timing`):
 
   * the tally (`bb_cm_expected` / `bb_triples_expected` with all weights 1);
   * the list (count, scan, write) and the p-value pass: cells per second, mean terms per cell;
-  * the host's stable argsort of the p-values and the Benjamini-Hochberg scan;
-  * the whole `fit_transform`, and the share of the sort in it;
+  * the host's stable argsort of the p-values and the Benjamini-Hochberg scan: the q stage as it
+    was before the device sort, timed here in the same process;
+  * the device q stage (`bb_sig_q_values`): its two HIP-event times, the call and the read-back of
+    q by wall clock, and host against device with their ranges over 5;
+  * the whole `fit_transform`, without and with `q_max = 0.01`;
   * lane utilisation of the p-value pass, from the model's term counts of every 50th wave of the
     list (64 consecutive cells): sum of terms over 64 x sum of the waves' longest.
 
@@ -69,10 +72,45 @@ def route(name, X, n, bias, max_dist, f_args):
     order = numpy.argsort(p, kind="stable")
     ps_sorted = p[order]
     t_bh = median_of(lambda: bb.benjamini_hochberg(ps_sorted, f.n_tests_))
-    t_all = median_of(lambda: f.fit_transform(X, biases=bias, **f_args), 3)
-    say("%s: host stable argsort of p %.1f ms; BH scan (upload, scan, download) %.1f ms; fit_transform "
-        "%.1f ms: the sort is %.0f %% of it" % (name, t_sort * 1e3, t_bh * 1e3, t_all * 1e3,
-                                                 100.0 * t_sort / t_all))
+    say("%s: host stable argsort of p %.1f ms; BH scan (upload, scan, download) %.1f ms"
+        % (name, t_sort * 1e3, t_bh * 1e3))
+
+    # the q stage both ways in this one process: the host route as fit_transform had it (argsort,
+    # gather, bb.benjamini_hochberg, scatter; p already on the host) against the device route
+    # (bb_sig_q_values on the resident list, and the read-back of q)
+    def host_q():
+        o = numpy.argsort(p, kind="stable")
+        q = numpy.empty_like(p)
+        q[o] = bb.benjamini_hochberg(p[o], f.n_tests_)
+        return q
+
+    host = [timed(host_q) for _ in range(5)]
+    res = fh.significance_list(X, n, k_lo, k_hi, bias, f.bias_range, f.prior_by_distance_, f.n_reads_)
+    res.q_values(f.n_tests_)                                            # warm
+    same = numpy.array_equal(res.read_q().view(numpy.uint64), host_q().view(numpy.uint64))
+    sorts, scans, calls, reads = [], [], [], []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        a, b = res.q_values(f.n_tests_)
+        t1 = time.perf_counter()
+        res.read_q()
+        t2 = time.perf_counter()
+        sorts.append(a), scans.append(b), calls.append(t1 - t0), reads.append(t2 - t1)
+    res.close()
+    dev = [c + r for c, r in zip(calls, reads)]
+    med = statistics.median
+    say("%s: device q stage: keys + sort %.3f ms, gather + scan + scatter %.3f ms (HIP events); the call "
+        "%.2f ms, the read-back of q %.2f ms (wall clock, medians of 5); same bits as the host route: %s"
+        % (name, med(sorts), med(scans), med(calls) * 1e3, med(reads) * 1e3, same))
+    say("%s: q stage, host (argsort, gather, BH round trip, scatter) %.1f ms (%.1f to %.1f over 5); device "
+        "(call + read-back) %.2f ms (%.2f to %.2f over 5): %.1f x, ranges %s"
+        % (name, med(host) * 1e3, min(host) * 1e3, max(host) * 1e3, med(dev) * 1e3, min(dev) * 1e3,
+           max(dev) * 1e3, med(host) / med(dev), "apart" if max(dev) < min(host) else "OVERLAP"))
+    t_all = median_of(lambda: f.fit_transform(X, biases=bias, **f_args))
+    t_sel = median_of(lambda: f.fit_transform(X, biases=bias, q_max=0.01, **f_args))
+    say("%s: fit_transform %.1f ms (q stage on the device: sort %.3f + scan %.3f ms by its events); with "
+        "q_max = 0.01 %.1f ms (%d selected of %d listed)"
+        % (name, t_all * 1e3, f.sort_ms_, f.bh_ms_, t_sel * 1e3, f.n_selected_, f.n_listed_))
     return f, out
 
 
