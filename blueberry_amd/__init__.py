@@ -16,6 +16,9 @@ Net-new (the reference has no solver; docs/SPEC.md):
     shortest_paths                sparse map -> complete wish distances (SPEC 2.1.1)
     balance_triples, DeviceTriples
                                   ICE bias and expected straight from a pixel list (SPEC 2.5.3)
+    landmark_start, landmark_coefficients, GeodesicRows
+                                  a start for sparse maps that holds the global fold: landmark MDS
+                                  over device shortest paths from a pixel list (SPEC 2.1.2, 2.5.4)
     FitHiC, binomial_sf           Fit-Hi-C p- and q-values of a resident raw map (SPEC 2.9; the
                                   computation of blueberry/fithic.py:76-108 without its files)
     q_values                      Benjamini-Hochberg q-values of p-values in any order: stable
@@ -32,8 +35,9 @@ from .band import count_band_regions  # noqa: F401
 from .datatypes import (ContactMap, EigenNoConvergence, FithicContactMap,  # noqa: F401
                         shortest_paths)
 from .fithic import FitHiC, binomial_sf  # noqa: F401
-from .solver import (DeviceTriples, FitScore, HipEngine, RankDeficient,  # noqa: F401
-                     StructureSolver, TriplesBalance, balance_triples)
+from .solver import (DeviceTriples, FitScore, GeodesicRows, HipEngine, RankDeficient,  # noqa: F401
+                     StructureSolver, TriplesBalance, balance_triples, landmark_coefficients,
+                     landmark_start)
 from .stats import benjamini_hochberg, downsample, q_values  # noqa: F401
 
 __version__ = "0.1.0"

@@ -126,6 +126,16 @@ SIGNATURES = {
                                    ctypes.POINTER(ctypes.c_uint8), p_i64, p_dbl]),
     "bb_triples_expected": (c_int, [c_void_p, c_i64, p_dbl, p_dbl, p_i64]),
     "bb_triples_pairs": (c_int, [c_void_p, c_i64, p_i64]),
+    "bb_triples_edge_degrees": (c_int, [c_void_p, c_i64, c_int, c_dbl, p_dbl, p_dbl, p_i64]),
+    "bb_triples_paths": (c_int, [c_void_p, c_i64, c_int, c_dbl, p_dbl, p_dbl, p_i64, c_i64,
+                                 ctypes.POINTER(c_void_p)]),
+    "bb_paths_info": (c_int, [c_void_p, p_i64, p_i64, p_i64, p_i64]),
+    "bb_paths_reached": (c_int, [c_void_p, p_i64]),
+    "bb_paths_read": (c_int, [c_void_p, p_dbl]),
+    "bb_paths_read_columns": (c_int, [c_void_p, p_i64, c_i64, p_dbl]),
+    "bb_paths_place": (c_int, [c_void_p, p_dbl, p_dbl, p_dbl, ctypes.POINTER(ctypes.c_uint8)]),
+    "bb_paths_timing": (c_int, [c_void_p, p_dbl, p_dbl]),
+    "bb_paths_destroy": (c_int, [c_void_p]),
     "bb_binomial_sf": (c_int, [p_i64, c_dbl, p_dbl, p_dbl, c_i64, c_int]),
     "bb_cm_significance": (c_int, [c_void_p, c_i64, c_i64, c_i64, p_dbl, c_dbl, c_dbl, p_dbl, c_dbl,
                                    ctypes.POINTER(c_void_p)]),

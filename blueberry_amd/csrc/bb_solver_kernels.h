@@ -24,6 +24,7 @@
 
 #include <type_traits>
 
+#include "bb_wish.h"
 #include "blueberry_hip.h"
 
 namespace {
@@ -47,22 +48,12 @@ struct Traits<double> {
     static __device__ __forceinline__ double eps2() { return 1e-300; }
 };
 
-// Wish distances below this are stored as 0 = "no constraint" by every pack kernel: far
-// below the distance floor eps of SPEC 2.2 (1e-15 / 1e-150), and what lets the kernels
-// turn "delta > 0" into a 0/1 weight with one clamped multiply (delta * 2^100 resp.
-// 2^1000 saturates to 1 for every delta that survives the flush).
-template <typename T>
-__host__ __device__ constexpr double wish_floor() { return sizeof(T) == 4 ? 1e-30 : 1e-290; }
-// ... and the largest one: a float64 distance far above the largest finite T would become
-// +inf in the cast (1e39 as 'wish', the count 1e-120) -- a pair that counts as a constraint and
-// makes every stress non-finite.  Every distance above this value AS A DOUBLE is "no
-// constraint", like one below the floor: the doubles within half a float32 step above
-// FLT_MAX, which the cast would round down to it, included; so is +inf (generated coordinates
-// whose squared separation overflows).
-template <typename T>
-__host__ __device__ constexpr double wish_ceiling() {
-    return sizeof(T) == 4 ? 3.4028234663852886e38 : 1.7976931348623157e308;
-}
+// The wish floor and ceiling, the flush and the value rule: bb_wish.h (shared with the
+// shortest paths over triples).
+using bb::flush_wish;
+using bb::wish_ceiling;
+using bb::wish_floor;
+using bb::wish_from_value;
 
 // Shape of a unit (8 KiB = 8 wave-loads) and of a strip.  LPR 16-byte loads per lane
 // and matrix row, VW = 64 * VPL * LPR columns per strip, RPU = 8 / LPR matrix rows.
@@ -1498,25 +1489,8 @@ __global__ __launch_bounds__(256) void group_apply_kernel(
 // --------------------------------------------------------------------------
 // packing kernels
 // --------------------------------------------------------------------------
-// What becomes a stored wish distance -- the ONE place that says so; the sweep's 0/1 weight
-// depends on the flush (wish_floor).  flush_wish: a distance below the floor is 0 = "no
-// constraint" (fp32: the kernel's 0/1 weight needs delta >= 2^-100; anything that small is
-// below the distance clamp eps = 1e-15 anyway), and so is one above the largest finite T
-// (wish_ceiling: the units never hold +inf).  wish_from_value: an input value v of `kind` --
-// finite and positive, else no constraint; counts -> v^(-1/alpha) -- then the flush.
-template <typename T>
-__device__ __forceinline__ T flush_wish(double v) {
-    return (T)((v < wish_floor<T>() || v > wish_ceiling<T>()) ? 0.0 : v);
-}
-template <typename T>
-__device__ __forceinline__ T wish_from_value(double v, int kind, double neg_inv_alpha) {
-    const bool ok = (v > 0.0) && (v <= 1.7976931348623157e308);  // finite, positive
-    if (!ok)
-        v = 0.0;
-    else if (kind == BB_KIND_COUNTS)
-        v = pow(v, neg_inv_alpha);
-    return flush_wish<T>(v);
-}
+// What becomes a stored wish distance -- flush_wish and wish_from_value -- is said in ONE
+// place, bb_wish.h; the sweep's 0/1 weight depends on the flush (wish_floor).
 
 // The cell walk of unit `dsc` = {i0, j0} by a workgroup of 256 threads: f(e, i, j, stored) for
 // the cells e = r * VW + c of the thread, (i, j) = (i0 + r, j0 + c) its bin pair, stored =

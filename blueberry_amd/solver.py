@@ -130,6 +130,42 @@ class DeviceTriples(object):
         from .fithic import _significance
         return _significance(self, int(map_bins), kwargs)
 
+    def _graph_arguments(self, n_nodes, kind, alpha, KRnorm, KRexpected):
+        """(n_nodes, kind code, alpha, KR pointers) of the graph calls, checked."""
+        n = int(n_nodes)
+        if n < 1:
+            raise ValueError("n_nodes must be at least 1")
+        if kind not in _KINDS:
+            raise ValueError("kind must be 'counts' or 'wish'")
+        if not float(alpha) > 0:
+            raise ValueError("alpha must be positive")
+        kr, ke = _kr_pair(KRnorm, KRexpected, n)
+        return n, _KINDS[kind], float(alpha), kr, ke
+
+    def edge_degrees(self, n_nodes, kind="counts", alpha=3.0, KRnorm=None, KRexpected=None):
+        """The number of graph edges of every node 0 .. n_nodes - 1 (`bb_triples_edge_degrees`,
+        docs/SPEC.md 2.1.2): the stored off-diagonal cells whose wish distance -- under `kind`,
+        `alpha` and the KR vectors, as `fit_triples` forms it -- is finite and positive.  int64."""
+        n, kind, alpha, kr, ke = self._graph_arguments(n_nodes, kind, alpha, KRnorm, KRexpected)
+        deg = numpy.zeros(n, dtype=numpy.int64)
+        _lib.check(self._lib.bb_triples_edge_degrees(self._h, n, kind, alpha, kr, ke,
+                                                     deg.ctypes.data_as(_lib.p_i64)),
+                   "bb_triples_edge_degrees")
+        return deg
+
+    def shortest_paths(self, n_nodes, sources, kind="counts", alpha=3.0, KRnorm=None, KRexpected=None):
+        """The shortest-path lengths from the nodes `sources` (any order, repeats allowed, at most
+        `GeodesicRows.MAX_SOURCES`) to all n_nodes nodes of the graph whose edges are the triples'
+        wish distances (`bb_triples_paths`, docs/SPEC.md 2.1.2), without the dense matrix: a
+        `GeodesicRows`, resident on the device.  Bit for bit scipy's Dijkstra in float64."""
+        n, kind, alpha, kr, ke = self._graph_arguments(n_nodes, kind, alpha, KRnorm, KRexpected)
+        src = numpy.ascontiguousarray(sources, dtype=numpy.int64).ravel()
+        h = _lib.c_void_p()
+        _lib.check(self._lib.bb_triples_paths(self._h, n, kind, alpha, kr, ke,
+                                              src.ctypes.data_as(_lib.p_i64), src.shape[0], h),
+                   "bb_triples_paths")
+        return GeodesicRows(h)
+
     def close(self):
         if self._h:
             self._lib.bb_triples_destroy(self._h)
@@ -140,6 +176,198 @@ class DeviceTriples(object):
             self.close()
         except Exception:
             pass
+
+
+class GeodesicRows(object):
+    """What `DeviceTriples.shortest_paths` returns: the (n_sources, n_nodes) float64 geodesics,
+    resident on the device as a `bb_paths`, which owns its memory (it may outlive the triples).
+    `sweeps_`: Bellman-Ford sweeps made (not reproducible: the distances are updated in place);
+    `unreachable_`: (source, node) pairs without a path.  A context manager; `close()` frees it,
+    any other call after that is a ValueError."""
+    MAX_SOURCES = 1024                      # BB_PATHS_MAX_SOURCES
+
+    def __init__(self, handle):
+        self._lib = _lib.load()
+        self._h = handle
+        ns, nn, sw, un = _lib.c_i64(), _lib.c_i64(), _lib.c_i64(), _lib.c_i64()
+        _lib.check(self._lib.bb_paths_info(self._h, ns, nn, sw, un), "bb_paths_info")
+        self.n_sources, self.n_nodes = int(ns.value), int(nn.value)
+        self.sweeps_, self.unreachable_ = int(sw.value), int(un.value)
+
+    def _open(self):
+        if not self._h:
+            raise ValueError("these geodesic rows are closed")
+        return self._h
+
+    def to_host(self):
+        """(n_sources, n_nodes): 0 where no path exists and on a source's own node."""
+        out = numpy.empty((self.n_sources, self.n_nodes), dtype=numpy.float64)
+        _lib.check(self._lib.bb_paths_read(self._open(), _lib.as_f64_ptr(out)), "bb_paths_read")
+        return out
+
+    def columns(self, nodes):
+        """(n_sources, len(nodes)): the distances to the listed nodes alone."""
+        idx = numpy.ascontiguousarray(nodes, dtype=numpy.int64).ravel()
+        out = numpy.empty((self.n_sources, idx.shape[0]), dtype=numpy.float64)
+        _lib.check(self._lib.bb_paths_read_columns(self._open(), idx.ctypes.data_as(_lib.p_i64),
+                                                   idx.shape[0], _lib.as_f64_ptr(out)),
+                   "bb_paths_read_columns")
+        return out
+
+    def reached(self):
+        """int64 (n_sources,): the nodes every source has a path to, its own included."""
+        out = numpy.zeros(self.n_sources, dtype=numpy.int64)
+        _lib.check(self._lib.bb_paths_reached(self._open(), out.ctypes.data_as(_lib.p_i64)),
+                   "bb_paths_reached")
+        return out
+
+    def place(self, coef, mu, out=None):
+        """Landmark placement on the device (`bb_paths_place`): (xyz, placed).  xyz[j] =
+        -1/2 sum_a coef[a] (D[j][a]^2 - mu[a]) for every node with a path from every source that
+        takes part (a source whose coef row and mu are 0 does not); the other rows keep what
+        `out` -- (n_nodes, 3) float64, C-ordered; None: zeros -- held.  placed: bool."""
+        import ctypes
+        coef = numpy.ascontiguousarray(coef, dtype=numpy.float64)
+        mu = numpy.ascontiguousarray(mu, dtype=numpy.float64)
+        if coef.shape != (self.n_sources, 3) or mu.shape != (self.n_sources,):
+            raise ValueError("coef must have shape (n_sources, 3) and mu (n_sources,)")
+        if out is None:
+            out = numpy.zeros((self.n_nodes, 3), dtype=numpy.float64)
+        if (not isinstance(out, numpy.ndarray) or out.dtype != numpy.float64
+                or out.shape != (self.n_nodes, 3) or not out.flags.c_contiguous):
+            raise ValueError("out must be a C-ordered float64 array of shape (n_nodes, 3)")
+        placed = numpy.zeros(self.n_nodes, dtype=numpy.uint8)
+        _lib.check(self._lib.bb_paths_place(self._open(), _lib.as_f64_ptr(coef), _lib.as_f64_ptr(mu),
+                                            _lib.as_f64_ptr(out),
+                                            placed.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
+                   "bb_paths_place")
+        return out, placed.astype(bool)
+
+    def timing(self):
+        """(weights_ms, sweeps_ms) of the call that made these rows, by HIP events."""
+        w, s = _lib.c_dbl(), _lib.c_dbl()
+        _lib.check(self._lib.bb_paths_timing(self._open(), w, s), "bb_paths_timing")
+        return float(w.value), float(s.value)
+
+    def close(self):
+        if self._h:
+            self._lib.bb_paths_destroy(self._h)
+            self._h = _lib.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def landmark_choice(live, n_landmarks):
+    """The landmarks of docs/SPEC.md 2.5.4 among the live nodes `live` (ascending):
+    L = min(n_landmarks, len(live)) of them, landmark k = live[((2 k + 1) len(live)) // (2 L)]."""
+    live = numpy.asarray(live, dtype=numpy.int64)
+    L = min(int(n_landmarks), live.shape[0])
+    k = numpy.arange(L, dtype=numpy.int64)
+    return live[((2 * k + 1) * live.shape[0]) // (2 * max(L, 1))]
+
+
+def landmark_coefficients(G_LL):
+    """(coef, mu) of landmark MDS (de Silva & Tenenbaum) from the (L, L) geodesics among the
+    landmarks, docs/SPEC.md 2.5.4 -- the only place the rule lives; pure numpy.
+    Delta2 = (G^2 + G^2.T) / 2, mu = its column means, B = -J Delta2 J / 2, numpy.linalg.eigh,
+    the three largest eigenvalues l_c with their vectors v_c, each vector's sign such that its
+    entry of largest magnitude (lowest index on ties) is positive; coef[:, c] = v_c / sqrt(l_c),
+    a zero column where l_c <= 1e-12 l_1 (a flat or collinear map).  A node with squared
+    geodesics d2 to the landmarks is placed at -coef.T (d2 - mu) / 2."""
+    G = numpy.asarray(G_LL, dtype=numpy.float64)
+    if G.ndim != 2 or G.shape[0] != G.shape[1] or G.shape[0] < 1:
+        raise ValueError("G_LL must be a square (L, L) array")
+    L = G.shape[0]
+    sq = G * G
+    d2 = 0.5 * (sq + sq.T)
+    mu = d2.mean(axis=0)
+    J = numpy.eye(L) - 1.0 / L
+    B = -0.5 * (J @ d2 @ J)
+    w, V = numpy.linalg.eigh(B)
+    order = numpy.argsort(w, kind="stable")[::-1][:3]
+    coef = numpy.zeros((L, 3))
+    top = w[order[0]]
+    for c, q in enumerate(order):
+        if top > 0.0 and w[q] > 1e-12 * top:
+            v = V[:, q]
+            if v[numpy.argmax(numpy.abs(v))] < 0.0:
+                v = -v
+            coef[:, c] = v / numpy.sqrt(w[q])
+    return coef, mu
+
+
+class LandmarkInfo(object):
+    """What `landmark_start(..., return_info=True)` tells besides the start: `landmarks_` (the L
+    landmark nodes), `kept_` (bool per landmark: reached by the main one), `placed_` (bool per
+    node), `sweeps_` and `unreachable_` of the shortest paths."""
+
+    def __init__(self, landmarks, kept, placed, sweeps, unreachable):
+        self.landmarks_, self.kept_, self.placed_ = landmarks, kept, placed
+        self.sweeps_, self.unreachable_ = sweeps, unreachable
+
+
+def _check_n_landmarks(n_landmarks):
+    if (isinstance(n_landmarks, bool) or not isinstance(n_landmarks, (int, numpy.integer))
+            or not 4 <= int(n_landmarks) <= GeodesicRows.MAX_SOURCES):
+        raise ValueError("n_landmarks must be an int in [4, %d]" % GeodesicRows.MAX_SOURCES)
+    return int(n_landmarks)
+
+
+def landmark_start(triples, resolution, n_bins, n_landmarks=64, kind="counts", alpha=3.0, KRnorm=None,
+                   KRexpected=None, seed=0, device=0, return_info=False):
+    """A start for sparse maps that holds the global fold (docs/SPEC.md 2.5.4): landmark MDS
+    (L-Isomap) over the graph of the triples' wish distances, never forming the dense matrix.
+    Landmarks are spread evenly over the bins that have an edge; shortest paths run from them on
+    the device (`DeviceTriples.shortest_paths`); the landmark that reaches the most nodes (the
+    lowest on ties) is the main one, landmarks it does not reach are dropped (fewer than 4 left:
+    ValueError); `landmark_coefficients` of the kept landmarks' mutual geodesics place every node
+    the main landmark reaches, on the device (the (L, N) array never travels to the host).  Nodes
+    that are not placed -- dead bins, small components -- keep the rows of the seeded default start
+    `numpy.random.default_rng(seed).standard_normal((n_bins + 1, 3))`.
+    Returns the (n_bins + 1, 3) float64 array; with return_info=True, (array, `LandmarkInfo`).
+    `triples` may be a `DeviceTriples` (its own resolution and device are used; it stays open)."""
+    from .datatypes import _pick_device
+    n_landmarks = _check_n_landmarks(n_landmarks)
+    n = int(n_bins) + 1
+    if n < 1:
+        raise ValueError("n_bins must not be negative")
+    own = not isinstance(triples, DeviceTriples)
+    if own and int(resolution) <= 0:
+        raise ValueError("resolution must be positive")
+    dev = DeviceTriples(_check_triples(triples), resolution, _pick_device(device)) if own else triples
+    graph = dict(kind=kind, alpha=alpha, KRnorm=KRnorm, KRexpected=KRexpected)
+    try:
+        live = numpy.flatnonzero(dev.edge_degrees(n, **graph) > 0)
+        landmarks = landmark_choice(live, n_landmarks)
+        few = "the map is too disconnected for a landmark start: %s (need 4)"
+        if landmarks.shape[0] < 4:
+            raise ValueError(few % ("%d bins have an edge" % live.shape[0]))
+        with dev.shortest_paths(n, landmarks, **graph) as rows:
+            main = int(numpy.argmax(rows.reached()))           # (the lowest index on ties)
+            G = rows.columns(landmarks)
+            kept = G[main] > 0.0
+            kept[main] = True
+            if int(kept.sum()) < 4:
+                raise ValueError(few % ("%d landmarks lie in the largest component" % int(kept.sum())))
+            coef, mu = numpy.zeros((landmarks.shape[0], 3)), numpy.zeros(landmarks.shape[0])
+            coef[kept], mu[kept] = landmark_coefficients(G[numpy.ix_(kept, kept)])
+            start = numpy.random.default_rng(int(seed)).standard_normal((n, 3))
+            start, placed = rows.place(coef, mu, out=start)
+            info = LandmarkInfo(landmarks, kept, placed, rows.sweeps_, rows.unreachable_)
+    finally:
+        if own:
+            dev.close()
+    return (start, info) if return_info else start
 
 
 def _check_triples(triples):
@@ -1145,9 +1373,21 @@ class StructureSolver(object):
         None: exactly n_iter steps.  Otherwise stop as soon as the relative stress
         decrease of one step is <= tol, checked every `check_every` steps (n_iter is
         then the maximum); `n_iter_` tells how many were run.
-    init : 'random' or 'spectral'
+    init : 'random', 'spectral', 'landmark' or ('landmark', n_landmarks)
         Start used when `fit()` gets no `init=` array: seeded standard normal, or
-        classical MDS computed on the device (`spectral_init`).
+        classical MDS computed on the device (`spectral_init`), or -- for the sparse inputs,
+        `fit_triples` and `fit(scipy.sparse)` -- landmark MDS over shortest paths on the stored
+        pairs (`landmark_start`, SPEC 2.5.4), which gives a map with counts only between nearby
+        bins its global fold without the dense matrix.  'landmark' takes 64 landmarks; the
+        tuple form another number, an int in [4, 1024] (`n_landmarks` reads it back; it is part
+        of `init` and not a constructor argument of its own, so that clones carry it).  The
+        start is computed once, on devices[0] of `devices=` or on the rank's own device, under
+        this solver's kind and alpha and the bias the fit uses (KR vectors, `balance=`), and
+        handed to the unchanged fit as `init=`; `landmarks_` and `landmark_placed_` tell which
+        bins were landmarks and which were placed.  Not for dense inputs or a ContactMap
+        (`complete='shortest_path'` is their route, or init='spectral'), not with
+        `complete='shortest_path'`, `fit_many`, or an engine without a device: ValueError.
+        The stored pairs alone do not hold the fold for ever (SPEC 2.5.4): few iterations.
     degree_steps : bool
         A step per bin from the map itself (SPEC 2.4.1): bin i steps by 1 / (2 (deg_i + 1)),
         deg_i = the number of pairs that constrain it (counted on the device, summed over
@@ -1235,8 +1475,11 @@ class StructureSolver(object):
         if int(check_every) < 1:
             raise ValueError("check_every must be >= 1")
         self.tol, self.check_every = (None if tol is None else float(tol)), int(check_every)
-        if init not in ("random", "spectral"):
-            raise ValueError("init must be 'random' or 'spectral' (or pass init= to fit())")
+        if isinstance(init, tuple) and len(init) == 2 and init[0] == "landmark":
+            init = ("landmark", _check_n_landmarks(init[1]))
+        elif not (isinstance(init, str) and init in ("random", "spectral", "landmark")):
+            raise ValueError("init must be 'random', 'spectral', 'landmark' or ('landmark', "
+                             "n_landmarks) (or pass init= to fit())")
         self.init = init
         if int(spectral_iter) < 0 or not 0.0 <= float(spectral_tol) < 1.0:
             raise ValueError("need spectral_iter >= 0 and 0 <= spectral_tol < 1")
@@ -1263,6 +1506,34 @@ class StructureSolver(object):
             return int(self.device)
         return int(os.environ.get("LOCAL_RANK", "0")) if world > 1 else 0
 
+    @property
+    def n_landmarks(self):
+        """The landmarks of init='landmark' (64) / ('landmark', n); None for another init."""
+        if self.init == "landmark":
+            return 64
+        return self.init[1] if isinstance(self.init, tuple) else None
+
+    def _landmark_refusal(self, why, instead):
+        return ValueError("init='landmark' %s; use %s" % (why, instead))
+
+    def _check_landmark_route(self, complete):
+        """The refusals of a landmark start that need no device (the caller has a sparse input)."""
+        if complete is not None:
+            raise self._landmark_refusal("does not go with complete='shortest_path', which "
+                                         "determines the fold itself", "init='random' or 'spectral'")
+        if not hasattr(self._engine_factory, "set_wish_triples"):
+            raise self._landmark_refusal("runs on the device and this solver's engine has none",
+                                         "init='spectral'")
+
+    def _landmark_init(self, dev, n_bins, KRnorm, KRexpected):
+        """The landmark start of the map in `dev` (a DeviceTriples) under this solver's kind and
+        alpha and the fit's KR vectors; `landmarks_` and `landmark_placed_` stay on the solver."""
+        start, info = landmark_start(dev, dev.resolution, n_bins, n_landmarks=self.n_landmarks,
+                                     kind=self.kind, alpha=self.alpha, KRnorm=KRnorm,
+                                     KRexpected=KRexpected, seed=self.seed, return_info=True)
+        self.landmarks_, self.landmark_placed_ = info.landmarks_, info.placed_
+        return start
+
     def fit(self, X, init=None, complete=None):
         """Solve for the structure of `X`: a ContactMap, a square ndarray, or a
         scipy.sparse matrix (symmetric; either triangle is enough; of several
@@ -1280,8 +1551,11 @@ class StructureSolver(object):
             `devices=[...]` the completion runs once on devices[0]; inside a torch.distributed
             job every rank completes the same input on its own GPU.  The dense matrix and a
             work matrix of its size must fit on one device: a whole-genome blocked-sparse map
-            (720 GB dense at 10 kb) cannot be completed this way (MemoryError)."""
+            (720 GB dense at 10 kb) cannot be completed this way (MemoryError); init='landmark'
+            (SPEC 2.5.4) is the route of such a map to its global fold."""
         _check_complete(complete)
+        if init is None and self.n_landmarks is not None:
+            init = self._landmark_init_of_map(X, complete)
         if complete is None:
             source, n = self._map_source(X)
             return self._fit_impl(source, n, init, None, None)
@@ -1289,6 +1563,27 @@ class StructureSolver(object):
         self.completed_unreachable_pairs_ = cm.unreachable_pairs_
         source, n = self._map_source(cm)
         return self._fit_impl(source, n, init, None, None, kind="wish")
+
+    def _landmark_init_of_map(self, X, complete):
+        """fit(X) under init='landmark': the start of a scipy.sparse X, whose COO entries are the
+        triples [row, col, value] at resolution 1 over N - 1 bins (an entry that is not finite is
+        no constraint there and no edge here); any other input is refused."""
+        matrix = X if hasattr(X, "tocoo") else None     # (a ContactMap's matrix is never read)
+        if matrix is None:
+            raise self._landmark_refusal("needs a sparse input (fit_triples, or fit of a "
+                                         "scipy.sparse matrix), not a dense array or a ContactMap",
+                                         "complete='shortest_path' or init='spectral'")
+        self._check_landmark_route(complete)
+        coo = matrix.tocoo()
+        n = _square_bins(coo.shape)
+        vals = numpy.asarray(coo.data, dtype=numpy.float64)
+        triples = numpy.stack([coo.row.astype(numpy.float64), coo.col.astype(numpy.float64),
+                               numpy.where(numpy.isfinite(vals), vals, 0.0)], axis=1)
+        dev = DeviceTriples(triples, 1, self._completion_device())
+        try:
+            return self._landmark_init(dev, n - 1, None, None)
+        finally:
+            dev.close()
 
     def _completion_device(self):
         """Where a fit's completion runs: devices[0] of a group, else this rank's device."""
@@ -1554,6 +1849,9 @@ class StructureSolver(object):
         device (one-device fits without `complete`), which stays open."""
         _check_complete(complete)
         n = int(n_bins) + 1
+        landmark = init is None and self.n_landmarks is not None
+        if landmark:
+            self._check_landmark_route(complete)
         if balance is not None:
             if KRnorm is not None or KRexpected is not None:
                 raise ValueError("balance= computes the bias itself: it takes no KRnorm / KRexpected")
@@ -1590,6 +1888,8 @@ class StructureSolver(object):
                     dev.per_device = per_device
                     if balance is not None:
                         KRnorm, KRexpected = self._balance_on(dev, int(n_bins), bal_args, bal_expected)
+                    if landmark:
+                        init = self._landmark_init(dev, int(n_bins), KRnorm, KRexpected)
                     return self._fit_impl(dev, n, init, KRnorm, KRexpected)
                 finally:
                     for t in per_device.values():
@@ -1600,6 +1900,8 @@ class StructureSolver(object):
             try:
                 if balance is not None:
                     KRnorm, KRexpected = self._balance_on(dev, int(n_bins), bal_args, bal_expected)
+                if landmark:
+                    init = self._landmark_init(dev, int(n_bins), KRnorm, KRexpected)
                 return self._fit_impl(dev, n, init, KRnorm, KRexpected)
             finally:
                 if own:
@@ -1640,6 +1942,9 @@ class StructureSolver(object):
             raise ValueError("fit_many with devices= / n_gpus= is not supported: fit_many runs "
                              "on one device, or one per rank of a torch.distributed job")
         _check_complete(complete)
+        if self.n_landmarks is not None:
+            raise self._landmark_refusal("is not for fit_many, which packs dense blocks",
+                                         "complete='shortest_path' or init='spectral'")
         if not hasattr(self._engine_factory, "set_maps"):
             raise TypeError("fit_many needs an engine that holds several maps (HipEngine)")
         maps = list(maps)

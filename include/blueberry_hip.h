@@ -662,6 +662,70 @@ BB_API int bb_triples_balance(bb_triples *t, int64_t n_bins, int64_t ignore_diag
 BB_API int bb_triples_expected(bb_triples *t, int64_t n_bins, const double *bias, double *sums,
                                int64_t *counts);
 BB_API int bb_triples_pairs(bb_triples *t, int64_t n_bins, int64_t *n_pairs);
+/* Shortest paths from a few sources over the graph resident triples define, without the dense
+ * matrix (docs/SPEC.md 2.1.2) -- the geodesic rows of a landmark start (SPEC 2.5.4).
+ * Nodes are 0 .. n_nodes - 1 (fit_triples' matrix size, n_bins + 1).  The calls use the handle's
+ * canonical index for n_nodes (bb_triples_balance's rules: nan_to_num, the binning, the LAST
+ * triple of a pair wins; built if it is not there; a later call with another size rebuilds it).
+ * A position that maps to a bin outside [0, n_nodes): BB_ERR_INVALID, as
+ * bb_solver_set_wish_triples refuses a bin outside its map (here a diagonal triple too).  There is
+ * one undirected edge per stored off-diagonal cell; its weight is the wish distance of SPEC 2.1 in
+ * float64, formed as bb_solver_set_wish_triples forms it before rounding to the run's dtype: the
+ * value, divided by KRnorm[i] * KRnorm[j] * KRexpected[j - i] (i < j; n_nodes doubles each, both
+ * or neither) and nan_to_num'ed if the vectors are given, then c^(-1/alpha) for BB_KIND_COUNTS or
+ * the value itself for BB_KIND_WISH, then the float64 flush.  Anything that is not a finite
+ * positive distance is no edge.  alpha <= 0 (either kind), an unknown kind: BB_ERR_INVALID.
+ *
+ * bb_triples_edge_degrees: deg[i] = the number of edges of node i, exact; n_nodes values.
+ * bb_triples_paths: the lengths of the shortest paths from sources[a], a < n_sources, to every
+ * node.  1 <= n_sources <= BB_PATHS_MAX_SOURCES; sources may repeat and come in any order; one
+ * outside [0, n_nodes) is BB_ERR_INVALID.  Multi-source Bellman-Ford over the index: one launch
+ * per sweep, a wave per segment of a row and 64 sources, a batch of sweeps per read of the
+ * "changed" flags, the end at the first sweep that changes nothing and after n_nodes sweeps at
+ * the latest.  Float64; the only atomic is an integer min on the bit pattern of a non-negative
+ * double.  The distances are updated in place, and the fixed point of d[v] = min(d[v], fl(d[u] +
+ * w)) is unique for positive weights: the results are, bit for bit and on every run, those of
+ * Dijkstra's algorithm in float64 (scipy.sparse.csgraph.dijkstra); the NUMBER of sweeps depends
+ * on the order the hardware runs the waves in and is NOT reproducible.  Device memory: 8 B x
+ * n_nodes x (n_sources rounded up to 64), kept by the result, plus 8 B per directed entry of the
+ * index during the call; the size is checked first, and what cannot be had is BB_ERR_NOMEM with
+ * the sizes in the message, nothing half-built left on the handle (a complete index stays).
+ * Nothing is allocated per sweep.
+ * The result lives in a bb_paths, which owns its device memory and outlives the triples (the
+ * lifetime rules of bb_sig); *out is NULL after an error.
+ *   bb_paths_info     n_sources, n_nodes, sweeps (launches made, the confirming one included; 0
+ *                     for a graph without stored cells), unreachable (the (source, node) pairs
+ *                     without a path); each may be NULL
+ *   bb_paths_read     dist (n_sources, n_nodes) float64 to the host, in SPEC 2.1.1's convention:
+ *                     0 where no path exists ("no constraint") and on a source's own node
+ *   bb_paths_read_columns  the same for the m nodes listed: out (n_sources, m); a node outside
+ *                     [0, n_nodes) is BB_ERR_INVALID
+ *   bb_paths_reached  reached[a] = the number of nodes source a has a path to, its own included;
+ *                     n_sources values
+ *   bb_paths_place    landmark placement on the device: for every node j with a path from EVERY
+ *                     source that takes part, xyz[j][c] = -1/2 sum_a coef[a][c] (D[j][a]^2 -
+ *                     mu[a]), a ascending, float64, placed[j] = 1; else placed[j] = 0 and xyz[j]
+ *                     is left as it was.  A source whose coef row and mu are all 0 takes no part,
+ *                     in the sum or in `placed` (a landmark that was dropped).
+ *                     coef (n_sources, 3), mu n_sources, xyz (n_nodes, 3), placed n_nodes: host.
+ *   bb_paths_timing   HIP-event times (ms) of the call: the weights, and all sweeps
+ *   bb_paths_destroy  frees it (NULL is fine) */
+#define BB_PATHS_MAX_SOURCES 1024
+typedef struct bb_paths bb_paths;
+BB_API int bb_triples_edge_degrees(bb_triples *t, int64_t n_nodes, int kind, double alpha,
+                                   const double *KRnorm, const double *KRexpected, int64_t *deg);
+BB_API int bb_triples_paths(bb_triples *t, int64_t n_nodes, int kind, double alpha,
+                            const double *KRnorm, const double *KRexpected, const int64_t *sources,
+                            int64_t n_sources, bb_paths **out);
+BB_API int bb_paths_info(const bb_paths *p, int64_t *n_sources, int64_t *n_nodes, int64_t *sweeps,
+                         int64_t *unreachable);
+BB_API int bb_paths_reached(const bb_paths *p, int64_t *reached);
+BB_API int bb_paths_read(const bb_paths *p, double *dist);
+BB_API int bb_paths_read_columns(const bb_paths *p, const int64_t *nodes, int64_t m, double *out);
+BB_API int bb_paths_place(const bb_paths *p, const double *coef, const double *mu, double *xyz,
+                          uint8_t *placed);
+BB_API int bb_paths_timing(const bb_paths *p, double *weights_ms, double *sweeps_ms);
+BB_API int bb_paths_destroy(bb_paths *p);
 /* The Fit-Hi-C significance call on a resident map (docs/SPEC.md 2.9; reference:
  * blueberry/fithic.py:413-435, one text line at a time through scipy.special.bdtrc).
  *
