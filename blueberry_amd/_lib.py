@@ -136,6 +136,11 @@ SIGNATURES = {
     "bb_paths_place": (c_int, [c_void_p, p_dbl, p_dbl, p_dbl, ctypes.POINTER(ctypes.c_uint8)]),
     "bb_paths_timing": (c_int, [c_void_p, p_dbl, p_dbl]),
     "bb_paths_destroy": (c_int, [c_void_p]),
+    "bb_solver_set_anchors": (c_int, [c_void_p, c_void_p, ctypes.POINTER(ctypes.c_uint8), c_dbl]),
+    "bb_solver_anchor_sums": (c_int, [c_void_p, p_dbl, c_i64]),
+    "bb_solver_anchor_stress": (c_int, [c_void_p, p_dbl]),
+    "bb_solver_anchor_info": (c_int, [c_void_p, p_i64, p_i64, p_i64]),
+    "bb_solver_measure_anchors": (c_int, [c_void_p, c_int, p_dbl]),
     "bb_binomial_sf": (c_int, [p_i64, c_dbl, p_dbl, p_dbl, c_i64, c_int]),
     "bb_cm_significance": (c_int, [c_void_p, c_i64, c_i64, c_i64, p_dbl, c_dbl, c_dbl, p_dbl, c_dbl,
                                    ctypes.POINTER(c_void_p)]),

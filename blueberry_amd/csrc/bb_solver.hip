@@ -3,7 +3,8 @@
 // buffers), kernel launches, the multi-rank exchanges (RCCL, peer arenas) and the
 // bb_solver_* / bb_comm_* entry points of include/blueberry_hip.h, and the groups of solvers
 // one process drives on several devices (bb_group_*).  The kernels are in
-// bb_solver_kernels.h.  gfx950 only.
+// bb_solver_kernels.h, those of the landmark constraints (bb_solver_set_anchors) in
+// bb_anchor_kernels.h.  gfx950 only.
 //
 // Who owns what: every device allocation and event of a handle (bb_solver, bb_triples, bb_group)
 // is a bb::DevBuf / bb::Event member of it (bb_common.h) and goes with the handle, or earlier
@@ -37,6 +38,7 @@
 #include "bb_group_barrier.h"
 #include "bb_score.h"
 #include "bb_solver_kernels.h"
+#include "bb_anchor_kernels.h"
 #include "bb_triples.h"
 
 // --------------------------------------------------------------------------
@@ -139,6 +141,16 @@ struct bb_solver {
     bool pk_stale = true, pk_valid = false;
     bb::DevBuf pk_stream, pk_table;   // outside the arena: the solver runs raw without them
     int64_t pk_packed = 0, pk_bytes = 0, pk_switches = 0;
+
+    // landmark constraints (bb_solver_set_anchors, SPEC 2.5.5): the solver's own copy of the kept
+    // rows in its dtype; anchor_n = 0: none, and every path is the one it was without them
+    int anchor_n = 0;                    // kept rows L'
+    double anchor_weight = 0.0;          // lambda
+    int64_t anchor_terms = 0;            // values > 0 among the rows
+    int anchor_chunks = 0, anchor_node_blocks = 0;
+    bb::DevBuf anchor_rows;              // T (anchor_n, n_pad)
+    bb::DevBuf anchor_nodes;             // int per kept row: its landmark's node
+    bb::DevBuf anchor_part;              // double: anchor stress | per-workgroup stress | (a, chunk, 3)
 
     bool timing = false;
     int timing_stride = 1;      // events on every timing_stride-th iteration
@@ -710,6 +722,55 @@ int launch_exchange(bb_solver *s, double lr, double *stress_out, double scale = 
     return by_layout(s, [&](auto lay) { return launch_exchange_t(lay, s, lr, stress_out, scale); });
 }
 
+// The landmark terms of SPEC 2.5.5 at the coordinates X (bb_anchor_kernels.h), behind a reduce
+// that has left its result: fold = kAnchorFoldExchange adds gradient and stress to the exchange
+// buffer (three launches), kAnchorFoldStress adds the stress to stress_out[0], kAnchorFoldAlone
+// leaves the anchor stress in anchor_part[0] alone (two launches: no gradient is formed).
+double *anchor_stress_ptr(const bb_solver *s) { return s->anchor_part.as<double>(); }
+double *anchor_node_part(const bb_solver *s) { return s->anchor_part.as<double>() + 8; }
+double *anchor_lm_part(const bb_solver *s) {
+    return anchor_node_part(s) + bb::round_up(s->anchor_node_blocks, 8);
+}
+int launch_anchors(bb_solver *s, int fold, double *stress_out = nullptr) {
+    return by_dtype(s, [&](auto t) {
+        using T = typename decltype(t)::T;
+        return with_int<1, 2, 0>(s->weight_power, [&](auto qc) -> int {
+            constexpr int Q = decltype(qc)::value;
+            const T *A = s->anchor_rows.as<const T>();
+            const int *nodes = s->anchor_nodes.as<const int>();
+            const T *bin_scale = s->d_bin_scale.as<const T>();
+            T *exch = fold == kAnchorFoldExchange ? (T *)s->d_exch : nullptr;
+            BB_HIP_CHECK(bb::launch(anchor_node_kernel<T, Q>, dim3((unsigned)s->anchor_node_blocks), dim3(256),
+                                    0, s->stream, A, s->L.n_pad, s->L.n_bins, s->anchor_n, nodes,
+                                    (const T *)s->d_X, exch, bin_scale, (T)s->anchor_weight,
+                                    anchor_node_part(s)));
+            if (fold == kAnchorFoldExchange)
+                BB_HIP_CHECK(bb::launch(anchor_landmark_kernel<T, Q>,
+                                        dim3((unsigned)s->anchor_chunks, (unsigned)s->anchor_n), dim3(256), 0,
+                                        s->stream, A, s->L.n_pad, s->L.n_bins, nodes, (const T *)s->d_X,
+                                        (T)s->anchor_weight, anchor_lm_part(s)));
+            const unsigned fold_grid = fold == kAnchorFoldExchange ? (unsigned)s->anchor_n : 1u;
+            BB_HIP_CHECK(bb::launch(anchor_fold_kernel<T>, dim3(fold_grid), dim3(256), 0, s->stream, fold,
+                                    (const double *)anchor_node_part(s), s->anchor_node_blocks,
+                                    (const double *)anchor_lm_part(s), s->anchor_chunks, nodes,
+                                    (T *)s->d_exch, bin_scale, s->L.n_pad, anchor_stress_ptr(s), stress_out));
+            return BB_OK;
+        });
+    });
+}
+
+// X <- X + V, V <- mu V - lr * exchange[0 : 3 n_pad]; the stress of the buffer to stress_out.
+int launch_apply(bb_solver *s, double lr, double *stress_out) {
+    const int64_t n3 = s->L.n_pad * 3;
+    return by_dtype(s, [&](auto t) -> int {
+        using T = typename decltype(t)::T;
+        BB_HIP_CHECK(bb::launch(apply_kernel<T>, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, s->stream,
+                                (T *)s->d_X, (T *)s->d_V, (const T *)s->d_exch, n3, (T)lr, (T)s->momentum,
+                                stress_out));
+        return BB_OK;
+    });
+}
+
 // One iteration's two halves, sweep() and reduce(), with the timing events around them on
 // every timing_stride-th iteration while timing is on: ev[0] sweep ev[1] reduce ev[2].
 template <typename Sweep, typename Reduce>
@@ -1155,6 +1216,9 @@ int bb_solver_set_maps(bb_solver *s, int n_maps, const int64_t *bin_begin, const
     BB_REQUIRE(s != nullptr && bin_begin != nullptr && lr_scale != nullptr,
                "bb_solver_set_maps: NULL argument");
     BB_REQUIRE(n_maps >= 1 && n_maps <= s->L.n_blocks, "bb_solver_set_maps: bad n_maps");
+    if (s->anchor_n > 0)
+        return bb::fail(BB_ERR_STATE, "bb_solver_set_maps: the solver holds landmark anchors, which are "
+                                      "for one map (clear them with bb_solver_set_anchors first)");
     if (s->world != 1)
         return bb::fail(BB_ERR_STATE, "bb_solver_set_maps: one rank only (on several GPUs give every "
                                       "rank maps of its own)");
@@ -1306,6 +1370,145 @@ int bb_solver_weight_sums(bb_solver *s, double *sums, int64_t n_bins) {
     }));
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));
     BB_HIP_CHECK(hipMemcpy(sums, d_sum, (size_t)n_bins * sizeof(double), hipMemcpyDeviceToHost));
+    return BB_OK;
+}
+
+// SPEC 2.5.5: the solver's own resident copy of the kept rows of `paths`, in its dtype.  All of
+// the new state is built in locals and handed to the solver at the end: a refusal or a failed
+// allocation leaves the solver as it was.
+int bb_solver_set_anchors(bb_solver *s, const bb_paths *paths, const uint8_t *kept, double weight) {
+    const char *who = "bb_solver_set_anchors";
+    BB_REQUIRE(s != nullptr, "bb_solver_set_anchors: solver is NULL");
+    BB_REQUIRE(std::isfinite(weight) && weight >= 0.0,
+               "bb_solver_set_anchors: the weight must be finite and not negative");
+    if (s->grad_pending)
+        return bb::fail(BB_ERR_STATE, "bb_solver_set_anchors: a bb_solver_grad is pending");
+    BB_TRY(bb::enter_device(s->device));
+    if (paths == nullptr || weight == 0.0) {       // clear: every path is the unanchored one again
+        BB_HIP_CHECK(hipStreamSynchronize(s->stream));
+        s->anchor_rows.reset(), s->anchor_nodes.reset(), s->anchor_part.reset();
+        s->anchor_n = 0, s->anchor_weight = 0.0, s->anchor_terms = 0;
+        s->anchor_chunks = s->anchor_node_blocks = 0;
+        return BB_OK;
+    }
+    if (s->world > 1)
+        return bb::fail(BB_ERR_STATE, "bb_solver_set_anchors: landmark anchors run on one rank "
+                                      "(world > 1: several devices are not covered)");
+    if (s->n_maps > 1)
+        return bb::fail(BB_ERR_STATE, "bb_solver_set_anchors: landmark anchors are for one map, not for "
+                                      "a solver of several maps (bb_solver_set_maps)");
+    BB_REQUIRE(paths->n_nodes == s->L.n_bins,
+               "bb_solver_set_anchors: the paths have " + std::to_string(paths->n_nodes) +
+                   " nodes, the solver " + std::to_string(s->L.n_bins) + " bins (n_nodes != n_bins)");
+    BB_REQUIRE(paths->device == s->device, "bb_solver_set_anchors: the paths live on another device");
+    std::vector<int> col, node;
+    for (int64_t a = 0; a < paths->n_sources; ++a)
+        if (kept == nullptr || kept[a]) {
+            col.push_back((int)a);
+            node.push_back((int)paths->sources[(size_t)a]);
+        }
+    BB_REQUIRE(!col.empty(), "bb_solver_set_anchors: fewer than 1 kept row");
+    BB_REQUIRE((int)col.size() <= kAnchorMaxRows, "bb_solver_set_anchors: too many kept rows");
+    {
+        std::vector<int> sorted(node);
+        std::sort(sorted.begin(), sorted.end());
+        BB_REQUIRE(std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end(),
+                   "bb_solver_set_anchors: two kept rows have the same source node");
+    }
+    const int n_rows = (int)col.size();
+    const int64_t es = bb::elem_size(s->dtype), n_pad = s->L.n_pad;
+    const int node_blocks = (int)((s->L.n_bins + 255) / 256);
+    const int chunks = (int)((s->L.n_bins + kAnchorChunk - 1) / kAnchorChunk);
+    const size_t rows_bytes = (size_t)n_rows * (size_t)n_pad * (size_t)es;
+    const size_t idx_bytes = bb::align256((size_t)n_rows * sizeof(int)) * 2 + 256;   // nodes | columns | count
+    const size_t part_bytes =
+        (size_t)(8 + bb::round_up(node_blocks, 8) + (int64_t)n_rows * chunks * 3) * sizeof(double);
+    size_t free_b = 0, total_b = 0;
+    BB_TRY(bb::hip_status(who, hipMemGetInfo(&free_b, &total_b)));
+    const std::string sizes = std::to_string(n_rows) + " rows of " + std::to_string(n_pad) + " values need " +
+                              std::to_string(rows_bytes) + " B and their sums " +
+                              std::to_string(part_bytes + idx_bytes) + " B; " + std::to_string(free_b) +
+                              " B are free";
+    if (rows_bytes + part_bytes + idx_bytes > free_b) return bb::fail(BB_ERR_NOMEM, std::string(who) + ": " + sizes);
+    bb::DevBuf rows, idx, part;
+    hipError_t e = rows.alloc(rows_bytes);
+    if (e == hipSuccess) e = idx.alloc(idx_bytes);
+    if (e == hipSuccess) e = part.alloc(part_bytes);
+    if (e != hipSuccess) return bb::fail(BB_ERR_NOMEM, std::string(who) + ": hipMalloc failed: " + sizes);
+    int *d_node = idx.as<int>();
+    int *d_col = (int *)((char *)idx.p + bb::align256((size_t)n_rows * sizeof(int)));
+    unsigned long long *d_terms = (unsigned long long *)((char *)d_col + bb::align256((size_t)n_rows * sizeof(int)));
+    unsigned long long terms = 0;
+    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
+    BB_HIP_CHECK(hipMemcpy(d_node, node.data(), (size_t)n_rows * sizeof(int), hipMemcpyHostToDevice));
+    BB_HIP_CHECK(hipMemcpy(d_col, col.data(), (size_t)n_rows * sizeof(int), hipMemcpyHostToDevice));
+    BB_HIP_CHECK(hipMemsetAsync(d_terms, 0, sizeof(unsigned long long), s->stream));
+    BB_HIP_CHECK(hipMemsetAsync(part.p, 0, part_bytes, s->stream));
+    BB_TRY(by_dtype(s, [&](auto t) -> int {
+        using T = typename decltype(t)::T;
+        BB_HIP_CHECK(bb::launch(anchor_rows_kernel<T>, dim3((unsigned)(n_pad / 64), (unsigned)((n_rows + 63) / 64)),
+                                dim3(256), 0, s->stream, paths->D.as<const double>(), paths->ld,
+                                paths->n_nodes, n_pad, (const int *)d_col, n_rows, rows.as<T>(), d_terms));
+        return BB_OK;
+    }));
+    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
+    BB_HIP_CHECK(hipMemcpy(&terms, d_terms, sizeof(terms), hipMemcpyDeviceToHost));
+    s->anchor_rows = std::move(rows);
+    s->anchor_nodes = std::move(idx);
+    s->anchor_part = std::move(part);
+    s->anchor_n = n_rows;
+    s->anchor_weight = weight;
+    s->anchor_terms = (int64_t)terms;
+    s->anchor_chunks = chunks;
+    s->anchor_node_blocks = node_blocks;
+    return BB_OK;
+}
+
+int bb_solver_anchor_info(const bb_solver *s, int64_t *kept_rows, int64_t *terms, int64_t *bytes) {
+    BB_REQUIRE(s != nullptr, "bb_solver_anchor_info: solver is NULL");
+    if (kept_rows) *kept_rows = s->anchor_n;
+    if (terms) *terms = s->anchor_terms;
+    if (bytes) *bytes = (int64_t)(s->anchor_rows.bytes + s->anchor_nodes.bytes + s->anchor_part.bytes);
+    return BB_OK;
+}
+
+int bb_solver_anchor_sums(bb_solver *s, double *sums, int64_t n_bins) {
+    BB_REQUIRE(s != nullptr && sums != nullptr, "bb_solver_anchor_sums: NULL argument");
+    BB_REQUIRE(n_bins == s->L.n_bins, "bb_solver_anchor_sums: one sum per bin");
+    if (s->anchor_n == 0) {
+        std::fill(sums, sums + n_bins, 0.0);
+        return BB_OK;
+    }
+    BB_TRY(bb::enter_device(s->device));
+    // (the staging buffer of set_coords / get_coords: 3 n_pad doubles >= n_bins; see degrees)
+    double *d_sum = s->d_f64_tmp;
+    BB_TRY(by_dtype(s, [&](auto t) {
+        using T = typename decltype(t)::T;
+        return with_int<1, 2, 0>(s->weight_power, [&](auto qc) -> int {
+            constexpr int Q = decltype(qc)::value;
+            BB_HIP_CHECK(bb::launch(anchor_sums_node_kernel<T, Q>, dim3((unsigned)((n_bins + 255) / 256)),
+                                    dim3(256), 0, s->stream, s->anchor_rows.as<const T>(), s->L.n_pad, n_bins,
+                                    s->anchor_n, s->anchor_weight, d_sum));
+            BB_HIP_CHECK(bb::launch(anchor_sums_landmark_kernel<T, Q>, dim3((unsigned)s->anchor_n), dim3(256), 0,
+                                    s->stream, s->anchor_rows.as<const T>(), s->L.n_pad, n_bins,
+                                    s->anchor_nodes.as<const int>(), s->anchor_weight, d_sum));
+            return BB_OK;
+        });
+    }));
+    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
+    BB_HIP_CHECK(hipMemcpy(sums, d_sum, (size_t)n_bins * sizeof(double), hipMemcpyDeviceToHost));
+    return BB_OK;
+}
+
+int bb_solver_anchor_stress(bb_solver *s, double *stress) {
+    BB_TRY(check_ready(s, "bb_solver_anchor_stress"));
+    BB_REQUIRE(stress != nullptr, "bb_solver_anchor_stress: stress is NULL");
+    *stress = 0.0;
+    if (s->anchor_n == 0) return BB_OK;
+    BB_TRY(bb::enter_device(s->device));
+    BB_TRY(launch_anchors(s, kAnchorFoldAlone));
+    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
+    BB_HIP_CHECK(hipMemcpy(stress, anchor_stress_ptr(s), sizeof(double), hipMemcpyDeviceToHost));
     return BB_OK;
 }
 
@@ -1570,6 +1773,19 @@ int bb_solver_iterate(bb_solver *s, int64_t iters, double lr) {
                         "bb_solver_iterate: world > 1 needs bb_solver_grad / all-reduce / "
                         "bb_solver_apply");
     BB_TRY(bb::enter_device(s->device));
+    if (s->anchor_n > 0) {
+        // SPEC 2.5.5: the path bb_solver_grad / bb_solver_apply form, the landmark terms added to
+        // the exchange buffer between them (maps of the row-owner path too, while anchors are set)
+        for (int64_t k = 0; k < iters; ++k) {
+            BB_TRY(timed_step(s, [&] { return launch_grad(s); }, [&] {
+                BB_TRY(launch_reduce(s, kReduceExchange, 0.0, nullptr));
+                BB_TRY(launch_anchors(s, kAnchorFoldExchange));
+                return launch_apply(s, lr, s->d_stress_hist + s->hist_n);
+            }));
+            s->hist_n++;
+        }
+        return BB_OK;
+    }
     if (s->row_owner) {
         // one launch per iteration; launch k also folds the stress of launch k-1
         for (int64_t k = 0; k < iters; ++k) {
@@ -1597,6 +1813,7 @@ int bb_solver_grad(bb_solver *s) {
     BB_TRY(bb::enter_device(s->device));
     BB_TRY(timed_step(s, [&] { return launch_grad(s); },
                       [&] { return launch_reduce(s, kReduceExchange, 0.0, nullptr); }));
+    if (s->anchor_n > 0) BB_TRY(launch_anchors(s, kAnchorFoldExchange));
     s->grad_pending = true;
     return BB_OK;
 }
@@ -1608,14 +1825,7 @@ int bb_solver_apply(bb_solver *s, double lr) {
     if (s->hist_n + 1 > s->hist_cap)
         return bb::fail(BB_ERR_STATE, "bb_solver_apply: stress history full");
     BB_TRY(bb::enter_device(s->device));
-    const int64_t n3 = s->L.n_pad * 3;
-    BB_TRY(by_dtype(s, [&](auto t) -> int {
-        using T = typename decltype(t)::T;
-        BB_HIP_CHECK(bb::launch(apply_kernel<T>, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, s->stream,
-                                (T *)s->d_X, (T *)s->d_V, (const T *)s->d_exch, n3, (T)lr, (T)s->momentum,
-                                s->d_stress_hist + s->hist_n));
-        return BB_OK;
-    }));
+    BB_TRY(launch_apply(s, lr, s->d_stress_hist + s->hist_n));
     s->hist_n++;
     s->grad_pending = false;
     return BB_OK;
@@ -2103,6 +2313,10 @@ int bb_solver_peer_status(bb_solver *s, int *status) {
 
 int bb_solver_iterate_peer(bb_solver *s, int64_t iters, double lr) {
     BB_TRY(check_iterate(s, iters, "bb_solver_iterate_peer"));
+    // (its kernels step from the reduce itself: nothing could add the landmark terms in between)
+    if (s->anchor_n > 0)
+        return bb::fail(BB_ERR_STATE, "bb_solver_iterate_peer: a solver with landmark anchors iterates "
+                                      "with bb_solver_iterate");
     if (!s->peer_connected)
         return bb::fail(BB_ERR_STATE, "bb_solver_iterate_peer: bb_solver_peer_connect first");
     if (s->grad_pending)
@@ -2225,6 +2439,7 @@ int bb_solver_stress_maps(bb_solver *s, double *stress, int n_maps) {
     BB_TRY(launch_grad(s));
     double *out = s->n_maps > 1 ? s->d_map_scalar.as<double>() : s->d_stress_scalar;
     BB_TRY(launch_reduce(s, kReduceStressOnly, 0.0, out));
+    if (s->anchor_n > 0) BB_TRY(launch_anchors(s, kAnchorFoldStress, out));   // (one map: SPEC 2.5.5's total)
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));
     BB_HIP_CHECK(hipMemcpy(stress, out, (size_t)s->n_maps * sizeof(double), hipMemcpyDeviceToHost));
     return BB_OK;
@@ -2375,6 +2590,30 @@ int bb_solver_measure_stream_read(bb_solver *s, int launches, double *ms_avg) {
     BB_HIP_CHECK(launch());  // warm-up
     BB_HIP_CHECK(hipEventRecord(e0, s->stream));
     for (int k = 0; k < launches; ++k) BB_HIP_CHECK(launch());
+    BB_HIP_CHECK(hipEventRecord(e1, s->stream));
+    BB_HIP_CHECK(hipEventSynchronize(e1));
+    float ms = 0.f;
+    BB_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    *ms_avg = ms / launches;
+    return BB_OK;
+}
+
+int bb_solver_measure_anchors(bb_solver *s, int launches, double *ms_avg) {
+    BB_TRY(check_ready(s, "bb_solver_measure_anchors"));
+    BB_REQUIRE(ms_avg != nullptr, "bb_solver_measure_anchors: ms_avg is NULL");
+    BB_REQUIRE(launches >= 1 && launches <= 1000, "bb_solver_measure_anchors: bad launches");
+    if (s->anchor_n == 0) return bb::fail(BB_ERR_STATE, "bb_solver_measure_anchors: no anchors set");
+    if (s->grad_pending)
+        return bb::fail(BB_ERR_STATE, "bb_solver_measure_anchors: a bb_solver_grad is pending");
+    BB_TRY(bb::enter_device(s->device));
+    bb::Event e0, e1;
+    BB_HIP_CHECK(e0.create());
+    BB_HIP_CHECK(e1.create());
+    // (the exchange buffer holds nothing anybody waits for: no gradient is pending)
+    BB_HIP_CHECK(hipMemsetAsync(s->d_exch, 0, (size_t)(3 * s->L.n_pad + 2) * bb::elem_size(s->dtype), s->stream));
+    BB_TRY(launch_anchors(s, kAnchorFoldExchange));   // warm-up
+    BB_HIP_CHECK(hipEventRecord(e0, s->stream));
+    for (int k = 0; k < launches; ++k) BB_TRY(launch_anchors(s, kAnchorFoldExchange));
     BB_HIP_CHECK(hipEventRecord(e1, s->stream));
     BB_HIP_CHECK(hipEventSynchronize(e1));
     float ms = 0.f;
@@ -2648,6 +2887,7 @@ int group_grad(bb_group *g, int r) {
     for (const bb::Event &e : g->applied) BB_HIP_CHECK(hipStreamWaitEvent(s->stream, e, 0));
     BB_TRY(launch_grad(s));
     BB_TRY(launch_reduce(s, kReduceExchange, 0.0, nullptr));
+    if (s->anchor_n > 0) BB_TRY(launch_anchors(s, kAnchorFoldExchange));   // (a group of one: world 1)
     BB_HIP_CHECK(hipEventRecord(g->ready[(size_t)r], s->stream));
     return BB_OK;
 }

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "bb_common.h"
 
 namespace bb {
@@ -65,6 +67,17 @@ struct bb_triples {
     bb::DevBuf d;                       // 3 n doubles
     bb::TriplesIndex index;             // (bb_triples_balance.hip; freed with the handle)
     const double *from(int64_t t0) const { return d.as<double>() + t0 * (st == 3 ? 3 : 1); }
+};
+
+// The geodesic rows bb_triples_paths leaves (bb_triples_paths.hip owns their lifetime); the solver
+// reads them when it copies its anchors (bb_solver_set_anchors, docs/SPEC.md 2.5.5).
+struct bb_paths {
+    int device = 0;
+    int64_t n_sources = 0, n_nodes = 0, ld = 0;   // ld: doubles per node in D
+    int64_t sweeps = 0, unreachable = 0;
+    double weights_ms = 0.0, sweeps_ms = 0.0;
+    std::vector<int64_t> sources;                 // the node of every source
+    bb::DevBuf D;                                 // float64 (n_nodes, ld): +inf where no path exists
 };
 
 namespace bb {

@@ -47,14 +47,6 @@
 #include "bb_triples.h"
 #include "bb_wish.h"
 
-struct bb_paths {
-    int device = 0;
-    int64_t n_sources = 0, n_nodes = 0, ld = 0;   // ld: doubles per node in D
-    int64_t sweeps = 0, unreachable = 0;
-    double weights_ms = 0.0, sweeps_ms = 0.0;
-    bb::DevBuf D;                                 // float64 (n_nodes, ld)
-};
-
 namespace {
 
 using bb::kTbSeg;
@@ -380,6 +372,7 @@ int bb_triples_paths(bb_triples *t, int64_t n_nodes, int kind, double alpha, con
     if (!p) return bb::fail(BB_ERR_NOMEM, "bb_triples_paths: out of host memory");
     p->device = t->device;
     p->n_sources = n_sources;
+    p->sources.assign(sources, sources + n_sources);
     p->n_nodes = n_nodes;
     p->ld = ld;
     bb::DevBuf wt, kr_buf, small;                 // small: sources | flags | the count

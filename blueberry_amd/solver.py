@@ -309,11 +309,13 @@ def landmark_coefficients(G_LL):
 class LandmarkInfo(object):
     """What `landmark_start(..., return_info=True)` tells besides the start: `landmarks_` (the L
     landmark nodes), `kept_` (bool per landmark: reached by the main one), `placed_` (bool per
-    node), `sweeps_` and `unreachable_` of the shortest paths."""
+    node), `sweeps_` and `unreachable_` of the shortest paths; with keep_rows=True `rows_`, the
+    open `GeodesicRows` of the landmarks (the caller closes them), else None."""
 
-    def __init__(self, landmarks, kept, placed, sweeps, unreachable):
+    def __init__(self, landmarks, kept, placed, sweeps, unreachable, rows=None):
         self.landmarks_, self.kept_, self.placed_ = landmarks, kept, placed
         self.sweeps_, self.unreachable_ = sweeps, unreachable
+        self.rows_ = rows
 
 
 def _check_n_landmarks(n_landmarks):
@@ -323,8 +325,15 @@ def _check_n_landmarks(n_landmarks):
     return int(n_landmarks)
 
 
+def _check_landmark_weight(weight):
+    if (isinstance(weight, bool) or not isinstance(weight, (int, float, numpy.integer, numpy.floating))
+            or not numpy.isfinite(weight) or weight < 0):
+        raise ValueError("landmark_weight must be a finite number >= 0")
+    return float(weight)
+
+
 def landmark_start(triples, resolution, n_bins, n_landmarks=64, kind="counts", alpha=3.0, KRnorm=None,
-                   KRexpected=None, seed=0, device=0, return_info=False):
+                   KRexpected=None, seed=0, device=0, return_info=False, keep_rows=False):
     """A start for sparse maps that holds the global fold (docs/SPEC.md 2.5.4): landmark MDS
     (L-Isomap) over the graph of the triples' wish distances, never forming the dense matrix.
     Landmarks are spread evenly over the bins that have an edge; shortest paths run from them on
@@ -335,6 +344,8 @@ def landmark_start(triples, resolution, n_bins, n_landmarks=64, kind="counts", a
     that are not placed -- dead bins, small components -- keep the rows of the seeded default start
     `numpy.random.default_rng(seed).standard_normal((n_bins + 1, 3))`.
     Returns the (n_bins + 1, 3) float64 array; with return_info=True, (array, `LandmarkInfo`).
+    keep_rows=True (with return_info) leaves the geodesic rows open as `info.rows_` -- what
+    `HipEngine.set_anchors` copies for a fit with landmark constraints (SPEC 2.5.5).
     `triples` may be a `DeviceTriples` (its own resolution and device are used; it stays open)."""
     from .datatypes import _pick_device
     n_landmarks = _check_n_landmarks(n_landmarks)
@@ -352,7 +363,8 @@ def landmark_start(triples, resolution, n_bins, n_landmarks=64, kind="counts", a
         few = "the map is too disconnected for a landmark start: %s (need 4)"
         if landmarks.shape[0] < 4:
             raise ValueError(few % ("%d bins have an edge" % live.shape[0]))
-        with dev.shortest_paths(n, landmarks, **graph) as rows:
+        rows = dev.shortest_paths(n, landmarks, **graph)
+        try:
             main = int(numpy.argmax(rows.reached()))           # (the lowest index on ties)
             G = rows.columns(landmarks)
             kept = G[main] > 0.0
@@ -363,7 +375,14 @@ def landmark_start(triples, resolution, n_bins, n_landmarks=64, kind="counts", a
             coef[kept], mu[kept] = landmark_coefficients(G[numpy.ix_(kept, kept)])
             start = numpy.random.default_rng(int(seed)).standard_normal((n, 3))
             start, placed = rows.place(coef, mu, out=start)
-            info = LandmarkInfo(landmarks, kept, placed, rows.sweeps_, rows.unreachable_)
+            keep = bool(keep_rows and return_info)
+            info = LandmarkInfo(landmarks, kept, placed, rows.sweeps_, rows.unreachable_,
+                                rows if keep else None)
+            if keep:
+                rows = None
+        finally:
+            if rows is not None:
+                rows.close()
     finally:
         if own:
             dev.close()
@@ -591,6 +610,39 @@ class HipEngine(object):
         out = numpy.zeros(self.n_bins, dtype=numpy.float64)
         self._call("weight_sums", _lib.as_f64_ptr(out), out.shape[0])
         return out
+
+    anchored = False                # landmark constraints resident (set_anchors)
+
+    def set_anchors(self, rows, kept=None, weight=0.0):
+        """Landmark constraints inside the fit (SPEC 2.5.5, `bb_solver_set_anchors`): the engine
+        makes its own copy of the rows of `rows` (a `GeodesicRows`) with kept[a] true (None:
+        all), which may be closed afterwards.  rows None or weight 0 clears them."""
+        import ctypes
+        k = None
+        if rows is not None and kept is not None:
+            k = numpy.ascontiguousarray(kept, dtype=numpy.uint8)
+            if k.shape != (rows.n_sources,):
+                raise ValueError("kept must have one entry per source")
+        self._call("set_anchors", None if rows is None else rows._open(),
+                   None if k is None else k.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), float(weight))
+        self.anchored = self.anchor_info()[0] > 0
+
+    def anchor_sums(self):
+        """Per bin, weight * sum of D^-q over the landmark terms that touch it, float64
+        (`bb_solver_anchor_sums`): what joins `weight_sums` in the steps of SPEC 2.4.1."""
+        out = numpy.zeros(self.n_bins, dtype=numpy.float64)
+        self._call("anchor_sums", _lib.as_f64_ptr(out), out.shape[0])
+        return out
+
+    def anchor_stress(self):
+        """The landmark terms' share of the stress at the current coordinates."""
+        return float(self._get(_lib.c_dbl, "anchor_stress"))
+
+    def anchor_info(self):
+        """(kept rows, terms, bytes resident) of the anchors; zeros without."""
+        rows, terms, nbytes = _lib.c_i64(), _lib.c_i64(), _lib.c_i64()
+        self._call("anchor_info", rows, terms, nbytes)
+        return int(rows.value), int(terms.value), int(nbytes.value)
 
     def score(self, xyz=None):
         """The sums of SPEC 2.8 over this rank's units (`bb_solver_score`): (profile, bins),
@@ -841,6 +893,11 @@ class HipEngine(object):
         """Average ms between two HIP events recorded back to back behind a sweep launch:
         what an event-timed interval contains besides its kernel (measurement aid)."""
         return float(self._get(_lib.c_dbl, "measure_event_gap", int(pairs)))
+
+    def anchor_ms(self, launches=10):
+        """Average ms of one iteration's three anchor launches alone (`bb_solver_measure_anchors`;
+        measurement aid)."""
+        return float(self._get(_lib.c_dbl, "measure_anchors", int(launches)))
 
     def stream_read_ms(self, launches=10):
         """Average ms of a read-only sweep over the resident units (measurement aid)."""
@@ -1373,7 +1430,8 @@ class StructureSolver(object):
         None: exactly n_iter steps.  Otherwise stop as soon as the relative stress
         decrease of one step is <= tol, checked every `check_every` steps (n_iter is
         then the maximum); `n_iter_` tells how many were run.
-    init : 'random', 'spectral', 'landmark' or ('landmark', n_landmarks)
+    init : 'random', 'spectral', 'landmark', ('landmark', n_landmarks) or
+           ('landmark', n_landmarks, landmark_weight)
         Start used when `fit()` gets no `init=` array: seeded standard normal, or
         classical MDS computed on the device (`spectral_init`), or -- for the sparse inputs,
         `fit_triples` and `fit(scipy.sparse)` -- landmark MDS over shortest paths on the stored
@@ -1387,7 +1445,17 @@ class StructureSolver(object):
         bins were landmarks and which were placed.  Not for dense inputs or a ContactMap
         (`complete='shortest_path'` is their route, or init='spectral'), not with
         `complete='shortest_path'`, `fit_many`, or an engine without a device: ValueError.
-        The stored pairs alone do not hold the fold for ever (SPEC 2.5.4): few iterations.
+        The stored pairs alone do not hold the fold for ever (SPEC 2.5.4): few iterations, or
+        ('landmark', n_landmarks, landmark_weight) with landmark_weight > 0 (SPEC 2.5.5): the
+        kept landmarks' geodesic rows stay in the fit as constraints, every term weighted
+        landmark_weight * D^-weight_power, and hold the fold over any number of iterations
+        (`landmark_weight` reads it back; 0, the default, is the fit without them bit for bit).
+        It needs degree_steps=True (a landmark touches about N terms: ValueError otherwise) and
+        ONE device (`devices=` / `n_gpus` of several, a distributed world > 1: ValueError);
+        `stress_` is then the total of stored pairs and landmark terms, `anchor_stress_` the
+        latter's share at the end, `landmark_terms_` their number.  An `init=` array given to
+        the call replaces the start only; the constraints stay.  The anchored fit reduces the
+        stress of the stored pairs less than the free one.
     degree_steps : bool
         A step per bin from the map itself (SPEC 2.4.1): bin i steps by 1 / (2 (deg_i + 1)),
         deg_i = the number of pairs that constrain it (counted on the device, summed over
@@ -1475,11 +1543,13 @@ class StructureSolver(object):
         if int(check_every) < 1:
             raise ValueError("check_every must be >= 1")
         self.tol, self.check_every = (None if tol is None else float(tol)), int(check_every)
-        if isinstance(init, tuple) and len(init) == 2 and init[0] == "landmark":
-            init = ("landmark", _check_n_landmarks(init[1]))
+        if isinstance(init, tuple) and len(init) in (2, 3) and init[0] == "landmark":
+            init = ("landmark", _check_n_landmarks(init[1])) + tuple(
+                _check_landmark_weight(w) for w in init[2:])
         elif not (isinstance(init, str) and init in ("random", "spectral", "landmark")):
-            raise ValueError("init must be 'random', 'spectral', 'landmark' or ('landmark', "
-                             "n_landmarks) (or pass init= to fit())")
+            raise ValueError("init must be 'random', 'spectral', 'landmark', ('landmark', "
+                             "n_landmarks) or ('landmark', n_landmarks, landmark_weight) (or pass "
+                             "init= to fit())")
         self.init = init
         if int(spectral_iter) < 0 or not 0.0 <= float(spectral_tol) < 1.0:
             raise ValueError("need spectral_iter >= 0 and 0 <= spectral_tol < 1")
@@ -1500,6 +1570,14 @@ class StructureSolver(object):
             self.device = self._group[0]           # one entry: as device=
         elif self._group is not None and engine is not None:
             raise ValueError("devices= runs HIP engines of its own; it takes no engine=")
+        self._anchor = None                 # (rows, kept) between the landmark start and the fit
+        if self.landmark_weight > 0.0:
+            if not self.degree_steps:
+                raise ValueError("landmark_weight > 0 needs degree_steps=True: a landmark touches "
+                                 "about landmark_weight * N terms, so the one global step its "
+                                 "weighted degree allows, 1 / (2 landmark_weight N), would slow "
+                                 "every bin down to it (docs/SPEC.md 2.5.5)")
+            self._check_anchor_devices(None)
 
     def _pick_device(self, world):
         if self.device is not None:
@@ -1513,8 +1591,23 @@ class StructureSolver(object):
             return 64
         return self.init[1] if isinstance(self.init, tuple) else None
 
+    @property
+    def landmark_weight(self):
+        """The weight of the landmark constraints (SPEC 2.5.5): the third entry of
+        init=('landmark', n_landmarks, landmark_weight); 0.0 (none) for every other init."""
+        return self.init[2] if isinstance(self.init, tuple) and len(self.init) == 3 else 0.0
+
     def _landmark_refusal(self, why, instead):
         return ValueError("init='landmark' %s; use %s" % (why, instead))
+
+    def _check_anchor_devices(self, world):
+        """Landmark constraints (landmark_weight > 0) run on one device: a group of several, or
+        -- `world` given -- a torch.distributed job of several ranks, is refused."""
+        if self.landmark_weight > 0.0 and ((self._group is not None and len(self._group) > 1)
+                                           or (world is not None and world > 1)):
+            raise self._landmark_refusal("with landmark_weight > 0 keeps its constraints on one "
+                                         "device (several devices are not covered)",
+                                         "one device, or landmark_weight = 0")
 
     def _check_landmark_route(self, complete):
         """The refusals of a landmark start that need no device (the caller has a sparse input)."""
@@ -1524,15 +1617,48 @@ class StructureSolver(object):
         if not hasattr(self._engine_factory, "set_wish_triples"):
             raise self._landmark_refusal("runs on the device and this solver's engine has none",
                                          "init='spectral'")
+        if self.landmark_weight > 0.0:
+            self._check_anchor_devices(1 if self._group is not None else _dist_state(self.distributed)[1])
+
+    def _landmark_wanted(self, init):
+        """Whether a call with this `init=` goes the landmark route: for the start (no init
+        given), and -- an array replaces only the start -- for the constraints."""
+        return self.n_landmarks is not None and (init is None or self.landmark_weight > 0.0)
 
     def _landmark_init(self, dev, n_bins, KRnorm, KRexpected):
         """The landmark start of the map in `dev` (a DeviceTriples) under this solver's kind and
-        alpha and the fit's KR vectors; `landmarks_` and `landmark_placed_` stay on the solver."""
+        alpha and the fit's KR vectors; `landmarks_` and `landmark_placed_` stay on the solver.
+        With landmark_weight > 0 the geodesic rows stay open for the fit (`_anchor`), which hands
+        them to its engine and closes them."""
+        keep = self.landmark_weight > 0.0
+        self._drop_anchor()
         start, info = landmark_start(dev, dev.resolution, n_bins, n_landmarks=self.n_landmarks,
                                      kind=self.kind, alpha=self.alpha, KRnorm=KRnorm,
-                                     KRexpected=KRexpected, seed=self.seed, return_info=True)
+                                     KRexpected=KRexpected, seed=self.seed, return_info=True,
+                                     keep_rows=keep)
         self.landmarks_, self.landmark_placed_ = info.landmarks_, info.placed_
+        if keep:
+            self._anchor = (info.rows_, info.kept_)
         return start
+
+    def _drop_anchor(self):
+        if self._anchor is not None:
+            self._anchor[0].close()
+            self._anchor = None
+
+    def _take_anchor(self, eng, world):
+        """The rows `_landmark_init` kept, copied into the engine (which then owns its copy)
+        and closed."""
+        if self._anchor is None:
+            return
+        try:
+            self._check_anchor_devices(world)
+            if not hasattr(eng, "set_anchors"):
+                raise self._landmark_refusal("with landmark_weight > 0 needs an engine that holds "
+                                             "the constraints on the device", "HipEngine")
+            eng.set_anchors(self._anchor[0], self._anchor[1], self.landmark_weight)
+        finally:
+            self._drop_anchor()
 
     def fit(self, X, init=None, complete=None):
         """Solve for the structure of `X`: a ContactMap, a square ndarray, or a
@@ -1554,8 +1680,13 @@ class StructureSolver(object):
             (720 GB dense at 10 kb) cannot be completed this way (MemoryError); init='landmark'
             (SPEC 2.5.4) is the route of such a map to its global fold."""
         _check_complete(complete)
-        if init is None and self.n_landmarks is not None:
-            init = self._landmark_init_of_map(X, complete)
+        if self._landmark_wanted(init):
+            try:
+                start = self._landmark_init_of_map(X, complete)
+                source, n = self._map_source(X)
+                return self._fit_impl(source, n, start if init is None else init, None, None)
+            finally:
+                self._drop_anchor()
         if complete is None:
             source, n = self._map_source(X)
             return self._fit_impl(source, n, init, None, None)
@@ -1623,15 +1754,21 @@ class StructureSolver(object):
         (degree_steps), or None for the one step of SPEC 2.4."""
         if self.weight_power:
             eng.set_weight_power(self.weight_power)
-            return _sum_over_ranks(eng.weight_sums(), eng, world)
-        if self.degree_steps:
-            return _sum_over_ranks(eng.degrees(), eng, world)
-        return None
+            sums = _sum_over_ranks(eng.weight_sums(), eng, world)
+        elif self.degree_steps:
+            sums = _sum_over_ranks(eng.degrees(), eng, world)
+        else:
+            return None
+        if getattr(eng, "anchored", False):
+            # SPEC 2.5.5: the landmark terms join the (weighted) degrees, as float64
+            sums = numpy.asarray(sums, dtype=numpy.float64) + eng.anchor_sums()
+        return sums
 
-    def _steps(self, sums, n):
+    def _steps(self, sums, n, anchored=False):
         """(lr, scale) for one map of n bins from its slice of `_bin_sums`: `weighted_steps`
-        or `degree_step_factors`, a float `lr` being the step of the best-connected bin."""
-        if self.weight_power:
+        (weighted stress, or `anchored`: the sums hold landmark terms, SPEC 2.5.5) or
+        `degree_step_factors`, a float `lr` being the step of the best-connected bin."""
+        if self.weight_power or anchored:
             return weighted_steps(sums, n, self.dtype, self.lr, self.degree_steps)
         lr, scale = degree_step_factors(sums)
         return (lr if self.lr == "auto" else float(self.lr)), scale
@@ -1674,9 +1811,11 @@ class StructureSolver(object):
             init = self._default_start(n)
         with _teardown(eng):
             pack(kind, KRnorm, KRexpected)
+            self._take_anchor(eng, world)
+            anchored = bool(getattr(eng, "anchored", False))
             sums = self._bin_sums(eng, world)
             if sums is not None:
-                lr, scale = self._steps(sums, n)
+                lr, scale = self._steps(sums, n, anchored)
                 if scale is not None:
                     eng.set_bin_steps(scale)
             on_device = False
@@ -1724,6 +1863,9 @@ class StructureSolver(object):
             self.exchange_ = _exchange_state(eng)
             self.structure_ = eng.get_coords()
             self.stress_ = eng.stress_history()
+            if self.n_landmarks is not None:
+                self.anchor_stress_ = eng.anchor_stress() if anchored else 0.0
+                self.landmark_terms_ = eng.anchor_info()[1] if anchored else 0
         self.devices_ = devices
         self.n_bins_, self.lr_, self.n_iter_ = n, lr, int(self.stress_.shape[0])
         return self
@@ -1849,7 +1991,7 @@ class StructureSolver(object):
         device (one-device fits without `complete`), which stays open."""
         _check_complete(complete)
         n = int(n_bins) + 1
-        landmark = init is None and self.n_landmarks is not None
+        landmark = self._landmark_wanted(init)
         if landmark:
             self._check_landmark_route(complete)
         if balance is not None:
@@ -1889,7 +2031,8 @@ class StructureSolver(object):
                     if balance is not None:
                         KRnorm, KRexpected = self._balance_on(dev, int(n_bins), bal_args, bal_expected)
                     if landmark:
-                        init = self._landmark_init(dev, int(n_bins), KRnorm, KRexpected)
+                        start = self._landmark_init(dev, int(n_bins), KRnorm, KRexpected)
+                        init = start if init is None else init
                     return self._fit_impl(dev, n, init, KRnorm, KRexpected)
                 finally:
                     for t in per_device.values():
@@ -1901,9 +2044,11 @@ class StructureSolver(object):
                 if balance is not None:
                     KRnorm, KRexpected = self._balance_on(dev, int(n_bins), bal_args, bal_expected)
                 if landmark:
-                    init = self._landmark_init(dev, int(n_bins), KRnorm, KRexpected)
+                    start = self._landmark_init(dev, int(n_bins), KRnorm, KRexpected)
+                    init = start if init is None else init
                 return self._fit_impl(dev, n, init, KRnorm, KRexpected)
             finally:
+                self._drop_anchor()
                 if own:
                     dev.close()
         # engines without a device (tests): bin on the host, as round 3 did

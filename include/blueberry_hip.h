@@ -726,6 +726,52 @@ BB_API int bb_paths_place(const bb_paths *p, const double *coef, const double *m
                           uint8_t *placed);
 BB_API int bb_paths_timing(const bb_paths *p, double *weights_ms, double *sweeps_ms);
 BB_API int bb_paths_destroy(bb_paths *p);
+/* Landmark constraints inside the fit (docs/SPEC.md 2.5.5): the kept rows of a bb_paths stay in
+ * the solver as weighted wish distances between each landmark s_a and every node v,
+ *     S(X) = S_q(X) + weight * sum_a sum_v D_av^-q (|x_{s_a} - x_v|_eps - D_av)^2,
+ * q the solver's weight power (bb_solver_set_weight_power, also when set afterwards), eps the
+ * floor of SPEC 2.2.  A term exists where D_av, rounded to the solver's dtype by the value rule of
+ * every input route (finite, positive, inside the dtype's wish floor and ceiling), is > 0 and
+ * v != s_a; each ordered (a, v) is a term of its own, and one that coincides with a stored pair
+ * is added to it.
+ *   bb_solver_set_anchors   the solver makes its OWN resident copy: row a of the paths for every
+ *                           a with kept[a] != 0 (kept: n_sources bytes; NULL = all), converted on
+ *                           the device, n_pad values per row in the solver's dtype (0 in the
+ *                           padding and on the landmark's own node), and the kept sources' nodes;
+ *                           the paths may be destroyed afterwards.  paths == NULL or weight == 0
+ *                           clears the anchors.  The size is checked first: BB_ERR_NOMEM with the
+ *                           sizes in the message; after any failure the solver is as it was.
+ *                           BB_ERR_INVALID: a negative or non-finite weight, n_nodes != the
+ *                           solver's bins, paths of another device, fewer than 1 kept row, two
+ *                           kept rows of one node; BB_ERR_STATE: world > 1, a solver of several
+ *                           maps (n_maps > 1; bb_solver_set_maps refuses while anchors are set),
+ *                           a pending bb_solver_grad
+ *   bb_solver_anchor_sums   per bin, weight * sum of D^-q over the terms that touch it (as node
+ *                           and as landmark), float64, a fixed order: what joins the weighted
+ *                           degrees of SPEC 2.4.1; zeros without anchors
+ *   bb_solver_anchor_stress the second sum of S at the current coordinates, alone (0 without)
+ *   bb_solver_anchor_info   kept rows, terms, bytes resident; each may be NULL
+ * While anchors are set, bb_solver_iterate runs per iteration the sweep, the reduce into the
+ * exchange buffer, three launches that add the terms there -- per node, a ascending over the
+ * coalesced rows; per (landmark, chunk of 1,024 nodes) into own slots; one fold in chunk order,
+ * the stress into hi / lo in double -- and the update of bb_solver_apply; maps of the one-launch
+ * path (bb_solver_iteration_path) take this path too.  bb_solver_grad (world 1) adds the terms,
+ * so bb_solver_read_exchange shows them; bb_solver_stress, the history and bb_solver_apply
+ * report the total S (bb_solver_iterate_dist at world 1 and a bb_group of one member go through
+ * the same buffer and add them too; bb_solver_iterate_peer, whose kernels step from the reduce
+ * itself, is BB_ERR_STATE).  No floating-point atomics: the same bits on every run.  Without anchors
+ * every path, launch and bit is what it was.  An anchored map needs a step per bin
+ * (bb_solver_set_bin_steps from the sums above): a landmark touches about n_bins terms. */
+BB_API int bb_solver_set_anchors(bb_solver *s, const bb_paths *paths, const uint8_t *kept,
+                                 double weight);
+BB_API int bb_solver_anchor_sums(bb_solver *s, double *sums, int64_t n_bins);
+BB_API int bb_solver_anchor_stress(bb_solver *s, double *stress);
+BB_API int bb_solver_anchor_info(const bb_solver *s, int64_t *kept_rows, int64_t *terms,
+                                 int64_t *bytes);
+/* Measurement aid: the average HIP-event time of the three anchor launches of one iteration,
+ * back to back `launches` times at the current coordinates into the (zeroed) exchange buffer.
+ * BB_ERR_STATE without anchors or while a bb_solver_grad is pending. */
+BB_API int bb_solver_measure_anchors(bb_solver *s, int launches, double *ms_avg);
 /* The Fit-Hi-C significance call on a resident map (docs/SPEC.md 2.9; reference:
  * blueberry/fithic.py:413-435, one text line at a time through scipy.special.bdtrc).
  *
