@@ -4,8 +4,9 @@ held as 6 KiB of offset codes.  What must hold:
 
   - a fit, a gradient and a stress history are the SAME BITS with the stream (BB_PACK24=1) and
     without it (BB_PACK24=0): there is no tolerance anywhere in this file;
-  - which units are held packed follows the rule, as a numpy model of it written here says
-    (packed units, raw units, stream bytes, format switches of `HipEngine.stream_info`).
+  - which units are held packed follows the rule, as the numpy model of it says
+    (tests/_pack24_model.py: packed units, raw units, stream bytes, format switches of
+    `HipEngine.stream_info`).
 
 Every map is small enough that a case takes a second or two; BB_ROW_OWNER_MAX=0 keeps the small
 ones on the unit sweep."""
@@ -14,11 +15,9 @@ import pytest
 
 from blueberry_amd.solver import HipEngine
 from tests import _oracle
+from tests._pack24_model import RPU, SPAN, UPT, VW, model
 
 pytestmark = pytest.mark.gpu
-
-VW, RPU, UPT = 512, 4, 128          # fp32: 512-column strips, units of 4 rows, 128 units per tile
-SPAN = 1 << 24
 
 
 def _bits(a):
@@ -69,36 +68,6 @@ def _cu_count():
     v = ctypes.c_int(0)
     assert hip.hipDeviceGetAttribute(ctypes.byref(v), 63, 0) == 0    # hipDeviceAttributeMultiprocessorCount
     return int(v.value)
-
-
-def model(w, n, u_begin, u_end, min_run):
-    """The rule, in numpy: the words of unit u are the float32 wish distances of its 4 rows x 512
-    columns (0 on the diagonal, below it and in the padding); packable: max - min < 2^24 as
-    uint32; stored packed: inside a run of >= min_run packable units of the rank's order."""
-    nb = (n + VW - 1) // VW
-    full = numpy.zeros((nb * VW, nb * VW), dtype=numpy.float32)
-    full[:n, :n] = numpy.triu(w, 1).astype(numpy.float32)
-    packable = []
-    for J in range(nb):
-        for I in range(J + 1):
-            tile = full[I * VW:(I + 1) * VW, J * VW:(J + 1) * VW].view(numpy.uint32)
-            words = tile.reshape(UPT, RPU * VW).astype(numpy.int64)
-            packable.append(words.max(1) - words.min(1) < SPAN)
-    packable = numpy.concatenate(packable)[u_begin:u_end]
-    packed = numpy.zeros(packable.shape, dtype=bool)
-    a = 0
-    while a < packable.size:
-        b = a
-        while b < packable.size and packable[b] == packable[a]:
-            b += 1
-        packed[a:b] = packable[a] and b - a >= min_run
-        a = b
-    n_packed = int(packed.sum())
-    if n_packed == 0:
-        return {"packed_units": 0, "raw_units": int(packed.size), "stream_bytes": 0, "format_switches": 0}, packed
-    return {"packed_units": n_packed, "raw_units": int(packed.size) - n_packed,
-            "stream_bytes": 1024 * (6 * n_packed + 8 * (int(packed.size) - n_packed)),
-            "format_switches": int((packed[1:] != packed[:-1]).sum())}, packed
 
 
 def _run(n, set_wish, x0, steps=(7, 8), rank=0, world=1):
@@ -156,7 +125,7 @@ def _compare(monkeypatch, n, set_wish, x0, env, **kw):
 
 
 def _check_model(on, w, n, min_run):
-    want, packed = model(w, n, on["layout"]["u_begin"], on["layout"]["u_end"], min_run)
+    want, packed, _ = model(w, n, on["layout"]["u_begin"], on["layout"]["u_end"], min_run)
     assert on["info"] == want
     return packed
 
