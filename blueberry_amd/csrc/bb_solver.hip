@@ -490,8 +490,10 @@ decltype(auto) with_int(int v, F &&f) {
 }
 
 // The 24-bit stream pays only where it takes bytes off the sweep: its kernel carries a second
-// copy of the unit body and drains its window at every change of format, and a packed unit
-// costs 48 more VALU instructions than a raw one.  Below a saving of an eighth of the raw bytes
+// copy of the unit body and drains its window at every change of format (an all-zero packed
+// unit is a run of its own in the raw body), and a packed unit costs 15 more VALU instructions
+// than a raw one (383 against 368: 48 of decode, less the empty-pair mask a unit without a zero
+// does without; it was 52 more with the mask).  Below a saving of an eighth of the raw bytes
 // (all a sparse raw map with zeros in most units can offer is 0) the solver keeps reading
 // d_units with the kernel it always had.
 constexpr int64_t kPk24MinSavingDiv = 8;   // stream bytes <= raw bytes * (1 - 1/8)

@@ -506,9 +506,13 @@ __device__ __forceinline__ f32x2 weight01(f32x2 delta) {
     return w;
 }
 
-template <int K, int H, bool FIRST, int OP>
+// MASK = false (kOpStress only): the caller knows that no delta of the unit is 0 -- a packed unit
+// of the 24-bit stream with base != 0, see process_unit_f32 -- so the weight is exactly 1.0f and
+// res * 1.0f is res, bit for bit: neither is formed.
+template <int K, int H, bool FIRST, int OP, bool MASK = true>
 __device__ __forceinline__ void pair_step2(f32x2 delta, f32x2 xi, f32x2 yi, f32x2 zi, StripF32 &st,
                                            f32x2 &rx, f32x2 &ry, f32x2 &rz, f32x2 &s2) {
+    static_assert(MASK || OP == kOpStress, "only the plain stress sweep has a mask-free form");
     if constexpr (OP == kOpMatvec2) {
         const f32x2 a = delta * delta;
         if constexpr (FIRST) {
@@ -552,7 +556,7 @@ __device__ __forceinline__ void pair_step2(f32x2 delta, f32x2 xi, f32x2 yi, f32x
         return;
     }
     f32x2 res = d2 * rinv - delta;
-    res *= weight01(delta);  // (dist - delta) or 0
+    if constexpr (MASK) res *= weight01(delta);  // (dist - delta) or 0
     s2 += res * res;
     const f32x2 coef = res * rinv;
     if constexpr (FIRST) {
@@ -583,8 +587,16 @@ __device__ __forceinline__ void pair_step2(f32x2 delta, f32x2 xi, f32x2 yi, f32x
 // together and are refilled as in a raw unit, as are those of row 2; only load 3 waits one row
 // for its refill.  Decode: one v_mad_u32_u24 per pair of rows 0..2 (mask to 24 bits, add the
 // unit's base from a scalar register), two v_perm_b32 and one add per pair of row 3 -- 48 per
-// unit, and 4 moves.  The pair math, its order and every sum are those of the raw unit: the
-// bits are the same.
+// unit (row 1 decodes load 3, which keeps its top bytes for row 2, out of place into the
+// registers of load 2: no move).
+// This body runs the packed units whose base is not 0, and those hold NO empty pair: every
+// stored wish distance is 0 or at least 1e-30 (bb_wish.h), whose bit pattern lies above 2^24,
+// and a unit packs only when its words span less than 2^24 from the base, its smallest word --
+// so a zero in the unit means base = 0 and nothing but zeros (such a unit goes through the raw
+// body: bb_sweep_body.inc).  1e-30 is above 2^-100, where weight01 saturates: every weight here
+// is exactly 1.0f, and the body forms neither the weight nor res * weight (MASK = false, 32
+// packed instructions per unit).  The pair math, its order and every sum are otherwise those
+// of the raw unit: the bits are the same.
 template <bool ROW3>
 __device__ __forceinline__ void pk24_decode(float &word, unsigned base) {
     // volatile: memory operations keep their side of such a statement, so the refills stay in
@@ -605,6 +617,14 @@ template <bool ROW3>
 __device__ __forceinline__ void pk24_decode(float4 &w, unsigned base) {
     pk24_decode<ROW3>(w.x, base); pk24_decode<ROW3>(w.y, base);
     pk24_decode<ROW3>(w.z, base); pk24_decode<ROW3>(w.w, base);
+}
+// out of place: the codes of `src`, whose top bytes are still wanted, as distances in `dst`
+__device__ __forceinline__ void pk24_decode_to(float &dst, float src, unsigned base) {
+    asm volatile("v_mad_u32_u24 %0, %1, 1, %2" : "=v"(dst) : "v"(src), "s"(base));
+}
+__device__ __forceinline__ void pk24_decode_to(float4 &dst, const float4 &src, unsigned base) {
+    pk24_decode_to(dst.x, src.x, base); pk24_decode_to(dst.y, src.y, base);
+    pk24_decode_to(dst.z, src.z, base); pk24_decode_to(dst.w, src.w, base);
 }
 constexpr unsigned kPk24SelPair = 0x0c0c0703u;   // {0, 0, top of S0, top of S1}
 constexpr unsigned kPk24SelThird = 0x0c070100u;  // {0, top of S0, byte 1 of S1, byte 0 of S1}
@@ -636,8 +656,8 @@ __device__ __forceinline__ void process_unit_f32(float4 (&d)[8], const float (&x
             // The codes become distances IN the window's registers, and d[6], d[7] -- which a
             // packed unit has no loads for -- collect the codes of row 3: the body holds what
             // the raw one holds (alone in the kernel it takes 124 VGPRs).  Row 1 decodes its
-            // second load into the registers of its first (done with by then), because load 3
-            // keeps its top bytes for row 2.
+            // second load INTO the registers of its first (done with by then), because load 3
+            // keeps its top bytes for row 2.  No pair of this body has a zero distance: no mask.
             constexpr int A = r < 3 ? 2 * r : 6, B = r == 0 ? 1 : (r == 1 ? 2 : (r == 2 ? 5 : 7));
             if constexpr (r == 0) d[6] = pk24_tops(d[1], d[0], kPk24SelPair);
             if constexpr (r == 1) d[6] = pk24_tops(d[2], d[6], kPk24SelThird);
@@ -646,14 +666,14 @@ __device__ __forceinline__ void process_unit_f32(float4 (&d)[8], const float (&x
                 d[3] = next.template load<NT>(3);
             }
             pk24_decode<r == 3>(d[A], base);
-            pair_step2<0, 0, true, OP>(f32x2{d[A].x, d[A].y}, xi, yi, zi, st, rx, ry, rz, s2);
-            pair_step2<0, 1, false, OP>(f32x2{d[A].z, d[A].w}, xi, yi, zi, st, rx, ry, rz, s2);
+            pair_step2<0, 0, true, OP, false>(f32x2{d[A].x, d[A].y}, xi, yi, zi, st, rx, ry, rz, s2);
+            pair_step2<0, 1, false, OP, false>(f32x2{d[A].z, d[A].w}, xi, yi, zi, st, rx, ry, rz, s2);
             if constexpr (r == 0) d[0] = next.template load<NT>(0);
             if constexpr (r == 2) d[4] = next.template load<NT>(4);
-            if constexpr (r == 1) d[2] = d[3];
-            pk24_decode<r == 3>(d[B], base);
-            pair_step2<1, 0, false, OP>(f32x2{d[B].x, d[B].y}, xi, yi, zi, st, rx, ry, rz, s2);
-            pair_step2<1, 1, false, OP>(f32x2{d[B].z, d[B].w}, xi, yi, zi, st, rx, ry, rz, s2);
+            if constexpr (r == 1) pk24_decode_to(d[2], d[3], base);
+            else pk24_decode<r == 3>(d[B], base);
+            pair_step2<1, 0, false, OP, false>(f32x2{d[B].x, d[B].y}, xi, yi, zi, st, rx, ry, rz, s2);
+            pair_step2<1, 1, false, OP, false>(f32x2{d[B].z, d[B].w}, xi, yi, zi, st, rx, ry, rz, s2);
             if constexpr (r == 0) d[1] = next.template load<NT>(1);
             if constexpr (r == 1) d[2] = next.template load<NT>(2);
             if constexpr (r == 2) d[5] = next.template load<NT>(5);
@@ -773,6 +793,10 @@ __device__ __forceinline__ bool pk24_packed(const int4 &e) { return e.z < 0; }
 __device__ __forceinline__ bool pk24_packed(const int2 &) { return false; }
 __device__ __forceinline__ unsigned pk24_base(const int4 &e) { return (unsigned)e.w; }
 __device__ __forceinline__ unsigned pk24_base(const int2 &) { return 0u; }
+// the packed BODY runs a packed unit whose base is not 0 (no zero in it: process_unit_f32); a
+// packed unit with base 0 is 6 KiB of zero dwords and goes through the raw body
+__device__ __forceinline__ bool pk24_packed_body(const int4 &e) { return e.z < 0 && e.w != 0; }
+__device__ __forceinline__ bool pk24_packed_body(const int2 &) { return false; }
 
 // One wave = one contiguous chunk of units; 4 independent waves per workgroup.
 // No LDS, no barriers, no atomics: results are bitwise reproducible.
@@ -839,8 +863,8 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
 
 // The fp32 sweep over the 24-bit stream: `units` is the stream, `udesc` its int4 table.  Built
 // for the waves per SIMD the sweep runs with (waves_per_cu): two in workgroups of 8 waves, one
-// in workgroups of 4 -- hipcc needs 222 resp. 266 registers for the two bodies.  Ranks that
-// share a GPU do not use it (ensure_pk24): their kernels share the wave slots.
+// in workgroups of 4 -- hipcc takes 256 registers for the two bodies in either form, no scratch.
+// Ranks that share a GPU do not use it (ensure_pk24): their kernels share the wave slots.
 // (T = float, W = true only; parameters so that the body's choices by type stay dependent)
 template <typename T, bool W, bool NT, int OP, int WPB>
 __global__ __launch_bounds__(64 * WPB, (WPB == 8 ? 2 : 1)) void stream24_grad_kernel(

@@ -221,25 +221,37 @@
             // register k from KiB k of the next unit whichever body issues it, so a packed run
             // finds its 6 loads there (what a raw body fetched beyond them is not looked at: the
             // stream ends in 8 KiB of padding), and a raw run asks for the two it is short of.
+            // The packed body has no empty-pair mask and runs the packed units with base != 0,
+            // which hold no zero (process_unit_f32).  A packed unit with base 0 is all zeros, 6 KiB
+            // of zero dwords in the stream: window registers 0..5 hold its distances (+0.0) as they
+            // are, 6 and 7 are set, and the RAW body computes what it computes on such a unit
+            // without the stream, the signs of its zero sums included.  That run is one unit
+            // long: the body's refills 6 and 7 come from beyond the next unit's 6 KiB if that
+            // one is packed, so whatever follows enters its run afresh.
             for (;;) {
                 const int curj = dc.y;
                 strip_load(curj);
                 for (;;) {
-                    if (pk24_packed(dc)) {
+                    if (pk24_packed_body(dc)) {
                         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
                         do {
                             unit_step(u, std::true_type{});
                             ++u;
-                        } while (u < ub && dc.y == curj && pk24_packed(dc));
+                        } while (u < ub && dc.y == curj && pk24_packed_body(dc));
                     } else {
-                        const Win here = window_here();
-                        d[6] = here.template load<NT>(6);
-                        d[7] = here.template load<NT>(7);
+                        const bool zeros = pk24_packed(dc);
+                        if (zeros) {
+                            d[6] = d[7] = make_float4(0.f, 0.f, 0.f, 0.f);
+                        } else {
+                            const Win here = window_here();
+                            d[6] = here.template load<NT>(6);
+                            d[7] = here.template load<NT>(7);
+                        }
                         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
                         do {
                             unit_step(u, std::false_type{});
                             ++u;
-                        } while (u < ub && dc.y == curj && !pk24_packed(dc));
+                        } while (!zeros && u < ub && dc.y == curj && !pk24_packed(dc));
                     }
                     if (u >= ub || dc.y != curj) break;
                 }
