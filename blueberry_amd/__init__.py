@@ -23,6 +23,10 @@ Net-new (the reference has no solver; docs/SPEC.md):
                                   computation of blueberry/fithic.py:76-108 without its files)
     q_values                      Benjamini-Hochberg q-values of p-values in any order: stable
                                   sort, scan and scatter on the device (SPEC 2.9.7)
+    compare_structures, StructureComparison
+                                  structure against structure: superposition up to a mirror image,
+                                  pair distances per separation and per bin, Spearman ranks by the
+                                  device's sort (SPEC 2.10)
 
 All compute runs in libblueberry_hip.so (hand-written HIP for gfx950) behind
 the C-ABI of include/blueberry_hip.h.  Importing this package needs neither
@@ -34,6 +38,7 @@ from .utils import (HIGH_FITHIC_CUTOFF, LOW_FITHIC_CUTOFF, Q_LOWER_BOUND,  # noq
 from .band import count_band_regions  # noqa: F401
 from .datatypes import (ContactMap, EigenNoConvergence, FithicContactMap,  # noqa: F401
                         shortest_paths)
+from .compare import StructureComparison, compare_structures  # noqa: F401
 from .fithic import FitHiC, binomial_sf  # noqa: F401
 from .solver import (DeviceTriples, FitScore, GeodesicRows, HipEngine, RankDeficient,  # noqa: F401
                      StructureSolver, TriplesBalance, balance_triples, landmark_coefficients,

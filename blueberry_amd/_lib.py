@@ -15,6 +15,7 @@ BB_OK, BB_ERR_INVALID, BB_ERR_HIP, BB_ERR_STATE, BB_ERR_NOMEM = 0, 1, 2, 3, 4
 BB_F32, BB_F64 = 0, 1
 BB_KIND_WISH, BB_KIND_COUNTS = 0, 1
 BB_PEER_HANDLE_BYTES = 128
+BB_CMP_SPEARMAN = 1
 
 c_i32, c_i64, c_dbl = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 p_i32, p_i64, p_dbl = (ctypes.POINTER(c_i32), ctypes.POINTER(c_i64), ctypes.POINTER(c_dbl))
@@ -171,6 +172,9 @@ SIGNATURES = {
     "bb_q_values": (c_int, [p_dbl, c_i64, c_i64, p_dbl, p_i64, c_int]),
     "bb_downsample": (c_int, [ctypes.POINTER(ctypes.c_float), c_i64,
                               ctypes.POINTER(ctypes.c_float), c_i64, c_int]),
+    "bb_structures_moments": (c_int, [p_dbl, p_dbl, ctypes.POINTER(ctypes.c_uint8), c_i64, c_int, p_dbl]),
+    "bb_structures_compare": (c_int, [p_dbl, p_dbl, ctypes.POINTER(ctypes.c_uint8), c_i64, p_dbl, c_int,
+                                      c_int, p_dbl, p_dbl, p_dbl, p_dbl, p_dbl, p_dbl]),
 }
 
 _lib = None

@@ -197,20 +197,12 @@ __global__ __launch_bounds__(256) void downsample_kernel(const float *__restrict
 // ---- the q-value rule (docs/SPEC.md 2.9.7) -------------------------------------------------------
 typedef bb::sort_key u64;
 
-// numpy's order of float64 as the unsigned order of 64 bits: negatives (bits inverted) below the
-// zeros (both signs one key) below the positives (sign bit set), every NaN above them all
-__device__ __forceinline__ u64 qv_key(double v) {
-    const u64 b = (u64)__double_as_longlong(v), top = (u64)1 << 63;
-    if (v != v) return ~(u64)0;
-    if (v == 0.0) return top;
-    return (b & top) ? ~b : (b | top);
-}
-
+// (the key: bb::order_key of bb_sort.h, numpy's order of float64)
 __global__ __launch_bounds__(256) void qv_key_kernel(const double *__restrict__ p, int64_t m,
                                                      u64 *__restrict__ keys, uint32_t *__restrict__ place) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= m) return;
-    keys[i] = qv_key(p[i]);
+    keys[i] = bb::order_key(p[i]);
     place[i] = (uint32_t)i;
 }
 

@@ -28,6 +28,15 @@ typedef unsigned long long sort_key;
 
 constexpr int kSortRounds = 16, kSortTile = 256 * kSortRounds;
 
+// numpy's order of float64 as the unsigned order of 64 bits: negatives (bits inverted) below the
+// zeros (both signs one key) below the positives (sign bit set), every NaN above them all
+__device__ __forceinline__ sort_key order_key(double v) {
+    const sort_key b = (sort_key)__double_as_longlong(v), top = (sort_key)1 << 63;
+    if (v != v) return ~(sort_key)0;
+    if (v == 0.0) return top;
+    return (b & top) ? ~b : (b | top);
+}
+
 static __global__ __launch_bounds__(256) void digit_hist_kernel(const sort_key *__restrict__ keys, int64_t m,
                                                                 int shift, int64_t n_wg,
                                                                 sort_key *__restrict__ hist) {

@@ -1931,6 +1931,17 @@ class StructureSolver(object):
             bins = _sum_over_ranks(bins, eng, world)
         return FitScore(profile, bins)
 
+    def compare(self, B, A=None, **kw):
+        """This fit against another structure `B` of the same bins (SPEC 2.10): a
+        `StructureComparison`, `compare_structures(A, B, **kw)` with A = `structure_` of the last
+        fit unless given -- B is laid onto A."""
+        from .compare import compare_structures
+        if A is None:
+            A = getattr(self, "structure_", None)
+            if A is None:
+                raise ValueError("compare: no structure given and none fitted yet (structure_)")
+        return compare_structures(A, B, **kw)
+
     def _group_devices(self):
         """The devices of a devices= / n_gpus= fit (one entry included), checked against this
         process (device count, no torch.distributed job), or None without them."""

@@ -883,6 +883,42 @@ BB_API int bb_q_values(const double *p, int64_t m, int64_t n_tests, double *q, i
  * (n1,n1)) for i, j < n5-1 (reference: blueberry/blueberry.pyx:93-104). */
 BB_API int bb_downsample(const float *yp1, int64_t n1, float *yp5i, int64_t n5, int device);
 
+/* ---------------------------------------------------------------------- */
+/* Structure against structure (docs/SPEC.md 2.10)                          */
+/* ---------------------------------------------------------------------- */
+
+/* a, b: (n, 3) float64 host, 2 <= n < 2^31.  A bin is USED when use[i] != 0 (use = NULL: every
+ * bin) and its six coordinates are finite; without used bins the means are NaN and every sum
+ * is 0 (the Python wrapper refuses fewer than 2 before it calls).  Host in, host out, all arithmetic float64 on the device, every sum in an order fixed by n and the used
+ * bins alone: two calls give the same bits.  No counterpart in the reference (it has no solver;
+ * SURVEY.md 0).
+ *   bb_structures_moments  what a superposition needs, over the used bins, in two passes (means,
+ *                          then centred sums).  out18: the number of used bins, cA (3), cB (3),
+ *                          EA = sum |A_i - cA|^2, EB = sum |B_i - cB|^2, and H row-major,
+ *                          H[p][q] = sum (B_i - cB)_p (A_i - cA)_q.
+ *   bb_structures_compare  transform13 = R row-major, t, s.  aligned (n, 3; may be NULL) =
+ *                          s R B + t; bin_dev (n) = |A_i - aligned_i|^2 -- both NaN at unused
+ *                          bins.  Over the pairs i < j of used bins, dA = |A_i - A_j| and dB =
+ *                          |aligned_i - aligned_j|: profile (n, 7), row k = the pairs of
+ *                          separation j - i = k: pairs, sum dA, sum dB, sum dA^2, sum dB^2,
+ *                          sum dA dB, sum (dA - dB)^2; bins (n, 2), row i = the pairs that hold
+ *                          bin i: pairs, sum (dA - dB)^2.  With BB_CMP_SPEARMAN in flags,
+ *                          rank_sums (4; else may be NULL) = m, sum rA^2, sum rB^2, sum rA rB:
+ *                          m the pairs, r the average rank of a pair's distance among its
+ *                          structure's m, less (m + 1) / 2; the flag without rank_sums, or with
+ *                          m >= 2^32, is BB_ERR_INVALID.  ms (5; may be NULL): HIP-event
+ *                          milliseconds of the transform, the pair pass, its fold, the per-bin
+ *                          pass and the ranks.  Device memory: under 1,200 B per bin + 0.5 MB,
+ *                          and 40 B per pair with the flag; a failed allocation is BB_ERR_NOMEM
+ *                          and the text names the bytes asked for. */
+enum { BB_CMP_SPEARMAN = 1 };
+BB_API int bb_structures_moments(const double *a, const double *b, const uint8_t *use, int64_t n,
+                                 int device, double *out18);
+BB_API int bb_structures_compare(const double *a, const double *b, const uint8_t *use, int64_t n,
+                                 const double *transform13, int flags, int device, double *aligned,
+                                 double *bin_dev, double *profile, double *bins, double *rank_sums,
+                                 double *ms);
+
 #ifdef __cplusplus
 }
 #endif
