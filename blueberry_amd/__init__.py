@@ -11,7 +11,8 @@ Drop-in names (same meaning as in `blueberry.*`, reference
     Q_LOWER_BOUND, Q_UPPER_BOUND, HIGH_FITHIC_CUTOFF, LOW_FITHIC_CUTOFF
                                   blueberry/utils.py:23-26
 Net-new (the reference has no solver; docs/SPEC.md):
-    StructureSolver               contact matrix -> 3D coordinates
+    StructureSolver               contact matrix -> 3D coordinates; alpha='auto' infers the
+                                  count-to-distance exponent in the fit (SPEC 2.11)
     FitScore                      how well a structure fits a map (SPEC 2.8)
     shortest_paths                sparse map -> complete wish distances (SPEC 2.1.1)
     balance_triples, DeviceTriples

@@ -166,6 +166,8 @@ SIGNATURES = {
     "bb_solver_weight_sums": (c_int, [c_void_p, p_dbl, c_i64]),
     "bb_solver_score": (c_int, [c_void_p, p_dbl, p_dbl, p_dbl]),
     "bb_solver_get_score_timing": (c_int, [c_void_p, p_dbl, p_dbl, p_dbl]),
+    "bb_solver_loglog": (c_int, [c_void_p, p_dbl, p_dbl]),
+    "bb_solver_repower": (c_int, [c_void_p, c_dbl]),
     "bb_contactmap_scatter": (c_int, [p_dbl, c_i64, c_i32, p_dbl, c_i64, c_int]),
     "bb_contactmap_normalize": (c_int, [p_dbl, c_i64, p_dbl, p_dbl, c_int]),
     "bb_benjamini_hochberg": (c_int, [p_dbl, c_i64, c_i64, p_dbl, c_int]),

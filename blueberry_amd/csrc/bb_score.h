@@ -23,4 +23,8 @@ struct ScoreInput {
 // float64.  ms (may be NULL): HIP-event times of the profile, fold and per-bin kernels.
 int score_pass(const ScoreInput &in, double *profile, double *bins, double *ms);
 
+// The log-log sums of SPEC 2.11 over the same pairs, by the same profile and fold kernels with
+// seven columns: profile (n_bins, 7), host float64.  ms as above (the per-bin entry stays 0).
+int loglog_pass(const ScoreInput &in, double *profile, double *ms);
+
 }  // namespace bb

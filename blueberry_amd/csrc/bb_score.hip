@@ -15,6 +15,10 @@
 // Slot memory of a call: n_runs * (2 vw - 1) * 9 * 8 bytes (73,656 B per run at vw = 512, a run
 // being at most one tile: 1 MiB of fp32 units, 2 MiB of fp64), + (9 + 3) * 8 * n_bins for the two
 // results and 16 B per run of indices.  One allocation, made for the call and released with it.
+//
+// The log-log sums of SPEC 2.11 (bb_solver_loglog) are the same pass with other terms: the
+// profile and fold kernels take what a pair adds (ScoreTerms: 9 columns, LogTerms: 7) as a
+// template parameter, so the slot scheme, the order of every sum and the reads are shared.
 #include <cmath>
 #include <vector>
 
@@ -23,7 +27,7 @@
 
 namespace {
 
-constexpr int kProfileCols = 9, kBinCols = 3;
+constexpr int kProfileCols = 9, kBinCols = 3, kLogCols = 7;
 
 // |x_i - x_j| in float64: products and sums rounded one by one, ((dx^2 + dy^2) + dz^2), and a
 // correctly rounded root.  No floor: nothing divides by it.
@@ -44,19 +48,44 @@ __device__ __forceinline__ Residuals residuals(double d, double delta) {
     return {res * res, (res * res) / delta, u * u};
 }
 
-__device__ __forceinline__ void add_pair(double (&a)[kProfileCols], double d, double delta) {
+// What a pair adds to the sums of its diagonal: the nine columns of SPEC 2.8 ...
+struct ScoreTerms {
+    static constexpr int COLS = kProfileCols;
+    static __device__ __forceinline__ void add(double (&a)[COLS], double d, double delta) {
 #pragma clang fp contract(off)
-    const Residuals r = residuals(d, delta);
-    a[0] += 1.0;
-    a[1] += d;
-    a[2] += delta;
-    a[3] += d * d;
-    a[4] += delta * delta;
-    a[5] += d * delta;
-    a[6] += r.sq;
-    a[7] += r.sammon;
-    a[8] += r.rel;
-}
+        const Residuals r = residuals(d, delta);
+        a[0] += 1.0;
+        a[1] += d;
+        a[2] += delta;
+        a[3] += d * d;
+        a[4] += delta * delta;
+        a[5] += d * delta;
+        a[6] += r.sq;
+        a[7] += r.sammon;
+        a[8] += r.rel;
+    }
+};
+// ... or the seven of SPEC 2.11: u = log delta, v = log d, products rounded one by one.  A pair
+// with d = 0 has no logarithm: it is counted on its own (column 6) and adds nothing else.  So is
+// a d that is not a number (the solver's own coordinates after a fit that diverged; a given xyz
+// is checked to be finite): the caller that scores its own coordinates checks them.
+struct LogTerms {
+    static constexpr int COLS = kLogCols;
+    static __device__ __forceinline__ void add(double (&a)[COLS], double d, double delta) {
+#pragma clang fp contract(off)
+        if (!(d > 0.0)) {
+            a[6] += 1.0;
+            return;
+        }
+        const double u = log(delta), v = log(d);
+        a[0] += 1.0;
+        a[1] += u;
+        a[2] += v;
+        a[3] += u * u;
+        a[4] += v * v;
+        a[5] += u * v;
+    }
+};
 
 // Sum over the 64 lanes, the same bits in every lane (a + b = b + a): fixed butterfly.
 __device__ __forceinline__ double wave_sum_all(double v) {
@@ -69,8 +98,8 @@ __device__ __forceinline__ double wave_sum_all(double v) {
 // j0, same block of rows I0 = i0 - i0 % VW).  Thread t owns the diagonals o = t + 256 m of the
 // tile, o = (j - j0) - (i - I0) + VW - 1 in [0, 2 VW - 2]; in matrix row i its column is
 // c = o - (VW - 1) + (i - I0), so consecutive threads read consecutive elements and every
-// element of the row has exactly one reader.  slots: (9, 2 VW - 1) doubles per run.
-template <typename T, int VW, int RPU>
+// element of the row has exactly one reader.  slots: (Terms::COLS, 2 VW - 1) doubles per run.
+template <typename T, int VW, int RPU, typename Terms>
 __global__ __launch_bounds__(256) void score_profile_kernel(const T *__restrict__ units,
                                                             const int2 *__restrict__ udesc,
                                                             const int2 *__restrict__ runs,
@@ -83,11 +112,12 @@ __global__ __launch_bounds__(256) void score_profile_kernel(const T *__restrict_
     const int j0 = first.y, I0 = first.x - first.x % VW;
     for (int q = threadIdx.x; q < 3 * VW; q += 256) xs[q] = xyz[(int64_t)j0 * 3 + q];
     __syncthreads();
-    double acc[OPT][kProfileCols];
+    constexpr int COLS = Terms::COLS;
+    double acc[OPT][COLS];
 #pragma unroll
     for (int m = 0; m < OPT; ++m)
 #pragma unroll
-        for (int q = 0; q < kProfileCols; ++q) acc[m][q] = 0.0;
+        for (int q = 0; q < COLS; ++q) acc[m][q] = 0.0;
 
     for (int u = 0; u < run.y; ++u) {
         const int64_t ul = (int64_t)run.x + u;
@@ -113,25 +143,25 @@ __global__ __launch_bounds__(256) void score_profile_kernel(const T *__restrict_
                 const int64_t j = (int64_t)j0 + c;
                 const double delta = (double)v[r][m];
                 if (c >= 0 && c < VW && j > i && j < n_bins && delta > 0.0)
-                    add_pair(acc[m], pair_distance(xi, yi, zi, xs[3 * c], xs[3 * c + 1], xs[3 * c + 2]),
-                             delta);
+                    Terms::add(acc[m], pair_distance(xi, yi, zi, xs[3 * c], xs[3 * c + 1], xs[3 * c + 2]),
+                               delta);
             }
         }
     }
-    double *slot = slots + (int64_t)blockIdx.x * (kProfileCols * NO);
+    double *slot = slots + (int64_t)blockIdx.x * (COLS * NO);
 #pragma unroll
     for (int m = 0; m < OPT; ++m) {
         const int o = (int)threadIdx.x + 256 * m;
         if (o < NO)
 #pragma unroll
-            for (int q = 0; q < kProfileCols; ++q) slot[q * NO + o] = acc[m][q];
+            for (int q = 0; q < COLS; ++q) slot[q * NO + o] = acc[m][q];
     }
 }
 
 // profile[k][col] = the sum over the runs that hold diagonal k, in run order.  A run of tile
 // (I, J) holds k at o = k - (J - I) VW + VW - 1, so only D = J - I in {k / VW, k / VW + 1} can:
 // diff_runs[diff_ptr[D] .. diff_ptr[D + 1]) lists the runs of tile difference D in run order.
-template <int VW>
+template <int VW, int COLS>
 __global__ __launch_bounds__(256) void score_fold_kernel(const double *__restrict__ slots,
                                                          const int *__restrict__ diff_ptr,
                                                          const int *__restrict__ diff_runs, int n_blocks,
@@ -147,10 +177,10 @@ __global__ __launch_bounds__(256) void score_fold_kernel(const double *__restric
             const int o = (int)(k - (int64_t)D * VW) + VW - 1;
             if (o < 0) continue;
             for (int p = diff_ptr[D]; p < diff_ptr[D + 1]; ++p)
-                s += slots[(int64_t)diff_runs[p] * (kProfileCols * NO) + col * NO + o];
+                s += slots[(int64_t)diff_runs[p] * (COLS * NO) + col * NO + o];
         }
     }
-    profile[k * kProfileCols + col] = s;
+    profile[k * COLS + col] = s;
 }
 
 // Per bin i: pairs, sum (d - delta)^2 and sum ((d - delta) / delta)^2 over this rank's stored
@@ -217,9 +247,12 @@ __global__ __launch_bounds__(256) void score_bins_kernel(const T *__restrict__ u
     }
 }
 
-template <typename T, int VW, int RPU>
+// Terms = ScoreTerms: profile (n, 9) and bins (n, 3).  Terms = LogTerms: profile (n, 7), bins NULL
+// (no per-bin kernel runs).
+template <typename T, int VW, int RPU, typename Terms>
 int score_pass_t(const bb::ScoreInput &in, double *profile, double *bins, double *ms) {
     constexpr int64_t NO = 2 * VW - 1;
+    constexpr int COLS = Terms::COLS;
     const int64_t n = in.n_bins, n_blocks = (n + VW - 1) / VW;
     // the runs, and per tile difference D = J - I the runs that have it, in run order
     std::vector<int2> runs;
@@ -246,9 +279,9 @@ int score_pass_t(const bb::ScoreInput &in, double *profile, double *bins, double
         for (int64_t b = 0; b < n_runs; ++b) diff_runs[(size_t)fill[(size_t)run_diff[(size_t)b]]++] = (int)b;
     }
 
-    const size_t slot_bytes = bb::align256((size_t)(n_runs * NO * kProfileCols) * sizeof(double));
-    const size_t prof_bytes = bb::align256((size_t)n * kProfileCols * sizeof(double));
-    const size_t bins_bytes = bb::align256((size_t)n * kBinCols * sizeof(double));
+    const size_t slot_bytes = bb::align256((size_t)(n_runs * NO * COLS) * sizeof(double));
+    const size_t prof_bytes = bb::align256((size_t)n * COLS * sizeof(double));
+    const size_t bins_bytes = bins ? bb::align256((size_t)n * kBinCols * sizeof(double)) : 0;
     const size_t runs_bytes = bb::align256((size_t)n_runs * sizeof(int2));
     const size_t ptr_bytes = bb::align256(diff_ptr.size() * sizeof(int));
     const size_t list_bytes = bb::align256((size_t)n_runs * sizeof(int));
@@ -272,21 +305,24 @@ int score_pass_t(const bb::ScoreInput &in, double *profile, double *bins, double
     if (ms)
         for (bb::Event &e : ev) BB_HIP_CHECK(e.create());
     if (ms) BB_HIP_CHECK(hipEventRecord(ev[0], st));
-    BB_HIP_CHECK(bb::launch(score_profile_kernel<T, VW, RPU>, dim3((unsigned)n_runs), dim3(256), 0, st,
+    BB_HIP_CHECK(bb::launch(score_profile_kernel<T, VW, RPU, Terms>, dim3((unsigned)n_runs), dim3(256), 0, st,
                             (const T *)in.d_units, in.d_udesc, d_runs, in.d_xyz, n, d_slots));
     if (ms) BB_HIP_CHECK(hipEventRecord(ev[1], st));
-    BB_HIP_CHECK(bb::launch(score_fold_kernel<VW>, dim3((unsigned)((n + 255) / 256), kProfileCols), dim3(256),
+    BB_HIP_CHECK(bb::launch(score_fold_kernel<VW, COLS>, dim3((unsigned)((n + 255) / 256), COLS), dim3(256),
                             0, st, d_slots, d_diff_ptr, d_diff_runs, (int)n_blocks, n, d_profile));
     if (ms) BB_HIP_CHECK(hipEventRecord(ev[2], st));
-    BB_HIP_CHECK(bb::launch(score_bins_kernel<T, VW, RPU>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st,
-                            (const T *)in.d_units, in.d_udesc, in.n_local, in.d_xyz, n, d_bins));
-    if (ms) BB_HIP_CHECK(hipEventRecord(ev[3], st));
-    BB_HIP_CHECK(hipMemcpyAsync(profile, d_profile, (size_t)n * kProfileCols * sizeof(double),
+    if (bins) {
+        BB_HIP_CHECK(bb::launch(score_bins_kernel<T, VW, RPU>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st,
+                                (const T *)in.d_units, in.d_udesc, in.n_local, in.d_xyz, n, d_bins));
+        if (ms) BB_HIP_CHECK(hipEventRecord(ev[3], st));
+    }
+    BB_HIP_CHECK(hipMemcpyAsync(profile, d_profile, (size_t)n * COLS * sizeof(double),
                                 hipMemcpyDeviceToHost, st));
-    BB_HIP_CHECK(hipMemcpyAsync(bins, d_bins, (size_t)n * kBinCols * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (bins)
+        BB_HIP_CHECK(hipMemcpyAsync(bins, d_bins, (size_t)n * kBinCols * sizeof(double), hipMemcpyDeviceToHost, st));
     BB_HIP_CHECK(hipStreamSynchronize(st));
     if (ms)
-        for (int k = 0; k < 3; ++k) {
+        for (int k = 0; k < (bins ? 3 : 2); ++k) {       // (no per-bin kernel: its entry stays 0)
             float t = 0.f;
             BB_HIP_CHECK(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
             ms[k] = t;
@@ -298,15 +334,27 @@ int score_pass_t(const bb::ScoreInput &in, double *profile, double *bins, double
 
 namespace bb {
 
-int score_pass(const ScoreInput &in, double *profile, double *bins, double *ms) {
-    for (int64_t q = 0; q < in.n_bins * kProfileCols; ++q) profile[q] = 0.0;
-    for (int64_t q = 0; q < in.n_bins * kBinCols; ++q) bins[q] = 0.0;
+namespace {
+template <typename Terms>
+int pass_by_shape(const ScoreInput &in, double *profile, double *bins, double *ms) {
+    for (int64_t q = 0; q < in.n_bins * Terms::COLS; ++q) profile[q] = 0.0;
+    if (bins)
+        for (int64_t q = 0; q < in.n_bins * kBinCols; ++q) bins[q] = 0.0;
     if (ms) ms[0] = ms[1] = ms[2] = 0.0;
     if (in.n_local == 0) return BB_OK;             // a rank without units: zeros
     // the three unit shapes of docs/SPEC.md 3 (Lay<T, W> of the solver's kernels)
-    if (in.dtype == BB_F32) return score_pass_t<float, 512, 4>(in, profile, bins, ms);
-    if (in.wide) return score_pass_t<double, 512, 2>(in, profile, bins, ms);
-    return score_pass_t<double, 128, 8>(in, profile, bins, ms);
+    if (in.dtype == BB_F32) return score_pass_t<float, 512, 4, Terms>(in, profile, bins, ms);
+    if (in.wide) return score_pass_t<double, 512, 2, Terms>(in, profile, bins, ms);
+    return score_pass_t<double, 128, 8, Terms>(in, profile, bins, ms);
+}
+}  // namespace
+
+int score_pass(const ScoreInput &in, double *profile, double *bins, double *ms) {
+    return pass_by_shape<ScoreTerms>(in, profile, bins, ms);
+}
+
+int loglog_pass(const ScoreInput &in, double *profile, double *ms) {
+    return pass_by_shape<LogTerms>(in, profile, nullptr, ms);
 }
 
 }  // namespace bb

@@ -1518,16 +1518,17 @@ int bb_solver_anchor_stress(bb_solver *s, double *stress) {
 // staging buffer of set_coords / get_coords as float64 (the caller's, or the solver's own
 // widened); the pass itself is bb_score.hip's and keeps what it allocates for the call only.
 // Coordinates, velocity, stress history and per-bin steps are not touched.
-int bb_solver_score(bb_solver *s, const double *xyz, double *profile, double *bins) {
-    BB_REQUIRE(s != nullptr && profile != nullptr && bins != nullptr, "bb_solver_score: NULL argument");
-    if (s->n_maps > 1) return bb::fail(BB_ERR_STATE, "bb_solver_score: not for a solver of several maps");
-    if (!s->have_wish) return bb::fail(BB_ERR_STATE, "bb_solver_score: no wish distances set");
-    if (s->grad_pending) return bb::fail(BB_ERR_STATE, "bb_solver_score: a bb_solver_grad is pending");
+// (who = the entry's name; bins NULL: the log-log sums of SPEC 2.11, whose profile has 7 columns)
+static int score_or_loglog(bb_solver *s, const char *who, const double *xyz, double *profile, double *bins) {
+    const std::string w(who);
+    if (s->n_maps > 1) return bb::fail(BB_ERR_STATE, w + ": not for a solver of several maps");
+    if (!s->have_wish) return bb::fail(BB_ERR_STATE, w + ": no wish distances set");
+    if (s->grad_pending) return bb::fail(BB_ERR_STATE, w + ": a bb_solver_grad is pending");
     if (xyz == nullptr && !s->have_coords)
-        return bb::fail(BB_ERR_STATE, "bb_solver_score: no coordinates set");
+        return bb::fail(BB_ERR_STATE, w + ": no coordinates set");
     if (xyz != nullptr)
         for (int64_t q = 0; q < s->L.n_bins * 3; ++q)
-            BB_REQUIRE(std::isfinite(xyz[q]), "bb_solver_score: coordinates must be finite");
+            BB_REQUIRE(std::isfinite(xyz[q]), w + ": coordinates must be finite");
     BB_TRY(bb::enter_device(s->device));
     if (xyz != nullptr) BB_HIP_CHECK(upload_padded(s, s->d_f64_tmp, xyz, s->stream));
     else BB_HIP_CHECK(widen(s, s->d_X, s->d_f64_tmp, s->L.n_pad * 3));
@@ -1536,12 +1537,47 @@ int bb_solver_score(bb_solver *s, const double *xyz, double *profile, double *bi
     in.n_bins = s->L.n_bins, in.n_local = s->n_local;
     in.d_units = s->d_units, in.d_udesc = s->d_udesc, in.udesc = s->udesc.data();
     in.d_xyz = s->d_f64_tmp, in.stream = s->stream;
-    const int rc = bb::score_pass(in, profile, bins, s->timing ? s->score_ms : nullptr);
+    double *ms = s->timing ? s->score_ms : nullptr;
+    const int rc = bins ? bb::score_pass(in, profile, bins, ms) : bb::loglog_pass(in, profile, ms);
     // (whatever happened, nothing of the call is left on the stream: the host arrays behind the
     // upload above belong to the caller)
     if (hipStreamSynchronize(s->stream) != hipSuccess && rc == BB_OK)
-        return bb::fail(BB_ERR_HIP, "bb_solver_score: the stream did not drain");
+        return bb::fail(BB_ERR_HIP, w + ": the stream did not drain");
     return rc;
+}
+
+int bb_solver_score(bb_solver *s, const double *xyz, double *profile, double *bins) {
+    BB_REQUIRE(s != nullptr && profile != nullptr && bins != nullptr, "bb_solver_score: NULL argument");
+    return score_or_loglog(s, "bb_solver_score", xyz, profile, bins);
+}
+
+// SPEC 2.11: the log-log sums over the pairs of the score pass, by its kernels (bb_score.hip).
+int bb_solver_loglog(bb_solver *s, const double *xyz, double *profile) {
+    BB_REQUIRE(s != nullptr && profile != nullptr, "bb_solver_loglog: NULL argument");
+    return score_or_loglog(s, "bb_solver_loglog", xyz, profile, nullptr);
+}
+
+// SPEC 2.11: the units re-exponentiated in place, then what every writer of the units does.
+int bb_solver_repower(bb_solver *s, double p) {
+    BB_REQUIRE(s != nullptr, "bb_solver_repower: solver is NULL");
+    BB_REQUIRE(std::isfinite(p) && p > 0.0, "bb_solver_repower: p must be finite and > 0");
+    if (!s->have_wish) return bb::fail(BB_ERR_STATE, "bb_solver_repower: no wish distances set");
+    if (s->grad_pending) return bb::fail(BB_ERR_STATE, "bb_solver_repower: a bb_solver_grad is pending");
+    if (s->anchor_n > 0)
+        return bb::fail(BB_ERR_STATE, "bb_solver_repower: the solver holds landmark anchors, whose "
+                                      "geodesic rows are not a power of anything");
+    BB_TRY(bb::enter_device(s->device));
+    s->pk_stale = true;   // d_units is about to be written: whatever happens, the 24-bit stream is not of it
+    if (s->n_local > 0)
+        BB_TRY(by_layout(s, [&](auto lay) -> int {
+            using T = typename decltype(lay)::T;
+            const int64_t n_words = s->n_local * (bb::kUnitBytes / (int64_t)sizeof(T));
+            const unsigned grid = (unsigned)std::min<int64_t>((n_words + 255) / 256, 256 * 64);
+            BB_HIP_CHECK(bb::launch(repower_units_kernel<T>, dim3(grid), dim3(256), 0, s->stream,
+                                    (T *)s->d_units, n_words, p));
+            return BB_OK;
+        }));
+    return inputs_done(s);
 }
 
 int bb_solver_get_score_timing(bb_solver *s, double *profile_ms, double *fold_ms, double *bins_ms) {

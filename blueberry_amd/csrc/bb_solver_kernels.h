@@ -1689,6 +1689,19 @@ __global__ __launch_bounds__(256) void gen_units_kernel(const double *__restrict
     });
 }
 
+// SPEC 2.11: every stored word w > 0 of this rank's units becomes pow((double)w, p), taken as
+// a kind='wish' input (the one value rule of bb_wish.h: floor, ceiling, rounding to T); zeros
+// stay zeros.  n_words = n_local * (8 KiB / sizeof(T)); a grid-stride loop, one word per thread.
+template <typename T>
+__global__ __launch_bounds__(256) void repower_units_kernel(T *__restrict__ units, int64_t n_words,
+                                                            double p) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n_words; e += stride) {
+        const T w = units[e];
+        if (w > T(0)) units[e] = wish_from_value<T>(pow((double)w, p), BB_KIND_WISH, 0.0);
+    }
+}
+
 // --------------------------------------------------------------------------
 // row-owner path: small maps, one launch per iteration
 // --------------------------------------------------------------------------

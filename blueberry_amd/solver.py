@@ -14,6 +14,7 @@ torch (`GroupEngine`: one solver per device, one host thread each, the sum over 
 ordered by HIP events, `bb_group_*`).
 """
 import contextlib
+import math
 import os
 import sys
 
@@ -654,6 +655,20 @@ class HipEngine(object):
                    _lib.as_f64_ptr(profile), _lib.as_f64_ptr(bins))
         return profile, bins
 
+    def loglog(self, xyz=None):
+        """The log-log sums of SPEC 2.11 over this rank's units (`bb_solver_loglog`): float64 of
+        shape (n_bins, 7), row k = the pairs of separation k: pairs with d > 0, sum u, sum v,
+        sum u^2, sum v^2, sum u v (u = log delta, v = log d), pairs with d = 0.  xyz as `score`."""
+        profile = numpy.zeros((self.n_bins, 7), dtype=numpy.float64)
+        self._call("loglog", None if xyz is None else _lib.as_f64_ptr(_check_coords(xyz, self.n_bins)),
+                   _lib.as_f64_ptr(profile))
+        return profile
+
+    def repower(self, p):
+        """Every stored wish distance w > 0 becomes w^p under the wish rule of SPEC 2.1, in place
+        (`bb_solver_repower`); degrees and weight sums are the caller's to recompute."""
+        self._call("repower", float(p))
+
     def stress_maps(self):
         out = numpy.empty(self.n_maps, dtype=numpy.float64)
         self._call("stress_maps", _lib.as_f64_ptr(out), out.shape[0])
@@ -884,7 +899,8 @@ class HipEngine(object):
                 "step_ms": float(self._get(_lib.c_dbl, "get_step_timing"))}
 
     def score_timing(self):
-        """(profile_ms, fold_ms, bins_ms) of the last `score` made with timing on."""
+        """(profile_ms, fold_ms, bins_ms) of the last `score` or `loglog` (bins_ms = 0) made with
+        timing on."""
         t = [_lib.c_dbl() for _ in range(3)]
         self._call("get_score_timing", *t)
         return tuple(float(v.value) for v in t)
@@ -1037,6 +1053,13 @@ class GroupEngine(object):
             p, b = e.score(xyz)
             profile, bins = profile + p, bins + b
         return profile, bins
+
+    def loglog(self, xyz=None):
+        """SPEC 2.11 over the whole map: the members' sums added in rank order."""
+        return self._summed("loglog", xyz)
+
+    def repower(self, p):
+        self._each("repower", p)
 
     def matvec_sq(self, x):
         """(D o D) @ x over the whole map: the members' products summed in rank order (the
@@ -1258,6 +1281,88 @@ def weighted_steps(sums, n_bins, dtype, lr, degree_steps):
     return out_lr, numpy.where(s > 0.0, top / numpy.where(s > 0.0, s, 1.0), 1.0)
 
 
+# -- the count-to-distance exponent inferred in the fit (SPEC 2.11) -------------------------------
+ALPHA_MIN, ALPHA_MAX = 0.25, 16.0      # what a step of the search is clipped to
+
+
+def _check_alpha(alpha):
+    """The constructor's `alpha` normalised: a positive float, or ('auto', alpha0, max_rounds,
+    tol) from 'auto' and the tuples that begin with it (defaults 3.0, 8, 1e-3)."""
+    if isinstance(alpha, str) or isinstance(alpha, tuple):
+        form = (alpha,) if isinstance(alpha, str) else alpha
+        if not (1 <= len(form) <= 4 and isinstance(form[0], str) and form[0] == "auto"):
+            raise ValueError("alpha must be a positive number, 'auto', ('auto', alpha0), ('auto', "
+                             "alpha0, max_rounds) or ('auto', alpha0, max_rounds, tol)")
+        def number(v, what):
+            if isinstance(v, bool) or not isinstance(v, (int, float, numpy.integer, numpy.floating)):
+                raise ValueError("alpha: %s of 'auto' must be a number" % what)
+            return float(v)
+        alpha0 = number(form[1], "the start alpha0") if len(form) > 1 else 3.0
+        rounds = form[2] if len(form) > 2 else 8
+        tol = number(form[3], "tol") if len(form) > 3 else 1e-3
+        if not (numpy.isfinite(alpha0) and alpha0 > 0):
+            raise ValueError("alpha: the start alpha0 of 'auto' must be positive and finite")
+        if (isinstance(rounds, bool) or not isinstance(rounds, (int, numpy.integer))
+                or not 1 <= int(rounds) <= 64):
+            raise ValueError("alpha: max_rounds of 'auto' must be an int in [1, 64]")
+        if not (numpy.isfinite(tol) and tol > 0):
+            raise ValueError("alpha: tol of 'auto' must be positive and finite")
+        return ("auto", alpha0, int(rounds), tol)
+    if not float(alpha) > 0:
+        raise ValueError("alpha must be positive")
+    return float(alpha)
+
+
+def loglog_totals(profile):
+    """The seven sums of SPEC 2.11 over all separations of one rank's (n_bins, 7) profile, added
+    in ascending k."""
+    p = numpy.asarray(profile, dtype=numpy.float64)
+    return numpy.cumsum(p, axis=0)[-1] if p.shape[0] else numpy.zeros(7)
+
+
+def loglog_slope(totals):
+    """(p, a, r_log, mean u, mean v) from the seven totals (pairs, sum u, sum v, sum u^2,
+    sum v^2, sum u v, pairs with d = 0): the least-squares line v = a + p u of log fitted
+    distance on log wish distance and their correlation (NaN when v does not vary).
+    ValueError: fewer than 3 usable pairs, or a var(u) that the rounding of its own sums could
+    have made (SPEC 2.8's guard): the map's counts do not vary.  RuntimeError: p <= 0."""
+    n, su, sv, suu, svv, suv = (float(t) for t in numpy.asarray(totals, dtype=numpy.float64)[:6])
+    if n < 3:
+        raise ValueError("alpha='auto': fewer than 3 usable pairs (stored, delta > 0, d > 0): "
+                         "no slope to take")
+    noise = 8.0 * n * n * 2.0 ** -53
+    var_u, var_v = n * suu - su * su, n * svv - sv * sv
+    if not var_u > noise * suu:
+        raise ValueError("alpha='auto': the wish distances of the stored pairs do not vary (the "
+                         "map's counts are all alike): no exponent can be inferred")
+    cov = n * suv - su * sv
+    p = cov / var_u
+    if not p > 0:
+        raise RuntimeError("alpha='auto': the log-log slope of fitted on wish distance is %.6g "
+                           "<= 0: the fit does not follow the map (more iterations, another "
+                           "start or a fixed alpha)" % p)
+    r_log = cov / numpy.sqrt(var_u * var_v) if var_v > noise * svv else float("nan")
+    ubar, vbar = su / n, sv / n
+    return p, vbar - p * ubar, float(r_log), ubar, vbar
+
+
+def next_alpha(history):
+    """The exponent of the next round from history = [(alpha_0, p_0), ..., (alpha_r, p_r)]
+    (SPEC 2.11): alpha_r / p_r after the first round; later a secant step on (ln alpha, ln p),
+    alpha_r / p_r again when its slope g is not finite and > 0; clipped to [alpha_r / 2,
+    2 alpha_r], then to [ALPHA_MIN, ALPHA_MAX]."""
+    a1, p1 = (float(v) for v in history[-1][:2])
+    nxt = a1 / p1
+    if len(history) >= 2:
+        a0, p0 = (float(v) for v in history[-2][:2])
+        with numpy.errstate(divide="ignore", invalid="ignore"):
+            g = numpy.float64(math.log(p1) - math.log(p0)) / numpy.float64(math.log(a1) - math.log(a0))
+        if numpy.isfinite(g) and g > 0:
+            nxt = math.exp(math.log(a1) - math.log(p1) / float(g))
+    nxt = min(max(nxt, a1 / 2.0), 2.0 * a1)
+    return min(max(nxt, ALPHA_MIN), ALPHA_MAX)
+
+
 def allreduce_exchange(t):
     """Sum a device-resident exchange tensor over all ranks, in place: one
     all-reduce of 3*n_pad+2 elements (backend nccl = RCCL, over xGMI)."""
@@ -1420,8 +1525,27 @@ class StructureSolver(object):
         Step size; 'auto' = 1 / (2 * n_bins).
     dtype : 'float32' or 'float64'
         Arithmetic type on the GPU.
-    alpha : float
-        Count-to-distance exponent, delta = c^(-1/alpha).
+    alpha : float, 'auto', ('auto', alpha0), ('auto', alpha0, max_rounds) or
+            ('auto', alpha0, max_rounds, tol)
+        Count-to-distance exponent, delta = c^(-1/alpha).  'auto' infers it in the fit (SPEC
+        2.11): after `n_iter` iterations at alpha0 (3.0) the log-log slope p of fitted on wish
+        distance is taken on the device; while |p - 1| > tol (1e-3) and fewer than max_rounds
+        (8) rounds have run, the next exponent comes from a secant step on (ln alpha, ln p),
+        the resident wish distances are re-exponentiated in place, the structure is rescaled
+        and `n_iter` iterations run again.  Then the map is packed once more at `alpha_` and
+        `n_iter` iterations run from `alpha_init_`: `structure_` and `stress_` are bit for bit
+        those of StructureSolver(alpha=alpha_, ...).fit(X, init=alpha_init_).  The options ride
+        in `alpha` (stored normalised; `alpha_start`, `alpha_rounds`, `alpha_tol` read them
+        back) so that clones carry them.  For every input of `fit` and `fit_triples`
+        (`balance=`, `devices=`, a distributed world: every rank takes the same alpha); `score`
+        then uses `alpha_` (ValueError before a fit).  ValueError with kind='wish' (no counts),
+        complete='shortest_path' and init='landmark' (distances that are sums along paths
+        cannot be re-exponentiated) and for `fit_many`; ValueError for a map with fewer than 3
+        usable pairs or whose counts do not vary; RuntimeError when a slope is <= 0 or a round's
+        coordinates are not finite (the fit diverged).  Exact on
+        noise-free maps; on Poisson-sampled counts whose zero cells are dropped the estimate is
+        biased upwards (3.27 for a true 3; 3.58 with weight_power=2): the zeros are truncated
+        and the estimator has no model for them.
     kind : 'counts' or 'wish'
         Whether the input matrix holds contact counts or wish distances.
     seed : int
@@ -1507,6 +1631,11 @@ class StructureSolver(object):
         'host', 'group' for devices=), None on one rank.  Results are reproducible bit for
         bit for a given transport; fit() never picks one by timing (that is bench.py's trial).
     devices_ : the devices of a `devices=` / `n_gpus=` fit, member by member; else None.
+    alpha_ : the exponent of the fit: the inferred one under alpha='auto', else `alpha`.
+    alpha_rounds_ : (rounds, 5) float64, per round of the search alpha_r, the slope p_r, the
+        intercept a_r, the log-log correlation, the iterations run; (0, 5) for a float alpha.
+    alpha_converged_ : whether the search ended by |p - 1| <= tol (True for a float alpha).
+    alpha_init_ : (n_bins, 3), the start of the last fit under 'auto'; None for a float alpha.
 
     Failure on several ranks.  A rank that fails mid-fit raises, and takes the library's
     communicator out of the cache (its peers may still sit in a collective on it).  With
@@ -1533,8 +1662,15 @@ class StructureSolver(object):
                              "lives on the device (include/blueberry_hip.h, bb_solver_iterate)")
         if not (lr == "auto" or float(lr) > 0):
             raise ValueError("lr must be positive or 'auto'")
-        if not float(alpha) > 0:
-            raise ValueError("alpha must be positive")
+        alpha = _check_alpha(alpha)
+        if isinstance(alpha, tuple):
+            if kind == "wish":
+                raise self._auto_refusal("infers the exponent of counts: kind='wish' holds wish "
+                                         "distances, which have none")
+            if init == "landmark" or (isinstance(init, tuple) and init[:1] == ("landmark",)):
+                raise self._auto_refusal("does not go with init='landmark': the landmark start and "
+                                         "its geodesic rows are made of the wish distances of one "
+                                         "alpha, which the search changes")
         if not 0.0 <= float(momentum) < 1.0:
             raise ValueError("momentum must be in [0, 1)")
         self.momentum = float(momentum)
@@ -1559,7 +1695,7 @@ class StructureSolver(object):
             raise ValueError("weight_power must be 0, 1 or 2")
         self.weight_power = int(weight_power)
         self.n_iter, self.lr, self.dtype, self.alpha, self.kind, self.seed = (
-            int(n_iter), lr, dtype, float(alpha), kind, int(seed))
+            int(n_iter), lr, dtype, alpha, kind, int(seed))
         self.device, self.distributed = device, distributed
         # Engine factory: the HIP engine unless a test injects another one to
         # rehearse the multi-rank orchestration without a GPU.
@@ -1583,6 +1719,39 @@ class StructureSolver(object):
         if self.device is not None:
             return int(self.device)
         return int(os.environ.get("LOCAL_RANK", "0")) if world > 1 else 0
+
+    @staticmethod
+    def _auto_refusal(why):
+        return ValueError("alpha='auto' %s; give a float alpha" % why)
+
+    @property
+    def alpha_auto(self):
+        """Whether the exponent is inferred in the fit (alpha='auto' in any form, SPEC 2.11)."""
+        return isinstance(self.alpha, tuple)
+
+    @property
+    def alpha_start(self):
+        """alpha0 of alpha=('auto', alpha0, ...) (3.0 for 'auto'); a float alpha: that alpha."""
+        return self.alpha[1] if self.alpha_auto else self.alpha
+
+    @property
+    def alpha_rounds(self):
+        """max_rounds of alpha=('auto', alpha0, max_rounds, ...) (8); None for a float alpha."""
+        return self.alpha[2] if self.alpha_auto else None
+
+    @property
+    def alpha_tol(self):
+        """tol of alpha=('auto', alpha0, max_rounds, tol) (1e-3); None for a float alpha."""
+        return self.alpha[3] if self.alpha_auto else None
+
+    def _pack_alpha(self):
+        """The exponent a map is packed under outside a search: the float alpha, or alpha_ of
+        the last 'auto' fit (ValueError before one)."""
+        if not self.alpha_auto:
+            return self.alpha
+        if getattr(self, "alpha_", None) is None:
+            raise ValueError("alpha='auto': no exponent inferred yet (alpha_ is set by a fit)")
+        return self.alpha_
 
     @property
     def n_landmarks(self):
@@ -1680,6 +1849,7 @@ class StructureSolver(object):
             (720 GB dense at 10 kb) cannot be completed this way (MemoryError); init='landmark'
             (SPEC 2.5.4) is the route of such a map to its global fold."""
         _check_complete(complete)
+        self._check_auto_route(complete)
         if self._landmark_wanted(init):
             try:
                 start = self._landmark_init_of_map(X, complete)
@@ -1694,6 +1864,12 @@ class StructureSolver(object):
         self.completed_unreachable_pairs_ = cm.unreachable_pairs_
         source, n = self._map_source(cm)
         return self._fit_impl(source, n, init, None, None, kind="wish")
+
+    def _check_auto_route(self, complete):
+        if self.alpha_auto and complete is not None:
+            raise self._auto_refusal("does not go with complete='shortest_path': the completed "
+                                     "distances are sums along paths, not a power of a count, so "
+                                     "they cannot be re-exponentiated")
 
     def _landmark_init_of_map(self, X, complete):
         """fit(X) under init='landmark': the start of a scipy.sparse X, whose COO entries are the
@@ -1809,8 +1985,13 @@ class StructureSolver(object):
         lr = 1.0 / (2.0 * n) if self.lr == "auto" else float(self.lr)
         if init is None and self.init == "random":
             init = self._default_start(n)
+        auto = self.alpha_auto
+        if auto and not (hasattr(eng, "loglog") and hasattr(eng, "repower")):
+            eng.close()
+            raise self._auto_refusal("needs an engine with the log-log pass and the "
+                                     "re-exponentiation (HipEngine)")
         with _teardown(eng):
-            pack(kind, KRnorm, KRexpected)
+            pack(kind, KRnorm, KRexpected, self.alpha_start)
             self._take_anchor(eng, world)
             anchored = bool(getattr(eng, "anchored", False))
             sums = self._bin_sums(eng, world)
@@ -1855,9 +2036,16 @@ class StructureSolver(object):
             if world > 1:
                 select_exchange(eng, lr)
             # converged: the relative decrease of the last step is <= tol (never at stress 0)
-            self._iterate(lambda k: run_iterations(eng, k, lr, world), eng.stress_history,
-                          lambda h: h.size >= 2 and h[-2] > 0
-                          and abs(h[-2] - h[-1]) <= self.tol * h[-2])
+            def run(lr):
+                self._iterate(lambda k: run_iterations(eng, k, lr, world), eng.stress_history,
+                              lambda h: h.size >= 2 and h[-2] > 0
+                              and abs(h[-2] - h[-1]) <= self.tol * h[-2])
+            run(lr)
+            if auto:
+                lr = self._alpha_search(eng, world, n, run, lambda a: pack(kind, KRnorm, KRexpected, a))
+            else:
+                self.alpha_, self.alpha_rounds_ = self.alpha, numpy.zeros((0, 5))
+                self.alpha_converged_, self.alpha_init_ = True, None
             if _exchange_state(eng) == "peer":
                 eng.peer_status()              # raises if a peer wait ran into its time limit
             self.exchange_ = _exchange_state(eng)
@@ -1897,16 +2085,65 @@ class StructureSolver(object):
             eng = self._engine_factory(n, self.dtype, rank=rank, world=world,
                                        device=self._pick_device(world), tiles=tiles)
 
-        def pack(kind, KRnorm, KRexpected):
+        def pack(kind, KRnorm, KRexpected, alpha=None):
+            alpha = self._pack_alpha() if alpha is None else alpha
             if resident:
-                eng.set_wish_resident(matrix, kind, self.alpha)
+                eng.set_wish_resident(matrix, kind, alpha)
             elif triples:
-                eng.set_wish_triples(matrix, kind, self.alpha, KRnorm, KRexpected)
+                eng.set_wish_triples(matrix, kind, alpha, KRnorm, KRexpected)
             elif sparse:
-                eng.set_wish_sparse(rows, cols, vals, kind, self.alpha, KRnorm, KRexpected)
+                eng.set_wish_sparse(rows, cols, vals, kind, alpha, KRnorm, KRexpected)
             else:
-                eng.set_wish_dense(matrix, kind, self.alpha)
+                eng.set_wish_dense(matrix, kind, alpha)
         return eng, world, devices, pack
+
+    def _alpha_search(self, eng, world, n, run, pack_at):
+        """SPEC 2.11 on the engine of a fit whose round 0 (packed at alpha_start, `n_iter`
+        iterations from the fit's start) has just run: the rounds of the search -- log-log sums,
+        slope, next exponent, the units re-exponentiated on the device, the structure rescaled
+        -- and then the fit proper at alpha_: the map packed once more from the input by
+        pack_at(alpha), the steps recomputed, `n_iter` iterations from alpha_init_.  run(lr)
+        iterates; returns the lr of that last fit.  Every rank takes the same decisions: the
+        sums are the same on all of them."""
+        def steps():
+            lr = 1.0 / (2.0 * n) if self.lr == "auto" else float(self.lr)
+            sums = self._bin_sums(eng, world)
+            if sums is not None:
+                lr, scale = self._steps(sums, n)
+                eng.set_bin_steps(scale)            # (None: one step for all again)
+            return lr
+        _, alpha, max_rounds, tol = self.alpha
+        rounds, converged = [], False
+        while True:
+            x = eng.get_coords()
+            if not numpy.isfinite(x).all():
+                # (a distance that is not a number has no logarithm either: the sums would count
+                # it with the pairs at d = 0 and the slope would speak of too few pairs)
+                raise RuntimeError("alpha='auto': the fit diverged in round %d at alpha = %.6g (its "
+                                   "coordinates are not finite): a smaller lr, or a fixed alpha"
+                                   % (len(rounds), alpha))
+            iters = int(eng.stress_history().shape[0])
+            totals =_sum_over_ranks(loglog_totals(eng.loglog()), eng, world)
+            p, a, r_log, ubar, vbar = loglog_slope(totals)
+            rounds.append((alpha, p, a, r_log, float(iters)))
+            converged = abs(p - 1.0) <= tol
+            if converged or len(rounds) == max_rounds:
+                break
+            nxt = next_alpha(rounds)
+            power = alpha / nxt
+            eng.repower(power)
+            lr = steps()
+            eng.set_coords(math.exp(power * ubar - vbar) * x)
+            alpha = nxt
+            run(lr)
+        self.alpha_, self.alpha_converged_ = float(alpha), bool(converged)
+        self.alpha_rounds_ = numpy.array(rounds, dtype=numpy.float64)
+        self.alpha_init_ = math.exp(ubar - vbar) * x
+        pack_at(self.alpha_)
+        lr = steps()
+        eng.set_coords(self.alpha_init_)
+        run(lr)
+        return lr
 
     def score(self, X, structure=None):
         """How well a structure fits the map `X` (SPEC 2.8): a `FitScore`.  `X` takes every
@@ -2001,6 +2238,7 @@ class StructureSolver(object):
         balanced (`ContactMap.balance`).  `triples` may be a `DeviceTriples` on this solver's
         device (one-device fits without `complete`), which stays open."""
         _check_complete(complete)
+        self._check_auto_route(complete)
         n = int(n_bins) + 1
         landmark = self._landmark_wanted(init)
         if landmark:
@@ -2098,6 +2336,9 @@ class StructureSolver(object):
             raise ValueError("fit_many with devices= / n_gpus= is not supported: fit_many runs "
                              "on one device, or one per rank of a torch.distributed job")
         _check_complete(complete)
+        if self.alpha_auto:
+            raise self._auto_refusal("is not for fit_many: its maps share one solver and one "
+                                     "exponent, and a per-map alpha is not covered")
         if self.n_landmarks is not None:
             raise self._landmark_refusal("is not for fit_many, which packs dense blocks",
                                          "complete='shortest_path' or init='spectral'")

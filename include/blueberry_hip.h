@@ -479,6 +479,31 @@ BB_API int bb_solver_stress(bb_solver *s, double *stress);
 BB_API int bb_solver_score(bb_solver *s, const double *xyz, double *profile, double *bins);
 BB_API int bb_solver_get_score_timing(bb_solver *s, double *profile_ms, double *fold_ms,
                                       double *bins_ms);
+/* Inferring the count-to-distance exponent (docs/SPEC.md 2.11): the two device passes of the
+ * search StructureSolver(alpha='auto') runs; the search itself is the caller's.
+ *   bb_solver_loglog   the log-log sums of a structure against the resident map, over the
+ *                      pairs of bb_solver_score (stored, i < j < n_bins, delta > 0) and with its
+ *                      d: profile (n_bins, 7), row k = the pairs of separation k: pairs with
+ *                      d > 0, sum u, sum v, sum u^2, sum v^2, sum u v (u = log delta, v = log d,
+ *                      float64), and the pairs with d = 0, which add nothing else (a d that is
+ *                      not a number -- xyz = NULL after a fit that diverged -- counts there
+ *                      too: check the solver's own coordinates before relying on it).  Same pass,
+ *                      same order of every sum, same state rules, same errors and the same xyz
+ *                      as bb_solver_score; scratch runs * (2 vw - 1) * 56 bytes + 56 n_bins.
+ *                      With bb_solver_set_timing on, bb_solver_get_score_timing then reports
+ *                      this call's profile and fold kernels (bins_ms = 0).
+ *   bb_solver_repower  every stored word w > 0 of this rank's units becomes pow((double)w, p),
+ *                      taken as a BB_KIND_WISH input (floor, ceiling, rounding to the dtype);
+ *                      zeros stay.  delta = c^(-1/a) thereby becomes c^(-1/a') for p = a / a'
+ *                      without the input.  The row-owner matrix is rebuilt, the 24-bit stream
+ *                      is stale; degrees and weight sums are the caller's to recompute (pairs
+ *                      may have left by the floor or the ceiling).  Coordinates, velocity and
+ *                      stress history stay.  BB_ERR_INVALID unless p is finite and > 0;
+ *                      BB_ERR_STATE before wish distances are set, while a bb_solver_grad is
+ *                      pending, and with landmark anchors set (geodesic rows are no power of
+ *                      anything). */
+BB_API int bb_solver_loglog(bb_solver *s, const double *xyz, double *profile);
+BB_API int bb_solver_repower(bb_solver *s, double p);
 /* Copies the stress history (one value per completed iteration since the
  * last bb_solver_set_coords) to the host; synchronises the stream. */
 BB_API int bb_solver_get_stress_history(bb_solver *s, double *out, int64_t cap, int64_t *n);
