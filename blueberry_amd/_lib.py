@@ -20,6 +20,7 @@ BB_CMP_SPEARMAN = 1
 c_i32, c_i64, c_dbl = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 p_i32, p_i64, p_dbl = (ctypes.POINTER(c_i32), ctypes.POINTER(c_i64), ctypes.POINTER(c_dbl))
 c_int, c_void_p = ctypes.c_int, ctypes.c_void_p
+p_u8 = ctypes.POINTER(ctypes.c_ubyte)       # uint8_t: masks and flags
 
 
 class LayoutInfo(ctypes.Structure):
@@ -52,7 +53,7 @@ SIGNATURES = {
                                           p_dbl, p_dbl]),
     "bb_triples_create": (c_int, [ctypes.POINTER(c_void_p), p_dbl, c_i64, c_i32, c_i32, c_int]),
     "bb_triples_destroy": (c_int, [c_void_p]),
-    "bb_triples_tiles": (c_int, [c_void_p, c_i64, c_int, ctypes.POINTER(ctypes.c_uint8), c_i64]),
+    "bb_triples_tiles": (c_int, [c_void_p, c_i64, c_int, p_u8, c_i64]),
     "bb_solver_set_wish_triples": (c_int, [c_void_p, c_void_p, c_int, c_dbl, p_dbl, p_dbl]),
     "bb_solver_set_wish_from_coords": (c_int, [c_void_p, p_dbl]),
     "bb_solver_set_coords": (c_int, [c_void_p, p_dbl]),
@@ -110,21 +111,21 @@ SIGNATURES = {
     "bb_cm_upload": (c_int, [c_void_p, p_dbl, c_i64]),
     "bb_cm_download": (c_int, [c_void_p, p_dbl, c_i64]),
     "bb_cm_scatter": (c_int, [c_void_p, p_dbl, c_i64, c_i32]),
-    "bb_cm_scatter_ex": (c_int, [c_void_p, p_dbl, c_i64, c_i32, c_i32, ctypes.POINTER(ctypes.c_uint8),
+    "bb_cm_scatter_ex": (c_int, [c_void_p, p_dbl, c_i64, c_i32, c_i32, p_u8,
                                  ctypes.POINTER(c_i32)]),
     "bb_cm_normalize": (c_int, [c_void_p, c_i64, p_dbl, p_dbl]),
     "bb_cm_marginals": (c_int, [c_void_p, p_dbl]),
-    "bb_cm_filter": (c_int, [c_void_p, c_dbl, p_i64, ctypes.POINTER(ctypes.c_uint8)]),
+    "bb_cm_filter": (c_int, [c_void_p, c_dbl, p_i64, p_u8]),
     "bb_cm_symv": (c_int, [c_void_p, p_dbl, p_dbl]),
     "bb_cm_eigenvector": (c_int, [c_void_p, p_dbl, p_dbl, c_dbl, c_i64, p_i64, p_dbl]),
     "bb_cm_correlation": (c_int, [c_void_p, p_dbl]),
     "bb_cm_release_scratch": (c_int, [c_int]),
     "bb_cm_shortest_paths": (c_int, [c_void_p, c_void_p, c_int, c_dbl, p_i64]),
     "bb_cm_balance": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_dbl, c_i64, c_dbl, p_dbl,
-                              ctypes.POINTER(ctypes.c_uint8), p_i64, p_dbl]),
+                              p_u8, p_i64, p_dbl]),
     "bb_cm_expected": (c_int, [c_void_p, c_i64, p_dbl, p_dbl, p_i64]),
     "bb_triples_balance": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_dbl, c_i64, c_dbl, p_dbl,
-                                   ctypes.POINTER(ctypes.c_uint8), p_i64, p_dbl]),
+                                   p_u8, p_i64, p_dbl]),
     "bb_triples_expected": (c_int, [c_void_p, c_i64, p_dbl, p_dbl, p_i64]),
     "bb_triples_pairs": (c_int, [c_void_p, c_i64, p_i64]),
     "bb_triples_edge_degrees": (c_int, [c_void_p, c_i64, c_int, c_dbl, p_dbl, p_dbl, p_i64]),
@@ -134,10 +135,10 @@ SIGNATURES = {
     "bb_paths_reached": (c_int, [c_void_p, p_i64]),
     "bb_paths_read": (c_int, [c_void_p, p_dbl]),
     "bb_paths_read_columns": (c_int, [c_void_p, p_i64, c_i64, p_dbl]),
-    "bb_paths_place": (c_int, [c_void_p, p_dbl, p_dbl, p_dbl, ctypes.POINTER(ctypes.c_uint8)]),
+    "bb_paths_place": (c_int, [c_void_p, p_dbl, p_dbl, p_dbl, p_u8]),
     "bb_paths_timing": (c_int, [c_void_p, p_dbl, p_dbl]),
     "bb_paths_destroy": (c_int, [c_void_p]),
-    "bb_solver_set_anchors": (c_int, [c_void_p, c_void_p, ctypes.POINTER(ctypes.c_uint8), c_dbl]),
+    "bb_solver_set_anchors": (c_int, [c_void_p, c_void_p, p_u8, c_dbl]),
     "bb_solver_anchor_sums": (c_int, [c_void_p, p_dbl, c_i64]),
     "bb_solver_anchor_stress": (c_int, [c_void_p, p_dbl]),
     "bb_solver_anchor_info": (c_int, [c_void_p, p_i64, p_i64, p_i64]),
@@ -174,8 +175,8 @@ SIGNATURES = {
     "bb_q_values": (c_int, [p_dbl, c_i64, c_i64, p_dbl, p_i64, c_int]),
     "bb_downsample": (c_int, [ctypes.POINTER(ctypes.c_float), c_i64,
                               ctypes.POINTER(ctypes.c_float), c_i64, c_int]),
-    "bb_structures_moments": (c_int, [p_dbl, p_dbl, ctypes.POINTER(ctypes.c_uint8), c_i64, c_int, p_dbl]),
-    "bb_structures_compare": (c_int, [p_dbl, p_dbl, ctypes.POINTER(ctypes.c_uint8), c_i64, p_dbl, c_int,
+    "bb_structures_moments": (c_int, [p_dbl, p_dbl, p_u8, c_i64, c_int, p_dbl]),
+    "bb_structures_compare": (c_int, [p_dbl, p_dbl, p_u8, c_i64, p_dbl, c_int,
                                       c_int, p_dbl, p_dbl, p_dbl, p_dbl, p_dbl, p_dbl]),
 }
 
@@ -235,3 +236,59 @@ def check(rc, what=""):
 
 def as_f64_ptr(arr):
     return arr.ctypes.data_as(p_dbl)
+
+
+class Handle(object):
+    """Owner of one library handle (`_h`, a c_void_p) whose entry points are `prefix` + name.
+    The subclass names `prefix` and makes the handle with `_create`, or adopts one that another
+    call returned.  `close()` (or leaving the `with` block, or the last reference going) destroys
+    it; any call after that is a ValueError raised here, before C sees the NULL."""
+    prefix = None                       # "bb_solver_", "bb_cm_", ...
+
+    def __init__(self, handle=None):
+        self._lib = load()
+        self._h = c_void_p() if handle is None else handle
+
+    def _create(self, *args):
+        """<prefix>create(&handle, *args)."""
+        name = self.prefix + "create"
+        check(getattr(self._lib, name)(self._h, *args), name)
+
+    def _open(self):
+        if not self._h:
+            raise ValueError("this %s handle is closed" % self.prefix[:-1])
+        return self._h
+
+    def _status(self, name, *args):
+        """The status of <prefix><name>(handle, *args), for the few calls where a status other
+        than BB_OK is an outcome the caller handles and not an error."""
+        return getattr(self._lib, self.prefix + name)(self._open(), *args)
+
+    def _call(self, name, *args):
+        """<prefix><name>(handle, *args); any status but BB_OK raises (`check`)."""
+        check(self._status(name, *args), self.prefix + name)
+
+    def _get(self, ctype, name, *args):
+        """The one scalar <prefix><name>(handle, *args, &out) writes: ctype is c_int, c_dbl
+        or c_i64."""
+        out = ctype()
+        self._call(name, *args, out)
+        return out.value
+
+    def close(self):
+        """Destroy the handle; again, or on an object whose create failed: nothing."""
+        if getattr(self, "_h", None):
+            getattr(self._lib, self.prefix + "destroy")(self._h)
+            self._h = c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

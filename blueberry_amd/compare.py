@@ -1,8 +1,6 @@
 """Structure against structure (docs/SPEC.md 2.10): the two O(1) / O(n) host steps of a
 comparison -- the used-bin vector and the 3 x 3 SVD of the superposition -- around the two device
 calls that do the rest (`bb_structures_moments`, `bb_structures_compare`)."""
-import ctypes
-
 import numpy
 
 from . import _lib
@@ -10,8 +8,6 @@ from . import _lib
 # the places of a pair are 32 bits wide on the device, so the C entry refuses 2^32 pairs or more;
 # the documented limit here is floor(sqrt(2^33)) bins, one below the last count that would fit
 MAX_SPEARMAN_BINS = 92681
-
-_p_u8 = ctypes.POINTER(ctypes.c_uint8)
 
 
 def superposition(moments, mirror=True, scale=False):
@@ -161,14 +157,14 @@ def compare_structures(A, B, mask=None, mirror=True, scale=False, spearman=False
     lib = _lib.load()
     use = numpy.ascontiguousarray(used, dtype=numpy.uint8)
     moments = numpy.zeros(18)
-    _lib.check(lib.bb_structures_moments(_lib.as_f64_ptr(A), _lib.as_f64_ptr(B), use.ctypes.data_as(_p_u8), n,
+    _lib.check(lib.bb_structures_moments(_lib.as_f64_ptr(A), _lib.as_f64_ptr(B), use.ctypes.data_as(_lib.p_u8), n,
                                          device, _lib.as_f64_ptr(moments)), "bb_structures_moments")
     R, t, s, mirrored = superposition(moments, mirror=mirror, scale=scale)
     transform = numpy.concatenate([R.reshape(9), t, [s]])
     aligned, bin_dev = numpy.zeros((n, 3)), numpy.zeros(n)
     sums, bin_sums = numpy.zeros((n, 7)), numpy.zeros((n, 2))
     rank_sums = numpy.zeros(4) if spearman else None
-    _lib.check(lib.bb_structures_compare(_lib.as_f64_ptr(A), _lib.as_f64_ptr(B), use.ctypes.data_as(_p_u8), n,
+    _lib.check(lib.bb_structures_compare(_lib.as_f64_ptr(A), _lib.as_f64_ptr(B), use.ctypes.data_as(_lib.p_u8), n,
                                          _lib.as_f64_ptr(transform), _lib.BB_CMP_SPEARMAN if spearman else 0,
                                          device, _lib.as_f64_ptr(aligned), _lib.as_f64_ptr(bin_dev),
                                          _lib.as_f64_ptr(sums), _lib.as_f64_ptr(bin_sums),

@@ -87,14 +87,30 @@ def _nan_to_num(a):
     return a if numpy.isfinite(a).all() else numpy.nan_to_num(a)
 
 
-class _DeviceMatrix(object):
+def triples_buffer(triples):
+    """(t, buf, row_major) of a `triples` argument: t, its float64 (n, 3) view (ValueError for
+    another shape); buf, the array C reads, and whether it holds t row by row.  C-ordered rows
+    are read in place; the reference's own layout -- pandas hands it an F-ordered array and its
+    pointer arithmetic reads that column-major (pyx:111-113) -- is read in place too; anything
+    else is copied once."""
+    t = numpy.asarray(triples, dtype=numpy.float64)
+    if t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError("triples must have shape (n, 3)")
+    if t.flags.c_contiguous:
+        return t, t, 1
+    if t.flags.f_contiguous:
+        return t, t.T, 0
+    return t, numpy.ascontiguousarray(t), 1
+
+
+class _DeviceMatrix(_lib.Handle):
     """Owner of one bb_cm handle: the (d, d) float64 matrix resident in HBM."""
+    prefix = "bb_cm_"
 
     def __init__(self, d, device):
-        self._lib = _lib.load()
-        self._h = _lib.c_void_p()
+        _lib.Handle.__init__(self)
         self.device = int(device)
-        _lib.check(self._lib.bb_cm_create(self._h, int(d), self.device), "bb_cm_create")
+        self._create(int(d), self.device)
 
     @classmethod
     def from_triples(cls, triples, resolution, n_bins, device, want_regions=False):
@@ -102,29 +118,15 @@ class _DeviceMatrix(object):
         `numpy.union1d(pos_i, pos_j)` (pyx:120): when every position is exactly
         bin * resolution -- Rao's format -- it is the bins the scatter kernel saw times the
         resolution (no sort of 2n doubles on the host); otherwise numpy's own union1d."""
-        import ctypes
         # numpy.nan_to_num (pyx:102) is applied by the scatter kernels to the values they read:
         # no pass over the triples on the host
-        t = numpy.asarray(triples, dtype=numpy.float64)
-        if t.ndim != 2 or t.shape[1] != 3:
-            raise ValueError("triples must have shape (n, 3)")
-        # C-ordered rows are read in place; the reference's own layout -- pandas hands it
-        # an F-ordered array and its pointer arithmetic reads that column-major
-        # (pyx:111-113) -- is read in place too; anything else is copied once
-        if t.flags.c_contiguous:
-            buf, row_major = t, 1
-        elif t.flags.f_contiguous:
-            buf, row_major = t.T, 0
-        else:
-            buf, row_major = numpy.ascontiguousarray(t), 1
+        t, buf, row_major = triples_buffer(triples)
         d = int(n_bins) + 1
         self = cls(d, device)                                               # zeros, pyx:99
         present = numpy.zeros(d, dtype=numpy.uint8)
         on_grid = _lib.c_i32(0)
-        _lib.check(self._lib.bb_cm_scatter_ex(
-            self._h, _lib.as_f64_ptr(buf), t.shape[0], int(resolution), row_major,
-            present.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(on_grid)),
-            "bb_cm_scatter")
+        self._call("scatter_ex", _lib.as_f64_ptr(buf), t.shape[0], int(resolution), row_major,
+                   present.ctypes.data_as(_lib.p_u8), on_grid)
         if not want_regions:
             return self
         if on_grid.value:
@@ -137,32 +139,19 @@ class _DeviceMatrix(object):
     def from_host(cls, matrix, device):
         m = numpy.ascontiguousarray(matrix, dtype=numpy.float64)
         self = cls(m.shape[0], device)
-        _lib.check(self._lib.bb_cm_upload(self._h, _lib.as_f64_ptr(m), m.shape[1]), "bb_cm_upload")
+        self._call("upload", _lib.as_f64_ptr(m), m.shape[1])
         return self
 
     @property
     def d(self):
-        n = _lib.c_i64()
-        _lib.check(self._lib.bb_cm_dim(self._h, n), "bb_cm_dim")
-        return int(n.value)
+        return int(self._get(_lib.c_i64, "dim"))
 
     def to_host(self):
         d = self.d
         out = numpy.empty((d, d), dtype=numpy.float64)
         if d:
-            _lib.check(self._lib.bb_cm_download(self._h, _lib.as_f64_ptr(out), d), "bb_cm_download")
+            self._call("download", _lib.as_f64_ptr(out), d)
         return out
-
-    def close(self):
-        if self._h:
-            self._lib.bb_cm_destroy(self._h)
-            self._h = _lib.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def check_balance_args(ignore_diags=0, min_nnz=0, tol=1e-5, max_iter=200, row_sum=None):
@@ -189,6 +178,47 @@ def expected_from_sums(sums, counts):
     e = numpy.full(sums.shape, numpy.nan)
     e[ok] = sums[ok] / numpy.asarray(counts)[ok]
     return e
+
+
+def _balance(target, n, args):
+    """`ContactMap.balance` and `DeviceTriples.balance` in one: the ICE bias of `target`'s map
+    over bins 0 .. n - 1 (`bb_cm_balance` / `bb_triples_balance`, whichever handle
+    `target._balance_target()` is) under `args`, the tuple `check_balance_args` returned; the
+    four `balance_*_` attributes are left on `target`."""
+    ignore_diags, min_nnz, tol, max_iter, row_sum = args
+    bias = numpy.empty(n, dtype=numpy.float64)
+    masked = numpy.zeros(n, dtype=numpy.uint8)
+    it, var = _lib.c_i64(), _lib.c_dbl()
+    target._balance_target()._call(
+        "balance", n, ignore_diags, min_nnz, tol, max_iter, 0.0 if row_sum is None else float(row_sum),
+        _lib.as_f64_ptr(bias), masked.ctypes.data_as(_lib.p_u8), it, var)
+    target.balance_iterations_, target.balance_variance_ = int(it.value), float(var.value)
+    target.balance_converged_ = target.balance_variance_ < tol
+    target.balance_masked_ = masked.astype(bool)
+    return bias
+
+
+def expected_sums(dev, n, bias=None):
+    """(sums, counts) per distance k = 0 .. n - 1 of the handle `dev`'s map divided by
+    bias[i] bias[j] (`bb_cm_expected` / `bb_triples_expected`; None: all ones)."""
+    sums = numpy.zeros(n, dtype=numpy.float64)
+    counts = numpy.zeros(n, dtype=numpy.int64)
+    dev._call("expected", n, None if bias is None else _lib.as_f64_ptr(bias), _lib.as_f64_ptr(sums),
+              counts.ctypes.data_as(_lib.p_i64))
+    return sums, counts
+
+
+def _expected(target, n, bias):
+    """`ContactMap.expected` and `DeviceTriples.expected` in one: the expected of `target`'s map
+    over bins 0 .. n - 1 under `bias` (None or n values); `expected_sums_` and
+    `expected_counts_` are left on `target`."""
+    if bias is not None:
+        bias = numpy.ascontiguousarray(bias, dtype=numpy.float64)
+        if bias.shape != (n,):
+            raise ValueError("bias must have n_bins = %d values, got shape %r" % (n, bias.shape))
+    sums, counts = expected_sums(target._balance_target(), n, bias)
+    target.expected_sums_, target.expected_counts_ = sums, counts
+    return expected_from_sums(sums, counts)
 
 
 class EigenNoConvergence(RuntimeError):
@@ -418,7 +448,7 @@ class ContactMap(object):
             return numpy.zeros(0)
         dev = self._resident()
         out = numpy.empty(dev.d, dtype=numpy.float64)
-        _lib.check(dev._lib.bb_cm_marginals(dev._h, _lib.as_f64_ptr(out)), "bb_cm_marginals")
+        dev._call("marginals", _lib.as_f64_ptr(out))
         return out
 
     def filter(self, threshold=0, keep_stale=False):
@@ -433,10 +463,7 @@ class ContactMap(object):
         d = dev.d
         keep = numpy.zeros(d, dtype=numpy.uint8)
         dn = _lib.c_i64()
-        import ctypes
-        _lib.check(dev._lib.bb_cm_filter(dev._h, float(threshold), dn,
-                                         keep.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
-                   "bb_cm_filter")
+        dev._call("filter", float(threshold), dn, keep.ctypes.data_as(_lib.p_u8))
         keep = keep.astype(bool)
         if not keep_stale:
             # bins that survive, in the old numbering; the zero padding row
@@ -472,9 +499,7 @@ class ContactMap(object):
         ke = numpy.ascontiguousarray(self._KRexpected[:n], dtype=numpy.float64)
         if n and (numpy.any(kr == 0.0) or numpy.any(ke == 0.0)):
             raise ZeroDivisionError("float division")
-        dev = self._resident()
-        _lib.check(dev._lib.bb_cm_normalize(dev._h, n, _lib.as_f64_ptr(kr), _lib.as_f64_ptr(ke)),
-                   "bb_cm_normalize")
+        self._resident()._call("normalize", n, _lib.as_f64_ptr(kr), _lib.as_f64_ptr(ke))
 
     # -- balancing a raw map (docs/SPEC.md 2.5.2) --------------------------
     def _balance_target(self):
@@ -515,24 +540,10 @@ class ContactMap(object):
         cell raises ValueError.  apply=False leaves the matrix as it is, bit for bit; apply=True
         then divides it in place by b_i b_j (`normalize()` with an all-ones expected vector:
         masked bins become 0).  The same bits on every run."""
-        import ctypes
-        ignore_diags, min_nnz, tol, max_iter, row_sum = check_balance_args(
-            ignore_diags, min_nnz, tol, max_iter, row_sum)
-        dev = self._balance_target()
-        n = self.n_bins
-        bias = numpy.empty(n, dtype=numpy.float64)
-        masked = numpy.zeros(n, dtype=numpy.uint8)
-        it, var = _lib.c_i64(), _lib.c_dbl()
-        _lib.check(dev._lib.bb_cm_balance(
-            dev._h, n, ignore_diags, min_nnz, tol, max_iter, 0.0 if row_sum is None else float(row_sum),
-            _lib.as_f64_ptr(bias), masked.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), it, var),
-            "bb_cm_balance")
-        self._KRnorm = bias
-        self.balance_iterations_, self.balance_variance_ = int(it.value), float(var.value)
-        self.balance_converged_ = self.balance_variance_ < tol
-        self.balance_masked_ = masked.astype(bool)
+        args = check_balance_args(ignore_diags, min_nnz, tol, max_iter, row_sum)
+        self._KRnorm = bias = _balance(self, self.n_bins, args)
         if apply:
-            self._divide(bias, numpy.ones(n))
+            self._divide(bias, numpy.ones(self.n_bins))
         return bias
 
     def expected(self, bias="auto", apply=False):
@@ -557,18 +568,7 @@ class ContactMap(object):
                 if bias.shape[0] < n:
                     raise ValueError("KRnorm shorter than n_bins")
                 bias = bias[:n]
-        if bias is not None:
-            bias = numpy.ascontiguousarray(bias, dtype=numpy.float64)
-            if bias.shape != (n,):
-                raise ValueError("bias must have n_bins = %d values, got shape %r" % (n, bias.shape))
-        dev = self._balance_target()
-        sums = numpy.zeros(n, dtype=numpy.float64)
-        counts = numpy.zeros(n, dtype=numpy.int64)
-        _lib.check(dev._lib.bb_cm_expected(
-            dev._h, n, None if bias is None else _lib.as_f64_ptr(bias), _lib.as_f64_ptr(sums),
-            counts.ctypes.data_as(_lib.p_i64)), "bb_cm_expected")
-        self._KRexpected = expected_from_sums(sums, counts)
-        self.expected_sums_, self.expected_counts_ = sums, counts
+        self._KRexpected = _expected(self, n, bias)
         if apply:
             self._divide(numpy.ones(n), self._KRexpected)
         return self._KRexpected
@@ -591,9 +591,7 @@ class ContactMap(object):
         if self.shape[0] == 0:
             return
         dev = self._resident()
-        tf = _lib.c_dbl()
-        _lib.check(dev._lib.bb_cm_correlation(dev._h, tf), "bb_cm_correlation")
-        self.correlation_tflops_ = float(tf.value)
+        self.correlation_tflops_ = float(dev._get(_lib.c_dbl, "correlation"))
 
     def shortest_paths(self, alpha=3.0, kind="counts"):
         """Complete the map by graph shortest paths (docs/SPEC.md 2.1.1; ShRec3D, Isomap): a
@@ -650,8 +648,7 @@ class ContactMap(object):
         d = dev.d
         vec = numpy.empty(d, dtype=numpy.float64)
         lam, used, res = _lib.c_dbl(), _lib.c_i64(), _lib.c_dbl()
-        _lib.check(dev._lib.bb_cm_eigenvector(dev._h, _lib.as_f64_ptr(vec), lam, float(tol),
-                                              int(max_matvecs), used, res), "bb_cm_eigenvector")
+        dev._call("eigenvector", _lib.as_f64_ptr(vec), lam, float(tol), int(max_matvecs), used, res)
         self.eigenvalue_, self.eigen_matvecs_, self.eigen_residual_ = (
             float(lam.value), int(used.value), float(res.value))
         if self.eigen_residual_ > max(float(tol), 2.3e-16) * abs(self.eigenvalue_):
@@ -679,10 +676,7 @@ def _completion_arguments(kind, alpha):
 def _shortest_paths_device(src, dst, kind_code, alpha):
     """`bb_cm_shortest_paths` from one _DeviceMatrix into another (or itself); returns the
     number of unreachable pairs."""
-    n = _lib.c_i64()
-    _lib.check(src._lib.bb_cm_shortest_paths(src._h, dst._h, kind_code, alpha, n),
-               "bb_cm_shortest_paths")
-    return int(n.value)
+    return int(src._get(_lib.c_i64, "shortest_paths", dst._open(), kind_code, alpha))
 
 
 def _dense_from_any(X):

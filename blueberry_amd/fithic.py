@@ -15,12 +15,10 @@ Deviations from the reference, all deliberate: one range rule, `mi
 p-values with the number of possible in-range pairs as the number of tests); `n_passes` is accepted
 and unused, as in the reference, where only the first pass runs.
 """
-import ctypes
-
 import numpy
 
 from . import _lib
-from .datatypes import ContactMap, FithicContactMap, _pick_device
+from .datatypes import ContactMap, FithicContactMap, _pick_device, expected_sums
 
 _DIST_SCALING = 10000.0            # `distScaling`, blueberry/fithic.py:45
 
@@ -125,29 +123,26 @@ def prior_by_distance(x, y, n, resolution, k_lo, k_hi):
     return sx, sy, numpy.ascontiguousarray(f, dtype=numpy.float64)
 
 
-class _Results(object):
-    """Owner of one bb_sig handle."""
-
-    def __init__(self, lib, handle):
-        self._lib, self._h = lib, handle
+class _Results(_lib.Handle):
+    """Owner of one bb_sig handle, made by a significance pass or by `select`."""
+    prefix = "bb_sig_"
 
     def size(self):
         n, terms = _lib.c_i64(), _lib.c_i64()
-        _lib.check(self._lib.bb_sig_size(self._h, n, terms), "bb_sig_size")
+        self._call("size", n, terms)
         return int(n.value), int(terms.value)
 
     def timing(self):
         a, b = _lib.c_dbl(), _lib.c_dbl()
-        _lib.check(self._lib.bb_sig_timing(self._h, a, b), "bb_sig_timing")
+        self._call("timing", a, b)
         return float(a.value), float(b.value)
 
     def read(self):
         m = self.size()[0]
         row, col = numpy.empty(m, dtype=numpy.int32), numpy.empty(m, dtype=numpy.int32)
         count, p = numpy.empty(m, dtype=numpy.float64), numpy.empty(m, dtype=numpy.float64)
-        _lib.check(self._lib.bb_sig_read(self._h, row.ctypes.data_as(_lib.p_i32),
-                                         col.ctypes.data_as(_lib.p_i32), _lib.as_f64_ptr(count),
-                                         _lib.as_f64_ptr(p)), "bb_sig_read")
+        self._call("read", row.ctypes.data_as(_lib.p_i32), col.ctypes.data_as(_lib.p_i32),
+                   _lib.as_f64_ptr(count), _lib.as_f64_ptr(p))
         return row, col, count, p
 
     def q_values(self, n_tests):
@@ -155,67 +150,38 @@ class _Results(object):
         handle (`bb_sig_q_values`; again: recomputed).  Returns the HIP-event times (ms) of keys +
         sort and of gather + scan + scatter."""
         a, b = _lib.c_dbl(), _lib.c_dbl()
-        _lib.check(self._lib.bb_sig_q_values(self._h, int(n_tests), a, b), "bb_sig_q_values")
+        self._call("q_values", int(n_tests), a, b)
         return float(a.value), float(b.value)
 
     def read_q(self):
         """The q-values, in list order; RuntimeError before `q_values`."""
         q = numpy.empty(self.size()[0], dtype=numpy.float64)
-        _lib.check(self._lib.bb_sig_read_q(self._h, _lib.as_f64_ptr(q)), "bb_sig_read_q")
+        self._call("read_q", _lib.as_f64_ptr(q))
         return q
 
     def select(self, q_max):
         """The cells with q <= `q_max` as a new `_Results` (close it), in list order; a NaN q is
         never selected.  RuntimeError before `q_values`, ValueError for a NaN `q_max`."""
         out = _lib.c_void_p()
-        _lib.check(self._lib.bb_sig_select(self._h, float(q_max), ctypes.byref(out)), "bb_sig_select")
-        return _Results(self._lib, out)
-
-    def close(self):
-        if self._h:
-            self._lib.bb_sig_destroy(self._h)
-            self._h = _lib.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _device_handle(X):
-    """(the library's handle of the map, its entry points' prefix, its device)."""
-    if isinstance(X, ContactMap):
-        dev = X._balance_target()
-        return dev._h, "bb_cm", dev.device
-    return X._h, "bb_triples", X.device
+        self._call("select", float(q_max), out)
+        return _Results(out)
 
 
 def diagonal_sums(X, n):
     """O_k = sum_i M[i, i + k], k = 0 .. n - 1, of the map's leading n x n block: the sweep of
     `expected` with all weights 1 (`bb_cm_expected` / `bb_triples_expected`, bias NULL).  Leaves
     the map's own expected vector alone."""
-    handle, prefix, _ = _device_handle(X)
-    sums = numpy.zeros(n, dtype=numpy.float64)
-    counts = numpy.zeros(n, dtype=numpy.int64)
-    fn = getattr(_lib.load(), prefix + "_expected")
-    _lib.check(fn(handle, n, None, _lib.as_f64_ptr(sums), counts.ctypes.data_as(_lib.p_i64)),
-               prefix + "_expected")
-    return sums
+    return expected_sums(X._balance_target(), n)[0]
 
 
 def significance_list(X, n, k_lo, k_hi, bias, bias_range, prior, n_reads):
     """The device pass: the listed cells of the map in canonical order and their p-values, as a
     `_Results` (close it).  `bias`, `prior`: n float64 values each."""
-    handle, prefix, _ = _device_handle(X)
     lo, hi = (-numpy.inf, numpy.inf) if bias_range is None else bias_range
     out = _lib.c_void_p()
-    lib = _lib.load()
-    fn = getattr(lib, prefix + "_significance")
-    _lib.check(fn(handle, int(n), int(k_lo), int(k_hi), _lib.as_f64_ptr(bias), float(lo), float(hi),
-                  _lib.as_f64_ptr(prior), float(n_reads), ctypes.byref(out)),
-               prefix + "_significance")
-    return _Results(lib, out)
+    X._balance_target()._call("significance", int(n), int(k_lo), int(k_hi), _lib.as_f64_ptr(bias),
+                              float(lo), float(hi), _lib.as_f64_ptr(prior), float(n_reads), out)
+    return _Results(out)
 
 
 class FitHiC(object):

@@ -21,6 +21,8 @@ import sys
 import numpy
 
 from . import _lib
+from .datatypes import (_balance, _expected, _nan_to_num, _pick_device, check_balance_args,
+                        triples_buffer)
 
 _DTYPES = {"float32": _lib.BB_F32, "float64": _lib.BB_F64}
 _KINDS = {"wish": _lib.BB_KIND_WISH, "counts": _lib.BB_KIND_COUNTS}
@@ -32,7 +34,7 @@ class RankDeficient(RuntimeError):
     `fit()` then takes the host-driven start; every other library error propagates."""
 
 
-class DeviceTriples(object):
+class DeviceTriples(_lib.Handle):
     """The (n, 3) array [pos_i, pos_j, count] of a Rao-format file -- what
     `ContactMap.__init__` reads (`blueberry/datatypes.pyx:100-102`) -- copied to the device
     once (`bb_triples_*`): nan_to_num, binning and the scatter into the solver's tiles all
@@ -43,39 +45,30 @@ class DeviceTriples(object):
     matrix (docs/SPEC.md 2.5.3): the first call builds an index of the stored cells on the
     device, which stays with the handle."""
     is_triples = True
+    prefix = "bb_triples_"
 
     def __init__(self, triples, resolution, device):
-        t = _check_triples(triples)
+        t, buf, row_major = triples_buffer(triples)
         self.resolution = int(resolution)
-        if t.flags.c_contiguous:
-            buf, row_major = t, 1
-        elif t.flags.f_contiguous:
-            buf, row_major = t.T, 0
-        else:
-            buf, row_major = numpy.ascontiguousarray(t), 1
-        self._lib = _lib.load()
-        self._h = _lib.c_void_p()
+        _lib.Handle.__init__(self)
         self.n, self.device = int(t.shape[0]), int(device)
-        _lib.check(self._lib.bb_triples_create(self._h, _lib.as_f64_ptr(buf), self.n,
-                                               int(resolution), row_major, self.device),
-                   "bb_triples_create")
+        self._create(_lib.as_f64_ptr(buf), self.n, int(resolution), row_major, self.device)
+
+    def _balance_target(self):
+        """The handle `balance`, `expected` and the significance pass speak to: this one."""
+        return self
 
     def tiles(self, n_bins, dtype):
         """(tile_I, tile_J), device order, of the tiles the triples name."""
-        import ctypes
         nb = layout_info(n_bins, dtype)["n_blocks"]
         present = numpy.zeros((nb, nb), dtype=numpy.uint8)
-        _lib.check(self._lib.bb_triples_tiles(self._h, int(n_bins), _DTYPES[dtype],
-                                              present.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                              nb), "bb_triples_tiles")
+        self._call("tiles", int(n_bins), _DTYPES[dtype], present.ctypes.data_as(_lib.p_u8), nb)
         tj, ti = numpy.nonzero(present.T)            # J ascending, then I
         return ti.astype(numpy.int32), tj.astype(numpy.int32)
 
     def pairs(self, n_bins):
         """The number of distinct bin pairs i <= j < n_bins the triples store."""
-        out = _lib.c_i64()
-        _lib.check(self._lib.bb_triples_pairs(self._h, int(n_bins), out), "bb_triples_pairs")
-        return int(out.value)
+        return int(self._get(_lib.c_i64, "pairs", int(n_bins)))
 
     def balance(self, n_bins, ignore_diags=0, min_nnz=0, tol=1e-5, max_iter=200, row_sum=None):
         """The ICE bias vector of the map the triples define over bins 0 .. n_bins - 1
@@ -83,45 +76,15 @@ class DeviceTriples(object):
         and the attributes `balance_iterations_`, `balance_variance_`, `balance_converged_`,
         `balance_masked_` of `ContactMap.balance`.  The same bits on every run, and for every
         duplicate-free list of the same pairs."""
-        import ctypes
-        from .datatypes import check_balance_args
-        ignore_diags, min_nnz, tol, max_iter, row_sum = check_balance_args(
-            ignore_diags, min_nnz, tol, max_iter, row_sum)
-        n = int(n_bins)
-        if n < 0:
-            raise ValueError("n_bins must not be negative")
-        bias = numpy.empty(n, dtype=numpy.float64)
-        masked = numpy.zeros(n, dtype=numpy.uint8)
-        it, var = _lib.c_i64(), _lib.c_dbl()
-        _lib.check(self._lib.bb_triples_balance(
-            self._h, n, ignore_diags, min_nnz, tol, max_iter, 0.0 if row_sum is None else float(row_sum),
-            _lib.as_f64_ptr(bias), masked.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), it, var),
-            "bb_triples_balance")
-        self.balance_iterations_, self.balance_variance_ = int(it.value), float(var.value)
-        self.balance_converged_ = self.balance_variance_ < tol
-        self.balance_masked_ = masked.astype(bool)
-        return bias
+        args = check_balance_args(ignore_diags, min_nnz, tol, max_iter, row_sum)
+        return _balance(self, _bin_count(n_bins), args)
 
     def expected(self, n_bins, bias=None):
         """The distance-decay expected e of the balanced map (`bb_triples_expected`,
         `ContactMap.expected`): bias None -- all ones -- or a length-n_bins vector, NaN = not a
         live bin.  `expected_sums_` and `expected_counts_` (int64) hold the two raw vectors;
         pairs without a triple are zero cells and count."""
-        from .datatypes import expected_from_sums
-        n = int(n_bins)
-        if n < 0:
-            raise ValueError("n_bins must not be negative")
-        if bias is not None:
-            bias = numpy.ascontiguousarray(bias, dtype=numpy.float64)
-            if bias.shape != (n,):
-                raise ValueError("bias must have n_bins = %d values, got shape %r" % (n, bias.shape))
-        sums = numpy.zeros(n, dtype=numpy.float64)
-        counts = numpy.zeros(n, dtype=numpy.int64)
-        _lib.check(self._lib.bb_triples_expected(
-            self._h, n, None if bias is None else _lib.as_f64_ptr(bias), _lib.as_f64_ptr(sums),
-            counts.ctypes.data_as(_lib.p_i64)), "bb_triples_expected")
-        self.expected_sums_, self.expected_counts_ = sums, counts
-        return expected_from_sums(sums, counts)
+        return _expected(self, _bin_count(n_bins), bias)
 
     def significance(self, map_bins, **kwargs):
         """The Fit-Hi-C p- and q-values of the map the triples define over bins 0 .. map_bins - 1
@@ -149,9 +112,7 @@ class DeviceTriples(object):
         `alpha` and the KR vectors, as `fit_triples` forms it -- is finite and positive.  int64."""
         n, kind, alpha, kr, ke = self._graph_arguments(n_nodes, kind, alpha, KRnorm, KRexpected)
         deg = numpy.zeros(n, dtype=numpy.int64)
-        _lib.check(self._lib.bb_triples_edge_degrees(self._h, n, kind, alpha, kr, ke,
-                                                     deg.ctypes.data_as(_lib.p_i64)),
-                   "bb_triples_edge_degrees")
+        self._call("edge_degrees", n, kind, alpha, kr, ke, deg.ctypes.data_as(_lib.p_i64))
         return deg
 
     def shortest_paths(self, n_nodes, sources, kind="counts", alpha=3.0, KRnorm=None, KRexpected=None):
@@ -162,64 +123,43 @@ class DeviceTriples(object):
         n, kind, alpha, kr, ke = self._graph_arguments(n_nodes, kind, alpha, KRnorm, KRexpected)
         src = numpy.ascontiguousarray(sources, dtype=numpy.int64).ravel()
         h = _lib.c_void_p()
-        _lib.check(self._lib.bb_triples_paths(self._h, n, kind, alpha, kr, ke,
-                                              src.ctypes.data_as(_lib.p_i64), src.shape[0], h),
-                   "bb_triples_paths")
+        self._call("paths", n, kind, alpha, kr, ke, src.ctypes.data_as(_lib.p_i64), src.shape[0], h)
         return GeodesicRows(h)
 
-    def close(self):
-        if self._h:
-            self._lib.bb_triples_destroy(self._h)
-            self._h = _lib.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class GeodesicRows(object):
+class GeodesicRows(_lib.Handle):
     """What `DeviceTriples.shortest_paths` returns: the (n_sources, n_nodes) float64 geodesics,
     resident on the device as a `bb_paths`, which owns its memory (it may outlive the triples).
     `sweeps_`: Bellman-Ford sweeps made (not reproducible: the distances are updated in place);
     `unreachable_`: (source, node) pairs without a path.  A context manager; `close()` frees it,
     any other call after that is a ValueError."""
     MAX_SOURCES = 1024                      # BB_PATHS_MAX_SOURCES
+    prefix = "bb_paths_"
 
     def __init__(self, handle):
-        self._lib = _lib.load()
-        self._h = handle
+        _lib.Handle.__init__(self, handle)
         ns, nn, sw, un = _lib.c_i64(), _lib.c_i64(), _lib.c_i64(), _lib.c_i64()
-        _lib.check(self._lib.bb_paths_info(self._h, ns, nn, sw, un), "bb_paths_info")
+        self._call("info", ns, nn, sw, un)
         self.n_sources, self.n_nodes = int(ns.value), int(nn.value)
         self.sweeps_, self.unreachable_ = int(sw.value), int(un.value)
-
-    def _open(self):
-        if not self._h:
-            raise ValueError("these geodesic rows are closed")
-        return self._h
 
     def to_host(self):
         """(n_sources, n_nodes): 0 where no path exists and on a source's own node."""
         out = numpy.empty((self.n_sources, self.n_nodes), dtype=numpy.float64)
-        _lib.check(self._lib.bb_paths_read(self._open(), _lib.as_f64_ptr(out)), "bb_paths_read")
+        self._call("read", _lib.as_f64_ptr(out))
         return out
 
     def columns(self, nodes):
         """(n_sources, len(nodes)): the distances to the listed nodes alone."""
         idx = numpy.ascontiguousarray(nodes, dtype=numpy.int64).ravel()
         out = numpy.empty((self.n_sources, idx.shape[0]), dtype=numpy.float64)
-        _lib.check(self._lib.bb_paths_read_columns(self._open(), idx.ctypes.data_as(_lib.p_i64),
-                                                   idx.shape[0], _lib.as_f64_ptr(out)),
-                   "bb_paths_read_columns")
+        self._call("read_columns", idx.ctypes.data_as(_lib.p_i64), idx.shape[0], _lib.as_f64_ptr(out))
         return out
 
     def reached(self):
         """int64 (n_sources,): the nodes every source has a path to, its own included."""
         out = numpy.zeros(self.n_sources, dtype=numpy.int64)
-        _lib.check(self._lib.bb_paths_reached(self._open(), out.ctypes.data_as(_lib.p_i64)),
-                   "bb_paths_reached")
+        self._call("reached", out.ctypes.data_as(_lib.p_i64))
         return out
 
     def place(self, coef, mu, out=None):
@@ -227,7 +167,6 @@ class GeodesicRows(object):
         -1/2 sum_a coef[a] (D[j][a]^2 - mu[a]) for every node with a path from every source that
         takes part (a source whose coef row and mu are 0 does not); the other rows keep what
         `out` -- (n_nodes, 3) float64, C-ordered; None: zeros -- held.  placed: bool."""
-        import ctypes
         coef = numpy.ascontiguousarray(coef, dtype=numpy.float64)
         mu = numpy.ascontiguousarray(mu, dtype=numpy.float64)
         if coef.shape != (self.n_sources, 3) or mu.shape != (self.n_sources,):
@@ -238,34 +177,15 @@ class GeodesicRows(object):
                 or out.shape != (self.n_nodes, 3) or not out.flags.c_contiguous):
             raise ValueError("out must be a C-ordered float64 array of shape (n_nodes, 3)")
         placed = numpy.zeros(self.n_nodes, dtype=numpy.uint8)
-        _lib.check(self._lib.bb_paths_place(self._open(), _lib.as_f64_ptr(coef), _lib.as_f64_ptr(mu),
-                                            _lib.as_f64_ptr(out),
-                                            placed.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
-                   "bb_paths_place")
+        self._call("place", _lib.as_f64_ptr(coef), _lib.as_f64_ptr(mu), _lib.as_f64_ptr(out),
+                   placed.ctypes.data_as(_lib.p_u8))
         return out, placed.astype(bool)
 
     def timing(self):
         """(weights_ms, sweeps_ms) of the call that made these rows, by HIP events."""
         w, s = _lib.c_dbl(), _lib.c_dbl()
-        _lib.check(self._lib.bb_paths_timing(self._open(), w, s), "bb_paths_timing")
+        self._call("timing", w, s)
         return float(w.value), float(s.value)
-
-    def close(self):
-        if self._h:
-            self._lib.bb_paths_destroy(self._h)
-            self._h = _lib.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def landmark_choice(live, n_landmarks):
@@ -348,17 +268,10 @@ def landmark_start(triples, resolution, n_bins, n_landmarks=64, kind="counts", a
     keep_rows=True (with return_info) leaves the geodesic rows open as `info.rows_` -- what
     `HipEngine.set_anchors` copies for a fit with landmark constraints (SPEC 2.5.5).
     `triples` may be a `DeviceTriples` (its own resolution and device are used; it stays open)."""
-    from .datatypes import _pick_device
     n_landmarks = _check_n_landmarks(n_landmarks)
-    n = int(n_bins) + 1
-    if n < 1:
-        raise ValueError("n_bins must not be negative")
-    own = not isinstance(triples, DeviceTriples)
-    if own and int(resolution) <= 0:
-        raise ValueError("resolution must be positive")
-    dev = DeviceTriples(_check_triples(triples), resolution, _pick_device(device)) if own else triples
+    n = _bin_count(n_bins) + 1
     graph = dict(kind=kind, alpha=alpha, KRnorm=KRnorm, KRexpected=KRexpected)
-    try:
+    with _resident_triples(triples, resolution, [_pick_device(device)]) as dev:
         live = numpy.flatnonzero(dev.edge_degrees(n, **graph) > 0)
         landmarks = landmark_choice(live, n_landmarks)
         few = "the map is too disconnected for a landmark start: %s (need 4)"
@@ -384,18 +297,44 @@ def landmark_start(triples, resolution, n_bins, n_landmarks=64, kind="counts", a
         finally:
             if rows is not None:
                 rows.close()
-    finally:
-        if own:
-            dev.close()
     return (start, info) if return_info else start
 
 
 def _check_triples(triples):
     """The float64 (n, 3) view of `triples`, or ValueError."""
-    t = numpy.asarray(triples, dtype=numpy.float64)
-    if t.ndim != 2 or t.shape[1] != 3:
-        raise ValueError("triples must have shape (n, 3)")
-    return t
+    return triples_buffer(triples)[0]
+
+
+def _bin_count(n_bins):
+    n = int(n_bins)
+    if n < 0:
+        raise ValueError("n_bins must not be negative")
+    return n
+
+
+@contextlib.contextmanager
+def _resident_triples(triples, resolution, devices):
+    """The `DeviceTriples` a call works on.  A caller's own is yielded as it is and stays open;
+    anything else is uploaded -- once per distinct device of `devices`, the copy on devices[0]
+    being the one yielded and, where there are several entries, naming them all as its
+    `per_device` (what `GroupEngine.set_wish_triples` reads) -- and closed on exit."""
+    if isinstance(triples, DeviceTriples):
+        yield triples
+        return
+    if int(resolution) <= 0:
+        raise ValueError("resolution must be positive")
+    per_device = {}
+    try:
+        for d in devices:
+            if d not in per_device:
+                per_device[d] = DeviceTriples(triples, resolution, d)
+        dev = per_device[devices[0]]
+        if len(devices) > 1:
+            dev.per_device = per_device
+        yield dev
+    finally:
+        for t in per_device.values():
+            t.close()
 
 
 _BALANCE_KEYS = ("ignore_diags", "min_nnz", "tol", "max_iter", "row_sum")
@@ -404,7 +343,6 @@ _BALANCE_KEYS = ("ignore_diags", "min_nnz", "tol", "max_iter", "row_sum")
 def _balance_options(balance):
     """`fit_triples(balance=...)` as (checked keyword arguments of `DeviceTriples.balance`, whether
     the expected is wanted), without touching the library."""
-    from .datatypes import check_balance_args
     if balance is True:
         balance = {}
     if not isinstance(balance, dict):
@@ -438,31 +376,21 @@ def balance_triples(triples, resolution, n_bins, ignore_diags=0, min_nnz=0, tol=
     `ContactMap.from_triples(triples, resolution, n_bins)` followed by `balance(...)` and
     `expected()` defines.  Returns a `TriplesBalance`.  `triples` may be a `DeviceTriples`
     (its own resolution and device are used; it stays open)."""
-    from .datatypes import _pick_device, check_balance_args
     args = dict(zip(_BALANCE_KEYS, check_balance_args(ignore_diags, min_nnz, tol, max_iter, row_sum)))
-    n = int(n_bins)
-    if n < 0:
-        raise ValueError("n_bins must not be negative")
-    own = not isinstance(triples, DeviceTriples)
-    if own and int(resolution) <= 0:
-        raise ValueError("resolution must be positive")
-    dev = DeviceTriples(_check_triples(triples), resolution, _pick_device(device)) if own else triples
-    try:
+    n = _bin_count(n_bins)
+    with _resident_triples(triples, resolution, [_pick_device(device)]) as dev:
         bias = dev.balance(n, **args)
         return TriplesBalance(dev, bias, dev.expected(n, bias) if expected else None)
-    finally:
-        if own:
-            dev.close()
 
 
-class HipEngine(object):
+class HipEngine(_lib.Handle):
     """One rank's device state: thin, 1:1 over the bb_solver_* C-ABI."""
 
+    prefix = "bb_solver_"
     n_maps = 1                      # several once set_maps() has laid them end to end
 
     def __init__(self, n_bins, dtype, rank=0, world=1, device=0, tiles=None):
-        self._lib = _lib.load()
-        self._h = _lib.c_void_p()
+        _lib.Handle.__init__(self)
         self.n_bins, self.dtype, self.rank, self.world, self.device = (
             int(n_bins), dtype, int(rank), int(world), int(device))
         if tiles is None:
@@ -474,9 +402,9 @@ class HipEngine(object):
             if ti.shape != tj.shape or ti.ndim != 1:
                 raise ValueError("tiles must be a pair of equal-length 1-D index arrays")
             nt = ti.shape[0]
-        self._call("create", self.n_bins, _DTYPES[dtype], self.device, self.rank, self.world,
-                   None if ti is None else ti.ctypes.data_as(_lib.p_i32),
-                   None if tj is None else tj.ctypes.data_as(_lib.p_i32), nt)
+        self._create(self.n_bins, _DTYPES[dtype], self.device, self.rank, self.world,
+                     None if ti is None else ti.ctypes.data_as(_lib.p_i32),
+                     None if tj is None else tj.ctypes.data_as(_lib.p_i32), nt)
         self._exch = None
         self._comm_state = None     # "peer" | "rccl" | "torch" | "host" once chosen
         self._peer = None           # outcome of peer_setup()
@@ -484,30 +412,10 @@ class HipEngine(object):
         self._comm_trial = None     # timings of select_exchange's trial, if one ran
         self._comm_trial_error = None   # what made a leg of that trial fail on this rank
 
-    def _call(self, name, *args):
-        """bb_solver_<name>(handle, *args); any status but BB_OK raises (`_lib.check`)."""
-        name = "bb_solver_" + name
-        _lib.check(getattr(self._lib, name)(self._h, *args), name)
-
-    def _get(self, ctype, name, *args):
-        """The one scalar bb_solver_<name>(handle, *args, &out) writes: ctype is c_int, c_dbl
-        or c_i64."""
-        out = ctype()
-        self._call(name, *args, out)
-        return out.value
-
     # -- lifetime ---------------------------------------------------------
     def close(self):
-        if self._h:
-            self._lib.bb_solver_destroy(self._h)
-            self._h = _lib.c_void_p()
-            self._exch = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        _lib.Handle.close(self)
+        self._exch = None
 
     # -- layout -----------------------------------------------------------
     def layout(self):
@@ -526,7 +434,7 @@ class HipEngine(object):
 
     def set_wish_from_cm(self, dev_matrix, kind, alpha):
         """Device to device from a resident ContactMap matrix (datatypes._DeviceMatrix)."""
-        self._call("set_wish_from_cm", dev_matrix._h, _KINDS[kind], float(alpha))
+        self._call("set_wish_from_cm", dev_matrix._open(), _KINDS[kind], float(alpha))
 
     def set_wish_resident(self, cm, kind, alpha):
         """A resident ContactMap: device to device when it lives on this engine's GPU."""
@@ -552,7 +460,7 @@ class HipEngine(object):
         """From triples resident on the device (`DeviceTriples`): binned, KR / O-E
         normalised and converted there."""
         kr, ke = _kr_pair(KRnorm, KRexpected, self.n_bins)
-        self._call("set_wish_triples", dev_triples._h, _KINDS[kind], float(alpha), kr, ke)
+        self._call("set_wish_triples", dev_triples._open(), _KINDS[kind], float(alpha), kr, ke)
 
     # -- several maps in one solver (bb_solver_set_maps) -----------------------
     def set_maps(self, bin_begin, lr_scale):
@@ -571,7 +479,7 @@ class HipEngine(object):
                    int(bin_offset), _KINDS[kind], float(alpha))
 
     def set_wish_from_cm_block(self, dev_matrix, bin_offset, kind, alpha):
-        self._call("set_wish_from_cm_block", dev_matrix._h, int(bin_offset), _KINDS[kind],
+        self._call("set_wish_from_cm_block", dev_matrix._open(), int(bin_offset), _KINDS[kind],
                    float(alpha))
 
     def _set_steps(self, name, scale, per):
@@ -618,14 +526,13 @@ class HipEngine(object):
         """Landmark constraints inside the fit (SPEC 2.5.5, `bb_solver_set_anchors`): the engine
         makes its own copy of the rows of `rows` (a `GeodesicRows`) with kept[a] true (None:
         all), which may be closed afterwards.  rows None or weight 0 clears them."""
-        import ctypes
         k = None
         if rows is not None and kept is not None:
             k = numpy.ascontiguousarray(kept, dtype=numpy.uint8)
             if k.shape != (rows.n_sources,):
                 raise ValueError("kept must have one entry per source")
         self._call("set_anchors", None if rows is None else rows._open(),
-                   None if k is None else k.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), float(weight))
+                   None if k is None else k.ctypes.data_as(_lib.p_u8), float(weight))
         self.anchored = self.anchor_info()[0] > 0
 
     def anchor_sums(self):
@@ -716,8 +623,7 @@ class HipEngine(object):
         v0 = _check_coords(v0, self.n_bins)
         done, res = _lib.c_int(), _lib.c_dbl()
         # explicit: a lost rank is an outcome of its own (the caller takes the host-driven start)
-        rc = self._lib.bb_solver_spectral_init_tol(self._h, int(n_iter), float(tol),
-                                                   _lib.as_f64_ptr(v0), done, res)
+        rc = self._status("spectral_init_tol", int(n_iter), float(tol), _lib.as_f64_ptr(v0), done, res)
         if rc == _lib.BB_ERR_STATE and "lost rank" in _lib.last_error():
             raise RankDeficient(_lib.last_error())
         _lib.check(rc, "bb_solver_spectral_init_tol")
@@ -767,7 +673,7 @@ class HipEngine(object):
         if box[0] is None:
             return False
         # explicit: a failure here is this rank's vote, not an error
-        ok = self._lib.bb_solver_comm_init(self._h, box[0]) == _lib.BB_OK
+        ok = self._status("comm_init", box[0]) == _lib.BB_OK
         # all ranks must take the same path: agree on the outcome
         import torch
         flag = torch.tensor([1 if ok else 0], dtype=torch.int32,
@@ -794,10 +700,10 @@ class HipEngine(object):
 
     def _comm_attach(self):
         # explicit: the outcome is agreed between the ranks (`comm_reuse`), not raised
-        return self._lib.bb_solver_comm_attach(self._h) == _lib.BB_OK
+        return self._status("comm_attach") == _lib.BB_OK
 
     def _comm_detach(self):
-        self._lib.bb_solver_comm_detach(self._h)
+        self._status("comm_detach")
 
     def iterate_dist(self, iters, lr):
         """`iters` x { grad, RCCL all-reduce, apply }, all enqueued by one C call."""
@@ -815,12 +721,12 @@ class HipEngine(object):
             return self._peer
         buf = ctypes.create_string_buffer(_lib.BB_PEER_HANDLE_BYTES)
         # explicit, here and at the connect: a failure is this rank's vote, not an error
-        mine = buf.raw if self._lib.bb_solver_peer_export(self._h, buf) == _lib.BB_OK else None
+        mine = buf.raw if self._status("peer_export", buf) == _lib.BB_OK else None
         handles = [None] * self.world
         dist.all_gather_object(handles, mine)
         ok = all(h is not None for h in handles)
         if ok:
-            ok = self._lib.bb_solver_peer_connect(self._h, b"".join(handles)) == _lib.BB_OK
+            ok = self._status("peer_connect", b"".join(handles)) == _lib.BB_OK
         if not ok:
             self._peer_error = _lib.last_error()
         oks = [None] * self.world
@@ -856,7 +762,7 @@ class HipEngine(object):
         """Ranks RCCL reports for the library's communicator, or None without one."""
         n = _lib.c_int()
         # explicit: no communicator is an answer (None), not an error
-        if self._lib.bb_solver_comm_world(self._h, n) != _lib.BB_OK:
+        if self._status("comm_world", n) != _lib.BB_OK:
             return None
         return int(n.value)
 
@@ -940,7 +846,7 @@ class HipEngine(object):
                         (int(x.value) for x in v)))
 
 
-class GroupEngine(object):
+class GroupEngine(_lib.Handle):
     """Several GPUs from ONE process (`bb_group_*`): member r is a HipEngine playing rank r of
     world R on devices[r] (a device may repeat: members then share it), each holding only its
     own units; one host thread per member enqueues its iterations, and the partials are summed
@@ -948,39 +854,31 @@ class GroupEngine(object):
     like one engine of world 1: every setter goes to all members, degrees, weight sums, matvecs
     and scores come back summed over the members in rank order (float64 / int64), coordinates and
     stress history are member 0's -- all members hold the same bits."""
+    prefix = "bb_group_"
 
     def __init__(self, n_bins, dtype, devices, tiles=None):
-        self._lib = _lib.load()
+        _lib.Handle.__init__(self)
         self.n_bins, self.dtype = int(n_bins), dtype
         self.devices = [int(d) for d in devices]
         self.device = self.devices[0]
         self.world = 1                     # what the caller sees: one engine, summed results
         self._comm_state = "group"
-        self._g = _lib.c_void_p()
         self.members = []
         try:
             R = len(self.devices)
             for r, d in enumerate(self.devices):
                 self.members.append(HipEngine(n_bins, dtype, rank=r, world=R, device=d, tiles=tiles))
             handles = (_lib.c_void_p * R)(*[m._h.value for m in self.members])
-            _lib.check(self._lib.bb_group_create(self._g, handles, R), "bb_group_create")
+            self._create(handles, R)
         except BaseException:
             self.close()
             raise
 
     def close(self):
-        if self._g:
-            self._lib.bb_group_destroy(self._g)
-            self._g = _lib.c_void_p()
-        for m in self.members:
+        _lib.Handle.close(self)                # the group before its members
+        for m in getattr(self, "members", ()):
             m.close()
         self.members = []
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _each(self, name, *args):
         """Every member's `name`(*args), in rank order."""
@@ -1024,7 +922,7 @@ class GroupEngine(object):
                 e.set_wish_resident(cm, kind, alpha)
                 continue
             # explicit: "without peer access" sends this member through the host, not an error
-            rc = self._lib.bb_solver_set_wish_from_cm(e._h, dev._h, _KINDS[kind], float(alpha))
+            rc = e._status("set_wish_from_cm", dev._open(), _KINDS[kind], float(alpha))
             if rc == _lib.BB_OK:
                 continue
             if not (rc == _lib.BB_ERR_INVALID and "without peer access" in _lib.last_error()):
@@ -1074,7 +972,7 @@ class GroupEngine(object):
         self._each("set_momentum", mu)
 
     def iterate(self, iters, lr):
-        _lib.check(self._lib.bb_group_iterate(self._g, int(iters), float(lr)), "bb_group_iterate")
+        self._call("iterate", int(iters), float(lr))
 
     def get_coords(self):
         return self.members[0].get_coords()
@@ -1886,11 +1784,8 @@ class StructureSolver(object):
         vals = numpy.asarray(coo.data, dtype=numpy.float64)
         triples = numpy.stack([coo.row.astype(numpy.float64), coo.col.astype(numpy.float64),
                                numpy.where(numpy.isfinite(vals), vals, 0.0)], axis=1)
-        dev = DeviceTriples(triples, 1, self._completion_device())
-        try:
+        with _resident_triples(triples, 1, [self._completion_device()]) as dev:
             return self._landmark_init(dev, n - 1, None, None)
-        finally:
-            dev.close()
 
     def _completion_device(self):
         """Where a fit's completion runs: devices[0] of a group, else this rank's device."""
@@ -1923,6 +1818,18 @@ class StructureSolver(object):
 
     def _default_start(self, n):
         return numpy.random.default_rng(self.seed).standard_normal((n, 3))
+
+    def _one_step(self, n):
+        """The one step for all bins of a map of n bins: lr='auto' is SPEC 2.4's 1 / (2 n)."""
+        return 1.0 / (2.0 * n) if self.lr == "auto" else float(self.lr)
+
+    def _fitted(self, structure, who):
+        """`structure`, or `structure_` of the last fit where none is given (ValueError before one)."""
+        if structure is None:
+            structure = getattr(self, "structure_", None)
+            if structure is None:
+                raise ValueError("%s: no structure given and none fitted yet (structure_)" % who)
+        return structure
 
     def _bin_sums(self, eng, world):
         """What the per-bin steps of SPEC 2.4.1 are made from, summed over the ranks: the
@@ -1982,7 +1889,7 @@ class StructureSolver(object):
     def _fit_impl(self, matrix, n, init, KRnorm, KRexpected, kind=None):
         kind = self.kind if kind is None else kind      # 'wish' for a completed map
         eng, world, devices, pack = self._engine_for(matrix, n)
-        lr = 1.0 / (2.0 * n) if self.lr == "auto" else float(self.lr)
+        lr = self._one_step(n)
         if init is None and self.init == "random":
             init = self._default_start(n)
         auto = self.alpha_auto
@@ -2106,7 +2013,7 @@ class StructureSolver(object):
         iterates; returns the lr of that last fit.  Every rank takes the same decisions: the
         sums are the same on all of them."""
         def steps():
-            lr = 1.0 / (2.0 * n) if self.lr == "auto" else float(self.lr)
+            lr = self._one_step(n)
             sums = self._bin_sums(eng, world)
             if sums is not None:
                 lr, scale = self._steps(sums, n)
@@ -2155,11 +2062,7 @@ class StructureSolver(object):
         `ContactMap.shortest_paths(...)` to a kind='wish' solver.  Comparable across
         weight_power: `FitScore.stress` holds all three S_q."""
         source, n = self._map_source(X)
-        if structure is None:
-            structure = getattr(self, "structure_", None)
-            if structure is None:
-                raise ValueError("score: no structure given and none fitted yet (structure_)")
-        xyz = _check_coords(structure, n)
+        xyz = _check_coords(self._fitted(structure, "score"), n)
         eng, world, _, pack = self._engine_for(source, n)
         with _teardown(eng):
             pack(self.kind, None, None)
@@ -2173,11 +2076,7 @@ class StructureSolver(object):
         `StructureComparison`, `compare_structures(A, B, **kw)` with A = `structure_` of the last
         fit unless given -- B is laid onto A."""
         from .compare import compare_structures
-        if A is None:
-            A = getattr(self, "structure_", None)
-            if A is None:
-                raise ValueError("compare: no structure given and none fitted yet (structure_)")
-        return compare_structures(A, B, **kw)
+        return compare_structures(self._fitted(A, "compare"), B, **kw)
 
     def _group_devices(self):
         """The devices of a devices= / n_gpus= fit (one entry included), checked against this
@@ -2267,16 +2166,12 @@ class StructureSolver(object):
             # nan_to_num (pyx:102), the binning and the tile occupancy on the device: the host
             # never makes a pass over the triples (round 3: two isfinite passes, two divide +
             # astype passes and a scipy COO over 240 MB at chr1@10kb)
-            group = self._group_devices()
-            if group and len(group) > 1:
-                # uploaded once per distinct device; every member packs from its own device's copy
-                per_device = {}
+            devices = self._group_devices()
+            if not (devices and len(devices) > 1):
+                devices = [self._pick_device(_dist_state(self.distributed)[1])]
+            # (several devices: every member packs from its own device's copy)
+            with _resident_triples(triples, resolution, devices) as dev:
                 try:
-                    for d in group:
-                        if d not in per_device:
-                            per_device[d] = DeviceTriples(triples, resolution, d)
-                    dev = per_device[group[0]]
-                    dev.per_device = per_device
                     if balance is not None:
                         KRnorm, KRexpected = self._balance_on(dev, int(n_bins), bal_args, bal_expected)
                     if landmark:
@@ -2284,27 +2179,9 @@ class StructureSolver(object):
                         init = start if init is None else init
                     return self._fit_impl(dev, n, init, KRnorm, KRexpected)
                 finally:
-                    for t in per_device.values():
-                        t.close()
-            _, world = _dist_state(self.distributed)
-            own = not isinstance(triples, DeviceTriples)
-            dev = DeviceTriples(triples, resolution, self._pick_device(world)) if own else triples
-            try:
-                if balance is not None:
-                    KRnorm, KRexpected = self._balance_on(dev, int(n_bins), bal_args, bal_expected)
-                if landmark:
-                    start = self._landmark_init(dev, int(n_bins), KRnorm, KRexpected)
-                    init = start if init is None else init
-                return self._fit_impl(dev, n, init, KRnorm, KRexpected)
-            finally:
-                self._drop_anchor()
-                if own:
-                    dev.close()
+                    self._drop_anchor()
         # engines without a device (tests): bin on the host, as round 3 did
-        from .datatypes import _nan_to_num
-        t = _nan_to_num(triples)          # pyx:102 (no copy when every value is finite)
-        if t.ndim != 2 or t.shape[1] != 3:
-            raise ValueError("triples must have shape (n, 3)")
+        t = _nan_to_num(_check_triples(triples))     # pyx:102 (no copy when every value is finite)
         rows = (t[:, 0] / resolution).astype(numpy.int64)
         cols = (t[:, 1] / resolution).astype(numpy.int64)
         import scipy.sparse
@@ -2421,7 +2298,7 @@ class StructureSolver(object):
         ti, tj = numpy.concatenate(ti), numpy.concatenate(tj)
         order = numpy.lexsort((ti, tj))
         tiles = (ti[order].astype(numpy.int32), tj[order].astype(numpy.int32))
-        lrs = [1.0 / (2.0 * n) if self.lr == "auto" else float(self.lr) for n in sizes]
+        lrs = [self._one_step(n) for n in sizes]
         device = self._pick_device(1)
         x0 = numpy.zeros((total, 3))
         for m, (o, n) in enumerate(zip(off, sizes)):

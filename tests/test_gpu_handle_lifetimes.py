@@ -276,3 +276,82 @@ def test_triples_tiles_close_twice_and_empty(dtype, n):
     empty = DeviceTriples(numpy.zeros((0, 3)), res, 0)
     assert empty.n == 0
     empty.close()
+
+
+# ---- 9. every owner of a library handle: closed twice, refused afterwards, closed by `with` ------
+# The smallest size each exists at: N = 300 fp64 (the narrow layout), a band of seven diagonals
+# of whole counts over 300 bins (2,079 triples), 4 sources, d = 301.  A closed handle raises
+# ValueError in Python (`_lib.Handle`): the library never sees it.
+_RES, _BINS = 5000, 300
+
+
+def _band_triples():
+    i = numpy.repeat(numpy.arange(_BINS), 7)
+    j = i + numpy.tile(numpy.arange(7), _BINS)
+    keep = j < _BINS
+    i, j = i[keep], j[keep]
+    return numpy.stack([i * float(_RES), j * float(_RES), 1.0 + (i * 7 + j) % 9], axis=1)
+
+
+def _make_engine():
+    return _engine("float64", _BINS), lambda e: e.layout()["n_bins"] == _BINS
+
+
+def _make_group():
+    from blueberry_amd.solver import GroupEngine
+    xs, x0, lr = _problem(_BINS)
+    g = GroupEngine(_BINS, "float64", [0, 0])
+    g.set_wish_from_coords(xs)
+    g.set_coords(x0)
+
+    def call(g):
+        g.iterate(1, lr)
+        g.sync()
+        return True
+    return g, call
+
+
+def _make_triples():
+    t = _band_triples()
+    return DeviceTriples(t, _RES, 0), lambda d: d.pairs(_BINS) == t.shape[0]
+
+
+def _make_rows():
+    t = DeviceTriples(_band_triples(), _RES, 0)
+    rows = t.shortest_paths(_BINS, [0, 100, 200, 299])
+    t.close()                                      # (the rows own their memory)
+    return rows, lambda r: r.reached().tolist() == [_BINS] * 4
+
+
+def _make_matrix():
+    import blueberry_amd as bb
+    cm = bb.ContactMap.from_triples(_band_triples(), _RES, _BINS)
+    return cm._resident(), lambda m: m.d == _BINS + 1
+
+
+def _make_results():
+    import blueberry_amd as bb
+    from blueberry_amd import fithic
+    cm = bb.ContactMap.from_triples(_band_triples(), _RES, _BINS)
+    n_reads = 1e4
+    prior = 8.0 / (numpy.arange(_BINS) + 1.0) / n_reads
+    res = fithic.significance_list(cm, _BINS, 1, 6, numpy.ones(_BINS), None, prior, n_reads)
+    res.map_ = cm                                  # (the map lives as long as its list)
+    return res, lambda r: 0 < r.size()[0] <= _band_triples().shape[0] - _BINS
+
+
+@pytest.mark.parametrize("make", [_make_engine, _make_group, _make_triples, _make_rows, _make_matrix,
+                                  _make_results], ids=lambda f: f.__name__[6:])
+def test_every_handle_owner_closes_twice_refuses_then_and_closes_on_exit(make):
+    h, call = make()
+    members = list(getattr(h, "members", ()))
+    assert isinstance(h, _lib.Handle) and h._h
+    assert call(h)
+    h.close()
+    h.close()
+    assert not h._h and not any(m._h for m in members)
+    with pytest.raises(ValueError, match="closed"):
+        call(h)
+    with make()[0] as again:
+        assert again._h
+    assert not again._h

@@ -416,10 +416,10 @@ def test_a_refused_call_leaves_no_handle_and_the_next_one_works():
     ones = numpy.ones(n)
     heavy = numpy.full(n, 0.5)                                     # N pi = 5e6: above the limit
     for X in (cm, dev):
-        handle, prefix, _ = fh._device_handle(X)
+        owner = X._balance_target()                                # the map's own handle
         out = _lib.c_void_p(12345)
-        rc = getattr(lib, prefix + "_significance")(
-            handle, n, 1, n - 1, _lib.as_f64_ptr(ones), 0.5, 2.0, _lib.as_f64_ptr(heavy), 1e7,
+        rc = getattr(lib, owner.prefix + "significance")(
+            owner._h, n, 1, n - 1, _lib.as_f64_ptr(ones), 0.5, 2.0, _lib.as_f64_ptr(heavy), 1e7,
             ctypes.byref(out))
         assert rc == _lib.BB_ERR_INVALID and "1048576" in _lib.last_error()
         assert out.value is None                                   # no handle came back

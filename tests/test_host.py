@@ -713,3 +713,125 @@ def test_genome_boundaries_and_block_tile_list():
     assert degree_step_factors(numpy.full(7, 6)) == (1.0 / 14, None)      # a complete map of 7 bins
     with pytest.raises(ValueError):
         tiles_from_blocks(n, [0, 10, 5, n], band, "float32")
+
+
+# ---- the owner of a library handle (_lib.Handle) against a stub library ------------------------
+class _StubLib(object):
+    """A library whose every function records its call and returns the status chosen for it;
+    `bb_stub_create` writes a handle, a trailing c_double receives 2.5."""
+
+    def __init__(self):
+        self.calls, self.status = [], {}
+
+    def bb_last_error(self):
+        return b"the stub refuses"
+
+    def __getattr__(self, name):
+        def fn(*args):
+            self.calls.append((name, args))
+            status = self.status.get(name, _lib.BB_OK)
+            if name == "bb_stub_create" and status == _lib.BB_OK:
+                args[0].value = 0xB10E
+            elif args and isinstance(args[-1], _lib.c_dbl):
+                args[-1].value = 2.5
+            return status
+        return fn
+
+    def count(self, name):
+        return sum(1 for called, _ in self.calls if called == name)
+
+
+class _StubHandle(_lib.Handle):
+    prefix = "bb_stub_"
+
+    def __init__(self, fail_first=False):
+        if fail_first:
+            raise RuntimeError("before the handle exists")
+        _lib.Handle.__init__(self)
+        self._create(7)
+
+
+@pytest.fixture
+def stub(monkeypatch):
+    lib = _StubLib()
+    monkeypatch.setattr(_lib, "load", lambda: lib)
+    return lib
+
+
+def test_handle_calls_prefix_name_with_the_handle_first(stub):
+    h = _StubHandle()
+    assert stub.calls == [("bb_stub_create", (h._h, 7))] and h._h.value == 0xB10E and h._lib is stub
+    h._call("frob", 1, "two")
+    assert stub.calls[-1] == ("bb_stub_frob", (h._h, 1, "two"))
+    assert h._get(_lib.c_dbl, "measure", 3) == 2.5
+    name, args = stub.calls[-1]
+    assert name == "bb_stub_measure" and args[:2] == (h._h, 3) and isinstance(args[2], _lib.c_dbl)
+    # a status that is an outcome comes back as it is
+    stub.status["bb_stub_vote"] = _lib.BB_ERR_STATE
+    assert h._status("vote") == _lib.BB_ERR_STATE and stub.calls[-1] == ("bb_stub_vote", (h._h,))
+
+
+@pytest.mark.parametrize("status,exc", [(_lib.BB_ERR_INVALID, ValueError), (_lib.BB_ERR_NOMEM, MemoryError),
+                                        (_lib.BB_ERR_HIP, RuntimeError), (_lib.BB_ERR_STATE, RuntimeError)])
+def test_handle_raises_what_check_maps_a_status_to(stub, status, exc):
+    h = _StubHandle()
+    stub.status["bb_stub_frob"] = status
+    with pytest.raises(exc, match="the stub refuses"):
+        h._call("frob")
+    with pytest.raises(exc, match="the stub refuses"):
+        h._get(_lib.c_i64, "frob")
+    stub.status["bb_stub_create"] = status
+    with pytest.raises(exc, match="the stub refuses"):
+        _StubHandle()
+
+
+def test_handle_is_destroyed_exactly_once(stub):
+    a = _StubHandle()
+    first = a._h.value
+    a.close()
+    a.close()
+    assert stub.count("bb_stub_destroy") == 1 and not a._h
+    assert [args[0].value for name, args in stub.calls if name == "bb_stub_destroy"] == [first]
+    del a
+    assert stub.count("bb_stub_destroy") == 1
+    with _StubHandle() as b:
+        assert b._h and b._get(_lib.c_dbl, "measure") == 2.5
+    assert stub.count("bb_stub_destroy") == 2 and not b._h
+    del b
+    assert stub.count("bb_stub_destroy") == 2
+    c = _StubHandle()
+    c.__del__()                                   # what the last reference going runs
+    assert stub.count("bb_stub_destroy") == 3 and not c._h
+    del c
+    assert stub.count("bb_stub_destroy") == 3
+
+
+def test_a_closed_handle_never_reaches_the_library(stub):
+    h = _StubHandle()
+    h.close()
+    before = list(stub.calls)
+    for call in (lambda: h._call("frob", 1), lambda: h._get(_lib.c_dbl, "measure"),
+                 lambda: h._status("vote"), h._open):
+        with pytest.raises(ValueError, match="closed"):
+            call()
+    assert stub.calls == before
+
+
+def test_del_of_a_half_made_handle_does_not_raise(stub):
+    with pytest.raises(RuntimeError, match="before the handle exists"):
+        _StubHandle(fail_first=True)
+    h = _StubHandle.__new__(_StubHandle)          # no _h, no _lib: the constructor never got there
+    h.__del__()
+    h.close()
+    stub.status["bb_stub_create"] = _lib.BB_ERR_HIP
+    with pytest.raises(RuntimeError):
+        _StubHandle()                             # create refused: the handle stays NULL
+    assert stub.count("bb_stub_destroy") == 0
+    # a destroy that raises is swallowed by __del__, not by close()
+    stub.status.clear()
+    g = _StubHandle()
+    g._lib = None
+    g.__del__()
+    with pytest.raises(AttributeError):
+        g.close()
+    g._h = _lib.c_void_p()
