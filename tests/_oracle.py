@@ -298,6 +298,12 @@ def golden(name):
     return numpy.load(os.path.join(GOLDEN_DIR, name + ".npz"), allow_pickle=False)
 
 
+def band_cases():
+    """The names of the band-count cases of the golden vectors."""
+    z = golden("band_count")
+    return sorted(k[3:] for k in z.files if k.startswith("in_"))
+
+
 # -- synthetic inputs of BASELINE.md section 3 ------------------------------
 def random_walk(n, seed=0):
     """Ground truth X*: 3-D Gaussian random walk, centred."""

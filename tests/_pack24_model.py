@@ -13,6 +13,14 @@ WISH_FLOOR, F32_MAX = 1e-30, 3.4028234663852886e38
 EPS2 = 1e-30                        # the floor under the square root of SPEC 2.2, fp32 runs
 
 
+def uniform_map(n, seed=0, lo=1.0, hi=1.9):
+    """Symmetric, zero diagonal, off-diagonal distances uniform in [lo, hi], exact in float32."""
+    rng = numpy.random.default_rng(seed)
+    w = rng.uniform(lo, hi, (n, n)).astype(numpy.float32).astype(numpy.float64)
+    w = numpy.triu(w, 1)
+    return w + w.T
+
+
 def dense_tiles(n):
     """Tile list (I, J) of the dense upper triangle in device order: J ascending, then I."""
     nb = -(-int(n) // VW)

@@ -17,6 +17,8 @@ import os
 import sys
 import threading
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAX_RANK_PROCESSES = 4     # with the test process (and a tool between the two): at most 6
                            # processes hold the GPU at once
@@ -119,6 +121,13 @@ class Rank(object):
 def close_all():
     while LIVE:
         LIVE[-1].close()
+
+
+@pytest.fixture(autouse=True)
+def no_rank_process_outlives_its_test():
+    """For the test modules that start ranks to import: autouse in a module that holds it."""
+    yield
+    close_all()
 
 
 def start(world, n, dtype, tiles=None):

@@ -10,6 +10,7 @@ import pytest
 import blueberry_amd as bb
 from blueberry_amd import solver as S
 from tests import _alpha_model as model
+from tests._jobs import run_ranks
 
 
 # ---- 1. the argument forms and the read-backs ---------------------------------------------------
@@ -253,57 +254,23 @@ def test_constant_counts_are_refused():
 
 
 # ---- 7. two gloo ranks: the sums are all-reduced, every rank takes the same alpha -----------------
-def _free_port():
-    import socket
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-def _auto_worker(rank, world, port, q):
-    import os
-    import sys
-    import traceback
-    try:
-        sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        import torch.distributed as dist
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        c, start, kw = case_inputs("sparse", 4.0)
-        s = bb.StructureSolver(n_iter=N_ITER, dtype="float64", alpha=AUTO, engine=model.AlphaOracleEngine, **kw)
-        s.fit(c, init=start)
-        part = model.AlphaOracleEngine(c.shape[0], "float64", rank=rank, world=world)
-        part.set_wish_dense(c, "counts", 3.0)
-        q.put((rank, s.alpha_, s.alpha_rounds_, s.structure_, part.loglog(start)[:, 0].sum()))
-        dist.barrier()
-        dist.destroy_process_group()
-    except Exception:
-        q.put((rank, traceback.format_exc(), None, None, None))
+def _auto_worker(rank, world):
+    c, start, kw = case_inputs("sparse", 4.0)
+    s = bb.StructureSolver(n_iter=N_ITER, dtype="float64", alpha=AUTO, engine=model.AlphaOracleEngine, **kw)
+    s.fit(c, init=start)
+    part = model.AlphaOracleEngine(c.shape[0], "float64", rank=rank, world=world)
+    part.set_wish_dense(c, "counts", 3.0)
+    return s.alpha_, s.alpha_rounds_, s.structure_, part.loglog(start)[:, 0].sum()
 
 
 def test_search_on_two_gloo_ranks():
-    import torch.multiprocessing as mp
-    world = 2
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_auto_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = sorted((q.get(timeout=240) for _ in procs), key=lambda r: r[0])
-    for p in procs:
-        p.join(timeout=60)
-    for r in results:
-        assert not isinstance(r[1], str), r[1]
+    results = run_ranks(_auto_worker, 2, timeout=240)
     m = model_run("sparse", 4.0)
     pairs = (numpy.triu(case_inputs("sparse", 4.0)[0], 1) > 0).sum()
-    assert results[0][1] == results[1][1]                               # the same alpha on every rank
-    assert numpy.array_equal(results[0][2], results[1][2]) and numpy.array_equal(results[0][3], results[1][3])
-    for rank, alpha, rounds, structure, own in results:
+    assert results[0][0] == results[1][0]                               # the same alpha on every rank
+    assert numpy.array_equal(results[0][1], results[1][1]) and numpy.array_equal(results[0][2], results[1][2])
+    for alpha, rounds, structure, own in results:
         assert abs(alpha / 4.0 - 1) <= 1e-2 and rounds.shape == m["rounds"].shape
         assert numpy.allclose(rounds, m["rounds"], rtol=1e-9, atol=1e-12)
         assert 0 < own < pairs                                          # every rank held a share only
-    assert sum(r[4] for r in results) == pairs
+    assert sum(r[3] for r in results) == pairs

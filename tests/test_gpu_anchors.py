@@ -23,15 +23,12 @@ from blueberry_amd.solver import HipEngine, layout_info
 from tests import _anchor_model as am
 from tests import _input_model as im
 from tests import _landmark_model as lm
+from tests._util import bits
 
 pytestmark = pytest.mark.gpu
 
 TOL = {"float64": 1e-12, "float32": 1e-5}              # SPEC 4
 VW = {d: layout_info(100, d)["vw"] for d in TOL}       # the block width of maps this small
-
-
-def bits(a):
-    return numpy.ascontiguousarray(a, dtype=numpy.float64).view(numpy.uint64)
 
 
 def wish_map(n, seed):

@@ -29,6 +29,7 @@ import blueberry_amd as bb
 from blueberry_amd.datatypes import expected_from_sums
 from tests import _balance_model as bm
 from tests import _large_maps as lm
+from tests._util import max_rel, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -40,24 +41,6 @@ SIZES = [2, 3, 64, 65, 66, 129, 4096, 4097, 4098, 4161, 4162, 8193]
 # Hi-C-like map under that band, 113 and 3,893 of the integer map at min_nnz = 5.
 BAND17_SIZES = [129, 4161]
 EPS = 2.0 ** -52
-
-
-def bits(a):
-    return numpy.ascontiguousarray(a, dtype=numpy.float64).view(numpy.uint64)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and numpy.array_equal(bits(a), bits(b))
-
-
-def max_rel(got, want):
-    """max |got - want| / |want| over the entries where `want` is a number; the NaN patterns
-    must be the same."""
-    nan = numpy.isnan(want)
-    assert numpy.array_equal(numpy.isnan(got), nan)
-    if nan.all():
-        return 0.0
-    return float(numpy.max(numpy.abs(got[~nan] - want[~nan]) / numpy.abs(want[~nan])))
 
 
 # ---- 1. exact: integer maps ----------------------------------------------------------------------

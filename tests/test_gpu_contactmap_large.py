@@ -34,14 +34,11 @@ import pytest
 import blueberry_amd as bb
 from blueberry_amd import _lib
 from tests import _large_maps as lm
+from tests._util import bits
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-13           # ContactMap.eigenvector's default
-
-
-def bits(a):
-    return numpy.ascontiguousarray(a, dtype=numpy.float64).view(numpy.uint64)
 
 
 def symv(dev, x):

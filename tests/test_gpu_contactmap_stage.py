@@ -26,30 +26,15 @@ tests/test_contactmap_stage_inputs_cpu.py.
 NOT covered: `gather_kernel`'s `r += gridDim.y` stride.  A band holds at most
 8 Mi / d_new elements' worth of rows and the grid has min(rows, 32,768) of them in y: the stride
 would be taken only by a band of more than 32,768 rows, which the bounce buffer never holds."""
-import ctypes
-
 import numpy
 import pytest
 
 import blueberry_amd as bb
-from blueberry_amd import _lib
 from blueberry_amd.solver import HipEngine
 from tests import _stage_maps as sm
+from tests._util import cu_count
 
 pytestmark = pytest.mark.gpu
-
-
-def cu_count():
-    """The device's CU count as `bb_cm_normalize` reads it: hipDeviceGetAttribute(
-    hipDeviceAttributeMultiprocessorCount = 63) of the HIP runtime the library is bound to."""
-    _lib.load()
-    runtimes = _lib.hip_runtimes_loaded()
-    own = [p for p in runtimes if "/torch/" not in p] or runtimes
-    hip = ctypes.CDLL(own[0])
-    hip.hipDeviceGetAttribute.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int]
-    value = ctypes.c_int(0)
-    assert hip.hipDeviceGetAttribute(ctypes.byref(value), 63, 0) == 0 and value.value > 0
-    return int(value.value)
 
 
 def assert_same_bits(got, want, what, slab=1024):

@@ -14,26 +14,12 @@ import sys
 import numpy
 import pytest
 
+from tests._ranks import no_rank_process_outlives_its_test         # noqa: F401 -- autouse
+from tests._util import host_threads as _host_threads
+from tests._util import rel as _rel
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(autouse=True)
-def _no_rank_process_outlives_its_test():
-    yield
-    from tests import _ranks
-    _ranks.close_all()
-
-
-def _rel(a, b):
-    return numpy.abs(a - b).max() / numpy.abs(b).max()
-
-
-def _host_threads():
-    try:
-        return max(1, min(16, len(os.sched_getaffinity(0))))
-    except AttributeError:
-        return max(1, min(16, os.cpu_count() or 1))
 
 
 def _incomplete_wish(n):

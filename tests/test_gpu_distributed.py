@@ -10,54 +10,30 @@
   run uses, rehearsed as far as one GPU allows.
 """
 import os
-import socket
 import subprocess
 import sys
-import traceback
 
 import numpy
 import pytest
+
+from tests._jobs import free_port, run_ranks
+from tests._ranks import no_rank_process_outlives_its_test         # noqa: F401 -- autouse
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-def _worker(rank, world, port, n, k, dtype, q, comm="host"):
-    try:
-        sys.path.insert(0, ROOT)
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        os.environ["BB_COMM"] = comm.split("-")[0]
-        os.environ["BB_PEER_TIMEOUT_MS"] = "5000"
-        if comm == "peer-one-launch":
-            # ranks that share a GPU get the two-launch exchange by default (waiting workgroups
-            # of one rank can keep another's sweep off the device); a small problem is safe
-            os.environ["BB_PEER_FUSED"] = "1"
-        comm = comm.split("-")[0]
-        import torch.distributed as dist
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        import blueberry_amd as bb
-        from tests import _oracle
-        xs = _oracle.random_walk(n)
-        w = _oracle.wish_from_coords(xs)
-        s = bb.StructureSolver(n_iter=k, dtype=dtype, kind="wish", device=0,
-                               momentum=0.3 if comm == "peer" else 0.0)
-        s.fit(w, init=_oracle.noisy_init(xs))
-        band = bb.count_band_regions(_oracle.golden("band_count")["in_gappy_n5000"],
-                                     distributed=True)
-        q.put((rank, s.structure_, s.stress_, band))
-        dist.barrier()
-        dist.destroy_process_group()
-    except Exception:
-        q.put((rank, traceback.format_exc(), None, None))
+def _worker(rank, world, n, k, dtype, comm):
+    import blueberry_amd as bb
+    from tests import _oracle
+    xs = _oracle.random_walk(n)
+    w = _oracle.wish_from_coords(xs)
+    s = bb.StructureSolver(n_iter=k, dtype=dtype, kind="wish", device=0,
+                           momentum=0.3 if comm == "peer" else 0.0)
+    s.fit(w, init=_oracle.noisy_init(xs))
+    band = bb.count_band_regions(_oracle.golden("band_count")["in_gappy_n5000"],
+                                 distributed=True)
+    return s.structure_, s.stress_, band
 
 
 @pytest.mark.parametrize("dtype,tol,world,comm,n", [
@@ -72,60 +48,30 @@ def _worker(rank, world, port, n, k, dtype, q, comm="host"):
     # number of ranks, heavy-ball momentum
     ("float64", 1e-12, 3, "peer", 7000)])
 def test_ranks_share_one_gpu(dtype, tol, world, comm, n):
-    import torch.multiprocessing as mp
     import blueberry_amd as bb
     from tests import _oracle
     k = 5
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, n, k, dtype, q, comm))
-             for r in range(world)]
-    for p in procs:
-        p.start()
-    results = sorted((q.get(timeout=300) for _ in procs), key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=60)
-    for r in results:
-        assert not isinstance(r[1], str), r[1]
+    env = {"BB_COMM": comm.split("-")[0], "BB_PEER_TIMEOUT_MS": "5000"}
+    if comm == "peer-one-launch":
+        # ranks that share a GPU get the two-launch exchange by default (waiting workgroups
+        # of one rank can keep another's sweep off the device); a small problem is safe
+        env["BB_PEER_FUSED"] = "1"
+    results = run_ranks(_worker, world, n, k, dtype, env["BB_COMM"], timeout=300, env=env)
     xs = _oracle.random_walk(n)
     w = _oracle.wish_from_coords(xs)
     one = bb.StructureSolver(n_iter=k, dtype=dtype, kind="wish", distributed=False,
                              momentum=0.3 if comm.startswith("peer") else 0.0)
     one.fit(w, init=_oracle.noisy_init(xs))
-    for rank, X, hist, band in results:
+    for X, hist, band in results:
         assert numpy.abs(X - one.structure_).max() < tol * numpy.abs(one.structure_).max()
         assert numpy.abs(hist / one.stress_ - 1).max() < tol
         assert band == int(_oracle.golden("band_count")["out_gappy_n5000"])
     for r in results[1:]:
+        assert numpy.array_equal(results[0][0], r[0])
         assert numpy.array_equal(results[0][1], r[1])
-        assert numpy.array_equal(results[0][2], r[2])
 
 
-def _worker_genome(rank, world, port, n, k, q):
-    try:
-        sys.path.insert(0, ROOT)
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        os.environ["BB_COMM"] = "peer"
-        os.environ["BB_PEER_TIMEOUT_MS"] = "20000"
-        import torch.distributed as dist
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        from blueberry_amd.solver import HipEngine, run_iterations
-        from tests import _oracle
-        xs = _oracle.random_walk(n)
-        eng = HipEngine(n, "float32", rank=rank, world=world, device=0)
-        eng.set_wish_from_coords(xs)           # this rank's share, generated on the device
-        eng.set_coords(_oracle.noisy_init(xs))
-        run_iterations(eng, k, 1.0 / (2 * n), world)
-        eng.sync()
-        eng.peer_status()
-        q.put((rank, eng.get_coords(), eng.stress_history(), eng._comm_state))
-        dist.barrier()
-        eng.close()
-        dist.destroy_process_group()
-    except Exception:
-        q.put((rank, traceback.format_exc(), None, None))
+PEER = {"BB_COMM": "peer", "BB_PEER_TIMEOUT_MS": "20000"}
 
 
 def _band_tiles(n, vw=512, width=2):
@@ -136,30 +82,27 @@ def _band_tiles(n, vw=512, width=2):
     return tiles_from_blocks(n, genome_boundaries(n), 1000, "float32")[0]
 
 
-def _worker_band(rank, world, port, n, k, lr, q):
-    try:
-        sys.path.insert(0, ROOT)
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        os.environ["BB_COMM"] = "peer"
-        os.environ["BB_PEER_TIMEOUT_MS"] = "20000"
-        import torch.distributed as dist
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        from blueberry_amd.solver import HipEngine, run_iterations
-        from tests import _oracle
-        xs = _oracle.random_walk(n)
-        eng = HipEngine(n, "float32", rank=rank, world=world, device=0, tiles=_band_tiles(n))
-        eng.set_wish_from_coords(xs)
-        eng.set_coords(_oracle.noisy_init(xs))
-        run_iterations(eng, k, lr, world)
-        eng.sync()
-        eng.peer_status()
-        q.put((rank, eng.get_coords(), eng.stress_history(), eng._comm_state))
-        dist.barrier()
-        eng.close()
-        dist.destroy_process_group()
-    except Exception:
-        q.put((rank, traceback.format_exc(), None, None))
+def _worker_engine(rank, world, n, k, lr, band):
+    """k iterations of one rank's own HipEngine over the peer exchange: the dense map, or
+    (`band`) config 5's tile list."""
+    import torch.distributed as dist
+    from blueberry_amd.solver import HipEngine, run_iterations
+    from tests import _oracle
+    xs = _oracle.random_walk(n)
+    eng = HipEngine(n, "float32", rank=rank, world=world, device=0,
+                    tiles=_band_tiles(n) if band else None)
+    eng.set_wish_from_coords(xs)           # this rank's share, generated on the device
+    eng.set_coords(_oracle.noisy_init(xs))
+    run_iterations(eng, k, lr, world)
+    eng.sync()
+    eng.peer_status()
+    out = eng.get_coords(), eng.stress_history(), eng._comm_state
+    # the one place a worker needs a barrier of its own (the launcher's comes after the worker
+    # has returned and does not replace it): a peer's kernel may still be reading this rank's
+    # arena, so every rank must have finished before any engine is closed
+    dist.barrier()
+    eng.close()
+    return out
 
 
 def test_config5_shape_four_ranks_over_the_peer_exchange():
@@ -168,24 +111,14 @@ def test_config5_shape_four_ranks_over_the_peer_exchange():
     four ways) on FOUR ranks -- four processes sharing the test box's GPU, partial gradients
     of 929 k coordinates summed through the peer exchange every iteration -- against the
     same iterations on one rank (1e-5), the ranks bit-identical among themselves."""
-    import torch.multiprocessing as mp
     from blueberry_amd.solver import HipEngine
     from tests import _oracle
     from blueberry_amd.solver import max_degree
     n, k, world = 309568, 4, 4
     lr = 1.0 / (2 * max_degree(n, _band_tiles(n), "float32"))
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker_band, args=(r, world, port, n, k, lr, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = sorted((q.get(timeout=400) for _ in procs), key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=60)
+    results = run_ranks(_worker_engine, world, n, k, lr, True, timeout=400, env=PEER)
     for r in results:
-        assert not isinstance(r[1], str), r[1]
-        assert r[3] == "peer"
+        assert r[2] == "peer"
     xs = _oracle.random_walk(n)
     one = HipEngine(n, "float32", tiles=_band_tiles(n))
     one.set_wish_from_coords(xs)
@@ -193,11 +126,11 @@ def test_config5_shape_four_ranks_over_the_peer_exchange():
     one.iterate(k, lr)
     X1, h1 = one.get_coords(), one.stress_history()
     one.close()
-    for rank, X, hist, _ in results:
+    for X, hist, _ in results:
         assert numpy.abs(X - X1).max() < 1e-5 * numpy.abs(X1).max()
         assert numpy.abs(hist / h1 - 1).max() < 1e-5
     for r in results[1:]:
-        assert numpy.array_equal(results[0][1], r[1]) and numpy.array_equal(results[0][2], r[2])
+        assert numpy.array_equal(results[0][0], r[0]) and numpy.array_equal(results[0][1], r[1])
     assert (numpy.diff(h1) < 0).all()
 
 
@@ -207,22 +140,12 @@ def test_config4_size_two_ranks_over_the_peer_exchange():
     partial gradients through the in-kernel peer exchange (IPC arenas; the two share the one
     GPU of the test box) -- against the same iterations on one rank, within the config's
     1e-5, and bit-identical between the ranks."""
-    import torch.multiprocessing as mp
     from blueberry_amd.solver import HipEngine
     from tests import _oracle
     n, k, world = 61914, 3, 2
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker_genome, args=(r, world, port, n, k, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = sorted((q.get(timeout=400) for _ in procs), key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=60)
+    results = run_ranks(_worker_engine, world, n, k, 1.0 / (2 * n), False, timeout=400, env=PEER)
     for r in results:
-        assert not isinstance(r[1], str), r[1]
-        assert r[3] == "peer"
+        assert r[2] == "peer"
     xs = _oracle.random_walk(n)
     one = HipEngine(n, "float32")
     one.set_wish_from_coords(xs)
@@ -230,19 +153,12 @@ def test_config4_size_two_ranks_over_the_peer_exchange():
     one.iterate(k, 1.0 / (2 * n))
     X1, h1 = one.get_coords(), one.stress_history()
     one.close()
-    for rank, X, hist, _ in results:
+    for X, hist, _ in results:
         assert numpy.abs(X - X1).max() < 1e-5 * numpy.abs(X1).max()
         assert numpy.abs(hist / h1 - 1).max() < 1e-5
+    assert numpy.array_equal(results[0][0], results[1][0])
     assert numpy.array_equal(results[0][1], results[1][1])
-    assert numpy.array_equal(results[0][2], results[1][2])
     assert h1[-1] < h1[0]
-
-
-@pytest.fixture(autouse=True)
-def _no_rank_process_outlives_its_test():
-    yield
-    from tests import _ranks
-    _ranks.close_all()
 
 
 def _set_wish(eng, wish):
@@ -462,7 +378,7 @@ print("NCCL_PATH_OK")
 
 
 def test_rccl_single_rank_device_path():
-    script = _NCCL_SCRIPT % {"root": ROOT, "port": _free_port()}
+    script = _NCCL_SCRIPT % {"root": ROOT, "port": free_port()}
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True,
                        timeout=600, env=env)
@@ -773,24 +689,12 @@ def _degree_map(n):
     return numpy.where(keep, w, 0.0), _oracle.noisy_init(xs)
 
 
-def _worker_degree_fit(rank, world, port, n, dtype, comm, q):
-    try:
-        sys.path.insert(0, ROOT)
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        os.environ["BB_COMM"] = comm
-        os.environ["BB_PEER_TIMEOUT_MS"] = "20000"
-        import torch.distributed as dist
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        import blueberry_amd as bb
-        w, x0 = _degree_map(n)
-        s = bb.StructureSolver(n_iter=6, dtype=dtype, kind="wish", device=0, degree_steps=True,
-                               momentum=0.3).fit(w, init=x0)
-        q.put((rank, s.structure_, s.stress_, s.exchange_, s.lr_))
-        dist.barrier()
-        dist.destroy_process_group()
-    except Exception:
-        q.put((rank, traceback.format_exc(), None, None, None))
+def _worker_degree_fit(rank, world, n, dtype, weight_power):
+    import blueberry_amd as bb
+    w, x0 = _degree_map(n)
+    s = bb.StructureSolver(n_iter=6, dtype=dtype, kind="wish", device=0, degree_steps=True,
+                           weight_power=weight_power, momentum=0.3).fit(w, init=x0)
+    return s.structure_, s.stress_, s.exchange_, s.lr_
 
 
 @pytest.mark.parametrize("dtype,tol,world,comm", [("float64", 1e-11, 2, "peer"),
@@ -801,53 +705,23 @@ def test_fit_with_degree_steps_across_processes(dtype, tol, world, comm):
     degrees of its own units on the device, the counts are summed over the ranks, the same
     per-bin factors go to every rank's solver, and the scaled gradients travel through the
     peer exchange (arenas over HIP IPC) or the host-staged sum.  Equal to one process."""
-    import torch.multiprocessing as mp
     import blueberry_amd as bb
     n = 2300
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker_degree_fit, args=(r, world, port, n, dtype, comm, q))
-             for r in range(world)]
-    for p in procs:
-        p.start()
-    results = sorted((q.get(timeout=300) for _ in procs), key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=60)
+    results = run_ranks(_worker_degree_fit, world, n, dtype, 0, timeout=300,
+                        env=dict(PEER, BB_COMM=comm))
     for r in results:
-        assert not isinstance(r[1], str), r[1]
-        assert r[3] == comm
+        assert r[2] == comm
     w, x0 = _degree_map(n)
     one = bb.StructureSolver(n_iter=6, dtype=dtype, kind="wish", degree_steps=True, momentum=0.3,
                              distributed=False).fit(w, init=x0)
     deg = (w > 0).sum(axis=0)
     assert one.lr_ == 1.0 / (2 * (deg.max() + 1)) and deg.max() > 4 * deg.min()
-    for rank, X, h, _, lr in results:
+    for X, h, _, lr in results:
         assert lr == one.lr_
         assert numpy.abs(h / one.stress_ - 1).max() < tol
         assert numpy.abs(X - one.structure_).max() < tol * numpy.abs(one.structure_).max()
     for r in results[1:]:
-        assert numpy.array_equal(r[1], results[0][1])
-
-
-def _worker_weighted_fit(rank, world, port, n, dtype, comm, q):
-    try:
-        sys.path.insert(0, ROOT)
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        os.environ["BB_COMM"] = comm
-        os.environ["BB_PEER_TIMEOUT_MS"] = "20000"
-        import torch.distributed as dist
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        import blueberry_amd as bb
-        w, x0 = _degree_map(n)
-        s = bb.StructureSolver(n_iter=6, dtype=dtype, kind="wish", device=0, degree_steps=True,
-                               weight_power=2, momentum=0.3).fit(w, init=x0)
-        q.put((rank, s.structure_, s.stress_, s.exchange_, s.lr_))
-        dist.barrier()
-        dist.destroy_process_group()
-    except Exception:
-        q.put((rank, traceback.format_exc(), None, None, None))
+        assert numpy.array_equal(r[0], results[0][0])
 
 
 @pytest.mark.parametrize("dtype,tol,world,comm", [("float64", 1e-11, 2, "peer"),
@@ -859,65 +733,43 @@ def test_fit_weighted_with_degree_steps_across_processes(dtype, tol, world, comm
     the ranks, lr = 1 / (2 max s) and the factors max s / s_i go to every rank, and the scaled
     weighted gradients travel through the peer exchange or the host-staged sum.  Equal to one
     process, whose weighted degrees are checked on the host."""
-    import torch.multiprocessing as mp
     import blueberry_amd as bb
     n = 2300
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker_weighted_fit, args=(r, world, port, n, dtype, comm, q))
-             for r in range(world)]
-    for p in procs:
-        p.start()
-    results = sorted((q.get(timeout=300) for _ in procs), key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=60)
+    results = run_ranks(_worker_degree_fit, world, n, dtype, 2, timeout=300,
+                        env=dict(PEER, BB_COMM=comm))
     for r in results:
-        assert not isinstance(r[1], str), r[1]
-        assert r[3] == comm
+        assert r[2] == comm
     w, x0 = _degree_map(n)
     one = bb.StructureSolver(n_iter=6, dtype=dtype, kind="wish", degree_steps=True, momentum=0.3,
                              weight_power=2, distributed=False).fit(w, init=x0)
     w32 = w.astype(dtype).astype(numpy.float64)
     s = numpy.where(w32 > 0, 1.0 / numpy.where(w32 > 0, w32, 1.0) ** 2, 0.0).sum(1)
     assert abs(one.lr_ * 2.0 * s.max() - 1) < 1e-13
-    for rank, X, h, _, lr in results:
+    for X, h, _, lr in results:
         assert abs(lr / one.lr_ - 1) < 1e-14
         assert numpy.abs(h / one.stress_ - 1).max() < tol
         assert numpy.abs(X - one.structure_).max() < tol * numpy.abs(one.structure_).max()
     for r in results[1:]:
-        assert numpy.array_equal(r[1], results[0][1])
+        assert numpy.array_equal(r[0], results[0][0])
 
 
-def _worker_spectral_fit(rank, world, port, n, dtype, comm, q):
-    try:
-        sys.path.insert(0, ROOT)
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        os.environ["BB_COMM"] = comm
-        os.environ["BB_PEER_TIMEOUT_MS"] = "20000"
-        import torch.distributed as dist
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        import blueberry_amd as bb
-        from blueberry_amd import solver
-        from tests import _oracle
-        calls = {"host_form": 0}
-        host_form = solver.spectral_init
+def _worker_spectral_fit(rank, world, n, dtype):
+    import blueberry_amd as bb
+    from blueberry_amd import solver
+    from tests import _oracle
+    calls = {"host_form": 0}
+    host_form = solver.spectral_init
 
-        def counted(*a, **k):
-            calls["host_form"] += 1
-            return host_form(*a, **k)
+    def counted(*a, **k):
+        calls["host_form"] += 1
+        return host_form(*a, **k)
 
-        solver.spectral_init = counted
-        xs = _oracle.random_walk(n)
-        w = _oracle.wish_from_coords(xs)
-        s = bb.StructureSolver(n_iter=3, dtype=dtype, kind="wish", device=0, init="spectral",
-                               seed=0).fit(w)
-        q.put((rank, s.structure_, s.stress_, s.exchange_, calls["host_form"]))
-        dist.barrier()
-        dist.destroy_process_group()
-    except Exception:
-        q.put((rank, traceback.format_exc(), None, None, None))
+    solver.spectral_init = counted
+    xs = _oracle.random_walk(n)
+    w = _oracle.wish_from_coords(xs)
+    s = bb.StructureSolver(n_iter=3, dtype=dtype, kind="wish", device=0, init="spectral",
+                           seed=0).fit(w)
+    return s.structure_, s.stress_, s.exchange_, calls["host_form"]
 
 
 @pytest.mark.parametrize("dtype,tol,world,comm", [("float64", 1e-9, 2, "peer"),
@@ -930,78 +782,47 @@ def test_fit_with_spectral_start_across_processes(dtype, tol, world, comm):
     per-rank products going through it -- and through the host-driven loop when it does not
     (gloo, host-staged).  Every rank ends with the start one process computes alone and the
     same three iterations from it."""
-    import torch.multiprocessing as mp
     import blueberry_amd as bb
     from tests import _oracle
     n = 2300
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker_spectral_fit, args=(r, world, port, n, dtype, comm, q))
-             for r in range(world)]
-    for p in procs:
-        p.start()
-    results = sorted((q.get(timeout=300) for _ in procs), key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=60)
+    results = run_ranks(_worker_spectral_fit, world, n, dtype, timeout=300,
+                        env=dict(PEER, BB_COMM=comm))
     for r in results:
-        assert not isinstance(r[1], str), r[1]
-        assert r[3] == comm
-        assert r[4] == (0 if comm == "peer" else 1)        # device form vs host-driven form
+        assert r[2] == comm
+        assert r[3] == (0 if comm == "peer" else 1)        # device form vs host-driven form
     w = _oracle.wish_from_coords(_oracle.random_walk(n))
     one = bb.StructureSolver(n_iter=3, dtype=dtype, kind="wish", init="spectral", seed=0,
                              distributed=False).fit(w)
     scale = numpy.abs(one.structure_).max()
-    for rank, X, hist, _, _ in results:
+    for X, hist, _, _ in results:
         assert numpy.abs(X - one.structure_).max() < tol * scale
         # exact recovery on a complete map: the stress is at rounding level on both sides
         assert hist[0] < 1e-6 * (w ** 2).sum() and one.stress_[0] < 1e-6 * (w ** 2).sum()
     for r in results[1:]:
-        assert numpy.array_equal(results[0][1], r[1])
+        assert numpy.array_equal(results[0][0], r[0])
 
 
-def _worker_fit_many(rank, world, port, q):
-    try:
-        sys.path.insert(0, ROOT)
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        import torch.distributed as dist
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        import blueberry_amd as bb
-        from tests import _oracle
-        sizes = [900, 300, 1500, 640, 1100]
-        mats = [_oracle.wish_from_coords(_oracle.random_walk(n, seed=50 + m)) for m, n in enumerate(sizes)]
-        s = bb.StructureSolver(n_iter=5, dtype="float32", kind="wish", device=0, seed=1).fit_many(mats)
-        q.put((rank, s.structures_, s.stresses_, s.ranks_of_maps_))
-        dist.barrier()
-        dist.destroy_process_group()
-    except Exception:
-        q.put((rank, traceback.format_exc(), None, None))
+def _worker_fit_many(rank, world):
+    import blueberry_amd as bb
+    from tests import _oracle
+    sizes = [900, 300, 1500, 640, 1100]
+    mats = [_oracle.wish_from_coords(_oracle.random_walk(n, seed=50 + m)) for m, n in enumerate(sizes)]
+    s = bb.StructureSolver(n_iter=5, dtype="float32", kind="wish", device=0, seed=1).fit_many(mats)
+    return s.structures_, s.stresses_, s.ranks_of_maps_
 
 
 def test_fit_many_across_processes(oracle):
     """Several ranks: the maps are dealt to the ranks, every rank solves its own in one solver on
     the device, all ranks get all results; each map against the oracle's solve of it (fp32)."""
-    import torch.multiprocessing as mp
     from tests import _oracle
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker_fit_many, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    results = sorted((q.get(timeout=300) for _ in procs), key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=60)
-    for r in results:
-        assert not isinstance(r[1], str), r[1]
-    assert results[0][3] == results[1][3] and set(results[0][3]) == {0, 1}
+    results = run_ranks(_worker_fit_many, 2, timeout=300)
+    assert results[0][2] == results[1][2] and set(results[0][2]) == {0, 1}
     sizes = [900, 300, 1500, 640, 1100]
     for m, n in enumerate(sizes):
         w = _oracle.wish_from_coords(_oracle.random_walk(n, seed=50 + m))
         x0 = numpy.random.default_rng(1).standard_normal((n, 3))
         X, h = oracle.solve(w, x0, 5, 1.0 / (2 * n), f64=False)
         for r in results:
-            assert numpy.abs(r[1][m] - X).max() < 1e-5 * numpy.abs(X).max()
-            assert numpy.abs(r[2][m] / h - 1).max() < 1e-5
-        assert numpy.array_equal(results[0][1][m], results[1][1][m])
+            assert numpy.abs(r[0][m] - X).max() < 1e-5 * numpy.abs(X).max()
+            assert numpy.abs(r[1][m] / h - 1).max() < 1e-5
+        assert numpy.array_equal(results[0][0][m], results[1][0][m])

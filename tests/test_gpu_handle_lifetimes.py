@@ -19,6 +19,7 @@ import pytest
 from blueberry_amd import _lib
 from blueberry_amd.solver import DeviceTriples, HipEngine, layout_info
 from tests import _oracle
+from tests._util import solver_path                   # noqa: F401 -- a fixture
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,16 +28,6 @@ K = 5
 SIZES = [("float32", 1100), ("float64", 300)]
 # diagonal blocks and one off-diagonal tile inside the second map: no tile joins two maps
 TILES = (numpy.array([0, 1, 1, 2], dtype=numpy.int32), numpy.array([0, 1, 2, 2], dtype=numpy.int32))
-
-
-@pytest.fixture(params=["row_owner", "units"])
-def solver_path(request, monkeypatch):
-    """As test_gpu_parity.py's: the row-owner path, or BB_ROW_OWNER_MAX=0 for the unit sweep."""
-    if request.param == "units":
-        monkeypatch.setenv("BB_ROW_OWNER_MAX", "0")
-    else:
-        monkeypatch.delenv("BB_ROW_OWNER_MAX", raising=False)
-    return request.param
 
 
 _problems, _plain_runs = {}, {}

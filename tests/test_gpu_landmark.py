@@ -25,14 +25,11 @@ import blueberry_amd as bb
 from blueberry_amd import _lib
 from tests import _input_model as im
 from tests import _landmark_model as lm
+from tests._util import bits
 
 pytestmark = pytest.mark.gpu
 
 SOURCE_COUNTS = (1, 3, 64, 65, 130)
-
-
-def bits(a):
-    return numpy.ascontiguousarray(a, dtype=numpy.float64).view(numpy.uint64)
 
 
 def sources_for(n_nodes, count, seed):

@@ -16,12 +16,11 @@ import pytest
 from blueberry_amd.solver import HipEngine
 from tests import _oracle
 from tests._pack24_model import RPU, SPAN, UPT, VW, model
+from tests._pack24_model import uniform_map as _uniform_map
+from tests._util import bits as _bits
+from tests._util import cu_count as _cu_count
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(a):
-    return numpy.ascontiguousarray(a, dtype=numpy.float64).view(numpy.uint64)
 
 
 def _same(a, b):
@@ -37,14 +36,6 @@ def _env(monkeypatch, **env):
         monkeypatch.setenv(k, str(v))
 
 
-def _uniform_map(n, seed=0, lo=1.0, hi=1.9):
-    """Symmetric, zero diagonal, off-diagonal distances uniform in [lo, hi], exact in float32."""
-    rng = numpy.random.default_rng(seed)
-    w = rng.uniform(lo, hi, (n, n)).astype(numpy.float32).astype(numpy.float64)
-    w = numpy.triu(w, 1)
-    return w + w.T
-
-
 def _cell_of_unit(u, row=1, col=37):
     """A cell (i, j) of local unit u of a one-rank dense layout (strip-major: tile t = J (J + 1) / 2
     + I holds units t * 128 ..), off the diagonal tiles."""
@@ -57,17 +48,6 @@ def _cell_of_unit(u, row=1, col=37):
     I = t - J * (J + 1) // 2
     assert I < J, "a unit of a diagonal tile"
     return I * VW + sub * RPU + row, J * VW + col
-
-
-def _cu_count():
-    """Compute units of device 0, from the HIP runtime the library itself has loaded."""
-    import ctypes
-    from blueberry_amd import _lib
-    _lib.load()
-    hip = ctypes.CDLL([p for p in _lib.hip_runtimes_loaded() if "libamdhip64" in p][0])
-    v = ctypes.c_int(0)
-    assert hip.hipDeviceGetAttribute(ctypes.byref(v), 63, 0) == 0    # hipDeviceAttributeMultiprocessorCount
-    return int(v.value)
 
 
 def _run(n, set_wish, x0, steps=(7, 8), rank=0, world=1):

@@ -26,7 +26,10 @@ from tests import _many_model as mm
 from tests import _oracle
 from tests import _pack24_model as pm
 from tests._pack24_model import RPU, UPT, VW
-from tests.test_gpu_pack24 import _cu_count, _env, _same, _uniform_map
+from tests._pack24_model import uniform_map as _uniform_map
+from tests._ranks import no_rank_process_outlives_its_test as _no_rank_process_outlives_its_test    # noqa: F401
+from tests._util import cu_count as _cu_count
+from tests.test_gpu_pack24 import _env, _same
 
 pytestmark = pytest.mark.gpu
 
@@ -976,13 +979,6 @@ def test_anchored_fit_with_the_stream(monkeypatch):
     err_x = float(numpy.abs(on["X", 0.0] - X).max() / numpy.abs(X).max())
     _report("anchored fit, 8 landmarks", info, gradient=err_g, stress=err_s, history=err_h, coordinates=err_x)
     assert err_g <= TOL and err_s <= TOL and err_h <= TOL and err_x <= TOL
-
-
-@pytest.fixture
-def _no_rank_process_outlives_its_test():
-    yield
-    from tests import _ranks
-    _ranks.close_all()
 
 
 def _peer_map():

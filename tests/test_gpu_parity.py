@@ -9,16 +9,15 @@ import blueberry_amd as bb
 from blueberry_amd import _lib
 from blueberry_amd.solver import HipEngine
 from tests import _oracle
+from tests._oracle import band_cases
+from tests._util import host_threads as _host_threads
+from tests._util import rel as _rel
+from tests._util import solver_path                   # noqa: F401 -- a fixture
 
 pytestmark = pytest.mark.gpu
 
 
 # ---- K1 ---------------------------------------------------------------------
-def band_cases():
-    z = _oracle.golden("band_count")
-    return sorted(k[3:] for k in z.files if k.startswith("in_"))
-
-
 @pytest.mark.parametrize("name", band_cases())
 def test_band_count_golden(name):
     z = _oracle.golden("band_count")
@@ -473,22 +472,6 @@ def test_contactmap_zero_kr_raises_like_reference():
 def _problem(n, seed=0):
     xs = _oracle.random_walk(n, seed)
     return xs, _oracle.wish_from_coords(xs), _oracle.noisy_init(xs)
-
-
-@pytest.fixture(params=["row_owner", "units"])
-def solver_path(request, monkeypatch):
-    """Small one-rank problems iterate on the row-owner path (one launch per iteration,
-    both triangles resident); BB_ROW_OWNER_MAX=0 sends them down the unit sweep that
-    large maps and multi-rank jobs use.  Tests that carry this fixture hold for both."""
-    if request.param == "units":
-        monkeypatch.setenv("BB_ROW_OWNER_MAX", "0")
-    else:
-        monkeypatch.delenv("BB_ROW_OWNER_MAX", raising=False)
-    return request.param
-
-
-def _rel(a, b):
-    return numpy.abs(a - b).max() / numpy.abs(b).max()
 
 
 def test_solver_fp64_chr21_sized(oracle, solver_path):
@@ -1223,14 +1206,6 @@ def _dense_wish(n):
         d = xs[a:a + 2000, None, :] - xs[None, :, :]
         w[a:a + 2000] = numpy.sqrt((d * d).sum(-1))
     return w
-
-
-def _host_threads():
-    import os
-    try:
-        return max(1, min(16, len(os.sched_getaffinity(0))))
-    except AttributeError:
-        return max(1, min(16, os.cpu_count() or 1))
 
 
 @pytest.mark.parametrize("mu", [0.0, 0.5])

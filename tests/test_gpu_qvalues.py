@@ -23,20 +23,13 @@ from blueberry_amd import _lib
 from blueberry_amd import fithic as fh
 from tests import _fithic_model as fm
 from tests import _qvalue_model as qm
+from tests._util import same_bits
 
 pytestmark = pytest.mark.gpu
 
 RES = 10
 FULL = (0, 10000000)
 LENGTHS = [0, 1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097, 8193, 262145]
-
-
-def bits(a):
-    return numpy.ascontiguousarray(a, dtype=numpy.float64).view(numpy.uint64)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and numpy.array_equal(bits(a), bits(b))
 
 
 def host_route(p, n_tests):

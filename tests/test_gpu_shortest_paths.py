@@ -15,6 +15,7 @@ import pytest
 
 import blueberry_amd as bb
 from blueberry_amd import _lib
+from tests._util import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -60,10 +61,6 @@ def scipy_paths(weights):
     w = numpy.where(numpy.isfinite(weights) & (weights > 0), weights, 0.0)
     numpy.fill_diagonal(w, 0.0)
     return scipy.sparse.csgraph.shortest_path(scipy.sparse.csr_matrix(w), method="D", directed=False)
-
-
-def bits(a):
-    return numpy.ascontiguousarray(a, dtype=numpy.float64).view(numpy.uint64)
 
 
 def check_against_scipy(g, unreachable, ref, n, extra_tol):

@@ -31,6 +31,7 @@ import blueberry_amd as bb
 from blueberry_amd import _lib
 from blueberry_amd import fithic as fh
 from tests import _fithic_model as fm
+from tests._util import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -38,14 +39,6 @@ RES = 10
 DEVICE_BOUND = 16 * fm.MODEL_WORST
 DENSE_SIZES = [2, 3, 65, 66, 129, 1025, 1026, 1027]
 FULL = (0, 10000000)
-
-
-def bits(a):
-    return numpy.ascontiguousarray(a, dtype=numpy.float64).view(numpy.uint64)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and numpy.array_equal(bits(a), bits(b))
 
 
 def rel_to(got, want):

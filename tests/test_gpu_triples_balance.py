@@ -23,6 +23,7 @@ import blueberry_amd as bb
 from blueberry_amd import _lib
 from tests import _balance_model as bm
 from tests import _triples_model as tm
+from tests._util import max_rel, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -31,22 +32,6 @@ BAND17_SIZES = [129, 4097]
 EPS = 2.0 ** -52
 RES = tm.RESOLUTION
 SEG = 1024          # kTbSeg of bb_triples_balance.hip: the entries of a row one wave sums
-
-
-def bits(a):
-    return numpy.ascontiguousarray(a, dtype=numpy.float64).view(numpy.uint64)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and numpy.array_equal(bits(a), bits(b))
-
-
-def max_rel(got, want):
-    nan = numpy.isnan(want)
-    assert numpy.array_equal(numpy.isnan(got), nan)
-    if nan.all():
-        return 0.0
-    return float(numpy.max(numpy.abs(got[~nan] - want[~nan]) / numpy.abs(want[~nan])))
 
 
 _lists = {}

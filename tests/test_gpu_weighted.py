@@ -5,7 +5,6 @@ bb_oracle_mt.c bbo_solve_gen_weighted_mt; pinned to the numpy model of test_weig
 test_oracle.py).  Tolerances as for q = 0: fp64 1e-12, fp32 1e-5, relative, on every entry of the
 stress history and on the max-abs coordinates."""
 import functools
-import os
 
 import numpy
 import pytest
@@ -13,6 +12,9 @@ import pytest
 import blueberry_amd as bb
 from blueberry_amd.solver import HipEngine, layout_info, weighted_steps
 from tests import _oracle
+from tests._util import host_threads as _host_threads
+from tests._util import rel as _rel
+from tests._util import solver_path as path         # noqa: F401 -- the fixture, under this file's name
 from tests.test_weighted_stress import count_map, start, weights, wish_of
 
 pytestmark = pytest.mark.gpu
@@ -22,23 +24,12 @@ NT_BYTES = 240 << 20          # build_indices: non-temporal loads once a rank's 
 UNIT_BYTES = 8192
 
 
-def _rel(a, b):
-    return numpy.abs(a - b).max() / numpy.abs(b).max()
-
-
 def _close(X, h, X_ref, h_ref, dtype):
     tol = TOL[dtype]
     assert h.shape == h_ref.shape
     err_s, err_x = float(numpy.abs(h / h_ref - 1).max()), float(_rel(X, X_ref))
     assert err_s < tol and err_x < tol, (dtype, err_s, err_x)
     return err_s, err_x
-
-
-def _host_threads():
-    try:
-        return max(1, min(16, len(os.sched_getaffinity(0))))
-    except AttributeError:
-        return max(1, min(16, os.cpu_count() or 1))
 
 
 def _counts(n, seed):
@@ -94,17 +85,6 @@ def _run(n, dtype, W, q, x0, k, lr, mu=0.0, scale=None):
         return eng.get_coords(), eng.stress_history(), eng.iteration_path()
     finally:
         eng.close()
-
-
-@pytest.fixture(params=["row_owner", "units"])
-def path(request, monkeypatch):
-    """Maps up to 4,096 bins iterate on the row-owner kernel; BB_ROW_OWNER_MAX=0 sends them
-    down the unit sweep."""
-    if request.param == "units":
-        monkeypatch.setenv("BB_ROW_OWNER_MAX", "0")
-    else:
-        monkeypatch.delenv("BB_ROW_OWNER_MAX", raising=False)
-    return request.param
 
 
 def _want_path(n, path):

@@ -10,10 +10,7 @@ import blueberry_amd as bb
 from blueberry_amd import solver as bs
 from tests import _landmark_model as lm
 from tests._engines import OracleEngine
-
-
-def bits(a):
-    return numpy.ascontiguousarray(a, dtype=numpy.float64).view(numpy.uint64)
+from tests._util import bits
 
 
 # ---- 1. the fixed point is Dijkstra's, bit for bit -------------------------------------------

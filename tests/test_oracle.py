@@ -5,14 +5,10 @@ import numpy
 import pytest
 
 from tests import _oracle
+from tests._oracle import band_cases
 
 
 # ---- K1 count_band_regions (blueberry.pyx:77-91): exact -------------------
-def band_cases():
-    z = _oracle.golden("band_count")
-    return sorted(k[3:] for k in z.files if k.startswith("in_"))
-
-
 @pytest.mark.parametrize("name", band_cases())
 def test_band_count_matches_reference(oracle, name):
     z = _oracle.golden("band_count")

@@ -8,13 +8,7 @@ import pytest
 from tests import _oracle
 from tests import _pack24_model as pm
 from tests._pack24_model import RPU, SPAN, UPT, VW
-
-
-def _uniform_map(n, seed=0, lo=1.0, hi=1.9):
-    rng = numpy.random.default_rng(seed)
-    w = rng.uniform(lo, hi, (n, n)).astype(numpy.float32).astype(numpy.float64)
-    w = numpy.triu(w, 1)
-    return w + w.T
+from tests._pack24_model import uniform_map as _uniform_map
 
 
 def test_dense_2048_diagonal_tiles_raw_all_others_packed():

@@ -1,18 +1,12 @@
 """SPEC 2.8 without a GPU: the float64 model on closed forms, FitScore's derivations against
 direct numpy, and StructureSolver.score through the engine= seam (one process, and two gloo
 ranks whose sums are added)."""
-import os
-import socket
-import sys
-import traceback
-
 import numpy
 import pytest
 
 import blueberry_amd as bb
 from tests import _score_model as model
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests._jobs import run_ranks
 
 
 def _pairs(w, x):
@@ -233,50 +227,19 @@ def test_score_argument_validation():
 
 
 # ---- two gloo ranks: each scores its own units, the sums are added ----------------------------
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-def _score_worker(rank, world, port, n, q):
-    try:
-        sys.path.insert(0, ROOT)
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        import torch.distributed as dist
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        import blueberry_amd as bb
-        from tests import _score_model as model
-        w, x = model.exact_case(n)
-        s = bb.StructureSolver(dtype="float64", kind="wish", engine=model.ScoringOracleEngine).score(w, structure=x)
-        part = model.ScoringOracleEngine(n, "float64", rank=rank, world=world)
-        part.set_wish_dense(w, "wish", 3.0)
-        q.put((rank, s.sums, s.bin_sums, part.score(x)[0][:, 0].sum()))
-        dist.barrier()
-        dist.destroy_process_group()
-    except Exception:
-        q.put((rank, traceback.format_exc(), None, None))
+def _score_worker(rank, world, n):
+    w, x = model.exact_case(n)
+    s = bb.StructureSolver(dtype="float64", kind="wish", engine=model.ScoringOracleEngine).score(w, structure=x)
+    part = model.ScoringOracleEngine(n, "float64", rank=rank, world=world)
+    part.set_wish_dense(w, "wish", 3.0)
+    return s.sums, s.bin_sums, part.score(x)[0][:, 0].sum()
 
 
 def test_score_on_two_gloo_ranks_equals_one_process():
-    import torch.multiprocessing as mp
     n, world = 300, 2
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_score_worker, args=(r, world, port, n, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = [q.get(timeout=240) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
-    for r in results:
-        assert not isinstance(r[1], str), r[1]
+    results = run_ranks(_score_worker, world, n, timeout=240)
     w, x = model.exact_case(n)
     want = model.score_sums(w, x)
-    for rank, sums, bin_sums, own_pairs in results:
+    for sums, bin_sums, own_pairs in results:
         assert numpy.array_equal(sums, want[0]) and numpy.array_equal(bin_sums, want[1])
         assert 0 < own_pairs < want[0][:, 0].sum()              # every rank held a share only

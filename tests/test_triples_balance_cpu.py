@@ -14,18 +14,11 @@ import blueberry_amd as bb
 from blueberry_amd import _lib
 from tests import _balance_model as bm
 from tests import _triples_model as tm
+from tests._util import max_rel
 
 SIZES = [2, 3, 64, 65, 66, 129, 1025]
 BANDS = [0, 2, 17]
 EPS = 2.0 ** -52
-
-
-def max_rel(got, want):
-    nan = numpy.isnan(want)
-    assert numpy.array_equal(numpy.isnan(got), nan)
-    if nan.all():
-        return 0.0
-    return float(numpy.max(numpy.abs(got[~nan] - want[~nan]) / numpy.abs(want[~nan])))
 
 
 def maps(d):

@@ -7,6 +7,7 @@ import pytest
 
 import blueberry_amd as bb
 from blueberry_amd.solver import HipEngine, tiles_from_blocks, weighted_steps
+from tests._util import rel as _rel
 
 
 # --------------------------------------------------------------------------
@@ -75,10 +76,6 @@ def wish_of(C, dtype, alpha=3.0):
 
 def start(n, W, seed=1):
     return numpy.random.default_rng(seed).standard_normal((n, 3)) * float(numpy.median(W[W > 0]))
-
-
-def _rel(a, b):
-    return numpy.abs(a - b).max() / numpy.abs(b).max()
 
 
 # --------------------------------------------------------------------------
