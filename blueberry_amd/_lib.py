@@ -33,6 +33,21 @@ class LayoutInfo(ctypes.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class SweepKnobs(ctypes.Structure):
+    """struct bb_sweep_knobs (include/blueberry_hip.h)."""
+    _fields_ = [(name, c_i32) for name in ("waves_per_cu", "pair", "reduce_slices", "row_owner")]
+
+
+class SweepPlan(ctypes.Structure):
+    """struct bb_sweep_plan (include/blueberry_hip.h)."""
+    _fields_ = [(name, c_i64) for name in (
+        "n_local", "t_first", "n_local_tiles", "n_waves", "wpb", "chunk_q", "chunk_r", "n_slots",
+        "rowpart_elems", "colpart_elems", "zero_off", "part_total", "red_slices", "red_stride",
+        "red_blocks", "defer_cap_units", "lds_wave_floats", "defer_lds_bytes", "nontemporal",
+        "full_ld", "ro_wpr", "ro_blocks")]
+    as_dict = LayoutInfo.as_dict
+
+
 # name -> (restype, argtypes); every symbol include/blueberry_hip.h declares
 SIGNATURES = {
     "bb_version": (c_int, []),
@@ -43,6 +58,11 @@ SIGNATURES = {
     "bb_layout_dense_info": (c_int, [c_i64, c_int, ctypes.POINTER(LayoutInfo)]),
     "bb_layout_dense_tiles": (c_int, [c_i64, c_int, p_i32, p_i32, c_i64]),
     "bb_layout_rank_units": (c_int, [c_i64, c_int, c_int, p_i64, p_i64]),
+    "bb_layout_sweep_plan": (c_int, [c_i64, c_int, p_i32, p_i32, c_i64, c_i64, c_i64, c_int,
+                                     ctypes.POINTER(SweepKnobs), ctypes.POINTER(SweepPlan), p_i32,
+                                     p_i32, p_i32, p_i32, p_i64]),
+    "bb_layout_pk24_table": (c_int, [ctypes.POINTER(ctypes.c_uint32), p_i32, c_i64, c_i64, c_int,
+                                     p_i32, p_i64, p_i64, p_i64, ctypes.POINTER(c_int)]),
     "bb_solver_create": (c_int, [ctypes.POINTER(c_void_p), c_i64, c_int, c_int, c_int, c_int,
                                  p_i32, p_i32, c_i64]),
     "bb_solver_destroy": (c_int, [c_void_p]),

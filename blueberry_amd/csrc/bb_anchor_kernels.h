@@ -2,7 +2,7 @@
 // geodesics, resident in the run's dtype as A[a][v] (n_pad values per row, 0 = no term), add
 //     lambda * sum_a sum_v A_av^-q (|x_{s_a} - x_v|_eps - A_av)^2
 // to the stress and its gradient to the exchange buffer [g * 2 * bin_scale | stress hi | lo] the
-// reduce has left (bb_solver_kernels.h: kReduceExchange).  Three launches, no floating-point
+// reduce has left (bb_solver_device.h: kReduceExchange).  Three launches, no floating-point
 // atomics, every sum in an order fixed by (n_bins, L') alone:
 //   anchor_node_kernel      a thread owns node v: the landmarks' coordinates in LDS, a ascending
 //                           over the coalesced A[a][v], g_v and the stress share in registers
@@ -13,21 +13,19 @@
 //                           kAnchorChunk nodes, re-reading the row, to slot (a, c)
 //   anchor_fold_kernel      a workgroup per landmark: its slots added in a fixed order into
 //                           exch[3 s_a ..]; the first one folds the stress slots into hi / lo
-// and the two kernels behind bb_solver_anchor_sums, the conversion of the float64 rows of a
-// bb_paths into A (through bb_wish.h's flush: the one value rule), gfx950 only.
+// and the conversion of the float64 rows of a bb_paths into A (through bb_wish.h's flush: the
+// one value rule), gfx950 only.  (The two kernels behind bb_solver_anchor_sums are compiled with
+// the reduce, in bb_solver_kernels.h: see there.)  Included by
+// bb_solver_anchors.hip and by nothing else; the fold modes (AnchorFold), which the callers of
+// launch_anchors name, are in bb_solver_device.h.
 #pragma once
 
-#include "bb_solver_kernels.h"
+#include "bb_solver_device.h"
 
 namespace {
 
 constexpr int kAnchorMaxRows = 1024;    // BB_PATHS_MAX_SOURCES: what the LDS stage holds
 constexpr int kAnchorChunk = 1024;      // nodes of one workgroup of the landmark side
-enum AnchorFold {
-    kAnchorFoldExchange = 0,   // landmark gradients and the stress into the exchange buffer
-    kAnchorFoldStress = 1,     // stress_out[0] += the anchor stress
-    kAnchorFoldAlone = 2       // the anchor stress alone
-};
 
 // One term (a, v) with delta = A_av > 0 and (dx, dy, dz) = x_v - x_{s_a}, in the run's dtype:
 // st = lambda w (d - delta)^2 and coef = lambda w (d - delta) / d, w = delta^-Q; the factor 2 of
@@ -189,41 +187,6 @@ __global__ __launch_bounds__(256) void anchor_fold_kernel(
 #pragma unroll
         for (int k = 0; k < 3; ++k) anchor_add(exch, bin_scale, s, k, g[k]);
     }
-}
-
-// ---- the step quantities: per bin, lambda * sum of A^-Q over the terms that touch it ----------
-template <typename T, int Q>
-__device__ __forceinline__ double anchor_weight(T v) {
-    const double d = (double)v;
-    if (!(d > 0.0)) return 0.0;
-    return Q == 0 ? 1.0 : (Q == 1 ? 1.0 / d : 1.0 / (d * d));
-}
-// node side: sums[v] = lambda * sum_a w(A[a][v]), a ascending
-template <typename T, int Q>
-__global__ __launch_bounds__(256) void anchor_sums_node_kernel(const T *__restrict__ A, int64_t n_pad,
-                                                               int64_t n_bins, int n_rows, double lam,
-                                                               double *__restrict__ sums) {
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v >= n_bins) return;
-    double acc = 0.0;
-    for (int a = 0; a < n_rows; ++a) acc += anchor_weight<T, Q>(A[(int64_t)a * n_pad + v]);
-    sums[v] = lam * acc;
-}
-// landmark side, one workgroup per landmark, launched behind the node side: thread t adds nodes
-// t, t + 256, ... in order, the threads meet in the fixed tree, sums[s_a] += lambda * the total
-template <typename T, int Q>
-__global__ __launch_bounds__(256) void anchor_sums_landmark_kernel(const T *__restrict__ A, int64_t n_pad,
-                                                                   int64_t n_bins,
-                                                                   const int *__restrict__ nodes, double lam,
-                                                                   double *__restrict__ sums) {
-    __shared__ double sh[256];
-    const int tid = threadIdx.x, a = blockIdx.x;
-    double acc = 0.0;
-    for (int64_t v = tid; v < n_bins; v += 256) acc += anchor_weight<T, Q>(A[(int64_t)a * n_pad + v]);
-    sh[tid] = acc;
-    __syncthreads();
-    lds_tree_fold(sh, tid, 256);
-    if (tid == 0) sums[nodes[a]] += lam * sh[0];
 }
 
 // ---- A from the float64 rows of a bb_paths: D is (n_nodes, ld), node-major, +inf = no path ----

@@ -1,17 +1,10 @@
 // bb_solver.hip -- host side of the 3D-structure solver of libblueberry_hip.so: the
-// bb_solver handle (layout, partition into ranks / waves / partial-sum slots, device
-// buffers), kernel launches, the multi-rank exchanges (RCCL, peer arenas) and the
-// bb_solver_* / bb_comm_* entry points of include/blueberry_hip.h, and the groups of solvers
-// one process drives on several devices (bb_group_*).  The kernels are in
-// bb_solver_kernels.h, those of the landmark constraints (bb_solver_set_anchors) in
-// bb_anchor_kernels.h.  gfx950 only.
-//
-// Who owns what: every device allocation and event of a handle (bb_solver, bb_triples, bb_group)
-// is a bb::DevBuf / bb::Event member of it (bb_common.h) and goes with the handle, or earlier
-// by reset(); a staging buffer is such an owner as a local.  Plain pointers are views: into the
-// solver's arena, or -- d_exch -- of own_exch or of a caller's memory.  The destroy functions
-// keep only what has an order: the stream (the pool's), the communicator (the cache's, or the
-// solver's own) and the peers' arenas it opened.
+// bb_solver handle's create / destroy (the partition itself is bb_solver_plan.cpp: no device
+// call), kernel launches, the input routes, the multi-rank exchanges (RCCL, peer arenas) and
+// the bb_solver_* / bb_comm_* entry points of include/blueberry_hip.h.  The kernels are in
+// bb_solver_kernels.h.  The handle, and the parts of the solver that have a file of their own
+// (landmark constraints, spectral start, groups): bb_solver_internal.h.  The environment is
+// read in solver_env().  gfx950 only.
 //
 // Specification: docs/SPEC.md (build-authored; the reference has no solver,
 // SURVEY.md section 0).  Data layout and kernel design: DESIGN.md 3-4.
@@ -24,150 +17,25 @@
 
 #include <algorithm>
 #include <cmath>
-#include <type_traits>
-#include <vector>
-
-#include <condition_variable>
 #include <map>
 #include <mutex>
-#include <thread>
 #include <tuple>
 
-#include "bb_comm.h"
-#include "bb_common.h"
-#include "bb_group_barrier.h"
 #include "bb_score.h"
+#include "bb_solver_internal.h"
 #include "bb_solver_kernels.h"
-#include "bb_anchor_kernels.h"
 #include "bb_triples.h"
 
-// --------------------------------------------------------------------------
-// host side
-// --------------------------------------------------------------------------
-struct bb_solver {
-    int dtype = BB_F32, device = 0, rank = 0, world = 1;
-    bool wide = true;  // unit shape (Lay<T, wide>): false only for small fp64 problems
-    bb_layout_info L{};
-    std::vector<int32_t> tile_I, tile_J;  // global tile list (device order)
-    int64_t u_begin = 0, u_end = 0, n_local = 0;
-    int64_t t_first = 0, n_local_tiles = 0;
-    std::vector<int2> udesc;  // host copy
-
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    bool stream_stuck = false;     // behind a collective that cannot be aborted: never waited on again
-
-    void *d_units = nullptr, *d_X = nullptr, *d_V = nullptr, *d_part = nullptr;
-    // the exchange buffer: a view of own_exch, or -- own_exch empty -- the memory a caller gave
-    // (bb_solver_set_exchange_buffer), which is never freed here
-    void *d_exch = nullptr;
-    bb::DevBuf own_exch;
-    double momentum = 0.0;
-    int2 *d_udesc = nullptr;
-    int chunk_q = 0, chunk_r = 0;  // units per wave: n_local = n_waves * q + r
-    bool nontemporal = true;
-    bb::DevBuf d_arena;            // the one allocation behind every plain d_* pointer here (views of it)
-    int2 *d_wave_slots = nullptr;  // per wave {first private slot, the workgroup's shared slot}
-    int lds_wave_floats = 0;       // LDS region per wave of the sweep, in 4-byte words
-    double *d_stresspart = nullptr;
-    double *d_stress_slot = nullptr;     // one per column slot: the stress of a strip a wave left
-    std::vector<int32_t> slot_strip;     // strip (block column) of every column slot
-    std::vector<int32_t> wave_last_strip;  // strip each wave ends in, -1: no units
-    // several maps in one solver (bb_solver_set_maps)
-    int n_maps = 1;
-    bb::DevBuf d_bin_scale;              // T per bin (n_pad): the factor on its gradient
-    bb::DevBuf d_map_ptr, d_map_idx;     // int: the maps' lists of stress partials (CSR)
-    bb::DevBuf d_map_scalar;             // double: per-map stress of bb_solver_stress_maps
-    std::vector<int64_t> map_begin;      // first bin of every map, + n_bins
-    int64_t *d_red_lists = nullptr;   // reduce_sliced_kernel: one padded chunk list per block
-    int red_stride = 0, red_slices = 0;   // entries per block (multiple of 16 * slices); 4 or 8 slices
-    double *d_stress_hist = nullptr, *d_stress_scalar = nullptr;
-    double *d_f64_tmp = nullptr;  // (n_pad,3) staging for coordinate I/O
-    bb::DevBuf d_mv_in;           // (n_pad,3) right-hand sides of bb_solver_matvec_sq, kept
-    int64_t rowpart_elems = 0, colpart_elems = 0;
-    int n_waves = 0, n_slots = 0;
-    int wpb = 4;                   // waves per workgroup of the sweep: 4, or 8 (paired, see kernel)
-    int dense_u0 = -1;             // dense tile list: this rank's first global unit (the kernel then
-                                   // computes a wave's first descriptor), else -1
-    int defer_cap_units = 0;       // fp32 / fp64 wide: units of row sums a wave can park in LDS
-    int64_t defer_lds_bytes = 0;   // dynamic LDS per workgroup of the sweep
-    unsigned defer_attr_done = 0;  // sweep instantiations whose dynamic-LDS ceiling was raised
-    int64_t hist_cap = 0, hist_n = 0;
-    bool have_wish = false, have_coords = false, grad_pending = false;
-    // exchange_sum(): while set, the reduce / exchange kernels leave the plain sum over the
-    // ranks HERE instead of stepping the coordinates (X := this buffer, zeroed; V := d_V;
-    // mu = 0, lr = -1: 0 + (0 * v - (-1) * sum) is the sum, exactly)
-    void *sum_target = nullptr;
-
-    bb::Rccl::Comm comm = nullptr;  // direct RCCL path (bb_solver_comm_init), else null
-    bool comm_cached = false;       // the communicator belongs to the process-wide cache
-    bool comm_suspect = false;      // a collective on it failed to enqueue: never handed out again
-
-    // peer exchange (bb_solver_peer_*)
-    bb::DevBuf peer_arena;                  // this rank's receive arena (uncached)
-    int64_t peer_slot_elems = 0, peer_arena_bytes = 0;
-    std::vector<void *> peer_mapped;        // arenas of all ranks as mapped here (own = peer_arena)
-    std::vector<void *> peer_opened;        // the ones that came from hipIpcOpenMemHandle
-    bb::DevBuf d_peer_table;                // PeerTable<T>[2], one per parity
-    bb::DevBuf d_peer_table_x;              // PeerTableX<T>[2]: the one-launch exchange
-    bool peer_fused = true;                 // reduce_exchange_kernel (BB_PEER_FUSED=0: two launches)
-    bb::DevBuf d_peer_state;                // PeerState: sticky failure flag + last complete exchange
-    int peer_clock_khz = 100000;            // constant-rate clock behind wall_clock64()
-    int peer_ranks_on_gpu = 1;              // most ranks of the job on one GPU (a rehearsal: > 1)
-    bb::DevBuf d_peer_mask;                 // unsigned per block: the ranks whose units touch it (bit r)
-    bb::DevBuf d_peer_counter;              // unsigned: the reduce's two-level check-in
-    unsigned long long peer_seq = 0;        // iterations exchanged so far
-    long long peer_limit_ticks = 0;
-    bool peer_connected = false;
-
-    // row-owner path (small maps, world = 1): both triangles resident, one launch per
-    // iteration (row_owner_kernel); the units stay resident too and serve every other
-    // entry point (grad / apply, stress, matvec)
-    bool row_owner = false;
-    bool row_owner_built = false;        // created with the row-owner buffers (bb_solver_set_maps
-                                         // switches row_owner off)
-    bool bin_steps = false;              // d_bin_scale set by bb_solver_set_bin_steps / _block_steps
-    int weight_power = 0;                // SPEC 2.3.1: w = delta^-q, q in {0, 1, 2}
-    void *d_full = nullptr, *d_X2 = nullptr;
-    int64_t full_ld = 0;
-    double *d_ro_part = nullptr;   // 2 x ro_blocks per-workgroup stress sums (ping-pong)
-    int ro_blocks = 0, ro_wpr = 1;  // workgroups holding rows; waves per row (1, 2, 4)
-    int64_t ro_launches = 0;       // row-owner launches so far (parity of the ping-pong)
-
-    // the 24-bit stream of the fp32 sweep (SPEC 3.7): derived from d_units, rebuilt by
-    // ensure_pk24() before the first sweep after a writer of d_units (pk_stale)
-    int pk_mode = -1;              // BB_PACK24 at create: 0 never, 1 whenever a unit packs, else the rule
-    int64_t pk_min_run = 64;       // BB_PACK24_MIN_RUN at create: shortest run of units stored packed
-    bool pk_stale = true, pk_valid = false;
-    bb::DevBuf pk_stream, pk_table;   // outside the arena: the solver runs raw without them
-    int64_t pk_packed = 0, pk_bytes = 0, pk_switches = 0;
-
-    // landmark constraints (bb_solver_set_anchors, SPEC 2.5.5): the solver's own copy of the kept
-    // rows in its dtype; anchor_n = 0: none, and every path is the one it was without them
-    int anchor_n = 0;                    // kept rows L'
-    double anchor_weight = 0.0;          // lambda
-    int64_t anchor_terms = 0;            // values > 0 among the rows
-    int anchor_chunks = 0, anchor_node_blocks = 0;
-    bb::DevBuf anchor_rows;              // T (anchor_n, n_pad)
-    bb::DevBuf anchor_nodes;             // int per kept row: its landmark's node
-    bb::DevBuf anchor_part;              // double: anchor stress | per-workgroup stress | (a, chunk, 3)
-
-    bool timing = false;
-    int timing_stride = 1;      // events on every timing_stride-th iteration
-    int64_t timing_iter = 0;    // iterations seen since timing was (re-)enabled
-    std::vector<bb::Event> ev;   // triples: start, after grad, after reduce
-    size_t ev_used = 0;
-    double score_ms[3] = {0.0, 0.0, 0.0};   // the last timed bb_solver_score: profile, fold, per bin
-};
+using namespace bb::solver;
 
 namespace {
-
 void comm_release(bb_solver *s, bool destroy);   // the communicator cache, further down
+}  // namespace
+
+namespace bb {
+namespace solver {
 
 constexpr int64_t kHistCap = 1 << 20;
-// 24-bit stream: a packable unit is stored packed only inside a run of at least this many
-// (docs/MEASUREMENTS.md, "fp32 sweep: the 24-bit stream")
-constexpr int64_t kPk24MinRun = 64;
 constexpr size_t kMaxTimedLaunches = 4096;
 
 // The kind / alpha rule of every set_wish_* entry point, in who's name.
@@ -194,208 +62,66 @@ int enable_peer_access(const char *who, int device) {
     return BB_OK;
 }
 
-// A create that failed with rc: tear down what there is, the failure's text staying the last
-// error across the tear-down.
-template <typename TearDown>
-int failed_create(int rc, TearDown &&tear_down) {
-    const std::string keep = bb_last_error();
-    tear_down();
-    bb::set_error(keep);
-    return rc;
-}
-
-// The peer arena's layout: 2 parities x world slots of data | per-rank flags | poison words.
-int64_t peer_flags_offset(const bb_solver *s) {
-    return 2 * (int64_t)s->world * s->peer_slot_elems * bb::elem_size(s->dtype);
-}
-// the one-launch exchange (reduce_exchange_kernel): one poison word per source rank behind
-// the per-rank flags of the two-launch form (its data words say by themselves whether they
-// have arrived)
-int64_t peer_xpoison_offset(const bb_solver *s) {
-    return peer_flags_offset(s) + bb::round_up((int64_t)s->world * 64, 256);
-}
-int64_t peer_arena_size(const bb_solver *s) {
-    return peer_xpoison_offset(s) + bb::round_up((int64_t)s->world * 64, 256);
-}
-
-// Waves per CU (4 waves = one workgroup).  Measured on MI355X: with the rolling
-// 8-KiB window one wave per SIMD already keeps enough bytes in flight, and fewer,
-// longer chunks mean fewer column-partial slots and less prologue per byte; two
-// waves per SIMD overlap one wave's VALU work with the other's waits.  With the
-// current kernel (profiles/archive/r01_sweep_wpc.txt): 8/CU is 2-4 % faster from ~150k units
-// per rank (N=24,926) up, 4 and 8 tie at 77k units (1/8 of the N=50k matrix, where
-// 4 means half as many column partials for the reduce), 6 is always worse (a
-// workgroup count that is not a multiple of the CU count), 16 is 2 % slower.
-// Round 3, with the one-launch reduce (whose time no longer grows with the number of
-// column slots) and by the kernel trace (tools/wpc_timeline.sh, profiles/r03_wpc_ab.txt): 8
-// per CU takes 110.3-111.9 us per iteration at N=17,700 against 116.3-116.5 with 4, and ties
-// at N=12,000 and 14,500: the switch is at 65k units (N ~ 16,200 on one rank).
-// BB_WAVES_PER_CU overrides.
-int waves_per_cu(int64_t n_local) {
-    const char *e = getenv("BB_WAVES_PER_CU");
-    int v = e ? atoi(e) : (n_local >= 65000 ? 8 : 4);
-    if (v < 1) v = 1;
-    if (v > 32) v = 32;
+// Every environment variable the solver reads, as they stand at the time of the call: at
+// bb_solver_create the knobs of the sweep plan (bb_solver_plan.h) and of the 24-bit stream, the
+// row-owner limit and the descriptor form; at bb_solver_peer_connect the peer ones.  THE place
+// the solver reads its environment.
+struct SolverEnv {
+    bb::SweepKnobs knobs;          // BB_WAVES_PER_CU, BB_PAIR, BB_REDUCE_SLICES
+    int pk_mode = -1;              // BB_PACK24: 0 never, 1 whenever a unit packs, unset: the rule
+    int64_t pk_min_run = bb::kPk24MinRun;           // BB_PACK24_MIN_RUN
+    // Largest map (bins) that iterates on the row-owner path.  Measured on MI355X
+    // (tools/small_n_timing.py, profiles/archive/r02_small_n.txt); 0 turns the path off.
+    int64_t row_owner_max = bb::kRowOwnerMaxBins;   // BB_ROW_OWNER_MAX
+    bool arith_desc = true;        // BB_ARITH_DESC=0: the sweep loads a wave's first descriptor
+    bool peer_mask = true;         // BB_PEER_MASK=0: all ranks send all blocks
+    long long peer_timeout_ms = 10000;              // BB_PEER_TIMEOUT_MS
+    int peer_fused = -1;           // BB_PEER_FUSED: 0 two launches, 1 one, unset (-1): by the GPUs
+};
+SolverEnv solver_env() {
+    SolverEnv v;
+    const auto off = [](const char *name) {   // set, and to 0
+        const char *e = getenv(name);
+        return e && atoi(e) == 0;
+    };
+    if (const char *e = getenv("BB_WAVES_PER_CU")) v.knobs.waves_per_cu = std::max(1, std::min(atoi(e), 32));
+    v.knobs.pair = !off("BB_PAIR");
+    if (const char *e = getenv("BB_REDUCE_SLICES")) v.knobs.reduce_slices = atoi(e) == 4 ? 4 : 8;
+    if (const char *e = getenv("BB_PACK24")) v.pk_mode = atoi(e) != 0 ? 1 : 0;
+    if (const char *e = getenv("BB_PACK24_MIN_RUN")) v.pk_min_run = std::max<int64_t>(1, atoll(e));
+    if (const char *e = getenv("BB_ROW_OWNER_MAX")) v.row_owner_max = atoll(e);
+    v.arith_desc = !off("BB_ARITH_DESC");
+    v.peer_mask = !off("BB_PEER_MASK");
+    if (const char *e = getenv("BB_PEER_TIMEOUT_MS"))
+        if (atoll(e) > 0) v.peer_timeout_ms = atoll(e);
+    if (const char *e = getenv("BB_PEER_FUSED")) v.peer_fused = atoi(e) != 0 ? 1 : 0;
     return v;
 }
 
-// Largest map (bins) that iterates on the row-owner path.  Measured on MI355X
-// (tools/small_n_timing.py, profiles/archive/r02_small_n.txt); BB_ROW_OWNER_MAX overrides,
-// 0 turns the path off.
-int64_t row_owner_max() {
-    const char *e = getenv("BB_ROW_OWNER_MAX");
-    return e ? atoll(e) : bb::kRowOwnerMaxBins;
-}
+static_assert(bb::row_trip_cols(BB_F32) == RowTrip<float>::COLS && bb::row_trip_cols(BB_F64) == RowTrip<double>::COLS,
+              "the plan's full_ld is a whole number of the row-owner kernel's trips");
 
-// Build every index the kernels need from (tile list, unit range).
-int build_indices(bb_solver *s) {
-    const int64_t upt = s->L.units_per_tile, vw = s->L.vw;
-    const int64_t ch = 3 * vw;
-    s->n_local = s->u_end - s->u_begin;
-    s->t_first = s->n_local > 0 ? s->u_begin / upt : 0;
-    const int64_t t_last = s->n_local > 0 ? (s->u_end - 1) / upt : -1;
-    s->n_local_tiles = s->n_local > 0 ? t_last - s->t_first + 1 : 0;
-
-    s->udesc.resize((size_t)std::max<int64_t>(s->n_local, 1));
-    for (int64_t ul = 0; ul < s->n_local; ++ul) {
-        const int64_t u = s->u_begin + ul, t = u / upt, sub = u % upt;
-        s->udesc[ul] = make_int2((int)(s->tile_I[t] * vw + sub * s->L.rows_per_unit),
-                                 (int)(s->tile_J[t] * vw));
-    }
-
+// Build every index the kernels need from (tile list, unit range): the plan (bb_solver_plan.h),
+// its copy in the handle, then the one allocation and the uploads.
+int build_indices(bb_solver *s, const bb::SweepKnobs &knobs) {
     int cus = 256;
     hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device);
-    int64_t want = (int64_t)cus * waves_per_cu(s->n_local);
-    int64_t nw = std::max<int64_t>(1, std::min<int64_t>(want, s->n_local));
-    {
-        // 8 waves per CU: put the two waves of a SIMD into one workgroup so that they can
-        // keep each other's pace (stress_grad_kernel, WPB = 8).  BB_PAIR=0 turns it off.
-        const char *e = getenv("BB_PAIR");
-        const bool pair = !(e && atoi(e) == 0);
-        s->wpb = (pair && (s->dtype == BB_F32 || s->wide) && waves_per_cu(s->n_local) >= 8 && nw >= 8)
-                     ? 8 : 4;
-    }
-    nw = bb::round_up(nw, s->wpb);
-    s->n_waves = (int)nw;
-
-    if (s->n_local >= ((int64_t)1 << 31))
-        return bb::fail(BB_ERR_INVALID, "bb_solver_create: more than 2^31 units on one rank");
-    // Matrix loads are non-temporal (measured: +2.5 % on the kernel, +9 % on a pure read
-    // sweep at N=50k) unless this rank's units fit the 256-MB Infinity Cache: then they
-    // are read again from it on the next iteration, and plain loads keep them there
-    // (N=8,000 / 10,000: kernel -8 %, step -3.5 / -6 %; equal at N=12,000 = 288 MB;
-    // non-temporal 3-4 % better at N=17,700; profiles/archive/r02_nt_ab.txt).
-    s->nontemporal = s->n_local * bb::kUnitBytes > ((int64_t)240 << 20);
-    {
-        // the 24-bit stream of the fp32 sweep (ensure_pk24): BB_PACK24=0 never, =1 whenever a
-        // unit packs; BB_PACK24_MIN_RUN: the shortest run of packable units stored packed
-        const char *e = getenv("BB_PACK24");
-        s->pk_mode = e ? (atoi(e) != 0 ? 1 : 0) : -1;
-        const char *r = getenv("BB_PACK24_MIN_RUN");
-        s->pk_min_run = r ? std::max<int64_t>(1, atoll(r)) : kPk24MinRun;
-    }
-    // wave w owns the contiguous chunk [w*q + min(w, r), +q (+1 if w < r)), q = n_local / nw,
-    // r = n_local % nw: the kernels compute it the same way (no table to load)
-    s->chunk_q = (int)(s->n_local / nw);
-    s->chunk_r = (int)(s->n_local % nw);
-    std::vector<int2> wave_range(nw);
-    int64_t chunk_max = 0;
-    for (int64_t w = 0; w < nw; ++w) {
-        const int64_t a = w * s->chunk_q + std::min<int64_t>(w, s->chunk_r);
-        wave_range[w] = make_int2((int)a, (int)(a + s->chunk_q + (w < s->chunk_r ? 1 : 0)));
-        chunk_max = std::max<int64_t>(chunk_max, wave_range[w].y - wave_range[w].x);
-    }
-    {
-        // fp32 / fp64 wide: a wave parks the row sums of (the last cap units of) its chunk
-        // in LDS until it has finished reading (stress_grad_kernel, DEFER); cap is what the
-        // workgroups sharing a CU can hold, 0 only on a rank without units.
-        const int64_t wgs_per_cu = std::max<int64_t>(1, (nw / s->wpb + cus - 1) / cus);
-        const int64_t budget = 156 * 1024 / wgs_per_cu;               // of the CU's 160 KiB
-        const int64_t cap = std::min<int64_t>(chunk_max, (budget / s->wpb - 16 - 8) / 48);
-        if ((s->dtype == BB_F32 || s->wide) && cap > 0) s->defer_cap_units = (int)cap;
-        // a wave's LDS region: the parked row sums while it sweeps, its last column partial
-        // (3 * vw elements) at the end; + the 8 progress words of a paired workgroup
-        const int64_t col_words = 3 * vw * bb::elem_size(s->dtype) / 4;
-        s->lds_wave_floats = (int)std::max<int64_t>((int64_t)s->defer_cap_units * 12 + 4, col_words);
-        s->defer_lds_bytes = (int64_t)s->wpb * s->lds_wave_floats * 4 + 32;
-    }
-    // Column-partial slots.  A wave's strips but the last get private slots (it writes them
-    // itself, mid-sweep: rare); the strip a wave ENDS in shares one slot with the other
-    // waves of its workgroup that end in the same strip (summed in LDS by the sweep's
-    // epilogue).
-    std::vector<int32_t> &slot_strip = s->slot_strip;
-    slot_strip.clear();
-    s->wave_last_strip.assign((size_t)nw, -1);
-    std::vector<int2> wave_slots(nw);
-    for (int64_t w = 0; w < nw; ++w) {
-        wave_slots[w] = make_int2((int)slot_strip.size(), -1);
-        if (wave_range[w].x >= wave_range[w].y) continue;           // no units
-        int cur = -1;
-        std::vector<int> strips;
-        for (int64_t ul = wave_range[w].x; ul < wave_range[w].y; ++ul) {
-            const int J = s->udesc[ul].y / (int)vw;
-            if (J != cur) { strips.push_back(J); cur = J; }
-        }
-        for (size_t q = 0; q + 1 < strips.size(); ++q) slot_strip.push_back(strips[q]);
-        const int Jlast = strips.back();
-        s->wave_last_strip[(size_t)w] = Jlast;
-        const bool same_wg = w % s->wpb != 0;
-        if (same_wg && wave_slots[w - 1].y >= 0 &&
-            slot_strip[(size_t)wave_slots[w - 1].y] == Jlast) {
-            wave_slots[w].y = wave_slots[w - 1].y;
-        } else {
-            wave_slots[w].y = (int)slot_strip.size();
-            slot_strip.push_back(Jlast);
-        }
-    }
-    s->n_slots = (int)slot_strip.size();
-    s->rowpart_elems = s->n_local_tiles * ch;
-    s->colpart_elems = (int64_t)s->n_slots * ch;
-
-    // reduce CSR: block b <- row chunks of local tiles with I == b, then column slots of strip b
-    const int64_t nb = s->L.n_blocks;
-    std::vector<int64_t> blk_ptr(nb + 1, 0);
-    for (int64_t lt = 0; lt < s->n_local_tiles; ++lt) blk_ptr[s->tile_I[s->t_first + lt] + 1]++;
-    for (int sl = 0; sl < s->n_slots; ++sl) blk_ptr[slot_strip[sl] + 1]++;
-    for (int64_t b = 0; b < nb; ++b) blk_ptr[b + 1] += blk_ptr[b];
-    std::vector<int64_t> blk_chunk((size_t)std::max<int64_t>(blk_ptr[nb], 1));
-    std::vector<int64_t> fill(blk_ptr.begin(), blk_ptr.end() - 1);
-    for (int64_t lt = 0; lt < s->n_local_tiles; ++lt)
-        blk_chunk[fill[s->tile_I[s->t_first + lt]]++] = lt * ch;
-    for (int sl = 0; sl < s->n_slots; ++sl)
-        blk_chunk[fill[slot_strip[sl]]++] = s->rowpart_elems + (int64_t)sl * ch;
-
-    // Reduce (reduce_sliced_kernel): every block's whole list in one table of fixed stride,
-    // padded with the offset of a chunk of zeros that sits behind the column partials; 4
-    // slices per workgroup while no list is longer than 64 chunks, else 8
-    int64_t longest = 0;
-    for (int64_t b = 0; b < nb; ++b) longest = std::max(longest, blk_ptr[b + 1] - blk_ptr[b]);
-    const int64_t zero_off = s->rowpart_elems + s->colpart_elems;
-    const int64_t part_total = zero_off + ch;
-    std::vector<int64_t> red_lists;
-    {
-        s->red_slices = longest <= 64 ? 4 : 8;
-        if (const char *f = getenv("BB_REDUCE_SLICES")) s->red_slices = atoi(f) == 4 ? 4 : 8;
-        const int64_t quantum = 16 * s->red_slices;
-        s->red_stride = (int)bb::round_up(std::max<int64_t>(longest, 1), quantum);
-        red_lists.assign((size_t)(nb * s->red_stride), zero_off);
-        for (int64_t b = 0; b < nb; ++b)
-            for (int64_t k = blk_ptr[b]; k < blk_ptr[b + 1]; ++k)
-                red_lists[(size_t)(b * s->red_stride + (k - blk_ptr[b]))] = blk_chunk[k];
-    }
-
-    const int64_t es = bb::elem_size(s->dtype);
+    bb::SweepPlan p;
+    BB_TRY(bb::sweep_plan("bb_solver_create", s->L, s->dtype, s->wide, s->tile_I.data(), s->tile_J.data(), s->u_begin, s->u_end,
+                          cus, knobs, &p));
+    s->n_local = p.n_local, s->t_first = p.t_first, s->n_local_tiles = p.n_local_tiles;
+    s->udesc = std::move(p.udesc);
+    s->n_waves = p.n_waves, s->wpb = p.wpb, s->chunk_q = p.chunk_q, s->chunk_r = p.chunk_r;
+    s->nontemporal = p.nontemporal;
+    s->defer_cap_units = p.defer_cap_units, s->lds_wave_floats = p.lds_wave_floats;
+    s->defer_lds_bytes = p.defer_lds_bytes;
+    s->slot_strip = std::move(p.slot_strip), s->wave_last_strip = std::move(p.wave_last_strip);
+    s->n_slots = p.n_slots, s->rowpart_elems = p.rowpart_elems, s->colpart_elems = p.colpart_elems;
+    s->red_slices = p.red_slices, s->red_stride = p.red_stride;
+    s->full_ld = p.full_ld, s->ro_wpr = p.ro_wpr, s->ro_blocks = p.ro_blocks;
     s->hist_cap = kHistCap;
-    if (s->row_owner) {
-        // a whole number of trips per row: 256 columns in fp32, 128 in fp64 (RowTrip<T>::COLS)
-        s->full_ld = bb::round_up(s->L.n_bins, s->dtype == BB_F32 ? RowTrip<float>::COLS
-                                                                  : RowTrip<double>::COLS);
-        // waves per row: enough of them that a small map still covers the chip with
-        // about 16 waves per CU (N=963: 4 per row)
-        s->ro_wpr = s->L.n_bins <= 1024 ? 4 : (s->L.n_bins <= 2048 ? 2 : 1);
-        const int rows_per_wg = 4 / s->ro_wpr;
-        s->ro_blocks = (int)((s->L.n_bins + rows_per_wg - 1) / rows_per_wg);
-    }
+
+    const int64_t es = bb::elem_size(s->dtype), nw = p.n_waves;
     {
         // ONE device allocation for everything the solver owns (the exchange buffer apart:
         // a caller may replace it).  Twenty hipMalloc + hipFree pairs were 3 of the 4.5 ms a
@@ -407,12 +133,12 @@ int build_indices(bb_solver *s) {
         add((char **)&s->d_units, std::max<int64_t>(s->n_local, 1) * bb::kUnitBytes);
         add((char **)&s->d_X, s->L.n_pad * 3 * es);
         add((char **)&s->d_V, s->L.n_pad * 3 * es);
-        add((char **)&s->d_part, part_total * es);
+        add((char **)&s->d_part, p.part_total * es);
         add(&s->d_udesc, (int64_t)s->udesc.size());
         add(&s->d_wave_slots, nw);
         add(&s->d_stresspart, nw);
         add(&s->d_stress_slot, std::max<int64_t>(s->n_slots, 1));
-        add(&s->d_red_lists, (int64_t)red_lists.size());
+        add(&s->d_red_lists, (int64_t)p.red_lists.size());
         add(&s->d_stress_hist, kHistCap);
         add(&s->d_stress_scalar, 1);
         add(&s->d_f64_tmp, s->L.n_pad * 3);
@@ -436,12 +162,12 @@ int build_indices(bb_solver *s) {
     hipStream_t st = s->stream;
     BB_HIP_CHECK(hipMemcpyAsync(s->d_udesc, s->udesc.data(), s->udesc.size() * sizeof(int2),
                                 hipMemcpyHostToDevice, st));
-    BB_HIP_CHECK(hipMemcpyAsync(s->d_wave_slots, wave_slots.data(), nw * sizeof(int2),
+    BB_HIP_CHECK(hipMemcpyAsync(s->d_wave_slots, p.wave_slots.data(), nw * sizeof(int2),
                                 hipMemcpyHostToDevice, st));
-    BB_HIP_CHECK(hipMemcpyAsync(s->d_red_lists, red_lists.data(),
-                                red_lists.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    BB_HIP_CHECK(hipMemcpyAsync(s->d_red_lists, p.red_lists.data(),
+                                p.red_lists.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
     // rows of boundary tiles owned by another rank are never written: keep them 0
-    BB_HIP_CHECK(hipMemsetAsync(s->d_part, 0, (size_t)part_total * es, st));
+    BB_HIP_CHECK(hipMemsetAsync(s->d_part, 0, (size_t)p.part_total * es, st));
     BB_HIP_CHECK(hipMemsetAsync(s->d_X, 0, (size_t)(s->L.n_pad * 3 * es), st));
     BB_HIP_CHECK(hipMemsetAsync(s->d_V, 0, (size_t)(s->L.n_pad * 3 * es), st));
     if (s->row_owner)
@@ -451,58 +177,14 @@ int build_indices(bb_solver *s) {
     // (shared slots -- the strip a wave ENDS in -- carry no stress of their own: they stay 0)
     BB_HIP_CHECK(hipMemsetAsync(s->d_stress_slot, 0,
                                 (size_t)std::max<int64_t>(s->n_slots, 1) * sizeof(double), st));
-    BB_HIP_CHECK(hipStreamSynchronize(st));  // the host vectors above die with this scope
+    BB_HIP_CHECK(hipStreamSynchronize(st));  // the plan's host vectors die with this scope
     return BB_OK;
 }
 
-// Which instantiation a launch takes.  The kernels exist for three layouts, (float, wide),
-// (double, wide) and (double, narrow) (bb::wide_layout): by_layout(s, f) calls
-// f(LayoutTag<T, W>{}) with the solver's, by_dtype(s, f) calls f(TypeTag<T>{}) where only the
-// element type matters.  with_int<V...>(v, f) calls f(std::integral_constant<int, V>{}) for
-// the first V equal to v, the last V standing for every other value.
-template <typename TT>
-struct TypeTag {
-    using T = TT;
-};
-template <typename TT, bool WW>
-struct LayoutTag {
-    using T = TT;
-    static constexpr bool W = WW;
-};
-
-template <typename F>
-decltype(auto) by_layout(const bb_solver *s, F &&f) {
-    if (s->dtype == BB_F32) return f(LayoutTag<float, true>{});
-    if (s->wide) return f(LayoutTag<double, true>{});
-    return f(LayoutTag<double, false>{});
-}
-
-template <typename F>
-decltype(auto) by_dtype(const bb_solver *s, F &&f) {
-    if (s->dtype == BB_F32) return f(TypeTag<float>{});
-    return f(TypeTag<double>{});
-}
-
-template <int V, int... Rest, typename F>
-decltype(auto) with_int(int v, F &&f) {
-    if constexpr (sizeof...(Rest) == 0) return f(std::integral_constant<int, V>{});
-    else return v == V ? f(std::integral_constant<int, V>{}) : with_int<Rest...>(v, f);
-}
-
-// The 24-bit stream pays only where it takes bytes off the sweep: its kernel carries a second
-// copy of the unit body and drains its window at every change of format (an all-zero packed
-// unit is a run of its own in the raw body), and a packed unit costs 15 more VALU instructions
-// than a raw one (383 against 368: 48 of decode, less the empty-pair mask a unit without a zero
-// does without; it was 52 more with the mask).  Below a saving of an eighth of the raw bytes
-// (all a sparse raw map with zeros in most units can offer is 0) the solver keeps reading
-// d_units with the kernel it always had.
-constexpr int64_t kPk24MinSavingDiv = 8;   // stream bytes <= raw bytes * (1 - 1/8)
-constexpr int64_t kPk24PackedKiB = 6, kPk24RawKiB = bb::kUnitBytes / 1024;
-
 // The stream up to date with d_units (SPEC 3.7), or pk_valid = false: the sweep then reads
 // d_units.  fp32 only; by default only where the sweep streams from HBM.  One pass for the
-// smallest and largest word of every unit, the run rule and the offsets on the host (one D2H
-// of 8 bytes per unit, once per map), one pass that writes the stream.
+// smallest and largest word of every unit, the run rule and the offsets on the host
+// (bb::pk24_table; one D2H of 8 bytes per unit, once per map), one pass that writes the stream.
 int ensure_pk24(bb_solver *s) {
     if (!s->pk_stale) return BB_OK;
     s->pk_stale = false, s->pk_valid = false;
@@ -526,44 +208,23 @@ int ensure_pk24(bb_solver *s) {
     BB_HIP_CHECK(hipMemcpyAsync(mm.data(), d_minmax.p, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost,
                                 s->stream));
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-    // packable: max - min < 2^24; stored packed: inside a run of >= pk_min_run packable units
-    std::vector<int4> table((size_t)n);
-    int64_t kib = 0, packed = 0, switches = 0;
-    for (int64_t a = 0; a < n;) {
-        const bool pk = mm[(size_t)a].y - mm[(size_t)a].x < (1u << 24);
-        int64_t b = a + 1;
-        while (b < n && (mm[(size_t)b].y - mm[(size_t)b].x < (1u << 24)) == pk) ++b;
-        const bool store_packed = pk && b - a >= s->pk_min_run;
-        for (int64_t u = a; u < b; ++u) {
-            table[(size_t)u] = make_int4(s->udesc[(size_t)u].x, s->udesc[(size_t)u].y,
-                                         (int)((uint32_t)kib | (store_packed ? 0x80000000u : 0u)),
-                                         store_packed ? (int)mm[(size_t)u].x : 0);
-            kib += store_packed ? kPk24PackedKiB : kPk24RawKiB;
-        }
-        if (store_packed) packed += b - a;
-        a = b;
-    }
-    for (int64_t u = 1; u < n; ++u) switches += (table[(size_t)u].z < 0) != (table[(size_t)u - 1].z < 0);
-    const int64_t raw_kib = n * kPk24RawKiB;
-    const bool pays = s->pk_mode == 1 ? packed > 0 : kib * kPk24MinSavingDiv <= raw_kib * (kPk24MinSavingDiv - 1);
-    if (!pays || kib >= ((int64_t)1 << 31)) {
-        s->pk_stream.reset(), s->pk_table.reset();
-        return BB_OK;
-    }
+    bb::Pk24Table t;
+    bb::pk24_table(mm.data(), s->udesc.data(), n, s->pk_min_run, s->pk_mode, &t);
     // 8 KiB behind the last unit: no refill address a body can form lies outside
-    if (s->pk_stream.reserve((size_t)(kib + kPk24RawKiB) * 1024) != hipSuccess ||
+    if (!t.pays || s->pk_stream.reserve((size_t)(t.kib + bb::kPk24RawKiB) * 1024) != hipSuccess ||
         s->pk_table.reserve((size_t)n * sizeof(int4)) != hipSuccess) {
         s->pk_stream.reset(), s->pk_table.reset();
         return BB_OK;                                                              // raw: no error
     }
-    BB_HIP_CHECK(hipMemcpyAsync(s->pk_table.p, table.data(), (size_t)n * sizeof(int4), hipMemcpyHostToDevice,
+    BB_HIP_CHECK(hipMemcpyAsync(s->pk_table.p, t.table.data(), (size_t)n * sizeof(int4), hipMemcpyHostToDevice,
                                 s->stream));
-    BB_HIP_CHECK(hipMemsetAsync(s->pk_stream.as<char>() + kib * 1024, 0, (size_t)kPk24RawKiB * 1024, s->stream));
+    BB_HIP_CHECK(hipMemsetAsync(s->pk_stream.as<char>() + t.kib * 1024, 0, (size_t)bb::kPk24RawKiB * 1024,
+                                s->stream));
     BB_HIP_CHECK(bb::launch(pk24_pack_kernel, dim3((unsigned)n), dim3(256), 0, s->stream,
                             (const uint4 *)s->d_units, s->pk_table.as<const int4>(), s->pk_stream.as<uint4>()));
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));   // the host table dies with this scope
     s->pk_valid = true;
-    s->pk_packed = packed, s->pk_bytes = kib * 1024, s->pk_switches = switches;
+    s->pk_packed = t.packed, s->pk_bytes = t.kib * 1024, s->pk_switches = t.switches;
     return BB_OK;
 }
 
@@ -620,11 +281,6 @@ int launch_sweep_op(L lay, bb_solver *s, const void *x_in) {
         });
     });
 }
-
-// What the reduce multiplies the summed partials by: 2 for the gradient (SPEC 2.3: the sweep
-// leaves half of it), 1 for a plain sum (the matvec of the spectral start) -- and only a
-// gradient takes the per-bin step factors (fill_reduce_params).
-constexpr double kScaleGradient = 2.0, kScalePlainSum = 1.0;
 
 template <typename T>
 void fill_reduce_params(bb_solver *s, ReduceParams<T> &p, int mode, double lr, double *stress_out,
@@ -705,7 +361,7 @@ int launch_reduce_t(LayoutTag<T, W>, bb_solver *s, int mode, double lr, double *
     });
 }
 
-int launch_grad(bb_solver *s, int op = kOpStress, const void *x_in = nullptr) {
+int launch_grad(bb_solver *s, int op, const void *x_in) {
     if (!x_in) x_in = s->d_X;
     // the stress and its gradient: weighted (SPEC 2.3.1) once a weight power is set
     if (op == kOpStress && s->weight_power != 0)
@@ -716,49 +372,11 @@ int launch_grad(bb_solver *s, int op = kOpStress, const void *x_in = nullptr) {
         });
     });
 }
-int launch_reduce(bb_solver *s, int mode, double lr, double *stress_out,
-                  double scale = kScaleGradient) {
+int launch_reduce(bb_solver *s, int mode, double lr, double *stress_out, double scale) {
     return by_layout(s, [&](auto lay) { return launch_reduce_t(lay, s, mode, lr, stress_out, scale); });
 }
-int launch_exchange(bb_solver *s, double lr, double *stress_out, double scale = kScaleGradient) {
+int launch_exchange(bb_solver *s, double lr, double *stress_out, double scale) {
     return by_layout(s, [&](auto lay) { return launch_exchange_t(lay, s, lr, stress_out, scale); });
-}
-
-// The landmark terms of SPEC 2.5.5 at the coordinates X (bb_anchor_kernels.h), behind a reduce
-// that has left its result: fold = kAnchorFoldExchange adds gradient and stress to the exchange
-// buffer (three launches), kAnchorFoldStress adds the stress to stress_out[0], kAnchorFoldAlone
-// leaves the anchor stress in anchor_part[0] alone (two launches: no gradient is formed).
-double *anchor_stress_ptr(const bb_solver *s) { return s->anchor_part.as<double>(); }
-double *anchor_node_part(const bb_solver *s) { return s->anchor_part.as<double>() + 8; }
-double *anchor_lm_part(const bb_solver *s) {
-    return anchor_node_part(s) + bb::round_up(s->anchor_node_blocks, 8);
-}
-int launch_anchors(bb_solver *s, int fold, double *stress_out = nullptr) {
-    return by_dtype(s, [&](auto t) {
-        using T = typename decltype(t)::T;
-        return with_int<1, 2, 0>(s->weight_power, [&](auto qc) -> int {
-            constexpr int Q = decltype(qc)::value;
-            const T *A = s->anchor_rows.as<const T>();
-            const int *nodes = s->anchor_nodes.as<const int>();
-            const T *bin_scale = s->d_bin_scale.as<const T>();
-            T *exch = fold == kAnchorFoldExchange ? (T *)s->d_exch : nullptr;
-            BB_HIP_CHECK(bb::launch(anchor_node_kernel<T, Q>, dim3((unsigned)s->anchor_node_blocks), dim3(256),
-                                    0, s->stream, A, s->L.n_pad, s->L.n_bins, s->anchor_n, nodes,
-                                    (const T *)s->d_X, exch, bin_scale, (T)s->anchor_weight,
-                                    anchor_node_part(s)));
-            if (fold == kAnchorFoldExchange)
-                BB_HIP_CHECK(bb::launch(anchor_landmark_kernel<T, Q>,
-                                        dim3((unsigned)s->anchor_chunks, (unsigned)s->anchor_n), dim3(256), 0,
-                                        s->stream, A, s->L.n_pad, s->L.n_bins, nodes, (const T *)s->d_X,
-                                        (T)s->anchor_weight, anchor_lm_part(s)));
-            const unsigned fold_grid = fold == kAnchorFoldExchange ? (unsigned)s->anchor_n : 1u;
-            BB_HIP_CHECK(bb::launch(anchor_fold_kernel<T>, dim3(fold_grid), dim3(256), 0, s->stream, fold,
-                                    (const double *)anchor_node_part(s), s->anchor_node_blocks,
-                                    (const double *)anchor_lm_part(s), s->anchor_chunks, nodes,
-                                    (T *)s->d_exch, bin_scale, s->L.n_pad, anchor_stress_ptr(s), stress_out));
-            return BB_OK;
-        });
-    });
 }
 
 // X <- X + V, V <- mu V - lr * exchange[0 : 3 n_pad]; the stress of the buffer to stress_out.
@@ -771,23 +389,6 @@ int launch_apply(bb_solver *s, double lr, double *stress_out) {
                                 stress_out));
         return BB_OK;
     });
-}
-
-// One iteration's two halves, sweep() and reduce(), with the timing events around them on
-// every timing_stride-th iteration while timing is on: ev[0] sweep ev[1] reduce ev[2].
-template <typename Sweep, typename Reduce>
-int timed_step(bb_solver *s, Sweep &&sweep, Reduce &&reduce) {
-    bb::Event *ev = nullptr;
-    if (s->timing && s->timing_iter++ % s->timing_stride == 0 && s->ev_used + 3 <= s->ev.size()) {
-        ev = &s->ev[s->ev_used];
-        s->ev_used += 3;
-    }
-    if (ev) BB_HIP_CHECK(hipEventRecord(ev[0], s->stream));
-    BB_TRY(sweep());
-    if (ev) BB_HIP_CHECK(hipEventRecord(ev[1], s->stream));
-    BB_TRY(reduce());
-    if (ev) BB_HIP_CHECK(hipEventRecord(ev[2], s->stream));
-    return BB_OK;
 }
 
 int check_ready(const bb_solver *s, const char *who) {
@@ -1025,10 +626,12 @@ int scatter_entries(bb_solver *s, const char *who, int64_t n, int64_t chunk, int
     return inputs_done(s);
 }
 
-}  // namespace
+}  // namespace solver
+}  // namespace bb
 
 // ---- peer exchange ---------------------------------------------------------
-namespace {
+namespace bb {
+namespace solver {
 
 // What travels between ranks: the IPC handle of the arena plus what is needed to
 // check that both sides agree on its shape (and to short-cut ranks that live in
@@ -1093,7 +696,8 @@ int build_peer_tables(TypeTag<T>, bb_solver *s) {
     return BB_OK;
 }
 
-}  // namespace
+}  // namespace solver
+}  // namespace bb
 
 extern "C" {
 
@@ -1117,7 +721,9 @@ int bb_solver_create(bb_solver **out, int64_t n_bins, int dtype, int device, int
     s->world = world;
     int rc = bb_layout_dense_info(n_bins, dtype, &s->L);
     s->wide = bb::wide_layout(dtype, n_bins);
-    s->row_owner = s->row_owner_built = world == 1 && n_bins <= row_owner_max();
+    const SolverEnv env = solver_env();
+    s->row_owner = s->row_owner_built = world == 1 && n_bins <= env.row_owner_max;
+    s->pk_mode = env.pk_mode, s->pk_min_run = env.pk_min_run;
     if (rc == BB_OK) {
         if (tile_I == nullptr) {
             s->tile_I.resize((size_t)s->L.n_tiles);
@@ -1125,18 +731,7 @@ int bb_solver_create(bb_solver **out, int64_t n_bins, int dtype, int device, int
             rc = bb_layout_dense_tiles(n_bins, dtype, s->tile_I.data(), s->tile_J.data(),
                                        s->L.n_tiles);
         } else {
-            // blocked-sparse: validate order (J, then I ascending; I <= J < n_blocks)
-            for (int64_t t = 0; t < n_tiles && rc == BB_OK; ++t) {
-                const bool in_range = tile_I[t] >= 0 && tile_I[t] <= tile_J[t] &&
-                                      tile_J[t] < s->L.n_blocks;
-                const bool ordered =
-                    t == 0 || tile_J[t] > tile_J[t - 1] ||
-                    (tile_J[t] == tile_J[t - 1] && tile_I[t] > tile_I[t - 1]);
-                if (!in_range || !ordered)
-                    rc = bb::fail(BB_ERR_INVALID,
-                                  "bb_solver_create: tile list must be strictly ordered by "
-                                  "(J, I) with 0 <= I <= J < n_blocks");
-            }
+            rc = bb::check_tile_list("bb_solver_create", s->L, tile_I, tile_J, n_tiles);
             s->tile_I.assign(tile_I, tile_I + n_tiles);
             s->tile_J.assign(tile_J, tile_J + n_tiles);
             s->L.n_tiles = n_tiles;
@@ -1144,10 +739,8 @@ int bb_solver_create(bb_solver **out, int64_t n_bins, int dtype, int device, int
         }
     }
     if (rc == BB_OK) rc = bb_layout_rank_units(s->L.n_units, rank, world, &s->u_begin, &s->u_end);
-    if (rc == BB_OK && tile_I == nullptr && s->u_end < ((int64_t)1 << 31)) {
-        const char *e = getenv("BB_ARITH_DESC");
-        if (!(e && atoi(e) == 0)) s->dense_u0 = (int)s->u_begin;
-    }
+    if (rc == BB_OK && tile_I == nullptr && s->u_end < ((int64_t)1 << 31) && env.arith_desc)
+        s->dense_u0 = (int)s->u_begin;
     if (rc == BB_OK) {
         hipError_t e = bb::acquire_stream(device, &s->stream);
         if (e != hipSuccess)
@@ -1155,7 +748,11 @@ int bb_solver_create(bb_solver **out, int64_t n_bins, int dtype, int device, int
         else
             s->own_stream = true;
     }
-    if (rc == BB_OK) rc = build_indices(s);
+    if (rc == BB_OK) {
+        bb::SweepKnobs knobs = env.knobs;
+        knobs.row_owner = s->row_owner;
+        rc = build_indices(s, knobs);
+    }
     if (rc != BB_OK) return failed_create(rc, [&] { bb_solver_destroy(s); });
     *out = s;
     return BB_OK;
@@ -1375,105 +972,6 @@ int bb_solver_weight_sums(bb_solver *s, double *sums, int64_t n_bins) {
     return BB_OK;
 }
 
-// SPEC 2.5.5: the solver's own resident copy of the kept rows of `paths`, in its dtype.  All of
-// the new state is built in locals and handed to the solver at the end: a refusal or a failed
-// allocation leaves the solver as it was.
-int bb_solver_set_anchors(bb_solver *s, const bb_paths *paths, const uint8_t *kept, double weight) {
-    const char *who = "bb_solver_set_anchors";
-    BB_REQUIRE(s != nullptr, "bb_solver_set_anchors: solver is NULL");
-    BB_REQUIRE(std::isfinite(weight) && weight >= 0.0,
-               "bb_solver_set_anchors: the weight must be finite and not negative");
-    if (s->grad_pending)
-        return bb::fail(BB_ERR_STATE, "bb_solver_set_anchors: a bb_solver_grad is pending");
-    BB_TRY(bb::enter_device(s->device));
-    if (paths == nullptr || weight == 0.0) {       // clear: every path is the unanchored one again
-        BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-        s->anchor_rows.reset(), s->anchor_nodes.reset(), s->anchor_part.reset();
-        s->anchor_n = 0, s->anchor_weight = 0.0, s->anchor_terms = 0;
-        s->anchor_chunks = s->anchor_node_blocks = 0;
-        return BB_OK;
-    }
-    if (s->world > 1)
-        return bb::fail(BB_ERR_STATE, "bb_solver_set_anchors: landmark anchors run on one rank "
-                                      "(world > 1: several devices are not covered)");
-    if (s->n_maps > 1)
-        return bb::fail(BB_ERR_STATE, "bb_solver_set_anchors: landmark anchors are for one map, not for "
-                                      "a solver of several maps (bb_solver_set_maps)");
-    BB_REQUIRE(paths->n_nodes == s->L.n_bins,
-               "bb_solver_set_anchors: the paths have " + std::to_string(paths->n_nodes) +
-                   " nodes, the solver " + std::to_string(s->L.n_bins) + " bins (n_nodes != n_bins)");
-    BB_REQUIRE(paths->device == s->device, "bb_solver_set_anchors: the paths live on another device");
-    std::vector<int> col, node;
-    for (int64_t a = 0; a < paths->n_sources; ++a)
-        if (kept == nullptr || kept[a]) {
-            col.push_back((int)a);
-            node.push_back((int)paths->sources[(size_t)a]);
-        }
-    BB_REQUIRE(!col.empty(), "bb_solver_set_anchors: fewer than 1 kept row");
-    BB_REQUIRE((int)col.size() <= kAnchorMaxRows, "bb_solver_set_anchors: too many kept rows");
-    {
-        std::vector<int> sorted(node);
-        std::sort(sorted.begin(), sorted.end());
-        BB_REQUIRE(std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end(),
-                   "bb_solver_set_anchors: two kept rows have the same source node");
-    }
-    const int n_rows = (int)col.size();
-    const int64_t es = bb::elem_size(s->dtype), n_pad = s->L.n_pad;
-    const int node_blocks = (int)((s->L.n_bins + 255) / 256);
-    const int chunks = (int)((s->L.n_bins + kAnchorChunk - 1) / kAnchorChunk);
-    const size_t rows_bytes = (size_t)n_rows * (size_t)n_pad * (size_t)es;
-    const size_t idx_bytes = bb::align256((size_t)n_rows * sizeof(int)) * 2 + 256;   // nodes | columns | count
-    const size_t part_bytes =
-        (size_t)(8 + bb::round_up(node_blocks, 8) + (int64_t)n_rows * chunks * 3) * sizeof(double);
-    size_t free_b = 0, total_b = 0;
-    BB_TRY(bb::hip_status(who, hipMemGetInfo(&free_b, &total_b)));
-    const std::string sizes = std::to_string(n_rows) + " rows of " + std::to_string(n_pad) + " values need " +
-                              std::to_string(rows_bytes) + " B and their sums " +
-                              std::to_string(part_bytes + idx_bytes) + " B; " + std::to_string(free_b) +
-                              " B are free";
-    if (rows_bytes + part_bytes + idx_bytes > free_b) return bb::fail(BB_ERR_NOMEM, std::string(who) + ": " + sizes);
-    bb::DevBuf rows, idx, part;
-    hipError_t e = rows.alloc(rows_bytes);
-    if (e == hipSuccess) e = idx.alloc(idx_bytes);
-    if (e == hipSuccess) e = part.alloc(part_bytes);
-    if (e != hipSuccess) return bb::fail(BB_ERR_NOMEM, std::string(who) + ": hipMalloc failed: " + sizes);
-    int *d_node = idx.as<int>();
-    int *d_col = (int *)((char *)idx.p + bb::align256((size_t)n_rows * sizeof(int)));
-    unsigned long long *d_terms = (unsigned long long *)((char *)d_col + bb::align256((size_t)n_rows * sizeof(int)));
-    unsigned long long terms = 0;
-    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-    BB_HIP_CHECK(hipMemcpy(d_node, node.data(), (size_t)n_rows * sizeof(int), hipMemcpyHostToDevice));
-    BB_HIP_CHECK(hipMemcpy(d_col, col.data(), (size_t)n_rows * sizeof(int), hipMemcpyHostToDevice));
-    BB_HIP_CHECK(hipMemsetAsync(d_terms, 0, sizeof(unsigned long long), s->stream));
-    BB_HIP_CHECK(hipMemsetAsync(part.p, 0, part_bytes, s->stream));
-    BB_TRY(by_dtype(s, [&](auto t) -> int {
-        using T = typename decltype(t)::T;
-        BB_HIP_CHECK(bb::launch(anchor_rows_kernel<T>, dim3((unsigned)(n_pad / 64), (unsigned)((n_rows + 63) / 64)),
-                                dim3(256), 0, s->stream, paths->D.as<const double>(), paths->ld,
-                                paths->n_nodes, n_pad, (const int *)d_col, n_rows, rows.as<T>(), d_terms));
-        return BB_OK;
-    }));
-    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-    BB_HIP_CHECK(hipMemcpy(&terms, d_terms, sizeof(terms), hipMemcpyDeviceToHost));
-    s->anchor_rows = std::move(rows);
-    s->anchor_nodes = std::move(idx);
-    s->anchor_part = std::move(part);
-    s->anchor_n = n_rows;
-    s->anchor_weight = weight;
-    s->anchor_terms = (int64_t)terms;
-    s->anchor_chunks = chunks;
-    s->anchor_node_blocks = node_blocks;
-    return BB_OK;
-}
-
-int bb_solver_anchor_info(const bb_solver *s, int64_t *kept_rows, int64_t *terms, int64_t *bytes) {
-    BB_REQUIRE(s != nullptr, "bb_solver_anchor_info: solver is NULL");
-    if (kept_rows) *kept_rows = s->anchor_n;
-    if (terms) *terms = s->anchor_terms;
-    if (bytes) *bytes = (int64_t)(s->anchor_rows.bytes + s->anchor_nodes.bytes + s->anchor_part.bytes);
-    return BB_OK;
-}
-
 int bb_solver_anchor_sums(bb_solver *s, double *sums, int64_t n_bins) {
     BB_REQUIRE(s != nullptr && sums != nullptr, "bb_solver_anchor_sums: NULL argument");
     BB_REQUIRE(n_bins == s->L.n_bins, "bb_solver_anchor_sums: one sum per bin");
@@ -1499,18 +997,6 @@ int bb_solver_anchor_sums(bb_solver *s, double *sums, int64_t n_bins) {
     }));
     BB_HIP_CHECK(hipStreamSynchronize(s->stream));
     BB_HIP_CHECK(hipMemcpy(sums, d_sum, (size_t)n_bins * sizeof(double), hipMemcpyDeviceToHost));
-    return BB_OK;
-}
-
-int bb_solver_anchor_stress(bb_solver *s, double *stress) {
-    BB_TRY(check_ready(s, "bb_solver_anchor_stress"));
-    BB_REQUIRE(stress != nullptr, "bb_solver_anchor_stress: stress is NULL");
-    *stress = 0.0;
-    if (s->anchor_n == 0) return BB_OK;
-    BB_TRY(bb::enter_device(s->device));
-    BB_TRY(launch_anchors(s, kAnchorFoldAlone));
-    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-    BB_HIP_CHECK(hipMemcpy(stress, anchor_stress_ptr(s), sizeof(double), hipMemcpyDeviceToHost));
     return BB_OK;
 }
 
@@ -2079,7 +1565,8 @@ int bb_solver_iterate_dist(bb_solver *s, int64_t iters, double lr) {
 
 }  // extern "C"
 
-namespace {
+namespace bb {
+namespace solver {
 // The receiving half of the two-launch peer exchange (peer_receive_kernel): wait for every
 // rank's flag of exchange `peer_seq`, X <- X + (mu V - lr * sum over the ranks in rank order).
 int launch_peer_receive(bb_solver *s, void *X, double lr, double mu, double *stress_out) {
@@ -2137,7 +1624,8 @@ int exchange_sum(bb_solver *s) {
     return bb::fail(BB_ERR_STATE, "no exchange between the ranks is set up (bb_solver_peer_connect "
                                   "or bb_solver_comm_init / _attach first)");
 }
-}  // namespace
+}  // namespace solver
+}  // namespace bb
 
 extern "C" {
 
@@ -2205,6 +1693,7 @@ int bb_solver_peer_connect(bb_solver *s, const void *handles) {
     if (!s->peer_arena) return bb::fail(BB_ERR_STATE, "bb_solver_peer_connect: export first");
     if (s->peer_connected) return bb::fail(BB_ERR_STATE, "bb_solver_peer_connect: already connected");
     BB_TRY(bb::enter_device(s->device));
+    const SolverEnv env = solver_env();
     s->peer_mapped.assign((size_t)s->world, nullptr);
     std::map<uint64_t, int> ranks_on_gpu;      // how many ranks sit on each GPU of the node
     int most_on_one_gpu = 1;
@@ -2243,9 +1732,8 @@ int bb_solver_peer_connect(bb_solver *s, const void *handles) {
         // receivers agree without a word exchanged.  Dense N=50,000 on 8 ranks: rank 0 touches
         // a third of the blocks (28 % fewer bytes on the links over all ranks); the whole genome
         // as blocks: a rank touches the blocks of a few chromosomes (BB_PEER_MASK=0: all send all).
-        const char *env = getenv("BB_PEER_MASK");
         s->d_peer_mask.reset();
-        if (!(env && atoi(env) == 0) && s->world <= 32) {
+        if (env.peer_mask && s->world <= 32) {
             std::vector<unsigned> mask;
             BB_TRY(contributor_mask(s, &mask));
             BB_TRY(bb::alloc_status(s->d_peer_mask, mask.size() * sizeof(unsigned)));
@@ -2268,12 +1756,7 @@ int bb_solver_peer_connect(bb_solver *s, const void *handles) {
         khz = 0;
     }
     s->peer_clock_khz = khz > 0 ? khz : 100000;
-    long long ms = 10000;
-    if (const char *env = getenv("BB_PEER_TIMEOUT_MS")) {
-        const long long v = atoll(env);
-        if (v > 0) ms = v;
-    }
-    s->peer_limit_ticks = ms * s->peer_clock_khz;
+    s->peer_limit_ticks = env.peer_timeout_ms * s->peer_clock_khz;
     s->peer_seq = 0;
     {
         // The one-launch exchange (reduce_exchange_kernel) has every workgroup wait for its
@@ -2285,8 +1768,7 @@ int bb_solver_peer_connect(bb_solver *s, const void *handles) {
         // handle (PCI ids), so all of them decide alike: any GPU with two ranks on it -- a
         // rehearsal -- and it is the two-launch form.  BB_PEER_FUSED=0|1 overrides (the same
         // on every rank; small problems on a shared GPU do run in one launch).
-        const char *env = getenv("BB_PEER_FUSED");
-        s->peer_fused = env ? atoi(env) != 0 : most_on_one_gpu == 1;
+        s->peer_fused = env.peer_fused >= 0 ? env.peer_fused != 0 : most_on_one_gpu == 1;
         s->peer_ranks_on_gpu = most_on_one_gpu;
         if (most_on_one_gpu > 1) s->pk_stale = true;   // a stream built before this goes (ensure_pk24)
     }
@@ -2636,30 +2118,6 @@ int bb_solver_measure_stream_read(bb_solver *s, int launches, double *ms_avg) {
     return BB_OK;
 }
 
-int bb_solver_measure_anchors(bb_solver *s, int launches, double *ms_avg) {
-    BB_TRY(check_ready(s, "bb_solver_measure_anchors"));
-    BB_REQUIRE(ms_avg != nullptr, "bb_solver_measure_anchors: ms_avg is NULL");
-    BB_REQUIRE(launches >= 1 && launches <= 1000, "bb_solver_measure_anchors: bad launches");
-    if (s->anchor_n == 0) return bb::fail(BB_ERR_STATE, "bb_solver_measure_anchors: no anchors set");
-    if (s->grad_pending)
-        return bb::fail(BB_ERR_STATE, "bb_solver_measure_anchors: a bb_solver_grad is pending");
-    BB_TRY(bb::enter_device(s->device));
-    bb::Event e0, e1;
-    BB_HIP_CHECK(e0.create());
-    BB_HIP_CHECK(e1.create());
-    // (the exchange buffer holds nothing anybody waits for: no gradient is pending)
-    BB_HIP_CHECK(hipMemsetAsync(s->d_exch, 0, (size_t)(3 * s->L.n_pad + 2) * bb::elem_size(s->dtype), s->stream));
-    BB_TRY(launch_anchors(s, kAnchorFoldExchange));   // warm-up
-    BB_HIP_CHECK(hipEventRecord(e0, s->stream));
-    for (int k = 0; k < launches; ++k) BB_TRY(launch_anchors(s, kAnchorFoldExchange));
-    BB_HIP_CHECK(hipEventRecord(e1, s->stream));
-    BB_HIP_CHECK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    BB_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    *ms_avg = ms / launches;
-    return BB_OK;
-}
-
 int bb_solver_stream_info(bb_solver *s, int64_t *packed_units, int64_t *raw_units, int64_t *stream_bytes,
                           int64_t *format_switches) {
     BB_REQUIRE(s != nullptr, "bb_solver_stream_info: solver is NULL");
@@ -2690,435 +2148,6 @@ int bb_solver_traffic(bb_solver *s, int64_t *unit_bytes, int64_t *pairs_dense) {
     }
     if (unit_bytes) *unit_bytes = s->pk_valid && !s->pk_stale ? s->pk_bytes : s->n_local * bb::kUnitBytes;
     if (pairs_dense) *pairs_dense = s->L.n_bins * (s->L.n_bins - 1) / 2;
-    return BB_OK;
-}
-
-}  // extern "C"
-
-// ---- spectral start, device resident ---------------------------------------------
-namespace {
-
-// small dense helpers on the host (3 x 3, row-major)
-void jacobi3(double *a, double *z) {   // a symmetric 3 x 3 -> eigenvalues on its diagonal, vectors in z
-    for (int q = 0; q < 9; ++q) z[q] = (q % 4 == 0) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 50; ++sweep) {
-        const double off = a[1] * a[1] + a[2] * a[2] + a[5] * a[5];
-        if (off < 1e-300) break;
-        for (int p = 0; p < 3; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-                const double apq = a[p * 3 + q];
-                if (apq == 0.0) continue;
-                const double theta = (a[q * 3 + q] - a[p * 3 + p]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-                for (int k = 0; k < 3; ++k) {
-                    const double akp = a[k * 3 + p], akq = a[k * 3 + q];
-                    a[k * 3 + p] = c * akp - sn * akq;
-                    a[k * 3 + q] = sn * akp + c * akq;
-                }
-                for (int k = 0; k < 3; ++k) {
-                    const double apk = a[p * 3 + k], aqk = a[q * 3 + k];
-                    a[p * 3 + k] = c * apk - sn * aqk;
-                    a[q * 3 + k] = sn * apk + c * aqk;
-                }
-                for (int k = 0; k < 3; ++k) {
-                    const double zkp = z[k * 3 + p], zkq = z[k * 3 + q];
-                    z[k * 3 + p] = c * zkp - sn * zkq;
-                    z[k * 3 + q] = sn * zkp + c * zkq;
-                }
-            }
-    }
-}
-
-template <typename T>
-int spectral_init_t(TypeTag<T>, bb_solver *s, int n_iter, const double *v0, double tol, int *iters_done,
-                    double *residual_out) {
-    const int64_t n = s->L.n_bins, n_pad = s->L.n_pad, n3 = n_pad * 3;
-    if (!s->d_mv_in) BB_TRY(bb::alloc_status(s->d_mv_in, (size_t)n3 * sizeof(T)));
-    // V, Z: (n_pad,3) doubles; dS: 12 sums (the two host steps at the end); dP0 / dP1: the
-    // per-workgroup partial sums a pass leaves for the next one (two buffers: a pass reads its
-    // producer's while it writes its own); dF: rank-loss flag
-    bb::DevBuf bV, bZ, bS, bP, bF;
-    if (bV.alloc((size_t)n3 * 8) != hipSuccess || bZ.alloc((size_t)n3 * 8) != hipSuccess ||
-        bS.alloc(24 * 8) != hipSuccess || bP.alloc((size_t)2 * kSpMaxGroups * 12 * 8) != hipSuccess ||
-        bF.alloc(sizeof(int)) != hipSuccess)
-        return bb::fail(BB_ERR_NOMEM, "bb_solver_spectral_init: out of device memory");
-    double *dV = (double *)bV.p, *dZ = (double *)bZ.p, *dS = (double *)bS.p;
-    double *dP0 = (double *)bP.p, *dP1 = dP0 + kSpMaxGroups * 12;
-    int *dF = (int *)bF.p;
-    hipStream_t st = s->stream;
-    const dim3 gvec((unsigned)((n_pad + kSpWG - 1) / kSpWG)), bwg(kSpWG);
-    const int groups = (int)std::min<int64_t>(kSpMaxGroups, (n_pad + kSpWG - 1) / kSpWG);
-    const dim3 ggrp((unsigned)groups);
-    const Affine3 ident = {{0, 0, 0}, {1, 0, 0, 0, 1, 0, 0, 0, 1}, 1.0};
-    double sums[12];
-    auto fetch_sums = [&]() -> int {
-        BB_HIP_CHECK(hipStreamSynchronize(st));
-        BB_HIP_CHECK(hipMemcpy(sums, dS, sizeof(sums), hipMemcpyDeviceToHost));
-        return BB_OK;
-    };
-    // dZ (any basis of the subspace, its 12 sums in dP1) -> dV orthonormal by Cholesky-QR, twice
-    // (the second pass removes what the first leaves at cond(Z)^2 * eps), and the sweep's
-    // right-hand sides d_mv_in = (T)(V - mean V): two kernels, the 3 x 3 steps in their prologues
-    auto orthonormalise = [&]() -> int {
-        BB_HIP_CHECK(bb::launch(sp_affine_stats_kernel<double>, ggrp, bwg, 0, st, (const double *)dZ, dV,
-                                n, n_pad, (const double *)dP1, groups, (int)kSpChol, 1.0, dF, dP0));
-        BB_HIP_CHECK(bb::launch(sp_affine_centre_kernel<T>, gvec, bwg, 0, st, (const double *)dV, dV,
-                                s->d_mv_in.as<T>(), n, n_pad, (const double *)dP0, groups, dF));
-        return BB_OK;
-    };
-    // dZ = -1/2 J (D o D) J V  (J = I - 11'/n) from the centred V in d_mv_in: sweep, sum over
-    // the ranks, centre; the 12 sums of dZ are left in dP1
-    auto apply_B = [&]() -> int {
-        BB_TRY(launch_grad(s, kOpMatvec2, s->d_mv_in.p));
-        BB_TRY(exchange_sum(s));
-        BB_HIP_CHECK(bb::launch(sp_stats_kernel<T>, ggrp, bwg, 0, st, (const T *)s->d_exch, n, n_pad, dP0));
-        BB_HIP_CHECK(bb::launch(sp_affine_stats_kernel<T>, ggrp, bwg, 0, st, (const T *)s->d_exch, dZ, n,
-                                n_pad, (const double *)dP0, groups, (int)kSpMean, -0.5, dF, dP1));
-        return BB_OK;
-    };
-    BB_HIP_CHECK(hipMemsetAsync(dF, 0, sizeof(int), st));
-    BB_HIP_CHECK(hipMemsetAsync(s->d_V, 0, (size_t)n3 * sizeof(T), st));   // exchange_sum reads it
-    BB_HIP_CHECK(upload_padded(s, dZ, v0, st));
-    BB_HIP_CHECK(bb::launch(sp_stats_kernel<double>, ggrp, bwg, 0, st, (const double *)dZ, n, n_pad, dP1));
-    BB_TRY(orthonormalise());
-    // tol > 0: after every product but the first (a random V cannot have converged), the
-    // relative distance of Z = B V from span(V), ||Z - V (V^T Z)||_F / ||Z||_F -- from the
-    // Gram matrix V^T Z and the sums of Z^T Z the product left in dP1: V is orthonormal, so
-    // the squared distance is ||Z||_F^2 - ||V^T Z||_F^2 (the difference of two sums resolves
-    // a ratio down to about 1e-7).  Below tol the loop ends; the product just made is the
-    // Rayleigh-Ritz step's.  Costs two small kernels and a read of 24 doubles per product.  Every
-    // rank holds the same V and Z bit for bit (the summed products are identical on all
-    // ranks), so all ranks leave at the same product.
-    double zsums[12];
-    double residual = -1.0;
-    int done = 0;
-    bool have_product = false;
-    for (int it = 0; it < n_iter; ++it) {
-        BB_TRY(apply_B());
-        if (tol > 0.0 && it > 0) {
-            BB_HIP_CHECK(bb::launch(gram3_kernel<double, double>, dim3(1), dim3(1024), 0, st,
-                                    (const double *)dV, (const double *)dZ, n, dS));
-            BB_HIP_CHECK(bb::launch(sp_fold_partials_kernel, dim3(1), dim3(64), 0, st,
-                                    (const double *)dP1, groups, dS + 12));
-            BB_TRY(fetch_sums());
-            BB_HIP_CHECK(hipMemcpy(zsums, dS + 12, sizeof(zsums), hipMemcpyDeviceToHost));
-            double gg = 0.0;
-            const double zz = zsums[0] + zsums[4] + zsums[8];
-            for (int q = 0; q < 9; ++q) gg += sums[q] * sums[q];
-            residual = zz > 0.0 ? sqrt(std::max(0.0, zz - gg) / zz) : 0.0;
-            if (residual < tol) { have_product = true; break; }
-        }
-        BB_TRY(orthonormalise());
-        done = it + 1;
-    }
-    if (iters_done) *iters_done = done;
-    if (residual_out) *residual_out = residual;
-    // Rayleigh-Ritz on span(V): M = sym(V^T B V), X0 = V E sqrt(max(lambda, 0)).  From here on
-    // the host takes part: three reads of 12 doubles for the whole start.
-    if (!have_product) {
-        BB_TRY(apply_B());
-        BB_HIP_CHECK(bb::launch(gram3_kernel<double, double>, dim3(1), dim3(1024), 0, st,
-                                (const double *)dV, (const double *)dZ, n, dS));
-        BB_TRY(fetch_sums());
-    }
-    int lost = 0;
-    BB_HIP_CHECK(hipMemcpy(&lost, dF, sizeof(int), hipMemcpyDeviceToHost));
-    if (lost)
-        return bb::fail(BB_ERR_STATE, "bb_solver_spectral_init: the iterate lost rank "
-                                      "(fewer than 3 independent directions in the map)");
-    double m[9], z[9];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) m[i * 3 + j] = 0.5 * (sums[i * 3 + j] + sums[j * 3 + i]);
-    jacobi3(m, z);
-    int order[3] = {0, 1, 2};
-    std::sort(order, order + 3, [&](int a, int b) { return m[a * 4] > m[b * 4]; });
-    // An eigenvector's sign is arbitrary: every Ritz vector V z_c is turned to the side of
-    // the start's first column p (p . V z_c >= 0), as solver.py's spectral_init does, so one
-    // seed gives one start whichever of the two computed it.
-    BB_HIP_CHECK(upload_padded(s, dZ, v0, st));
-    BB_HIP_CHECK(bb::launch(gram3_kernel<double, double>, dim3(1), dim3(1024), 0, st, (const double *)dV,
-                            (const double *)dZ, n, dS));
-    BB_TRY(fetch_sums());                                  // sums[r * 3 + 0] = V[:, r] . p
-    Affine3 f = ident;
-    for (int c = 0; c < 3; ++c) {
-        const double lam = m[order[c] * 4] > 0.0 ? m[order[c] * 4] : 0.0;
-        double side = 0.0;
-        for (int r = 0; r < 3; ++r) side += z[r * 3 + order[c]] * sums[r * 3];
-        const double sg = side < 0.0 ? -1.0 : 1.0;
-        for (int r = 0; r < 3; ++r) f.m[r * 3 + c] = sg * z[r * 3 + order[c]] * sqrt(lam);
-    }
-    BB_HIP_CHECK(bb::launch(affine3_kernel<double, T>, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0,
-                            st, (const double *)dV, (T *)s->d_X, n, n_pad, f));
-    BB_HIP_CHECK(hipMemsetAsync(s->d_V, 0, (size_t)n3 * sizeof(T), st));
-    BB_HIP_CHECK(hipStreamSynchronize(st));
-    return BB_OK;
-}
-
-}  // namespace
-
-extern "C" int bb_solver_spectral_init_tol(bb_solver *s, int n_iter, double tol, const double *v0,
-                                           int *iters_done, double *residual);
-extern "C" int bb_solver_spectral_init(bb_solver *s, int n_iter, const double *v0) {
-    return bb_solver_spectral_init_tol(s, n_iter, 0.0, v0, nullptr, nullptr);
-}
-extern "C" int bb_solver_spectral_init_tol(bb_solver *s, int n_iter, double tol, const double *v0,
-                                           int *iters_done, double *residual) {
-    BB_REQUIRE(s != nullptr && v0 != nullptr, "bb_solver_spectral_init: NULL argument");
-    BB_REQUIRE(n_iter >= 0 && n_iter <= 100000, "bb_solver_spectral_init: bad n_iter");
-    BB_REQUIRE(tol >= 0.0 && tol < 1.0, "bb_solver_spectral_init: need 0 <= tol < 1");
-    if (!s->have_wish) return bb::fail(BB_ERR_STATE, "bb_solver_spectral_init: no wish distances set");
-    if (s->world != 1 && !s->peer_connected && !s->comm)
-        return bb::fail(BB_ERR_STATE, "bb_solver_spectral_init: with world > 1 the ranks need their "
-                                      "exchange first (bb_solver_peer_connect, or bb_solver_comm_init "
-                                      "/ _attach); without one the caller sums bb_solver_matvec_sq "
-                                      "over the ranks");
-    if (s->grad_pending)
-        return bb::fail(BB_ERR_STATE, "bb_solver_spectral_init: a bb_solver_grad is pending");
-    if (s->n_maps > 1)
-        return bb::fail(BB_ERR_STATE, "bb_solver_spectral_init: not for a solver of several maps "
-                                      "(start each map with a solver of its own)");
-    BB_REQUIRE(s->L.n_bins >= 3, "bb_solver_spectral_init: needs at least 3 bins");
-    BB_TRY(bb::enter_device(s->device));
-    BB_TRY(by_dtype(s, [&](auto t) { return spectral_init_t(t, s, n_iter, v0, tol, iters_done, residual); }));
-    s->have_coords = true;
-    s->hist_n = 0;
-    s->grad_pending = false;
-    return BB_OK;
-}
-
-// ---- groups: several solvers of ONE process, one host thread each (bb_group_*) ----------
-// The exchange of a group is ordered by HIP events alone: no kernel waits for another, so
-// members may share a GPU (and its hardware queues) in any number.  DESIGN.md 6.9.
-namespace {
-
-constexpr int kGroupAborted = -1;   // a member that left because another one failed
-
-}  // namespace
-
-struct bb_group {
-    std::vector<bb_solver *> m;         // member r = rank r of world m.size()
-    std::vector<void *> exch;           // the members' exchange buffers the tables point to
-    std::vector<bb::DevBuf> d_src;      // per member, on its device: the R exchange pointers
-    std::vector<bb::DevBuf> d_mask;     // per member, on its device: block -> contributing ranks (unsigned)
-    std::vector<bb::Event> ready, applied;
-    std::vector<std::thread> threads;
-    // one job at a time, handed to the threads under `mu`
-    std::mutex mu;
-    std::condition_variable cv_job, cv_done;
-    uint64_t job = 0;
-    int done = 0;
-    bool quit = false;
-    int64_t iters = 0;
-    double lr = 0.0;
-    bb::GroupBarrier bar;
-    std::vector<int> rc;
-    std::vector<std::string> err;
-};
-
-namespace {
-
-// Steps 1-2 of an iteration on member r's stream: wait until every member has applied the
-// previous step (its group_apply_kernel read this member's partial: WAR), grad, "ready".
-int group_grad(bb_group *g, int r) {
-    bb_solver *s = g->m[(size_t)r];
-    for (const bb::Event &e : g->applied) BB_HIP_CHECK(hipStreamWaitEvent(s->stream, e, 0));
-    BB_TRY(launch_grad(s));
-    BB_TRY(launch_reduce(s, kReduceExchange, 0.0, nullptr));
-    if (s->anchor_n > 0) BB_TRY(launch_anchors(s, kAnchorFoldExchange));   // (a group of one: world 1)
-    BB_HIP_CHECK(hipEventRecord(g->ready[(size_t)r], s->stream));
-    return BB_OK;
-}
-
-// Step 4: wait for every member's partial, sum in rank order and step, "applied".
-int group_apply(bb_group *g, int r) {
-    bb_solver *s = g->m[(size_t)r];
-    for (const bb::Event &e : g->ready) BB_HIP_CHECK(hipStreamWaitEvent(s->stream, e, 0));
-    const int64_t n3 = s->L.n_pad * 3;
-    const dim3 grid((unsigned)((n3 + 255) / 256)), block(256);
-    const int world = (int)g->m.size(), ch = (int)(3 * s->L.vw);
-    double *hist = s->d_stress_hist + s->hist_n;
-    BB_TRY(by_dtype(s, [&](auto t) -> int {
-        using T = typename decltype(t)::T;
-        BB_HIP_CHECK(bb::launch(group_apply_kernel<T>, grid, block, 0, s->stream, (T *)s->d_X, (T *)s->d_V,
-                                g->d_src[(size_t)r].as<const T *const>(), world, n3, (T)g->lr, (T)s->momentum,
-                                hist, g->d_mask[(size_t)r].as<unsigned>(), ch));
-        return BB_OK;
-    }));
-    BB_HIP_CHECK(hipEventRecord(g->applied[(size_t)r], s->stream));
-    s->hist_n++;
-    return BB_OK;
-}
-
-// One member's share of a bb_group_iterate.  The barriers put every record of an event before
-// every wait that refers to it; a member that fails to enqueue makes all of them leave at the
-// next barrier, before anybody waits on something it will not record.
-int group_run(bb_group *g, int r) {
-    static_assert(BB_OK == 0, "bb::group_steps takes 0 for success");
-    return bb::group_steps(g->bar, g->iters, bb::enter_device(g->m[(size_t)r]->device),
-                           kGroupAborted, [&](int64_t) { return group_grad(g, r); },
-                           [&](int64_t) { return group_apply(g, r); });
-}
-
-void group_worker(bb_group *g, int r) {
-    (void)hipSetDevice(g->m[(size_t)r]->device);
-    uint64_t seen = 0;
-    for (;;) {
-        {
-            std::unique_lock<std::mutex> lk(g->mu);
-            g->cv_job.wait(lk, [&] { return g->quit || g->job != seen; });
-            if (g->quit) return;
-            seen = g->job;
-        }
-        const int rc = group_run(g, r);
-        std::lock_guard<std::mutex> lk(g->mu);
-        g->rc[(size_t)r] = rc;
-        g->err[(size_t)r] = rc > 0 ? std::string(bb_last_error()) : std::string();
-        if (++g->done == (int)g->m.size()) g->cv_done.notify_all();
-    }
-}
-
-void group_free(bb_group *g) {
-    {
-        std::lock_guard<std::mutex> lk(g->mu);
-        g->quit = true;
-    }
-    g->cv_job.notify_all();
-    for (std::thread &t : g->threads) t.join();
-    for (size_t r = 0; r < g->m.size(); ++r) {
-        hipSetDevice(g->m[r]->device);
-        hipStreamSynchronize(g->m[r]->stream);
-        // (each is made or empty: a setup that failed half way leaves the rest empty)
-        g->ready[r].reset();
-        g->applied[r].reset();
-        g->d_src[r].reset();
-        g->d_mask[r].reset();
-    }
-    delete g;
-    (void)hipGetLastError();
-}
-
-int group_setup(bb_group *g) {
-    const int n = (int)g->m.size();
-    // peer access between every pair of DISTINCT devices (a repeated device needs none)
-    for (int a = 0; a < n; ++a)
-        for (int b = 0; b < n; ++b) {
-            const int da = g->m[(size_t)a]->device, db = g->m[(size_t)b]->device;
-            if (da == db) continue;
-            int can = 0;
-            BB_HIP_CHECK(hipDeviceCanAccessPeer(&can, da, db));
-            if (!can)
-                return bb::fail(BB_ERR_HIP, "bb_group_create: device " + std::to_string(da) +
-                                                " has no peer access to device " + std::to_string(db));
-            BB_TRY(bb::enter_device(da));
-            BB_TRY(enable_peer_access("bb_group_create: hipDeviceEnablePeerAccess", db));
-        }
-    std::vector<unsigned> mask;
-    BB_TRY(contributor_mask(g->m[0], &mask));
-    for (int r = 0; r < n; ++r) {
-        bb_solver *s = g->m[(size_t)r];
-        BB_TRY(bb::enter_device(s->device));
-        BB_HIP_CHECK(hipStreamSynchronize(s->stream));
-        BB_TRY(bb::alloc_status(g->d_src[(size_t)r], n * sizeof(void *)));
-        BB_HIP_CHECK(hipMemcpy(g->d_src[(size_t)r].p, g->exch.data(), n * sizeof(void *),
-                               hipMemcpyHostToDevice));
-        BB_TRY(bb::alloc_status(g->d_mask[(size_t)r], mask.size() * sizeof(unsigned)));
-        BB_HIP_CHECK(hipMemcpy(g->d_mask[(size_t)r].p, mask.data(), mask.size() * sizeof(unsigned),
-                               hipMemcpyHostToDevice));
-        BB_HIP_CHECK(g->ready[(size_t)r].create(hipEventDisableTiming));
-        BB_HIP_CHECK(g->applied[(size_t)r].create(hipEventDisableTiming));
-        // recorded once, so that the first iteration's waits refer to a completed record
-        BB_HIP_CHECK(hipEventRecord(g->applied[(size_t)r], s->stream));
-        BB_HIP_CHECK(hipEventRecord(g->ready[(size_t)r], s->stream));
-    }
-    for (int r = 0; r < n; ++r) {
-        try {
-            g->threads.emplace_back(group_worker, g, r);
-        } catch (...) {
-            return bb::fail(BB_ERR_NOMEM, "bb_group_create: cannot start a host thread");
-        }
-    }
-    return BB_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int bb_group_create(bb_group **out, bb_solver *const *members, int n) {
-    BB_REQUIRE(out != nullptr && members != nullptr, "bb_group_create: NULL argument");
-    *out = nullptr;
-    BB_REQUIRE(n >= 1 && n <= kMaxPeers, "bb_group_create: need 1 <= n <= 16 members");
-    for (int r = 0; r < n; ++r) {
-        const bb_solver *s = members[r];
-        const bb_solver *s0 = members[0];
-        if (!s) return bb::fail(BB_ERR_INVALID, "bb_group_create: member " + std::to_string(r) + " is NULL");
-        if (s->rank != r || s->world != n)
-            return bb::fail(BB_ERR_INVALID, "bb_group_create: member " + std::to_string(r) +
-                                                " is rank " + std::to_string(s->rank) + " of world " +
-                                                std::to_string(s->world) + "; member r must be rank r "
-                                                "of world " + std::to_string(n));
-        if (s->L.n_bins != s0->L.n_bins)
-            return bb::fail(BB_ERR_INVALID, "bb_group_create: member " + std::to_string(r) +
-                                                " has n_bins " + std::to_string(s->L.n_bins) +
-                                                ", member 0 " + std::to_string(s0->L.n_bins));
-        if (s->dtype != s0->dtype)
-            return bb::fail(BB_ERR_INVALID, "bb_group_create: member " + std::to_string(r) +
-                                                " has another dtype than member 0");
-        if (s->tile_I != s0->tile_I || s->tile_J != s0->tile_J)
-            return bb::fail(BB_ERR_INVALID, "bb_group_create: member " + std::to_string(r) +
-                                                " has another tile list than member 0");
-        if (s->n_maps > 1)
-            return bb::fail(BB_ERR_INVALID, "bb_group_create: member " + std::to_string(r) +
-                                                " is a solver of several maps");
-    }
-    bb_group *g = new (std::nothrow) bb_group();
-    if (!g) return bb::fail(BB_ERR_NOMEM, "bb_group_create: out of host memory");
-    g->m.assign(members, members + n);
-    for (bb_solver *s : g->m) g->exch.push_back(s->d_exch);
-    g->d_src.resize((size_t)n);
-    g->d_mask.resize((size_t)n);
-    g->ready.resize((size_t)n);
-    g->applied.resize((size_t)n);
-    g->rc.assign((size_t)n, BB_OK);
-    g->err.assign((size_t)n, std::string());
-    g->bar.n = n;
-    const int rc = group_setup(g);
-    if (rc != BB_OK) return failed_create(rc, [&] { group_free(g); });
-    *out = g;
-    return BB_OK;
-}
-
-int bb_group_iterate(bb_group *g, int64_t iters, double lr) {
-    BB_REQUIRE(g != nullptr, "bb_group_iterate: group is NULL");
-    for (size_t r = 0; r < g->m.size(); ++r) {
-        bb_solver *s = g->m[r];
-        BB_TRY(check_iterate(s, iters, "bb_group_iterate"));
-        if (s->grad_pending)
-            return bb::fail(BB_ERR_STATE, "bb_group_iterate: member " + std::to_string(r) +
-                                              " has a bb_solver_grad pending");
-        if (s->d_exch != g->exch[r])
-            return bb::fail(BB_ERR_STATE, "bb_group_iterate: member " + std::to_string(r) +
-                                              " changed its exchange buffer after bb_group_create");
-    }
-    if (iters == 0) return BB_OK;
-    std::unique_lock<std::mutex> lk(g->mu);
-    g->iters = iters;
-    g->lr = lr;
-    g->done = 0;
-    std::fill(g->rc.begin(), g->rc.end(), BB_OK);
-    ++g->job;
-    g->cv_job.notify_all();
-    g->cv_done.wait(lk, [&] { return g->done == (int)g->m.size(); });
-    for (size_t r = 0; r < g->m.size(); ++r)
-        if (g->rc[r] > 0)
-            return bb::fail(g->rc[r], "bb_group_iterate: member " + std::to_string(r) + ": " + g->err[r]);
-    return BB_OK;
-}
-
-int bb_group_destroy(bb_group *g) {
-    if (!g) return BB_OK;
-    group_free(g);
     return BB_OK;
 }
 

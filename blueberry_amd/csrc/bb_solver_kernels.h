@@ -1,204 +1,21 @@
-// bb_solver_kernels.h -- device code of the 3D-structure solver (gfx950 only): the
-// stress + gradient sweep, the deterministic partial reduce (+ update / exchange /
-// peer push), the update kernels, the pack kernels and the read-only sweep used for
-// measurement.  Included by bb_solver.hip (the host side and the C-ABI) and by nothing
-// else: everything here lives in that translation unit's anonymous namespace.
+// bb_solver_kernels.h -- device code of the core of the 3D-structure solver (gfx950 only): the
+// stress + gradient sweep, the deterministic partial reduce (+ update / exchange / peer push),
+// the update kernels, the pack kernels of the input routes, the row-owner kernel, the 24-bit
+// stream's pack kernels, the read-only sweeps used for measurement and the f64 <-> T
+// conversions.  Included by bb_solver.hip and by nothing else: everything here lives in that translation unit's
+// anonymous namespace.  Shapes, wave helpers and shared constants: bb_solver_device.h.
 //
 // Specification: docs/SPEC.md (build-authored; the reference has no solver,
 // SURVEY.md section 0).  Data layout and kernel design: DESIGN.md 3-4.
-//
-// Layout recap (SPEC 3).  The matrix is cut into vw x vw tiles (vw = 512 columns;
-// 128 for small fp64 problems, see Lay<> below), upper-triangular tiles only, ordered
-// column-strip major (J, then I).  A tile is vw/rpu "units"; a unit is rpu matrix rows
-// x vw columns = 8 KiB, row-major (fp32: 4 rows of 2 KiB; fp64: 2 rows of 4 KiB, or 8
-// rows of 1 KiB).
-// One wave reads a matrix row of a unit with LPR 16-B-per-lane loads and lane
-// l always owns the same LPR*VPL columns of the strip.  That makes the column
-// side of the symmetric update register-resident for a whole strip sweep (no
-// cross-lane traffic), and only the row side needs one DPP wave reduction per
-// matrix row -- amortised over 8 pairs per lane in fp32.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <type_traits>
-
-#include "bb_wish.h"
-#include "blueberry_hip.h"
+#include "bb_solver_device.h"
 
 namespace {
-
-
-// --------------------------------------------------------------------------
-// type traits
-// --------------------------------------------------------------------------
-template <typename T>
-struct Traits;
-template <>
-struct Traits<float> {
-    using Vec = float4;
-    static constexpr int VPL = 4;  // elements per lane per 16-B load
-    static __device__ __forceinline__ float eps2() { return 1e-30f; }
-};
-template <>
-struct Traits<double> {
-    using Vec = double2;
-    static constexpr int VPL = 2;
-    static __device__ __forceinline__ double eps2() { return 1e-300; }
-};
-
-// The wish floor and ceiling, the flush and the value rule: bb_wish.h (shared with the
-// shortest paths over triples).
-using bb::flush_wish;
-using bb::wish_ceiling;
-using bb::wish_floor;
-using bb::wish_from_value;
-
-// Shape of a unit (8 KiB = 8 wave-loads) and of a strip.  LPR 16-byte loads per lane
-// and matrix row, VW = 64 * VPL * LPR columns per strip, RPU = 8 / LPR matrix rows.
-//   fp32          4 rows x 512 columns: 8 pairs per lane and row, packed math
-//   fp64 wide     2 rows x 512 columns: also 8 pairs per lane and row, so the DPP
-//                 reduction, the row-coordinate fetch and the row-sum stores are
-//                 amortised over 4x more pairs than in the narrow shape (+40 % at
-//                 N=20k); 96 VGPRs of column state, so at most 2 waves per SIMD
-//   fp64 narrow   8 rows x 128 columns: 4x smaller column partials and 4x more
-//                 blocks for the reduce -- what small problems want (N=963: 14.5 us
-//                 per iteration against 26 us in the wide shape); bb_common.h picks
-//                 it for n_bins <= kF64WideFrom
-template <typename T, bool W>
-struct Lay;
-template <bool W>
-struct Lay<float, W> {
-    static constexpr int LPR = 2, VW = 512, RPU = 4;
-    static constexpr int MIN_WG = 4;            // __launch_bounds__: <= 128 VGPRs
-    static constexpr bool SCALAR_XROW = true;   // 12 row coordinates through the scalar cache
-};
-template <>
-struct Lay<double, true> {
-    static constexpr int LPR = 4, VW = 512, RPU = 2;
-    static constexpr int MIN_WG = 2;            // <= 256 VGPRs
-    static constexpr bool SCALAR_XROW = true;   // 6 doubles = 12 SGPRs, double-buffered
-};
-template <>
-struct Lay<double, false> {
-    static constexpr int LPR = 1, VW = 128, RPU = 8;
-    // <= 256 VGPRs.  This shape only ever runs one workgroup of 4 waves per CU (at most 4096
-    // bins: fewer than 65k units, waves_per_cu() = 4), so a cap of 128 registers bought no
-    // occupancy and, from round 3 on, cost a 20-byte scratch spill in the stress sweep
-    // (tests/test_host.py::test_product_kernels_do_not_spill guards against the next one).
-    static constexpr int MIN_WG = 2;
-    static constexpr bool SCALAR_XROW = false;  // 24 doubles x 2 would not fit the SGPR file:
-                                                // one per-lane load + v_readlane instead
-};
-
-// --------------------------------------------------------------------------
-// cross-lane helpers (wave64, DPP; no LDS)
-// --------------------------------------------------------------------------
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_get(float v) {
-    return __int_as_float(
-        __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xF, false));
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_get(double v) {
-    int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xF, false);
-    int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-
-// Sum over the 64 lanes; the total is valid in lanes 48..63 (we read lane 63).
-// Fixed tree => bitwise deterministic.
-template <typename T>
-__device__ __forceinline__ T wave_sum_hi(T v) {
-    v += dpp_get<0xB1, 0xF>(v);   // quad_perm [1,0,3,2]
-    v += dpp_get<0x4E, 0xF>(v);   // quad_perm [2,3,0,1]
-    v += dpp_get<0x141, 0xF>(v);  // row_half_mirror
-    v += dpp_get<0x140, 0xF>(v);  // row_mirror
-    v += dpp_get<0x142, 0xA>(v);  // row_bcast15 -> rows 1,3
-    v += dpp_get<0x143, 0xC>(v);  // row_bcast31 -> rows 2,3
-    return v;
-}
-
-// The same tree for three fp32 values at once, as one asm block.  Interleaving
-// the three chains puts two independent VALU ops between every write of a
-// register and its next DPP read, which is exactly the 2 wait states that
-// hazard needs (the compiler serialises the chains and pads each step with
-// s_nop), and the two row_bcast steps become single v_add_f32_dpp with a
-// partial row_mask (disabled rows keep their value) instead of mov+mov+add.
-// Only the leading s_nop is needed: the inputs were just written by VALU code.
-__device__ __forceinline__ void wave_sum_hi3(float &a, float &b, float &c) {
-    asm("s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %2, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %2, %2, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %1, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %2, %2, %2 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %1, %1, %1 row_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %2, %2, %2 row_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-        "v_add_f32_dpp %1, %1, %1 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-        "v_add_f32_dpp %2, %2, %2 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-        "v_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-        "v_add_f32_dpp %1, %1, %1 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-        "v_add_f32_dpp %2, %2, %2 row_bcast:31 row_mask:0xc bank_mask:0xf"
-        : "+v"(a), "+v"(b), "+v"(c));
-}
-__device__ __forceinline__ void wave_sum_hi3(double &a, double &b, double &c) {
-    a = wave_sum_hi(a);
-    b = wave_sum_hi(b);
-    c = wave_sum_hi(c);
-}
-
-// Value of `v` in lane `l` (compile-time l) as a wave-uniform scalar.
-__device__ __forceinline__ float lane_value(float v, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ double lane_value(double v, int l) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-
-// Branch-free "lane 63 only" store of a row's three sums through a raw buffer
-// descriptor: every other lane carries an out-of-range offset and the
-// hardware range check drops its store.  (An `if (lane == 63)` around a plain
-// store splits the unit into basic blocks, and LLVM then sinks all column-side
-// accumulation below the last of them, spilling 32 pairs of forces.)
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned kDropOffset = 0x80000000u;
-
-__device__ __forceinline__ void store_row3(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, double a,
-                                           double b, double c) {
-    u32x4 v = {(unsigned)__double2loint(a), (unsigned)__double2hiint(a),
-               (unsigned)__double2loint(b), (unsigned)__double2hiint(b)};
-    u32x2 w = {(unsigned)__double2loint(c), (unsigned)__double2hiint(c)};
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b64(w, rsrc, voff + 16, 0, 0);
-}
 
 // --------------------------------------------------------------------------
 // stress + gradient kernel
 // --------------------------------------------------------------------------
-// What the sweep computes per pair (i, j), template parameter OP:
-//   kOpStress : residual force of SPEC 2.3 -> gradient (row and column side) + stress
-//   kOpMatvec2: y_i += delta_ij^2 * x_j and y_j += delta_ij^2 * x_i for three
-//               right-hand sides held in the coordinate slots: Y = (D o D) X, the
-//               kernel of classical-MDS / spectral initialisation
-//   kOpStressW1, kOpStressW2: the weighted stress of SPEC 2.3.1, w = delta^-1 (Sammon) or
-//               delta^-2 (relative stress); r = 1/delta is computed in-kernel from the delta
-//               the sweep loads anyway (no extra bytes), and masked where delta = 0
-enum { kOpStress = 0, kOpMatvec2 = 1, kOpStressW1 = 2, kOpStressW2 = 3 };
-template <int OP>
-constexpr bool is_weighted_op() { return OP == kOpStressW1 || OP == kOpStressW2; }
-
 // 1/sqrt(d2) and sqrt(d2) in fp64 from the v_rsq_f64 seed (relative error <= 2^-23) by ONE
 // third-order step: with e = 1 - d2 r0^2, r = r0 (1 - e)^(-1/2) = r0 (1 + e/2 + 3 e^2/8 + ...);
 // the term dropped is 5 e^3 / 16 < 1e-20, so both results are good to the last bit or two.
@@ -880,37 +697,6 @@ __global__ __launch_bounds__(64 * WPB, (WPB == 8 ? 2 : 1)) void stream24_grad_ke
 // --------------------------------------------------------------------------
 // reduce (+ update) kernel: one workgroup per vw-bin block
 // --------------------------------------------------------------------------
-enum ReduceMode {
-    kReduceApply = 0,      // X -= lr * 2 * sum
-    kReduceExchange = 1,   // exch = 2 * sum (+ stress hi/lo)
-    kReduceStressOnly = 2, // stress only
-    kReducePeer = 4        // 2 * sum (+ stress hi/lo) stored into this rank's slot on every peer
-};
-
-// Peer exchange (bb_solver_peer_*): where this rank's partial goes on each rank
-// (its slot in that rank's receive arena, for one parity) and the flag to raise.
-constexpr int kMaxPeers = 16;
-template <typename T>
-struct PeerTable {
-    T *dst[kMaxPeers];
-    unsigned long long *flag[kMaxPeers];
-};
-// Health of this rank's peer exchange, in device memory.  `status` is sticky: once a
-// wait has failed (time limit, or a peer reported its own failure) every later launch
-// of this rank leaves X alone and pushes nothing.  `verdict` is the sequence number of
-// the last exchange whose R partials all arrived, `decided` that of the last launch whose
-// wait has ended either way: both written by ONE wave (the first of peer_receive_kernel);
-// the other workgroups of that launch poll `decided`, then read `verdict`, so a step is
-// applied by all of its workgroups or by none.
-struct PeerState {
-    int status;
-    int pad;
-    unsigned long long verdict;
-    unsigned long long decided;   // sequence number of the last launch whose wait has ended, either way
-};
-// Flag value a failed rank leaves on every peer: their waits end at once and fail too.
-constexpr unsigned long long kPeerPoison = ~0ull;
-
 template <typename T>
 struct ReduceParams {
     const T *__restrict__ part;              // rowpart | colpart | a chunk of zeros
@@ -968,69 +754,6 @@ __device__ __forceinline__ double stress_share(const ReduceParams<T> &p, int m, 
 }
 
 constexpr int kRedWG = 128;  // elements a reduce workgroup sums
-
-// SPEC 2.4: V <- mu V - lr g ; X <- X + V   (mu = 0: X -= lr g).  The new velocity; for element
-// o with the old values xo, vo at hand (the reduces load them early, independent of the sum);
-// in place.  row_owner_kernel writes X to a second buffer, three elements at a time: it takes
-// the velocities and stores for itself.
-template <typename T>
-__device__ __forceinline__ T momentum_velocity(T mu, T vo, T lr, T g) { return mu * vo - lr * g; }
-template <typename T>
-__device__ __forceinline__ void momentum_step(T *__restrict__ X, T *__restrict__ V, int64_t o, T xo, T vo,
-                                              T mu, T lr, T g) {
-    const T v = momentum_velocity(mu, vo, lr, g);
-    V[o] = v;
-    X[o] = xo + v;
-}
-template <typename T>
-__device__ __forceinline__ void momentum_step(T *__restrict__ X, T *__restrict__ V, int64_t o, T mu, T lr,
-                                              T g) {
-    const T vo = V[o];
-    momentum_step(X, V, o, X[o], vo, mu, lr, g);
-}
-
-// The sum over ranks of N elements, in rank order from 0 (part of the specification: every
-// transport gives the same bits).  Eight ranks at a time: the words of all N elements are
-// requested before the first add -- one memory round trip per eight ranks, not one per rank and
-// element -- and a rank outside an element's mask mk[q] adds 0.  load(q, r): rank r's word of
-// element q, asked for only where live[q] and the rank is in the mask.
-template <int N, typename T, typename L>
-__device__ __forceinline__ void rank_ordered_sums(T (&g)[N], const bool (&live)[N],
-                                                  const unsigned (&mk)[N], int world, L load) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) g[q] = T(0);
-    for (int r0 = 0; r0 < world; r0 += 8) {
-        T v[N][8];
-#pragma unroll
-        for (int q = 0; q < N; ++q)
-#pragma unroll
-            for (int p = 0; p < 8; ++p)
-                v[q][p] = (live[q] && r0 + p < world && (mk[q] >> (r0 + p) & 1u)) ? load(q, r0 + p) : T(0);
-#pragma unroll
-        for (int q = 0; q < N; ++q)
-#pragma unroll
-            for (int p = 0; p < 8; ++p)
-                if (r0 + p < world) g[q] += v[q][p];
-    }
-}
-
-// The stress travels in the solver's type as a pair: hi = (T)S, lo = (T)(S - hi).
-template <typename T>
-__device__ __forceinline__ void split_hi_lo(double S, T &hi, T &lo) {
-    hi = (T)S;
-    lo = (T)(S - (double)hi);
-}
-
-// sh[0] <- sh[0] + ... + sh[n - 1] by a fixed tree (bitwise reproducible); n = the workgroup's
-// threads, a power of two.  Called by every thread, behind the barrier that follows its own
-// store to sh[tid].
-__device__ __forceinline__ void lds_tree_fold(double *sh, int tid, int n) {
-    for (int off = n >> 1; off > 0; off >>= 1) {
-        if (tid < off) sh[tid] += sh[tid + off];
-        __syncthreads();
-    }
-}
-
 
 // ---- the reduce in ONE launch of one memory round trip (round 3) ------------------
 // Round 2's reduce walked a block's list with one thread per element: a list of L chunks was
@@ -1211,12 +934,6 @@ __global__ __launch_bounds__(128 * S) void reduce_sliced_kernel(ReduceParams<T> 
 // Unlike the two-launch form this one can fail PARTIALLY (some 64-element pieces of the
 // step applied, others not): the status is sticky, bb_solver_peer_status reports it, and the
 // coordinates of a failed solver are not a result.
-template <typename T>
-struct PeerTableX {
-    T *dst[kMaxPeers];                       // this rank's slot in rank q's arena (one parity)
-    unsigned long long *poison[kMaxPeers];   // this rank's poison word in rank q's arena
-};
-
 __device__ __forceinline__ bool peer_word_empty(float v) { return __float_as_uint(v) == 0xffffffffu; }
 __device__ __forceinline__ bool peer_word_empty(double v) { return __double_as_longlong(v) == -1ll; }
 __device__ __forceinline__ float peer_empty_word(float) { return __uint_as_float(0xffffffffu); }
@@ -1481,33 +1198,6 @@ __global__ __launch_bounds__(256) void apply_kernel(T *__restrict__ X, T *__rest
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e < n3) momentum_step(X, V, e, mu, lr, exch[e]);
     if (e == 0 && stress_out) *stress_out = (double)exch[n3] + (double)exch[n3 + 1];
-}
-
-// ---- the event-ordered exchange of a group (bb_group_*: several solvers of ONE process) ----
-// src[r] (a device-side table, local or peer pointers) is member r's exchange buffer
-// [g (n_pad,3) | stress hi | lo], left there by bb_solver_grad's reduce: the same partial the
-// peer-mode reduce pushes (scale and per-bin factor applied the same way).  The host has
-// ordered this launch behind every member's grad by events, so nothing here waits or polls.
-// Per element: the sum over members is peer_receive_kernel's (rank_ordered_sums: member order
-// from 0, a masked-out member adds 0), then V <- mu V - lr g, X <- X + V.  The stress: (hi, lo)
-// summed in double, in order.
-template <typename T>
-__global__ __launch_bounds__(256) void group_apply_kernel(
-    T *__restrict__ X, T *__restrict__ V, const T *const *__restrict__ src, int world, int64_t n3,
-    T lr, T mu, double *__restrict__ stress_out, const unsigned *__restrict__ peer_mask, int ch) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e < n3) {
-        const unsigned mk[1] = {peer_mask != nullptr ? peer_mask[e / ch] : ~0u};
-        const bool live[1] = {true};
-        T g[1];
-        rank_ordered_sums(g, live, mk, world, [&](int, int r) { return src[r][e]; });
-        momentum_step(X, V, e, mu, lr, g[0]);
-    }
-    if (e == 0) {
-        double S = 0.0;
-        for (int r = 0; r < world; ++r) S += (double)src[r][n3] + (double)src[r][n3 + 1];
-        *stress_out = S;
-    }
 }
 
 // --------------------------------------------------------------------------
@@ -2111,269 +1801,46 @@ __global__ __launch_bounds__(256, 4) void stream_read_pk24_kernel(const float4 *
 }
 
 // --------------------------------------------------------------------------
-// spectral start on the device (bb_solver_spectral_init): the N x 3 side of the block
-// power iteration.  All of it is O(N): one workgroup, fixed-order sums.
+// landmark constraints (SPEC 2.5.5), the step quantities only: per bin, lambda * sum of A^-Q
+// over the terms that touch it (bb_solver_anchor_sums; A as in bb_anchor_kernels.h)
 // --------------------------------------------------------------------------
-// out[0..8] = A^T B (3 x 3) and out[9..11] = column sums of A, over n rows of (n,3) arrays
-template <typename TA, typename TB>
-__global__ __launch_bounds__(1024) void gram3_kernel(const TA *__restrict__ A,
-                                                     const TB *__restrict__ B, int64_t n,
-                                                     double *__restrict__ out) {
-    __shared__ double sh[12][16];
-    double acc[12];
-#pragma unroll
-    for (int q = 0; q < 12; ++q) acc[q] = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += 1024) {
-        const double a0 = (double)A[3 * i], a1 = (double)A[3 * i + 1], a2 = (double)A[3 * i + 2];
-        const double b0 = (double)B[3 * i], b1 = (double)B[3 * i + 1], b2 = (double)B[3 * i + 2];
-        acc[0] = fma(a0, b0, acc[0]); acc[1] = fma(a0, b1, acc[1]); acc[2] = fma(a0, b2, acc[2]);
-        acc[3] = fma(a1, b0, acc[3]); acc[4] = fma(a1, b1, acc[4]); acc[5] = fma(a1, b2, acc[5]);
-        acc[6] = fma(a2, b0, acc[6]); acc[7] = fma(a2, b1, acc[7]); acc[8] = fma(a2, b2, acc[8]);
-        acc[9] += a0; acc[10] += a1; acc[11] += a2;
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < 12; ++q) {
-        double v = acc[q];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if (lane == 0) sh[q][wv] = v;
-    }
+// Why here and not with the other landmark kernels: lds_tree_fold is inlined after the
+// compiler has looked at all of its callers in the translation unit.  Beside the reduce (n =
+// 512, 1024) the fold of 256 below keeps its generic last step; in a unit whose every caller
+// passes 256 that step is folded to constants, and the kernel is no longer the instructions it
+// was.  It stays with the reduce so that splitting the sources changed no kernel.
+template <typename T, int Q>
+__device__ __forceinline__ double anchor_weight(T v) {
+    const double d = (double)v;
+    if (!(d > 0.0)) return 0.0;
+    return Q == 0 ? 1.0 : (Q == 1 ? 1.0 / d : 1.0 / (d * d));
+}
+// node side: sums[v] = lambda * sum_a w(A[a][v]), a ascending
+template <typename T, int Q>
+__global__ __launch_bounds__(256) void anchor_sums_node_kernel(const T *__restrict__ A, int64_t n_pad,
+                                                               int64_t n_bins, int n_rows, double lam,
+                                                               double *__restrict__ sums) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= n_bins) return;
+    double acc = 0.0;
+    for (int a = 0; a < n_rows; ++a) acc += anchor_weight<T, Q>(A[(int64_t)a * n_pad + v]);
+    sums[v] = lam * acc;
+}
+// landmark side, one workgroup per landmark, launched behind the node side: thread t adds nodes
+// t, t + 256, ... in order, the threads meet in the fixed tree, sums[s_a] += lambda * the total
+template <typename T, int Q>
+__global__ __launch_bounds__(256) void anchor_sums_landmark_kernel(const T *__restrict__ A, int64_t n_pad,
+                                                                   int64_t n_bins,
+                                                                   const int *__restrict__ nodes, double lam,
+                                                                   double *__restrict__ sums) {
+    __shared__ double sh[256];
+    const int tid = threadIdx.x, a = blockIdx.x;
+    double acc = 0.0;
+    for (int64_t v = tid; v < n_bins; v += 256) acc += anchor_weight<T, Q>(A[(int64_t)a * n_pad + v]);
+    sh[tid] = acc;
     __syncthreads();
-    if (threadIdx.x < 12) {
-        double v = 0.0;
-        for (int k = 0; k < 16; ++k) v += sh[threadIdx.x][k];
-        out[threadIdx.x] = v;
-    }
-}
-
-// out_i = scale * ((in_i - mean) M), rows i < n_bins; M is 3 x 3 row-major; rows beyond
-// n_bins (padding) are written as 0.  The 12 numbers travel as kernel arguments.
-struct Affine3 {
-    double mean[3], m[9], scale;
-};
-template <typename TI, typename TO>
-__global__ __launch_bounds__(256) void affine3_kernel(const TI *__restrict__ in, TO *__restrict__ out,
-                                                      int64_t n_bins, int64_t n_pad, Affine3 a) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_pad) return;
-    double o0 = 0.0, o1 = 0.0, o2 = 0.0;
-    if (i < n_bins) {
-        const double x0 = (double)in[3 * i] - a.mean[0], x1 = (double)in[3 * i + 1] - a.mean[1],
-                     x2 = (double)in[3 * i + 2] - a.mean[2];
-        o0 = a.scale * (x0 * a.m[0] + x1 * a.m[3] + x2 * a.m[6]);
-        o1 = a.scale * (x0 * a.m[1] + x1 * a.m[4] + x2 * a.m[7]);
-        o2 = a.scale * (x0 * a.m[2] + x1 * a.m[5] + x2 * a.m[8]);
-    }
-    out[3 * i] = (TO)o0; out[3 * i + 1] = (TO)o1; out[3 * i + 2] = (TO)o2;
-}
-
-// ---- the same N x 3 algebra WITHOUT a host round trip (round 4) -------------------------
-// bb_solver_spectral_init used to read 12 sums back four times per product (centre, centre,
-// two Cholesky-QR passes): four stream synchronisations around a sweep that takes 0.1 ms on a
-// 1/8 share.  Now the 3 x 3 work stays on the device: every pass over an (n,3) array is ONE
-// kernel that leaves the 12 sums of its OUTPUT (Gram matrix + column sums) as per-workgroup
-// partials, and the NEXT pass adds them in a fixed order and does the 3 x 3 step (mean, or
-// Cholesky factor and its inverse) in its own prologue.  A factor that is not positive definite
-// (the iterate lost rank) raises a flag the host reads once, at the end.  Sums are in double,
-// fixed order: bitwise reproducible, and identical on every rank of a multi-rank start.
-constexpr int kSpWG = 256;          // threads per workgroup of the passes
-constexpr int kSpMaxGroups = 256;   // partials per pass
-
-// rows [r0, r1) of workgroup g of G over n_pad rows
-__device__ __forceinline__ void sp_rows(int64_t n_pad, int64_t &r0, int64_t &r1) {
-    const int64_t per = (n_pad + gridDim.x - 1) / gridDim.x;
-    r0 = (int64_t)blockIdx.x * per;
-    r1 = r0 + per < n_pad ? r0 + per : n_pad;
-}
-// the workgroup's 12 sums -> partial[blockIdx.x * 12 ..]: lanes by shuffle, waves through LDS
-__device__ __forceinline__ void sp_store_partial(double (&acc)[12], double *__restrict__ partial) {
-    __shared__ double sh[12][kSpWG / 64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < 12; ++q) {
-        double v = acc[q];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if (lane == 0) sh[q][wv] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 12) {
-        double v = 0.0;
-#pragma unroll
-        for (int k = 0; k < kSpWG / 64; ++k) v += sh[threadIdx.x][k];
-        partial[(int64_t)blockIdx.x * 12 + threadIdx.x] = v;
-    }
-}
-__device__ __forceinline__ void sp_accumulate(double (&acc)[12], double a0, double a1, double a2) {
-    acc[0] = fma(a0, a0, acc[0]); acc[1] = fma(a0, a1, acc[1]); acc[2] = fma(a0, a2, acc[2]);
-    acc[3] = fma(a1, a0, acc[3]); acc[4] = fma(a1, a1, acc[4]); acc[5] = fma(a1, a2, acc[5]);
-    acc[6] = fma(a2, a0, acc[6]); acc[7] = fma(a2, a1, acc[7]); acc[8] = fma(a2, a2, acc[8]);
-    acc[9] += a0; acc[10] += a1; acc[11] += a2;
-}
-
-// partial sums of in^T in and of in's columns (rows < n_bins)
-template <typename TI>
-__global__ __launch_bounds__(kSpWG) void sp_stats_kernel(const TI *__restrict__ in, int64_t n_bins,
-                                                         int64_t n_pad, double *__restrict__ partial) {
-    int64_t r0, r1;
-    sp_rows(n_pad, r0, r1);
-    double acc[12];
-#pragma unroll
-    for (int q = 0; q < 12; ++q) acc[q] = 0.0;
-    for (int64_t i = r0 + threadIdx.x; i < r1 && i < n_bins; i += kSpWG)
-        sp_accumulate(acc, (double)in[3 * i], (double)in[3 * i + 1], (double)in[3 * i + 2]);
-    sp_store_partial(acc, partial);
-}
-
-// the 12 sums themselves (groups added in order), for the stopping rule's one small read-back
-__global__ __launch_bounds__(64) void sp_fold_partials_kernel(const double *__restrict__ partial,
-                                                              int groups, double *__restrict__ out) {
-    if (threadIdx.x >= 12) return;
-    double v = 0.0;
-    for (int g = 0; g < groups; ++g) v += partial[(int64_t)g * 12 + threadIdx.x];
-    out[threadIdx.x] = v;
-}
-
-// g = R^T R (R upper) -> R^-1 (upper), 3 x 3 row-major.  False if g is not positive definite.
-__host__ __device__ inline bool sp_chol3_inv_upper(const double *g, double *rinv) {
-    double r[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int j = 0; j < 3; ++j) {
-        double d = g[j * 3 + j];
-        for (int k = 0; k < j; ++k) d -= r[k * 3 + j] * r[k * 3 + j];
-        if (!(d > 0.0)) return false;
-        r[j * 3 + j] = sqrt(d);
-        for (int c = j + 1; c < 3; ++c) {
-            double v = g[j * 3 + c];
-            for (int k = 0; k < j; ++k) v -= r[k * 3 + j] * r[k * 3 + c];
-            r[j * 3 + c] = v / r[j * 3 + j];
-        }
-    }
-    for (int q = 0; q < 9; ++q) rinv[q] = 0.0;
-    for (int j = 0; j < 3; ++j) {
-        rinv[j * 3 + j] = 1.0 / r[j * 3 + j];
-        for (int i = j - 1; i >= 0; --i) {
-            double v = 0.0;
-            for (int k = i + 1; k <= j; ++k) v -= r[i * 3 + k] * rinv[k * 3 + j];
-            rinv[i * 3 + j] = v / r[i * 3 + i];
-        }
-    }
-    return true;
-}
-
-// The 3 x 3 step BETWEEN two passes, done by every workgroup of the consuming pass for itself
-// (round 4, second version: as a kernel of its own it cost what every tiny kernel costs here,
-// 4.7 us by the kernel trace, three times per product).  The producer left `groups` partial
-// sums of 12 values; 12 x 16 threads add them in a fixed order (thread (q, l) takes the groups
-// l, l + 16, ... of value q, then a 16-lane tree), thread 0 does the 3 x 3 step, LDS hands the
-// map to everybody.  Every workgroup -- and every rank -- computes the same bits.
-//   kSpMean     A = { mean = column sums / n, M = I, scale }           (centring)
-//   kSpChol     A = { 0, R^-1, 1 } with R^T R = the Gram matrix        (Cholesky-QR pass)
-//   kSpCholMean the same, and B.mean = (column sums / n) R^-1: the mean of what the map is
-//               about to produce (sp_affine_centre_kernel)
-// A Gram matrix that is not positive definite sets *flag and leaves the identity.
-enum { kSpMean = 0, kSpChol = 1, kSpCholMean = 2 };
-__device__ __forceinline__ void sp_map_from_partials(const double *__restrict__ partial, int groups,
-                                                     int64_t n_bins, int mode, double scale,
-                                                     int *__restrict__ flag, Affine3 &A, Affine3 &B) {
-    __shared__ double tot[12];
-    __shared__ Affine3 maps[2];
-    const int t = threadIdx.x;
-    if (t < 192) {
-        const int q = t >> 4, l = t & 15;
-        double v = 0.0;
-        for (int g = l; g < groups; g += 16) v += partial[(int64_t)g * 12 + q];
-#pragma unroll
-        for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 16);
-        if (l == 0) tot[q] = v;
-    }
-    __syncthreads();
-    if (t == 0) {
-        Affine3 a, b;
-        for (int k = 0; k < 3; ++k) a.mean[k] = 0.0;
-        for (int k = 0; k < 9; ++k) a.m[k] = (k % 4 == 0) ? 1.0 : 0.0;
-        a.scale = 1.0;
-        b = a;
-        if (mode == kSpMean) {
-            for (int k = 0; k < 3; ++k) a.mean[k] = tot[9 + k] / (double)n_bins;
-            a.scale = scale;
-        } else {
-            double rinv[9];
-            if (!sp_chol3_inv_upper(tot, rinv)) {
-                *flag = 1;                       // (every workgroup writes the same 1)
-            } else {
-                for (int k = 0; k < 9; ++k) a.m[k] = rinv[k];
-                b = a;
-                const double m0 = tot[9] / (double)n_bins, m1 = tot[10] / (double)n_bins,
-                             m2 = tot[11] / (double)n_bins;
-                b.mean[0] = m0 * rinv[0] + m1 * rinv[3] + m2 * rinv[6];
-                b.mean[1] = m0 * rinv[1] + m1 * rinv[4] + m2 * rinv[7];
-                b.mean[2] = m0 * rinv[2] + m1 * rinv[5] + m2 * rinv[8];
-            }
-        }
-        maps[0] = a;
-        maps[1] = b;
-    }
-    __syncthreads();
-    A = maps[0];
-    B = maps[1];
-}
-
-// out_i = A.scale * ((in_i - A.mean) A.m) for rows < n_bins (0 beyond), A = the 3 x 3 step
-// `mode` on the producer's partial sums, + the partial sums of the OUTPUT.  In place
-// (in == out) is fine: a thread reads its row before it writes it.
-template <typename TI>
-__global__ __launch_bounds__(kSpWG) void sp_affine_stats_kernel(const TI *in, double *out,
-                                                                int64_t n_bins, int64_t n_pad,
-                                                                const double *__restrict__ partial_in,
-                                                                int groups, int mode, double scale,
-                                                                int *__restrict__ flag,
-                                                                double *__restrict__ partial) {
-    Affine3 A, unused;
-    sp_map_from_partials(partial_in, groups, n_bins, mode, scale, flag, A, unused);
-    int64_t r0, r1;
-    sp_rows(n_pad, r0, r1);
-    double acc[12];
-#pragma unroll
-    for (int q = 0; q < 12; ++q) acc[q] = 0.0;
-    for (int64_t i = r0 + threadIdx.x; i < r1; i += kSpWG) {
-        double o0 = 0.0, o1 = 0.0, o2 = 0.0;
-        if (i < n_bins) {
-            const double x0 = (double)in[3 * i] - A.mean[0], x1 = (double)in[3 * i + 1] - A.mean[1],
-                         x2 = (double)in[3 * i + 2] - A.mean[2];
-            o0 = A.scale * (x0 * A.m[0] + x1 * A.m[3] + x2 * A.m[6]);
-            o1 = A.scale * (x0 * A.m[1] + x1 * A.m[4] + x2 * A.m[7]);
-            o2 = A.scale * (x0 * A.m[2] + x1 * A.m[5] + x2 * A.m[8]);
-            sp_accumulate(acc, o0, o1, o2);
-        }
-        out[3 * i] = o0; out[3 * i + 1] = o1; out[3 * i + 2] = o2;
-    }
-    sp_store_partial(acc, partial);
-}
-
-// The last pass of an orthonormalisation: V = V' R^-1, written as double, and the sweep's
-// right-hand sides mv = (T)(V - mean V) -- V centred, in the solver's type -- in one go; R^-1 and
-// the mean from the producer's partial sums (kSpCholMean).
-template <typename T>
-__global__ __launch_bounds__(kSpWG) void sp_affine_centre_kernel(const double *in, double *out_v,
-                                                                 T *__restrict__ out_mv,
-                                                                 int64_t n_bins, int64_t n_pad,
-                                                                 const double *__restrict__ partial_in,
-                                                                 int groups, int *__restrict__ flag) {
-    Affine3 A, B;
-    sp_map_from_partials(partial_in, groups, n_bins, kSpCholMean, 1.0, flag, A, B);
-    const int64_t i = (int64_t)blockIdx.x * kSpWG + threadIdx.x;
-    if (i >= n_pad) return;
-    double o0 = 0.0, o1 = 0.0, o2 = 0.0, c0 = 0.0, c1 = 0.0, c2 = 0.0;
-    if (i < n_bins) {
-        const double x0 = in[3 * i], x1 = in[3 * i + 1], x2 = in[3 * i + 2];
-        o0 = x0 * A.m[0] + x1 * A.m[3] + x2 * A.m[6];
-        o1 = x0 * A.m[1] + x1 * A.m[4] + x2 * A.m[7];
-        o2 = x0 * A.m[2] + x1 * A.m[5] + x2 * A.m[8];
-        c0 = o0 - B.mean[0]; c1 = o1 - B.mean[1]; c2 = o2 - B.mean[2];
-    }
-    out_v[3 * i] = o0; out_v[3 * i + 1] = o1; out_v[3 * i + 2] = o2;
-    out_mv[3 * i] = (T)c0; out_mv[3 * i + 1] = (T)c1; out_mv[3 * i + 2] = (T)c2;
+    lds_tree_fold(sh, tid, 256);
+    if (tid == 0) sums[nodes[a]] += lam * sh[0];
 }
 
 template <typename T>

@@ -95,6 +95,57 @@ BB_API int bb_layout_dense_tiles(int64_t n_bins, int dtype, int32_t *tile_I, int
 BB_API int bb_layout_rank_units(int64_t n_units, int rank, int world, int64_t *u_begin,
                                 int64_t *u_end);
 
+/* The sweep plan of a rank (docs/SPEC.md 3.3-3.5): what bb_solver_create derives from the
+ * tile list, the rank's units [u_begin, u_end) and the device's CU count before it allocates
+ * anything.  Knobs: what the BB_* environment variables of the same names set in a solver. */
+typedef struct bb_sweep_knobs {
+    int32_t waves_per_cu;   /* 1..32; 0: 8 from 65,000 units per rank, else 4               */
+    int32_t pair;           /* not 0: workgroups of 8 waves at 8 waves per CU (the default)  */
+    int32_t reduce_slices;  /* 4 or 8; 0: 4 while no reduce list is longer than 64 entries   */
+    int32_t row_owner;      /* not 0: also the sizes of the row-owner path                   */
+} bb_sweep_knobs;
+typedef struct bb_sweep_plan {
+    int64_t n_local;          /* u_end - u_begin                                             */
+    int64_t t_first;          /* first tile with a local unit                                */
+    int64_t n_local_tiles;
+    int64_t n_waves;          /* a multiple of wpb                                           */
+    int64_t wpb;              /* waves per workgroup: 4 or 8                                 */
+    int64_t chunk_q, chunk_r; /* wave w owns units [w q + min(w, r), + q (+ 1 if w < r))     */
+    int64_t n_slots;          /* column-partial slots                                        */
+    int64_t rowpart_elems;    /* n_local_tiles * 3 vw                                        */
+    int64_t colpart_elems;    /* n_slots * 3 vw                                              */
+    int64_t zero_off;         /* offset of the chunk of zeros the reduce lists are padded with */
+    int64_t part_total;       /* elements of the partials, the zero chunk included           */
+    int64_t red_slices;       /* 4 or 8                                                      */
+    int64_t red_stride;       /* entries per block of red_lists                              */
+    int64_t red_blocks;       /* blocks of red_lists (the layout's n_blocks)                 */
+    int64_t defer_cap_units;  /* units of row sums a wave parks in LDS                       */
+    int64_t lds_wave_floats;  /* 4-byte words of LDS per wave                                */
+    int64_t defer_lds_bytes;  /* dynamic LDS per workgroup                                   */
+    int64_t nontemporal;      /* 1: the sweep's matrix loads are non-temporal                */
+    int64_t full_ld;          /* row-owner path: row stride of the full matrix, else 0       */
+    int64_t ro_wpr, ro_blocks;/* row-owner path: waves per row, workgroups holding rows      */
+} bb_sweep_plan;
+/* tile_I / tile_J NULL (n_tiles 0): the dense list of (n_bins, dtype).  Every array may be NULL:
+ * `plan` alone then gives the counts to size them with -- udesc 2 n_local (row, column of each
+ * unit), wave_slots 2 n_waves (first private slot, shared slot or -1), slot_strip n_slots,
+ * wave_last_strip n_waves (-1: a wave without units), red_lists red_blocks * red_stride
+ * offsets into the partials.  Host-only. */
+BB_API int bb_layout_sweep_plan(int64_t n_bins, int dtype, const int32_t *tile_I, const int32_t *tile_J,
+                                int64_t n_tiles, int64_t u_begin, int64_t u_end, int cus,
+                                const bb_sweep_knobs *knobs, bb_sweep_plan *plan, int32_t *udesc,
+                                int32_t *wave_slots, int32_t *slot_strip, int32_t *wave_last_strip,
+                                int64_t *red_lists);
+/* The table of the 24-bit stream (SPEC 3.7) of n units from min_max, 2 n words (the smallest and
+ * the largest stored word of each unit), and udesc as above.  A unit is packable when largest -
+ * smallest < 2^24 and stored packed inside a run of at least min_run packable units.  table: NULL,
+ * or 4 n words (row, column, offset in KiB | packed << 31, base).  pays: whether a solver builds
+ * the stream -- mode 0 never, 1 when a unit is packed, else when it saves an eighth of the raw
+ * bytes -- and never at 2^31 KiB or more.  Host-only. */
+BB_API int bb_layout_pk24_table(const uint32_t *min_max, const int32_t *udesc, int64_t n, int64_t min_run,
+                                int mode, int32_t *table, int64_t *stream_kib, int64_t *packed_units,
+                                int64_t *format_switches, int *pays);
+
 /* ---------------------------------------------------------------------- */
 /* S0  3D-structure solver  (docs/SPEC.md; absent from the reference)       */
 /* ---------------------------------------------------------------------- */

@@ -11,6 +11,8 @@
 #                                           (no addresses, no encodings, no trailing comments).
 #                                           Sorted by name, so the outputs of two builds `diff`:
 #                                           an equal line = the same machine code
+# The summary on stderr counts kernels and code objects and names every kernel that more than
+# one code object defines (the tables are keyed by name and show one copy of it).
 digest=0
 if [ "$1" = "--digest" ]; then digest=1; shift; fi
 exec python3 - "${1:-blueberry_amd/libblueberry_hip.so}" "$digest" "${2:-}" <<'PY'
@@ -20,6 +22,7 @@ B = "/opt/rocm/lib/llvm/bin/"
 run = lambda *a: subprocess.run(a, text=True, capture_output=True, check=True).stdout
 blob = open(so, "rb").read()
 meta, code = {}, {}          # mangled name -> resources / instruction lines
+seen = collections.Counter() # mangled name -> code objects that define it
 with tempfile.TemporaryDirectory() as tmp:
     pos = images = 0
     while True:
@@ -39,14 +42,16 @@ with tempfile.TemporaryDirectory() as tmp:
         # a kernel's entry runs from its "- .agpr_count:" to the next one (keys are sorted)
         for blk in re.split(r"^\s*- \.agpr_count:", run(B + "llvm-readelf", "--notes", co), flags=re.M)[1:]:
             g = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1))
-            meta[re.search(r"\.symbol:\s+(\S+)\.kd", blk).group(1)] = (
-                g("vgpr_count"), g("sgpr_count"), g("private_segment_fixed_size"),
-                g("group_segment_fixed_size"), g("kernarg_segment_size"))
+            name = re.search(r"\.symbol:\s+(\S+)\.kd", blk).group(1)
+            seen[name] += 1
+            meta[name] = (g("vgpr_count"), g("sgpr_count"), g("private_segment_fixed_size"),
+                          g("group_segment_fixed_size"), g("kernarg_segment_size"))
         if digest or pat:
             asm = run(B + "llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", co)
             for m in re.finditer(r"^[0-9a-f]* ?<(\S+)>:\n(.*?)(?=^[0-9a-f]* ?<\S+>:\n|\Z)", asm, re.S | re.M):
                 lines = [re.sub(r"\s*//.*", "", l).strip() for l in m.group(2).splitlines()]
-                code[m.group(1)] = [l for l in lines if l]
+                # ("...": the zero padding behind a code object's last kernel, not an instruction)
+                code[m.group(1)] = [l for l in lines if l and l != "..."]
 names = sorted(meta)
 try:                         # sorted by demangled name where c++filt is there, else by mangled
     demangled = dict(zip(names, subprocess.run(["c++filt"], input="\n".join(names), text=True,
@@ -68,4 +73,11 @@ for k in sorted(names):
                 'scratch_store_dword', 's_load_dwordx8', 'v_readlane_b32', 's_nop']
         print(k[:100], 'total', sum(c.values()), {q: c[q] for q in keys if c[q]})
 print("# %d kernels in %d code objects" % (len(names), images), file=sys.stderr)
+# the tables above are keyed by name: a kernel compiled into two code objects would show once
+twice = sorted(k for k in names if seen[k] > 1)
+if twice:
+    print("# NOTE: %d kernels are defined in more than one code object (the line above shows one "
+          "copy of each):" % len(twice), file=sys.stderr)
+    for k in twice:
+        print("#   x%d %s" % (seen[k], demangled[k][:120]), file=sys.stderr)
 PY
