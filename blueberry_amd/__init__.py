@@ -28,6 +28,11 @@ Net-new (the reference has no solver; docs/SPEC.md):
                                   structure against structure: superposition up to a mirror image,
                                   pair distances per separation and per bin, Spearman ranks by the
                                   device's sort (SPEC 2.10)
+    ContactMap.coarsen, DeviceTriples.coarsen, coarsen_triples
+                                  a map pooled to a coarser resolution on the device, dense and
+                                  pixel list, the same bits (SPEC 2.12)
+    coarsen_structure, prolong_structure
+                                  a structure between two resolutions, host numpy (SPEC 2.12)
 
 All compute runs in libblueberry_hip.so (hand-written HIP for gfx950) behind
 the C-ABI of include/blueberry_hip.h.  Importing this package needs neither
@@ -41,9 +46,10 @@ from .datatypes import (ContactMap, EigenNoConvergence, FithicContactMap,  # noq
                         shortest_paths)
 from .compare import StructureComparison, compare_structures  # noqa: F401
 from .fithic import FitHiC, binomial_sf  # noqa: F401
+from .resolution import coarsen_structure, prolong_structure  # noqa: F401
 from .solver import (DeviceTriples, FitScore, GeodesicRows, HipEngine, RankDeficient,  # noqa: F401
-                     StructureSolver, TriplesBalance, balance_triples, landmark_coefficients,
-                     landmark_start)
+                     StructureSolver, TriplesBalance, balance_triples, coarsen_triples,
+                     landmark_coefficients, landmark_start)
 from .stats import benjamini_hochberg, downsample, q_values  # noqa: F401
 
 __version__ = "0.1.0"

@@ -16,6 +16,7 @@ BB_F32, BB_F64 = 0, 1
 BB_KIND_WISH, BB_KIND_COUNTS = 0, 1
 BB_PEER_HANDLE_BYTES = 128
 BB_CMP_SPEARMAN = 1
+BB_COARSEN_SUM, BB_COARSEN_MEAN = 0, 1
 
 c_i32, c_i64, c_dbl = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 p_i32, p_i64, p_dbl = (ctypes.POINTER(c_i32), ctypes.POINTER(c_i64), ctypes.POINTER(c_dbl))
@@ -175,6 +176,12 @@ SIGNATURES = {
     "bb_sig_read_q": (c_int, [c_void_p, p_dbl]),
     "bb_sig_select": (c_int, [c_void_p, c_dbl, ctypes.POINTER(c_void_p)]),
     "bb_sig_destroy": (c_int, [c_void_p]),
+    "bb_cm_coarsen": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p]),
+    "bb_cm_coarsen_timing": (c_int, [c_void_p, p_dbl]),
+    "bb_triples_coarsen": (c_int, [c_void_p, c_i64, c_i64, c_int, ctypes.POINTER(c_void_p)]),
+    "bb_triples_coarsen_timing": (c_int, [c_void_p, p_dbl]),
+    "bb_triples_size": (c_int, [c_void_p, p_i64]),
+    "bb_triples_download": (c_int, [c_void_p, p_dbl]),
     "bb_solver_set_wish_from_cm": (c_int, [c_void_p, c_void_p, c_int, c_dbl]),
     "bb_solver_set_wish_from_cm_block": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_dbl]),
     "bb_solver_set_maps": (c_int, [c_void_p, c_int, p_i64, p_dbl]),

@@ -310,6 +310,7 @@ struct bb_cm {
     // rows and columns (bb_cm_balance / bb_cm_expected), which also holds the diagonal work
     // list.  Two, so that alternating calls do not rebuild the lists.
     bb::ProductScratch sv, bal;
+    double coarsen_ms = 0.0;  // on a map bb_cm_coarsen wrote: the pooling kernel, by HIP events
 };
 
 namespace bb {

@@ -66,6 +66,8 @@ struct bb_triples {
     double resolution = 1.0;
     bb::DevBuf d;                       // 3 n doubles
     bb::TriplesIndex index;             // (bb_triples_balance.hip; freed with the handle)
+    double coarsen_ms = 0.0;            // on a list bb_triples_coarsen left: count + scan + write
+                                        // over the source's index, by HIP events
     const double *from(int64_t t0) const { return d.as<double>() + t0 * (st == 3 ? 3 : 1); }
 };
 

@@ -171,6 +171,20 @@ def check_balance_args(ignore_diags=0, min_nnz=0, tol=1e-5, max_iter=200, row_su
     return ignore_diags, min_nnz, tol, max_iter, row_sum
 
 
+_COARSEN_HOW = {"sum": _lib.BB_COARSEN_SUM, "mean": _lib.BB_COARSEN_MEAN}
+
+
+def check_coarsen_args(factor, how="sum"):
+    """(factor, how code) of `ContactMap.coarsen`, `DeviceTriples.coarsen` and `coarsen_triples`,
+    checked (ValueError) without touching the library: an int >= 1 -- no bool, no float -- and
+    'sum' or 'mean'."""
+    from .resolution import check_factor
+    factor = check_factor(factor)
+    if not isinstance(how, str) or how not in _COARSEN_HOW:
+        raise ValueError("how must be 'sum' or 'mean'")
+    return factor, _COARSEN_HOW[how]
+
+
 def expected_from_sums(sums, counts):
     """e[k] = sums[k] / counts[k], NaN where counts[k] == 0 or sums[k] == 0 (docs/SPEC.md 2.5.2)."""
     sums = numpy.asarray(sums, dtype=numpy.float64)
@@ -621,6 +635,38 @@ class ContactMap(object):
         out._host = out._view = None
         out._dev = _DeviceMatrix(src.d, src.device)
         out.unreachable_pairs_ = _shortest_paths_device(src, out._dev, kind_code, alpha)
+        return out
+
+    def coarsen(self, factor, how="sum"):
+        """The map pooled to resolution `resolution * factor` (docs/SPEC.md 2.12): a NEW resident
+        ContactMap of `ceil(n_bins / factor)` bins (same celltype, chromosome and device; no KR
+        vectors, nothing of `balance()` / `expected()`), computed on the device from the upper
+        triangle of the leading n_bins x n_bins block (`bb_cm_coarsen`).  Coarse bin I holds the
+        fine bins [I factor, (I + 1) factor) -- the last may be ragged; cell (I, J) is the sum of
+        its block, (I, I) the sum of the block's upper triangle with the diagonal (every fine pair
+        once: the contacts inside the bin, cooler's convention).  how='mean' divides by the
+        number of fine cells pooled, zero cells included -- for O/E-normalised maps.  `regions`
+        are the old ones rounded down to the new grid.  Float64 in a fixed order of summation: the
+        same bits on every run, and the bits `coarsen_triples` gives from the pixel list.  This
+        map is left as it is and stays resident; a filtered map (its edge is no longer
+        n_bins + 1) is refused."""
+        factor, how = check_coarsen_args(factor, how)
+        src = self._balance_target()
+        n = self.n_bins
+        nc = -(-n // factor)
+        out = ContactMap.__new__(ContactMap)
+        out.resolution = self.resolution * factor
+        out.chromosome, out.celltype = self.chromosome, self.celltype
+        out.device, out.filename, out.n_bins = src.device, self.filename, nc
+        if self.regions is None:
+            out.regions = None
+        else:
+            R = float(out.resolution)
+            out.regions = numpy.unique(numpy.floor(numpy.asarray(self.regions, dtype=numpy.float64) / R) * R)
+        out._KRnorm = out._KRexpected = None
+        out._host = out._view = None
+        out._dev = _DeviceMatrix(nc + 1, src.device)
+        src._call("coarsen", n, factor, how, out._dev._open())
         return out
 
     def plot(self, arcsinh=True, **kwargs):

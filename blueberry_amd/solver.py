@@ -22,7 +22,7 @@ import numpy
 
 from . import _lib
 from .datatypes import (_balance, _expected, _nan_to_num, _pick_device, check_balance_args,
-                        triples_buffer)
+                        check_coarsen_args, triples_buffer)
 
 _DTYPES = {"float32": _lib.BB_F32, "float64": _lib.BB_F64}
 _KINDS = {"wish": _lib.BB_KIND_WISH, "counts": _lib.BB_KIND_COUNTS}
@@ -54,9 +54,42 @@ class DeviceTriples(_lib.Handle):
         self.n, self.device = int(t.shape[0]), int(device)
         self._create(_lib.as_f64_ptr(buf), self.n, int(resolution), row_major, self.device)
 
+    @classmethod
+    def _adopt(cls, handle, resolution, device):
+        """The owner of a `bb_triples` another call left (`bb_triples_coarsen`)."""
+        self = cls.__new__(cls)
+        _lib.Handle.__init__(self, handle)
+        self.resolution, self.device = int(resolution), int(device)
+        self.n = int(self._get(_lib.c_i64, "size"))
+        return self
+
     def _balance_target(self):
         """The handle `balance`, `expected` and the significance pass speak to: this one."""
         return self
+
+    def to_host(self):
+        """The (n, 3) float64 rows [pos_i, pos_j, count] the handle holds, C-ordered, as they
+        were given (`bb_triples_download`)."""
+        out = numpy.empty((self.n, 3), dtype=numpy.float64)
+        self._call("download", _lib.as_f64_ptr(out))
+        return out
+
+    def coarsen(self, n_bins, factor, how="sum"):
+        """The pixel list of the map the triples define over bins 0 .. n_bins - 1, pooled to
+        resolution `resolution * factor` (`ContactMap.coarsen`; docs/SPEC.md 2.12): a NEW
+        `DeviceTriples` on the same device -- nothing goes through the host -- of one triple
+        [I R, J R, value] per pooled cell I <= J with at least one stored fine cell (a stored 0
+        included), I ascending, then J; `n_bins_` holds ceil(n_bins / factor).  The values are
+        bit for bit those of `ContactMap.from_triples(...).coarsen(factor, how)`.  The new handle
+        is usable wherever a `DeviceTriples` is and does not depend on this one, which stays as
+        it is (the first call builds its index, as `balance` does)."""
+        factor, how = check_coarsen_args(factor, how)
+        n = _bin_count(n_bins)
+        h = _lib.c_void_p()
+        self._call("coarsen", n, factor, how, h)
+        out = DeviceTriples._adopt(h, self.resolution * factor, self.device)
+        out.n_bins_ = -(-n // factor)
+        return out
 
     def tiles(self, n_bins, dtype):
         """(tile_I, tile_J), device order, of the tiles the triples name."""
@@ -381,6 +414,21 @@ def balance_triples(triples, resolution, n_bins, ignore_diags=0, min_nnz=0, tol=
     with _resident_triples(triples, resolution, [_pick_device(device)]) as dev:
         bias = dev.balance(n, **args)
         return TriplesBalance(dev, bias, dev.expected(n, bias) if expected else None)
+
+
+def coarsen_triples(triples, resolution, n_bins, factor, how="sum", device=None):
+    """Pool a map straight from its Rao-format (n, 3) triples [pos_i, pos_j, count], never
+    building the dense matrix (`DeviceTriples.coarsen`; docs/SPEC.md 2.12), host to host: returns
+    (pooled, nc) -- the (m, 3) float64 triples at resolution `resolution * factor`, in canonical
+    order, and nc = ceil(n_bins / factor).  `ContactMap.from_triples(pooled, resolution * factor,
+    nc)` is bit for bit `ContactMap.from_triples(triples, resolution, n_bins).coarsen(factor,
+    how)`.  `triples` may be a `DeviceTriples` (its own resolution and device are used; it stays
+    open)."""
+    check_coarsen_args(factor, how)
+    n = _bin_count(n_bins)
+    with _resident_triples(triples, resolution, [_pick_device(device)]) as dev:
+        with dev.coarsen(n, factor, how) as pooled:
+            return pooled.to_host(), pooled.n_bins_
 
 
 class HipEngine(_lib.Handle):

@@ -916,6 +916,38 @@ BB_API int bb_sig_q_values(bb_sig *s, int64_t n_tests, double *sort_ms, double *
 BB_API int bb_sig_read_q(const bb_sig *s, double *q);
 BB_API int bb_sig_select(const bb_sig *s, double q_max, bb_sig **out);
 BB_API int bb_sig_destroy(bb_sig *s);
+/* Pooling a map to a coarser resolution (docs/SPEC.md 2.12).  Coarse bin I holds the fine bins
+ * [I factor, min((I + 1) factor, n_bins)), nc = ceil(n_bins / factor); pooled cell (I, J), I < J,
+ * is the sum of the block's fine cells, (I, I) the sum of the block's upper triangle with its
+ * diagonal; BB_COARSEN_MEAN divides that sum once by the number of fine cells pooled (absent and
+ * zero cells count).  Float64 in a FIXED order -- per fine row of the block, top to bottom, a
+ * partial of its cells left to right; then the partials top to bottom; all from +0.0 -- so that
+ * both routes give the same bits, on every run.  No atomics.  Values are added as stored: a NaN
+ * or an infinity reaches its own pooled cell alone.  Any factor >= 1 works (beyond n_bins: one
+ * bin).  factor < 1, an unknown `how`, n_bins < 0: BB_ERR_INVALID.
+ *
+ * bb_cm_coarsen: from the upper triangle of the leading n_bins x n_bins block of src (its edge
+ * must be n_bins + 1: a filtered map is refused; the matrix is taken to be symmetric, as
+ * bb_cm_symv takes it) into dst, another map of edge nc + 1 on the same device: the lower
+ * triangle mirrors the upper bit for bit, the padding row and column are 0.  src is not changed.
+ * bb_cm_coarsen_timing: the ms of the pooling kernel that wrote dst, by HIP events.
+ *
+ * bb_triples_coarsen: the same on the matrix resident triples define (bb_triples_balance's rules
+ * and index), device to device: *out is a NEW handle on src's device, at resolution
+ * src's x factor (which must fit 31 bits), of one triple [I R, J R, value] per pooled cell
+ * I <= J that has at least one stored fine cell (a stored 0 included), I ascending, then J.
+ * *out is NULL after an error; bb_triples_destroy frees it; it does not depend on src.
+ * bb_triples_coarsen_timing: the ms of count + scan + write that made dst (the index apart).
+ * bb_triples_size: the number of triples of a handle.  bb_triples_download: they, as (n, 3)
+ * C-ordered rows, to the host -- the values as stored (nan_to_num is a reader's rule). */
+enum { BB_COARSEN_SUM = 0, BB_COARSEN_MEAN = 1 };
+BB_API int bb_cm_coarsen(const bb_cm *src, int64_t n_bins, int64_t factor, int how, bb_cm *dst);
+BB_API int bb_cm_coarsen_timing(const bb_cm *dst, double *kernel_ms);
+BB_API int bb_triples_coarsen(bb_triples *src, int64_t n_bins, int64_t factor, int how,
+                              bb_triples **out);
+BB_API int bb_triples_coarsen_timing(const bb_triples *dst, double *pool_ms);
+BB_API int bb_triples_size(const bb_triples *t, int64_t *n);
+BB_API int bb_triples_download(const bb_triples *t, double *triples);
 /* Hand the resident matrix to a solver of n_bins = d bins on the same device, device
  * to device (same meaning of kind / alpha as bb_solver_set_wish_dense).  A solver on another
  * device packs over peer access where hipDeviceCanAccessPeer allows it (enabled here); without
