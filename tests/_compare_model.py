@@ -7,7 +7,9 @@ far below one float64 ulp of a sum; the aligned copy, the per-bin deviation and 
 distance are the device's bits.  The bounds are built as tests/_score_model.sums_and_bounds builds
 its own: the number of terms times 2^-53 times the sum of the terms' magnitudes, plus the
 roundings of a term itself.  On the inputs of exact_case() every term and every sum is an integer
-below 2^53 and the model is exact."""
+below 2^53 and the model is exact; so are the 18 moments on those of exact_moments_case().
+pair_sums lists all pairs (1.3 GB at n = 4,097); pair_sums_by_diagonal gives the same bits from
+O(n) memory, for the sizes above that."""
 import numpy
 import scipy.stats
 
@@ -121,6 +123,86 @@ def pair_sums_and_bounds(A, aligned, used):
     return p, b, (p[:, :1] + 16) * EPS * mp, (b[:, :1] + 16) * EPS * mb
 
 
+def _one_segment(terms):
+    """The float64 that _segment_sums gives the terms (..., m) as one segment each: the same
+    numpy call on the same numbers in the same order, hence the same bits (add.reduceat adds a
+    segment's first term to the pairwise sum of the rest wherever the segment starts, which a
+    plain .sum() does not; tests/test_compare_cpu.py holds the two routes against each other)."""
+    if terms.shape[-1] == 0:
+        return numpy.zeros(terms.shape[:-1])
+    return numpy.add.reduceat(terms.astype(numpy.longdouble), [0], axis=-1)[..., 0].astype(numpy.float64)
+
+
+def pair_sums_by_diagonal(A, aligned, used, with_magnitudes=False):
+    """pair_sums without the list of all pairs: the same arrays and the same bits in O(n)
+    memory and O(n^2) time (0.9 s at n = 4,097 where pair_sums takes 3.6 s, 3 s at 8,193).  The
+    terms are formed as _distance and pair_sums form them and summed in numpy.longdouble, a
+    segment of pair_sums at a time:
+      the profile  walks the separations k = 1 .. n - 1 over the slices x[:-k], x[k:]: the used
+                   pairs of one k by ascending i are pair_sums' segment of k;
+      the bins     walk the used bins i over x[i] against x: the used j > i and the used j < i,
+                   each by ascending j, are pair_sums' two segments of bin i (a pair's terms are
+                   the same bits from either end: (-d)^2 = d^2)."""
+    n = A.shape[0]
+    used = numpy.asarray(used, dtype=bool)
+    every = bool(used.all())
+    x = numpy.ascontiguousarray(numpy.stack([numpy.asarray(A, dtype=numpy.float64).T,
+                                             numpy.asarray(aligned, dtype=numpy.float64).T]))   # (2, 3, n)
+    x[:, :, ~used] = 0.0                                            # (finite; never in a sum)
+    profile, bins = numpy.zeros((n, 7)), numpy.zeros((n, 2))
+    mag_profile, mag_bins = numpy.zeros((n, 7)), numpy.zeros((n, 2))
+
+    def distances(d):
+        d *= d
+        return numpy.sqrt((d[:, 0] + d[:, 1]) + d[:, 2])
+
+    def squares(da, db):                                            # (dA - dB)^2 and, where asked, (dA + dB)^2
+        sq = numpy.stack([da - db, da + db]) if with_magnitudes else (da - db)[None]
+        sq *= sq
+        return sq
+
+    def separation(k):
+        m = n - k
+        on = None if every else used[:m] & used[k:]
+        if on is not None and not on.any():
+            return
+        dist = distances(x[:, :, :m] - x[:, :, k:])
+        if on is not None:
+            dist = dist[:, on]
+        da, db = dist
+        sq = squares(da, db)
+        profile[k, 0] = da.shape[0]
+        profile[k, 1:] = _one_segment(numpy.stack([da, db, da * da, db * db, da * db, sq[0]]))
+        if with_magnitudes:
+            mag_profile[k, 6] = _one_segment(sq[1])
+
+    def one_bin(i):
+        da, db = distances(x[:, :, i:i + 1] - x)
+        sq = squares(da, db)
+        below, above = sq[:, :i], sq[:, i + 1:]
+        if not every:
+            below, above = below[:, used[:i]], above[:, used[i + 1:]]
+        total = _one_segment(above) + _one_segment(below)
+        bins[i] = below.shape[1] + above.shape[1], total[0]
+        if with_magnitudes:
+            mag_bins[i] = bins[i, 0], total[1]
+
+    for k in range(1, n):
+        separation(k)
+    for i in numpy.nonzero(used)[0]:
+        one_bin(i)
+    if not with_magnitudes:
+        return profile, bins
+    mag_profile[:, :6] = profile[:, :6]
+    return profile, bins, mag_profile, mag_bins
+
+
+def pair_sums_and_bounds_by_diagonal(A, aligned, used):
+    """pair_sums_and_bounds through pair_sums_by_diagonal: the same rule."""
+    p, b, mp, mb = pair_sums_by_diagonal(A, aligned, used, with_magnitudes=True)
+    return p, b, (p[:, :1] + 16) * EPS * mp, (b[:, :1] + 16) * EPS * mb
+
+
 def centred_ranks(d):
     """scipy's average ranks of d less (m + 1) / 2: exact half-integers."""
     return scipy.stats.rankdata(d) - (d.shape[0] + 1) / 2.0
@@ -193,6 +275,32 @@ def edge_mask(n, tile=TILE, seed=0):
     for edge in range(tile, n, tile):
         mask[edge - 1] = mask[edge] = False
     return mask
+
+
+def block_mask(n, tile=TILE, seed=0, blocks=((768, 1024), (1024, 2048))):
+    """edge_mask less whole blocks of bins [begin, end): by default one tile of the pair pass
+    (768 .. 1,023) and the four after it (1,024 .. 2,047), which are a whole workgroup of the
+    moment kernels (kMomentBins = 1,024) and, from n = 4,097 on, every tile of one chunk of the
+    pair pass on the main tile diagonal."""
+    mask = edge_mask(n, tile, seed)
+    for begin, end in blocks:
+        mask[begin:end] = False
+    return mask
+
+
+def exact_moments_case(n, used, seed=0):
+    """(A, B): integers in [0, 1000) in all six columns, the last used bin then raised (by less
+    than n_used) so that every column's sum over the used bins is a multiple of n_used.  The
+    means are then integers, and so is every centred term and every one of the 18 moments, all
+    below 2^53: exact in float64 in whatever order they are added."""
+    rng = numpy.random.default_rng(4200 + 7 * n + seed)
+    A = rng.integers(0, 1000, (n, 3)).astype(numpy.float64)
+    B = rng.integers(0, 1000, (n, 3)).astype(numpy.float64)
+    idx = numpy.nonzero(used)[0]
+    nu = idx.shape[0]
+    for x in (A, B):
+        x[idx[-1]] += (-x[idx].sum(axis=0)) % nu
+    return A, B
 
 
 IDENTITY13 = numpy.array([1.0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1])

@@ -199,6 +199,68 @@ def test_the_exact_case_is_exact():
     assert not used[[0, 255, 256, 299]].any() and not profile[0].any()
 
 
+@pytest.mark.parametrize("case,masked", [("exact", False), ("float", False), ("exact", True), ("float", True)])
+@pytest.mark.parametrize("n", [2, 3, 257, 769])
+def test_the_sum_by_diagonals_is_pair_sums_bit_for_bit(n, case, masked):
+    A, B = model.exact_case(n) if case == "exact" else model.float_case(n)
+    used = model.edge_mask(n) if masked else numpy.ones(n, dtype=bool)
+    if case == "exact":
+        aligned, _ = model.transform(A, B, used, numpy.eye(3), numpy.zeros(3), 1.0)
+    else:
+        aligned, _ = model.transform(A, B, used, model.rotation(3), numpy.array([1.0, -2.0, 0.5]), 2.7)
+    want = model.pair_sums(A, aligned, used, with_magnitudes=True)
+    got = model.pair_sums_by_diagonal(A, aligned, used, with_magnitudes=True)
+    assert len(got) == 4
+    for g, w, what in zip(got, want, ("profile", "bins", "profile magnitudes", "bin magnitudes")):
+        assert g.shape == w.shape and g.dtype == w.dtype == numpy.float64, what
+        assert numpy.array_equal(g, w), (what, numpy.argwhere(g != w)[:5])
+    for g, w in zip(model.pair_sums_by_diagonal(A, aligned, used), want[:2]):
+        assert numpy.array_equal(g, w)
+    for g, w in zip(model.pair_sums_and_bounds_by_diagonal(A, aligned, used),
+                    model.pair_sums_and_bounds(A, aligned, used)):
+        assert numpy.array_equal(g, w)
+    nu = int(used.sum())
+    assert got[0][:, 0].sum() == nu * (nu - 1) // 2 and got[1][:, 0].sum() == nu * (nu - 1)
+    if masked and n > 3:
+        assert nu < n - 2 and not got[1][~used].any()
+
+
+@pytest.mark.parametrize("n,masked", [(2, False), (1025, False), (1025, True), (2049, True), (263169, True)])
+def test_the_exact_moments_case_is_exact(n, masked):
+    used = model.block_mask(n) if masked else numpy.ones(n, dtype=bool)
+    A, B = model.exact_moments_case(n, used)
+    idx = numpy.nonzero(used)[0]
+    nu = idx.shape[0]
+    assert numpy.array_equal(A, numpy.rint(A)) and numpy.array_equal(B, numpy.rint(B))
+    assert A.min() >= 0 and B.min() >= 0 and max(A.max(), B.max()) < 1000 + nu
+    assert max(numpy.delete(A, idx[-1], axis=0).max(), numpy.delete(B, idx[-1], axis=0).max()) < 1000
+    out, _ = model.moments_and_bounds(A, B, used)
+    assert numpy.array_equal(out, numpy.rint(out)) and numpy.abs(out).max() < 2.0 ** 53
+    # the same 18 numbers in integers
+    a, b = A[used].astype(numpy.int64), B[used].astype(numpy.int64)
+    assert not (a.sum(axis=0) % nu).any() and not (b.sum(axis=0) % nu).any()
+    da, db = a - a.sum(axis=0) // nu, b - b.sum(axis=0) // nu
+    want = numpy.concatenate([[nu], a.sum(axis=0) // nu, b.sum(axis=0) // nu, [(da * da).sum(), (db * db).sum()],
+                              (db.T @ da).reshape(9)])
+    assert numpy.array_equal(out, want.astype(numpy.float64))
+    assert n == 2 or (out[7] > 0 and out[8] > 0 and numpy.abs(out[9:]).min() > 0)
+    if masked and n > 2048:                          # more than the edges: whole blocks are out
+        assert nu < n - 1280
+
+
+def test_the_block_mask_drops_whole_blocks():
+    for n in (700, 1000, 2049, 4097):
+        mask, edges = model.block_mask(n), model.edge_mask(n)
+        assert not mask[768:2048].any() and not (mask & ~edges).any()
+        keep = numpy.ones(n, dtype=bool)
+        keep[768:2048] = False
+        assert numpy.array_equal(mask[keep], edges[keep])
+    assert model.block_mask(4097)[[767, 2048]].tolist() == [False, False]        # (tile edges)
+    assert model.block_mask(4097)[2049:2304].sum() > 200
+    assert numpy.array_equal(model.block_mask(3000, blocks=((10, 20),))[5:25],
+                             model.edge_mask(3000)[5:25] & ~((numpy.arange(5, 25) >= 10) & (numpy.arange(5, 25) < 20)))
+
+
 # ---- the report -----------------------------------------------------------------------------------
 def test_the_report_derived_from_given_sums():
     n = 50
