@@ -122,7 +122,8 @@ __device__ __forceinline__ double2 stream_load(const double2 *p) {
 // unit, through plain pointers.  (Buffer loads through a descriptor of the wave's chunk, so
 // that the refills of its last unit fall out of range, measured 1.5-2.5 us slower per launch:
 // profiles/r03_window_ab.txt.  The pointer form gets the same saving by pointing all lanes of
-// those last refills at one line: see window_of in the kernel.)
+// those last refills at one line: see window_of in the kernel.)  The fp64 units keep a pointer per
+// lane; the fp32 unit gives the same addresses as a scalar base + a lane offset (WinBase32).
 template <typename Vec>
 struct WinPtr {
     const Vec *p;
@@ -323,13 +324,47 @@ __device__ __forceinline__ f32x2 weight01(f32x2 delta) {
     return w;
 }
 
+// The row coordinates of an fp32 unit: x0 y0 | z0 x1 | y1 z1 | x2 y2 | z2 x3 | y3 z3, twelve
+// consecutive floats of X fetched through the scalar cache as six 64-bit scalars, so that every
+// pair sits in an aligned pair of scalar registers.  Coordinate q is half q & 1 of pair q >> 1.
+struct XRowS32 {
+    f32x2 p[6];
+};
+// {s, s} - xj for the scalar s = half HALF of `pair`, read where it is: a VOP3P source may be an
+// aligned scalar pair, and op_sel / op_sel_hi pick the same half of it for both results.  The
+// instruction hipcc forms for f32x2{s, s} - xj once s is in a vector register, without the copy
+// that puts it there (12 v_mov_b32 per unit).  One scalar source: within the constant-bus limit.
+template <int HALF>
+__device__ __forceinline__ f32x2 row_minus(f32x2 pair, f32x2 xj) {
+    f32x2 d;
+    if constexpr (HALF == 0)
+        asm("v_pk_add_f32 %0, %1, %2 op_sel_hi:[0,1] neg_lo:[0,1] neg_hi:[0,1]"
+            : "=v"(d) : "s"(pair), "v"(xj));
+    else
+        asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]"
+            : "=v"(d) : "s"(pair), "v"(xj));
+    return d;
+}
+// acc += a * {s, s}, the matvec's column side, from the pair in the same way (the fused multiply-add
+// hipcc contracts `acc += a * xi` to: the same bits)
+template <int HALF>
+__device__ __forceinline__ void row_fma(f32x2 &acc, f32x2 a, f32x2 pair) {
+    if constexpr (HALF == 0)
+        asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(acc) : "v"(a), "s"(pair));
+    else
+        asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]"
+            : "+v"(acc) : "v"(a), "s"(pair));
+}
+
 // MASK = false (kOpStress only): the caller knows that no delta of the unit is 0 -- a packed unit
 // of the 24-bit stream with base != 0, see process_unit_f32 -- so the weight is exactly 1.0f and
 // res * 1.0f is res, bit for bit: neither is formed.
-template <int K, int H, bool FIRST, int OP, bool MASK = true>
-__device__ __forceinline__ void pair_step2(f32x2 delta, f32x2 xi, f32x2 yi, f32x2 zi, StripF32 &st,
+// R: the matrix row of the unit; its coordinates are read from the scalar pairs of `xr`.
+template <int K, int H, bool FIRST, int OP, int R, bool MASK = true>
+__device__ __forceinline__ void pair_step2(f32x2 delta, const XRowS32 &xr, StripF32 &st,
                                            f32x2 &rx, f32x2 &ry, f32x2 &rz, f32x2 &s2) {
     static_assert(MASK || OP == kOpStress, "only the plain stress sweep has a mask-free form");
+    constexpr int QX = 3 * R, QY = 3 * R + 1, QZ = 3 * R + 2;
     if constexpr (OP == kOpMatvec2) {
         const f32x2 a = delta * delta;
         if constexpr (FIRST) {
@@ -337,13 +372,15 @@ __device__ __forceinline__ void pair_step2(f32x2 delta, f32x2 xi, f32x2 yi, f32x
         } else {
             rx += a * st.x[K][H][0]; ry += a * st.x[K][H][1]; rz += a * st.x[K][H][2];
         }
-        st.g[K][H][0] += a * xi;
-        st.g[K][H][1] += a * yi;
-        st.g[K][H][2] += a * zi;
+        row_fma<QX & 1>(st.g[K][H][0], a, xr.p[QX >> 1]);
+        row_fma<QY & 1>(st.g[K][H][1], a, xr.p[QY >> 1]);
+        row_fma<QZ & 1>(st.g[K][H][2], a, xr.p[QZ >> 1]);
         return;
     }
     const f32x2 eps2 = {1e-30f, 1e-30f};
-    const f32x2 dx = xi - st.x[K][H][0], dy = yi - st.x[K][H][1], dz = zi - st.x[K][H][2];
+    const f32x2 dx = row_minus<QX & 1>(xr.p[QX >> 1], st.x[K][H][0]),
+                dy = row_minus<QY & 1>(xr.p[QY >> 1], st.x[K][H][1]),
+                dz = row_minus<QZ & 1>(xr.p[QZ >> 1], st.x[K][H][2]);
     const f32x2 d2 = dx * dx + (dy * dy + (dz * dz + eps2));  // SPEC 2.2: |d|^2 + eps^2
     f32x2 rinv;
     rinv.x = __builtin_amdgcn_rsqf(d2.x);
@@ -455,9 +492,57 @@ __device__ __forceinline__ float4 pk24_tops(float4 hi, float4 lo, unsigned sel) 
                        pk24_tops(hi.z, lo.z, sel), pk24_tops(hi.w, lo.w, sel));
 }
 
+// The row coordinates of the NEXT unit, into the registers of the current one as matrix row R lets
+// go of them: a second set of twelve does not fit the scalar file beside the rest of the sweep,
+// and a refresh in place needs none.  Rows 0 and 1 share the pair z0 x1, rows 2 and 3 z2 x3, so
+// x y of an even row go when that row is done and the other four floats after the odd row: each
+// scalar load is at least a quarter of a unit ahead of its first reader.
+// xnext: where the next unit's rows begin in X, in bytes.  `after` is a value of row R that
+// exists only when the row's subtracts are done (one of its sums); the empty asm statement makes
+// the load's address depend on it.  X is read-only here, so nothing else orders these loads, and
+// left alone hipcc issues all of them early in the raw body, into twelve more registers that it
+// copies over at the end: a double buffer again, and scalars spilled around the loops.
+template <int R>
+__device__ __forceinline__ void xrow_refresh(XRowS32 &xr, const float *__restrict__ X, unsigned xnext,
+                                             float after) {
+    asm("" : "+s"(xnext) : "v"(after));
+    const f32x2 *__restrict__ px =
+        reinterpret_cast<const f32x2 *>(reinterpret_cast<const char *>(X) + xnext);
+    constexpr int P = 3 * (R >> 1);
+    if constexpr (R & 1) {
+        xr.p[P + 1] = px[P + 1];
+        xr.p[P + 2] = px[P + 2];
+    } else {
+        xr.p[P] = px[P];
+    }
+}
+
+// The fp32 window: the k-th wave-load of a unit from a wave-uniform base, kept in scalar
+// registers, and a 32-bit per-lane byte offset that is a loop constant (lane * 16; 0 where all
+// lanes ask for the same 16 bytes: window_of) -- global_load_dwordx4 v, v_off, s[base:base+1].
+// The base points at the unit's byte 4,096, so that the instruction's signed 13-bit offset
+// reaches all eight KiB.  The addresses are those of WinPtr.
+struct WinBase32 {
+    const char *mid;
+    unsigned voff;
+    // (the distance through an empty asm statement: hipcc otherwise folds the 4,096 back into
+    // the offsets, reaches four loads from the scalar base and builds 64-bit vector addresses
+    // for the rest; the distance and not the pointer, which stays a pointer to global memory)
+    __device__ __forceinline__ WinBase32(const void *units, int64_t unit_byte, unsigned lane_off)
+        : voff(lane_off) {
+        int64_t to_mid = unit_byte + 4096;
+        asm("" : "+s"(to_mid));
+        mid = static_cast<const char *>(units) + to_mid;
+    }
+    template <bool NT>
+    __device__ __forceinline__ float4 load(int k) const {
+        return stream_load<NT>(reinterpret_cast<const float4 *>(mid + voff + (k * 1024 - 4096)));
+    }
+};
+
 template <bool NT, int OP, bool PK = false, typename WIN>
-__device__ __forceinline__ void process_unit_f32(float4 (&d)[8], const float (&xrow)[12],
-                                                 const WIN &next, StripF32 &st,
+__device__ __forceinline__ void process_unit_f32(float4 (&d)[8], XRowS32 &xrow, const float *X,
+                                                 unsigned xnext, const WIN &next, StripF32 &st,
                                                  double &stress, __amdgpu_buffer_rsrc_t row_rsrc,
                                                  unsigned row_voff, int stage_idx,
                                                  unsigned base = 0u) {
@@ -466,8 +551,6 @@ __device__ __forceinline__ void process_unit_f32(float4 (&d)[8], const float (&x
     float g[12], h[6], m[3];  // the unit's 12 row sums on their way through the tree
     auto row = [&](auto rc) __attribute__((always_inline)) {
         constexpr int r = decltype(rc)::value;
-        const float xs = xrow[3 * r], ys = xrow[3 * r + 1], zs = xrow[3 * r + 2];
-        const f32x2 xi = {xs, xs}, yi = {ys, ys}, zi = {zs, zs};
         f32x2 rx, ry, rz;  // row-side sums of the row's 8 pairs
         if constexpr (PK) {
             // The codes become distances IN the window's registers, and d[6], d[7] -- which a
@@ -483,31 +566,33 @@ __device__ __forceinline__ void process_unit_f32(float4 (&d)[8], const float (&x
                 d[3] = next.template load<NT>(3);
             }
             pk24_decode<r == 3>(d[A], base);
-            pair_step2<0, 0, true, OP, false>(f32x2{d[A].x, d[A].y}, xi, yi, zi, st, rx, ry, rz, s2);
-            pair_step2<0, 1, false, OP, false>(f32x2{d[A].z, d[A].w}, xi, yi, zi, st, rx, ry, rz, s2);
+            pair_step2<0, 0, true, OP, r, false>(f32x2{d[A].x, d[A].y}, xrow, st, rx, ry, rz, s2);
+            pair_step2<0, 1, false, OP, r, false>(f32x2{d[A].z, d[A].w}, xrow, st, rx, ry, rz, s2);
             if constexpr (r == 0) d[0] = next.template load<NT>(0);
             if constexpr (r == 2) d[4] = next.template load<NT>(4);
             if constexpr (r == 1) pk24_decode_to(d[2], d[3], base);
             else pk24_decode<r == 3>(d[B], base);
-            pair_step2<1, 0, false, OP, false>(f32x2{d[B].x, d[B].y}, xi, yi, zi, st, rx, ry, rz, s2);
-            pair_step2<1, 1, false, OP, false>(f32x2{d[B].z, d[B].w}, xi, yi, zi, st, rx, ry, rz, s2);
+            pair_step2<1, 0, false, OP, r, false>(f32x2{d[B].x, d[B].y}, xrow, st, rx, ry, rz, s2);
+            pair_step2<1, 1, false, OP, r, false>(f32x2{d[B].z, d[B].w}, xrow, st, rx, ry, rz, s2);
             if constexpr (r == 0) d[1] = next.template load<NT>(1);
             if constexpr (r == 1) d[2] = next.template load<NT>(2);
             if constexpr (r == 2) d[5] = next.template load<NT>(5);
             g[3 * r] = rx.x + rx.y; g[3 * r + 1] = ry.x + ry.y; g[3 * r + 2] = rz.x + rz.y;
             row_sums_step<r>(g, h, m);
+            xrow_refresh<r>(xrow, X, xnext, g[3 * r + 2]);
             return;
         }
-        pair_step2<0, 0, true, OP>(f32x2{d[2 * r].x, d[2 * r].y}, xi, yi, zi, st, rx, ry, rz, s2);
-        pair_step2<0, 1, false, OP>(f32x2{d[2 * r].z, d[2 * r].w}, xi, yi, zi, st, rx, ry, rz, s2);
+        pair_step2<0, 0, true, OP, r>(f32x2{d[2 * r].x, d[2 * r].y}, xrow, st, rx, ry, rz, s2);
+        pair_step2<0, 1, false, OP, r>(f32x2{d[2 * r].z, d[2 * r].w}, xrow, st, rx, ry, rz, s2);
         d[2 * r] = next.template load<NT>(2 * r);
         // (no sched_barrier here: letting the scheduler mix the rows of a unit measured
         // 1 % faster at N=50k and 6 % faster at 1/8 size; it stays within 125 VGPRs)
-        pair_step2<1, 0, false, OP>(f32x2{d[2 * r + 1].x, d[2 * r + 1].y}, xi, yi, zi, st, rx, ry, rz, s2);
-        pair_step2<1, 1, false, OP>(f32x2{d[2 * r + 1].z, d[2 * r + 1].w}, xi, yi, zi, st, rx, ry, rz, s2);
+        pair_step2<1, 0, false, OP, r>(f32x2{d[2 * r + 1].x, d[2 * r + 1].y}, xrow, st, rx, ry, rz, s2);
+        pair_step2<1, 1, false, OP, r>(f32x2{d[2 * r + 1].z, d[2 * r + 1].w}, xrow, st, rx, ry, rz, s2);
         d[2 * r + 1] = next.template load<NT>(2 * r + 1);
         g[3 * r] = rx.x + rx.y; g[3 * r + 1] = ry.x + ry.y; g[3 * r + 2] = rz.x + rz.y;
         row_sums_step<r>(g, h, m);
+        xrow_refresh<r>(xrow, X, xnext, g[3 * r + 2]);
     };
     row(std::integral_constant<int, 0>{});
     row(std::integral_constant<int, 1>{});
@@ -680,7 +765,8 @@ __global__ __launch_bounds__(64 * WPB, (Lay<T, W>::MIN_WG)) void stress_grad_ker
 
 // The fp32 sweep over the 24-bit stream: `units` is the stream, `udesc` its int4 table.  Built
 // for the waves per SIMD the sweep runs with (waves_per_cu): two in workgroups of 8 waves, one
-// in workgroups of 4 -- hipcc takes 256 registers for the two bodies in either form, no scratch.
+// in workgroups of 4 -- hipcc takes 256 registers for the two bodies in the first form and 257
+// in the second, no scratch (with a bound of two there as well: 256 and one spilled).
 // Ranks that share a GPU do not use it (ensure_pk24): their kernels share the wave slots.
 // (T = float, W = true only; parameters so that the body's choices by type stay dependent)
 template <typename T, bool W, bool NT, int OP, int WPB>

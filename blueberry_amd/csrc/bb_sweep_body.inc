@@ -80,7 +80,10 @@
         // Prologue: the x rows of the first unit, then its 8 matrix rows.
         // Row coordinates of a unit, one unit ahead.  XRowS: 3*RPU wave-uniform scalars
         // fetched through the scalar cache (X is read-only in this kernel) -- no VMEM
-        // slot, no v_readlane (12 floats or 6 doubles: 12 SGPRs, double-buffered).
+        // slot, no v_readlane (fp64 wide, 6 doubles: 12 SGPRs, double-buffered).
+        // XRowS32 (fp32, 12 floats): six scalar pairs that the subtracts read as they are, ONE
+        // set of 12 SGPRs -- the unit body loads the next unit's over them row by row
+        // (xrow_refresh), so after a unit xr holds the rows of the descriptor that was `dn`.
         // XRowV (fp64 narrow: 24 doubles): one per-lane load, v_readlane per use.
         struct XRowS {
             T v[3 * Lay<T, W>::RPU];
@@ -90,10 +93,20 @@
             T v;
             __device__ __forceinline__ T get(int q) const { return lane_value(v, q); }
         };
-        using XRow = typename std::conditional<Lay<T, W>::SCALAR_XROW, XRowS, XRowV>::type;
+        using XRow = typename std::conditional<
+            sizeof(T) == 4, XRowS32,
+            typename std::conditional<Lay<T, W>::SCALAR_XROW, XRowS, XRowV>::type>::type;
+        // fp32: a unit's rows begin at a multiple of 4 bins, 48 bytes: the pairs are aligned
+        auto xrow_pairs = [&](int i0) __attribute__((always_inline)) {
+            return reinterpret_cast<const f32x2 *>(X + (int64_t)i0 * 3);
+        };
         auto xrow_load = [&](int i0) __attribute__((always_inline)) {
             XRow x;
-            if constexpr (std::is_same<XRow, XRowS>::value) {
+            if constexpr (std::is_same<XRow, XRowS32>::value) {
+                const f32x2 *px = xrow_pairs(i0);
+#pragma unroll
+                for (int q = 0; q < 6; ++q) x.p[q] = px[q];
+            } else if constexpr (std::is_same<XRow, XRowS>::value) {
                 const T *px = X + (int64_t)i0 * 3;
 #pragma unroll
                 for (int q = 0; q < 3 * Lay<T, W>::RPU; ++q) x.v[q] = px[q];
@@ -103,7 +116,9 @@
             return x;
         };
         XRow xr = xrow_load(dc.x);
-        using Win = WinPtr<Vec>;
+        // fp32: a scalar base and the lane's byte offset (WinBase32); fp64: a pointer per lane
+        using Win = typename std::conditional<sizeof(T) == 4, WinBase32, WinPtr<Vec>>::type;
+        [[maybe_unused]] const unsigned lane_off = (unsigned)lane * 16u;
         auto window_of = [&](int u_next) __attribute__((always_inline)) {
             // The refills of the wave's LAST unit are never consumed.  They stay in the
             // loop (a branch around them would cost every unit its exact wait counts),
@@ -113,8 +128,11 @@
             const bool real = u_next < ub;
             if constexpr (PK) {
                 // dn is the table's entry of u_next, or -- clamped -- of the chunk's last unit
-                return Win{reinterpret_cast<const Vec *>(units) + pk24_word_offset(dn) +
-                           (real ? lane : 0)};
+                return Win{units, pk24_word_offset(dn) * 16,
+                           real ? lane_off : 0u};
+            } else if constexpr (sizeof(T) == 4) {
+                return Win{units, (int64_t)(real ? u_next : ub - 1) * 8192,
+                           real ? lane_off : 0u};
             } else {
                 return Win{unit_ptr<T>(units, real ? u_next : ub - 1, real ? lane : 0)};
             }
@@ -122,7 +140,11 @@
         // PK: the window of the CURRENT unit (the prologue, and the two loads a raw run is
         // short of when it begins)
         auto window_here = [&]() __attribute__((always_inline)) {
-            return Win{reinterpret_cast<const Vec *>(units) + pk24_word_offset(dc) + lane};
+            if constexpr (sizeof(T) == 4)
+                return Win{units, pk24_word_offset(dc) * 16,
+                           lane_off};
+            else
+                return Win{reinterpret_cast<const Vec *>(units) + pk24_word_offset(dc) + lane};
         };
         if constexpr (PK) {
             const Win first = window_here();
@@ -160,7 +182,9 @@
             }
             // (the descriptors of the units behind the wave's last one are never used)
             const int un = u + 1 < ub ? u + 1 : u;
-            const XRow xrn = xrow_load(dn.x);
+            // (fp32: the unit body fetches them itself, into xr)
+            [[maybe_unused]] XRow xrn;
+            if constexpr (sizeof(T) != 4) xrn = xrow_load(dn.x);
             const Desc dnn = table[un + 1 < ub ? un + 1 : un];
             // the unit, in the form of <T, W>: where its row sums go, then its math
             const int k = u - ua;
@@ -180,15 +204,12 @@
                 const unsigned row_voff =
                     f32_voff_lane + (parked ? 0x40000000u : (unsigned)k * kRowBytes);
                 const int stage_slot = f32_lds_lane + (parked ? k - park_from : 0) * 12;
-                float xs12[12];             // scalar registers
-#pragma unroll
-                for (int q = 0; q < 12; ++q) xs12[q] = xr.get(q);
                 if constexpr (decltype(packed_body)::value) {
-                    process_unit_f32<NT, OP, true>(d, xs12, window_of(u + 1), st, stress, row_rsrc,
-                                                   row_voff, stage_slot, pk24_base(dc));
+                    process_unit_f32<NT, OP, true>(d, xr, X, (unsigned)dn.x * 12u, window_of(u + 1), st, stress,
+                                                   row_rsrc, row_voff, stage_slot, pk24_base(dc));
                 } else {
-                    process_unit_f32<NT, OP>(d, xs12, window_of(u + 1), st, stress, row_rsrc, row_voff,
-                                             stage_slot);
+                    process_unit_f32<NT, OP>(d, xr, X, (unsigned)dn.x * 12u, window_of(u + 1), st, stress,
+                                             row_rsrc, row_voff, stage_slot);
                 }
             } else if constexpr (W) {
                 // fp64, 2 x 512 units: lanes 48..53 hold one of the unit's 6 sums each
@@ -207,7 +228,7 @@
                 process_unit_f64n<NT, OP>(d, xr, window_of(u + 1), st.xj, st.gc, stress,
                                           row_rsrc, row_voff);
             }
-            xr = xrn;
+            if constexpr (sizeof(T) != 4) xr = xrn;
             dc = dn;
             dn = dnn;
         };
