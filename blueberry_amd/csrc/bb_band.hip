@@ -13,6 +13,7 @@
 #include <cstdlib>
 
 #include "bb_common.h"
+#include "bb_device_sums.h"
 
 namespace {
 
@@ -55,15 +56,12 @@ __global__ __launch_bounds__(kIB) void band_count_kernel(const double *__restric
             cnt += (row_ok && k < lim && lo <= d && d <= hi) ? 1u : 0u;
         }
     }
-    // wavefront shuffle reduction, then one integer atomic per workgroup
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+    // the workgroup's hits (<= kIB * kJC: 32 bits hold them), then one integer atomic
     __shared__ unsigned int wsum[kIB / 64];
-    if ((tid & 63) == 0) wsum[tid >> 6] = cnt;
+    bb::wave_sum_to_lds(cnt, wsum);
     __syncthreads();
     if (tid == 0) {
-        unsigned long long tot = 0;
-        for (int w = 0; w < kIB / 64; ++w) tot += wsum[w];
+        const unsigned long long tot = bb::lds_wave_total(wsum);
         if (tot) atomicAdd(out, tot);
     }
 }
@@ -106,17 +104,16 @@ __global__ __launch_bounds__(kIB) void band_count_sorted_kernel(
         }
         cnt = b > a ? (unsigned long long)(b - a) : 0ull;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
     __shared__ unsigned long long wsum[kIB / 64];
     __shared__ int wbad[kIB / 64];
     const bool any_bad = __ballot(bad) != 0;
-    if ((tid & 63) == 0) { wsum[tid >> 6] = cnt; wbad[tid >> 6] = any_bad ? 1 : 0; }
+    bb::wave_sum_to_lds(cnt, wsum);
+    if ((tid & 63) == 0) wbad[tid >> 6] = any_bad ? 1 : 0;
     __syncthreads();
     if (tid == 0) {
-        unsigned long long tot = 0;
+        const unsigned long long tot = bb::lds_wave_total(wsum);
         int b = 0;
-        for (int w = 0; w < kIB / 64; ++w) { tot += wsum[w]; b |= wbad[w]; }
+        for (int w = 0; w < kIB / 64; ++w) b |= wbad[w];
         if (tot) atomicAdd(out, tot);
         if (b) atomicOr(out + 1, 1ull);
     }

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "bb_common.h"
+#include "bb_device_sums.h"
 
 namespace bb {
 
@@ -139,9 +140,7 @@ __device__ __forceinline__ void symv_item(const double *__restrict__ m, int64_t 
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        double v = racc[r];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        const double v = bb::wave_sum_first(racc[r]);
         if (lane == 0 && row0 + r < n) rowpart[S * n + row0 + r] = v;
     }
 }

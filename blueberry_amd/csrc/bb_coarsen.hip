@@ -31,18 +31,18 @@
 //               between them; within a fine row the thread whose entry is the FIRST of its
 //               coarse column adds that column's run left to right (at most k entries) and
 //               then adds the run's sum to the accumulator, which no other thread touches for
-//               this row.  Run twice: count (which pooled cells exist), rocprim scan, write.
+//               this row.  Run twice: count (which pooled cells exist), scan, write.
 #include <math.h>
 
 #include <algorithm>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "bb_cm_internal.h"
 #include "bb_common.h"
+#include "bb_sort.h"
 #include "bb_triples.h"
 
 namespace bb {
@@ -282,22 +282,18 @@ int bb_cm_coarsen(const bb_cm *src, int64_t n_bins, int64_t factor, int how, bb_
     const int64_t gx = (g.nc + g.rc - 1) / g.rc, gy = (g.nc + g.wct - 1) / g.wct;
     BB_REQUIRE(gy <= 65535, std::string(who) + ": the map is too large");
     hipStream_t st = src->stream;
-    bb::Event ev[2];
-    hipError_t e = ev[0].create();
-    if (e == hipSuccess) e = ev[1].create();
+    bb::StageClock<2> clock;
+    hipError_t e = clock.start();
     // (the lower triangle's and the padding's cells that the kernel does not write)
     if (e == hipSuccess) e = hipMemsetAsync(dst->m, 0, (size_t)dst->d * dst->d * sizeof(double), st);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], st);
+    if (e == hipSuccess) e = clock.mark(0, st);
     if (e == hipSuccess && g.nc > 0)
         e = bb::launch(coarsen_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st,
                        (const double *)src->m, src->d, g, how == BB_COARSEN_MEAN ? 1 : 0, dst->m, dst->d);
-    if (e == hipSuccess) e = hipEventRecord(ev[1], st);
+    if (e == hipSuccess) e = clock.mark(1, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    BB_TRY(bb::hip_status(who, e));
-    dst->coarsen_ms = ms;
-    return BB_OK;
+    if (e == hipSuccess) e = clock.read(0, &dst->coarsen_ms);
+    return bb::hip_status(who, e);
 }
 
 int bb_cm_coarsen_timing(const bb_cm *dst, double *kernel_ms) {
@@ -319,63 +315,46 @@ int bb_triples_coarsen(bb_triples *src, int64_t n_bins, int64_t factor, int how,
     const int64_t nc = (n_bins + k - 1) / k;
     const double R = src->resolution * (double)factor;
     const bb::SegmentedList &rows = src->index.rows;
-    bb_triples *t = new (std::nothrow) bb_triples();
+    std::unique_ptr<bb_triples> t(new (std::nothrow) bb_triples());
     if (!t) return bb::fail(BB_ERR_NOMEM, std::string(who) + ": out of host memory");
     t->device = src->device;
     t->resolution = R;
     hipStream_t st = nullptr;
     bb::DevBuf count, offset, tmp;
-    bb::Event ev[2];
+    bb::StageClock<2> clock;                      // count + scan + write
     size_t scan_bytes = 0;
     u64 total = 0;
-    float ms = 0.f;
     hipError_t e = count.alloc((size_t)(nc + 1) * 8);
     if (e == hipSuccess) e = offset.alloc((size_t)(nc + 1) * 8);
-    if (e == hipSuccess)
-        e = rocprim::exclusive_scan(nullptr, scan_bytes, count.as<u64>(), offset.as<u64>(), (u64)0,
-                                    (size_t)(nc + 1), rocprim::plus<u64>(), st);
+    if (e == hipSuccess) e = bb::exclusive_scan_bytes((size_t)(nc + 1), &scan_bytes);
     if (e == hipSuccess) e = tmp.alloc(scan_bytes);
-    int rc = bb::hip_status(who, e, BB_ERR_NOMEM);
-    if (rc == BB_OK) {
-        e = ev[0].create();
-        if (e == hipSuccess) e = ev[1].create();
-        if (e == hipSuccess) e = hipMemsetAsync(count.p, 0, (size_t)(nc + 1) * 8, st);
-        if (e == hipSuccess) e = hipEventRecord(ev[0], st);
-        if (e == hipSuccess && nc > 0)
-            e = bb::launch(triples_pool_kernel<false>, dim3((unsigned)nc), dim3(256), 0, st,
-                           (const long long *)rows.ptr.p, (const int *)rows.other.p,
-                           (const double *)rows.val.p, n_bins, k, nc, 0, R, (const u64 *)nullptr,
-                           count.as<u64>(), (double *)nullptr);
-        // (count[nc] is 0: offset[nc] is the number of pooled cells)
-        if (e == hipSuccess)
-            e = rocprim::exclusive_scan(tmp.p, scan_bytes, count.as<u64>(), offset.as<u64>(), (u64)0,
-                                        (size_t)(nc + 1), rocprim::plus<u64>(), st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = hipMemcpy(&total, offset.as<u64>() + nc, 8, hipMemcpyDeviceToHost);
-        rc = bb::hip_status(who, e);
-    }
-    if (rc == BB_OK) {
-        t->n = (int64_t)total;
-        rc = bb::hip_status(who, t->d.alloc((size_t)total * 24), BB_ERR_NOMEM);
-    }
-    if (rc == BB_OK) {
-        e = hipSuccess;
-        if (total > 0)
-            e = bb::launch(triples_pool_kernel<true>, dim3((unsigned)nc), dim3(256), 0, st,
-                           (const long long *)rows.ptr.p, (const int *)rows.other.p,
-                           (const double *)rows.val.p, n_bins, k, nc, how == BB_COARSEN_MEAN ? 1 : 0, R,
-                           (const u64 *)offset.p, (u64 *)nullptr, t->d.as<double>());
-        if (e == hipSuccess) e = hipEventRecord(ev[1], st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-        rc = bb::hip_status(who, e);
-    }
-    if (rc != BB_OK) {
-        delete t;
-        return rc;
-    }
-    t->coarsen_ms = ms;
-    *out = t;
+    BB_TRY(bb::hip_status(who, e, BB_ERR_NOMEM));
+    e = clock.start();
+    if (e == hipSuccess) e = hipMemsetAsync(count.p, 0, (size_t)(nc + 1) * 8, st);
+    if (e == hipSuccess) e = clock.mark(0, st);
+    if (e == hipSuccess && nc > 0)
+        e = bb::launch(triples_pool_kernel<false>, dim3((unsigned)nc), dim3(256), 0, st,
+                       (const long long *)rows.ptr.p, (const int *)rows.other.p,
+                       (const double *)rows.val.p, n_bins, k, nc, 0, R, (const u64 *)nullptr,
+                       count.as<u64>(), (double *)nullptr);
+    // (count[nc] is 0: offset[nc] is the number of pooled cells)
+    if (e == hipSuccess)
+        e = bb::exclusive_scan(tmp.p, scan_bytes, count.as<u64>(), offset.as<u64>(), (size_t)(nc + 1), st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipMemcpy(&total, offset.as<u64>() + nc, 8, hipMemcpyDeviceToHost);
+    BB_TRY(bb::hip_status(who, e));
+    t->n = (int64_t)total;
+    BB_TRY(bb::hip_status(who, t->d.alloc((size_t)total * 24), BB_ERR_NOMEM));
+    if (total > 0)
+        e = bb::launch(triples_pool_kernel<true>, dim3((unsigned)nc), dim3(256), 0, st,
+                       (const long long *)rows.ptr.p, (const int *)rows.other.p,
+                       (const double *)rows.val.p, n_bins, k, nc, how == BB_COARSEN_MEAN ? 1 : 0, R,
+                       (const u64 *)offset.p, (u64 *)nullptr, t->d.as<double>());
+    if (e == hipSuccess) e = clock.mark(1, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = clock.read(0, &t->coarsen_ms);
+    BB_TRY(bb::hip_status(who, e));
+    *out = t.release();
     return BB_OK;
 }
 

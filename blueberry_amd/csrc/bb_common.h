@@ -176,6 +176,40 @@ struct Event {
     }
 };
 
+// The clock of a call's stages: K events, stage k being what a stream does between mark(k) and
+// mark(k + 1).  start(false) leaves it off: no event is made, a mark does nothing and every stage
+// reads 0, so a call writes its marks once, timed or not.  A stage whose end was never marked -- one
+// the call skipped -- reads 0 too.  It never synchronises: read after the caller's own wait.
+template <int K>
+struct StageClock {
+    Event ev[K];
+    bool marked[K] = {};
+    bool on = false;
+    hipError_t start(bool want = true) {
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < K && want && e == hipSuccess; ++k) e = ev[k].create();
+        on = want && e == hipSuccess;
+        return e;
+    }
+    hipError_t mark(int k, hipStream_t stream) {
+        if (!on) return hipSuccess;
+        marked[k] = true;
+        return hipEventRecord(ev[k], stream);
+    }
+    hipError_t read(int k, double *ms) const {
+        float t = 0.f;
+        const hipError_t e =
+            on && marked[k] && marked[k + 1] ? hipEventElapsedTime(&t, ev[k], ev[k + 1]) : hipSuccess;
+        *ms = t;
+        return e;
+    }
+    hipError_t read_all(double *ms) const {   // ms[0 .. K - 2]
+        hipError_t e = hipSuccess;
+        for (int k = 0; k + 1 < K && e == hipSuccess; ++k) e = read(k, ms + k);
+        return e;
+    }
+};
+
 // Scratch kept per device between calls: a stream made on first use and ONE grow-only arena,
 // guarded by a mutex -- calls that share a scratch serialise, which is what one stream would
 // do anyway.  What it saves, and when the arena is given back, is told where each is used.

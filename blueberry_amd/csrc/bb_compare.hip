@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "bb_common.h"
+#include "bb_device_sums.h"
 #include "bb_sort.h"
 
 namespace {
@@ -67,29 +68,6 @@ __device__ __forceinline__ void add_pair(double (&a)[kProfileCols], double da, d
     a[6] += res * res;
 }
 
-// Sum over the 64 lanes, the same bits in every lane (a + b = b + a): fixed butterfly.
-__device__ __forceinline__ double wave_sum_all(double v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// The sums of a workgroup of 256 threads, in every thread: the wave butterfly, then the 4 waves
-// in their order.  sh: Q x 4 doubles of LDS.
-template <int Q>
-__device__ __forceinline__ void block_sum_all(double (&v)[Q], double (*sh)[4]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        v[q] = wave_sum_all(v[q]);
-        if (lane == 0) sh[q][wave] = v[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < Q; ++q) v[q] = ((sh[q][0] + sh[q][1]) + sh[q][2]) + sh[q][3];
-    __syncthreads();
-}
-
 // partials[g][q] = over the used bins of workgroup g's 1,024: the count, sum A (3), sum B (3)
 __global__ __launch_bounds__(256) void cmp_sum_kernel(const double *__restrict__ a,
                                                       const double *__restrict__ b,
@@ -108,7 +86,7 @@ __global__ __launch_bounds__(256) void cmp_sum_kernel(const double *__restrict__
             }
         }
     }
-    block_sum_all<7>(v, sh);
+    bb::block_sums_all(v, sh);
     if (threadIdx.x < 7) partials[(int64_t)blockIdx.x * 7 + threadIdx.x] = v[threadIdx.x];
 }
 
@@ -141,7 +119,7 @@ __global__ __launch_bounds__(256) void cmp_centred_kernel(const double *__restri
                 for (int q = 0; q < 3; ++q) v[2 + 3 * p + q] += db[p] * da[q];
         }
     }
-    block_sum_all<11>(v, sh);
+    bb::block_sums_all(v, sh);
     if (threadIdx.x < 11) partials[(int64_t)blockIdx.x * 11 + threadIdx.x] = v[threadIdx.x];
 }
 
@@ -157,7 +135,7 @@ __global__ __launch_bounds__(256) void cmp_reduce_kernel(const double *__restric
     for (int64_t g = threadIdx.x; g < n_parts; g += 256)
 #pragma unroll
         for (int q = 0; q < Q; ++q) v[q] += partials[g * Q + q];
-    block_sum_all<Q>(v, sh);
+    bb::block_sums_all(v, sh);
     if (threadIdx.x == 0)
 #pragma unroll
         for (int q = 0; q < Q; ++q) out[q] = (as_mean && q > 0) ? v[q] / v[0] : v[q];
@@ -352,7 +330,7 @@ __global__ __launch_bounds__(256) void cmp_bins_kernel(const double *__restrict_
     }
 #pragma unroll
     for (int w = 0; w < kBinsPerWave; ++w) {
-        const double c = wave_sum_all(cnt[w]), s = wave_sum_all(sq[w]);
+        const double c = bb::wave_sum_all(cnt[w]), s = bb::wave_sum_all(sq[w]);
         if (lane == 0 && first + w < n) {
             bins[(first + w) * kBinCols] = c;
             bins[(first + w) * kBinCols + 1] = s;
@@ -425,7 +403,7 @@ __global__ __launch_bounds__(256) void cmp_rank_sum_kernel(const double *__restr
         v[1] += y * y;
         v[2] += x * y;
     }
-    block_sum_all<3>(v, sh);
+    bb::block_sums_all(v, sh);
     if (threadIdx.x < 3) partials[(int64_t)blockIdx.x * 3 + threadIdx.x] = v[threadIdx.x];
 }
 
@@ -574,23 +552,22 @@ int bb_structures_compare(const double *a, const double *b, const uint8_t *use, 
     BB_HIP_CHECK(hipMemcpyAsync(d_chunk_ptr, chunk_ptr.data(), chunk_ptr.size() * sizeof(int),
                                 hipMemcpyHostToDevice, st));
     BB_HIP_CHECK(hipMemcpyAsync(d_tr, transform13, 13 * 8, hipMemcpyHostToDevice, st));
-    bb::Event ev[6];
-    if (ms)
-        for (bb::Event &e : ev) BB_HIP_CHECK(e.create());
-    if (ms) BB_HIP_CHECK(hipEventRecord(ev[0], st));
+    bb::StageClock<6> clock;                         // transform | pairs | fold | bins | ranks
+    BB_HIP_CHECK(clock.start(ms != nullptr));
+    BB_HIP_CHECK(clock.mark(0, st));
     BB_HIP_CHECK(bb::launch(cmp_transform_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                             (const double *)d_a, (const double *)d_b, (const uint8_t *)d_use, n,
                             (const double *)d_tr, d_al, d_dev));
-    if (ms) BB_HIP_CHECK(hipEventRecord(ev[1], st));
+    BB_HIP_CHECK(clock.mark(1, st));
     BB_HIP_CHECK(bb::launch(cmp_pairs_kernel, dim3((unsigned)n_chunks), dim3(256), 0, st, (const double *)d_a,
                             (const double *)d_al, (const uint8_t *)d_use, n, (const int4 *)d_chunks, d_slots));
-    if (ms) BB_HIP_CHECK(hipEventRecord(ev[2], st));
+    BB_HIP_CHECK(clock.mark(2, st));
     BB_HIP_CHECK(bb::launch(cmp_fold_kernel, dim3((unsigned)((n + 255) / 256), kProfileCols), dim3(256), 0, st,
                             (const double *)d_slots, (const int *)d_chunk_ptr, (int)nb, n, d_profile));
-    if (ms) BB_HIP_CHECK(hipEventRecord(ev[3], st));
+    BB_HIP_CHECK(clock.mark(3, st));
     BB_HIP_CHECK(bb::launch(cmp_bins_kernel, dim3((unsigned)((n + kBinsPerBlock - 1) / kBinsPerBlock)), dim3(256),
                             0, st, (const double *)d_a, (const double *)d_al, (const uint8_t *)d_use, n, d_bins));
-    if (ms) BB_HIP_CHECK(hipEventRecord(ev[4], st));
+    BB_HIP_CHECK(clock.mark(4, st));
     if (aligned) BB_HIP_CHECK(hipMemcpyAsync(aligned, d_al, (size_t)n * 24, hipMemcpyDeviceToHost, st));
     BB_HIP_CHECK(hipMemcpyAsync(bin_dev, d_dev, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     BB_HIP_CHECK(hipMemcpyAsync(profile, d_profile, (size_t)n * kProfileCols * 8, hipMemcpyDeviceToHost, st));
@@ -621,17 +598,12 @@ int bb_structures_compare(const double *a, const double *b, const uint8_t *use, 
                                 (const double *)rb, m, per, d_part));
         BB_HIP_CHECK(bb::launch(cmp_reduce_kernel<3>, dim3(1), dim3(256), 0, st, (const double *)d_part, groups, 0,
                                 d_sums));
-        if (ms) BB_HIP_CHECK(hipEventRecord(ev[5], st));
+        BB_HIP_CHECK(clock.mark(5, st));
         BB_HIP_CHECK(hipMemcpyAsync(rank_sums + 1, d_sums, 3 * 8, hipMemcpyDeviceToHost, st));
         BB_HIP_CHECK(hipStreamSynchronize(st));      // (work is still alive)
     }
     BB_HIP_CHECK(hipStreamSynchronize(st));
-    if (ms)
-        for (int k = 0; k < (ranks ? 5 : 4); ++k) {
-            float t = 0.f;
-            BB_HIP_CHECK(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
-            ms[k] = t;
-        }
+    if (ms) BB_HIP_CHECK(clock.read_all(ms));        // (no ranks: that entry is 0)
     return BB_OK;
 }
 

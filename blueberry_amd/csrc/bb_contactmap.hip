@@ -402,9 +402,7 @@ __global__ __launch_bounds__(256) void center_rows_kernel(const double *__restri
     const double *p = m + row * d;
     double acc = 0.0;
     for (int64_t c = lane; c < d; c += 64) acc += p[c];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    const double mean = acc / (double)d;
+    const double mean = bb::wave_sum_all(acc) / (double)d;
     double *q = xc + row * ldx;
     for (int64_t c = lane; c < d; c += 64) q[c] = p[c] - mean;
 }
@@ -445,14 +443,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
     double acc = 0.0;
 #pragma unroll
     for (int q = 0; q < CH; ++q) acc += v[q];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if (lane == 0) part[wv] = acc;
+    bb::wave_sum_to_lds(acc, part);
     __syncthreads();
-    double tot = 0.0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) tot += part[k];      // every thread, the same order
-    const double mean = tot / (double)d;
+    const double mean = bb::lds_wave_total(part) / (double)d;   // every thread, the same order
 #pragma unroll
     for (int q = 0; q < CH; ++q) {
         const double o = c0 + 64 * q < (int)d ? v[q] - mean : 0.0;      // d .. ldx: the padding
@@ -1110,7 +1103,7 @@ int bb_cm_correlation(bb_cm *cm, double *tflops) {
     g.p = (char *)scr->buf.p + xc_bytes;
     sd.p = (char *)scr->buf.p + xc_bytes + g_bytes;
     hipStream_t st = cm->stream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bb::StageClock<2> clock;                         // the Gram kernel
     const double fact_inv = 1.0 / (double)(d - 1);   // numpy: true_divide(1, N - ddof); d = 1 -> inf
     // a whole row in the registers of one workgroup where it fits (d <= 32,768); else two passes
     const int ch = d >= 2048 && d <= 32768 ? (int)((d + 1023) / 1024) : 0;
@@ -1130,15 +1123,14 @@ int bb_cm_correlation(bb_cm *cm, double *tflops) {
               : ch <= 24 ? BB_CENTER(24) : BB_CENTER(32);
 #undef BB_CENTER
     }
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, st);
+    if (e == hipSuccess) e = clock.start(tflops != nullptr);
+    if (e == hipSuccess) e = clock.mark(0, st);
     const unsigned nt = (unsigned)(dp / kGT);
     const unsigned np = (nt + kGP - 1) / kGP;
     if (e == hipSuccess)
         e = bb::launch(gram_kernel, dim3(np * np * kGP * kGP), dim3(256), 0, st,
                        (const double *)xc.p, ldx, (double *)g.p, dp, (int)nt);
-    if (e == hipSuccess) e = hipEventRecord(e1, st);
+    if (e == hipSuccess) e = clock.mark(1, st);
     if (e == hipSuccess)
         e = bb::launch(gram_diag_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st,
                        (const double *)g.p, dp, d, fact_inv, (double *)sd.p);
@@ -1149,14 +1141,12 @@ int bb_cm_correlation(bb_cm *cm, double *tflops) {
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess && tflops) {
-        float ms = 0.f;
-        e = hipEventElapsedTime(&ms, e0, e1);
+        double ms = 0.0;
+        e = clock.read(0, &ms);
         // flops of the tiles that were computed: nt (nt + 1) / 2 tiles of 2 * 128 * 128 * ldx
-        *tflops = ms > 0.f ? (double)nt * (nt + 1) / 2 * 2.0 * kGT * kGT * (double)ldx / (ms * 1e-3) / 1e12
+        *tflops = ms > 0.0 ? (double)nt * (nt + 1) / 2 * 2.0 * kGT * kGT * (double)ldx / (ms * 1e-3) / 1e12
                            : 0.0;
     }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
     return bb::hip_status("bb_cm_correlation", e);
 }
 

@@ -264,30 +264,28 @@ int bb::q_values_device(const char *who, const double *p, int64_t m, int64_t n_t
     double *ps = (double *)(base + 2 * k8 + 2 * k4), *qs = (double *)(base + 3 * k8 + 2 * k4);
     void *bh_work = base + 4 * k8 + 2 * k4;
     const dim3 grid((unsigned)((m + 255) / 256)), block(256);
-    bb::Event ev[3];
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = ev[i].create();
-    if (e == hipSuccess) e = hipEventRecord(ev[0], st);
+    bb::StageClock<3> clock;                      // sort | gather, scan, scatter
+    hipError_t e = clock.start(sort_ms != nullptr || scan_ms != nullptr);
+    if (e == hipSuccess) e = clock.mark(0, st);
     if (e == hipSuccess) e = bb::launch(qv_key_kernel, grid, block, 0, st, p, m, ka, ia);
     if (e == hipSuccess) {
         e = bb::stable_sort_pairs<uint32_t>(ka, ia, kb, ib, m, 64, st);   // (ia: the sorted order)
         if (e == hipErrorOutOfMemory) return bb::hip_status(who, e, BB_ERR_NOMEM);
     }
-    if (e == hipSuccess) e = hipEventRecord(ev[1], st);
+    if (e == hipSuccess) e = clock.mark(1, st);
     if (e == hipSuccess) e = bb::launch(qv_gather_kernel, grid, block, 0, st, p, (const uint32_t *)ia, m, ps);
     if (e == hipSuccess) e = bb::bh_scan_enqueue(ps, m, (double)n_tests, qs, bh_work, st);
     if (e == hipSuccess)
         e = bb::launch(qv_scatter_kernel, grid, block, 0, st, (const double *)qs, (const uint32_t *)ia, m, q);
-    if (e == hipSuccess) e = hipEventRecord(ev[2], st);
+    if (e == hipSuccess) e = clock.mark(2, st);
     if (e == hipSuccess && order != nullptr)
         e = hipMemcpyAsync(order, ia, (size_t)m * 4, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    float a = 0.f, b = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&a, ev[0], ev[1]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&b, ev[1], ev[2]);
+    double ms[2] = {0.0, 0.0};
+    if (e == hipSuccess) e = clock.read_all(ms);
     BB_TRY(bb::hip_status(who, e));
-    if (sort_ms) *sort_ms = a;
-    if (scan_ms) *scan_ms = b;
+    if (sort_ms) *sort_ms = ms[0];
+    if (scan_ms) *scan_ms = ms[1];
     return BB_OK;
 }
 

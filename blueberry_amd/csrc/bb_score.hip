@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "bb_common.h"
+#include "bb_device_sums.h"
 #include "bb_score.h"
 
 namespace {
@@ -86,13 +87,6 @@ struct LogTerms {
         a[5] += u * v;
     }
 };
-
-// Sum over the 64 lanes, the same bits in every lane (a + b = b + a): fixed butterfly.
-__device__ __forceinline__ double wave_sum_all(double v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 
 // runs[b] = {first local unit, units} of run b: consecutive local units of ONE tile (same strip
 // j0, same block of rows I0 = i0 - i0 % VW).  Thread t owns the diagonals o = t + 256 m of the
@@ -237,9 +231,9 @@ __global__ __launch_bounds__(256) void score_bins_kernel(const T *__restrict__ u
         for (int q = 0; q < RPU; ++q)
             if (p * RPU + q < i) add((double)col[q * VW], p * RPU + q);
     }
-    cnt = wave_sum_all(cnt);
-    sq = wave_sum_all(sq);
-    rel = wave_sum_all(rel);
+    cnt = bb::wave_sum_all(cnt);
+    sq = bb::wave_sum_all(sq);
+    rel = bb::wave_sum_all(rel);
     if (lane == 0) {
         bins[i * kBinCols] = cnt;
         bins[i * kBinCols + 1] = sq;
@@ -301,32 +295,26 @@ int score_pass_t(const bb::ScoreInput &in, double *profile, double *bins, double
                                 hipMemcpyHostToDevice, st));
     BB_HIP_CHECK(hipMemcpyAsync(d_diff_runs, diff_runs.data(), (size_t)n_runs * sizeof(int),
                                 hipMemcpyHostToDevice, st));
-    bb::Event ev[4];
-    if (ms)
-        for (bb::Event &e : ev) BB_HIP_CHECK(e.create());
-    if (ms) BB_HIP_CHECK(hipEventRecord(ev[0], st));
+    bb::StageClock<4> clock;                         // profile | fold | bins
+    BB_HIP_CHECK(clock.start(ms != nullptr));
+    BB_HIP_CHECK(clock.mark(0, st));
     BB_HIP_CHECK(bb::launch(score_profile_kernel<T, VW, RPU, Terms>, dim3((unsigned)n_runs), dim3(256), 0, st,
                             (const T *)in.d_units, in.d_udesc, d_runs, in.d_xyz, n, d_slots));
-    if (ms) BB_HIP_CHECK(hipEventRecord(ev[1], st));
+    BB_HIP_CHECK(clock.mark(1, st));
     BB_HIP_CHECK(bb::launch(score_fold_kernel<VW, COLS>, dim3((unsigned)((n + 255) / 256), COLS), dim3(256),
                             0, st, d_slots, d_diff_ptr, d_diff_runs, (int)n_blocks, n, d_profile));
-    if (ms) BB_HIP_CHECK(hipEventRecord(ev[2], st));
+    BB_HIP_CHECK(clock.mark(2, st));
     if (bins) {
         BB_HIP_CHECK(bb::launch(score_bins_kernel<T, VW, RPU>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st,
                                 (const T *)in.d_units, in.d_udesc, in.n_local, in.d_xyz, n, d_bins));
-        if (ms) BB_HIP_CHECK(hipEventRecord(ev[3], st));
+        BB_HIP_CHECK(clock.mark(3, st));
     }
     BB_HIP_CHECK(hipMemcpyAsync(profile, d_profile, (size_t)n * COLS * sizeof(double),
                                 hipMemcpyDeviceToHost, st));
     if (bins)
         BB_HIP_CHECK(hipMemcpyAsync(bins, d_bins, (size_t)n * kBinCols * sizeof(double), hipMemcpyDeviceToHost, st));
     BB_HIP_CHECK(hipStreamSynchronize(st));
-    if (ms)
-        for (int k = 0; k < (bins ? 3 : 2); ++k) {       // (no per-bin kernel: its entry stays 0)
-            float t = 0.f;
-            BB_HIP_CHECK(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
-            ms[k] = t;
-        }
+    if (ms) BB_HIP_CHECK(clock.read_all(ms));        // (no per-bin kernel: its entry is 0)
     return BB_OK;
 }
 

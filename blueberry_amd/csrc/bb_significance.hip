@@ -37,11 +37,10 @@
 #include <memory>
 #include <string>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "bb_cm_internal.h"
 #include "bb_common.h"
 #include "bb_qvalues.h"
+#include "bb_sort.h"
 #include "bb_triples.h"
 
 namespace bb {
@@ -267,9 +266,7 @@ __global__ void sig_total_kernel(const u64 *__restrict__ counts, const u64 *__re
 
 // terms of the wave's lanes into the status, one integer atomic per wave
 __device__ __forceinline__ void sf_account(int terms, int capped, SigStatus *__restrict__ status) {
-    u64 t = (u64)terms;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+    const u64 t = bb::wave_sum_first((u64)terms);
     if ((threadIdx.x & 63) == 0 && t != 0) atomicAdd(&status->terms, t);
     if (capped) status->capped = 1;
 }
@@ -345,9 +342,7 @@ int significance_run(const std::string &who, int device, hipStream_t st, int64_t
     const size_t vec = bb::align256((size_t)n * 8), cells = bb::align256((size_t)std::max<int64_t>(items, 1) * 8);
     size_t scan_bytes = 0;
     hipError_t e = hipSuccess;
-    if (items > 0)
-        e = rocprim::exclusive_scan(nullptr, scan_bytes, (u64 *)nullptr, (u64 *)nullptr, (u64)0, (size_t)items,
-                                    rocprim::plus<u64>(), st);
+    if (items > 0) e = bb::exclusive_scan_bytes((size_t)items, &scan_bytes);
     BB_TRY(bb::hip_status(who.c_str(), e));
     bb::DevBuf work;
     BB_TRY(bb::hip_status(who.c_str(), work.alloc(2 * vec + 256 + 2 * cells + scan_bytes), BB_ERR_NOMEM));
@@ -358,16 +353,15 @@ int significance_run(const std::string &who, int device, hipStream_t st, int64_t
     void *scan_tmp = base + 2 * vec + 256 + 2 * cells;
     g.bias = dbias;
     g.f = df;
-    bb::Event ev[3];
-    for (int q = 0; q < 3 && e == hipSuccess; ++q) e = ev[q].create();
+    bb::StageClock<3> clock;                      // the list | its p-values
+    e = clock.start();
     if (e == hipSuccess) e = hipMemcpyAsync(dbias, bias, (size_t)n * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(df, prior, (size_t)n * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(status, 0, sizeof(SigStatus), st);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], st);
+    if (e == hipSuccess) e = clock.mark(0, st);
     if (e == hipSuccess && items > 0) e = pass(false, g, counts, offset, nullptr, nullptr, nullptr, status);
     if (e == hipSuccess && items > 0)
-        e = rocprim::exclusive_scan(scan_tmp, scan_bytes, counts, offset, (u64)0, (size_t)items,
-                                    rocprim::plus<u64>(), st);
+        e = bb::exclusive_scan(scan_tmp, scan_bytes, counts, offset, (size_t)items, st);
     if (e == hipSuccess)
         e = bb::launch(sig_total_kernel, dim3(1), dim3(1), 0, st, (const u64 *)counts, (const u64 *)offset,
                        items, status);
@@ -395,24 +389,21 @@ int significance_run(const std::string &who, int device, hipStream_t st, int64_t
     BB_TRY(bb::hip_status(who.c_str(), e, BB_ERR_NOMEM));
     if (items > 0 && m > 0)
         e = pass(true, g, counts, offset, sig->row.as<int>(), sig->col.as<int>(), sig->count.as<double>(), status);
-    if (e == hipSuccess) e = hipEventRecord(ev[1], st);
+    if (e == hipSuccess) e = clock.mark(1, st);
     if (e == hipSuccess && m > 0)
         e = bb::launch(sig_p_kernel, dim3((unsigned)((m + kSfBlock - 1) / kSfBlock)), dim3(kSfBlock), 0, st,
                        (const int *)sig->row.p, (const int *)sig->col.p, (const double *)sig->count.p,
                        (int64_t)m, (const double *)dbias, (const double *)df, g.n_total, sig->p.as<double>(),
                        status);
-    if (e == hipSuccess) e = hipEventRecord(ev[2], st);
+    if (e == hipSuccess) e = clock.mark(2, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipMemcpy(&hs, status, sizeof(hs), hipMemcpyDeviceToHost);
-    float list_ms = 0.f, p_ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&list_ms, ev[0], ev[1]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&p_ms, ev[1], ev[2]);
+    if (e == hipSuccess) e = clock.read(0, &sig->list_ms);
+    if (e == hipSuccess) e = clock.read(1, &sig->p_ms);
     BB_TRY(bb::hip_status(who.c_str(), e));
     if (hs.capped != 0)
         return bb::fail(BB_ERR_STATE, who + ": a binomial tail sum ran into its cap of terms; no result");
     sig->terms = (int64_t)hs.terms;
-    sig->list_ms = list_ms;
-    sig->p_ms = p_ms;
     *out = sig.release();
     return BB_OK;
 }
@@ -595,8 +586,7 @@ int bb_sig_select(const bb_sig *s, double q_max, bb_sig **out) {
         // keep | pos | the scan's temporary storage
         const size_t cells = bb::align256((size_t)m * 8);
         size_t scan_bytes = 0;
-        e = rocprim::exclusive_scan(nullptr, scan_bytes, (u64 *)nullptr, (u64 *)nullptr, (u64)0, (size_t)m,
-                                    rocprim::plus<u64>(), st);
+        e = bb::exclusive_scan_bytes((size_t)m, &scan_bytes);
         BB_TRY(bb::hip_status(who, e));
         BB_TRY(bb::hip_status(who, work.alloc(2 * cells + scan_bytes), BB_ERR_NOMEM));
         keep = (u64 *)work.p;
@@ -604,8 +594,7 @@ int bb_sig_select(const bb_sig *s, double q_max, bb_sig **out) {
         e = bb::launch(sig_keep_kernel, dim3((unsigned)((m + kSfBlock - 1) / kSfBlock)), dim3(kSfBlock), 0, st,
                        (const double *)s->q.p, m, q_max, keep);
         if (e == hipSuccess)
-            e = rocprim::exclusive_scan((char *)work.p + 2 * cells, scan_bytes, keep, pos, (u64)0, (size_t)m,
-                                        rocprim::plus<u64>(), st);
+            e = bb::exclusive_scan((char *)work.p + 2 * cells, scan_bytes, keep, pos, (size_t)m, st);
         u64 last_pos = 0, last_keep = 0;
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e == hipSuccess) e = hipMemcpy(&last_pos, pos + (m - 1), 8, hipMemcpyDeviceToHost);

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <cmath>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <tuple>
 
@@ -1168,21 +1169,17 @@ int bb_triples_create(bb_triples **out, const double *triples, int64_t n, int32_
     BB_REQUIRE(n >= 0 && (n == 0 || triples != nullptr), "bb_triples_create: NULL triples");
     BB_REQUIRE(resolution > 0, "bb_triples_create: resolution must be positive");
     BB_TRY(bb::use_device(device));
-    bb_triples *t = new (std::nothrow) bb_triples();
+    std::unique_ptr<bb_triples> t(new (std::nothrow) bb_triples());
     if (!t) return bb::fail(BB_ERR_NOMEM, "bb_triples_create: out of host memory");
     t->device = device;
     t->n = n;
     t->resolution = (double)resolution;
     if (row_major) { t->st = 3; t->sc = 1; } else { t->st = 1; t->sc = n; }
-    int rc = bb::alloc_status(t->d, (size_t)(3 * n) * sizeof(double));
-    if (rc == BB_OK && n > 0)
-        rc = bb::hip_status("bb_triples_create",
-                            hipMemcpy(t->d.p, triples, (size_t)n * 24, hipMemcpyHostToDevice));
-    if (rc != BB_OK) {
-        delete t;
-        return rc;
-    }
-    *out = t;
+    BB_TRY(bb::alloc_status(t->d, (size_t)(3 * n) * sizeof(double)));
+    if (n > 0)
+        BB_TRY(bb::hip_status("bb_triples_create",
+                              hipMemcpy(t->d.p, triples, (size_t)n * 24, hipMemcpyHostToDevice)));
+    *out = t.release();
     return BB_OK;
 }
 
@@ -2062,25 +2059,24 @@ int bb_solver_measure_event_gap(bb_solver *s, int pairs, double *ms_avg) {
     BB_REQUIRE(pairs >= 1 && pairs <= 256, "bb_solver_measure_event_gap: bad pairs");
     BB_TRY(check_ready(s, "bb_solver_measure_event_gap"));
     BB_TRY(bb::enter_device(s->device));
-    std::vector<bb::Event> ev((size_t)2 * pairs);
+    std::vector<bb::StageClock<2>> gap((size_t)pairs);   // a clock per pair: its one stage is empty
     hipError_t e = hipSuccess;
-    for (bb::Event &x : ev)
-        if (e == hipSuccess) e = x.create();
+    for (bb::StageClock<2> &g : gap)
+        if (e == hipSuccess) e = g.start();
     for (int k = 0; k < pairs && e == hipSuccess; ++k) {
         // behind a sweep launch, as the timed intervals are (the sweep only writes partials)
         if (!s->row_owner && launch_grad(s) != BB_OK) e = hipErrorUnknown;
-        if (e == hipSuccess) e = hipEventRecord(ev[(size_t)2 * k], s->stream);
-        if (e == hipSuccess) e = hipEventRecord(ev[(size_t)2 * k + 1], s->stream);
+        if (e == hipSuccess) e = gap[(size_t)k].mark(0, s->stream);
+        if (e == hipSuccess) e = gap[(size_t)k].mark(1, s->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
     double t = 0.0;
     for (int k = 0; k < pairs && e == hipSuccess; ++k) {
-        float a = 0.f;
-        e = hipEventElapsedTime(&a, ev[(size_t)2 * k], ev[(size_t)2 * k + 1]);
+        double a = 0.0;
+        e = gap[(size_t)k].read(0, &a);
         t += a;
     }
-    if (e != hipSuccess)
-        return bb::hip_status("bb_solver_measure_event_gap", e);
+    BB_TRY(bb::hip_status("bb_solver_measure_event_gap", e));
     *ms_avg = t / pairs;
     return BB_OK;
 }
@@ -2091,9 +2087,8 @@ int bb_solver_measure_stream_read(bb_solver *s, int launches, double *ms_avg) {
     if (!s->have_wish)
         return bb::fail(BB_ERR_STATE, "bb_solver_measure_stream_read: no wish distances set");
     BB_TRY(bb::enter_device(s->device));
-    bb::Event e0, e1;
-    BB_HIP_CHECK(e0.create());
-    BB_HIP_CHECK(e1.create());
+    bb::StageClock<2> clock;
+    BB_HIP_CHECK(clock.start());
     if (s->dtype == BB_F32) BB_TRY(ensure_pk24(s));
     auto launch = [&]() {
         // what the sweep reads: the 24-bit stream when it is in use
@@ -2108,12 +2103,12 @@ int bb_solver_measure_stream_read(bb_solver *s, int launches, double *ms_avg) {
                           (float *)s->d_f64_tmp);
     };
     BB_HIP_CHECK(launch());  // warm-up
-    BB_HIP_CHECK(hipEventRecord(e0, s->stream));
+    BB_HIP_CHECK(clock.mark(0, s->stream));
     for (int k = 0; k < launches; ++k) BB_HIP_CHECK(launch());
-    BB_HIP_CHECK(hipEventRecord(e1, s->stream));
-    BB_HIP_CHECK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    BB_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    BB_HIP_CHECK(clock.mark(1, s->stream));
+    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
+    double ms = 0.0;
+    BB_HIP_CHECK(clock.read(0, &ms));
     *ms_avg = ms / launches;
     return BB_OK;
 }

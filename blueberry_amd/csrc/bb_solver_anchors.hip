@@ -182,18 +182,17 @@ int bb_solver_measure_anchors(bb_solver *s, int launches, double *ms_avg) {
     if (s->grad_pending)
         return bb::fail(BB_ERR_STATE, "bb_solver_measure_anchors: a bb_solver_grad is pending");
     BB_TRY(bb::enter_device(s->device));
-    bb::Event e0, e1;
-    BB_HIP_CHECK(e0.create());
-    BB_HIP_CHECK(e1.create());
+    bb::StageClock<2> clock;
+    BB_HIP_CHECK(clock.start());
     // (the exchange buffer holds nothing anybody waits for: no gradient is pending)
     BB_HIP_CHECK(hipMemsetAsync(s->d_exch, 0, (size_t)(3 * s->L.n_pad + 2) * bb::elem_size(s->dtype), s->stream));
     BB_TRY(launch_anchors(s, kAnchorFoldExchange));   // warm-up
-    BB_HIP_CHECK(hipEventRecord(e0, s->stream));
+    BB_HIP_CHECK(clock.mark(0, s->stream));
     for (int k = 0; k < launches; ++k) BB_TRY(launch_anchors(s, kAnchorFoldExchange));
-    BB_HIP_CHECK(hipEventRecord(e1, s->stream));
-    BB_HIP_CHECK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    BB_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    BB_HIP_CHECK(clock.mark(1, s->stream));
+    BB_HIP_CHECK(hipStreamSynchronize(s->stream));
+    double ms = 0.0;
+    BB_HIP_CHECK(clock.read(0, &ms));
     *ms_avg = ms / launches;
     return BB_OK;
 }

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bb_device_sums.h"
+
 namespace {
 
 // --------------------------------------------------------------------------
@@ -28,20 +30,8 @@ __global__ __launch_bounds__(1024) void gram3_kernel(const TA *__restrict__ A,
         acc[6] = fma(a2, b0, acc[6]); acc[7] = fma(a2, b1, acc[7]); acc[8] = fma(a2, b2, acc[8]);
         acc[9] += a0; acc[10] += a1; acc[11] += a2;
     }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < 12; ++q) {
-        double v = acc[q];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if (lane == 0) sh[q][wv] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 12) {
-        double v = 0.0;
-        for (int k = 0; k < 16; ++k) v += sh[threadIdx.x][k];
-        out[threadIdx.x] = v;
-    }
+    bb::wave_sums_to_lds(acc, sh);
+    if (threadIdx.x < 12) out[threadIdx.x] = bb::lds_wave_total(sh[threadIdx.x]);
 }
 
 // out_i = scale * ((in_i - mean) M), rows i < n_bins; M is 3 x 3 row-major; rows beyond
@@ -83,24 +73,11 @@ __device__ __forceinline__ void sp_rows(int64_t n_pad, int64_t &r0, int64_t &r1)
     r0 = (int64_t)blockIdx.x * per;
     r1 = r0 + per < n_pad ? r0 + per : n_pad;
 }
-// the workgroup's 12 sums -> partial[blockIdx.x * 12 ..]: lanes by shuffle, waves through LDS
+// the workgroup's 12 sums -> partial[blockIdx.x * 12 ..]
 __device__ __forceinline__ void sp_store_partial(double (&acc)[12], double *__restrict__ partial) {
     __shared__ double sh[12][kSpWG / 64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < 12; ++q) {
-        double v = acc[q];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if (lane == 0) sh[q][wv] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 12) {
-        double v = 0.0;
-#pragma unroll
-        for (int k = 0; k < kSpWG / 64; ++k) v += sh[threadIdx.x][k];
-        partial[(int64_t)blockIdx.x * 12 + threadIdx.x] = v;
-    }
+    bb::wave_sums_to_lds(acc, sh);
+    if (threadIdx.x < 12) partial[(int64_t)blockIdx.x * 12 + threadIdx.x] = bb::lds_wave_total(sh[threadIdx.x]);
 }
 __device__ __forceinline__ void sp_accumulate(double (&acc)[12], double a0, double a1, double a2) {
     acc[0] = fma(a0, a0, acc[0]); acc[1] = fma(a0, a1, acc[1]); acc[2] = fma(a0, a2, acc[2]);

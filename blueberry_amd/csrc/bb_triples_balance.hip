@@ -43,8 +43,6 @@
 #include <string>
 #include <vector>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "bb_balance_loop.h"
 #include "bb_cm_internal.h"
 #include "bb_common.h"
@@ -212,8 +210,7 @@ __global__ __launch_bounds__(256) void seg_sum_kernel(const long long *__restric
             }
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    acc = bb::wave_sum_first(acc);
     if (lane == 0) part[w] = acc;
 }
 
@@ -260,8 +257,7 @@ __global__ __launch_bounds__(256) void pair_counts_kernel(const u64 *__restrict_
         const u64 shifted = r == 0 ? lo : (lo >> r) | (hi << (64 - r));
         acc += __popcll(L[w] & shifted);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    acc = bb::wave_sum_first(acc);
     if (lane == 0) counts[k] = acc;
 }
 
@@ -296,11 +292,9 @@ hipError_t build_list(bb::DevBuf &keys, bb::DevBuf &vals, int64_t m, u64 none, u
         u64 *keep = fk, *place = (u64 *)fv;
         TB_HIP(bb::launch(winners_kernel, grid256(m), dim3(256), 0, st, (const u64 *)sk, m, none, keep));
         size_t scan_bytes = 0;
-        TB_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, keep, place, (u64)0, (size_t)m,
-                                       rocprim::plus<u64>(), st));
+        TB_HIP(bb::exclusive_scan_bytes((size_t)m, &scan_bytes));
         TB_HIP(tmp.reserve(scan_bytes));
-        TB_HIP(rocprim::exclusive_scan(tmp.p, scan_bytes, keep, place, (u64)0, (size_t)m,
-                                       rocprim::plus<u64>(), st));
+        TB_HIP(bb::exclusive_scan(tmp.p, scan_bytes, keep, place, (size_t)m, st));
         u64 last_place = 0, last_keep = 0;
         TB_HIP(hipStreamSynchronize(st));
         TB_HIP(hipMemcpy(&last_place, place + (m - 1), 8, hipMemcpyDeviceToHost));

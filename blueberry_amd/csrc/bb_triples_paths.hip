@@ -40,10 +40,12 @@
 #include <math.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "bb_common.h"
+#include "bb_device_sums.h"
 #include "bb_triples.h"
 #include "bb_wish.h"
 
@@ -111,8 +113,7 @@ __global__ __launch_bounds__(256) void weights_kernel(const long long *__restric
         edges += d > 0.0 ? 1 : 0;
     }
     if (deg != nullptr) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) edges += __shfl_down(edges, off, 64);
+        edges = bb::wave_sum_first(edges);
         if (lane == 0 && edges > 0) atomicAdd(deg + o, (u64)edges);
     }
 }
@@ -368,7 +369,7 @@ int bb_triples_paths(bb_triples *t, int64_t n_nodes, int kind, double alpha, con
                               std::to_string(free_b) + " B are free";
     if (d_bytes + w_bytes > free_b) return bb::fail(BB_ERR_NOMEM, std::string(who) + ": " + sizes);
 
-    bb_paths *p = new (std::nothrow) bb_paths();
+    std::unique_ptr<bb_paths> p(new (std::nothrow) bb_paths());
     if (!p) return bb::fail(BB_ERR_NOMEM, "bb_triples_paths: out of host memory");
     p->device = t->device;
     p->n_sources = n_sources;
@@ -376,52 +377,44 @@ int bb_triples_paths(bb_triples *t, int64_t n_nodes, int kind, double alpha, con
     p->n_nodes = n_nodes;
     p->ld = ld;
     bb::DevBuf wt, kr_buf, small;                 // small: sources | flags | the count
-    bb::Event ev[3];
+    bb::StageClock<3> clock;                      // the weights | the sweeps
     const double *kr = nullptr, *ke = nullptr;
     const size_t src_bytes = bb::align256((size_t)n_sources * 8);
     hipError_t e = p->D.alloc(d_bytes);
     if (e == hipSuccess) e = wt.alloc(w_bytes);
     if (e == hipSuccess) e = small.alloc(src_bytes + 512);
     if (e == hipSuccess) e = upload_kr(KRnorm, KRexpected, n_nodes, kr_buf, &kr, &ke);
-    if (e == hipErrorOutOfMemory) {
-        delete p;
+    if (e == hipErrorOutOfMemory)
         return bb::fail(BB_ERR_NOMEM, std::string(who) + ": hipMalloc failed: " + sizes);
-    }
     hipStream_t st = nullptr;
     long long *d_sources = small.as<long long>();
     int *flags = (int *)((char *)small.p + src_bytes);
     u64 *count = (u64 *)((char *)small.p + src_bytes + 256);
     bool converged = false;
-    for (int q = 0; q < 3 && e == hipSuccess; ++q) e = ev[q].create();
+    if (e == hipSuccess) e = clock.start();
     if (e == hipSuccess) e = hipMemcpy(d_sources, sources, (size_t)n_sources * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemsetAsync(count, 0, 8, st);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], st);
+    if (e == hipSuccess) e = clock.mark(0, st);
     if (e == hipSuccess) e = weights_enqueue(rows, kind, alpha, kr, ke, wt.as<double>(), nullptr);
-    if (e == hipSuccess) e = hipEventRecord(ev[1], st);
+    if (e == hipSuccess) e = clock.mark(1, st);
     if (e == hipSuccess)
         e = bb::launch(fill_inf_kernel, grid256(n_nodes * ld), dim3(256), 0, st, p->D.as<double>(), n_nodes * ld);
     if (e == hipSuccess)
         e = bb::launch(seed_sources_kernel, grid256(n_sources), dim3(256), 0, st, p->D.as<double>(), ld,
                        (const long long *)d_sources, n_sources);
-    if (e == hipSuccess) e = run_sweeps(rows, wt.as<double>(), p, flags, &p->sweeps, &converged);
-    if (e == hipSuccess) e = hipEventRecord(ev[2], st);
+    if (e == hipSuccess) e = run_sweeps(rows, wt.as<double>(), p.get(), flags, &p->sweeps, &converged);
+    if (e == hipSuccess) e = clock.mark(2, st);
     if (e == hipSuccess)
         e = bb::launch(count_inf_kernel, grid256(n_nodes * ld), dim3(256), 0, st, (const double *)p->D.p,
                        n_nodes, ld, n_sources, count);
     u64 none = 0;
     if (e == hipSuccess) e = hipMemcpy(&none, count, 8, hipMemcpyDeviceToHost);
-    float ms_w = 0.f, ms_s = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms_w, ev[0], ev[1]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms_s, ev[1], ev[2]);
-    if (e != hipSuccess || !converged) {
-        delete p;
-        if (e != hipSuccess) return bb::hip_status(who, e);
-        return bb::fail(BB_ERR_STATE, "bb_triples_paths: no fixed point after n_nodes sweeps");
-    }
+    if (e == hipSuccess) e = clock.read(0, &p->weights_ms);
+    if (e == hipSuccess) e = clock.read(1, &p->sweeps_ms);
+    BB_TRY(bb::hip_status(who, e));
+    if (!converged) return bb::fail(BB_ERR_STATE, "bb_triples_paths: no fixed point after n_nodes sweeps");
     p->unreachable = (int64_t)none;
-    p->weights_ms = ms_w;
-    p->sweeps_ms = ms_s;
-    *out = p;
+    *out = p.release();
     return BB_OK;
 }
 

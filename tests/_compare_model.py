@@ -17,7 +17,7 @@ from tests._score_model import _segment_sums
 
 EPS = 2.0 ** -53
 TILE = 256                      # the tile edge of the pair pass (kT of bb_compare.hip)
-SORT_TILE = 4096                # slots per workgroup of the device's sort (bb_sort.h)
+SORT_TILE = 4096                # slots per workgroup of the device's sort (bb_sort.hip)
 
 
 def used_bins(A, B, mask=None):
