@@ -45,11 +45,13 @@ from .band import count_band_regions  # noqa: F401
 from .datatypes import (ContactMap, EigenNoConvergence, FithicContactMap,  # noqa: F401
                         shortest_paths)
 from .compare import StructureComparison, compare_structures  # noqa: F401
+from .engine import HipEngine, RankDeficient  # noqa: F401
 from .fithic import FitHiC, binomial_sf  # noqa: F401
+from .landmark import landmark_coefficients, landmark_start  # noqa: F401
 from .resolution import coarsen_structure, prolong_structure  # noqa: F401
-from .solver import (DeviceTriples, FitScore, GeodesicRows, HipEngine, RankDeficient,  # noqa: F401
-                     StructureSolver, TriplesBalance, balance_triples, coarsen_triples,
-                     landmark_coefficients, landmark_start)
+from .solver import FitScore, StructureSolver  # noqa: F401
 from .stats import benjamini_hochberg, downsample, q_values  # noqa: F401
+from .triples import (DeviceTriples, GeodesicRows, TriplesBalance, balance_triples,  # noqa: F401
+                      coarsen_triples)
 
 __version__ = "0.1.0"

@@ -1,9 +1,8 @@
 """count_band_regions -- host side of K1 (reference: blueberry/blueberry.pyx:77-91)."""
-import os
-
 import numpy
 
 from . import _lib
+from .ranks import pick_device
 from .utils import HIGH_FITHIC_CUTOFF, LOW_FITHIC_CUTOFF
 
 
@@ -50,13 +49,6 @@ def count_band_regions(regions_ndarray, device=None, distributed=False):
                                       HIGH_FITHIC_CUTOFF, i_begin, i_end, device, out),
                "bb_band_count_rows")
     return int(allreduce_count(int(out.value), device))
-
-
-def pick_device(device, distributed):
-    """An explicit index wins; else LOCAL_RANK in a distributed call, 0 otherwise."""
-    if device is not None:
-        return int(device)
-    return int(os.environ.get("LOCAL_RANK", "0")) if distributed else 0
 
 
 def band_row_share(n, rank, world):

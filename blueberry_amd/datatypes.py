@@ -33,28 +33,17 @@ Deviations from the reference, all deliberate:
 import numpy
 
 from . import _lib
+from .ranks import pick_device, several_ranks
+from .resolution import check_factor
+from .utils import Q_LOWER_BOUND
 
-RAO = "/net/noble/vol1/data/hic-datasets/"
+RAO ="/net/noble/vol1/data/hic-datasets/"
 RAW_DIR = RAO + ("data/Rao-Cell2014/rawFromGEO/{0}/{2}kb_resolution_intrachromosomal/chr{1}/"
                  "MAPQGE30/chr{1}_{2}kb.RAWobserved")
 KR_NORM = RAO + ("data/Rao-Cell2014/rawFromGEO/{0}/{2}kb_resolution_intrachromosomal/chr{1}/"
                  "MAPQGE30/chr{1}_{2}kb.KRnorm")
 KR_EXP = RAO + ("data/Rao-Cell2014/rawFromGEO/{0}/{2}kb_resolution_intrachromosomal/chr{1}/"
                 "MAPQGE30/chr{1}_{2}kb.KRexpected")
-
-
-def _pick_device(device):
-    """An explicit index wins; else this rank's own GPU inside a torch.distributed job
-    (LOCAL_RANK, the rule of StructureSolver._pick_device and band.pick_device), else 0.
-    torch is only looked at if the process has imported it already."""
-    if device is not None:
-        return int(device)
-    import os
-    import sys
-    td = sys.modules.get("torch.distributed")
-    if td is not None and td.is_available() and td.is_initialized() and td.get_world_size() > 1:
-        return int(os.environ.get("LOCAL_RANK", "0"))
-    return 0
 
 
 def scatter_triples(triples, resolution, n_bins, device=0):
@@ -178,7 +167,6 @@ def check_coarsen_args(factor, how="sum"):
     """(factor, how code) of `ContactMap.coarsen`, `DeviceTriples.coarsen` and `coarsen_triples`,
     checked (ValueError) without touching the library: an int >= 1 -- no bool, no float -- and
     'sum' or 'mean'."""
-    from .resolution import check_factor
     factor = check_factor(factor)
     if not isinstance(how, str) or how not in _COARSEN_HOW:
         raise ValueError("how must be 'sum' or 'mean'")
@@ -282,7 +270,7 @@ class ContactMap(object):
         self.resolution = int(resolution)
         self.chromosome = chromosome
         self.celltype = celltype
-        self.device = _pick_device(device)
+        self.device = pick_device(device, several_ranks())
         kb = self.resolution // 1000
         self.filename = RAW_DIR.format(celltype, chromosome, kb)
         self._KRnorm = numpy.atleast_1d(numpy.loadtxt(KR_NORM.format(celltype, chromosome, kb)))
@@ -388,7 +376,7 @@ class ContactMap(object):
         self.resolution = int(resolution)
         self.chromosome = chromosome
         self.celltype = celltype
-        self.device = _pick_device(device)
+        self.device = pick_device(device, several_ranks())
         self.filename = ""
         contacts = numpy.asarray(contacts, dtype=numpy.float64)
         if contacts.ndim != 2 or contacts.shape[1] != 3:
@@ -427,7 +415,7 @@ class ContactMap(object):
         if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 1:
             raise ValueError("matrix must be square")
         self.resolution, self.chromosome, self.celltype = int(resolution), chromosome, celltype
-        self.device, self.filename = _pick_device(device), ""
+        self.device, self.filename = pick_device(device, several_ranks()), ""
         self._host, self._dev, self._view = m, None, None
         self.n_bins = m.shape[0] - 1
         self.regions = numpy.arange(self.n_bins, dtype=numpy.float64) * self.resolution
@@ -444,7 +432,7 @@ class ContactMap(object):
         device; the matrix is never built on the host."""
         self = cls.__new__(cls)
         self.resolution, self.chromosome, self.celltype = int(resolution), chromosome, celltype
-        self.device, self.filename = _pick_device(device), ""
+        self.device, self.filename = pick_device(device, several_ranks()), ""
         data = numpy.asarray(triples, dtype=numpy.float64)         # nan_to_num: on the device
         self.n_bins = int(n_bins)
         self._host = self._view = None
@@ -593,7 +581,7 @@ class ContactMap(object):
         with `biases` ('auto': the map's KRnorm, e.g. what `balance()` left) and `q_max` (only the
         contacts with q <= q_max, selected on the device) passed on to `fit_transform`.  The map
         stays as it is and stays resident."""
-        from .fithic import _significance
+        from .fithic import _significance      # (late: fithic takes this very type -- a real cycle)
         return _significance(self, None, kwargs)
 
     def correlation(self):
@@ -840,7 +828,6 @@ class FithicContactMap(object):
     def contacts(self):
         """All contacts with a q-value <= Q_LOWER_BOUND, as (mid1, mid2) rows
         (`blueberry/datatypes.pyx:341-350`)."""
-        from .utils import Q_LOWER_BOUND
         return self.map[self.map[:, 4] <= Q_LOWER_BOUND, :2]
 
     def _bins(self):

@@ -18,7 +18,8 @@ and unused, as in the reference, where only the first pass runs.
 import numpy
 
 from . import _lib
-from .datatypes import ContactMap, FithicContactMap, _pick_device, expected_sums
+from .datatypes import ContactMap, FithicContactMap, expected_sums
+from .ranks import pick_device, several_ranks
 
 _DIST_SCALING = 10000.0            # `distScaling`, blueberry/fithic.py:45
 
@@ -44,7 +45,8 @@ def binomial_sf(k, n, p, device=None):
         raise ValueError("binomial_sf: n must be a whole number in [0, 2^53]")
     out = numpy.empty(k.shape[0], dtype=numpy.float64)
     _lib.check(_lib.load().bb_binomial_sf(k.ctypes.data_as(_lib.p_i64), n, _lib.as_f64_ptr(p),
-                                          _lib.as_f64_ptr(out), k.shape[0], _pick_device(device)),
+                                          _lib.as_f64_ptr(out), k.shape[0],
+                                          pick_device(device, several_ranks())),
                "bb_binomial_sf")
     return out.reshape(shape)
 

@@ -6,1345 +6,39 @@ reference has, `FitHiC(hyper-parameters).fit_transform(data)`
 (`blueberry/fithic.py:76-108`), and the input is the dense float64 matrix a
 `ContactMap` holds (`blueberry/datatypes.pyx:78-86`).  The algorithm is
 specified in docs/SPEC.md and runs entirely in libblueberry_hip.so
-(include/blueberry_hip.h); this module only validates arguments, owns the
-handle and, for world_size > 1, drives one all-reduce per iteration through
-torch.distributed (backend "nccl" = RCCL over xGMI) -- or, with
+(include/blueberry_hip.h); this module is the estimator: it validates arguments,
+runs the fit on an engine (engine.py) and, for world_size > 1, has exchange.py drive
+one sum over the ranks per iteration (backend "nccl" = RCCL over xGMI) -- or, with
 `StructureSolver(devices=[...])`, drives several GPUs from this one process without
 torch (`GroupEngine`: one solver per device, one host thread each, the sum over them
 ordered by HIP events, `bb_group_*`).
 """
 import contextlib
 import math
-import os
-import sys
+import os    # noqa: F401
+import sys   # noqa: F401
 
 import numpy
 
 from . import _lib
-from .datatypes import (_balance, _expected, _nan_to_num, _pick_device, check_balance_args,
-                        check_coarsen_args, triples_buffer)
-
-_DTYPES = {"float32": _lib.BB_F32, "float64": _lib.BB_F64}
-_KINDS = {"wish": _lib.BB_KIND_WISH, "counts": _lib.BB_KIND_COUNTS}
-
-
-class RankDeficient(RuntimeError):
-    """The block power iteration of the device-resident spectral start lost rank: the map has
-    fewer than three independent directions (an empty or unconstrained map, fewer than 4 bins).
-    `fit()` then takes the host-driven start; every other library error propagates."""
-
-
-class DeviceTriples(_lib.Handle):
-    """The (n, 3) array [pos_i, pos_j, count] of a Rao-format file -- what
-    `ContactMap.__init__` reads (`blueberry/datatypes.pyx:100-102`) -- copied to the device
-    once (`bb_triples_*`): nan_to_num, binning and the scatter into the solver's tiles all
-    happen there.  C-ordered rows and the reference's column-major array are read in place.
-
-    `balance` and `expected` are `ContactMap.balance` / `ContactMap.expected` on the matrix the
-    triples define -- `ContactMap.from_triples(triples, resolution, n_bins)` -- without that
-    matrix (docs/SPEC.md 2.5.3): the first call builds an index of the stored cells on the
-    device, which stays with the handle."""
-    is_triples = True
-    prefix = "bb_triples_"
-
-    def __init__(self, triples, resolution, device):
-        t, buf, row_major = triples_buffer(triples)
-        self.resolution = int(resolution)
-        _lib.Handle.__init__(self)
-        self.n, self.device = int(t.shape[0]), int(device)
-        self._create(_lib.as_f64_ptr(buf), self.n, int(resolution), row_major, self.device)
-
-    @classmethod
-    def _adopt(cls, handle, resolution, device):
-        """The owner of a `bb_triples` another call left (`bb_triples_coarsen`)."""
-        self = cls.__new__(cls)
-        _lib.Handle.__init__(self, handle)
-        self.resolution, self.device = int(resolution), int(device)
-        self.n = int(self._get(_lib.c_i64, "size"))
-        return self
-
-    def _balance_target(self):
-        """The handle `balance`, `expected` and the significance pass speak to: this one."""
-        return self
-
-    def to_host(self):
-        """The (n, 3) float64 rows [pos_i, pos_j, count] the handle holds, C-ordered, as they
-        were given (`bb_triples_download`)."""
-        out = numpy.empty((self.n, 3), dtype=numpy.float64)
-        self._call("download", _lib.as_f64_ptr(out))
-        return out
-
-    def coarsen(self, n_bins, factor, how="sum"):
-        """The pixel list of the map the triples define over bins 0 .. n_bins - 1, pooled to
-        resolution `resolution * factor` (`ContactMap.coarsen`; docs/SPEC.md 2.12): a NEW
-        `DeviceTriples` on the same device -- nothing goes through the host -- of one triple
-        [I R, J R, value] per pooled cell I <= J with at least one stored fine cell (a stored 0
-        included), I ascending, then J; `n_bins_` holds ceil(n_bins / factor).  The values are
-        bit for bit those of `ContactMap.from_triples(...).coarsen(factor, how)`.  The new handle
-        is usable wherever a `DeviceTriples` is and does not depend on this one, which stays as
-        it is (the first call builds its index, as `balance` does)."""
-        factor, how = check_coarsen_args(factor, how)
-        n = _bin_count(n_bins)
-        h = _lib.c_void_p()
-        self._call("coarsen", n, factor, how, h)
-        out = DeviceTriples._adopt(h, self.resolution * factor, self.device)
-        out.n_bins_ = -(-n // factor)
-        return out
-
-    def tiles(self, n_bins, dtype):
-        """(tile_I, tile_J), device order, of the tiles the triples name."""
-        nb = layout_info(n_bins, dtype)["n_blocks"]
-        present = numpy.zeros((nb, nb), dtype=numpy.uint8)
-        self._call("tiles", int(n_bins), _DTYPES[dtype], present.ctypes.data_as(_lib.p_u8), nb)
-        tj, ti = numpy.nonzero(present.T)            # J ascending, then I
-        return ti.astype(numpy.int32), tj.astype(numpy.int32)
-
-    def pairs(self, n_bins):
-        """The number of distinct bin pairs i <= j < n_bins the triples store."""
-        return int(self._get(_lib.c_i64, "pairs", int(n_bins)))
-
-    def balance(self, n_bins, ignore_diags=0, min_nnz=0, tol=1e-5, max_iter=200, row_sum=None):
-        """The ICE bias vector of the map the triples define over bins 0 .. n_bins - 1
-        (`bb_triples_balance`): the arguments, the result (length n_bins, NaN at masked bins)
-        and the attributes `balance_iterations_`, `balance_variance_`, `balance_converged_`,
-        `balance_masked_` of `ContactMap.balance`.  The same bits on every run, and for every
-        duplicate-free list of the same pairs."""
-        args = check_balance_args(ignore_diags, min_nnz, tol, max_iter, row_sum)
-        return _balance(self, _bin_count(n_bins), args)
-
-    def expected(self, n_bins, bias=None):
-        """The distance-decay expected e of the balanced map (`bb_triples_expected`,
-        `ContactMap.expected`): bias None -- all ones -- or a length-n_bins vector, NaN = not a
-        live bin.  `expected_sums_` and `expected_counts_` (int64) hold the two raw vectors;
-        pairs without a triple are zero cells and count."""
-        return _expected(self, _bin_count(n_bins), bias)
-
-    def significance(self, map_bins, **kwargs):
-        """The Fit-Hi-C p- and q-values of the map the triples define over bins 0 .. map_bins - 1
-        (`ContactMap.significance`; docs/SPEC.md 2.9), bit for bit what `ContactMap.from_triples(
-        ...).significance(...)` gives, without that matrix; `biases` and `q_max` go on to
-        `FitHiC.fit_transform`.  One chromosome."""
-        from .fithic import _significance
-        return _significance(self, int(map_bins), kwargs)
-
-    def _graph_arguments(self, n_nodes, kind, alpha, KRnorm, KRexpected):
-        """(n_nodes, kind code, alpha, KR pointers) of the graph calls, checked."""
-        n = int(n_nodes)
-        if n < 1:
-            raise ValueError("n_nodes must be at least 1")
-        if kind not in _KINDS:
-            raise ValueError("kind must be 'counts' or 'wish'")
-        if not float(alpha) > 0:
-            raise ValueError("alpha must be positive")
-        kr, ke = _kr_pair(KRnorm, KRexpected, n)
-        return n, _KINDS[kind], float(alpha), kr, ke
-
-    def edge_degrees(self, n_nodes, kind="counts", alpha=3.0, KRnorm=None, KRexpected=None):
-        """The number of graph edges of every node 0 .. n_nodes - 1 (`bb_triples_edge_degrees`,
-        docs/SPEC.md 2.1.2): the stored off-diagonal cells whose wish distance -- under `kind`,
-        `alpha` and the KR vectors, as `fit_triples` forms it -- is finite and positive.  int64."""
-        n, kind, alpha, kr, ke = self._graph_arguments(n_nodes, kind, alpha, KRnorm, KRexpected)
-        deg = numpy.zeros(n, dtype=numpy.int64)
-        self._call("edge_degrees", n, kind, alpha, kr, ke, deg.ctypes.data_as(_lib.p_i64))
-        return deg
-
-    def shortest_paths(self, n_nodes, sources, kind="counts", alpha=3.0, KRnorm=None, KRexpected=None):
-        """The shortest-path lengths from the nodes `sources` (any order, repeats allowed, at most
-        `GeodesicRows.MAX_SOURCES`) to all n_nodes nodes of the graph whose edges are the triples'
-        wish distances (`bb_triples_paths`, docs/SPEC.md 2.1.2), without the dense matrix: a
-        `GeodesicRows`, resident on the device.  Bit for bit scipy's Dijkstra in float64."""
-        n, kind, alpha, kr, ke = self._graph_arguments(n_nodes, kind, alpha, KRnorm, KRexpected)
-        src = numpy.ascontiguousarray(sources, dtype=numpy.int64).ravel()
-        h = _lib.c_void_p()
-        self._call("paths", n, kind, alpha, kr, ke, src.ctypes.data_as(_lib.p_i64), src.shape[0], h)
-        return GeodesicRows(h)
-
-
-class GeodesicRows(_lib.Handle):
-    """What `DeviceTriples.shortest_paths` returns: the (n_sources, n_nodes) float64 geodesics,
-    resident on the device as a `bb_paths`, which owns its memory (it may outlive the triples).
-    `sweeps_`: Bellman-Ford sweeps made (not reproducible: the distances are updated in place);
-    `unreachable_`: (source, node) pairs without a path.  A context manager; `close()` frees it,
-    any other call after that is a ValueError."""
-    MAX_SOURCES = 1024                      # BB_PATHS_MAX_SOURCES
-    prefix = "bb_paths_"
-
-    def __init__(self, handle):
-        _lib.Handle.__init__(self, handle)
-        ns, nn, sw, un = _lib.c_i64(), _lib.c_i64(), _lib.c_i64(), _lib.c_i64()
-        self._call("info", ns, nn, sw, un)
-        self.n_sources, self.n_nodes = int(ns.value), int(nn.value)
-        self.sweeps_, self.unreachable_ = int(sw.value), int(un.value)
-
-    def to_host(self):
-        """(n_sources, n_nodes): 0 where no path exists and on a source's own node."""
-        out = numpy.empty((self.n_sources, self.n_nodes), dtype=numpy.float64)
-        self._call("read", _lib.as_f64_ptr(out))
-        return out
-
-    def columns(self, nodes):
-        """(n_sources, len(nodes)): the distances to the listed nodes alone."""
-        idx = numpy.ascontiguousarray(nodes, dtype=numpy.int64).ravel()
-        out = numpy.empty((self.n_sources, idx.shape[0]), dtype=numpy.float64)
-        self._call("read_columns", idx.ctypes.data_as(_lib.p_i64), idx.shape[0], _lib.as_f64_ptr(out))
-        return out
-
-    def reached(self):
-        """int64 (n_sources,): the nodes every source has a path to, its own included."""
-        out = numpy.zeros(self.n_sources, dtype=numpy.int64)
-        self._call("reached", out.ctypes.data_as(_lib.p_i64))
-        return out
-
-    def place(self, coef, mu, out=None):
-        """Landmark placement on the device (`bb_paths_place`): (xyz, placed).  xyz[j] =
-        -1/2 sum_a coef[a] (D[j][a]^2 - mu[a]) for every node with a path from every source that
-        takes part (a source whose coef row and mu are 0 does not); the other rows keep what
-        `out` -- (n_nodes, 3) float64, C-ordered; None: zeros -- held.  placed: bool."""
-        coef = numpy.ascontiguousarray(coef, dtype=numpy.float64)
-        mu = numpy.ascontiguousarray(mu, dtype=numpy.float64)
-        if coef.shape != (self.n_sources, 3) or mu.shape != (self.n_sources,):
-            raise ValueError("coef must have shape (n_sources, 3) and mu (n_sources,)")
-        if out is None:
-            out = numpy.zeros((self.n_nodes, 3), dtype=numpy.float64)
-        if (not isinstance(out, numpy.ndarray) or out.dtype != numpy.float64
-                or out.shape != (self.n_nodes, 3) or not out.flags.c_contiguous):
-            raise ValueError("out must be a C-ordered float64 array of shape (n_nodes, 3)")
-        placed = numpy.zeros(self.n_nodes, dtype=numpy.uint8)
-        self._call("place", _lib.as_f64_ptr(coef), _lib.as_f64_ptr(mu), _lib.as_f64_ptr(out),
-                   placed.ctypes.data_as(_lib.p_u8))
-        return out, placed.astype(bool)
-
-    def timing(self):
-        """(weights_ms, sweeps_ms) of the call that made these rows, by HIP events."""
-        w, s = _lib.c_dbl(), _lib.c_dbl()
-        self._call("timing", w, s)
-        return float(w.value), float(s.value)
-
-
-def landmark_choice(live, n_landmarks):
-    """The landmarks of docs/SPEC.md 2.5.4 among the live nodes `live` (ascending):
-    L = min(n_landmarks, len(live)) of them, landmark k = live[((2 k + 1) len(live)) // (2 L)]."""
-    live = numpy.asarray(live, dtype=numpy.int64)
-    L = min(int(n_landmarks), live.shape[0])
-    k = numpy.arange(L, dtype=numpy.int64)
-    return live[((2 * k + 1) * live.shape[0]) // (2 * max(L, 1))]
-
-
-def landmark_coefficients(G_LL):
-    """(coef, mu) of landmark MDS (de Silva & Tenenbaum) from the (L, L) geodesics among the
-    landmarks, docs/SPEC.md 2.5.4 -- the only place the rule lives; pure numpy.
-    Delta2 = (G^2 + G^2.T) / 2, mu = its column means, B = -J Delta2 J / 2, numpy.linalg.eigh,
-    the three largest eigenvalues l_c with their vectors v_c, each vector's sign such that its
-    entry of largest magnitude (lowest index on ties) is positive; coef[:, c] = v_c / sqrt(l_c),
-    a zero column where l_c <= 1e-12 l_1 (a flat or collinear map).  A node with squared
-    geodesics d2 to the landmarks is placed at -coef.T (d2 - mu) / 2."""
-    G = numpy.asarray(G_LL, dtype=numpy.float64)
-    if G.ndim != 2 or G.shape[0] != G.shape[1] or G.shape[0] < 1:
-        raise ValueError("G_LL must be a square (L, L) array")
-    L = G.shape[0]
-    sq = G * G
-    d2 = 0.5 * (sq + sq.T)
-    mu = d2.mean(axis=0)
-    J = numpy.eye(L) - 1.0 / L
-    B = -0.5 * (J @ d2 @ J)
-    w, V = numpy.linalg.eigh(B)
-    order = numpy.argsort(w, kind="stable")[::-1][:3]
-    coef = numpy.zeros((L, 3))
-    top = w[order[0]]
-    for c, q in enumerate(order):
-        if top > 0.0 and w[q] > 1e-12 * top:
-            v = V[:, q]
-            if v[numpy.argmax(numpy.abs(v))] < 0.0:
-                v = -v
-            coef[:, c] = v / numpy.sqrt(w[q])
-    return coef, mu
-
-
-class LandmarkInfo(object):
-    """What `landmark_start(..., return_info=True)` tells besides the start: `landmarks_` (the L
-    landmark nodes), `kept_` (bool per landmark: reached by the main one), `placed_` (bool per
-    node), `sweeps_` and `unreachable_` of the shortest paths; with keep_rows=True `rows_`, the
-    open `GeodesicRows` of the landmarks (the caller closes them), else None."""
-
-    def __init__(self, landmarks, kept, placed, sweeps, unreachable, rows=None):
-        self.landmarks_, self.kept_, self.placed_ = landmarks, kept, placed
-        self.sweeps_, self.unreachable_ = sweeps, unreachable
-        self.rows_ = rows
-
-
-def _check_n_landmarks(n_landmarks):
-    if (isinstance(n_landmarks, bool) or not isinstance(n_landmarks, (int, numpy.integer))
-            or not 4 <= int(n_landmarks) <= GeodesicRows.MAX_SOURCES):
-        raise ValueError("n_landmarks must be an int in [4, %d]" % GeodesicRows.MAX_SOURCES)
-    return int(n_landmarks)
-
-
-def _check_landmark_weight(weight):
-    if (isinstance(weight, bool) or not isinstance(weight, (int, float, numpy.integer, numpy.floating))
-            or not numpy.isfinite(weight) or weight < 0):
-        raise ValueError("landmark_weight must be a finite number >= 0")
-    return float(weight)
-
-
-def landmark_start(triples, resolution, n_bins, n_landmarks=64, kind="counts", alpha=3.0, KRnorm=None,
-                   KRexpected=None, seed=0, device=0, return_info=False, keep_rows=False):
-    """A start for sparse maps that holds the global fold (docs/SPEC.md 2.5.4): landmark MDS
-    (L-Isomap) over the graph of the triples' wish distances, never forming the dense matrix.
-    Landmarks are spread evenly over the bins that have an edge; shortest paths run from them on
-    the device (`DeviceTriples.shortest_paths`); the landmark that reaches the most nodes (the
-    lowest on ties) is the main one, landmarks it does not reach are dropped (fewer than 4 left:
-    ValueError); `landmark_coefficients` of the kept landmarks' mutual geodesics place every node
-    the main landmark reaches, on the device (the (L, N) array never travels to the host).  Nodes
-    that are not placed -- dead bins, small components -- keep the rows of the seeded default start
-    `numpy.random.default_rng(seed).standard_normal((n_bins + 1, 3))`.
-    Returns the (n_bins + 1, 3) float64 array; with return_info=True, (array, `LandmarkInfo`).
-    keep_rows=True (with return_info) leaves the geodesic rows open as `info.rows_` -- what
-    `HipEngine.set_anchors` copies for a fit with landmark constraints (SPEC 2.5.5).
-    `triples` may be a `DeviceTriples` (its own resolution and device are used; it stays open)."""
-    n_landmarks = _check_n_landmarks(n_landmarks)
-    n = _bin_count(n_bins) + 1
-    graph = dict(kind=kind, alpha=alpha, KRnorm=KRnorm, KRexpected=KRexpected)
-    with _resident_triples(triples, resolution, [_pick_device(device)]) as dev:
-        live = numpy.flatnonzero(dev.edge_degrees(n, **graph) > 0)
-        landmarks = landmark_choice(live, n_landmarks)
-        few = "the map is too disconnected for a landmark start: %s (need 4)"
-        if landmarks.shape[0] < 4:
-            raise ValueError(few % ("%d bins have an edge" % live.shape[0]))
-        rows = dev.shortest_paths(n, landmarks, **graph)
-        try:
-            main = int(numpy.argmax(rows.reached()))           # (the lowest index on ties)
-            G = rows.columns(landmarks)
-            kept = G[main] > 0.0
-            kept[main] = True
-            if int(kept.sum()) < 4:
-                raise ValueError(few % ("%d landmarks lie in the largest component" % int(kept.sum())))
-            coef, mu = numpy.zeros((landmarks.shape[0], 3)), numpy.zeros(landmarks.shape[0])
-            coef[kept], mu[kept] = landmark_coefficients(G[numpy.ix_(kept, kept)])
-            start = numpy.random.default_rng(int(seed)).standard_normal((n, 3))
-            start, placed = rows.place(coef, mu, out=start)
-            keep = bool(keep_rows and return_info)
-            info = LandmarkInfo(landmarks, kept, placed, rows.sweeps_, rows.unreachable_,
-                                rows if keep else None)
-            if keep:
-                rows = None
-        finally:
-            if rows is not None:
-                rows.close()
-    return (start, info) if return_info else start
-
-
-def _check_triples(triples):
-    """The float64 (n, 3) view of `triples`, or ValueError."""
-    return triples_buffer(triples)[0]
-
-
-def _bin_count(n_bins):
-    n = int(n_bins)
-    if n < 0:
-        raise ValueError("n_bins must not be negative")
-    return n
-
-
-@contextlib.contextmanager
-def _resident_triples(triples, resolution, devices):
-    """The `DeviceTriples` a call works on.  A caller's own is yielded as it is and stays open;
-    anything else is uploaded -- once per distinct device of `devices`, the copy on devices[0]
-    being the one yielded and, where there are several entries, naming them all as its
-    `per_device` (what `GroupEngine.set_wish_triples` reads) -- and closed on exit."""
-    if isinstance(triples, DeviceTriples):
-        yield triples
-        return
-    if int(resolution) <= 0:
-        raise ValueError("resolution must be positive")
-    per_device = {}
-    try:
-        for d in devices:
-            if d not in per_device:
-                per_device[d] = DeviceTriples(triples, resolution, d)
-        dev = per_device[devices[0]]
-        if len(devices) > 1:
-            dev.per_device = per_device
-        yield dev
-    finally:
-        for t in per_device.values():
-            t.close()
-
-
-_BALANCE_KEYS = ("ignore_diags", "min_nnz", "tol", "max_iter", "row_sum")
-
-
-def _balance_options(balance):
-    """`fit_triples(balance=...)` as (checked keyword arguments of `DeviceTriples.balance`, whether
-    the expected is wanted), without touching the library."""
-    if balance is True:
-        balance = {}
-    if not isinstance(balance, dict):
-        raise ValueError("balance must be None, True or a dict of balance_triples' arguments")
-    unknown = sorted(set(balance) - set(_BALANCE_KEYS) - {"expected"})
-    if unknown:
-        raise ValueError("balance: unknown argument %r" % (unknown[0],))
-    args = {k: balance[k] for k in _BALANCE_KEYS if k in balance}
-    return dict(zip(_BALANCE_KEYS, check_balance_args(**args))), bool(balance.get("expected", False))
-
-
-class TriplesBalance(object):
-    """What `balance_triples` returns: `bias` (length n_bins, NaN at masked bins), `masked` (bool),
-    `iterations`, `variance`, `converged`; `expected`, `expected_sums`, `expected_counts` (None
-    unless asked for)."""
-
-    def __init__(self, dev, bias, expected=None):
-        self.bias, self.masked = bias, dev.balance_masked_
-        self.iterations, self.variance = dev.balance_iterations_, dev.balance_variance_
-        self.converged = dev.balance_converged_
-        self.expected = expected
-        self.expected_sums = None if expected is None else dev.expected_sums_
-        self.expected_counts = None if expected is None else dev.expected_counts_
-
-
-def balance_triples(triples, resolution, n_bins, ignore_diags=0, min_nnz=0, tol=1e-5, max_iter=200,
-                    row_sum=None, expected=False, device=None):
-    """Balance a raw map straight from its Rao-format (n, 3) triples [pos_i, pos_j, count],
-    never building the dense matrix (docs/SPEC.md 2.5.3): the ICE bias vector -- and with
-    expected=True the distance-decay expected of the balanced map -- that
-    `ContactMap.from_triples(triples, resolution, n_bins)` followed by `balance(...)` and
-    `expected()` defines.  Returns a `TriplesBalance`.  `triples` may be a `DeviceTriples`
-    (its own resolution and device are used; it stays open)."""
-    args = dict(zip(_BALANCE_KEYS, check_balance_args(ignore_diags, min_nnz, tol, max_iter, row_sum)))
-    n = _bin_count(n_bins)
-    with _resident_triples(triples, resolution, [_pick_device(device)]) as dev:
-        bias = dev.balance(n, **args)
-        return TriplesBalance(dev, bias, dev.expected(n, bias) if expected else None)
-
-
-def coarsen_triples(triples, resolution, n_bins, factor, how="sum", device=None):
-    """Pool a map straight from its Rao-format (n, 3) triples [pos_i, pos_j, count], never
-    building the dense matrix (`DeviceTriples.coarsen`; docs/SPEC.md 2.12), host to host: returns
-    (pooled, nc) -- the (m, 3) float64 triples at resolution `resolution * factor`, in canonical
-    order, and nc = ceil(n_bins / factor).  `ContactMap.from_triples(pooled, resolution * factor,
-    nc)` is bit for bit `ContactMap.from_triples(triples, resolution, n_bins).coarsen(factor,
-    how)`.  `triples` may be a `DeviceTriples` (its own resolution and device are used; it stays
-    open)."""
-    check_coarsen_args(factor, how)
-    n = _bin_count(n_bins)
-    with _resident_triples(triples, resolution, [_pick_device(device)]) as dev:
-        with dev.coarsen(n, factor, how) as pooled:
-            return pooled.to_host(), pooled.n_bins_
-
-
-class HipEngine(_lib.Handle):
-    """One rank's device state: thin, 1:1 over the bb_solver_* C-ABI."""
-
-    prefix = "bb_solver_"
-    n_maps = 1                      # several once set_maps() has laid them end to end
-
-    def __init__(self, n_bins, dtype, rank=0, world=1, device=0, tiles=None):
-        _lib.Handle.__init__(self)
-        self.n_bins, self.dtype, self.rank, self.world, self.device = (
-            int(n_bins), dtype, int(rank), int(world), int(device))
-        if tiles is None:
-            ti = tj = None
-            nt = 0
-        else:
-            ti = numpy.ascontiguousarray(tiles[0], dtype=numpy.int32)
-            tj = numpy.ascontiguousarray(tiles[1], dtype=numpy.int32)
-            if ti.shape != tj.shape or ti.ndim != 1:
-                raise ValueError("tiles must be a pair of equal-length 1-D index arrays")
-            nt = ti.shape[0]
-        self._create(self.n_bins, _DTYPES[dtype], self.device, self.rank, self.world,
-                     None if ti is None else ti.ctypes.data_as(_lib.p_i32),
-                     None if tj is None else tj.ctypes.data_as(_lib.p_i32), nt)
-        self._exch = None
-        self._comm_state = None     # "peer" | "rccl" | "torch" | "host" once chosen
-        self._peer = None           # outcome of peer_setup()
-        self._peer_error = ""
-        self._comm_trial = None     # timings of select_exchange's trial, if one ran
-        self._comm_trial_error = None   # what made a leg of that trial fail on this rank
-
-    # -- lifetime ---------------------------------------------------------
-    def close(self):
-        _lib.Handle.close(self)
-        self._exch = None
-
-    # -- layout -----------------------------------------------------------
-    def layout(self):
-        info = _lib.LayoutInfo()
-        ub, ue = _lib.c_i64(), _lib.c_i64()
-        self._call("layout", info, ub, ue)
-        d = info.as_dict()
-        d["u_begin"], d["u_end"] = int(ub.value), int(ue.value)
-        return d
-
-    # -- inputs -----------------------------------------------------------
-    def set_wish_dense(self, matrix, kind, alpha):
-        m = _check_square(matrix, self.n_bins)
-        self._call("set_wish_dense", _lib.as_f64_ptr(m), m.strides[0] // 8, _KINDS[kind],
-                   float(alpha))
-
-    def set_wish_from_cm(self, dev_matrix, kind, alpha):
-        """Device to device from a resident ContactMap matrix (datatypes._DeviceMatrix)."""
-        self._call("set_wish_from_cm", dev_matrix._open(), _KINDS[kind], float(alpha))
-
-    def set_wish_resident(self, cm, kind, alpha):
-        """A resident ContactMap: device to device when it lives on this engine's GPU."""
-        dev = cm._resident()
-        if dev.device == self.device:
-            self.set_wish_from_cm(dev, kind, alpha)
-        else:
-            # the map lives on another GPU than this rank's solver (a ContactMap made with
-            # an explicit device): through the host once, like a plain matrix
-            self.set_wish_dense(cm.to_host(), kind, alpha)
-
-    def set_wish_sparse(self, rows, cols, vals, kind, alpha, KRnorm=None, KRexpected=None):
-        r = numpy.ascontiguousarray(rows, dtype=numpy.int64)
-        c = numpy.ascontiguousarray(cols, dtype=numpy.int64)
-        v = numpy.ascontiguousarray(vals, dtype=numpy.float64)
-        if not (r.ndim == c.ndim == v.ndim == 1 and r.shape == c.shape == v.shape):
-            raise ValueError("rows, cols, vals must be 1-D arrays of equal length")
-        kr, ke = _kr_pair(KRnorm, KRexpected, self.n_bins)
-        self._call("set_wish_sparse", r.ctypes.data_as(_lib.p_i64), c.ctypes.data_as(_lib.p_i64),
-                   _lib.as_f64_ptr(v), r.shape[0], _KINDS[kind], float(alpha), kr, ke)
-
-    def set_wish_triples(self, dev_triples, kind, alpha, KRnorm=None, KRexpected=None):
-        """From triples resident on the device (`DeviceTriples`): binned, KR / O-E
-        normalised and converted there."""
-        kr, ke = _kr_pair(KRnorm, KRexpected, self.n_bins)
-        self._call("set_wish_triples", dev_triples._open(), _KINDS[kind], float(alpha), kr, ke)
-
-    # -- several maps in one solver (bb_solver_set_maps) -----------------------
-    def set_maps(self, bin_begin, lr_scale):
-        """Declare the maps laid end to end in this solver: map m owns the bins
-        [bin_begin[m], bin_begin[m + 1]) and steps with lr * lr_scale[m]."""
-        b = numpy.ascontiguousarray(bin_begin, dtype=numpy.int64)
-        sc = numpy.ascontiguousarray(lr_scale, dtype=numpy.float64)
-        if b.ndim != 1 or sc.ndim != 1 or b.shape[0] != sc.shape[0] + 1:
-            raise ValueError("bin_begin needs one entry more than lr_scale")
-        self._call("set_maps", sc.shape[0], b.ctypes.data_as(_lib.p_i64), _lib.as_f64_ptr(sc))
-        self.n_maps = int(sc.shape[0])
-
-    def set_wish_dense_block(self, matrix, bin_offset, kind, alpha):
-        m = _check_square(matrix, numpy.asarray(matrix).shape[0])
-        self._call("set_wish_dense_block", _lib.as_f64_ptr(m), m.strides[0] // 8, m.shape[0],
-                   int(bin_offset), _KINDS[kind], float(alpha))
-
-    def set_wish_from_cm_block(self, dev_matrix, bin_offset, kind, alpha):
-        self._call("set_wish_from_cm_block", dev_matrix._open(), int(bin_offset), _KINDS[kind],
-                   float(alpha))
-
-    def _set_steps(self, name, scale, per):
-        if scale is None:
-            self._call(name, None, 0)
-            return
-        sc = numpy.ascontiguousarray(scale, dtype=numpy.float64)
-        if sc.ndim != 1:
-            raise ValueError("scale must be one factor per " + per)
-        self._call(name, _lib.as_f64_ptr(sc), sc.shape[0])
-
-    def set_block_steps(self, scale):
-        """A step per block of the layout (`bb_solver_set_block_steps`): bin i moves by
-        lr * scale[i // vw] * g_i; None = one step for all again."""
-        self._set_steps("set_block_steps", scale, "block")
-
-    def set_bin_steps(self, scale):
-        """A step per bin (`bb_solver_set_bin_steps`): bin i moves by lr * scale[i] * g_i;
-        None = one step for all again."""
-        self._set_steps("set_bin_steps", scale, "bin")
-
-    def degrees(self):
-        """Per bin, the number of this rank's stored pairs that constrain it (delta > 0):
-        `bb_solver_degrees`, one pass over the resident units."""
-        out = numpy.zeros(self.n_bins, dtype=numpy.int64)
-        self._call("degrees", out.ctypes.data_as(_lib.p_i64), out.shape[0])
-        return out
-
-    def set_weight_power(self, q):
-        """Weighted stress (SPEC 2.3.1): w = delta^-q, q in {0, 1, 2}
-        (`bb_solver_set_weight_power`)."""
-        self._call("set_weight_power", int(q))
-
-    def weight_sums(self):
-        """Per bin, s_i = sum_j delta_ij^-q over this rank's stored pairs, float64
-        (`bb_solver_weight_sums`; q = 0: the degrees)."""
-        out = numpy.zeros(self.n_bins, dtype=numpy.float64)
-        self._call("weight_sums", _lib.as_f64_ptr(out), out.shape[0])
-        return out
-
-    anchored = False                # landmark constraints resident (set_anchors)
-
-    def set_anchors(self, rows, kept=None, weight=0.0):
-        """Landmark constraints inside the fit (SPEC 2.5.5, `bb_solver_set_anchors`): the engine
-        makes its own copy of the rows of `rows` (a `GeodesicRows`) with kept[a] true (None:
-        all), which may be closed afterwards.  rows None or weight 0 clears them."""
-        k = None
-        if rows is not None and kept is not None:
-            k = numpy.ascontiguousarray(kept, dtype=numpy.uint8)
-            if k.shape != (rows.n_sources,):
-                raise ValueError("kept must have one entry per source")
-        self._call("set_anchors", None if rows is None else rows._open(),
-                   None if k is None else k.ctypes.data_as(_lib.p_u8), float(weight))
-        self.anchored = self.anchor_info()[0] > 0
-
-    def anchor_sums(self):
-        """Per bin, weight * sum of D^-q over the landmark terms that touch it, float64
-        (`bb_solver_anchor_sums`): what joins `weight_sums` in the steps of SPEC 2.4.1."""
-        out = numpy.zeros(self.n_bins, dtype=numpy.float64)
-        self._call("anchor_sums", _lib.as_f64_ptr(out), out.shape[0])
-        return out
-
-    def anchor_stress(self):
-        """The landmark terms' share of the stress at the current coordinates."""
-        return float(self._get(_lib.c_dbl, "anchor_stress"))
-
-    def anchor_info(self):
-        """(kept rows, terms, bytes resident) of the anchors; zeros without."""
-        rows, terms, nbytes = _lib.c_i64(), _lib.c_i64(), _lib.c_i64()
-        self._call("anchor_info", rows, terms, nbytes)
-        return int(rows.value), int(terms.value), int(nbytes.value)
-
-    def score(self, xyz=None):
-        """The sums of SPEC 2.8 over this rank's units (`bb_solver_score`): (profile, bins),
-        float64 of shape (n_bins, 9) and (n_bins, 3).  xyz: the structure to score; None: the
-        engine's own coordinates."""
-        profile = numpy.zeros((self.n_bins, 9), dtype=numpy.float64)
-        bins = numpy.zeros((self.n_bins, 3), dtype=numpy.float64)
-        self._call("score", None if xyz is None else _lib.as_f64_ptr(_check_coords(xyz, self.n_bins)),
-                   _lib.as_f64_ptr(profile), _lib.as_f64_ptr(bins))
-        return profile, bins
-
-    def loglog(self, xyz=None):
-        """The log-log sums of SPEC 2.11 over this rank's units (`bb_solver_loglog`): float64 of
-        shape (n_bins, 7), row k = the pairs of separation k: pairs with d > 0, sum u, sum v,
-        sum u^2, sum v^2, sum u v (u = log delta, v = log d), pairs with d = 0.  xyz as `score`."""
-        profile = numpy.zeros((self.n_bins, 7), dtype=numpy.float64)
-        self._call("loglog", None if xyz is None else _lib.as_f64_ptr(_check_coords(xyz, self.n_bins)),
-                   _lib.as_f64_ptr(profile))
-        return profile
-
-    def repower(self, p):
-        """Every stored wish distance w > 0 becomes w^p under the wish rule of SPEC 2.1, in place
-        (`bb_solver_repower`); degrees and weight sums are the caller's to recompute."""
-        self._call("repower", float(p))
-
-    def stress_maps(self):
-        out = numpy.empty(self.n_maps, dtype=numpy.float64)
-        self._call("stress_maps", _lib.as_f64_ptr(out), out.shape[0])
-        return out
-
-    def set_wish_from_coords(self, xstar):
-        self._call("set_wish_from_coords", _lib.as_f64_ptr(_check_coords(xstar, self.n_bins)))
-
-    def set_coords(self, x0):
-        self._call("set_coords", _lib.as_f64_ptr(_check_coords(x0, self.n_bins)))
-
-    def get_coords(self):
-        out = numpy.empty((self.n_bins, 3), dtype=numpy.float64)
-        self._call("get_coords", _lib.as_f64_ptr(out))
-        return out
-
-    # -- iterations -------------------------------------------------------
-    def set_momentum(self, mu):
-        self._call("set_momentum", float(mu))
-
-    def iterate(self, iters, lr):
-        self._call("iterate", int(iters), float(lr))
-
-    def grad(self):
-        self._call("grad")
-
-    def apply(self, lr):
-        self._call("apply", float(lr))
-
-    def matvec_sq(self, x):
-        """(D o D) @ x for this rank's units; x is (n_bins, 3)."""
-        x = _check_coords(x, self.n_bins)
-        y = numpy.empty_like(x)
-        self._call("matvec_sq", _lib.as_f64_ptr(x), _lib.as_f64_ptr(y))
-        return y
-
-    def spectral_init_device(self, n_iter, v0, tol=0.0):
-        """Classical-MDS start computed and left on the device: `bb_solver_spectral_init_tol`.
-        v0: (n_bins, 3) start of the block power iteration (the same on every rank).  With
-        several ranks it is collective and needs their exchange set up first (peer arenas or
-        the library's communicator): the per-rank products are summed on the device, nothing
-        of size N crosses PCIe.  tol > 0: n_iter is the most products made; the loop ends once
-        B V lies within tol (relative) of span(V).  Returns (products orthonormalised, last
-        distance read or -1).  Raises RankDeficient when the iterate lost rank."""
-        v0 = _check_coords(v0, self.n_bins)
-        done, res = _lib.c_int(), _lib.c_dbl()
-        # explicit: a lost rank is an outcome of its own (the caller takes the host-driven start)
-        rc = self._status("spectral_init_tol", int(n_iter), float(tol), _lib.as_f64_ptr(v0), done, res)
-        if rc == _lib.BB_ERR_STATE and "lost rank" in _lib.last_error():
-            raise RankDeficient(_lib.last_error())
-        _lib.check(rc, "bb_solver_spectral_init_tol")
-        return int(done.value), float(res.value)
-
-    def stress(self):
-        return float(self._get(_lib.c_dbl, "stress"))
-
-    def stress_history(self):
-        out = numpy.empty(int(self._get(_lib.c_i64, "get_stress_history", None, 0)),
-                          dtype=numpy.float64)
-        if out.size:
-            self._get(_lib.c_i64, "get_stress_history", _lib.as_f64_ptr(out), out.size)
-        return out
-
-    def sync(self):
-        self._call("sync")
-
-    def exchange_size(self):
-        return int(self._get(_lib.c_i64, "exchange_size"))
-
-    def read_exchange(self):
-        """Exchange buffer [g (n_pad,3) | stress hi | lo] as float64 on the host."""
-        out = numpy.empty(self.exchange_size(), dtype=numpy.float64)
-        self._call("read_exchange", _lib.as_f64_ptr(out), out.size)
-        return out
-
-    def write_exchange(self, host):
-        host = numpy.ascontiguousarray(host, dtype=numpy.float64)
-        self._call("write_exchange", _lib.as_f64_ptr(host), host.size)
-
-    # -- the all-reduce boundary (world > 1) --------------------------------
-    def comm_setup(self):
-        """Make the library's own RCCL communicator for this job: rank 0 draws the
-        128-byte id, torch.distributed only carries it to the other ranks, every
-        rank joins (`ncclCommInitRank`).  Collective.  Returns False -- on every
-        rank alike -- when RCCL cannot be used, so that the caller can fall back
-        to the torch.distributed all-reduce."""
-        import ctypes
-        import torch.distributed as dist
-        box = [None]
-        if self.rank == 0:
-            buf = ctypes.create_string_buffer(128)
-            if self._lib.bb_comm_unique_id(buf) == _lib.BB_OK:
-                box[0] = buf.raw
-        dist.broadcast_object_list(box, src=0)
-        if box[0] is None:
-            return False
-        # explicit: a failure here is this rank's vote, not an error
-        ok = self._status("comm_init", box[0]) == _lib.BB_OK
-        # all ranks must take the same path: agree on the outcome
-        import torch
-        flag = torch.tensor([1 if ok else 0], dtype=torch.int32,
-                            device=torch.device("cuda", self.device))
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        return bool(flag.item())
-
-    # the library's communicator cache (bb_comm_cached / bb_solver_comm_attach / _detach):
-    # `comm_reuse` below drives these three
-    def _comm_cached(self):
-        import ctypes
-        have = ctypes.c_int(0)
-        self._lib.bb_comm_cached(self.device, self.rank, self.world, ctypes.byref(have))
-        return bool(have.value)
-
-    def _comm_generation(self):
-        """Generation of the free cached communicator for this engine's key -- a hash of the
-        unique id it was made with, equal on the ranks that made it together -- or 0."""
-        import ctypes
-        have, gen = ctypes.c_int(0), ctypes.c_uint64(0)
-        self._lib.bb_comm_cached_generation(self.device, self.rank, self.world,
-                                            ctypes.byref(have), ctypes.byref(gen))
-        return int(gen.value) if have.value else 0
-
-    def _comm_attach(self):
-        # explicit: the outcome is agreed between the ranks (`comm_reuse`), not raised
-        return self._status("comm_attach") == _lib.BB_OK
-
-    def _comm_detach(self):
-        self._status("comm_detach")
-
-    def iterate_dist(self, iters, lr):
-        """`iters` x { grad, RCCL all-reduce, apply }, all enqueued by one C call."""
-        self._call("iterate_dist", int(iters), float(lr))
-
-    def peer_setup(self):
-        """Connect the peer exchange (one-shot all-reduce inside the solver's own
-        kernels, include/blueberry_hip.h): every rank exports its receive arena,
-        torch.distributed only carries the 128-byte handles, every rank maps all
-        arenas.  Collective.  Returns False -- on every rank alike -- when any
-        rank could not export or map, so that the caller can fall back to RCCL."""
-        import ctypes
-        import torch.distributed as dist
-        if self._peer is not None:
-            return self._peer
-        buf = ctypes.create_string_buffer(_lib.BB_PEER_HANDLE_BYTES)
-        # explicit, here and at the connect: a failure is this rank's vote, not an error
-        mine = buf.raw if self._status("peer_export", buf) == _lib.BB_OK else None
-        handles = [None] * self.world
-        dist.all_gather_object(handles, mine)
-        ok = all(h is not None for h in handles)
-        if ok:
-            ok = self._status("peer_connect", b"".join(handles)) == _lib.BB_OK
-        if not ok:
-            self._peer_error = _lib.last_error()
-        oks = [None] * self.world
-        dist.all_gather_object(oks, bool(ok))
-        self._peer = all(oks)
-        return self._peer
-
-    def iterate_peer(self, iters, lr):
-        """`iters` x { grad, reduce + push to every peer, wait + rank-ordered sum +
-        update }, all enqueued by one C call."""
-        self._call("iterate_peer", int(iters), float(lr))
-
-    def sync_timeout(self, milliseconds):
-        """sync() that raises RuntimeError if the stream has not drained in time."""
-        self._call("sync_timeout", int(milliseconds))
-
-    def comm_abort(self):
-        self._call("comm_abort")
-
-    def peer_form(self):
-        """'one launch' (reduce, push, wait, sum and update in one kernel) or 'two launches'
-        (include/blueberry_hip.h, peer exchange)."""
-        return "one launch" if self._get(_lib.c_int, "peer_form") else "two launches"
-
-    def peer_set_form(self, one_launch):
-        """Choose the exchange's form before its first use (the same on every rank)."""
-        self._call("peer_set_form", 1 if one_launch else 0)
-
-    def peer_set_timeout(self, milliseconds):
-        self._call("peer_set_timeout", int(milliseconds))
-
-    def comm_world(self):
-        """Ranks RCCL reports for the library's communicator, or None without one."""
-        n = _lib.c_int()
-        # explicit: no communicator is an answer (None), not an error
-        if self._status("comm_world", n) != _lib.BB_OK:
-            return None
-        return int(n.value)
-
-    def peer_status(self):
-        """Synchronise and raise if a peer wait ran into its time limit."""
-        return int(self._get(_lib.c_int, "peer_status"))
-
-    def exchange_tensor(self):
-        """A torch tensor aliasing the exchange buffer [g (n_pad,3) | hi | lo].
-
-        torch allocates it (plumbing: it is what torch.distributed can reduce)
-        and the solver is told to write its partial gradient there; the solver
-        is also moved onto torch's current stream so that the collective and
-        the kernels are ordered without host synchronisation."""
-        if self._exch is None:
-            import torch
-            rts = _lib.hip_runtimes_loaded()
-            if len(rts) > 1:
-                raise RuntimeError(
-                    "two HIP runtimes are loaded (%s): import torch BEFORE the first "
-                    "blueberry_amd compute call in a distributed job, so that "
-                    "libblueberry_hip.so binds to the runtime torch uses" % ", ".join(rts))
-            tdt = torch.float32 if self.dtype == "float32" else torch.float64
-            dev = torch.device("cuda", self.device)
-            self._exch = torch.zeros(self.exchange_size(), dtype=tdt, device=dev)
-            stream = torch.cuda.current_stream(dev)
-            self._call("set_stream", _lib.c_void_p(stream.cuda_stream))
-            self._call("set_exchange_buffer", _lib.c_void_p(self._exch.data_ptr()))
-        return self._exch
-
-    # -- measurement ------------------------------------------------------
-    def set_timing(self, enabled):
-        """True / 1: HIP events around every iteration; k > 1: every k-th; False: off."""
-        self._call("set_timing", int(enabled))
-
-    def timing(self):
-        g, r, n = _lib.c_dbl(), _lib.c_dbl(), _lib.c_i64()
-        self._call("get_timing", g, r, n)
-        return {"grad_ms": float(g.value), "reduce_ms": float(r.value), "launches": int(n.value),
-                "step_ms": float(self._get(_lib.c_dbl, "get_step_timing"))}
-
-    def score_timing(self):
-        """(profile_ms, fold_ms, bins_ms) of the last `score` or `loglog` (bins_ms = 0) made with
-        timing on."""
-        t = [_lib.c_dbl() for _ in range(3)]
-        self._call("get_score_timing", *t)
-        return tuple(float(v.value) for v in t)
-
-    def event_gap_ms(self, pairs=16):
-        """Average ms between two HIP events recorded back to back behind a sweep launch:
-        what an event-timed interval contains besides its kernel (measurement aid)."""
-        return float(self._get(_lib.c_dbl, "measure_event_gap", int(pairs)))
-
-    def anchor_ms(self, launches=10):
-        """Average ms of one iteration's three anchor launches alone (`bb_solver_measure_anchors`;
-        measurement aid)."""
-        return float(self._get(_lib.c_dbl, "measure_anchors", int(launches)))
-
-    def stream_read_ms(self, launches=10):
-        """Average ms of a read-only sweep over the resident units (measurement aid)."""
-        return float(self._get(_lib.c_dbl, "measure_stream_read", int(launches)))
-
-    def iteration_path(self):
-        """'row_owner' (small one-rank maps: one launch per iteration) or 'units'."""
-        ro, wpr = _lib.c_int(), _lib.c_int()
-        self._call("iteration_path", ro, wpr)
-        return ("row_owner", int(wpr.value)) if ro.value else ("units", 0)
-
-    def traffic(self):
-        b, p = _lib.c_i64(), _lib.c_i64()
-        self._call("traffic", b, p)
-        return {"unit_bytes": int(b.value), "pairs_dense": int(p.value)}
-
-    def stream_info(self):
-        """The 24-bit stream the fp32 stress sweep reads instead of the units, where it is in
-        use (`bb_solver_stream_info`): units held packed and raw, its bytes and the changes of
-        format between consecutive units; packed_units 0 and stream_bytes 0 with no stream."""
-        v = [_lib.c_i64() for _ in range(4)]
-        self._call("stream_info", *v)
-        return dict(zip(("packed_units", "raw_units", "stream_bytes", "format_switches"),
-                        (int(x.value) for x in v)))
-
-
-class GroupEngine(_lib.Handle):
-    """Several GPUs from ONE process (`bb_group_*`): member r is a HipEngine playing rank r of
-    world R on devices[r] (a device may repeat: members then share it), each holding only its
-    own units; one host thread per member enqueues its iterations, and the partials are summed
-    by group_apply_kernel in rank order, ordered by HIP events.  To `StructureSolver` it looks
-    like one engine of world 1: every setter goes to all members, degrees, weight sums, matvecs
-    and scores come back summed over the members in rank order (float64 / int64), coordinates and
-    stress history are member 0's -- all members hold the same bits."""
-    prefix = "bb_group_"
-
-    def __init__(self, n_bins, dtype, devices, tiles=None):
-        _lib.Handle.__init__(self)
-        self.n_bins, self.dtype = int(n_bins), dtype
-        self.devices = [int(d) for d in devices]
-        self.device = self.devices[0]
-        self.world = 1                     # what the caller sees: one engine, summed results
-        self._comm_state = "group"
-        self.members = []
-        try:
-            R = len(self.devices)
-            for r, d in enumerate(self.devices):
-                self.members.append(HipEngine(n_bins, dtype, rank=r, world=R, device=d, tiles=tiles))
-            handles = (_lib.c_void_p * R)(*[m._h.value for m in self.members])
-            self._create(handles, R)
-        except BaseException:
-            self.close()
-            raise
-
-    def close(self):
-        _lib.Handle.close(self)                # the group before its members
-        for m in getattr(self, "members", ()):
-            m.close()
-        self.members = []
-
-    def _each(self, name, *args):
-        """Every member's `name`(*args), in rank order."""
-        for e in self.members:
-            getattr(e, name)(*args)
-
-    def _summed(self, name, *args):
-        """The members' `name`(*args) added on the host in rank order: (m0 + m1) + m2 ..."""
-        out = getattr(self.members[0], name)(*args)
-        for e in self.members[1:]:
-            out = out + getattr(e, name)(*args)
-        return out
-
-    def layout(self):
-        return self.members[0].layout()
-
-    # -- inputs: every member packs its own units from the one input --------------------
-    def set_wish_dense(self, matrix, kind, alpha):
-        self._each("set_wish_dense", _check_square(matrix, self.n_bins), kind, alpha)
-
-    def set_wish_sparse(self, rows, cols, vals, kind, alpha, KRnorm=None, KRexpected=None):
-        self._each("set_wish_sparse", rows, cols, vals, kind, alpha, KRnorm, KRexpected)
-
-    def set_wish_triples(self, dev_triples, kind, alpha, KRnorm=None, KRexpected=None):
-        """`dev_triples.per_device`: the triples uploaded once per distinct device."""
-        per_device = getattr(dev_triples, "per_device", {dev_triples.device: dev_triples})
-        for e in self.members:
-            e.set_wish_triples(per_device[e.device], kind, alpha, KRnorm, KRexpected)
-
-    def set_wish_from_coords(self, xstar):
-        self._each("set_wish_from_coords", _check_coords(xstar, self.n_bins))
-
-    def set_wish_resident(self, cm, kind, alpha):
-        """A resident ContactMap: members on its device pack device to device, members on
-        other devices over peer access where the devices allow it; the rest share ONE host
-        download of it."""
-        dev = cm._resident()
-        host = None
-        for e in self.members:
-            if e.device == dev.device:
-                e.set_wish_resident(cm, kind, alpha)
-                continue
-            # explicit: "without peer access" sends this member through the host, not an error
-            rc = e._status("set_wish_from_cm", dev._open(), _KINDS[kind], float(alpha))
-            if rc == _lib.BB_OK:
-                continue
-            if not (rc == _lib.BB_ERR_INVALID and "without peer access" in _lib.last_error()):
-                _lib.check(rc, "bb_solver_set_wish_from_cm")
-            if host is None:
-                host = cm.to_host()
-            e.set_wish_dense(host, kind, alpha)
-
-    # -- per-bin steps, weighting: summed on the host in rank order ---------------------
-    def degrees(self):
-        return self._summed("degrees")
-
-    def set_weight_power(self, q):
-        self._each("set_weight_power", q)
-
-    def weight_sums(self):
-        return self._summed("weight_sums")
-
-    def set_bin_steps(self, scale):
-        self._each("set_bin_steps", scale)
-
-    def score(self, xyz=None):
-        """SPEC 2.8 over the whole map: each of the members' two arrays summed in rank order."""
-        profile, bins = self.members[0].score(xyz)
-        for e in self.members[1:]:
-            p, b = e.score(xyz)
-            profile, bins = profile + p, bins + b
-        return profile, bins
-
-    def loglog(self, xyz=None):
-        """SPEC 2.11 over the whole map: the members' sums added in rank order."""
-        return self._summed("loglog", xyz)
-
-    def repower(self, p):
-        self._each("repower", p)
-
-    def matvec_sq(self, x):
-        """(D o D) @ x over the whole map: the members' products summed in rank order (the
-        host-driven spectral start)."""
-        return self._summed("matvec_sq", x)
-
-    # -- iterations -------------------------------------------------------
-    def set_coords(self, x0):
-        self._each("set_coords", _check_coords(x0, self.n_bins))
-
-    def set_momentum(self, mu):
-        self._each("set_momentum", mu)
-
-    def iterate(self, iters, lr):
-        self._call("iterate", int(iters), float(lr))
-
-    def get_coords(self):
-        return self.members[0].get_coords()
-
-    def stress_history(self):
-        return self.members[0].stress_history()
-
-    def member_coords(self):
-        """Every member's coordinates (identical bits: a check, not a result)."""
-        return [e.get_coords() for e in self.members]
-
-    def member_stress_histories(self):
-        return [e.stress_history() for e in self.members]
-
-    def sync(self):
-        self._each("sync")
-
-
-def _check_square(matrix, n_bins):
-    m = numpy.asarray(matrix)
-    _square_bins(m.shape)
-    if m.shape[0] != n_bins:
-        raise ValueError("contact matrix has %d bins, solver was created for %d"
-                         % (m.shape[0], n_bins))
-    if m.dtype != numpy.float64 or m.strides[1] != 8 or m.strides[0] % 8 or m.strides[0] < 8 * n_bins:
-        m = numpy.ascontiguousarray(m, dtype=numpy.float64)
-    return m
-
-
-def _square_bins(shape):
-    """The number of bins of a contact matrix of this shape, which has to be n x n."""
-    if len(shape) != 2 or shape[0] != shape[1]:
-        raise ValueError("contact matrix must be square, got shape %r" % (shape,))
-    return int(shape[0])
-
-
-def _kr_pair(KRnorm, KRexpected, n_bins):
-    """The two KR vectors of an input, padded to n_bins and as the pointers the C-ABI takes
-    (they keep their arrays alive), or (None, None) without them."""
-    if KRnorm is None and KRexpected is None:
-        return None, None
-    if KRnorm is None or KRexpected is None:
-        raise ValueError("KRnorm and KRexpected go together")
-    return (_lib.as_f64_ptr(_pad_vector(KRnorm, n_bins)),
-            _lib.as_f64_ptr(_pad_vector(KRexpected, n_bins)))
-
-
-def _pad_vector(v, n):
-    """KR vectors have n_bins entries, the matrix n_bins+1 bins: pad with NaN
-    (a NaN divisor = no constraint, as for unmappable bins in Rao's files)."""
-    v = numpy.asarray(v, dtype=numpy.float64).ravel()
-    if v.shape[0] > n:
-        raise ValueError("KR vector longer than the number of bins")
-    out = numpy.full(n, numpy.nan)
-    out[:v.shape[0]] = v
-    return out
-
-
-def _check_coords(x, n_bins):
-    x = numpy.ascontiguousarray(x, dtype=numpy.float64)
-    if x.shape != (n_bins, 3):
-        raise ValueError("coordinates must have shape (%d, 3), got %r" % (n_bins, x.shape))
-    if not numpy.all(numpy.isfinite(x)):
-        raise ValueError("coordinates must be finite")
-    return x
-
-
-def layout_info(n_bins, dtype):
-    """bb_layout_dense_info as a dict (host-only arithmetic: no GPU needed)."""
-    info = _lib.LayoutInfo()
-    _lib.check(_lib.load().bb_layout_dense_info(int(n_bins), _DTYPES[dtype], info),
-               "bb_layout_dense_info")
-    return info.as_dict()
-
-
-def tiles_from_entries(n_bins, rows, cols, dtype):
-    """The (tile_I, tile_J) list -- device order: J ascending, then I -- of the
-    tiles that hold at least one entry (rows[k], cols[k]); either triangle."""
-    vw = layout_info(n_bins, dtype)["vw"]     # 512, or 128 for small fp64 problems
-    r = numpy.asarray(rows, dtype=numpy.int64)
-    c = numpy.asarray(cols, dtype=numpy.int64)
-    if r.size and (min(r.min(), c.min()) < 0 or max(r.max(), c.max()) >= n_bins):
-        raise ValueError("an index is outside [0, n_bins)")
-    lo, hi = numpy.minimum(r, c) // vw, numpy.maximum(r, c) // vw
-    nb = (int(n_bins) + vw - 1) // vw
-    key = numpy.unique(hi * nb + lo)
-    return (key % nb).astype(numpy.int32), (key // nb).astype(numpy.int32)
-
-
-def tiles_from_blocks(n_bins, boundaries, band_bins, dtype):
-    """Tile list of a block-sparse genome-wide map (BASELINE config 5; SURVEY.md 8(d):
-    a tile is kept "when genomic separation <= band or the tile has any c > 0"): every
-    tile that holds a pair of bins of ONE block of `boundaries` -- a chromosome's own
-    contacts, where a Hi-C map is populated -- plus every tile that holds a pair of bins
-    at most `band_bins` apart whatever the block.  `boundaries` = ascending bin offsets
-    [0, ..., n_bins] (blueberry_amd.utils.genome_boundaries).  Replaces the dense
-    `(n_bins+1)**2` float64 matrix of the reference (`blueberry/datatypes.pyx:99`: 720 GB
-    at 10 kb) for whole-genome maps.  Returns (tile_I, tile_J) in device order and the
-    number of stored pairs i < j < n_bins inside those tiles."""
-    vw = layout_info(n_bins, dtype)["vw"]
-    n = int(n_bins)
-    b = numpy.asarray(boundaries, dtype=numpy.int64)
-    if b.ndim != 1 or b.size < 2 or b[0] != 0 or b[-1] != n or (numpy.diff(b) < 0).any():
-        raise ValueError("boundaries must ascend from 0 to n_bins")
-    nb = (n + vw - 1) // vw
-    first = numpy.arange(nb, dtype=numpy.int64) * vw
-    last = numpy.minimum(first + vw, n) - 1
-    blk_lo = numpy.searchsorted(b, first, side="right") - 1     # block of a tile's first bin
-    blk_hi = numpy.searchsorted(b, last, side="right") - 1      # ... and of its last bin
-    J, I = numpy.meshgrid(numpy.arange(nb), numpy.arange(nb))
-    upper = I <= J
-    same_block = blk_hi[I] >= blk_lo[J]           # I <= J and blocks are contiguous runs
-    near = (J - I - 1) * vw + 1 <= int(band_bins)   # closest pair of bins of the two tiles
-    sel = upper & (same_block | near)
-    ti, tj = I[sel], J[sel]
-    order = numpy.lexsort((ti, tj))
-    ti, tj = ti[order].astype(numpy.int32), tj[order].astype(numpy.int32)
-    rows = numpy.minimum(vw, n - ti.astype(numpy.int64) * vw)
-    cols = numpy.minimum(vw, n - tj.astype(numpy.int64) * vw)
-    pairs = int(numpy.where(ti == tj, rows * (rows - 1) // 2, rows * cols).sum())
-    return (ti, tj), pairs
-
-
-def block_degrees(n_bins, tiles, dtype):
-    """Per block of the layout: an upper bound on the number of stored partners of its bins
-    under a tile list (tiles in the block's row and column, times the tile edge)."""
-    vw = layout_info(n_bins, dtype)["vw"]
-    nb = (int(n_bins) + vw - 1) // vw
-    ti, tj = numpy.asarray(tiles[0]), numpy.asarray(tiles[1])
-    deg = numpy.bincount(ti, minlength=nb) + numpy.bincount(tj, minlength=nb)
-    deg -= numpy.bincount(ti[ti == tj], minlength=nb)             # a diagonal tile counts once
-    return numpy.minimum(int(n_bins), deg * vw).astype(numpy.int64)
-
-
-def max_degree(n_bins, tiles, dtype):
-    """Upper bound on the number of stored partners of any bin under a tile list: the step
-    1 / (2 * max_degree) is the one SPEC 2.4 gives a dense map of that many bins."""
-    return int(block_degrees(n_bins, tiles, dtype).max())
-
-
-def block_step_factors(n_bins, tiles, dtype):
-    """(lr, scale) of SPEC 2.4.1 for a tile list: lr = 1 / (2 max_degree) and, per block,
-    scale[b] = max_degree / degree[b] -- every block takes the step 1 / (2 degree[b]) its own
-    number of stored partners allows (a block without tiles keeps the factor 1)."""
-    deg = block_degrees(n_bins, tiles, dtype)
-    top = int(deg.max()) if deg.size and deg.max() > 0 else int(n_bins)
-    return 1.0 / (2.0 * top), numpy.where(deg > 0, top / numpy.maximum(deg, 1), 1.0)
-
-
-def degree_step_factors(degree):
-    """(lr, scale) of SPEC 2.4.1 from the bins' degrees (number of constraining pairs):
-    lr = 1 / (2 (D + 1)), D the largest degree, and scale[i] = (D + 1) / (degree[i] + 1), so
-    that bin i steps by 1 / (2 (degree[i] + 1)) -- for a complete map of n bins exactly SPEC
-    2.4's 1 / (2 n).  scale is None when all bins have the same degree."""
-    deg = numpy.asarray(degree, dtype=numpy.int64)
-    top = int(deg.max()) if deg.size else 0
-    lr = 1.0 / (2.0 * (top + 1))
-    if deg.size == 0 or int(deg.min()) == top:
-        return lr, None
-    return lr, (top + 1.0) / (deg + 1.0)
-
-
-def _sum_over_ranks(counts, eng, world):
-    """Element-wise sum of an int64 host array over the ranks (world 1: the array); a float
-    array is summed in float64 (the weighted degrees of SPEC 2.4.1)."""
-    if world <= 1:
-        return counts
-    import torch
-    import torch.distributed as dist
-    kind = numpy.float64 if numpy.asarray(counts).dtype.kind == "f" else numpy.int64
-    t = torch.from_numpy(numpy.ascontiguousarray(counts, dtype=kind))
-    if dist.get_backend() == "nccl":
-        t = t.to(torch.device("cuda", eng.device))
-        dist.all_reduce(t)
-        return t.cpu().numpy()
-    dist.all_reduce(t)
-    return t.numpy()
-
-
-# fp32 with weight_power > 0: the largest weighted degree accepted (SPEC 2.3.1).  Every
-# weight is then <= 2^60, so the smallest wish distance is 2^-30 (q = 2) or 2^-60 (q = 1)
-# relative to a unit weight, and the terms and forces stay finite in float32.
-_F32_MAX_WEIGHT_SUM = 2.0 ** 60
-
-
-def weighted_steps(sums, n_bins, dtype, lr, degree_steps):
-    """(lr, scale) for weighted stress from the bins' weighted degrees s_i (SPEC 2.4.1):
-    lr='auto' is 1 / (2 max s); degree_steps: scale[i] = max s / s_i (1 where s_i = 0), else
-    None.  Raises ValueError for a map fp32 cannot weight without overflow, or whose weights
-    are not finite."""
-    s = numpy.asarray(sums, dtype=numpy.float64)
-    top = float(s.max()) if s.size else 0.0
-    if not numpy.isfinite(top):
-        raise ValueError("weight_power: the weights delta^-q of this map overflow float64")
-    if dtype == "float32" and top > _F32_MAX_WEIGHT_SUM:
-        raise ValueError("weight_power: the largest weighted degree of this map, %.3g, exceeds "
-                         "2^60: float32 would overflow (use dtype='float64' or rescale the wish "
-                         "distances)" % top)
-    if top <= 0.0:                                    # no constraint at all
-        return (1.0 / (2.0 * n_bins) if lr == "auto" else float(lr)), None
-    out_lr = 1.0 / (2.0 * top) if lr == "auto" else float(lr)
-    if not degree_steps:
-        return out_lr, None
-    return out_lr, numpy.where(s > 0.0, top / numpy.where(s > 0.0, s, 1.0), 1.0)
-
-
-# -- the count-to-distance exponent inferred in the fit (SPEC 2.11) -------------------------------
-ALPHA_MIN, ALPHA_MAX = 0.25, 16.0      # what a step of the search is clipped to
-
-
-def _check_alpha(alpha):
-    """The constructor's `alpha` normalised: a positive float, or ('auto', alpha0, max_rounds,
-    tol) from 'auto' and the tuples that begin with it (defaults 3.0, 8, 1e-3)."""
-    if isinstance(alpha, str) or isinstance(alpha, tuple):
-        form = (alpha,) if isinstance(alpha, str) else alpha
-        if not (1 <= len(form) <= 4 and isinstance(form[0], str) and form[0] == "auto"):
-            raise ValueError("alpha must be a positive number, 'auto', ('auto', alpha0), ('auto', "
-                             "alpha0, max_rounds) or ('auto', alpha0, max_rounds, tol)")
-        def number(v, what):
-            if isinstance(v, bool) or not isinstance(v, (int, float, numpy.integer, numpy.floating)):
-                raise ValueError("alpha: %s of 'auto' must be a number" % what)
-            return float(v)
-        alpha0 = number(form[1], "the start alpha0") if len(form) > 1 else 3.0
-        rounds = form[2] if len(form) > 2 else 8
-        tol = number(form[3], "tol") if len(form) > 3 else 1e-3
-        if not (numpy.isfinite(alpha0) and alpha0 > 0):
-            raise ValueError("alpha: the start alpha0 of 'auto' must be positive and finite")
-        if (isinstance(rounds, bool) or not isinstance(rounds, (int, numpy.integer))
-                or not 1 <= int(rounds) <= 64):
-            raise ValueError("alpha: max_rounds of 'auto' must be an int in [1, 64]")
-        if not (numpy.isfinite(tol) and tol > 0):
-            raise ValueError("alpha: tol of 'auto' must be positive and finite")
-        return ("auto", alpha0, int(rounds), tol)
-    if not float(alpha) > 0:
-        raise ValueError("alpha must be positive")
-    return float(alpha)
-
-
-def loglog_totals(profile):
-    """The seven sums of SPEC 2.11 over all separations of one rank's (n_bins, 7) profile, added
-    in ascending k."""
-    p = numpy.asarray(profile, dtype=numpy.float64)
-    return numpy.cumsum(p, axis=0)[-1] if p.shape[0] else numpy.zeros(7)
-
-
-def loglog_slope(totals):
-    """(p, a, r_log, mean u, mean v) from the seven totals (pairs, sum u, sum v, sum u^2,
-    sum v^2, sum u v, pairs with d = 0): the least-squares line v = a + p u of log fitted
-    distance on log wish distance and their correlation (NaN when v does not vary).
-    ValueError: fewer than 3 usable pairs, or a var(u) that the rounding of its own sums could
-    have made (SPEC 2.8's guard): the map's counts do not vary.  RuntimeError: p <= 0."""
-    n, su, sv, suu, svv, suv = (float(t) for t in numpy.asarray(totals, dtype=numpy.float64)[:6])
-    if n < 3:
-        raise ValueError("alpha='auto': fewer than 3 usable pairs (stored, delta > 0, d > 0): "
-                         "no slope to take")
-    noise = 8.0 * n * n * 2.0 ** -53
-    var_u, var_v = n * suu - su * su, n * svv - sv * sv
-    if not var_u > noise * suu:
-        raise ValueError("alpha='auto': the wish distances of the stored pairs do not vary (the "
-                         "map's counts are all alike): no exponent can be inferred")
-    cov = n * suv - su * sv
-    p = cov / var_u
-    if not p > 0:
-        raise RuntimeError("alpha='auto': the log-log slope of fitted on wish distance is %.6g "
-                           "<= 0: the fit does not follow the map (more iterations, another "
-                           "start or a fixed alpha)" % p)
-    r_log = cov / numpy.sqrt(var_u * var_v) if var_v > noise * svv else float("nan")
-    ubar, vbar = su / n, sv / n
-    return p, vbar - p * ubar, float(r_log), ubar, vbar
-
-
-def next_alpha(history):
-    """The exponent of the next round from history = [(alpha_0, p_0), ..., (alpha_r, p_r)]
-    (SPEC 2.11): alpha_r / p_r after the first round; later a secant step on (ln alpha, ln p),
-    alpha_r / p_r again when its slope g is not finite and > 0; clipped to [alpha_r / 2,
-    2 alpha_r], then to [ALPHA_MIN, ALPHA_MAX]."""
-    a1, p1 = (float(v) for v in history[-1][:2])
-    nxt = a1 / p1
-    if len(history) >= 2:
-        a0, p0 = (float(v) for v in history[-2][:2])
-        with numpy.errstate(divide="ignore", invalid="ignore"):
-            g = numpy.float64(math.log(p1) - math.log(p0)) / numpy.float64(math.log(a1) - math.log(a0))
-        if numpy.isfinite(g) and g > 0:
-            nxt = math.exp(math.log(a1) - math.log(p1) / float(g))
-    nxt = min(max(nxt, a1 / 2.0), 2.0 * a1)
-    return min(max(nxt, ALPHA_MIN), ALPHA_MAX)
-
-
-def allreduce_exchange(t):
-    """Sum a device-resident exchange tensor over all ranks, in place: one
-    all-reduce of 3*n_pad+2 elements (backend nccl = RCCL, over xGMI)."""
-    import torch.distributed as dist
-    dist.all_reduce(t, op=dist.ReduceOp.SUM)
-
-
-def allreduce_exchange_host(eng):
-    """The same sum for a host-memory collective (backend gloo: CPU rehearsals,
-    tests, 2 ranks sharing one GPU): read the buffer through the C-ABI, reduce
-    on the host in float64, write it back.  Transport only -- the kernels on
-    either side are the same ones the RCCL path runs."""
-    import torch
-    import torch.distributed as dist
-    host = torch.from_numpy(eng.read_exchange())
-    dist.all_reduce(host, op=dist.ReduceOp.SUM)
-    eng.write_exchange(host.numpy())
-
-
-def _dist_state(distributed):
-    """(rank, world) of the running torch.distributed job, or (0, 1)."""
-    if distributed is False:
-        return 0, 1
-    if distributed is None:
-        # auto: a process that runs a torch.distributed job has imported it already;
-        # importing torch here just to find that out costs the first fit() 0.7 s
-        dist = sys.modules.get("torch.distributed")
-        if dist is None:
-            return 0, 1
-    else:
-        import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_rank(), dist.get_world_size()
-    if distributed:
-        raise RuntimeError("distributed=True but torch.distributed is not initialised")
-    return 0, 1
+# what this module uses, and every name it has ever had, which stays importable from it
+from .compare import compare_structures
+from .datatypes import (ContactMap, _nan_to_num, check_balance_args, check_coarsen_args,  # noqa: F401
+                        complete_map, triples_buffer)
+from .engine import (_DTYPES, _KINDS, GroupEngine, HipEngine, RankDeficient,  # noqa: F401
+                     _check_coords, _square_bins)
+from .exchange import (_exchange_state, allreduce_exchange, allreduce_exchange_host,  # noqa: F401
+                       comm_reuse, run_iterations, select_exchange)
+from .landmark import (LandmarkInfo, _check_landmark_weight, _check_n_landmarks,  # noqa: F401
+                       landmark_choice, landmark_coefficients, landmark_start)
+from .plan import (ALPHA_MAX, ALPHA_MIN, _check_alpha, block_degrees,  # noqa: F401
+                   block_step_factors, degree_step_factors, layout_info, loglog_slope,
+                   loglog_totals, max_degree, next_alpha, tiles_from_blocks, tiles_from_entries,
+                   weighted_steps)
+from .ranks import (all_ranks as _all_ranks, dist_state as _dist_state, gather_objects,
+                    pick_device, running_job, sum_over_ranks as _sum_over_ranks)
+from .triples import (DeviceTriples, GeodesicRows, TriplesBalance, _balance_options,  # noqa: F401
+                      _check_triples, _resident_triples, balance_triples, coarsen_triples)
 
 
 def _check_devices(devices, n_gpus, device, distributed):
@@ -1662,9 +356,7 @@ class StructureSolver(object):
             self._check_anchor_devices(None)
 
     def _pick_device(self, world):
-        if self.device is not None:
-            return int(self.device)
-        return int(os.environ.get("LOCAL_RANK", "0")) if world > 1 else 0
+        return pick_device(self.device, world > 1)
 
     @staticmethod
     def _auto_refusal(why):
@@ -1845,7 +537,6 @@ class StructureSolver(object):
     def _completed(self, X, device=None):
         """The shortest-path completion of one input map under this solver's kind and alpha,
         as a resident ContactMap of wish distances."""
-        from .datatypes import complete_map
         return complete_map(X, kind=self.kind, alpha=self.alpha,
                             device=self._completion_device() if device is None else device)
 
@@ -2123,7 +814,6 @@ class StructureSolver(object):
         """This fit against another structure `B` of the same bins (SPEC 2.10): a
         `StructureComparison`, `compare_structures(A, B, **kw)` with A = `structure_` of the last
         fit unless given -- B is laid onto A."""
-        from .compare import compare_structures
         return compare_structures(self._fitted(A, "compare"), B, **kw)
 
     def _group_devices(self):
@@ -2131,8 +821,7 @@ class StructureSolver(object):
         process (device count, no torch.distributed job), or None without them."""
         if self._group is None:
             return None
-        dist = sys.modules.get("torch.distributed")      # never imported here
-        if dist is not None and dist.is_available() and dist.is_initialized():
+        if running_job() is not None:                    # (torch is never imported here)
             raise ValueError("devices= drives several GPUs from one process; inside a "
                              "torch.distributed job every rank runs its own GPU (leave devices "
                              "unset)")
@@ -2202,7 +891,6 @@ class StructureSolver(object):
                                    or numpy.any(numpy.asarray(KRexpected)[:n_bins] == 0.0)):
             raise ZeroDivisionError("float division")      # as ContactMap.normalize
         if complete is not None:
-            from .datatypes import ContactMap
             cm = ContactMap.from_triples(triples, resolution, n_bins, KRnorm=KRnorm,
                                          KRexpected=KRexpected, device=self._completion_device())
             if balance is not None:
@@ -2281,7 +969,6 @@ class StructureSolver(object):
             # Several GPUs: the maps are independent problems, so every rank solves maps of its
             # own (dealt by size, largest first, to the rank with the least pairs so far) and
             # the results are gathered -- no exchange during the iterations at all.
-            import torch.distributed as dist
             sizes = [self._map_source(X, sparse=False)[1] for X in maps]
             load, mine = [0] * world, [[] for _ in range(world)]
             for m in sorted(range(len(maps)), key=lambda q: (-sizes[q], q)):
@@ -2296,8 +983,7 @@ class StructureSolver(object):
                                       complete)
                 part = (mine[rank], local.structures_, local.stresses_, local.lrs_,
                         getattr(local, "completed_unreachable_pairs_", None))
-            parts = [None] * world
-            dist.all_gather_object(parts, part)
+            parts = gather_objects(part, world)
             n = len(maps)
             self.structures_, self.stresses_, self.lrs_ = [None] * n, [None] * n, [None] * n
             unreachable = [None] * n
@@ -2454,275 +1140,3 @@ def spectral_init(eng, n, world, n_iter=40, seed=0, tol=0.0, return_iterations=F
     U = U * numpy.where(U.T @ G0[:, 0] < 0.0, -1.0, 1.0)
     x0 = U * numpy.sqrt(numpy.maximum(evals[order], 0.0))
     return (x0, done) if return_iterations else x0
-
-
-def _all_ranks(ok):
-    """Collective AND over the ranks of one local outcome: every rank learns whether
-    ALL of them succeeded, so that all of them take the same next step."""
-    import torch.distributed as dist
-    flags = [None] * dist.get_world_size()
-    dist.all_gather_object(flags, bool(ok))
-    return all(flags)
-
-
-_TRIAL_PEER_TIMEOUT_MS = 2000
-_TRIAL_SYNC_TIMEOUT_MS = int(os.environ.get("BB_TRIAL_SYNC_TIMEOUT_MS", "30000"))
-
-
-def _trial_leg(eng, name, step, lr, x0, iters):
-    """One transport's trial run from the start x0: one step (coordinates kept for the
-    agreement check), ten more to warm up, `iters` timed.  After EVERY stage the ranks
-    agree on whether all of them got through it; the first stage that failed anywhere
-    ends the leg on every rank, so nobody enters a collective that a peer has left.
-    Returns (ok, coordinates after one step, seconds per iteration)."""
-    import time
-    import torch.distributed as dist
-    box = {}
-
-    def stage(fn):
-        try:
-            fn()
-            ok = True
-        except Exception as exc:                 # this transport is just not used
-            eng._comm_trial_error = "%s: %s" % (name, exc)
-            ok = False
-        return _all_ranks(ok)
-
-    def settle():
-        # bounded: a collective that a peer never joined must end the leg, not the job
-        bounded = getattr(eng, "sync_timeout", None)
-        if bounded:
-            bounded(_TRIAL_SYNC_TIMEOUT_MS)
-        else:
-            eng.sync()
-        if name == "peer":
-            eng.peer_status()                    # raises when a wait ran into its limit
-
-    def first():
-        eng.set_coords(x0)
-        step(1, lr)
-        settle()
-        box["x1"] = eng.get_coords()
-
-    def warm():
-        step(10, lr)
-        settle()
-
-    def timed():
-        t0 = time.perf_counter()
-        step(iters, lr)
-        settle()
-        box["dt"] = (time.perf_counter() - t0) / iters
-        box["xk"] = eng.get_coords()             # after 1 + 10 + iters steps (outside the clock)
-
-    for k, fn in enumerate((first, warm, timed)):
-        if k == 2:
-            dist.barrier()
-        if not stage(fn):
-            return False, None, float("inf")
-    # coordinates after the FIRST step and after the LAST: a transport that delivers a stale
-    # or torn partial now and then shows in the second even when the first step went well
-    return True, (box["x1"], box["xk"]), box["dt"]
-
-
-def comm_reuse(eng):
-    """Borrow the communicator an earlier solver of this job made: the library keeps one
-    per (device, rank, world) for the life of the process, so only the first multi-rank
-    fit() pays ncclCommInitRank (0.1-1 s; round 2 made and destroyed one per fit).
-    Collective, and the same on every rank by construction: the ranks first agree that
-    EVERY one of them holds a free cached communicator, then that every attach worked;
-    otherwise nobody uses the cache and `comm_setup` makes a fresh one everywhere."""
-    if hasattr(eng, "_comm_generation"):
-        # ... and that it is the SAME communicator on all of them: the cache is keyed by
-        # (device, rank, world) only, and a rank can hold one of another generation -- made
-        # while a peer's earlier solver still held the previous one, or by an earlier process
-        # group of the same size.  Attaching those would hang the first all-reduce.
-        import torch.distributed as dist
-        gens = [None] * dist.get_world_size()
-        dist.all_gather_object(gens, eng._comm_generation())
-        if gens[0] == 0 or any(g != gens[0] for g in gens):
-            return False
-    elif not _all_ranks(eng._comm_cached()):
-        return False
-    ok = eng._comm_attach()
-    if not _all_ranks(ok):
-        if ok:
-            eng._comm_detach()
-        return False
-    return True
-
-
-def _comm_get(eng):
-    """The library's communicator for this engine: the one an earlier fit() of this job
-    left in the library's cache (`comm_reuse`), else a new one (`comm_setup`).  Collective."""
-    if hasattr(eng, "_comm_cached") and comm_reuse(eng):
-        return True
-    return eng.comm_setup()
-
-
-def _exchange_state(eng):
-    """The transport `select_exchange` chose for this engine ('group' for a GroupEngine), or
-    None: nothing chosen yet, or an engine that never sums over ranks."""
-    return getattr(eng, "_comm_state", None)
-
-
-def select_exchange(eng, lr, trial=False):
-    """Decide, once per engine and identically on every rank, how the partial
-    gradients are summed over the ranks.  Collective.
-
-    BB_COMM = auto (default) | peer | rccl | torch | host
-      peer   one-shot exchange inside the solver's own kernels (IPC-mapped arenas)
-      rccl   the library's own RCCL communicator, all-reduce enqueued from C
-      torch  torch.distributed all-reduce on a tensor aliasing the exchange buffer
-      host   exchange buffer staged through host memory (gloo / CPU rehearsals)
-    auto on an RCCL job means rccl (torch if the communicator cannot be made).  With
-    `trial` true -- bench.py, or BB_COMM_TRIAL=1 -- and the coordinates just set, auto
-    also sets up peer and runs a few iterations through both from the same start
-    (`_exchange_trial`).  The outcome is kept in eng._comm_state / eng._comm_trial."""
-    if _exchange_state(eng):
-        return eng._comm_state
-    want = os.environ.get("BB_COMM", "auto")
-    if want not in ("auto", "peer", "rccl", "torch", "host"):
-        raise ValueError("BB_COMM must be auto, peer, rccl, torch or host, not %r" % want)
-    trial = bool(trial) or os.environ.get("BB_COMM_TRIAL") == "1"
-    state = _exchange_untried(eng, want, trial)
-    if state is None:
-        have_rccl = _comm_get(eng)
-        if eng.peer_setup() and (have_rccl or hasattr(eng, "exchange_tensor")):
-            state = _exchange_trial(eng, lr, have_rccl)
-        else:
-            state = "rccl" if have_rccl else "torch"
-    eng._comm_state = state
-    return state
-
-
-def _exchange_untried(eng, want, trial):
-    """The transport where no trial decides it, or None where one does (auto on an RCCL job
-    with `trial`)."""
-    import torch.distributed as dist
-    native = hasattr(eng, "peer_setup")
-    nccl = dist.get_backend() == "nccl"
-    if not native or want == "host" or (not nccl and want != "peer"):
-        return "host"
-    if want == "peer":
-        if not eng.peer_setup():
-            raise RuntimeError("BB_COMM=peer but the peer exchange could not be set up: %s"
-                               % eng._peer_error)
-        # No trial has compared this exchange with RCCL: keep the two-launch form, which
-        # applies a step whole or not at all and whose flags are ordered by release / acquire.
-        # The one-launch form (data as its own flag, no fences) is taken where a trial has
-        # validated it against RCCL on this very job, or on request (BB_PEER_FUSED=1).
-        if not trial and os.environ.get("BB_PEER_FUSED") is None and hasattr(eng, "peer_set_form"):
-            eng.peer_set_form(False)
-        return "peer"
-    if want == "torch":
-        return "torch"
-    if want == "rccl" or not trial:
-        return "rccl" if _comm_get(eng) else "torch"
-    return None
-
-
-def _exchange_trial(eng, lr, have_rccl):
-    """Run the peer exchange against a reference from the same start and return the one to
-    use: peer only if its coordinates agree with the reference's and it is faster on the
-    slowest rank; the start is restored afterwards.  The reference, which also runs if peer
-    loses, is the library's communicator or -- when that could not be made --
-    torch.distributed's all-reduce on the exchange buffer.  Every stage ends with an
-    agreement between the ranks (`_trial_leg`), and the peer waits are cut to 2 s while it
-    runs, so a transport that fails on one rank is dropped by all of them instead of leaving
-    the others inside a collective.  Collective; the figures go to eng._comm_trial."""
-    import torch.distributed as dist
-    ref = "rccl" if have_rccl else "torch"
-    ref_step = _stepper(eng, ref)
-    x0 = eng.get_coords()
-    set_limit = getattr(eng, "peer_set_timeout", None)
-    if set_limit:
-        set_limit(_TRIAL_PEER_TIMEOUT_MS)
-    eng._comm_trial_error = None
-
-    def reference_leg():
-        run = _trial_leg(eng, ref, ref_step, lr, x0, 30)
-        if have_rccl and not run[0] and hasattr(eng, "comm_abort"):
-            # the library's communicator is suspect (this rank may still sit in a
-            # collective a peer never joined): abort it -- every rank does,
-            # the leg's outcome is shared -- so that the stream drains again
-            try:
-                eng.comm_abort()
-            except Exception as exc:
-                eng._comm_trial_error = "%s; abort: %s" % (eng._comm_trial_error, exc)
-        return run
-
-    runs = {"reference": reference_leg()}
-    runs["peer"] = _trial_leg(eng, "peer", eng.iterate_peer, lr, x0, 30)
-    if runs["reference"][0] and runs["peer"][0]:
-        # the leg that runs first is timed on a chip whose clocks have not settled
-        # (a block right after idle runs 4-19 % slow, DESIGN.md 5): the reference gets a
-        # second timing behind the peer leg and keeps its better one.  (Leg outcomes
-        # are agreed between the ranks, so every rank takes this branch or none.)
-        again = reference_leg()
-        if again[0]:
-            runs["reference"] = (True, runs["reference"][1], min(runs["reference"][2], again[2]))
-        else:
-            runs["reference"] = again
-    if set_limit and runs["peer"][0]:
-        set_limit(int(os.environ.get("BB_PEER_TIMEOUT_MS", "10000")))
-    eng.set_coords(x0)
-    scale = float(numpy.abs(x0).max() + 1e-30)
-    # one step: 1e-4 (the transports add the ranks' partials in different orders); the
-    # whole leg, 41 steps: 1e-3 -- far above what the order of a sum does over that
-    # many steps in fp32 (1e-5), far below what a lost or torn partial does
-    agree = bool(runs["reference"][0] and runs["peer"][0]
-                 and numpy.allclose(runs["reference"][1][0], runs["peer"][1][0], rtol=1e-4,
-                                    atol=1e-6 * scale)
-                 and numpy.allclose(runs["reference"][1][1], runs["peer"][1][1], rtol=1e-3,
-                                    atol=1e-5 * scale))
-    mine = (agree, runs["reference"][2], runs["peer"][2])
-    every = [None] * eng.world
-    dist.all_gather_object(every, mine)
-    t_ref = max(e[1] for e in every)
-    t_peer = max(e[2] for e in every)
-    # the reference is the plain path: the peer exchange has to win by more than the
-    # trial's own noise (3 %), not by a coin flip
-    use_peer = all(e[0] for e in every) and t_peer < 0.97 * t_ref
-    ms = lambda t: t * 1e3 if numpy.isfinite(t) else None
-    eng._comm_trial = {"agree": all(e[0] for e in every), "reference": ref,
-                       "rccl_ms": ms(t_ref),      # (the reference leg's time)
-                       "peer_ms": ms(t_peer),
-                       "error": eng._comm_trial_error}
-    if use_peer:
-        return "peer"
-    return ref if runs["reference"][0] else "torch"
-
-
-def _stepper(eng, state):
-    """The callable (k, lr) that runs k iterations of `eng` with the transport `state`
-    summing the ranks' partial gradients."""
-    if state == "peer":
-        return eng.iterate_peer
-    if state == "rccl":
-        return eng.iterate_dist
-
-    def step(k, lr):
-        # per iteration: local partial gradient -> sum over ranks -> identical update
-        t = eng.exchange_tensor() if state == "torch" else None
-        for _ in range(k):
-            eng.grad()
-            if t is None:
-                allreduce_exchange_host(eng)
-            else:
-                allreduce_exchange(t)
-            eng.apply(lr)
-    return step
-
-
-def run_iterations(eng, n_iter, lr, world):
-    """n_iter solver iterations on an engine whose inputs are set.
-
-    world == 1: the whole loop is enqueued by one C call.  world > 1: per
-    iteration, local partial gradient -> sum over ranks -> identical update on
-    every rank, so the replicas of X stay identical; `select_exchange` picks the
-    transport."""
-    if world == 1:
-        eng.iterate(n_iter, lr)
-    else:
-        _stepper(eng, select_exchange(eng, lr))(n_iter, lr)
