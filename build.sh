@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build libblueberry_hip.so (gfx950) and the CPU oracle.  Used by
+# Build libblueberry_hip.so (gfx950), the tests' probe of its fp64 routines and the CPU oracle.  Used by
 # __graft_entry__.build(); safe to run by hand.  hipcc cross-compiles without a GPU.
 # THE list of the library's sources is here.  BB_EXTRA_FLAGS: more compiler flags; BB_OUT:
 # where the library goes (tools/build_variant.sh sets both for its A/B builds).
@@ -20,5 +20,14 @@ done
     -Wno-unused-value -Wno-unused-result -fno-slp-vectorize \
     -Iinclude -Iblueberry_amd/csrc ${BB_EXTRA_FLAGS:-} \
     -o "$OUT" $SRC -ldl
+# test-only: the refined fp64 routines of the pair arithmetic behind one entry point
+# (tests/test_gpu_pair_math.py).  BB_PROBE_OUT: where it goes; a variant build (BB_OUT alone)
+# leaves the tree's probe alone.
+if [ -n "${BB_PROBE_OUT:-}" ] || [ -z "${BB_OUT:-}" ]; then
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -fvisibility=hidden \
+        -Wno-unused-value -Wno-unused-result -Wno-unused-function -fno-slp-vectorize \
+        -Iinclude -Iblueberry_amd/csrc ${BB_EXTRA_FLAGS:-} \
+        -o "${BB_PROBE_OUT:-tests/probes/librefined_f64_probe.so}" tests/probes/refined_f64_probe.hip
+fi
 make -s -C oracle
 echo "built $OUT and oracle/libbb_oracle.so"
