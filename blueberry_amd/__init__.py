@@ -33,6 +33,10 @@ Net-new (the reference has no solver; docs/SPEC.md):
                                   pixel list, the same bits (SPEC 2.12)
     coarsen_structure, prolong_structure
                                   a structure between two resolutions, host numpy (SPEC 2.12)
+    ContactMap.insulation, DeviceTriples.insulation, insulation_triples, InsulationTrack
+                                  the insulation score of a map and its domain (TAD) boundaries:
+                                  a banded pass on the device, dense and pixel list, the same
+                                  bits; score, log2 and boundary strengths in numpy (SPEC 2.13)
 
 All compute runs in libblueberry_hip.so (hand-written HIP for gfx950) behind
 the C-ABI of include/blueberry_hip.h.  Importing this package needs neither
@@ -43,7 +47,7 @@ from .utils import (HIGH_FITHIC_CUTOFF, LOW_FITHIC_CUTOFF, Q_LOWER_BOUND,  # noq
                     Q_UPPER_BOUND)
 from .band import count_band_regions  # noqa: F401
 from .datatypes import (ContactMap, EigenNoConvergence, FithicContactMap,  # noqa: F401
-                        shortest_paths)
+                        InsulationTrack, shortest_paths)
 from .compare import StructureComparison, compare_structures  # noqa: F401
 from .engine import HipEngine, RankDeficient  # noqa: F401
 from .fithic import FitHiC, binomial_sf  # noqa: F401
@@ -52,6 +56,6 @@ from .resolution import coarsen_structure, prolong_structure  # noqa: F401
 from .solver import FitScore, StructureSolver  # noqa: F401
 from .stats import benjamini_hochberg, downsample, q_values  # noqa: F401
 from .triples import (DeviceTriples, GeodesicRows, TriplesBalance, balance_triples,  # noqa: F401
-                      coarsen_triples)
+                      coarsen_triples, insulation_triples)
 
 __version__ = "0.1.0"

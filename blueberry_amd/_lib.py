@@ -182,6 +182,10 @@ SIGNATURES = {
     "bb_triples_coarsen_timing": (c_int, [c_void_p, p_dbl]),
     "bb_triples_size": (c_int, [c_void_p, p_i64]),
     "bb_triples_download": (c_int, [c_void_p, p_dbl]),
+    "bb_cm_insulation": (c_int, [c_void_p, c_i64, c_i64, c_i64, p_dbl, p_dbl, p_i64]),
+    "bb_cm_insulation_timing": (c_int, [c_void_p, p_dbl]),
+    "bb_triples_insulation": (c_int, [c_void_p, c_i64, c_i64, c_i64, p_dbl, p_dbl, p_i64]),
+    "bb_triples_insulation_timing": (c_int, [c_void_p, p_dbl]),
     "bb_solver_set_wish_from_cm": (c_int, [c_void_p, c_void_p, c_int, c_dbl]),
     "bb_solver_set_wish_from_cm_block": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_dbl]),
     "bb_solver_set_maps": (c_int, [c_void_p, c_int, p_i64, p_dbl]),

@@ -310,6 +310,7 @@ struct bb_cm {
     // list.  Two, so that alternating calls do not rebuild the lists.
     bb::ProductScratch sv, bal;
     double coarsen_ms = 0.0;  // on a map bb_cm_coarsen wrote: the pooling kernel, by HIP events
+    double insulation_ms = 0.0;  // the kernel of the last bb_cm_insulation on this map, by HIP events
 };
 
 namespace bb {

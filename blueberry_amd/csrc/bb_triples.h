@@ -68,6 +68,7 @@ struct bb_triples {
     bb::TriplesIndex index;             // (bb_triples_balance.hip; freed with the handle)
     double coarsen_ms = 0.0;            // on a list bb_triples_coarsen left: count + scan + write
                                         // over the source's index, by HIP events
+    double insulation_ms = 0.0;         // the kernel of the last bb_triples_insulation, by HIP events
     const double *from(int64_t t0) const { return d.as<double>() + t0 * (st == 3 ? 3 : 1); }
 };
 

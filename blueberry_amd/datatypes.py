@@ -223,6 +223,140 @@ def _expected(target, n, bias):
     return expected_from_sums(sums, counts)
 
 
+def check_insulation_args(window, ignore_diags=2, min_valid=0.66):
+    """(window, ignore_diags, min_valid) of `ContactMap.insulation`, `DeviceTriples.insulation` and
+    `insulation_triples`, checked (ValueError) without touching the library: an int >= 1, an
+    int >= 0 -- no bool, no float -- and a share in [0, 1]."""
+    def whole(v):
+        return isinstance(v, (int, numpy.integer)) and not isinstance(v, bool)
+    if not whole(window) or int(window) < 1:
+        raise ValueError("window must be an int >= 1")
+    if not whole(ignore_diags) or int(ignore_diags) < 0:
+        raise ValueError("ignore_diags must be an int >= 0")
+    min_valid = float(min_valid)
+    if not 0.0 <= min_valid <= 1.0:
+        raise ValueError("min_valid must be in [0, 1]")
+    return int(window), int(ignore_diags), min_valid
+
+
+def insulation_full_cells(window, ignore_diags):
+    """The cells of an unclipped diamond: window^2 less the cells nearer the diagonal than
+    `ignore_diags` -- offset k = b - a has k + 1 cells up to window - 1 and 2 window - 1 - k above
+    (docs/SPEC.md 2.13; window 10, ignore_diags 2: 97)."""
+    w = int(window)
+    k = numpy.arange(min(int(ignore_diags), 2 * w - 1), dtype=numpy.int64)
+    return w * w - int(numpy.where(k <= w - 1, k + 1, 2 * w - 1 - k).sum())
+
+
+def _local_maxima(x):
+    """`scipy.signal.find_peaks(x)[0]` of a NaN-free vector: the samples higher than both
+    neighbours, a plateau once at floor((l + r) / 2); an end sample, or a plateau that reaches
+    one, never."""
+    n = x.shape[0]
+    change = numpy.flatnonzero(x[1:] != x[:-1]) + 1          # where a new plateau starts
+    starts = numpy.concatenate([numpy.zeros(1, dtype=numpy.int64), change])
+    ends = numpy.concatenate([change, numpy.full(1, n, dtype=numpy.int64)]) - 1
+    v = x[starts]
+    k = numpy.flatnonzero((v[1:-1] > v[:-2]) & (v[1:-1] > v[2:])) + 1
+    return ((starts[k] + ends[k]) // 2).astype(numpy.int64)
+
+
+def _nearest_higher_left(x):
+    """L[i]: the nearest j < i with x[j] > x[i], -1 where there is none.  Pointer jumping: nothing
+    between L[i] and i is higher than x[i] at any time, so a candidate that is not higher is
+    replaced by its own candidate -- every bin at once, a few passes."""
+    L = numpy.arange(-1, x.shape[0] - 1)
+    todo = numpy.flatnonzero(L >= 0)
+    while todo.shape[0]:
+        todo = todo[x[L[todo]] <= x[todo]]
+        L[todo] = L[L[todo]]
+        todo = todo[L[todo] >= 0]
+    return L
+
+
+def _prominences(x, peaks):
+    """`scipy.signal.peak_prominences(x, peaks)[0]` of a NaN-free vector: from each peak out to
+    the nearest higher sample on either side (or the end), the lowest sample of each stretch;
+    the peak less the higher of the two.  Comparisons and one subtraction."""
+    n = x.shape[0]
+    if peaks.shape[0] == 0:
+        return numpy.zeros(0)
+    first = _nearest_higher_left(x)[peaks] + 1                        # the left stretch is [first, peak]
+    end = n - 1 - _nearest_higher_left(x[::-1])[n - 1 - peaks]        # the right one [peak, end)
+    xs = numpy.append(x, numpy.inf)                                   # (so that end = n is an index)
+    left = numpy.minimum.reduceat(xs, numpy.stack([first, peaks + 1], axis=1).ravel())[::2]
+    right = numpy.minimum.reduceat(xs, numpy.stack([peaks, end], axis=1).ravel())[::2]
+    return x[peaks] - numpy.maximum(left, right)
+
+
+class InsulationTrack(object):
+    """The insulation score of a map along its diagonal and its domain boundaries (docs/SPEC.md
+    2.13), from the two vectors the device leaves -- `sums` (float64) and `counts` (int64) of the
+    live cells of every bin's diamond of `window` bins, cells nearer the diagonal than
+    `ignore_diags` left out.  Host numpy, O(n_bins); needs no device.
+
+    sums, counts    as given
+    full_cells      the cells of an unclipped diamond
+    score           sums / counts; NaN where counts is 0 or below min_valid * full_cells
+    log2            log2(score / mean), the mean over the finite positive scores; NaN where the
+                    score is NaN or <= 0
+    strength        the boundary strength -- the prominence of the minimum of `log2` within its
+                    maximal run of finite values (`scipy.signal.find_peaks` and `peak_prominences`
+                    of the negated run, bit for bit) -- at the bins that are local minima, NaN
+                    elsewhere; a plateau counts once, in its middle; the ends of a run never
+    kernel_ms       the ms of the kernel that made `sums`, by HIP events (0.0 if not given)"""
+
+    def __init__(self, sums, counts, window, ignore_diags, n_bins, resolution, min_valid=0.66,
+                 kernel_ms=0.0):
+        self.window, self.ignore_diags, self.min_valid = check_insulation_args(window, ignore_diags, min_valid)
+        self.n_bins, self.resolution, self.kernel_ms = int(n_bins), int(resolution), float(kernel_ms)
+        self.sums = numpy.asarray(sums, dtype=numpy.float64)
+        self.counts = numpy.asarray(counts, dtype=numpy.int64)
+        if self.sums.shape != (self.n_bins,) or self.counts.shape != (self.n_bins,):
+            raise ValueError("sums and counts must have n_bins = %d values" % self.n_bins)
+        self.full_cells = insulation_full_cells(self.window, self.ignore_diags)
+        ok = (self.counts > 0) & (self.counts >= self.min_valid * self.full_cells)
+        self.score = numpy.full(self.n_bins, numpy.nan)
+        with numpy.errstate(invalid="ignore", over="ignore"):
+            self.score[ok] = self.sums[ok] / self.counts[ok]
+            good = numpy.isfinite(self.score) & (self.score > 0.0)
+            self.log2 = numpy.full(self.n_bins, numpy.nan)
+            if good.any():
+                self.log2[good] = numpy.log2(self.score[good] / self.score[good].mean())
+        self.strength = numpy.full(self.n_bins, numpy.nan)
+        finite = numpy.isfinite(self.log2)
+        edge = numpy.flatnonzero(numpy.diff(numpy.concatenate([[False], finite, [False]]).astype(numpy.int8)))
+        for lo, hi in zip(edge[::2], edge[1::2]):            # the maximal runs [lo, hi) of finite log2
+            x = -self.log2[lo:hi]
+            peaks = _local_maxima(x)
+            self.strength[lo + peaks] = _prominences(x, peaks)
+
+    def boundaries(self, min_strength=0.0):
+        """(bins, strengths): the local minima of `log2` whose strength is at least
+        `min_strength`, bins int64 ascending."""
+        with numpy.errstate(invalid="ignore"):
+            bins = numpy.flatnonzero(self.strength >= float(min_strength)).astype(numpy.int64)
+        return bins, self.strength[bins]
+
+
+def _insulation(target, n, args, bias, resolution):
+    """`ContactMap.insulation` and `DeviceTriples.insulation` in one: the track of `target`'s map
+    over bins 0 .. n - 1 under `args`, the tuple `check_insulation_args` returned, and `bias`
+    (None or n values), by `bb_cm_insulation` / `bb_triples_insulation`."""
+    window, ignore_diags, min_valid = args
+    if bias is not None:
+        bias = numpy.ascontiguousarray(bias, dtype=numpy.float64)
+        if bias.shape != (n,):
+            raise ValueError("bias must have n_bins = %d values, got shape %r" % (n, bias.shape))
+    dev = target._balance_target()
+    sums = numpy.zeros(n, dtype=numpy.float64)
+    counts = numpy.zeros(n, dtype=numpy.int64)
+    dev._call("insulation", n, window, ignore_diags, None if bias is None else _lib.as_f64_ptr(bias),
+              _lib.as_f64_ptr(sums), counts.ctypes.data_as(_lib.p_i64))
+    return InsulationTrack(sums, counts, window, ignore_diags, n, resolution, min_valid,
+                           dev._get(_lib.c_dbl, "insulation_timing"))
+
+
 class EigenNoConvergence(RuntimeError):
     """`ContactMap.eigenvector` used up `max_matvecs` before its residual reached the
     tolerance (the counterpart of scipy's ArpackNoConvergence, which the reference's
@@ -548,6 +682,19 @@ class ContactMap(object):
             self._divide(bias, numpy.ones(self.n_bins))
         return bias
 
+    def _bias_argument(self, bias):
+        """The `bias` of `expected()` and `insulation()`: 'auto' -- the map's KRnorm, cut to n_bins
+        values, or None if there is none; anything else as it is."""
+        if not isinstance(bias, str):
+            return bias
+        if bias != "auto":
+            raise ValueError("bias must be 'auto', None or a vector of n_bins values")
+        if self._KRnorm is None:
+            return None
+        if self._KRnorm.shape[0] < self.n_bins:
+            raise ValueError("KRnorm shorter than n_bins")
+        return self._KRnorm[:self.n_bins]
+
     def expected(self, bias="auto", apply=False):
         """The distance-decay expected of the balanced map: e[k] = the mean over the live pairs
         at distance k of M[i, i+k] / (bias[i] bias[i+k]), k = 0 .. n_bins - 1, in one sweep of the
@@ -562,15 +709,7 @@ class ContactMap(object):
         e[|i - j|] alone (`normalize()` with an all-ones bias).  After `balance()` and
         `expected()` without `apply`, `normalize()` applies both, as on a Rao map."""
         n = self.n_bins
-        if isinstance(bias, str):
-            if bias != "auto":
-                raise ValueError("bias must be 'auto', None or a vector of n_bins values")
-            bias = None if self._KRnorm is None else self._KRnorm
-            if bias is not None:
-                if bias.shape[0] < n:
-                    raise ValueError("KRnorm shorter than n_bins")
-                bias = bias[:n]
-        self._KRexpected = _expected(self, n, bias)
+        self._KRexpected = _expected(self, n, self._bias_argument(bias))
         if apply:
             self._divide(numpy.ones(n), self._KRexpected)
         return self._KRexpected
@@ -656,6 +795,25 @@ class ContactMap(object):
         out._dev = _DeviceMatrix(nc + 1, src.device)
         src._call("coarsen", n, factor, how, out._dev._open())
         return out
+
+    def insulation(self, window, ignore_diags=2, bias="auto", min_valid=0.66):
+        """The insulation score of the map and its domain (TAD) boundaries as an `InsulationTrack`
+        (docs/SPEC.md 2.13; Crane et al. 2015, cooltools' convention): per bin i the sum and the
+        number of the live cells of the diamond of `window` bins whose corner sits on (i, i) --
+        rows i - window + 1 .. i, columns i .. i + window - 1, clipped to the map, the cells
+        nearer the diagonal than `ignore_diags` left out -- each cell divided by bias_a bias_b, in
+        one banded pass over the resident upper triangle (`bb_cm_insulation`); score, log2 and
+        boundaries follow on the host.  A bin with a NaN bias is not live: its cells are neither
+        added nor counted.  A bin whose diamond has fewer than `min_valid` of an unclipped
+        diamond's cells gets no score.
+
+        `bias` as in `expected()`: 'auto' -- the map's KRnorm (what `balance()` left, or what the
+        constructor was given) if there is one, else all ones; None -- all ones, for a map that
+        is balanced already; or a length-n_bins vector.  Float64 in a fixed order of summation:
+        the same bits on every run, and the bits `insulation_triples` gives from the pixel list.
+        The map is left as it is and stays resident; a filtered map is refused."""
+        args = check_insulation_args(window, ignore_diags, min_valid)
+        return _insulation(self, self.n_bins, args, self._bias_argument(bias), self.resolution)
 
     def plot(self, arcsinh=True, **kwargs):
         """Plot the contact map onto the current palette (pyx:190-214)."""

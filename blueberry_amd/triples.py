@@ -1,12 +1,13 @@
 """A Rao-format pixel list on the device: the `DeviceTriples` handle and the `GeodesicRows` its
-shortest paths leave, and balancing and pooling a map straight from its triples (docs/SPEC.md
-2.1.2, 2.5.3, 2.12)."""
+shortest paths leave, and balancing, pooling and the insulation score of a map straight from its
+triples (docs/SPEC.md 2.1.2, 2.5.3, 2.12, 2.13)."""
 import contextlib
 
 import numpy
 
 from . import _lib
-from .datatypes import _balance, _expected, check_balance_args, check_coarsen_args, triples_buffer
+from .datatypes import (_balance, _expected, _insulation, check_balance_args, check_coarsen_args,
+                        check_insulation_args, triples_buffer)
 from .engine import _kr_pair
 from .plan import _DTYPES, _KINDS, layout_info
 from .ranks import pick_device, several_ranks
@@ -96,6 +97,15 @@ class DeviceTriples(_lib.Handle):
         live bin.  `expected_sums_` and `expected_counts_` (int64) hold the two raw vectors;
         pairs without a triple are zero cells and count."""
         return _expected(self, _bin_count(n_bins), bias)
+
+    def insulation(self, n_bins, window, ignore_diags=2, bias=None, min_valid=0.66):
+        """The `InsulationTrack` of the map the triples define over bins 0 .. n_bins - 1
+        (`ContactMap.insulation`; docs/SPEC.md 2.13), bit for bit what `ContactMap.from_triples(
+        ...).insulation(...)` gives, without that matrix (`bb_triples_insulation`; the first call
+        builds the handle's index, as `balance` does).  bias None -- all ones -- or a length-n_bins
+        vector, NaN = not a live bin; pairs without a triple are zero cells and count."""
+        args = check_insulation_args(window, ignore_diags, min_valid)
+        return _insulation(self, _bin_count(n_bins), args, bias, self.resolution)
 
     def significance(self, map_bins, **kwargs):
         """The Fit-Hi-C p- and q-values of the map the triples define over bins 0 .. map_bins - 1
@@ -295,3 +305,16 @@ def coarsen_triples(triples, resolution, n_bins, factor, how="sum", device=None)
     with _resident_triples(triples, resolution, [pick_device(device, several_ranks())]) as dev:
         with dev.coarsen(n, factor, how) as pooled:
             return pooled.to_host(), pooled.n_bins_
+
+
+def insulation_triples(triples, resolution, n_bins, window, ignore_diags=2, bias=None, min_valid=0.66,
+                       device=None):
+    """The insulation score and the domain boundaries of a map straight from its Rao-format (n, 3)
+    triples [pos_i, pos_j, count], never building the dense matrix (`DeviceTriples.insulation`;
+    docs/SPEC.md 2.13): the `InsulationTrack` that `ContactMap.from_triples(triples, resolution,
+    n_bins).insulation(window, ignore_diags, bias, min_valid)` gives, bit for bit.  `triples` may
+    be a `DeviceTriples` (its own resolution and device are used; it stays open)."""
+    check_insulation_args(window, ignore_diags, min_valid)
+    n = _bin_count(n_bins)
+    with _resident_triples(triples, resolution, [pick_device(device, several_ranks())]) as dev:
+        return dev.insulation(n, window, ignore_diags, bias, min_valid)

@@ -13,7 +13,7 @@ SRC=""
 for f in bb_api.cpp bb_comm.cpp bb_solver_plan.cpp bb_solver.hip bb_solver_anchors.hip \
          bb_solver_spectral.hip bb_group.hip bb_score.hip bb_compare.hip bb_band.hip \
          bb_contactmap.hip bb_shortest.hip bb_balance.hip bb_triples_balance.hip bb_triples_paths.hip \
-         bb_significance.hip bb_coarsen.hip bb_sort.hip bb_misc.hip; do
+         bb_significance.hip bb_coarsen.hip bb_insulation.hip bb_sort.hip bb_misc.hip; do
     SRC="$SRC blueberry_amd/csrc/$f"
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -fvisibility=hidden \

@@ -948,6 +948,33 @@ BB_API int bb_triples_coarsen(bb_triples *src, int64_t n_bins, int64_t factor, i
 BB_API int bb_triples_coarsen_timing(const bb_triples *dst, double *pool_ms);
 BB_API int bb_triples_size(const bb_triples *t, int64_t *n);
 BB_API int bb_triples_download(const bb_triples *t, double *triples);
+/* The insulation sums of a map (docs/SPEC.md 2.13; Crane et al. 2015, cooltools' convention).
+ * M is the leading n x n block (n = n_bins) of the resident (n_bins + 1)^2 matrix, or the matrix
+ * resident triples define (bb_triples_balance's rules and index); symmetric, only a <= b is read.
+ * window w >= 1 in bins; ignore_diags g >= 0; bias: n_bins host doubles, NULL = all ones.
+ * x = 1 / bias, 0 where the bias is NaN; bin a is live iff x_a != 0; a cell is live iff both of
+ * its bins are.  The diamond of bin i is the cells (a, b) with
+ *   max(0, i - w + 1) <= a <= i <= b <= min(n - 1, i + w - 1)  and  b - a >= g
+ * (bin i sits on both sides; w > n is legal: the diamond is clipped).
+ * sums[i], float64 in a FIXED order: per row a of the diamond, top to bottom, a row partial of
+ * M_ab (x_a x_b) over the row's live cells, left to right; then the partials top to bottom; every
+ * accumulator from +0.0, so that a zero, dead or absent cell may be added as 0 or skipped (as in
+ * bb_cm_coarsen).  The product and the sum are two roundings (no fma).  Both routes give the
+ * same bits, on every run; no atomics.  Values are added as stored: a NaN or an infinity reaches
+ * exactly the bins whose diamond holds its live cell.
+ * counts[i]: the number of live cells of the diamond, zero and absent cells included -- for each
+ * live row a the live bins of [max(i, a + g), min(n - 1, i + w - 1)], from a prefix count of the
+ * live bins; one host rule for both routes.
+ * window < 1, ignore_diags < 0, an edge that is not n_bins + 1 (a filtered map), a triple's bin
+ * outside [0, n_bins]: BB_ERR_INVALID.  The map is not changed.
+ * bb_cm_insulation_timing, bb_triples_insulation_timing: the ms of the kernel of the handle's
+ * last call, by HIP events (the triples' index build apart). */
+BB_API int bb_cm_insulation(bb_cm *cm, int64_t n_bins, int64_t window, int64_t ignore_diags,
+                            const double *bias, double *sums, int64_t *counts);
+BB_API int bb_cm_insulation_timing(const bb_cm *cm, double *kernel_ms);
+BB_API int bb_triples_insulation(bb_triples *t, int64_t n_bins, int64_t window, int64_t ignore_diags,
+                                 const double *bias, double *sums, int64_t *counts);
+BB_API int bb_triples_insulation_timing(const bb_triples *t, double *kernel_ms);
 /* Hand the resident matrix to a solver of n_bins = d bins on the same device, device
  * to device (same meaning of kind / alpha as bb_solver_set_wish_dense).  A solver on another
  * device packs over peer access where hipDeviceCanAccessPeer allows it (enabled here); without
