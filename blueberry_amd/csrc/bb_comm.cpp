@@ -35,4 +35,9 @@ const Rccl &rccl() {
     return table;
 }
 
+CommCache &comm_cache() {
+    static CommCache cache(rccl().CommDestroy, rccl().CommAbort);
+    return cache;
+}
+
 }  // namespace bb

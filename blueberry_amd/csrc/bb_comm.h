@@ -6,9 +6,12 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "bb_comm_cache.h"
+
 namespace bb {
 
 constexpr int kUniqueIdBytes = 128;  // NCCL_UNIQUE_ID_BYTES (rccl.h:40)
+static_assert(kUniqueIdBytes == (int)kCommIdBytes, "the cache hashes a whole unique id");
 
 struct Rccl {
     // mirrors of the RCCL ABI we call (rccl.h:43, :187, :220, :260, :448, :466, :611)
@@ -27,5 +30,9 @@ struct Rccl {
 
 // The process-wide table (loaded once); ok == false if librccl is not loadable.
 const Rccl &rccl();
+
+// The process-wide cache of the library's communicators (bb_comm_cache.h), ending them with the
+// table's ncclCommDestroy and -- where this librccl has one -- ncclCommAbort.
+CommCache &comm_cache();
 
 }  // namespace bb

@@ -1,4 +1,4 @@
-// bb_score.h -- what bb_solver_score (bb_solver.hip: the handle and its state rules) hands
+// bb_score.h -- what bb_solver_score (bb_solver_queries.hip: the handle and its state rules) hands
 // to the scoring pass (bb_score.hip: the kernels and their launches).
 #pragma once
 

@@ -1,7 +1,7 @@
 // bb_score.hip -- scoring a structure against the resident map (docs/SPEC.md 2.8, DESIGN.md
 // 4.16): one pass over a rank's units that forms, in float64, nine sums per genomic separation
 // k = j - i and three sums per bin over the constrained pairs.  No iteration, no solver state:
-// bb_solver_score (bb_solver.hip) checks the handle and hands its views in (bb_score.h).
+// bb_solver_score (bb_solver_queries.hip) checks the handle and hands its views in (bb_score.h).
 // gfx950 only.
 //
 // Three kernels, no floating-point atomics, every sum in an order fixed by the layout and the

@@ -160,7 +160,7 @@ int bb_solver_anchor_info(const bb_solver *s, int64_t *kept_rows, int64_t *terms
     return BB_OK;
 }
 
-// (bb_solver_anchor_sums is in bb_solver.hip, with its two kernels: see bb_solver_kernels.h)
+// (bb_solver_anchor_sums is in bb_solver_queries.hip, with its two kernels: see bb_query_kernels.h)
 
 int bb_solver_anchor_stress(bb_solver *s, double *stress) {
     BB_TRY(check_ready(s, "bb_solver_anchor_stress"));

@@ -3,8 +3,11 @@
 // store), the op / mode constants that host and kernels both name, the peer exchange's tables,
 // the momentum step and the fixed-order sums.  Helpers only -- no kernel is defined here, so a
 // file that includes it compiles none: every kernel belongs to exactly one translation unit,
-//   bb_solver_kernels.h    sweep, reduce, peer, apply, row-owner, 24-bit stream, bb_solver.hip
-//                          pack / scatter / gen / repower / degrees / weights
+//   bb_solver_kernels.h    sweep, reduce, one-launch exchange, apply,            bb_solver.hip
+//                          row-owner, 24-bit stream
+//   bb_peer_kernels.h      the peer exchange's waits, peer_receive_kernel        bb_solver_exchange.hip
+//   bb_input_kernels.h     pack / scatter / gen / repower, units -> full matrix  bb_solver_inputs.hip
+//   bb_query_kernels.h     degrees / weight sums / anchor sums, read probes      bb_solver_queries.hip
 //   bb_anchor_kernels.h   landmark constraints                                  bb_solver_anchors.hip
 //   bb_spectral_kernels.h  the N x 3 algebra of the spectral start               bb_solver_spectral.hip
 // and group_apply_kernel to bb_group.hip.  Everything here lives in the including translation
@@ -295,6 +298,29 @@ __device__ __forceinline__ void lds_tree_fold(double *sh, int tid, int n) {
     for (int off = n >> 1; off > 0; off >>= 1) {
         if (tid < off) sh[tid] += sh[tid + off];
         __syncthreads();
+    }
+}
+
+// Matrix rows are read exactly once per launch: NT = true marks the loads
+// non-temporal so the stream does not evict X and the partials from L2 / MALL.
+typedef float f32x4_raw __attribute__((ext_vector_type(4)));
+typedef double f64x2_raw __attribute__((ext_vector_type(2)));
+template <bool NT>
+__device__ __forceinline__ float4 stream_load(const float4 *p) {
+    if constexpr (NT) {
+        const f32x4_raw v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_raw *>(p));
+        return make_float4(v.x, v.y, v.z, v.w);
+    } else {
+        return *p;
+    }
+}
+template <bool NT>
+__device__ __forceinline__ double2 stream_load(const double2 *p) {
+    if constexpr (NT) {
+        const f64x2_raw v = __builtin_nontemporal_load(reinterpret_cast<const f64x2_raw *>(p));
+        return make_double2(v.x, v.y);
+    } else {
+        return *p;
     }
 }
 

@@ -1,7 +1,9 @@
 // bb_solver_internal.h -- what the translation units of the 3D-structure solver share on the
 // host: the bb_solver handle, the layout / dtype dispatchers, and the helpers that cross files.
-//   bb_solver.hip           the handle, the sweep plan's device half, the launch layer, iterate;
-//                           the input routes and the exchanges between ranks (RCCL, peer arenas)
+//   bb_solver.hip           the handle, the sweep plan's device half, the launch layer, iterate
+//   bb_solver_inputs.hip    every writer of the units, and the resident triples' handle
+//   bb_solver_exchange.hip  the exchanges between ranks: RCCL (over bb_comm_cache.h), peer arenas
+//   bb_solver_queries.hip   degrees and weight sums, the score, timing getters, probes
 //   bb_solver_anchors.hip   landmark constraints
 //   bb_solver_spectral.hip  the spectral start
 //   bb_group.hip            several solvers of one process
@@ -11,9 +13,11 @@
 // Who owns what: every device allocation and event of a handle (bb_solver, bb_triples, bb_group)
 // is a bb::DevBuf / bb::Event member of it (bb_common.h) and goes with the handle, or earlier
 // by reset(); a staging buffer is such an owner as a local.  Plain pointers are views: into the
-// solver's arena, or -- d_exch -- of own_exch or of a caller's memory.  The destroy functions
-// keep only what has an order: the stream (the pool's), the communicator (the cache's, or the
-// solver's own) and the peers' arenas it opened.
+// solver's arena, or -- d_exch -- of own_exch or of a caller's memory.  The communicator is a
+// bb::CommLease (bb_comm_cache.h: the cache's, or the solver's own) and what the peer exchange
+// made a bb::solver::PeerLink; both are members and end with the handle like the rest.  The
+// destroy functions keep only what has an order: the stream (the pool's), drained before the
+// members go and given back after them.
 #pragma once
 
 #include <string>
@@ -24,6 +28,48 @@
 #include "bb_common.h"
 #include "bb_solver_device.h"
 #include "bb_solver_plan.h"
+
+namespace bb {
+namespace solver {
+
+// Everything bb_solver_peer_export and bb_solver_peer_connect make.  The arena's layout: 2
+// parities x world slots of data | per-rank flags | poison words.
+struct PeerLink {
+    bb::DevBuf arena;                  // this rank's receive arena (uncached)
+    int world = 1;                     // the solver's, as of the export: the arena's shape
+    int64_t elem_bytes = 4, slot_elems = 0, arena_bytes = 0;
+    std::vector<void *> mapped;        // arenas of all ranks as mapped here (own = arena)
+    std::vector<void *> opened;        // the ones that came from hipIpcOpenMemHandle
+    bb::DevBuf d_table;                // PeerTable<T>[2], one per parity
+    bb::DevBuf d_table_x;              // PeerTableX<T>[2]: the one-launch exchange
+    bool fused = true;                 // reduce_exchange_kernel (BB_PEER_FUSED=0: two launches)
+    bb::DevBuf d_state;                // PeerState: sticky failure flag + last complete exchange
+    int clock_khz = 100000;            // constant-rate clock behind wall_clock64()
+    int ranks_on_gpu = 1;              // most ranks of the job on one GPU (a rehearsal: > 1)
+    bb::DevBuf d_mask;                 // unsigned per block: the ranks whose units touch it (bit r)
+    bb::DevBuf d_counter;              // unsigned: the reduce's two-level check-in
+    unsigned long long seq = 0;        // iterations exchanged so far
+    long long limit_ticks = 0;
+    bool connected = false;
+
+    PeerLink() = default;
+    PeerLink(const PeerLink &) = delete;
+    PeerLink &operator=(const PeerLink &) = delete;
+    // the peers' arenas are closed before this rank's own buffers go (the members, after this)
+    ~PeerLink() {
+        for (void *m : opened) hipIpcCloseMemHandle(m);
+    }
+
+    int64_t flags_offset() const { return 2 * (int64_t)world * slot_elems * elem_bytes; }
+    // the one-launch exchange (reduce_exchange_kernel): one poison word per source rank behind
+    // the per-rank flags of the two-launch form (its data words say by themselves whether they
+    // have arrived)
+    int64_t xpoison_offset() const { return flags_offset() + bb::round_up((int64_t)world * 64, 256); }
+    int64_t arena_size() const { return xpoison_offset() + bb::round_up((int64_t)world * 64, 256); }
+};
+
+}  // namespace solver
+}  // namespace bb
 
 struct bb_solver {
     int dtype = BB_F32, device = 0, rank = 0, world = 1;
@@ -80,27 +126,6 @@ struct bb_solver {
     // mu = 0, lr = -1: 0 + (0 * v - (-1) * sum) is the sum, exactly)
     void *sum_target = nullptr;
 
-    bb::Rccl::Comm comm = nullptr;  // direct RCCL path (bb_solver_comm_init), else null
-    bool comm_cached = false;       // the communicator belongs to the process-wide cache
-    bool comm_suspect = false;      // a collective on it failed to enqueue: never handed out again
-
-    // peer exchange (bb_solver_peer_*)
-    bb::DevBuf peer_arena;                  // this rank's receive arena (uncached)
-    int64_t peer_slot_elems = 0, peer_arena_bytes = 0;
-    std::vector<void *> peer_mapped;        // arenas of all ranks as mapped here (own = peer_arena)
-    std::vector<void *> peer_opened;        // the ones that came from hipIpcOpenMemHandle
-    bb::DevBuf d_peer_table;                // PeerTable<T>[2], one per parity
-    bb::DevBuf d_peer_table_x;              // PeerTableX<T>[2]: the one-launch exchange
-    bool peer_fused = true;                 // reduce_exchange_kernel (BB_PEER_FUSED=0: two launches)
-    bb::DevBuf d_peer_state;                // PeerState: sticky failure flag + last complete exchange
-    int peer_clock_khz = 100000;            // constant-rate clock behind wall_clock64()
-    int peer_ranks_on_gpu = 1;              // most ranks of the job on one GPU (a rehearsal: > 1)
-    bb::DevBuf d_peer_mask;                 // unsigned per block: the ranks whose units touch it (bit r)
-    bb::DevBuf d_peer_counter;              // unsigned: the reduce's two-level check-in
-    unsigned long long peer_seq = 0;        // iterations exchanged so far
-    long long peer_limit_ticks = 0;
-    bool peer_connected = false;
-
     // row-owner path (small maps, world = 1): both triangles resident, one launch per
     // iteration (row_owner_kernel); the units stay resident too and serve every other
     // entry point (grad / apply, stress, matvec)
@@ -139,6 +164,11 @@ struct bb_solver {
     std::vector<bb::Event> ev;   // triples: start, after grad, after reduce
     size_t ev_used = 0;
     double score_ms[3] = {0.0, 0.0, 0.0};   // the last timed bb_solver_score: profile, fold, per bin
+
+    // the exchanges between ranks, declared last so that they end first: the communicator, then
+    // the peers' arenas, then every buffer above
+    bb::solver::PeerLink peer;      // peer exchange (bb_solver_peer_*)
+    bb::CommLease comm;             // direct RCCL path (bb_solver_comm_init / _attach), else empty
 };
 
 namespace bb {
@@ -188,26 +218,30 @@ int failed_create(int rc, TearDown &&tear_down) {
     return rc;
 }
 
-// The peer arena's layout: 2 parities x world slots of data | per-rank flags | poison words.
-inline int64_t peer_flags_offset(const bb_solver *s) {
-    return 2 * (int64_t)s->world * s->peer_slot_elems * bb::elem_size(s->dtype);
-}
-// the one-launch exchange (reduce_exchange_kernel): one poison word per source rank behind
-// the per-rank flags of the two-launch form (its data words say by themselves whether they
-// have arrived)
-inline int64_t peer_xpoison_offset(const bb_solver *s) {
-    return peer_flags_offset(s) + bb::round_up((int64_t)s->world * 64, 256);
-}
-inline int64_t peer_arena_size(const bb_solver *s) {
-    return peer_xpoison_offset(s) + bb::round_up((int64_t)s->world * 64, 256);
-}
-
 // What the reduce multiplies the summed partials by: 2 for the gradient (SPEC 2.3: the sweep
 // leaves half of it), 1 for a plain sum (the matvec of the spectral start) -- and only a
 // gradient takes the per-bin step factors (fill_reduce_params).
 constexpr double kScaleGradient = 2.0, kScalePlainSum = 1.0;
 
+// Every environment variable the solver reads, as they stand at the time of the call: at
+// bb_solver_create the knobs of the sweep plan (bb_solver_plan.h) and of the 24-bit stream, the
+// row-owner limit and the descriptor form; at bb_solver_peer_connect the peer ones.  THE place
+// the solver reads its environment is solver_env() (bb_solver.hip).
+struct SolverEnv {
+    bb::SweepKnobs knobs;          // BB_WAVES_PER_CU, BB_PAIR, BB_REDUCE_SLICES
+    int pk_mode = -1;              // BB_PACK24: 0 never, 1 whenever a unit packs, unset: the rule
+    int64_t pk_min_run = bb::kPk24MinRun;           // BB_PACK24_MIN_RUN
+    // Largest map (bins) that iterates on the row-owner path.  Measured on MI355X
+    // (tools/small_n_timing.py, profiles/archive/r02_small_n.txt); 0 turns the path off.
+    int64_t row_owner_max = bb::kRowOwnerMaxBins;   // BB_ROW_OWNER_MAX
+    bool arith_desc = true;        // BB_ARITH_DESC=0: the sweep loads a wave's first descriptor
+    bool peer_mask = true;         // BB_PEER_MASK=0: all ranks send all blocks
+    long long peer_timeout_ms = 10000;              // BB_PEER_TIMEOUT_MS
+    int peer_fused = -1;           // BB_PEER_FUSED: 0 two launches, 1 one, unset (-1): by the GPUs
+};
+
 // ---- bb_solver.hip ----
+SolverEnv solver_env();
 int check_ready(const bb_solver *s, const char *who);
 int check_iterate(const bb_solver *s, int64_t iters, const char *who);
 hipError_t upload_padded(const bb_solver *s, double *dst, const double *rows, hipStream_t stream);
@@ -218,10 +252,11 @@ int launch_grad(bb_solver *s, int op = kOpStress, const void *x_in = nullptr);
 int launch_reduce(bb_solver *s, int mode, double lr, double *stress_out, double scale = kScaleGradient);
 int launch_exchange(bb_solver *s, double lr, double *stress_out, double scale = kScaleGradient);
 int launch_apply(bb_solver *s, double lr, double *stress_out);
-int launch_peer_receive(bb_solver *s, void *X, double lr, double mu, double *stress_out);
+int enable_peer_access(const char *who, int device);
 // ---- bb_solver_anchors.hip ----
 int launch_anchors(bb_solver *s, int fold, double *stress_out = nullptr);
-int enable_peer_access(const char *who, int device);
+// ---- bb_solver_exchange.hip ----
+int launch_peer_receive(bb_solver *s, void *X, double lr, double mu, double *stress_out);
 int contributor_mask(const bb_solver *s, std::vector<unsigned> *mask);
 int exchange_sum(bb_solver *s);
 

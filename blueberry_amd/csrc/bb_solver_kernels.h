@@ -1,15 +1,19 @@
 // bb_solver_kernels.h -- device code of the core of the 3D-structure solver (gfx950 only): the
-// stress + gradient sweep, the deterministic partial reduce (+ update / exchange / peer push),
-// the update kernels, the pack kernels of the input routes, the row-owner kernel, the 24-bit
-// stream's pack kernels, the read-only sweeps used for measurement and the f64 <-> T
-// conversions.  Included by bb_solver.hip and by nothing else: everything here lives in that translation unit's
-// anonymous namespace.  Shapes, wave helpers and shared constants: bb_solver_device.h.
+// pair math, the stress + gradient sweep, the deterministic partial reduce (+ update / exchange
+// / peer push, and the one-launch peer exchange over the helpers of bb_peer_kernels.h), the
+// apply kernel, the row-owner kernel, the 24-bit stream's pack kernels and the f64 <-> T
+// conversions.  Included by bb_solver.hip and by nothing else in the library (the tests' probe
+// of the refined fp64 routines includes it too): everything here lives in the including
+// translation unit's anonymous namespace.  The kernels of the input routes:
+// bb_input_kernels.h; of the queries: bb_query_kernels.h.  Shapes, wave helpers, the streaming
+// loads and shared constants: bb_solver_device.h.
 //
 // Specification: docs/SPEC.md (build-authored; the reference has no solver,
 // SURVEY.md section 0).  Data layout and kernel design: DESIGN.md 3-4.
 #pragma once
 
 #include "bb_solver_device.h"
+#include "bb_peer_kernels.h"
 
 namespace {
 
@@ -93,29 +97,6 @@ __device__ __forceinline__ void pair_step(const double2 &drow, double xi, double
     gc[C][0] = fma(-coef, dx, gc[C][0]);
     gc[C][1] = fma(-coef, dy, gc[C][1]);
     gc[C][2] = fma(-coef, dz, gc[C][2]);
-}
-
-// Matrix rows are read exactly once per launch: NT = true marks the loads
-// non-temporal so the stream does not evict X and the partials from L2 / MALL.
-typedef float f32x4_raw __attribute__((ext_vector_type(4)));
-typedef double f64x2_raw __attribute__((ext_vector_type(2)));
-template <bool NT>
-__device__ __forceinline__ float4 stream_load(const float4 *p) {
-    if constexpr (NT) {
-        const f32x4_raw v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_raw *>(p));
-        return make_float4(v.x, v.y, v.z, v.w);
-    } else {
-        return *p;
-    }
-}
-template <bool NT>
-__device__ __forceinline__ double2 stream_load(const double2 *p) {
-    if constexpr (NT) {
-        const f64x2_raw v = __builtin_nontemporal_load(reinterpret_cast<const f64x2_raw *>(p));
-        return make_double2(v.x, v.y);
-    } else {
-        return *p;
-    }
 }
 
 // Where a wave's rolling window is refilled from: the k-th wave-load (1 KiB) of the NEXT
@@ -1020,86 +1001,8 @@ __global__ __launch_bounds__(128 * S) void reduce_sliced_kernel(ReduceParams<T> 
 // Unlike the two-launch form this one can fail PARTIALLY (some 64-element pieces of the
 // step applied, others not): the status is sticky, bb_solver_peer_status reports it, and the
 // coordinates of a failed solver are not a result.
-__device__ __forceinline__ bool peer_word_empty(float v) { return __float_as_uint(v) == 0xffffffffu; }
-__device__ __forceinline__ bool peer_word_empty(double v) { return __double_as_longlong(v) == -1ll; }
-__device__ __forceinline__ float peer_empty_word(float) { return __uint_as_float(0xffffffffu); }
-__device__ __forceinline__ double peer_empty_word(double) { return __longlong_as_double(-1ll); }
-// what is pushed must not look empty: a sum with exactly those bits becomes the canonical NaN
-template <typename T>
-__device__ __forceinline__ T peer_sendable(T v) {
-    return peer_word_empty(v) ? (T)__builtin_nanf("") : v;
-}
-
-// One wave's wait for `n_words` words per lane of every rank: base + r * slot_elems (+ 1 for
-// the second word), r < R.  Returns true with the rank-ordered sum(s) in out0 / out1 and the
-// words emptied; false after a time-out, a poison word or a set status (status set, peers
-// poisoned).  `active` lanes have an element; the others only take part in the votes.
-template <typename T, int NW>
-__device__ __forceinline__ bool peer_wait_sum(const T *base, bool active, int R, int64_t slot_elems,
-                                              const PeerTableX<T> *xt, const unsigned long long *my_poison,
-                                              PeerState *state, long long limit, T &sum, double &pair_sum,
-                                              unsigned mask = ~0u) {
-    const int lane = threadIdx.x & 63;
-    T v[NW][kMaxPeers];
-    bool ok = false;
-    const long long t0 = wall_clock64();
-    for (;;) {
-        bool missing = false;
-#pragma unroll
-        for (int r = 0; r < kMaxPeers; ++r) {
-            if (r < R) {
-                const bool sends = (mask >> r & 1u) != 0;        // (wave-uniform)
-#pragma unroll
-                for (int w = 0; w < NW; ++w) {
-                    v[w][r] = (active && sends)
-                                  ? __hip_atomic_load(base + (int64_t)r * slot_elems + w, __ATOMIC_RELAXED,
-                                                      __HIP_MEMORY_SCOPE_SYSTEM)
-                                  : T(0);
-                    missing |= peer_word_empty(v[w][r]);
-                }
-            }
-        }
-        // lanes [0, R): rank `lane`'s poison word in this arena; lane R: this rank's status
-        unsigned long long f = 0;
-        if (lane < R)
-            f = __hip_atomic_load(my_poison + 8 * lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        else if (lane == R)
-            f = (unsigned long long)__hip_atomic_load(&state->status, __ATOMIC_RELAXED,
-                                                      __HIP_MEMORY_SCOPE_AGENT);
-        if (__ballot(lane < R ? f == kPeerPoison : f != 0) != 0) break;
-        if (__ballot(missing) == 0) { ok = true; break; }
-        if (__ballot(wall_clock64() - t0 > limit) != 0) break;      // wave-uniform exits only
-        __builtin_amdgcn_s_sleep(2);
-    }
-    if (!ok) {
-        if (lane < R)
-            __hip_atomic_store(xt->poison[lane], kPeerPoison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (lane == 0)
-            __hip_atomic_store(&state->status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return false;
-    }
-    // NW = 1: the element's sum over the ranks, in rank order, in T.  NW = 2: the words are a
-    // (hi, lo) pair of one double per rank: their sum in double, rank by rank
-    T s0 = T(0);
-    double s2 = 0.0;
-#pragma unroll
-    for (int r = 0; r < kMaxPeers; ++r) {
-        if (r < R) {
-            s0 += v[0][r];
-            if (NW > 1) s2 += (double)v[0][r] + (double)v[NW - 1][r];
-            if (active && (mask >> r & 1u)) {
-#pragma unroll
-                for (int w = 0; w < NW; ++w)
-                    __hip_atomic_store(const_cast<T *>(base) + (int64_t)r * slot_elems + w,
-                                       peer_empty_word(T(0)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-    }
-    sum = s0;
-    pair_sum = s2;
-    return true;
-}
-
+// (What a slot word says -- peer_word_empty, peer_sendable -- and a wave's bounded wait for the
+// words of every rank, peer_wait_sum: bb_peer_kernels.h.)
 template <typename T, bool W, int S>
 __global__ __launch_bounds__(128 * S) void reduce_exchange_kernel(
     ReduceParams<T> p, const int64_t *__restrict__ lists, int list_stride,
@@ -1163,120 +1066,6 @@ __global__ __launch_bounds__(128 * S) void reduce_exchange_kernel(
     }
 }
 
-// Peer exchange, receiving side -- one launch.  Wave 0 of workgroup 0 waits until every
-// source rank's flag has reached `seq` and publishes the outcome (state->verdict = seq);
-// wave 0 of every other workgroup polls that LOCAL word and the sticky status, so the
-// step is applied by all workgroups or by none.  The wait is bounded: past `limit`
-// ticks of the constant-rate clock -- or when a peer has left its poison flag -- the
-// status word is set, the verdict is withheld, and this rank's own flag on every peer
-// is poisoned so that nobody goes on consuming partials computed from coordinates that
-// no longer move.  Deciding in one place is what keeps X whole: with every workgroup
-// polling the remote flags for itself, some could time out while later ones saw them
-// arrive.  Workgroup 0 is dispatched first, so the deciding wave is resident before any
-// wave that waits for it; it waits for other devices only.
-// Then X <- X + (mu V - lr * sum over ranks, in rank order).  `arena` is this parity's
-// first slot; it is uncached memory, read past L1/L2.
-template <typename T>
-__global__ __launch_bounds__(256) void peer_receive_kernel(
-    T *__restrict__ X, T *__restrict__ V, const T *arena, const unsigned long long *flags,
-    unsigned long long *const *poison_flags, int world, int64_t slot_elems, int64_t n3, T lr, T mu,
-    double *stress_out, unsigned long long seq, PeerState *state, long long limit,
-    const unsigned *__restrict__ peer_mask, int ch) {
-    const int tid = threadIdx.x;
-    __shared__ int go;
-    if (tid < 64) {
-        bool all_ok = false;
-        if (blockIdx.x == 0) {
-            const int lane = tid;
-            if (__hip_atomic_load(&state->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-                // The whole wave polls together until EVERY flag is there: a lane whose
-                // flag has arrived keeps reading it, so a poison that lands later is seen.
-                const long long t0 = wall_clock64();
-                for (;;) {
-                    const unsigned long long f =
-                        lane < world ? __hip_atomic_load(flags + 8 * lane, __ATOMIC_ACQUIRE,
-                                                         __HIP_MEMORY_SCOPE_SYSTEM)
-                                     : seq;
-                    if (__ballot(f == kPeerPoison) != 0) break;
-                    if (__ballot(f >= seq) == __ballot(1)) { all_ok = true; break; }
-                    if (__ballot(wall_clock64() - t0 > limit) != 0) break;   // wave-uniform exits only
-                    __builtin_amdgcn_s_sleep(4);
-                }
-            }
-            if (all_ok) {
-                if (lane == 0)
-                    __hip_atomic_store(&state->verdict, seq, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                if (lane < world)
-                    __hip_atomic_store(poison_flags[lane], kPeerPoison, __ATOMIC_RELEASE,
-                                       __HIP_MEMORY_SCOPE_SYSTEM);
-                if (lane == 0)
-                    __hip_atomic_store(&state->status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            // one word says "this launch's wait is over": what the other workgroups poll
-            if (lane == 0)
-                __hip_atomic_store(&state->decided, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            // ends when workgroup 0 has decided, one way or the other (it always does:
-            // its own wait is bounded)
-            // (relaxed polls of ONE word, well apart, and ONE acquire fence at the end: an
-            // acquire is a cache invalidate on this part -- 200 waves issuing one per poll
-            // cost 12 us -- and a thousand waves hammering one line leave little of its
-            // memory channel to the ranks that share the device in a rehearsal)
-            while (__hip_atomic_load(&state->decided, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != seq)
-                __builtin_amdgcn_s_sleep(32);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            all_ok = __hip_atomic_load(&state->verdict, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == seq;
-        }
-        if (tid == 0) go = all_ok ? 1 : 0;
-    }
-    __syncthreads();
-    if (!go) return;
-    // The arena is read with system-scope loads, which go past L1/L2 to memory: issued
-    // after the barrier they cannot be older than the flags wave 0 acquired.
-    // The grid is capped (kPeerReceiveWGs workgroups, a thread takes several elements): a
-    // grid the size of the update would fill every wave slot of the device with waves that
-    // spin, and when several ranks share one GPU -- the test box, a rehearsal -- the kernel of
-    // the rank they wait for could then not start at all (found by the four-rank test at
-    // N=309,568: 3,629 workgroups waiting, nobody delivering, time-out).
-    constexpr int EPT = 4;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t base = (int64_t)blockIdx.x * 256 + tid; base < n3; base += EPT * stride) {
-        // all slots of all of the thread's elements are requested before the first add; the
-        // sum of an element runs in rank order (rank_ordered_sums)
-        T g[EPT];
-        int64_t el[EPT];
-        bool live[EPT];
-        unsigned mk[EPT];                       // the ranks that sent something for the element's block
-#pragma unroll
-        for (int q = 0; q < EPT; ++q) {
-            el[q] = base + q * stride;
-            live[q] = el[q] < n3;
-            mk[q] = (peer_mask != nullptr && live[q]) ? peer_mask[el[q] / ch] : ~0u;
-        }
-        rank_ordered_sums(g, live, mk, world, [&](int q, int r) {
-            return __hip_atomic_load(arena + r * slot_elems + el[q], __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_SYSTEM);
-        });
-#pragma unroll
-        for (int q = 0; q < EPT; ++q) {
-            const int64_t e = base + q * stride;
-            if (e < n3) momentum_step(X, V, e, mu, lr, g[q]);
-        }
-    }
-    if (blockIdx.x == 0 && tid == 0) {
-        double S = 0.0;
-        for (int r = 0; r < world; ++r)
-            S += (double)__hip_atomic_load(arena + r * slot_elems + n3, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_SYSTEM) +
-                 (double)__hip_atomic_load(arena + r * slot_elems + n3 + 1, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_SYSTEM);
-        *stress_out = S;
-    }
-}
-constexpr unsigned kPeerReceiveWGs = 256;
-
 template <typename T>
 __global__ __launch_bounds__(256) void apply_kernel(T *__restrict__ X, T *__restrict__ V,
                                                     const T *__restrict__ exch, int64_t n3, T lr,
@@ -1284,198 +1073,6 @@ __global__ __launch_bounds__(256) void apply_kernel(T *__restrict__ X, T *__rest
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e < n3) momentum_step(X, V, e, mu, lr, exch[e]);
     if (e == 0 && stress_out) *stress_out = (double)exch[n3] + (double)exch[n3 + 1];
-}
-
-// --------------------------------------------------------------------------
-// packing kernels
-// --------------------------------------------------------------------------
-// What becomes a stored wish distance -- flush_wish and wish_from_value -- is said in ONE
-// place, bb_wish.h; the sweep's 0/1 weight depends on the flush (wish_floor).
-
-// The cell walk of unit `dsc` = {i0, j0} by a workgroup of 256 threads: f(e, i, j, stored) for
-// the cells e = r * VW + c of the thread, (i, j) = (i0 + r, j0 + c) its bin pair, stored =
-// whether the cell holds a pair at all (upper triangle, inside the map).
-template <typename T, bool W, typename F>
-__device__ __forceinline__ void for_each_cell(int2 dsc, int64_t n_bins, F f) {
-    constexpr int VW = Lay<T, W>::VW, RPU = Lay<T, W>::RPU;
-    for (int e = threadIdx.x; e < RPU * VW; e += 256) {
-        const int r = e / VW, c = e % VW;
-        const int64_t i = (int64_t)dsc.x + r, j = (int64_t)dsc.y + c;
-        f(e, i, j, j > i && j < n_bins);
-    }
-}
-
-// staged fp64 rows (row-major, ld = VW) -> units of one run of tiles.
-template <typename T, bool W>
-__global__ __launch_bounds__(256) void convert_units_kernel(
-    const double *__restrict__ stage, T *__restrict__ units_out, const int2 *__restrict__ udesc,
-    int64_t ul0, int64_t stage_row0 /* global row of stage row 0 */, int64_t n_bins, int kind,
-    double neg_inv_alpha) {
-    constexpr int VW = Lay<T, W>::VW, RPU = Lay<T, W>::RPU;
-    const int64_t ul = ul0 + blockIdx.x;
-    const int2 dsc = udesc[ul];
-    T *out = units_out + ul * (RPU * VW);
-    for_each_cell<T, W>(dsc, n_bins, [&](int e, int64_t i, int64_t j, bool stored) {
-        const double v = stored ? stage[(i - stage_row0) * VW + (j - dsc.y)] : 0.0;
-        out[e] = wish_from_value<T>(v, kind, neg_inv_alpha);
-    });
-}
-
-// A (d, d) float64 matrix that is ALREADY in HBM (a device-resident ContactMap,
-// bb_cm_*) -> this rank's units, device to device: the same conversion as
-// convert_units_kernel without the staging copy.  Only elements j > i are read.
-template <typename T, bool W>
-__global__ __launch_bounds__(256) void pack_units_from_matrix_kernel(
-    const double *__restrict__ m, int64_t ld, T *__restrict__ units_out,
-    const int2 *__restrict__ udesc, int64_t n_bins, int kind, double neg_inv_alpha, int64_t off) {
-    // (off > 0: m is the matrix of the bins [off, n_bins) of a solver of several maps; units of
-    // other maps are left alone)
-    constexpr int VW = Lay<T, W>::VW, RPU = Lay<T, W>::RPU;
-    const int64_t ul = blockIdx.x;
-    const int2 dsc = udesc[ul];
-    if (dsc.y < off || dsc.y >= n_bins || dsc.x < off) return;
-    T *out = units_out + ul * (RPU * VW);
-    for_each_cell<T, W>(dsc, n_bins, [&](int e, int64_t i, int64_t j, bool stored) {
-        const double v = stored ? m[(i - off) * ld + (j - off)] : 0.0;
-        out[e] = wish_from_value<T>(v, kind, neg_inv_alpha);
-    });
-}
-
-// Sparse (i, j, value) entries -> resident units (blocked-sparse input).  The
-// units were zeroed ("no constraint") first.  tilemap[I * n_blocks + J] is the
-// tile's index in the global list or -1.
-//
-// A bin pair that occurs more than once keeps its LAST entry, as in the reference's
-// scatter (`matrix[j*d+k] = ...` in file order, blueberry/datatypes.pyx:110-116) and
-// in bb_contactmap_scatter.  Three passes over the entries, nothing the size of the
-// matrix: `phase` 0 clears every cell an entry names, 1 records the highest entry
-// index + 1 per cell (integer atomicMax on the cell's own bits, which the clear left
-// at 0), 2 lets that entry alone store its value.
-// Where the entries come from: (rows, cols, vals) arrays, or -- `tr` set -- the (n, 3) triples
-// [pos_i, pos_j, count] of a Rao-format file as ContactMap.__init__ reads them
-// (blueberry/datatypes.pyx:100-113), resident on the device: numpy.nan_to_num applied to each
-// value as it is read (pyx:102), bin = (int)(pos / resolution) (pyx:111-112), element (t, c)
-// at tr[t * st + c * sc] (row-major rows or the reference's column-major array).
-struct EntrySrc {
-    const int64_t *rows, *cols;
-    const double *vals;
-    const double *tr;
-    int64_t st, sc;
-    double resolution;
-};
-__device__ __forceinline__ double nan_to_num_f64(double v) {
-    return v != v ? 0.0 : (v > 1.7976931348623157e308 ? 1.7976931348623157e308
-                                                      : (v < -1.7976931348623157e308 ? -1.7976931348623157e308 : v));
-}
-// Entry k's bin pair, ordered i < j.  False: an entry to skip -- the diagonal, which carries no
-// pair, or a bad one (a position outside what an int can hold, a bin outside the map), which
-// sets *bad.
-__device__ __forceinline__ bool entry_pair(const EntrySrc &src, int64_t k, int64_t n_bins, int64_t &i,
-                                           int64_t &j, int *__restrict__ bad) {
-    if (src.tr == nullptr) {
-        i = src.rows[k]; j = src.cols[k];
-    } else {
-        const double qi = nan_to_num_f64(src.tr[k * src.st]) / src.resolution,
-                     qj = nan_to_num_f64(src.tr[k * src.st + src.sc]) / src.resolution;
-        if (!(qi > -2147483648.0 && qi < 2147483648.0 && qj > -2147483648.0 && qj < 2147483648.0)) {
-            atomicExch(bad, 1);
-            return false;
-        }
-        i = (int)qi; j = (int)qj;
-    }
-    if (i == j) return false;
-    if (i > j) { const int64_t t = i; i = j; j = t; }
-    if (i < 0 || j >= n_bins) { atomicExch(bad, 1); return false; }
-    return true;
-}
-
-// Which tiles the entries name: present[I * n_blocks + J] = 1 (I <= J), so that the host can
-// write down the tile list of a blocked-sparse solver without binning the entries itself.
-__global__ __launch_bounds__(256) void entries_tiles_kernel(EntrySrc src, int64_t nnz, int64_t vw,
-                                                            int64_t n_blocks, int64_t n_bins,
-                                                            unsigned char *__restrict__ present,
-                                                            int *__restrict__ bad) {
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= nnz) return;
-    int64_t i, j;
-    if (!entry_pair(src, k, n_bins, i, j, bad)) return;
-    present[(i / vw) * n_blocks + j / vw] = 1;
-}
-
-template <typename T, bool W>
-__global__ __launch_bounds__(256) void scatter_entries_kernel(
-    EntrySrc src, int64_t nnz, const int32_t *__restrict__ tilemap,
-    int64_t n_blocks, int64_t n_bins, int64_t u_begin, int64_t u_end, T *__restrict__ units,
-    int kind, double neg_inv_alpha, const double *__restrict__ kr,
-    const double *__restrict__ krexp, int *__restrict__ bad, int phase) {
-    constexpr int VW = Lay<T, W>::VW, RPU = Lay<T, W>::RPU, UPT = VW / RPU;
-    using Bits = typename std::conditional<sizeof(T) == 4, unsigned int, unsigned long long>::type;
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= nnz) return;
-    int64_t i, j;
-    if (!entry_pair(src, k, n_bins, i, j, bad)) return;
-    const int64_t I = i / VW, J = j / VW;
-    const int32_t t = tilemap[I * n_blocks + J];
-    if (t < 0) { atomicExch(bad, 2); return; }   // entry outside the tile list
-    const int64_t ri = i - I * VW;
-    const int64_t u = (int64_t)t * UPT + ri / RPU;
-    if (u < u_begin || u >= u_end) return;  // another rank's unit
-    T *cell = units + (u - u_begin) * (RPU * VW) + (ri % RPU) * VW + (j - J * VW);
-    // Entry k's mark: k + 1 under the sign bit.  Phase 2 stores wish distances into cells that
-    // other threads of phase 2 are still comparing with their marks; a stored distance is 0 or
-    // positive (wish_from_value), so it can equal no mark.  (A bare k + 1 is the bit pattern of
-    // a float: from 228,737,632 entries in one chunk on, that of a distance >= wish_floor.)
-    // k + 1 <= 2^30 (the callers' chunks), and the marks order as the entries do.
-    const Bits mark = ((Bits)1 << (8 * sizeof(Bits) - 1)) | (Bits)(k + 1);
-    if (phase == 0) {
-        *reinterpret_cast<Bits *>(cell) = 0;
-        return;
-    }
-    if (phase == 1) {
-        atomicMax(reinterpret_cast<Bits *>(cell), mark);
-        return;
-    }
-    if (*reinterpret_cast<const Bits *>(cell) != mark) return;   // a later entry won
-    double v = src.tr ? nan_to_num_f64(src.tr[k * src.st + 2 * src.sc]) : src.vals[k];
-    // KR balancing + observed/expected, the element-wise form of the loop at
-    // reference datatypes.pyx:166-169 (same operation order)
-    // (... followed by the reference's nan_to_num over the matrix, pyx:171: a NaN quotient is 0 =
-    // no constraint, an overflowing one the largest double -- as ContactMap.normalize leaves it)
-    if (kr != nullptr) v = nan_to_num_f64(v / (kr[i] * kr[j] * krexp[j - i]));
-    *cell = wish_from_value<T>(v, kind, neg_inv_alpha);
-}
-
-// delta_ij = |x*_i - x*_j| generated in place (synthetic inputs).
-template <typename T, bool W>
-__global__ __launch_bounds__(256) void gen_units_kernel(const double *__restrict__ xs,
-                                                        T *__restrict__ units_out,
-                                                        const int2 *__restrict__ udesc,
-                                                        int64_t n_bins) {
-    constexpr int VW = Lay<T, W>::VW, RPU = Lay<T, W>::RPU;
-    const int64_t ul = blockIdx.x;
-    T *out = units_out + ul * (RPU * VW);
-    for_each_cell<T, W>(udesc[ul], n_bins, [&](int e, int64_t i, int64_t j, bool stored) {
-        double v = 0.0;
-        if (stored) {
-            const double dx = xs[3 * i] - xs[3 * j], dy = xs[3 * i + 1] - xs[3 * j + 1],
-                         dz = xs[3 * i + 2] - xs[3 * j + 2];
-            v = sqrt(dx * dx + dy * dy + dz * dz);
-        }
-        out[e] = flush_wish<T>(v);
-    });
-}
-
-// SPEC 2.11: every stored word w > 0 of this rank's units becomes pow((double)w, p), taken as
-// a kind='wish' input (the one value rule of bb_wish.h: floor, ceiling, rounding to T); zeros
-// stay zeros.  n_words = n_local * (8 KiB / sizeof(T)); a grid-stride loop, one word per thread.
-template <typename T>
-__global__ __launch_bounds__(256) void repower_units_kernel(T *__restrict__ units, int64_t n_words,
-                                                            double p) {
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n_words; e += stride) {
-        const T w = units[e];
-        if (w > T(0)) units[e] = wish_from_value<T>(pow((double)w, p), BB_KIND_WISH, 0.0);
-    }
 }
 
 // --------------------------------------------------------------------------
@@ -1644,164 +1241,6 @@ __global__ __launch_bounds__(256) void row_owner_kernel(
     if (tid == 0) part_out[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
-// resident units -> both triangles of the full matrix (zeroed first; one-off)
-template <typename T, bool W>
-__global__ __launch_bounds__(256) void units_to_full_kernel(const T *__restrict__ units,
-                                                            const int2 *__restrict__ udesc,
-                                                            T *__restrict__ full, int64_t ld,
-                                                            int64_t n_bins) {
-    constexpr int VW = Lay<T, W>::VW, RPU = Lay<T, W>::RPU;
-    const int64_t ul = blockIdx.x;
-    const T *in = units + ul * (RPU * VW);
-    for_each_cell<T, W>(udesc[ul], n_bins, [&](int e, int64_t i, int64_t j, bool stored) {
-        if (stored) {
-            const T v = in[e];
-            full[i * ld + j] = v;
-            full[j * ld + i] = v;
-        }
-    });
-}
-
-// Per bin: how many of this rank's stored pairs constrain it (delta > 0) -- the degrees a step
-// per bin is made from (bb_solver_degrees; once per map, not per iteration).  A workgroup takes
-// kDegUnits consecutive units: a row's count is a ballot per wave (one atomic per wave and
-// row), a column's is kept by the thread that owns the column for as long as the units stay
-// in one tile column (one atomic per column and run of units).
-constexpr int kDegUnits = 32;
-template <typename T, bool W>
-__global__ __launch_bounds__(256) void unit_degrees_kernel(const T *__restrict__ units,
-                                                           const int2 *__restrict__ udesc,
-                                                           int64_t n_local, int64_t n_bins,
-                                                           int *__restrict__ deg) {
-    constexpr int VW = Lay<T, W>::VW, RPU = Lay<T, W>::RPU, CPT = (VW + 255) / 256;
-    const int lane = threadIdx.x & 63;
-    const int64_t u0 = (int64_t)blockIdx.x * kDegUnits;
-    const int64_t u1 = u0 + kDegUnits < n_local ? u0 + kDegUnits : n_local;
-    int col[CPT];
-#pragma unroll
-    for (int k = 0; k < CPT; ++k) col[k] = 0;
-    int j0 = udesc[u0].y;
-    auto flush = [&]() {
-#pragma unroll
-        for (int k = 0; k < CPT; ++k) {
-            const int c = (int)threadIdx.x + 256 * k;
-            if (c < VW && col[k] > 0) atomicAdd(deg + j0 + c, col[k]);
-            col[k] = 0;
-        }
-    };
-    for (int64_t ul = u0; ul < u1; ++ul) {
-        const int2 dsc = udesc[ul];
-        if (dsc.y != j0) {                              // (uniform: every thread reads the same word)
-            flush();
-            j0 = dsc.y;
-        }
-        const T *in = units + ul * (RPU * VW);
-        for (int r = 0; r < RPU; ++r) {
-            const int64_t i = (int64_t)dsc.x + r;
-            int row = 0;
-#pragma unroll
-            for (int k = 0; k < CPT; ++k) {
-                const int c = (int)threadIdx.x + 256 * k;
-                const int64_t j = (int64_t)dsc.y + c;
-                const bool on = c < VW && j > i && j < n_bins && in[r * VW + c] > T(0);
-                col[k] += on ? 1 : 0;
-                row += __popcll(__ballot(on));
-            }
-            if (lane == 0 && row > 0) atomicAdd(deg + i, row);
-        }
-    }
-    flush();
-}
-
-// Per bin: s_i = sum_j w_ij over this rank's stored pairs, w = delta^-Q (SPEC 2.4.1, weighted
-// degrees; once per map).  One wave per bin and no atomics, so the sum has a fixed order:
-// each lane adds its own entries in a fixed sequence and the lanes meet in the fixed DPP tree.
-// Row side: the unit holding row i in every strip J >= block(i), found by binary search in
-// udesc (local units are ordered by (j0, i0)); column side: the units of strip block(i), lane l
-// taking row groups l, l + 64, ... of it.  Which lane adds which pair, and in what order, thus
-// depends on the pair's position alone, not on which tiles the layout holds: a blocked-sparse
-// and a dense layout of one map give the same bits.  fp64 throughout: delta^-Q of an fp32 delta is exact
-// enough to sum in double.
-template <typename T, bool W, int Q>
-__global__ __launch_bounds__(256) void unit_weight_sums_kernel(const T *__restrict__ units,
-                                                               const int2 *__restrict__ udesc,
-                                                               int64_t n_local, int64_t n_bins,
-                                                               double *__restrict__ sums) {
-    constexpr int VW = Lay<T, W>::VW, RPU = Lay<T, W>::RPU;
-    const int lane = threadIdx.x & 63;
-    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= n_bins) return;
-    auto weight = [](T v) -> double {
-        const double d = (double)v;
-        return d > 0.0 ? (Q == 1 ? 1.0 / d : 1.0 / (d * d)) : 0.0;
-    };
-    // first local unit whose (j0, i0) is not below (j0, i0)
-    auto lower = [&](int j0, int i0) -> int64_t {
-        int64_t lo = 0, hi = n_local;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            const int2 d = udesc[mid];
-            if (d.y < j0 || (d.y == j0 && d.x < i0)) lo = mid + 1;
-            else hi = mid;
-        }
-        return lo;
-    };
-    const int b = (int)(i / VW);
-    const int n_blocks = (int)((n_bins + VW - 1) / VW);
-    const int i0 = (int)(i - i % RPU), r = (int)(i % RPU);
-    double acc = 0.0;
-    for (int J = b; J < n_blocks; ++J) {
-        const int64_t ul = lower(J * VW, i0);
-        if (ul >= n_local || udesc[ul].y != J * VW || udesc[ul].x != i0) continue;
-        const T *row = units + ul * (RPU * VW) + (int64_t)r * VW;
-        for (int c = lane; c < VW; c += 64) {
-            const int64_t j = (int64_t)J * VW + c;
-            if (j > i && j < n_bins) acc += weight(row[c]);
-        }
-    }
-    const int c = (int)(i - (int64_t)b * VW);
-    for (int64_t p = lane; p * RPU < i; p += 64) {   // lane: the rows p*RPU.. of strip b
-        const int64_t ul = lower(b * VW, (int)(p * RPU));
-        if (ul >= n_local || udesc[ul].y != b * VW || udesc[ul].x != (int)(p * RPU)) continue;
-        const T *col = units + ul * (RPU * VW) + c;
-        for (int q = 0; q < RPU; ++q)
-            if (p * RPU + q < i) acc += weight(col[q * VW]);
-    }
-    acc = wave_sum_hi(acc);
-    if (lane == 63) sums[i] = acc;
-}
-
-// Measurement only: the same waves read the same units with the same rolling
-// 8-row window, but do nothing with the data except fold it into a checksum --
-// the practical HBM read ceiling for this access pattern on this box.
-template <bool NT>
-__global__ __launch_bounds__(256, 4) void stream_read_kernel(const float4 *__restrict__ units,
-                                                             int chunk_q, int chunk_r,
-                                                             float *__restrict__ sink) {
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-    const int ua = w * chunk_q + (w < chunk_r ? w : chunk_r);
-    const int ub = ua + chunk_q + (w < chunk_r ? 1 : 0);
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ua < ub) {
-        float4 d[8];
-        const float4 *first = units + (int64_t)ua * 512 + lane;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) d[r] = stream_load<NT>(first + r * 64);
-        for (int u = ua; u < ub; ++u) {
-            const int un = u + 1 < ub ? u + 1 : u;
-            const float4 *next = units + (int64_t)un * 512 + lane;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                acc.x += d[r].x; acc.y += d[r].y; acc.z += d[r].z; acc.w += d[r].w;
-                d[r] = stream_load<NT>(next + r * 64);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-    if (acc.x + acc.y + acc.z + acc.w == 12345.678f) sink[w] = acc.x;  // keep the loads alive
-}
-
 // --------------------------------------------------------------------------
 // The 24-bit stream of the fp32 sweep (SPEC 3.7): built from the units once per map
 // --------------------------------------------------------------------------
@@ -1852,81 +1291,6 @@ __global__ __launch_bounds__(256) void pk24_pack_kernel(const uint4 *__restrict_
                                      (w.z - base) | ((((r3.z - base) >> sh) & 0xffu) << 24),
                                      (w.w - base) | ((((r3.w - base) >> sh) & 0xffu) << 24));
     }
-}
-
-// Measurement only, as stream_read_kernel: the same waves read the stream of their units, KiB
-// by KiB with 8 KiB in flight (unit u begins at table[u].z KiB, the stream ends at end_kib).
-template <bool NT>
-__global__ __launch_bounds__(256, 4) void stream_read_pk24_kernel(const float4 *__restrict__ stream,
-                                                                  const int4 *__restrict__ table,
-                                                                  int n_units, int end_kib,
-                                                                  int chunk_q, int chunk_r,
-                                                                  float *__restrict__ sink) {
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-    const int ua = w * chunk_q + (w < chunk_r ? w : chunk_r);
-    const int ub = ua + chunk_q + (w < chunk_r ? 1 : 0);
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ua < ub) {
-        const int ka = table[ua].z & 0x7fffffff;
-        const int kb = ub < n_units ? table[ub].z & 0x7fffffff : end_kib;
-        float4 d[8];
-        const float4 *base = stream + lane;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) d[r] = stream_load<NT>(base + (int64_t)min(ka + r, kb - 1) * 64);
-        for (int k = ka; k < kb; k += 8) {
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                acc.x += d[r].x; acc.y += d[r].y; acc.z += d[r].z; acc.w += d[r].w;
-                d[r] = stream_load<NT>(base + (int64_t)min(k + 8 + r, kb - 1) * 64);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-    if (acc.x + acc.y + acc.z + acc.w == 12345.678f) sink[w] = acc.x;  // keep the loads alive
-}
-
-// --------------------------------------------------------------------------
-// landmark constraints (SPEC 2.5.5), the step quantities only: per bin, lambda * sum of A^-Q
-// over the terms that touch it (bb_solver_anchor_sums; A as in bb_anchor_kernels.h)
-// --------------------------------------------------------------------------
-// Why here and not with the other landmark kernels: lds_tree_fold is inlined after the
-// compiler has looked at all of its callers in the translation unit.  Beside the reduce (n =
-// 512, 1024) the fold of 256 below keeps its generic last step; in a unit whose every caller
-// passes 256 that step is folded to constants, and the kernel is no longer the instructions it
-// was.  It stays with the reduce so that splitting the sources changed no kernel.
-template <typename T, int Q>
-__device__ __forceinline__ double anchor_weight(T v) {
-    const double d = (double)v;
-    if (!(d > 0.0)) return 0.0;
-    return Q == 0 ? 1.0 : (Q == 1 ? 1.0 / d : 1.0 / (d * d));
-}
-// node side: sums[v] = lambda * sum_a w(A[a][v]), a ascending
-template <typename T, int Q>
-__global__ __launch_bounds__(256) void anchor_sums_node_kernel(const T *__restrict__ A, int64_t n_pad,
-                                                               int64_t n_bins, int n_rows, double lam,
-                                                               double *__restrict__ sums) {
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v >= n_bins) return;
-    double acc = 0.0;
-    for (int a = 0; a < n_rows; ++a) acc += anchor_weight<T, Q>(A[(int64_t)a * n_pad + v]);
-    sums[v] = lam * acc;
-}
-// landmark side, one workgroup per landmark, launched behind the node side: thread t adds nodes
-// t, t + 256, ... in order, the threads meet in the fixed tree, sums[s_a] += lambda * the total
-template <typename T, int Q>
-__global__ __launch_bounds__(256) void anchor_sums_landmark_kernel(const T *__restrict__ A, int64_t n_pad,
-                                                                   int64_t n_bins,
-                                                                   const int *__restrict__ nodes, double lam,
-                                                                   double *__restrict__ sums) {
-    __shared__ double sh[256];
-    const int tid = threadIdx.x, a = blockIdx.x;
-    double acc = 0.0;
-    for (int64_t v = tid; v < n_bins; v += 256) acc += anchor_weight<T, Q>(A[(int64_t)a * n_pad + v]);
-    sh[tid] = acc;
-    __syncthreads();
-    lds_tree_fold(sh, tid, 256);
-    if (tid == 0) sums[nodes[a]] += lam * sh[0];
 }
 
 template <typename T>

@@ -183,7 +183,7 @@ extern "C" int bb_solver_spectral_init_tol(bb_solver *s, int n_iter, double tol,
     BB_REQUIRE(n_iter >= 0 && n_iter <= 100000, "bb_solver_spectral_init: bad n_iter");
     BB_REQUIRE(tol >= 0.0 && tol < 1.0, "bb_solver_spectral_init: need 0 <= tol < 1");
     if (!s->have_wish) return bb::fail(BB_ERR_STATE, "bb_solver_spectral_init: no wish distances set");
-    if (s->world != 1 && !s->peer_connected && !s->comm)
+    if (s->world != 1 && !s->peer.connected && !s->comm)
         return bb::fail(BB_ERR_STATE, "bb_solver_spectral_init: with world > 1 the ranks need their "
                                       "exchange first (bb_solver_peer_connect, or bb_solver_comm_init "
                                       "/ _attach); without one the caller sums bb_solver_matvec_sq "

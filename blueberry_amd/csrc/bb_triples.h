@@ -1,5 +1,5 @@
 // bb_triples.h -- what the translation units that read Rao-format triples share: the resident
-// handle (bb_solver.hip owns its lifetime), the two rules every reader applies to a triple's
+// handle (bb_solver_inputs.hip owns its lifetime), the two rules every reader applies to a triple's
 // values -- numpy.nan_to_num and the binning of the ContactMap scatter -- and the canonical index
 // bb_triples_balance.hip builds on the handle (docs/SPEC.md 2.5.3).
 #pragma once

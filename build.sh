@@ -10,7 +10,8 @@ OUT="${BB_OUT:-blueberry_amd/libblueberry_hip.so}"
 # unit into long v_pk_* trees and spills ~500 B/lane in stress_grad_kernel;
 # without it the kernel needs 104 VGPRs and no scratch.
 SRC=""
-for f in bb_api.cpp bb_comm.cpp bb_solver_plan.cpp bb_solver.hip bb_solver_anchors.hip \
+for f in bb_api.cpp bb_comm.cpp bb_solver_plan.cpp bb_solver.hip bb_solver_inputs.hip \
+         bb_solver_exchange.hip bb_solver_queries.hip bb_solver_anchors.hip \
          bb_solver_spectral.hip bb_group.hip bb_score.hip bb_compare.hip bb_band.hip \
          bb_contactmap.hip bb_shortest.hip bb_balance.hip bb_triples_balance.hip bb_triples_paths.hip \
          bb_significance.hip bb_coarsen.hip bb_insulation.hip bb_sort.hip bb_misc.hip; do

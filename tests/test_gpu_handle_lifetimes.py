@@ -198,6 +198,35 @@ def test_peer_export_without_connect_then_close(dtype, n, solver_path):
     nxt.close()
 
 
+@pytest.mark.parametrize("one_launch", [True, False], ids=["one_launch", "two_launches"])
+@pytest.mark.parametrize("dtype,n", SIZES)
+def test_peer_link_connected_to_itself_then_close_twice_over(dtype, n, one_launch, monkeypatch):
+    """The one-rank rehearsal carried through: export, connect to its own arena (tables, mask,
+    state and counter are made), three bb_solver_iterate_peer steps in the given form, close --
+    the peer link ends with the handle -- and a second solver on the device does the same.  One
+    rank's exchange adds nothing, so both give the bits of three bb_solver_iterate steps of the
+    unit sweep (the path the peer exchange steps from) from the same start."""
+    monkeypatch.setenv("BB_ROW_OWNER_MAX", "0")
+    _, x0, lr = _problem(n)
+    want = _plain(dtype, n, "units", 3)
+    for _ in range(2):
+        e = _engine(dtype, n)
+        buf = ctypes.create_string_buffer(_lib.BB_PEER_HANDLE_BYTES)
+        _lib.check(e._lib.bb_solver_peer_export(e._h, buf), "bb_solver_peer_export")
+        _lib.check(e._lib.bb_solver_peer_connect(e._h, buf.raw), "bb_solver_peer_connect")
+        e.peer_set_form(one_launch)
+        assert e.peer_form() == ("one launch" if one_launch else "two launches")
+        e.set_coords(x0)
+        e.iterate_peer(3, lr)
+        assert e.peer_status() == 0
+        got = e.get_coords(), e.stress_history()
+        e.close()
+        assert numpy.array_equal(got[0], want[0])
+        # (the stress travels through the arena as a (hi, lo) pair of the solver's type: 48 bits
+        # of it in fp32, so the history agrees to 2^-48 and is not compared bit for bit)
+        assert got[1].shape == (3,) and numpy.abs(got[1] - want[1]).max() <= 2.0 ** -40 * want[1].max()
+
+
 # ---- 5. timing events and the two measurements on one handle -----------------------------------
 @pytest.mark.parametrize("dtype,n", SIZES)
 def test_timing_and_measurements_change_no_bit(dtype, n, solver_path):
